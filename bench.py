@@ -12,7 +12,12 @@ collective is one RCCL broadcast of the packed weights before the timed region).
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (largest share of device
 time), measured with HIP events recorded around every launch on the launch stream during the
-timed steps; `cpu_baseline` times the CPU oracle on a bounded sample (rank 0, N=1 only).
+timed steps.  A plain run does only that: set up, warm up, time the K steps, print the line.
+--full adds the side measurements after the timed region (never part of `value`): the warp
+kernel alone, board power, the other arithmetic modes, BASELINE configs[1], the streaming
+harness (N > 1: per rank), the pack against the offset spread and `cpu_baseline`, the CPU
+oracle on a bounded sample with the accuracy of every mode against it (rank 0, N=1 only).
+--dump-outputs DIR writes rank 0's frames of the last timed step (see dump_outputs).
 """
 import argparse
 import ctypes
@@ -42,9 +47,14 @@ def parse_args():
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"],
                     help="bf16 = BASELINE configs[2]; fp16 = the autocast arithmetic of the reference; fp32 = parity mode")
-    ap.add_argument("--cpu-reps", type=int, default=3, help="timed CPU-oracle forwards of one full frame (0 = skip the CPU baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run the side measurements (warp / power / fp16 / amp16 / fp32x3 / fp32 / 256x256 / stream / "
+                         "spread / CPU oracle); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frames the last timed step computed (rank 0) to DIR/<name>.npy, float32, at most 64 MB")
+    ap.add_argument("--cpu-reps", type=int, default=3, help="--full: timed CPU-oracle forwards of one full frame (0 = skip the CPU baseline)")
     ap.add_argument("--cpu-rows", type=int, default=None, help="deprecated: 0 = skip the CPU baseline")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side measurements (fp32 / fp16 / 256x256 / warp / CPU)")
+    ap.add_argument("--no-extras", action="store_true", help="skip the side measurements even with --full (a plain run has none)")
     ap.add_argument("--no-events", action="store_true", help="time the plain entry point (no per-launch events)")
     ap.add_argument("--rehearse", action="store_true",
                     help="no GPU: exercise launch, rendezvous, the weight-blob broadcast, barrier / MAX timing and the JSON relay with a "
@@ -660,6 +670,30 @@ def profiled_mode(hip, sd, dev, dtype, B, H, W, steps):
     return res
 
 
+DUMP_LIMIT_BYTES = 60 << 20    # 62.9 MB of values: the .npy headers stay within 64 MB
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array a caller of the timed path receives, as out_dir/<name>.npy in float32, so that two builds can be
+    compared value for value (same arguments = same inputs).  An array that fits in `limit` is written whole, in its shape; a larger one
+    (the default B = 8 x 720p frame is 88 MB) as `<name>_sample.npy`: the flat float32 values at the positions
+    sorted(numpy.random.default_rng(0).choice(numel, limit // 4, replace=False)), fixed by the array's size alone.  Returns {file: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        k = max(0, limit) // a.itemsize
+        if a.size > k:
+            pos = np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))
+            a, name = np.ascontiguousarray(a.reshape(-1)[pos]), f"{name}_sample"
+        path = os.path.join(out_dir, f"{name}.npy")
+        np.save(path, a)
+        written[os.path.basename(path)] = list(a.shape)
+        limit -= a.nbytes
+    return written
+
+
 def rehearse(args, rank, world):
     """--rehearse: the N > 1 plumbing without a GPU (CPU test, gloo): rendezvous, broadcast of a blob-sized buffer from rank 0,
     barrier + MAX-over-ranks timing around K stand-in steps, the rank census, ONE JSON line on rank 0.  `value` is null."""
@@ -767,11 +801,14 @@ def main():
     bad = sorted(int(r[0]) for r in census if r[3] != 1.0)
     if bad:
         raise SystemExit(f"bench.py: non-finite output frame on rank(s) {bad} (a foreign / corrupted packed blob yields an all-NaN frame)")
+    if rank == 0 and args.dump_outputs:
+        progress(f"outputs of the last timed step: {dump_outputs({'interpolated': out}, args.dump_outputs)} in {args.dump_outputs}")
 
     # N > 1: the PCIe-inclusive leg per rank (at N = 1 the extras below carry also_stream_pcie); gathered INSIDE a collective like the
     # rank census, so that no rank-local failure leaves the others blocked
     stream_rows = None
-    if world > 1 and not args.no_extras and args.dtype == "bf16":
+    extras = args.full and not args.no_extras
+    if world > 1 and extras and args.dtype == "bf16":
         fence()
         try:
             pairs, n_out, secs = stream_leg_one_rank(model, rank, world, B, H, W)
@@ -830,7 +867,7 @@ def main():
                 res["roofline_warp_in_forward"] = warp
         if stream_rows is not None:
             res["also_stream_pcie_per_rank"] = stream_leg_summary(stream_rows, value)
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             def timed_alt(dtype, b, h, w, steps):
                 alt = EMA_VFI(compute_dtype=dtype).to(dev).eval()
                 alt.load_state_dict(sd, strict=True)

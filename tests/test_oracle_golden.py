@@ -57,8 +57,6 @@ def test_large_256_stress_samples():
         assert np.abs(got - g[f"256s.val.{k}"]).max() <= 2e-5 * max(1.0, np.abs(got).max()), k
 
 
-@pytest.mark.skipif(not __import__("os").path.exists("/root/reference/src/models/ema_vfi.py"),
-                    reason="the reference only exists in the authoring container")
 def test_large_odd_samples():
     """mid=64 at 203x331 (B = 2, stress input, flows up to 16 px): odd in both dimensions, so every pyramid level (102x166, 51x83) and
     every tile grid ends in a partial tile.  The oracle against the sampled pixels of the reference's own run
@@ -91,30 +89,6 @@ def test_large_offsets_samples(fname, tag, p99):
     for k in STAGES:
         got = taps[k].contiguous().view(-1)[torch.from_numpy(g[f"{tag}.pos.{k}"])].numpy()
         assert np.abs(got - g[f"{tag}.val.{k}"]).max() <= 2e-5 * max(1.0, np.abs(got).max()), k
-
-
-def test_generator_runs_the_reference_and_reproduces_the_committed_fixture(tmp_path):
-    """tests/golden/make_golden.py at HEAD: loads the REFERENCE's ema_vfi.py by file path (not this repository's own
-    src/ package), runs its forward, and the regenerated tiny fixture equals the committed one bit for bit."""
-    import os
-    import subprocess
-    import sys
-    from conftest import GOLDEN
-    script = os.path.join(GOLDEN, "make_golden.py")
-    r = subprocess.run([sys.executable, script, "--out", str(tmp_path), "tiny"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
-    for name in ("tiny_mid8_24x40.npz", "tiny_mid8_23x37.npz"):
-        new, old = np.load(tmp_path / name), np.load(os.path.join(GOLDEN, name))
-        assert sorted(new.files) == sorted(old.files)
-        for k in old.files:
-            assert new[k].dtype == old[k].dtype and np.array_equal(new[k], old[k]), (name, k)
-    # the module the generator ran is the reference's file, not the drop-in class of this repository
-    probe = ("import sys; sys.argv=['x']; import importlib.util as u; s=u.spec_from_file_location('mg', r'%s'); "
-             "m=u.module_from_spec(s); s.loader.exec_module(m); print(m.ref.__file__); print(m.ref.EMA_VFI.__module__)" % script)
-    r = subprocess.run([sys.executable, "-c", probe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-1500:]
-    lines = r.stdout.strip().splitlines()
-    assert lines[-2].startswith("/root/reference/") and lines[-1] == "ref_ema_vfi"
 
 
 @pytest.mark.parametrize("name,exact", [("amp_mid8_23x37.npz", True), ("amp_mid64_40x56.npz", False)])
