@@ -190,6 +190,28 @@ int emavfi_forward_profiled(int in_channels, int mid_channels, int num_blocks, c
                             void *workspace, size_t workspace_bytes,
                             int B, int H, int W, int dtype, void *const *events, int n_events, void *stream);
 
+/* Per-block route of the 16-bit attention blocks.  The one-launch pack exists as two kernels with the same operands,
+ * weights (the blob and emavfi_layout_tag() do not change) and output:
+ *   EMAVFI_ROUTE_WINDOW  deform_pack3_kernel: stages a 23 x 23 window (+-2 px beyond every tap); samples that leave it take a fix-up pass,
+ *                        so its cost grows with the offsets (the census below counts them).  What every entry without a route runs.
+ *   EMAVFI_ROUTE_GATHER  deform_gather3_kernel: stages only offset_conv's 18 x 18 tile, gathers every corner from global memory; its cost
+ *                        does not depend on the offsets.  Bit-identical to the window route wherever that one's census shows no fix-up group.
+ * The gather route exists exactly where the one-launch pack runs (EMAVFI_BF16 / EMAVFI_F16 at mid_channels + 3 = 65..67); fp32,
+ * EMAVFI_AMP16, EMAVFI_F32X3 and other widths refuse it with EMAVFI_E_UNSUPPORTED.  Workspace sizes are the same for both routes.
+ * emavfi_forward_routed: the union of emavfi_forward / _staged / _profiled (`taps`, `stage_events`, `events` may each be NULL) plus
+ * `gather_blocks`: bit i routes attention block i to EMAVFI_ROUTE_GATHER; bits at or above num_blocks are EMAVFI_E_ARG.  Mask 0 is
+ * emavfi_forward exactly (same launches, same results).  emavfi_forward_launches_routed lists the launches of such a forward: a
+ * gathered block's launch is named "deform_gather<...> offset_conv+dcn_v2", a windowed one "deform<...> offset_conv+dcn_v2". */
+#define EMAVFI_ROUTE_WINDOW 0
+#define EMAVFI_ROUTE_GATHER 1
+int emavfi_forward_routed(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes,
+                          const float *frame1, const float *frame2, float *out,
+                          void *workspace, size_t workspace_bytes,
+                          int B, int H, int W, int dtype, float *const *taps, void *const *stage_events, void *const *events, int n_events,
+                          unsigned gather_blocks, void *stream);
+int emavfi_forward_launches_routed(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, unsigned gather_blocks,
+                                   char *names, size_t names_bytes, double *flops, double *bytes, int capacity);
+
 /* EMA_VFI.warp(frame2, feature, flow), ema_vfi.py:149-171 (grid build + normalise +
  * F.grid_sample bilinear/zeros/align_corners=True), fused into one HBM-bound kernel.
  * frame2 [B,C,H,W], flow [B,2,H,W] (channel 0 = dx, 1 = dy, pixels), out [B,C,H,W]; fp32. */
@@ -251,11 +273,18 @@ int emavfi_mdcn(const float *x, const float *offset_weight, const float *offset_
 int emavfi_mdcn_profiled(const float *x, const float *offset_weight, const float *offset_bias, const float *dcn_weight, const float *dcn_bias,
                          float *y, int B, int C, int H, int W, int dtype, int flags, void *workspace, size_t workspace_bytes,
                          void *const *events, int n_events, void *stream);
+/* emavfi_mdcn / emavfi_mdcn_profiled with a route (EMAVFI_ROUTE_WINDOW | EMAVFI_ROUTE_GATHER, see emavfi_forward_routed); `events` may be
+ * NULL.  All flag combinations of the one-launch pack are valid on both routes; emavfi_mdcn_census reads either route's counters. */
+int emavfi_mdcn_routed(const float *x, const float *offset_weight, const float *offset_bias, const float *dcn_weight, const float *dcn_bias,
+                       float *y, int B, int C, int H, int W, int dtype, int flags, int route, void *workspace, size_t workspace_bytes,
+                       void *const *events, int n_events, void *stream);
 
 /* Census of the one-launch ModulatedDeformConvPack kernel (measurement hook; the reference bounds its offsets nowhere, ema_vfi.py:55-60,
  * and the kernel stages a window that holds offsets up to +-2 px beyond the tap: samples that leave it take a fix-up pass).  The kernel
  * counts, while it runs: the (wave, tap) groups - 4 rows x 16 pixels x one tap - that took the fix-up, the samples outside the window and
- * the largest |offset| of the waves that had one (only those pay for the census: 0 = every sample was inside the window).  emavfi_forward_census reads the counters the LAST emavfi_forward* call on `workspace` left there
+ * the largest |offset| of the waves that had one (only those pay for the census: 0 = every sample was inside the window).  The gather route
+ * (EMAVFI_ROUTE_GATHER) writes the same record with the same meaning - what WOULD have left the window - so both routes report identical
+ * counts on the same input and a caller can route by it in either direction.  emavfi_forward_census reads the counters the LAST emavfi_forward* call on `workspace` left there
  * (same model, B, H, W, dtype; enqueue it on the same stream), emavfi_mdcn_census those of the last emavfi_mdcn* call:
  *   out[block][4] (unsigned 64-bit, DEVICE memory, num_blocks rows - one row for mdcn) =
  *     {fix-up wave-taps, all wave-taps (0: this block did not run the one-launch kernel, nothing was counted), samples outside the

@@ -341,6 +341,10 @@ int launch_conv3x3_f16(const ConvParams &p, hipStream_t s);
 int launch_deform_f32(const DeformParams &p, hipStream_t s);
 int launch_deform_bf16(const DeformParams &p, hipStream_t s);
 int launch_deform_f16(const DeformParams &p, hipStream_t s);
+// the window-free route of the same one-launch pack (deform_gather3.inl): same DeformParams / weights / input forms as
+// deform_pack3_kernel<T, true>, -2 for anything else
+int launch_deform_gather_bf16(const DeformParams &p, hipStream_t s);
+int launch_deform_gather_f16(const DeformParams &p, hipStream_t s);
 // 16-bit dtypes at the reference width: the whole ModulatedDeformConvPack is one launch (deform_pack3.inl / deform_pack.inl)
 #ifndef EMAVFI_PACK3
 #define EMAVFI_PACK3 1   // 0: the round-2 kernel (deform_pack.inl) and its weight layout (A/B builds)

@@ -1,2 +1,4 @@
 #include "deform_pack3.inl"
+#include "deform_gather3.inl"
 int launch_deform_f16(const DeformParams &p, hipStream_t s) { return launch_deform16<half_t>(p, s); }
+int launch_deform_gather_f16(const DeformParams &p, hipStream_t s) { return launch_deform_gather3<half_t>(p, s); }

@@ -440,7 +440,7 @@ unsigned long long *debug_stamp_buffer()
 int run_deform(const Plan &P, const Layer &L, const void *packed, const void *x, int x_ps, float *om, void *out,
                int out_ps, int cstore, int B, int H, int W, hipStream_t s, const void *zeros = nullptr, const Layer *off = nullptr,
                const void *x_tail = nullptr, int tail_ps = 0, int force_dtype = -1, int in_f16 = 0, int out_f16 = 0, void *out16 = nullptr, int out16_ps = 0,
-               unsigned *census = nullptr, int out16_lo_off = 0)
+               unsigned *census = nullptr, int out16_lo_off = 0, bool gather = false)
 {
     const int kd = force_dtype >= 0 ? force_dtype : P.dtype;
     DeformParams d{};
@@ -475,6 +475,8 @@ int run_deform(const Plan &P, const Layer &L, const void *packed, const void *x,
         for (int i = 1; i < atoi(rep); ++i)
             if (const int rc = kd == EMAVFI_F32 ? launch_deform_f32(d, s) : kd == EMAVFI_F16 ? launch_deform_f16(d, s) : launch_deform_bf16(d, s)) return rc;
 #endif
+    // the window-free route of the one-launch pack (deform_gather3.inl): 16-bit kinds only, -2 (no instantiation) for anything else
+    if (gather) return kd == EMAVFI_F16 ? launch_deform_gather_f16(d, s) : kd == EMAVFI_BF16 ? launch_deform_gather_bf16(d, s) : -2;
     return kd == EMAVFI_F32 ? launch_deform_f32(d, s) : kd == EMAVFI_F16 ? launch_deform_f16(d, s) : launch_deform_bf16(d, s);
 }
 
@@ -624,14 +626,29 @@ bool pack_f16_link(const Plan &P, int i)
     return P.dtype == EMAVFI_BF16 && pack_f16_chain() && i >= 0 && i + 1 < P.nb && P.dcn[i].pack3 && P.dcn[i + 1].pack3 && pack_fuses(P, i) &&
            pack_fuses(P, i + 1);
 }
+// Whether block i may take the window-free route (deform_gather3.inl): exactly where the one-launch pack runs in the deform_pack3 layout
+// (16-bit modes at the reference width); fp32, EMAVFI_AMP16, EMAVFI_F32X3 and other widths keep their kernels
+bool pack_gather_ok(const Plan &P, int i) { return pack_fuses(P, i) && P.dcn[i].pack3 == 1; }
 // 16-bit / fp32 models: x -> y (channels-last, pixel stride P.fps).  x_tail: the compact tail buffer (kTailPs channels per pixel) the first pack takes channels
-// 64.. from (or null); in_f16 / out_f16: the bf16 model's f16 hand-off (DeformParams)
+// 64.. from (or null); in_f16 / out_f16: the bf16 model's f16 hand-off (DeformParams).  route: EMAVFI_ROUTE_WINDOW (deform_pack3_kernel) or
+// EMAVFI_ROUTE_GATHER (deform_gather3_kernel: same operands, same output, no window - refused where pack_gather_ok does not hold)
 int attention_block(const Plan &P, int i, const void *packed, const void *x, void *y, float *om, const void *x_tail, int in_f16, int out_f16,
-                    int B, int H, int W, hipStream_t s, Recorder &rec, unsigned *census = nullptr)
+                    int B, int H, int W, hipStream_t s, Recorder &rec, unsigned *census = nullptr, int route = EMAVFI_ROUTE_WINDOW)
 {
     const double px = (double)B * H * W, e = P.esize, cf = P.mid + 3;
     double fl, by;
     conv_work(P, P.off[i], B, H, W, 4.0, fl, by);
+    if (route == EMAVFI_ROUTE_GATHER) {
+        if (!pack_gather_ok(P, i)) return fail(EMAVFI_E_UNSUPPORTED, "attention block %d: the gather route exists only where the one-launch pack runs (16-bit modes at the reference width)", i);
+        char nm[96];
+        snprintf(nm, sizeof nm, "deform_gather<%s,ck=%d,nf=%d> offset_conv+dcn_v2", dtype_name(P.dtype), P.dcn[i].ck, P.dcn[i].nf);
+        // corner pieces from global memory: 9 taps x 4 corners x one 144-byte pixel per output pixel (L1 / L2 traffic, not HBM)
+        EMAVFI_STEP(rec, nm, fl + 2.0 * 9.0 * cf * cf * px, px * (2.0 * cf * e) + 9.0 * cf * (cf + 27.0) * e,
+                    run_deform(P, P.dcn[i], packed, x, P.fps, om, y, P.fps, P.fps, B, H, W, s, nullptr, P.has_offh ? &P.offh[i] : &P.off[i], x_tail, kTailPs,
+                               -1, in_f16, out_f16, nullptr, 0, census, 0, true));
+        return EMAVFI_OK;
+    }
+    if (route != EMAVFI_ROUTE_WINDOW) return fail(EMAVFI_E_ARG, "attention block %d: unknown route %d", i, route);
     if (pack_fuses(P, i)) {
         // one launch for the whole pack (ema_vfi.py:54-60): offset_conv on the staged window, then the DCN;
         // the input is read once and the offsets / masks never leave the registers
@@ -751,10 +768,16 @@ BlobHeader expected_header(const Plan &P, int requested_dtype)
 
 int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes, const float *frame1,
                  const float *frame2, float *out, void *workspace, size_t workspace_bytes, int B, int H, int W, int dtype,
-                 float *const *taps, void *stream, Recorder &rec)
+                 float *const *taps, void *stream, Recorder &rec, unsigned gather_blocks = 0)
 {
     Plan P;
     if (!build_plan(P, in_channels, mid_channels, num_blocks, dtype)) return fail(EMAVFI_E_UNSUPPORTED, "%s", P.why);
+    // per-block route (emavfi_forward_routed): bit i sends attention block i to the window-free kernel
+    if (P.nb < 32 && (gather_blocks >> P.nb) != 0u)
+        return fail(EMAVFI_E_ARG, "forward: gather_blocks 0x%x names blocks at or above num_blocks = %d", gather_blocks, P.nb);
+    for (int i = 0; i < P.nb; ++i)
+        if (((gather_blocks >> i) & 1u) && (P.amp || !pack_gather_ok(P, i)))
+            return fail(EMAVFI_E_UNSUPPORTED, "forward: attention block %d has no gather route in this mode (the one-launch pack of the 16-bit modes at the reference width only)", i);
     const int requested_dtype = dtype;
     dtype = P.dtype;  // the kernel storage type from here on (EMAVFI_AMP16 -> EMAVFI_F16, with P.amp set)
     if (B < 1 || H < 1 || W < 1) return fail(EMAVFI_E_ARG, "forward: B, H, W must be >= 1 (got %d, %d, %d)", B, H, W);
@@ -938,7 +961,8 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
         for (int i = 0; i < P.nb; ++i) {
             if (const int rc = attention_block(P, i, packed, x, y, f.om, i == 0 && split_tail ? f.in16 : nullptr,
                                                (i == 0 ? feat16 : pack_f16_link(P, i - 1)) ? 1 : 0, pack_f16_link(P, i) ? 1 : 0, B, H, W, s, rec,
-                                               rec.dry ? nullptr : f.census + (size_t)i * DEFORM_CENSUS_SLOTS * 4);
+                                               rec.dry ? nullptr : f.census + (size_t)i * DEFORM_CENSUS_SLOTS * 4,
+                                               ((gather_blocks >> i) & 1u) ? EMAVFI_ROUTE_GATHER : EMAVFI_ROUTE_WINDOW);
                 rc != EMAVFI_OK)
                 return rc;
             if (!rec.dry && taps && taps[5 + i])
@@ -1138,14 +1162,34 @@ int emavfi_forward_staged(int in_channels, int mid_channels, int num_blocks, con
                         dtype, nullptr, stream, rec);
 }
 
+int emavfi_forward_routed(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes, const float *frame1,
+                          const float *frame2, float *out, void *workspace, size_t workspace_bytes, int B, int H, int W, int dtype,
+                          float *const *taps, void *const *stage_events, void *const *events, int n_events, unsigned gather_blocks, void *stream)
+{
+    Recorder rec;
+    rec.stage_events = stage_events;
+    if (events) {
+        if (n_events < 2) return fail(EMAVFI_E_ARG, "forward_routed: events given, n_events must be >= 2");
+        rec.events = events; rec.n_events = n_events;
+    }
+    return forward_impl(in_channels, mid_channels, num_blocks, packed, packed_bytes, frame1, frame2, out, workspace, workspace_bytes, B, H, W,
+                        dtype, taps, stream, rec, gather_blocks);
+}
+
 int emavfi_forward_launches(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype,
                             char *names, size_t names_bytes, double *flops, double *bytes, int capacity)
+{
+    return emavfi_forward_launches_routed(in_channels, mid_channels, num_blocks, B, H, W, dtype, 0u, names, names_bytes, flops, bytes, capacity);
+}
+
+int emavfi_forward_launches_routed(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, unsigned gather_blocks,
+                                   char *names, size_t names_bytes, double *flops, double *bytes, int capacity)
 {
     std::vector<LaunchRec> recs;
     Recorder rec;
     rec.recs = &recs; rec.dry = true;
     const int rc = forward_impl(in_channels, mid_channels, num_blocks, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, B, H, W,
-                                dtype, nullptr, nullptr, rec);
+                                dtype, nullptr, nullptr, rec, gather_blocks);
     if (rc != EMAVFI_OK) return rc;
     const int n = (int)recs.size();
     if (capacity <= 0) return n;
@@ -1380,11 +1424,15 @@ size_t emavfi_mdcn_workspace_bytes(int B, int C, int H, int W, int dtype, int fl
 }
 
 static int mdcn_impl(const float *x, const float *offset_weight, const float *offset_bias, const float *dcn_weight, const float *dcn_bias, float *y,
-                     int B, int C, int H, int W, int dtype, int flags, void *workspace, size_t workspace_bytes, void *stream, Recorder &rec)
+                     int B, int C, int H, int W, int dtype, int flags, void *workspace, size_t workspace_bytes, void *stream, Recorder &rec,
+                     int route = EMAVFI_ROUTE_WINDOW)
 {
     Plan P;
     bool split; int in_f16, out_f16;
     if (const int rc = mdcn_plan(P, C, dtype, flags, split, in_f16, out_f16); rc != EMAVFI_OK) return rc;
+    if (route != EMAVFI_ROUTE_WINDOW && route != EMAVFI_ROUTE_GATHER) return fail(EMAVFI_E_ARG, "mdcn: unknown route %d", route);
+    if (route == EMAVFI_ROUTE_GATHER && (P.amp || !pack_gather_ok(P, 0)))
+        return fail(EMAVFI_E_UNSUPPORTED, "mdcn: the gather route exists only where the one-launch pack runs (16-bit modes, C = 65..67)");
     if (!x || !offset_weight || !offset_bias || !dcn_weight || !y || !workspace) return fail(EMAVFI_E_ARG, "mdcn: null pointer");
     if (B < 1 || H < 1 || W < 1) return fail(EMAVFI_E_ARG, "mdcn: B, H, W must be >= 1");
     if (!aligned16(x) || !aligned16(y) || !aligned16(workspace)) return fail(EMAVFI_E_ARG, "mdcn: pointers must be 16-byte aligned");
@@ -1420,7 +1468,7 @@ static int mdcn_impl(const float *x, const float *offset_weight, const float *of
     } else {
         EMAVFI_TRY(launch_nchw_to_cl(x, m.xcl, B, C, H, W, P.fps, xdt, s), "mdcn layout in");
     }
-    if (const int rc = attention_block(P, 0, m.blob, m.xcl, m.ycl, m.om, m.tail, in_f16, out_f16, B, H, W, s, rec, m.census); rc != EMAVFI_OK) return rc;
+    if (const int rc = attention_block(P, 0, m.blob, m.xcl, m.ycl, m.om, m.tail, in_f16, out_f16, B, H, W, s, rec, m.census, route); rc != EMAVFI_OK) return rc;
     EMAVFI_TRY(launch_cl_to_nchw(m.ycl, y, B, C, H, W, P.fps, 0, ydt, s), "mdcn layout out");
     return EMAVFI_OK;
 }
@@ -1440,6 +1488,18 @@ int emavfi_mdcn_profiled(const float *x, const float *offset_weight, const float
     Recorder rec;
     rec.events = events; rec.n_events = n_events;
     return mdcn_impl(x, offset_weight, offset_bias, dcn_weight, dcn_bias, y, B, C, H, W, dtype, flags, workspace, workspace_bytes, stream, rec);
+}
+
+int emavfi_mdcn_routed(const float *x, const float *offset_weight, const float *offset_bias, const float *dcn_weight, const float *dcn_bias, float *y,
+                       int B, int C, int H, int W, int dtype, int flags, int route, void *workspace, size_t workspace_bytes, void *const *events,
+                       int n_events, void *stream)
+{
+    Recorder rec;
+    if (events) {
+        if (n_events < 2) return fail(EMAVFI_E_ARG, "mdcn_routed: events given, n_events must be >= 2");
+        rec.events = events; rec.n_events = n_events;
+    }
+    return mdcn_impl(x, offset_weight, offset_bias, dcn_weight, dcn_bias, y, B, C, H, W, dtype, flags, workspace, workspace_bytes, stream, rec, route);
 }
 
 // ---- census of the one-launch packs (round 6): what deform_pack3_kernel itself counted while it ran - the (wave, tap)

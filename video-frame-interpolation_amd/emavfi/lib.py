@@ -53,6 +53,10 @@ _PROTOTYPES = {
     "emavfi_mdcn_profiled": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p, c_size_t, POINTER(c_void_p), c_int, c_void_p]),
     "emavfi_forward_census": (c_int, [c_int] * 7 + [c_void_p, c_size_t, c_void_p, c_void_p]),
     "emavfi_mdcn_census": (c_int, [c_int] * 6 + [c_void_p, c_size_t, c_void_p, c_void_p]),
+    "emavfi_forward_routed": (c_int, [c_int] * 3 + [c_void_p, c_size_t] + [c_void_p] * 4 + [c_size_t] + [c_int] * 4
+                              + [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int, ctypes.c_uint, c_void_p]),
+    "emavfi_forward_launches_routed": (c_int, [c_int] * 7 + [ctypes.c_uint, c_char_p, c_size_t, POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int]),
+    "emavfi_mdcn_routed": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p, c_size_t, POINTER(c_void_p), c_int, c_void_p]),
     "emavfi_context_workspace_bytes": (c_size_t, [c_int] * 5),
     "emavfi_context": (c_int, [c_void_p, POINTER(c_void_p), c_void_p] + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
     "emavfi_reconstruct_workspace_bytes": (c_size_t, [c_int] * 5),
@@ -337,10 +341,17 @@ def deform_conv2d(x, offset, mask, weight, bias, dtype="fp32"):
     return y
 
 
-def mdcn(x, offset_weight, offset_bias, dcn_weight, dcn_bias, dtype="fp32", flags=0, _events=None):
+ROUTES = {"window": 0, "gather": 1}   # include/emavfi.h: EMAVFI_ROUTE_WINDOW / EMAVFI_ROUTE_GATHER
+
+
+def mdcn(x, offset_weight, offset_bias, dcn_weight, dcn_bias, dtype="fp32", flags=0, _events=None, route="window"):
     """ModulatedDeformConvPack.forward (reference ema_vfi.py:53-60) as ONE stage, routed as a block of the forward is
     (include/emavfi.h, emavfi_mdcn): the one-launch kernel in the 16-bit modes at the reference width.
-    `_events` (bench.py): (ctypes array of hipEvent_t, count) bracketing the stage's own launches (emavfi_mdcn_profiled)."""
+    `_events` (bench.py): (ctypes array of hipEvent_t, count) bracketing the stage's own launches (emavfi_mdcn_profiled).
+    `route`: "window" (deform_pack3_kernel, the default) or "gather" (the window-free kernel, emavfi_mdcn_routed; 16-bit modes at
+    C = 65..67 only - elsewhere the C error is raised)."""
+    if route not in ROUTES:
+        raise ValueError(f"mdcn: route must be one of {sorted(ROUTES)}, got {route!r}")
     import torch
     _require_cuda(x, offset_weight, offset_bias, dcn_weight, dcn_bias)
     dt = dtype_code(dtype)
@@ -356,7 +367,12 @@ def mdcn(x, offset_weight, offset_bias, dcn_weight, dcn_bias, dtype="fp32", flag
     ws = workspace(n, x.device)
     y = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        if _events is not None:
+        if route != "window":
+            ev, nev = (ctypes.cast(_events[0], POINTER(c_void_p)), _events[1]) if _events is not None else (None, 0)
+            check(L.emavfi_mdcn_routed(x.data_ptr(), ow.data_ptr(), ob.data_ptr(), dw.data_ptr(), db.data_ptr() if db is not None else None,
+                                       y.data_ptr(), B, C, H, W, dt, flags, ROUTES[route], ws.data_ptr(), ws.numel(), ev, nev, _stream()),
+                  "emavfi_mdcn_routed")
+        elif _events is not None:
             check(L.emavfi_mdcn_profiled(x.data_ptr(), ow.data_ptr(), ob.data_ptr(), dw.data_ptr(), db.data_ptr() if db is not None else None,
                                          y.data_ptr(), B, C, H, W, dt, flags, ws.data_ptr(), ws.numel(), ctypes.cast(_events[0], POINTER(c_void_p)),
                                          _events[1], _stream()), "emavfi_mdcn_profiled")
@@ -436,17 +452,21 @@ def reconstruct(fused, params, dtype="fp32"):
                   "emavfi_reconstruct")
 
 
-def forward_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype):
-    """[(name, algorithmic_flops, algorithmic_bytes)] for every kernel launch of one forward."""
+def forward_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, gather_blocks=0):
+    """[(name, algorithmic_flops, algorithmic_bytes)] for every kernel launch of one forward.  gather_blocks: bit i routes attention
+    block i to the window-free kernel (emavfi_forward_launches_routed); 0 lists exactly what emavfi_forward launches."""
     L = load()
     dt = dtype_code(dtype)
-    n = L.emavfi_forward_launches(in_channels, mid_channels, num_blocks, B, H, W, dt, None, 0, None, None, 0)
+    if gather_blocks:
+        entry, what = (lambda *a: L.emavfi_forward_launches_routed(*a[:7], gather_blocks, *a[7:])), "emavfi_forward_launches_routed"
+    else:
+        entry, what = L.emavfi_forward_launches, "emavfi_forward_launches"
+    n = entry(in_channels, mid_channels, num_blocks, B, H, W, dt, None, 0, None, None, 0)
     if n < 0:
-        raise RuntimeError(f"emavfi_forward_launches: {last_error()}")
+        raise RuntimeError(f"{what}: {last_error()}")
     names = ctypes.create_string_buffer(128 * n)
     fl, by = (ctypes.c_double * n)(), (ctypes.c_double * n)()
-    check(min(0, L.emavfi_forward_launches(in_channels, mid_channels, num_blocks, B, H, W, dt, names, len(names), fl, by, n)),
-          "emavfi_forward_launches")
+    check(min(0, entry(in_channels, mid_channels, num_blocks, B, H, W, dt, names, len(names), fl, by, n)), what)
     labels = names.value.decode().strip().split("\n")
     return [(labels[i], fl[i], by[i]) for i in range(n)]
 

@@ -31,6 +31,10 @@ import torch.nn as nn
 
 from . import lib as _lib
 
+# EMA_VFI.pack_policy ("Pack policy").  No census-driven "auto": the window-free kernel does not beat the window at
+# +-8 px (profiles/r07_gather_route_kill.md)
+PACK_POLICIES = ("window", "gather")
+
 
 def conv(in_channels, out_channels, kernel_size=3, stride=1, padding=1, dilation=1, groups=1, bias=True,
          padding_mode='zeros'):
@@ -118,6 +122,8 @@ class EMA_VFI(nn.Module):
         self.pipeline = int(os.environ.get("EMAVFI_PIPELINE", "1"))
         # which stage event of piece k releases piece k + 1: 0 = its front (default), 1 = its attention blocks, -1 = none (pieces start together)
         self.pipeline_stagger = int(os.environ.get("EMAVFI_PIPELINE_STAGGER", "0"))
+        # route of the 16-bit attention blocks (include/emavfi.h, emavfi_forward_routed): "window" (default) or "gather"
+        self.pack_policy = os.environ.get("EMAVFI_PACK_POLICY", "window")
         m = mid_channels
         self.feat_ext_conv1 = conv_block(in_channels * 2, m)
         self.feat_ext_blocks = nn.Sequential(OrderedDict(
@@ -298,6 +304,21 @@ class EMA_VFI(nn.Module):
         auto = get("cuda") if get is not None else torch.get_autocast_gpu_dtype()
         return _lib.BF16 if auto == torch.bfloat16 else _lib.AMP16
 
+    # ------------------------------------------------------------------ pack route
+    @property
+    def pack_policy(self):
+        """Which kernel runs the one-launch ModulatedDeformConvPack of each 16-bit attention block ("Pack policy"):
+        "window" (default) deform_pack3_kernel everywhere - the launches and frames of every earlier version; "gather" the window-free
+        kernel on every block (flat in the offsets, faster beyond about +-10 px; raises, with the library's error text, in modes
+        without a one-launch pack: fp32, amp16, fp32x3).  Initial value: EMAVFI_PACK_POLICY."""
+        return self._pack_policy
+
+    @pack_policy.setter
+    def pack_policy(self, value):
+        if value not in PACK_POLICIES:
+            raise ValueError(f"EMA_VFI.pack_policy must be one of {PACK_POLICIES}, got {value!r}")
+        self._pack_policy = value
+
     # ------------------------------------------------------------------ forward
     def forward(self, frame1, frame2, return_taps=False, _events=None):
         if frame1.shape != frame2.shape or frame1.dim() != 4 or frame1.shape[1] != self.in_channels:
@@ -334,8 +355,20 @@ class EMA_VFI(nn.Module):
         pieces = min(int(self.pipeline), B)
         if (C * H * W) % 4 != 0:
             pieces = 1   # a slice of the batch must start 16-byte aligned (include/emavfi.h): odd sample sizes run as one sequence
+        gmask = (1 << self.num_blocks) - 1 if self._pack_policy == "gather" else 0
         if pieces >= 2 and not return_taps and not torch.cuda.is_current_stream_capturing():
-            self._forward_pipelined(L, packed, f1, f2, out, dt, pieces, _events)
+            self._forward_pipelined(L, packed, f1, f2, out, dt, pieces, _events, gmask)
+        elif self._pack_policy != "window":
+            nws = L.emavfi_workspace_bytes(C, self.mid_channels, self.num_blocks, B, H, W, dt)
+            if nws == 0:
+                raise RuntimeError(f"EMA_VFI: {_lib.last_error()}")
+            ws = _lib.workspace(nws, dev)
+            with torch.cuda.device(dev):
+                evp, nev = (cast(_events[0], POINTER(c_void_p)), _events[1]) if _events is not None else (None, 0)
+                _lib.check(L.emavfi_forward_routed(C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(), f1.data_ptr(),
+                                                   f2.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, dt, taps_arg, None,
+                                                   evp, nev, gmask, _lib._stream()), "emavfi_forward_routed")
+            self._last_call = (dev, torch.cuda.current_stream(dev).cuda_stream, B, H, W, dt, nws, ws.data_ptr(), gmask)
         else:
             nws = L.emavfi_workspace_bytes(C, self.mid_channels, self.num_blocks, B, H, W, dt)
             if nws == 0:
@@ -351,7 +384,7 @@ class EMA_VFI(nn.Module):
                     _lib.check(L.emavfi_forward(C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(), f1.data_ptr(),
                                                 f2.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, dt, taps_arg,
                                                 _lib._stream()), "emavfi_forward")
-            self._last_call = (dev, torch.cuda.current_stream(dev).cuda_stream, B, H, W, dt, nws)
+            self._last_call = (dev, torch.cuda.current_stream(dev).cuda_stream, B, H, W, dt, nws, ws.data_ptr(), 0)
         # under autocast the reference's reconstruction tail is fp16, so its frame is an fp16 tensor (the values computed
         # here are fp16-representable: the conversion is exact)
         out = out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
@@ -365,21 +398,29 @@ class EMA_VFI(nn.Module):
         they ran (include/emavfi.h, emavfi_forward_census): per attention block a dict {fixup_wave_taps, wave_taps, fixup_share,
         samples_outside_window, samples_outside_share, abs_offset_px_max}, or None for a block that ran other kernels (fp32 / autocast
         modes, other widths).  The reference bounds its offsets nowhere (ema_vfi.py:55-60); the kernel's staged window holds offsets up
-        to +-2 px beyond the tap and pays for every (4 x 16 pixels, tap) group with a sample outside it.  One blocking D2H copy."""
+        to +-2 px beyond the tap and pays for every (4 x 16 pixels, tap) group with a sample outside it.  Every row also says which
+        kernel the block ran ("route": "window" | "gather", pack_policy); both count the same thing.  One blocking D2H copy."""
         last = getattr(self, "_last_call", None)
         if last is None:
             raise RuntimeError("EMA_VFI.pack_census: no one-sequence forward has run yet")
-        dev, stream, B, H, W, dt, nws = last
+        dev, stream, B, H, W, dt, nws, ws_ptr, gmask = last
         if torch.cuda.current_stream(dev).cuda_stream != stream:
             raise RuntimeError("EMA_VFI.pack_census: call it on the stream the forward ran on")
         ws = _lib.workspace(nws, dev)
+        if ws.data_ptr() != ws_ptr:
+            # the stream's workspace was replaced (a larger forward ran since): the counters of that forward are gone
+            raise RuntimeError("EMA_VFI.pack_census: the workspace of the last forward has been replaced since; run the forward again")
         out = torch.zeros(self.num_blocks, 4, dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
             _lib.check(_lib.load().emavfi_forward_census(self.in_channels, self.mid_channels, self.num_blocks, B, H, W, dt, ws.data_ptr(), ws.numel(),
                                                          out.data_ptr(), _lib._stream()), "emavfi_forward_census")
-        return _lib._census_rows(out, B * H * W * 9)
+        rows = _lib._census_rows(out, B * H * W * 9)
+        for i, row in enumerate(rows):
+            if row is not None:
+                row["route"] = "gather" if (gmask >> i) & 1 else "window"
+        return rows
 
-    def _forward_pipelined(self, L, packed, f1, f2, out, dt, pieces, _events=None):
+    def _forward_pipelined(self, L, packed, f1, f2, out, dt, pieces, _events=None, gather_blocks=0):
         """The batch as `pieces` contiguous slices alternating between the caller's stream and one side stream, piece k + 1 starting
         when piece k's FRONT (feature extraction, context, motion, warp: ema_vfi.py:112-130) has been enqueued-and-finished, so that one
         piece's attention blocks (the LDS-window pack kernel: gather / blend / MFMA per sample) run beside another piece's plain
@@ -427,10 +468,16 @@ class EMA_VFI(nn.Module):
                         evp = None
                         if _events is not None:
                             evp = cast(c_void_p(_events[0].value + k * per * ctypes.sizeof(c_void_p)), POINTER(c_void_p))
-                        _lib.check(L.emavfi_forward_staged(C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(),
-                                                           f1[b0:b1].data_ptr(), f2[b0:b1].data_ptr(), out[b0:b1].data_ptr(), ws.data_ptr(), ws.numel(),
-                                                           b1 - b0, H, W, dt, cast(stage, POINTER(c_void_p)), evp, per, c_void_p(s.cuda_stream)),
-                                   "emavfi_forward_staged")
+                        if gather_blocks:
+                            _lib.check(L.emavfi_forward_routed(C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(),
+                                                               f1[b0:b1].data_ptr(), f2[b0:b1].data_ptr(), out[b0:b1].data_ptr(), ws.data_ptr(),
+                                                               ws.numel(), b1 - b0, H, W, dt, None, cast(stage, POINTER(c_void_p)), evp, per,
+                                                               gather_blocks, c_void_p(s.cuda_stream)), "emavfi_forward_routed")
+                        else:
+                            _lib.check(L.emavfi_forward_staged(C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(),
+                                                               f1[b0:b1].data_ptr(), f2[b0:b1].data_ptr(), out[b0:b1].data_ptr(), ws.data_ptr(), ws.numel(),
+                                                               b1 - b0, H, W, dt, cast(stage, POINTER(c_void_p)), evp, per, c_void_p(s.cuda_stream)),
+                                       "emavfi_forward_staged")
                     front_prev = front if self.pipeline_stagger >= 0 else None
             finally:
                 # also when a piece failed to enqueue: `out` and the frames are known to the caching allocator on the caller's stream
