@@ -212,6 +212,40 @@ int emavfi_forward_routed(int in_channels, int mid_channels, int num_blocks, con
 int emavfi_forward_launches_routed(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, unsigned gather_blocks,
                                    char *names, size_t names_bytes, double *flops, double *bytes, int capacity);
 
+/* Adaptive per-block route: the route of every 16-bit attention block is chosen ON THE DEVICE from the census of the
+ * previous forward, so neither the caller nor a captured graph ever reads a counter back.  Each such block runs the ROUTED pack
+ * (deform_pack3_kernel<Route3<T>, true>): one launch that reads the block's route word in `route_state` and runs the window body or the
+ * gather body above - same operands, output and census as the plain kernel of that route, bit for bit.  After the last attention block
+ * one route_select launch reads this forward's census, records per block the route that ran and its fix-up share (fix-up wave-taps /
+ * all wave-taps, the fixup_share of emavfi_forward_census) and writes the route of the NEXT forward with hysteresis:
+ *   on EMAVFI_ROUTE_WINDOW: switch to gather when share >= enter_share;  on EMAVFI_ROUTE_GATHER: back to window when share <= leave_share.
+ * route_state: caller-owned DEVICE memory of emavfi_route_state_bytes() (<= 256) bytes, 16-byte aligned, one per stream of forwards;
+ * u32 words:
+ *   [0] EMAVFI_ROUTE_MAGIC   [1] num_blocks   [2] next mask (bit i: block i runs gather in the next adaptive forward)
+ *   [3] ran mask (bit i: block i ran gather in the last adaptive forward)   [4] adaptive forwards whose census was read   [5..7] 0
+ *   [8 + i]  route word of block i (EMAVFI_ROUTE_*; the routed pack reads it; always bit i of the next mask)
+ *   [16 + i] float: block i's fix-up share in the last adaptive forward (-1 before the first one)
+ *   [24 + i] switches of block i since the state was initialised
+ * emavfi_route_state_init writes a fresh state on `stream` (start_gather_mask: the starting routes; bits at or above num_blocks are
+ * EMAVFI_E_ARG).  emavfi_forward_adaptive takes emavfi_forward_routed's arguments with gather_blocks replaced by the state and the two
+ * thresholds (0 <= leave_share < enter_share <= 1, else EMAVFI_E_ARG).  The entry never reads the state back (no host sync): the library
+ * remembers the states emavfi_route_state_init wrote, and a null state, one it did not write (wrong magic) or one written for another
+ * num_blocks is EMAVFI_E_ARG.  On the device the selector also checks words [0] and [1] and leaves a state that fails them untouched.
+ * In modes and widths without a one-launch pack (fp32, EMAVFI_AMP16, EMAVFI_F32X3, other widths) emavfi_forward_adaptive is exactly
+ * emavfi_forward: same launches, same frame, no selector, the state untouched (adaptation is a preference, unlike
+ * EMAVFI_ROUTE_GATHER).  emavfi_forward_launches_adaptive lists such a forward's launches: "deform_routed<...> offset_conv+dcn_v2" per
+ * routed block and one final "route_select".  The thresholds of DESIGN 4.1 (0.75 / 0.65) come from one block at B = 8 x 720p. */
+#define EMAVFI_ROUTE_MAGIC 0x52544531u /* "1ETR" */
+size_t emavfi_route_state_bytes(void);
+int emavfi_route_state_init(void *route_state, int num_blocks, unsigned start_gather_mask, void *stream);
+int emavfi_forward_adaptive(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes,
+                            const float *frame1, const float *frame2, float *out,
+                            void *workspace, size_t workspace_bytes,
+                            int B, int H, int W, int dtype, float *const *taps, void *const *stage_events, void *const *events, int n_events,
+                            void *route_state, float enter_share, float leave_share, void *stream);
+int emavfi_forward_launches_adaptive(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype,
+                                     char *names, size_t names_bytes, double *flops, double *bytes, int capacity);
+
 /* EMA_VFI.warp(frame2, feature, flow), ema_vfi.py:149-171 (grid build + normalise +
  * F.grid_sample bilinear/zeros/align_corners=True), fused into one HBM-bound kernel.
  * frame2 [B,C,H,W], flow [B,2,H,W] (channel 0 = dx, 1 = dy, pixels), out [B,C,H,W]; fp32. */

@@ -274,7 +274,12 @@ struct DeformParams {
     int pack3;     // weights are in the deform_pack3.inl layout (K = 64 per tap + im2col tail, third fragment as an LDS table);
                    // 3: fp32, the deform_f32w.inl layout
     int in_f16, out_f16;  // bf16 storage only: x (and x_tail) / out hold IEEE f16 bit patterns (tensors handed between consecutive packs)
-    void *out16;          // fp32 LDS-window kernel (deform_f32w.inl) only, EMAVFI_AMP16: ALSO write the result's fp16 rounding, channels-last with
+    union {
+        void *out16;          // fp32 LDS-window kernel (deform_f32w.inl) only, EMAVFI_AMP16: ALSO write the result's fp16 rounding, channels-last with
+        const unsigned *route;  // the routed one-launch pack (deform_route3.inl) only: its block's route word (EMAVFI_ROUTE_WINDOW / _GATHER) in
+                                // device memory.  Shares out16's bytes: a field of its own would move the hidden kernel arguments of every
+                                // deform kernel (and with them deform_pack3_kernel's and deform_gather3_kernel's code objects)
+    };
     int out16_ps;         // pixel stride out16_ps (elements) - what the fp16 offset_conv / reconstruction.0 read (was a separate conversion pass)
     int out16_lo_off;     // EMAVFI_F32X3: > 0 = also write the lo half f16(v - f16(v)) at this element offset of the out16 pixel
     int x3;               // EMAVFI_F32X3: deform_f32w.inl contracts with the three-term f16 split (16x16x16 f16 MFMAs) instead of fp32 MFMAs
@@ -345,6 +350,15 @@ int launch_deform_f16(const DeformParams &p, hipStream_t s);
 // deform_pack3_kernel<T, true>, -2 for anything else
 int launch_deform_gather_bf16(const DeformParams &p, hipStream_t s);
 int launch_deform_gather_f16(const DeformParams &p, hipStream_t s);
+// the routed one-launch pack (deform_route3.inl): reads the route word at p.route and runs deform_pack3_kernel<T, true>'s or
+// deform_gather3_kernel<T>'s body; same operands, same output, same census; -2 where the gather route has no instantiation
+int launch_deform_routed_bf16(const DeformParams &p, hipStream_t s);
+int launch_deform_routed_f16(const DeformParams &p, hipStream_t s);
+// the adaptive forward's route selector (misc_kernels.hip): reads the census of this forward, applies the hysteresis, writes the route
+// state (include/emavfi.h, emavfi_forward_adaptive).  totals[i]: block i's wave-taps, 0 = no routed pack
+int launch_route_select(const unsigned *census, void *state, int nblocks, const unsigned long long *totals, float enter, float leave,
+                        unsigned magic, hipStream_t s);
+int launch_route_state_init(void *state, unsigned magic, int nblocks, unsigned start_gather, hipStream_t s);   // 32 words (include/emavfi.h)
 // 16-bit dtypes at the reference width: the whole ModulatedDeformConvPack is one launch (deform_pack3.inl / deform_pack.inl)
 #ifndef EMAVFI_PACK3
 #define EMAVFI_PACK3 1   // 0: the round-2 kernel (deform_pack.inl) and its weight layout (A/B builds)

@@ -1,6 +1,8 @@
 #include <cstdlib>
 #include "deform_pack3.inl"
 #include "deform_gather3.inl"
+#define DEFORM_ROUTE3_TS bf16_t
+#include "deform_route3.inl"
 
 bool deform16_can_fuse_offset_conv(int ck, int nf, int cin_real, int off_ck, int off_nf)
 {
@@ -11,3 +13,5 @@ bool deform16_can_fuse_offset_conv(int ck, int nf, int cin_real, int off_ck, int
 int launch_deform_bf16(const DeformParams &p, hipStream_t s) { return launch_deform16<bf16_t>(p, s); }
 
 int launch_deform_gather_bf16(const DeformParams &p, hipStream_t s) { return launch_deform_gather3<bf16_t>(p, s); }
+
+int launch_deform_routed_bf16(const DeformParams &p, hipStream_t s) { return launch_deform_route3(p, s); }

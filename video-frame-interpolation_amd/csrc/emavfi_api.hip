@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <unordered_map>
 #include <string>
 #include <vector>
 
@@ -440,7 +441,7 @@ unsigned long long *debug_stamp_buffer()
 int run_deform(const Plan &P, const Layer &L, const void *packed, const void *x, int x_ps, float *om, void *out,
                int out_ps, int cstore, int B, int H, int W, hipStream_t s, const void *zeros = nullptr, const Layer *off = nullptr,
                const void *x_tail = nullptr, int tail_ps = 0, int force_dtype = -1, int in_f16 = 0, int out_f16 = 0, void *out16 = nullptr, int out16_ps = 0,
-               unsigned *census = nullptr, int out16_lo_off = 0, bool gather = false)
+               unsigned *census = nullptr, int out16_lo_off = 0, bool gather = false, const unsigned *route = nullptr)
 {
     const int kd = force_dtype >= 0 ? force_dtype : P.dtype;
     DeformParams d{};
@@ -459,6 +460,7 @@ int run_deform(const Plan &P, const Layer &L, const void *packed, const void *x,
     d.x_ps = x_ps; d.out_ps = out_ps; d.H = H; d.W = W; d.B = B; d.cstore = cstore; d.cin_real = L.cin_take; d.ck = L.ck; d.nf = L.nf;
     d.cout_real = L.cout; d.pack3 = L.pack3; d.in_f16 = in_f16; d.out_f16 = out_f16;
     d.out16 = out16; d.out16_ps = out16_ps;
+    if (route) d.route = route;   // (shares out16's bytes: the routed pack has no fp16 side output)
 #if defined(EMAVFI_DEFORM_STAMPS) && EMAVFI_DEFORM_STAMPS
     {   // diagnostic build: EMAVFI_STAMP_PACK=i records only the i-th deformable launch of every 3 (default: every launch,
         // i.e. what is read back is the last pack of a forward)
@@ -475,6 +477,8 @@ int run_deform(const Plan &P, const Layer &L, const void *packed, const void *x,
         for (int i = 1; i < atoi(rep); ++i)
             if (const int rc = kd == EMAVFI_F32 ? launch_deform_f32(d, s) : kd == EMAVFI_F16 ? launch_deform_f16(d, s) : launch_deform_bf16(d, s)) return rc;
 #endif
+    // the routed pack (deform_route3.inl): the route word at `route` picks the window or the gather body; 16-bit kinds only
+    if (route) return kd == EMAVFI_F16 ? launch_deform_routed_f16(d, s) : kd == EMAVFI_BF16 ? launch_deform_routed_bf16(d, s) : -2;
     // the window-free route of the one-launch pack (deform_gather3.inl): 16-bit kinds only, -2 (no instantiation) for anything else
     if (gather) return kd == EMAVFI_F16 ? launch_deform_gather_f16(d, s) : kd == EMAVFI_BF16 ? launch_deform_gather_bf16(d, s) : -2;
     return kd == EMAVFI_F32 ? launch_deform_f32(d, s) : kd == EMAVFI_F16 ? launch_deform_f16(d, s) : launch_deform_bf16(d, s);
@@ -631,13 +635,26 @@ bool pack_f16_link(const Plan &P, int i)
 bool pack_gather_ok(const Plan &P, int i) { return pack_fuses(P, i) && P.dcn[i].pack3 == 1; }
 // 16-bit / fp32 models: x -> y (channels-last, pixel stride P.fps).  x_tail: the compact tail buffer (kTailPs channels per pixel) the first pack takes channels
 // 64.. from (or null); in_f16 / out_f16: the bf16 model's f16 hand-off (DeformParams).  route: EMAVFI_ROUTE_WINDOW (deform_pack3_kernel) or
-// EMAVFI_ROUTE_GATHER (deform_gather3_kernel: same operands, same output, no window - refused where pack_gather_ok does not hold)
+// EMAVFI_ROUTE_GATHER (deform_gather3_kernel: same operands, same output, no window - refused where pack_gather_ok does not hold) or
+// kRouteAdaptive (the routed pack, deform_route3.inl, reading the route word `route_word`: emavfi_forward_adaptive)
+constexpr int kRouteAdaptive = 2;
 int attention_block(const Plan &P, int i, const void *packed, const void *x, void *y, float *om, const void *x_tail, int in_f16, int out_f16,
-                    int B, int H, int W, hipStream_t s, Recorder &rec, unsigned *census = nullptr, int route = EMAVFI_ROUTE_WINDOW)
+                    int B, int H, int W, hipStream_t s, Recorder &rec, unsigned *census = nullptr, int route = EMAVFI_ROUTE_WINDOW,
+                    const unsigned *route_word = nullptr)
 {
     const double px = (double)B * H * W, e = P.esize, cf = P.mid + 3;
     double fl, by;
     conv_work(P, P.off[i], B, H, W, 4.0, fl, by);
+    if (route == kRouteAdaptive) {
+        if (!pack_gather_ok(P, i)) return fail(EMAVFI_E_UNSUPPORTED, "attention block %d: the routed pack exists only where the one-launch pack runs", i);
+        char nm[96];
+        snprintf(nm, sizeof nm, "deform_routed<%s,ck=%d,nf=%d> offset_conv+dcn_v2", dtype_name(P.dtype), P.dcn[i].ck, P.dcn[i].nf);
+        // (the window route's algorithmic work: which body runs is decided on the device)
+        EMAVFI_STEP(rec, nm, fl + 2.0 * 9.0 * cf * cf * px, px * (2.0 * cf * e) + 9.0 * cf * (cf + 27.0) * e,
+                    run_deform(P, P.dcn[i], packed, x, P.fps, om, y, P.fps, P.fps, B, H, W, s, nullptr, P.has_offh ? &P.offh[i] : &P.off[i], x_tail, kTailPs,
+                               -1, in_f16, out_f16, nullptr, 0, census, 0, false, route_word));
+        return EMAVFI_OK;
+    }
     if (route == EMAVFI_ROUTE_GATHER) {
         if (!pack_gather_ok(P, i)) return fail(EMAVFI_E_UNSUPPORTED, "attention block %d: the gather route exists only where the one-launch pack runs (16-bit modes at the reference width)", i);
         char nm[96];
@@ -766,12 +783,28 @@ BlobHeader expected_header(const Plan &P, int requested_dtype)
     return h;
 }
 
+// emavfi_forward_adaptive's part of a forward: the route state (device, include/emavfi.h) and the hysteresis thresholds
+struct Adapt { bool on = false; unsigned *state = nullptr; float enter = 0.0f, leave = 0.0f; };
+// all (wave, tap) groups of one one-launch pack: the census denominator (emavfi_forward_census, route_select)
+static unsigned long long pack3_wave_taps(int B, int H, int W) { return (unsigned long long)B * ((H + 15) / 16) * ((W + 15) / 16) * 4ull * 9ull; }
+// a forward in this mode has routed packs: every block runs the one-launch pack of the deform_pack3 layout (16-bit modes at the
+// reference width; not EMAVFI_AMP16 / EMAVFI_F32X3, whose blocks run the fp32-family DCN)
+static bool adaptive_applies(const Plan &P)
+{
+    if (P.amp || P.nb < 1) return false;
+    for (int i = 0; i < P.nb; ++i)
+        if (!pack_gather_ok(P, i)) return false;
+    return true;
+}
+
 int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes, const float *frame1,
                  const float *frame2, float *out, void *workspace, size_t workspace_bytes, int B, int H, int W, int dtype,
-                 float *const *taps, void *stream, Recorder &rec, unsigned gather_blocks = 0)
+                 float *const *taps, void *stream, Recorder &rec, unsigned gather_blocks = 0, const Adapt &adapt = Adapt{})
 {
     Plan P;
     if (!build_plan(P, in_channels, mid_channels, num_blocks, dtype)) return fail(EMAVFI_E_UNSUPPORTED, "%s", P.why);
+    // emavfi_forward_adaptive: every block of a mode with the one-launch pack runs the routed pack; elsewhere it is emavfi_forward
+    const bool adaptive = adapt.on && adaptive_applies(P);
     // per-block route (emavfi_forward_routed): bit i sends attention block i to the window-free kernel
     if (P.nb < 32 && (gather_blocks >> P.nb) != 0u)
         return fail(EMAVFI_E_ARG, "forward: gather_blocks 0x%x names blocks at or above num_blocks = %d", gather_blocks, P.nb);
@@ -962,12 +995,20 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
             if (const int rc = attention_block(P, i, packed, x, y, f.om, i == 0 && split_tail ? f.in16 : nullptr,
                                                (i == 0 ? feat16 : pack_f16_link(P, i - 1)) ? 1 : 0, pack_f16_link(P, i) ? 1 : 0, B, H, W, s, rec,
                                                rec.dry ? nullptr : f.census + (size_t)i * DEFORM_CENSUS_SLOTS * 4,
-                                               ((gather_blocks >> i) & 1u) ? EMAVFI_ROUTE_GATHER : EMAVFI_ROUTE_WINDOW);
+                                               adaptive ? kRouteAdaptive : ((gather_blocks >> i) & 1u) ? EMAVFI_ROUTE_GATHER : EMAVFI_ROUTE_WINDOW,
+                                               adaptive ? adapt.state + 8 + i : nullptr);
                 rc != EMAVFI_OK)
                 return rc;
             if (!rec.dry && taps && taps[5 + i])
                 EMAVFI_TRY(launch_cl_to_nchw(y, taps[5 + i], B, mid + 3, H, W, P.fps, 0, pack_f16_link(P, i) ? (int)EMAVFI_F16 : dtype, s), "tap fused");
             void *t = x; x = y; y = t;
+        }
+        if (adaptive) {
+            // the next forward's routes from this one's census (read here, before anything reuses those bytes)
+            unsigned long long totals[kMaxBlocks] = {};
+            for (int i = 0; i < P.nb; ++i) totals[i] = pack3_wave_taps(B, H, W);
+            EMAVFI_STEP(rec, "route_select", 0.0, (double)P.nb * kCensusBlock + 128.0,
+                        launch_route_select(f.census, adapt.state, P.nb, totals, adapt.enter, adapt.leave, EMAVFI_ROUTE_MAGIC, s));
         }
     }
 
@@ -1182,14 +1223,16 @@ int emavfi_forward_launches(int in_channels, int mid_channels, int num_blocks, i
     return emavfi_forward_launches_routed(in_channels, mid_channels, num_blocks, B, H, W, dtype, 0u, names, names_bytes, flops, bytes, capacity);
 }
 
-int emavfi_forward_launches_routed(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, unsigned gather_blocks,
-                                   char *names, size_t names_bytes, double *flops, double *bytes, int capacity)
+static int list_launches(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, unsigned gather_blocks, bool adaptive,
+                         char *names, size_t names_bytes, double *flops, double *bytes, int capacity)
 {
     std::vector<LaunchRec> recs;
     Recorder rec;
     rec.recs = &recs; rec.dry = true;
+    Adapt adapt;
+    adapt.on = adaptive;
     const int rc = forward_impl(in_channels, mid_channels, num_blocks, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, B, H, W,
-                                dtype, nullptr, nullptr, rec, gather_blocks);
+                                dtype, nullptr, nullptr, rec, gather_blocks, adapt);
     if (rc != EMAVFI_OK) return rc;
     const int n = (int)recs.size();
     if (capacity <= 0) return n;
@@ -1207,6 +1250,68 @@ int emavfi_forward_launches_routed(int in_channels, int mid_channels, int num_bl
         }
     }
     return n;
+}
+
+int emavfi_forward_launches_routed(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, unsigned gather_blocks,
+                                   char *names, size_t names_bytes, double *flops, double *bytes, int capacity)
+{
+    return list_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, gather_blocks, false, names, names_bytes, flops, bytes, capacity);
+}
+
+int emavfi_forward_launches_adaptive(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype,
+                                     char *names, size_t names_bytes, double *flops, double *bytes, int capacity)
+{
+    return list_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, 0u, true, names, names_bytes, flops, bytes, capacity);
+}
+
+// ---- adaptive per-block route (include/emavfi.h): the states emavfi_route_state_init wrote, by address -> num_blocks.  The forward
+// checks a state here instead of reading its magic back (that would be a host sync in every forward).
+static std::mutex g_route_states_mu;
+static std::unordered_map<const void *, int> g_route_states;
+constexpr size_t kRouteStateBytes = 32 * sizeof(unsigned);
+
+size_t emavfi_route_state_bytes(void) { return kRouteStateBytes; }
+
+int emavfi_route_state_init(void *route_state, int num_blocks, unsigned start_gather_mask, void *stream)
+{
+    if (!route_state) return fail(EMAVFI_E_ARG, "route_state_init: null state");
+    if (!aligned16(route_state)) return fail(EMAVFI_E_ARG, "route_state_init: the state must be 16-byte aligned");
+    if (num_blocks < 1 || num_blocks > kMaxBlocks) return fail(EMAVFI_E_ARG, "route_state_init: num_blocks must be 1..%d (got %d)", kMaxBlocks, num_blocks);
+    if ((start_gather_mask >> num_blocks) != 0u)
+        return fail(EMAVFI_E_ARG, "route_state_init: start_gather_mask 0x%x names blocks at or above num_blocks = %d", start_gather_mask, num_blocks);
+    EMAVFI_TRY(launch_route_state_init(route_state, EMAVFI_ROUTE_MAGIC, num_blocks, start_gather_mask, (hipStream_t)stream), "route_state_init");
+    std::lock_guard<std::mutex> lk(g_route_states_mu);
+    g_route_states[route_state] = num_blocks;
+    return EMAVFI_OK;
+}
+
+int emavfi_forward_adaptive(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes, const float *frame1,
+                            const float *frame2, float *out, void *workspace, size_t workspace_bytes, int B, int H, int W, int dtype,
+                            float *const *taps, void *const *stage_events, void *const *events, int n_events, void *route_state,
+                            float enter_share, float leave_share, void *stream)
+{
+    if (!(leave_share >= 0.0f && leave_share < enter_share && enter_share <= 1.0f))
+        return fail(EMAVFI_E_ARG, "forward_adaptive: thresholds need 0 <= leave_share < enter_share <= 1 (got enter %g, leave %g)", (double)enter_share,
+                    (double)leave_share);
+    if (!route_state) return fail(EMAVFI_E_ARG, "forward_adaptive: null route state");
+    {
+        std::lock_guard<std::mutex> lk(g_route_states_mu);
+        const auto it = g_route_states.find(route_state);
+        if (it == g_route_states.end())
+            return fail(EMAVFI_E_ARG, "forward_adaptive: bad route state magic (not written by emavfi_route_state_init)");
+        if (it->second != num_blocks)
+            return fail(EMAVFI_E_ARG, "forward_adaptive: the route state was written for num_blocks = %d, the model has %d", it->second, num_blocks);
+    }
+    Recorder rec;
+    rec.stage_events = stage_events;
+    if (events) {
+        if (n_events < 2) return fail(EMAVFI_E_ARG, "forward_adaptive: events given, n_events must be >= 2");
+        rec.events = events; rec.n_events = n_events;
+    }
+    Adapt adapt;
+    adapt.on = true; adapt.state = (unsigned *)route_state; adapt.enter = enter_share; adapt.leave = leave_share;
+    return forward_impl(in_channels, mid_channels, num_blocks, packed, packed_bytes, frame1, frame2, out, workspace, workspace_bytes, B, H, W,
+                        dtype, taps, stream, rec, 0u, adapt);
 }
 
 int emavfi_warp(const float *frame2, const float *flow, float *out, int B, int C, int H, int W, void *stream)
@@ -1506,7 +1611,6 @@ int emavfi_mdcn_routed(const float *x, const float *offset_weight, const float *
 // groups that took the fix-up, the samples outside the staged window, the largest |offset| - reduced over the launch's 64 atomic slots
 // into out[block][4] (u64, DEVICE memory): {fix-up wave-taps, all wave-taps, samples outside, max |offset| as fp32 bits}.  All wave-taps
 // is 0 for a block that did not run the one-launch kernel (fp32 / autocast modes, other widths): nothing was counted.
-static unsigned long long pack3_wave_taps(int B, int H, int W) { return (unsigned long long)B * ((H + 15) / 16) * ((W + 15) / 16) * 4ull * 9ull; }
 
 int emavfi_forward_census(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, const void *workspace,
                           size_t workspace_bytes, unsigned long long *out, void *stream)

@@ -1298,3 +1298,66 @@ int launch_census_reduce(const unsigned *census, unsigned long long *out, int nb
     census_reduce_kernel<<<nblocks, 64, 0, s>>>(census, out, t);
     return (int)hipGetLastError();
 }
+
+// ---- the adaptive forward's route selector (include/emavfi.h, emavfi_forward_adaptive): one wave, after the last attention block.  Per
+// block with a routed pack it adds the census slots of this forward (the counters route_select reads are the ones the packs above just
+// wrote: nothing else in a forward touches those bytes), divides by the host's wave-tap total (kernel arguments: fixed under graph
+// capture), records the route that ran and the share, and writes the next route with hysteresis.  State words: include/emavfi.h.
+struct RouteSelectArgs { unsigned long long totals[8]; float enter, leave; unsigned nblocks, magic; };
+__global__ void route_select_kernel(const unsigned *__restrict__ census, unsigned *__restrict__ state, RouteSelectArgs a)
+{
+    const int lane = threadIdx.x;   // 64 threads
+    if (state[0] != a.magic || state[1] != a.nblocks) return;   // not a state of this model: leave it as it is
+    unsigned next = 0u, ran = 0u;
+    for (unsigned i = 0; i < a.nblocks; ++i) {
+        const unsigned cur = state[8 + i] != 0u ? 1u : 0u;
+        unsigned nxt = cur;
+        if (a.totals[i] != 0ull) {
+            unsigned long long fix = census[((size_t)i * 64 + lane) * 4];
+#pragma unroll
+            for (int sh = 32; sh >= 1; sh >>= 1) fix += __shfl_xor(fix, sh);
+            const float share = (float)((double)fix / (double)a.totals[i]);
+            nxt = cur ? (share <= a.leave ? 0u : 1u) : (share >= a.enter ? 1u : 0u);
+            if (lane == 0) {
+                state[16 + i] = __float_as_uint(share);
+                if (nxt != cur) state[24 + i] += 1u;
+                state[8 + i] = nxt;
+            }
+        }
+        ran |= cur << i;
+        next |= nxt << i;
+    }
+    if (lane == 0) {
+        state[2] = next;
+        state[3] = ran;
+        state[4] += 1u;
+    }
+}
+int launch_route_select(const unsigned *census, void *state, int nblocks, const unsigned long long *totals, float enter, float leave,
+                        unsigned magic, hipStream_t s)
+{
+    if (nblocks < 1 || nblocks > 8) return (int)hipErrorInvalidValue;
+    RouteSelectArgs a{};
+    for (int i = 0; i < nblocks; ++i) a.totals[i] = totals[i];
+    a.enter = enter; a.leave = leave; a.nblocks = (unsigned)nblocks; a.magic = magic;
+    route_select_kernel<<<1, 64, 0, s>>>(census, (unsigned *)state, a);
+    return (int)hipGetLastError();
+}
+
+// a fresh route state (include/emavfi.h): 32 threads, one word each
+__global__ void route_state_init_kernel(unsigned *__restrict__ state, unsigned magic, unsigned nblocks, unsigned start_gather)
+{
+    const unsigned w = threadIdx.x;   // 32 threads, one word each
+    unsigned v = 0u;
+    if (w == 0) v = magic;
+    else if (w == 1) v = nblocks;
+    else if (w == 2) v = start_gather;
+    else if (w >= 8 && w < 16) v = (start_gather >> (w - 8)) & 1u;
+    else if (w >= 16 && w < 24) v = __float_as_uint(-1.0f);
+    state[w] = v;
+}
+int launch_route_state_init(void *state, unsigned magic, int nblocks, unsigned start_gather, hipStream_t s)
+{
+    route_state_init_kernel<<<1, 32, 0, s>>>((unsigned *)state, magic, (unsigned)nblocks, start_gather);
+    return (int)hipGetLastError();
+}

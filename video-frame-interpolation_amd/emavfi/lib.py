@@ -57,6 +57,11 @@ _PROTOTYPES = {
                               + [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int, ctypes.c_uint, c_void_p]),
     "emavfi_forward_launches_routed": (c_int, [c_int] * 7 + [ctypes.c_uint, c_char_p, c_size_t, POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int]),
     "emavfi_mdcn_routed": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p, c_size_t, POINTER(c_void_p), c_int, c_void_p]),
+    "emavfi_route_state_bytes": (c_size_t, []),
+    "emavfi_route_state_init": (c_int, [c_void_p, c_int, ctypes.c_uint, c_void_p]),
+    "emavfi_forward_adaptive": (c_int, [c_int] * 3 + [c_void_p, c_size_t] + [c_void_p] * 4 + [c_size_t] + [c_int] * 4
+                                + [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p, ctypes.c_float, ctypes.c_float, c_void_p]),
+    "emavfi_forward_launches_adaptive": (c_int, [c_int] * 7 + [c_char_p, c_size_t, POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int]),
     "emavfi_context_workspace_bytes": (c_size_t, [c_int] * 5),
     "emavfi_context": (c_int, [c_void_p, POINTER(c_void_p), c_void_p] + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
     "emavfi_reconstruct_workspace_bytes": (c_size_t, [c_int] * 5),
@@ -452,12 +457,18 @@ def reconstruct(fused, params, dtype="fp32"):
                   "emavfi_reconstruct")
 
 
-def forward_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, gather_blocks=0):
+def forward_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, gather_blocks=0, adaptive=False):
     """[(name, algorithmic_flops, algorithmic_bytes)] for every kernel launch of one forward.  gather_blocks: bit i routes attention
-    block i to the window-free kernel (emavfi_forward_launches_routed); 0 lists exactly what emavfi_forward launches."""
+    block i to the window-free kernel (emavfi_forward_launches_routed); 0 lists exactly what emavfi_forward launches.  adaptive: the
+    launches of emavfi_forward_adaptive (a routed pack per block plus one route_select; in modes without a one-launch pack exactly
+    emavfi_forward's)."""
     L = load()
     dt = dtype_code(dtype)
-    if gather_blocks:
+    if adaptive and gather_blocks:
+        raise ValueError("forward_launches: adaptive and gather_blocks exclude each other")
+    if adaptive:
+        entry, what = L.emavfi_forward_launches_adaptive, "emavfi_forward_launches_adaptive"
+    elif gather_blocks:
         entry, what = (lambda *a: L.emavfi_forward_launches_routed(*a[:7], gather_blocks, *a[7:])), "emavfi_forward_launches_routed"
     else:
         entry, what = L.emavfi_forward_launches, "emavfi_forward_launches"

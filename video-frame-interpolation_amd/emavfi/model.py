@@ -31,9 +31,39 @@ import torch.nn as nn
 
 from . import lib as _lib
 
-# EMA_VFI.pack_policy ("Pack policy").  No census-driven "auto": the window-free kernel does not beat the window at
-# +-8 px (profiles/r07_gather_route_kill.md)
+# EMA_VFI.pack_policy ("Pack policy").  No census-driven "auto" policy value: the window-free kernel does not beat the
+# window at +-8 px (profiles/r07_gather_route_kill.md); the census-driven choice is EMA_VFI.pack_adapt, which starts from pack_policy
 PACK_POLICIES = ("window", "gather")
+# EMA_VFI.pack_adapt's (enter, leave) fix-up shares for EMAVFI_PACK_ADAPT=1: the crossover measured for one block at B = 8 x 720p
+# (profiles/r07_gather_route_kill.md) plus hysteresis
+PACK_ADAPT_DEFAULT = (0.75, 0.65)
+
+
+def parse_pack_adapt(value):
+    """EMA_VFI.pack_adapt from a value or the EMAVFI_PACK_ADAPT string: None / "" / "0" = off, "1" = PACK_ADAPT_DEFAULT,
+    "enter,leave" or an (enter, leave) pair = those thresholds; 0 <= leave < enter <= 1, else ValueError."""
+    if value is None:
+        return None
+    if isinstance(value, str):
+        v = value.strip()
+        if v in ("", "0"):
+            return None
+        if v == "1":
+            return PACK_ADAPT_DEFAULT
+        parts = v.split(",")
+        if len(parts) != 2:
+            raise ValueError(f"EMAVFI_PACK_ADAPT must be 1 or 'enter,leave', got {value!r}")
+        try:
+            value = (float(parts[0]), float(parts[1]))
+        except ValueError:
+            raise ValueError(f"EMAVFI_PACK_ADAPT must be 1 or 'enter,leave', got {value!r}") from None
+    try:
+        enter, leave = (float(x) for x in value)
+    except (TypeError, ValueError):
+        raise ValueError(f"EMA_VFI.pack_adapt must be None or an (enter, leave) pair, got {value!r}") from None
+    if not (0.0 <= leave < enter <= 1.0):
+        raise ValueError(f"EMA_VFI.pack_adapt needs 0 <= leave < enter <= 1, got enter {enter}, leave {leave}")
+    return (enter, leave)
 
 
 def conv(in_channels, out_channels, kernel_size=3, stride=1, padding=1, dilation=1, groups=1, bias=True,
@@ -122,8 +152,11 @@ class EMA_VFI(nn.Module):
         self.pipeline = int(os.environ.get("EMAVFI_PIPELINE", "1"))
         # which stage event of piece k releases piece k + 1: 0 = its front (default), 1 = its attention blocks, -1 = none (pieces start together)
         self.pipeline_stagger = int(os.environ.get("EMAVFI_PIPELINE_STAGGER", "0"))
-        # route of the 16-bit attention blocks (include/emavfi.h, emavfi_forward_routed): "window" (default) or "gather"
+        # route of the 16-bit attention blocks (include/emavfi.h, emavfi_forward_routed): "window" (default) or "gather"; with
+        # pack_adapt set, the starting route of the census-driven choice (emavfi_forward_adaptive)
+        self._route_states = {}   # (device index, stream handle) -> route state (include/emavfi.h), created by the first adaptive forward
         self.pack_policy = os.environ.get("EMAVFI_PACK_POLICY", "window")
+        self.pack_adapt = os.environ.get("EMAVFI_PACK_ADAPT")
         m = mid_channels
         self.feat_ext_conv1 = conv_block(in_channels * 2, m)
         self.feat_ext_blocks = nn.Sequential(OrderedDict(
@@ -166,6 +199,7 @@ class EMA_VFI(nn.Module):
         self._installed.clear()          # the parameters are authoritative again: blobs re-pack from them
         self._packed.clear()
         self._params_loaded = True
+        self._reset_route_states()       # the census they hold described other offsets
         return res
 
     def _ordered_params(self):
@@ -288,6 +322,7 @@ class EMA_VFI(nn.Module):
             raise ValueError(f"load_packed_weights: a uint8 blob of {nbytes} bytes is expected for this model / dtype")
         # the blob's header must say this model, this dtype, this library version and this process's layout switches
         _lib.packed_check(self.in_channels, self.mid_channels, self.num_blocks, dt, blob)
+        self._reset_route_states()
         if params_are_source:
             self._packed[dt] = (self._weights_key(blob.device), blob)
             return
@@ -317,7 +352,76 @@ class EMA_VFI(nn.Module):
     def pack_policy(self, value):
         if value not in PACK_POLICIES:
             raise ValueError(f"EMA_VFI.pack_policy must be one of {PACK_POLICIES}, got {value!r}")
+        changed = getattr(self, "_pack_policy", value) != value
         self._pack_policy = value
+        if changed:
+            self._reset_route_states()   # the starting route of the adaptive choice
+
+    @property
+    def pack_adapt(self):
+        """Census-driven route per 16-bit attention block ("Pack policy"; include/emavfi.h, emavfi_forward_adaptive):
+        None (default: pack_policy decides alone) or the (enter, leave) fix-up shares of the hysteresis - a block on the window route
+        moves to the gather route in the next forward when its share reaches `enter`, and back when it falls to `leave`.  The choice is
+        made on the device from every forward's census (no host sync; a captured graph adapts on replay); pack_policy is the starting
+        route.  Modes without a one-launch pack (fp32, amp16, fp32x3) run their plain forward.  A batch runs as one sequence
+        (pipeline is ignored).  Initial value: EMAVFI_PACK_ADAPT (1 = PACK_ADAPT_DEFAULT, or "enter,leave").  Changing the thresholds
+        keeps the route state; load_state_dict, load_packed_weights and a new pack_policy reset it to the starting route."""
+        return self._pack_adapt
+
+    @pack_adapt.setter
+    def pack_adapt(self, value):
+        self._pack_adapt = parse_pack_adapt(value)
+
+    def _start_mask(self):
+        return (1 << self.num_blocks) - 1 if self._pack_policy == "gather" else 0
+
+    def _reset_route_states(self):
+        """Every route state back to the starting route, in place (a captured graph keeps the state's address), on its own stream."""
+        L = None
+        for (dev_index, stream), st in self._route_states.items():
+            L = L or _lib.load()
+            with torch.cuda.device(dev_index):
+                _lib.check(L.emavfi_route_state_init(st.data_ptr(), self.num_blocks, self._start_mask(), c_void_p(stream)),
+                           "emavfi_route_state_init")
+
+    def _route_state(self, dev):
+        """The route state of the current stream of `dev`, created (and initialised on that stream) by its first adaptive forward."""
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        key = (dev.index, stream)
+        st = self._route_states.get(key)
+        if st is None:
+            if torch.cuda.is_current_stream_capturing():
+                # created inside a capture, its initialisation would be part of every replay
+                raise RuntimeError("EMA_VFI: no route state for the capturing stream yet; run one adaptive forward on that stream "
+                                   "(a warm-up) before capturing")
+            L = _lib.load()
+            st = torch.empty(L.emavfi_route_state_bytes() // 4, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(L.emavfi_route_state_init(st.data_ptr(), self.num_blocks, self._start_mask(), _lib._stream()),
+                           "emavfi_route_state_init")
+            self._route_states[key] = st
+        return st
+
+    def pack_routes(self):
+        """The adaptive route of every attention block on the current stream (pack_adapt): per block a dict {ran, next, fixup_share,
+        switches} - the route ("window" | "gather") of the last adaptive forward, the route of the next one, the fix-up share that
+        forward measured and the route changes since the state was (re)set - or None for a block without a routed pack (fp32 / autocast
+        modes, other widths).  One blocking D2H copy."""
+        last = getattr(self, "_last_call", None)
+        if last is None or last[8] is not None:
+            raise RuntimeError("EMA_VFI.pack_routes: no adaptive one-sequence forward has run yet")
+        dev, stream, B, H, W, dt = last[:6]
+        if torch.cuda.current_stream(dev).cuda_stream != stream:
+            raise RuntimeError("EMA_VFI.pack_routes: call it on the stream the forward ran on")
+        routed = any(n.startswith("deform_routed") for n, _, _ in
+                     _lib.forward_launches(self.in_channels, self.mid_channels, self.num_blocks, B, H, W, dt, adaptive=True))
+        if not routed:
+            return [None] * self.num_blocks
+        w = self._route_states[(dev.index, stream)].cpu()
+        ran, share, sw = int(w[3]), w[16:24].view(torch.float32), w[24:32]
+        name = ("window", "gather")
+        return [{"ran": name[(ran >> i) & 1], "next": name[int(w[8 + i]) & 1], "fixup_share": float(share[i]), "switches": int(sw[i])}
+                for i in range(self.num_blocks)]
 
     # ------------------------------------------------------------------ forward
     def forward(self, frame1, frame2, return_taps=False, _events=None):
@@ -355,9 +459,25 @@ class EMA_VFI(nn.Module):
         pieces = min(int(self.pipeline), B)
         if (C * H * W) % 4 != 0:
             pieces = 1   # a slice of the batch must start 16-byte aligned (include/emavfi.h): odd sample sizes run as one sequence
+        if self._pack_adapt is not None:
+            pieces = 1   # one route state per stream, one census per forward: the adaptive forward runs as one sequence
         gmask = (1 << self.num_blocks) - 1 if self._pack_policy == "gather" else 0
         if pieces >= 2 and not return_taps and not torch.cuda.is_current_stream_capturing():
             self._forward_pipelined(L, packed, f1, f2, out, dt, pieces, _events, gmask)
+        elif self._pack_adapt is not None:
+            state = self._route_state(dev)
+            nws = L.emavfi_workspace_bytes(C, self.mid_channels, self.num_blocks, B, H, W, dt)
+            if nws == 0:
+                raise RuntimeError(f"EMA_VFI: {_lib.last_error()}")
+            ws = _lib.workspace(nws, dev)
+            enter, leave = self._pack_adapt
+            with torch.cuda.device(dev):
+                evp, nev = (cast(_events[0], POINTER(c_void_p)), _events[1]) if _events is not None else (None, 0)
+                _lib.check(L.emavfi_forward_adaptive(C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(), f1.data_ptr(),
+                                                     f2.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, dt, taps_arg, None,
+                                                     evp, nev, state.data_ptr(), enter, leave, _lib._stream()), "emavfi_forward_adaptive")
+            # (route None: the route of each block is in the state, pack_census / pack_routes read it there)
+            self._last_call = (dev, torch.cuda.current_stream(dev).cuda_stream, B, H, W, dt, nws, ws.data_ptr(), None)
         elif self._pack_policy != "window":
             nws = L.emavfi_workspace_bytes(C, self.mid_channels, self.num_blocks, B, H, W, dt)
             if nws == 0:
@@ -399,7 +519,8 @@ class EMA_VFI(nn.Module):
         samples_outside_window, samples_outside_share, abs_offset_px_max}, or None for a block that ran other kernels (fp32 / autocast
         modes, other widths).  The reference bounds its offsets nowhere (ema_vfi.py:55-60); the kernel's staged window holds offsets up
         to +-2 px beyond the tap and pays for every (4 x 16 pixels, tap) group with a sample outside it.  Every row also says which
-        kernel the block ran ("route": "window" | "gather", pack_policy); both count the same thing.  One blocking D2H copy."""
+        kernel the block ran ("route": "window" | "gather": pack_policy, or under pack_adapt the route the state says ran); both
+        count the same thing.  One blocking D2H copy (two under pack_adapt)."""
         last = getattr(self, "_last_call", None)
         if last is None:
             raise RuntimeError("EMA_VFI.pack_census: no one-sequence forward has run yet")
@@ -415,6 +536,8 @@ class EMA_VFI(nn.Module):
             _lib.check(_lib.load().emavfi_forward_census(self.in_channels, self.mid_channels, self.num_blocks, B, H, W, dt, ws.data_ptr(), ws.numel(),
                                                          out.data_ptr(), _lib._stream()), "emavfi_forward_census")
         rows = _lib._census_rows(out, B * H * W * 9)
+        if gmask is None:   # an adaptive forward: the ran mask of this stream's route state
+            gmask = int(self._route_states[(dev.index, stream)][3].item())
         for i, row in enumerate(rows):
             if row is not None:
                 row["route"] = "gather" if (gmask >> i) & 1 else "window"
