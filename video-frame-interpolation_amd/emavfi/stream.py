@@ -32,9 +32,13 @@ What changes is how the work is scheduled, not what is computed:
 identical prediction by recursive midpoints: factor 1 -> [1/2]; factor 3 -> [1/4, 1/2, 3/4]; factor 7 -> eighths.
 ``reference_quirks=False`` drops the de-normalisation of the already-[0,1] model output (appendix A of
 SURVEY.md) and passes source frames through untouched; order and counts stay the same.
+``numa="auto"`` (opt-in) places the host side of the harness on the CPUs of the device's NUMA node (``dist.numa_plan``): the
+staging pool's threads bind themselves to them, and the pinned buffers are allocated and first touched from one of those threads.
+Frames are the same either way.
 """
 from __future__ import annotations
 
+import os
 from typing import Iterable, Iterator, List, Optional
 
 import numpy as np
@@ -45,13 +49,16 @@ from . import lib as _lib
 
 class FrameInterpolator:
     def __init__(self, model, interpolation_factor: int = 1, frame_interval: int = 1, batch_pairs: int = 8,
-                 reference_quirks: bool = True, mode: str = "reference", device=None, copy_out: bool = True, zero_copy: bool = False):
+                 reference_quirks: bool = True, mode: str = "reference", device=None, copy_out: bool = True, zero_copy: bool = False,
+                 numa: str = "off"):
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
             raise ValueError("interpolation_factor >= 0, frame_interval >= 1, batch_pairs >= 1 required")
         if mode not in ("reference", "recursive"):
             raise ValueError("mode must be 'reference' (the reference's repeated identical prediction) or 'recursive'")
         if mode == "recursive" and (interpolation_factor + 1) & interpolation_factor:
             raise ValueError("recursive midpoints need interpolation_factor = 2^k - 1 (1, 3, 7, ...)")
+        if numa not in ("off", "auto"):
+            raise ValueError("numa must be 'off' or 'auto'")
         self.model = model
         self.factor = int(interpolation_factor)
         self.interval = int(frame_interval)
@@ -69,6 +76,12 @@ class FrameInterpolator:
         self.copy_out = bool(copy_out)
         # True: the round-1..4 transport (the pre / post kernels read / write the pinned host buffers in place) instead of SDMA copies
         self.zero_copy = bool(zero_copy)
+        # "auto": the device's NUMA plan, computed once (None when "off"); its `bind` flag says whether the host work is placed
+        if numa == "auto":
+            from .dist import numa_plan
+            self.numa = numa_plan(self.device)
+        else:
+            self.numa = None
 
     # ---- the reference's frame selection (inference.py:158-201), as (pairs, tail) over frame indices
     @staticmethod
@@ -136,10 +149,16 @@ class FrameInterpolator:
         self._shape = shape
         self._slots = []
         for _ in range(2):
+            if self._bound():
+                # pinned and first touched on a thread of the device's node (on the hosts measured the runtime already put pinned
+                # pages on the GPU's node whichever CPU asked: profiles/r09_numa_stream_ab.md)
+                pinned = self._copy_pool().submit(self._pinned_local, [(2 * nb, H, W, C), (nb * nout, H, W, C), (nb, H, W, C)]).result()
+            else:
+                pinned = [torch.empty(2 * nb, H, W, C, dtype=torch.uint8).pin_memory(),
+                          torch.empty(nb * nout, H, W, C, dtype=torch.uint8).pin_memory(),
+                          torch.empty(nb, H, W, C, dtype=torch.uint8).pin_memory()]
             self._slots.append({
-                "h_in": torch.empty(2 * nb, H, W, C, dtype=torch.uint8).pin_memory(),
-                "h_pred": torch.empty(nb * nout, H, W, C, dtype=torch.uint8).pin_memory(),
-                "h_src": torch.empty(nb, H, W, C, dtype=torch.uint8).pin_memory(),
+                "h_in": pinned[0], "h_pred": pinned[1], "h_src": pinned[2],
                 "x": torch.empty(2 * nb, C, H, W, dtype=torch.float32, device=self.device),
                 # device-side images of the three pinned buffers (the SDMA copies' other end)
                 "d_in": torch.empty(2 * nb, H, W, C, dtype=torch.uint8, device=self.device),
@@ -156,9 +175,32 @@ class FrameInterpolator:
         self._post = _lib.side_stream(self.device, which=3, priority=-1)
 
     _pool = None
+    _bound_pools = {}   # (node, cpus) -> a pool whose threads run on those CPUs only; the unbound pool above stays as it is
 
-    @classmethod
-    def _copy_pool(cls):
+    def _bound(self):
+        return self.numa is not None and self.numa["bind"]
+
+    @staticmethod
+    def _pinned_local(shapes):
+        bufs = [torch.empty(s, dtype=torch.uint8, pin_memory=True) for s in shapes]
+        for b in bufs:
+            b.numpy().fill(0)     # first touch, on this (bound) thread
+        return bufs
+
+    @staticmethod
+    def _bind_thread(cpus):
+        os.sched_setaffinity(0, cpus)   # pid 0: the calling thread (a new pool worker), not the process
+
+    def _copy_pool(self):
+        cls = type(self)
+        if self._bound():
+            key = (self.numa["numa_node"], tuple(self.numa["cpus"]))
+            pool = cls._bound_pools.get(key)
+            if pool is None:
+                from concurrent.futures import ThreadPoolExecutor
+                pool = cls._bound_pools[key] = ThreadPoolExecutor(max_workers=8, thread_name_prefix=f"emavfi-stage-n{key[0]}",
+                                                                  initializer=cls._bind_thread, initargs=(key[1],))
+            return pool
         if cls._pool is None:
             from concurrent.futures import ThreadPoolExecutor
             cls._pool = ThreadPoolExecutor(max_workers=8, thread_name_prefix="emavfi-stage")
