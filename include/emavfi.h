@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -170,25 +170,10 @@ int emavfi_forward(int in_channels, int mid_channels, int num_blocks, const void
  * emavfi_forward_launches enumerates the kernel launches one forward enqueues, in order: returns
  * their number (also when capacity == 0), and for capacity >= that number fills `names`
  * (newline-separated, "kernel<instantiation> reference-layer"), and each launch's ALGORITHMIC
- * flops and bytes (real, unpadded channels; every tensor touched once).
- * emavfi_forward_profiled is emavfi_forward with launch i bracketed by hipEventRecord on
- * events[2i] / events[2i+1] (caller-created hipEvent_t, timing enabled) on `stream`. */
+ * flops and bytes (real, unpadded channels; every tensor touched once).  emavfi_forward_routed
+ * below brackets these launches with events. */
 int emavfi_forward_launches(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype,
                             char *names, size_t names_bytes, double *flops, double *bytes, int capacity);
-/* emavfi_forward with STAGE events, for a caller that pipelines pieces of a batch over several streams (frame pairs are
- * independent, ema_vfi.py:110-147 has no cross-sample op; emavfi/model.py, EMAVFI_PIPELINE): `stage_events` is NULL or three
- * caller-created hipEvent_t (any may be NULL), recorded on `stream` behind
- *   [0] the front of the forward - feature extraction, context encoding, motion estimation, warp (ema_vfi.py:112-130),
- *   [1] the last attention block (:136-138),   [2] the reconstruction (:144-146; the forward's last launch).
- * `events` / `n_events` as in emavfi_forward_profiled, or NULL / 0.  No `taps`. */
-int emavfi_forward_staged(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes,
-                          const float *frame1, const float *frame2, float *out,
-                          void *workspace, size_t workspace_bytes,
-                          int B, int H, int W, int dtype, void *const *stage_events, void *const *events, int n_events, void *stream);
-int emavfi_forward_profiled(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes,
-                            const float *frame1, const float *frame2, float *out,
-                            void *workspace, size_t workspace_bytes,
-                            int B, int H, int W, int dtype, void *const *events, int n_events, void *stream);
 
 /* Per-block route of the 16-bit attention blocks.  The one-launch pack exists as two kernels with the same operands,
  * weights (the blob and emavfi_layout_tag() do not change) and output:
@@ -198,10 +183,19 @@ int emavfi_forward_profiled(int in_channels, int mid_channels, int num_blocks, c
  *                        does not depend on the offsets.  Bit-identical to the window route wherever that one's census shows no fix-up group.
  * The gather route exists exactly where the one-launch pack runs (EMAVFI_BF16 / EMAVFI_F16 at mid_channels + 3 = 65..67); fp32,
  * EMAVFI_AMP16, EMAVFI_F32X3 and other widths refuse it with EMAVFI_E_UNSUPPORTED.  Workspace sizes are the same for both routes.
- * emavfi_forward_routed: the union of emavfi_forward / _staged / _profiled (`taps`, `stage_events`, `events` may each be NULL) plus
- * `gather_blocks`: bit i routes attention block i to EMAVFI_ROUTE_GATHER; bits at or above num_blocks are EMAVFI_E_ARG.  Mask 0 is
- * emavfi_forward exactly (same launches, same results).  emavfi_forward_launches_routed lists the launches of such a forward: a
- * gathered block's launch is named "deform_gather<...> offset_conv+dcn_v2", a windowed one "deform<...> offset_conv+dcn_v2". */
+ * emavfi_forward_routed: emavfi_forward (`taps` may be NULL) plus
+ *   `events` / `n_events`  NULL (n_events ignored), or caller-created hipEvent_t (timing enabled) with n_events >= 2, else EMAVFI_E_ARG:
+ *                          launch i of emavfi_forward_launches_routed's list is bracketed by hipEventRecord on events[2i] / events[2i+1]
+ *                          on `stream` (the launches with 2i + 1 >= n_events are not bracketed);
+ *   `stage_events`         NULL or three caller-created hipEvent_t (any may be NULL), for a caller that pipelines pieces of a batch over
+ *                          several streams (frame pairs are independent, ema_vfi.py:110-147 has no cross-sample op; emavfi/model.py,
+ *                          EMAVFI_PIPELINE), recorded on `stream` behind
+ *                            [0] the front of the forward - feature extraction, context encoding, motion estimation, warp (ema_vfi.py:112-130),
+ *                            [1] the last attention block (:136-138),   [2] the reconstruction (:144-146; the forward's last launch);
+ *   `gather_blocks`        bit i routes attention block i to EMAVFI_ROUTE_GATHER; bits at or above num_blocks are EMAVFI_E_ARG.
+ * With NULL events and mask 0 it is emavfi_forward exactly (same launches, same results).  emavfi_forward_launches_routed lists the
+ * launches of such a forward: a gathered block's launch is named "deform_gather<...> offset_conv+dcn_v2", a windowed one
+ * "deform<...> offset_conv+dcn_v2". */
 #define EMAVFI_ROUTE_WINDOW 0
 #define EMAVFI_ROUTE_GATHER 1
 int emavfi_forward_routed(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes,
@@ -301,14 +295,12 @@ int emavfi_deform_conv2d(const float *x, const float *offset, const float *mask,
 size_t emavfi_mdcn_workspace_bytes(int B, int C, int H, int W, int dtype, int flags);
 int emavfi_mdcn(const float *x, const float *offset_weight, const float *offset_bias, const float *dcn_weight, const float *dcn_bias,
                 float *y, int B, int C, int H, int W, int dtype, int flags, void *workspace, size_t workspace_bytes, void *stream);
-/* Measurement hook: emavfi_mdcn with the stage's own launches (one in the 16-bit modes at C = 67, else two) bracketed by
- * hipEventRecord on events[2i] / events[2i+1]; the layout conversions around them are not bracketed (bench.py's
- * also_pack_vs_offset_spread: what the dominant kernel costs when the offsets leave its staged window). */
-int emavfi_mdcn_profiled(const float *x, const float *offset_weight, const float *offset_bias, const float *dcn_weight, const float *dcn_bias,
-                         float *y, int B, int C, int H, int W, int dtype, int flags, void *workspace, size_t workspace_bytes,
-                         void *const *events, int n_events, void *stream);
-/* emavfi_mdcn / emavfi_mdcn_profiled with a route (EMAVFI_ROUTE_WINDOW | EMAVFI_ROUTE_GATHER, see emavfi_forward_routed); `events` may be
- * NULL.  All flag combinations of the one-launch pack are valid on both routes; emavfi_mdcn_census reads either route's counters. */
+/* emavfi_mdcn with a route (EMAVFI_ROUTE_WINDOW | EMAVFI_ROUTE_GATHER, see emavfi_forward_routed) and a measurement hook: `events` is
+ * NULL, or n_events >= 2 caller-created hipEvent_t (else EMAVFI_E_ARG) and the stage's own launches (one in the 16-bit modes at C = 67,
+ * else two) are bracketed by hipEventRecord on events[2i] / events[2i+1]; the layout conversions around them are not bracketed
+ * (bench.py's also_pack_vs_offset_spread: what the dominant kernel costs when the offsets leave its staged window).  The window route
+ * with NULL events is emavfi_mdcn exactly.  All flag combinations of the one-launch pack are valid on both routes; emavfi_mdcn_census
+ * reads either route's counters. */
 int emavfi_mdcn_routed(const float *x, const float *offset_weight, const float *offset_bias, const float *dcn_weight, const float *dcn_bias,
                        float *y, int B, int C, int H, int W, int dtype, int flags, int route, void *workspace, size_t workspace_bytes,
                        void *const *events, int n_events, void *stream);

@@ -3,7 +3,7 @@
 // guards of the forward / stage entries, the blob header check on host memory, the switch word.  No kernel is launched and no GPU
 // is needed; the library is built with -fsanitize=address,undefined (csrc/Makefile, target `asan`) and this program with it, so
 // plan building, workspace carving, string handling and the guards run under ASan + UBSan on the CPU box.
-// Test infrastructure: tests/test_cabi_cpu.py::test_host_side_runs_clean_under_asan_ubsan builds and runs it.
+// Test infrastructure: tests/test_cabi_cpu.py::test_host_check_runs_clean_under_asan_ubsan builds and runs it.
 #include "../../include/emavfi.h"
 
 #include <cstdint>
@@ -101,11 +101,13 @@ int main()
     CHECK(emavfi_forward(3, 64, 3, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 8, 8, EMAVFI_F32, nullptr, nullptr) == EMAVFI_E_ARG);
     CHECK(emavfi_forward(3, 65, 3, fake, 0, ff, ff, fo, fake, 0, 1, 8, 8, EMAVFI_F32, nullptr, nullptr) == EMAVFI_E_UNSUPPORTED);
     void *evs[2] = {nullptr, nullptr};
-    CHECK(emavfi_forward_profiled(3, 64, 3, fake, 0, ff, ff, fo, fake, 0, 1, 8, 8, EMAVFI_F32, nullptr, 0, nullptr) == EMAVFI_E_ARG);
-    CHECK(emavfi_forward_profiled(3, 64, 3, nullptr, 0, ff, ff, fo, fake, 0, 1, 8, 8, EMAVFI_F32, evs, 2, nullptr) == EMAVFI_E_ARG);
-    // the staged form (round 5): the same guards with stage / launch events present or absent
-    CHECK(emavfi_forward_staged(3, 64, 3, nullptr, 0, ff, ff, fo, fake, 0, 1, 8, 8, EMAVFI_F32, nullptr, nullptr, 0, nullptr) == EMAVFI_E_ARG);
-    CHECK(emavfi_forward_staged(3, 64, 3, fake, 1000, ff, ff, fo, fake, (size_t)1 << 40, 1, 64, 64, EMAVFI_BF16, evs, evs, 2, nullptr) == EMAVFI_E_ARG);
+    // launch events: NULL = none; a non-NULL array with fewer than 2 events is refused
+    CHECK(emavfi_forward_routed(3, 64, 3, fake, 0, ff, ff, fo, fake, 0, 1, 8, 8, EMAVFI_F32, nullptr, nullptr, evs, 0, 0u, nullptr) == EMAVFI_E_ARG);
+    CHECK(emavfi_forward_routed(3, 64, 3, fake, 0, ff, ff, fo, fake, 0, 1, 8, 8, EMAVFI_F32, nullptr, nullptr, evs, 1, 0u, nullptr) == EMAVFI_E_ARG);
+    CHECK(emavfi_forward_routed(3, 64, 3, nullptr, 0, ff, ff, fo, fake, 0, 1, 8, 8, EMAVFI_F32, nullptr, nullptr, evs, 2, 0u, nullptr) == EMAVFI_E_ARG);
+    // the same guards with stage / launch events present or absent
+    CHECK(emavfi_forward_routed(3, 64, 3, nullptr, 0, ff, ff, fo, fake, 0, 1, 8, 8, EMAVFI_F32, nullptr, nullptr, nullptr, 0, 0u, nullptr) == EMAVFI_E_ARG);
+    CHECK(emavfi_forward_routed(3, 64, 3, fake, 1000, ff, ff, fo, fake, (size_t)1 << 40, 1, 64, 64, EMAVFI_BF16, nullptr, evs, evs, 2, 0u, nullptr) == EMAVFI_E_ARG);
     CHECK(strstr(emavfi_last_error(), "packed blob has 1000 bytes") != nullptr);
     CHECK(emavfi_warp(nullptr, nullptr, nullptr, 1, 3, 8, 8, nullptr) == EMAVFI_E_ARG);
     CHECK(emavfi_warp(ff, ff, fo, 0, 3, 8, 8, nullptr) == EMAVFI_E_ARG);
@@ -135,8 +137,9 @@ int main()
     CHECK(emavfi_mdcn_workspace_bytes(1, 67, 32, 32, EMAVFI_F32, EMAVFI_MDCN_IN_F16) == 0 && emavfi_mdcn_workspace_bytes(1, 67, 32, 32, EMAVFI_BF16, 8) == 0);
     CHECK(emavfi_mdcn(nullptr, ff, ff, ff, ff, fo, 1, 67, 8, 8, EMAVFI_BF16, 0, fake, 0, nullptr) == EMAVFI_E_ARG);
     CHECK(emavfi_mdcn(ff, ff, ff, ff, nullptr, fo, 1, 67, 8, 8, EMAVFI_BF16, 0, fake, 16, nullptr) == EMAVFI_E_WORKSPACE);
-    CHECK(emavfi_mdcn_profiled(ff, ff, ff, ff, ff, fo, 1, 67, 8, 8, EMAVFI_BF16, 0, fake, 16, nullptr, 0, nullptr) == EMAVFI_E_ARG);
-    CHECK(emavfi_mdcn_profiled(ff, ff, ff, ff, nullptr, fo, 1, 67, 8, 8, EMAVFI_BF16, 0, fake, 16, evs, 2, nullptr) == EMAVFI_E_WORKSPACE);
+    CHECK(emavfi_mdcn_routed(ff, ff, ff, ff, ff, fo, 1, 67, 8, 8, EMAVFI_BF16, 0, EMAVFI_ROUTE_WINDOW, fake, 16, evs, 0, nullptr) == EMAVFI_E_ARG);
+    CHECK(emavfi_mdcn_routed(ff, ff, ff, ff, ff, fo, 1, 67, 8, 8, EMAVFI_BF16, 0, EMAVFI_ROUTE_WINDOW, fake, 16, evs, 1, nullptr) == EMAVFI_E_ARG);
+    CHECK(emavfi_mdcn_routed(ff, ff, ff, ff, nullptr, fo, 1, 67, 8, 8, EMAVFI_BF16, 0, EMAVFI_ROUTE_WINDOW, fake, 16, evs, 2, nullptr) == EMAVFI_E_WORKSPACE);
     for (int dt : dtypes) CHECK(emavfi_context_workspace_bytes(2, 64, 75, 131, dt) > 0 && emavfi_reconstruct_workspace_bytes(2, 8, 23, 37, dt) > 0);
     CHECK(emavfi_context_workspace_bytes(1, 7, 32, 32, EMAVFI_BF16) == 0 && emavfi_reconstruct_workspace_bytes(0, 64, 32, 32, EMAVFI_BF16) == 0);
     {

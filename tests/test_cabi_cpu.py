@@ -569,7 +569,7 @@ def test_switch_word_is_latched_and_settable():
     assert lib.debug_switches() == old
 
 
-def test_host_side_runs_clean_under_asan_ubsan():
+def test_host_check_runs_clean_under_asan_ubsan():
     """SURVEY.md section 5 (sanitizers) / VERDICT r3 item 9: `make asan` builds libemavfi_asan.so with AddressSanitizer +
     UndefinedBehaviorSanitizer in every HOST pass (the gfx950 device code stays uninstrumented: GPU ASan / XNACK do not exist on this
     pool) and tests/host/host_check, which drives every entry that works or refuses on the host: plan building for every model /

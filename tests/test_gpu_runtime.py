@@ -1,6 +1,7 @@
 """Host-side contracts of the drop-in boundary on a real GPU (SURVEY.md section 8b "re-entrant ... safe for one
 process per GPU", 8e "one weight broadcast, shards equal the single-GPU result"): per-stream workspaces, captured
 graphs surviving workspace growth, installed (broadcast) weight blobs, and a two-process shard run."""
+import ctypes
 import os
 import subprocess
 import sys
@@ -343,7 +344,7 @@ def test_foreign_blob_is_refused_or_poisoned():
 @pytest.mark.parametrize("pieces,stagger", [(2, 0), (4, 0), (3, 1), (2, -1)])
 def test_pipelined_forward_is_bit_identical(dtype, pieces, stagger):
     """VERDICT r4 item 1: the batch as `pieces` slices pipelined over the caller's stream and a side stream (EMA_VFI.pipeline;
-    emavfi_forward_staged records the stage event that releases the next piece) - frame pairs are independent (ema_vfi.py:110-147 has
+    emavfi_forward_routed records the stage event that releases the next piece) - frame pairs are independent (ema_vfi.py:110-147 has
     no cross-sample op) and every kernel is batch-invariant per sample, so the frame must equal the one-sequence forward BIT FOR BIT,
     also on a non-default caller stream, for an uneven split (B = 5) and when the same model runs twice back to back (event reuse)."""
     sd = synth.synthetic_state_dict(seed=0)
@@ -370,3 +371,26 @@ def test_pipelined_forward_is_bit_identical(dtype, pieces, stagger):
     torch.cuda.synchronize()
     assert torch.equal(got, ref) and torch.equal(again, ref) and torch.equal(on_side, ref)
     assert torch.isfinite(ref).all()
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp32"])
+def test_launch_events_keep_the_taps(dtype):
+    """_events (bench.py's per-launch event pairs) only adds event records: under pack_policy="window" the frame and every tap of
+    model(..., return_taps=True, _events=...) equal those of the same call without events, bit for bit (that call once went through an
+    entry without taps and returned them unfilled)."""
+    sd = synth.synthetic_state_dict(seed=0)
+    m = make_model(sd, dtype=dtype)
+    m.pack_policy = "window"
+    B, H, W = 2, 64, 96
+    f1, f2 = (t.to(DEV) for t in synth.synthetic_frames(5, B, H, W, "natural"))
+    n = 2 * len(lib.forward_launches(3, 64, 3, B, H, W, dtype))
+    with torch.cuda.device(DEV):
+        evs = (ctypes.c_void_p * n)(*[lib.hip().event(("test_launch_events_keep_the_taps", i)).value for i in range(n)])
+    with torch.no_grad():
+        ref, ref_taps = m(f1, f2, return_taps=True)
+        got, got_taps = m(f1, f2, return_taps=True, _events=(ctypes.cast(evs, ctypes.c_void_p), n))
+    torch.cuda.synchronize()
+    assert torch.equal(got, ref) and torch.isfinite(ref).all()
+    assert list(got_taps) == list(ref_taps)
+    for name, t in ref_taps.items():
+        assert torch.isfinite(t).all() and torch.equal(got_taps[name], t), name

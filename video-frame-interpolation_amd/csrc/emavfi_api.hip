@@ -438,10 +438,16 @@ unsigned long long *debug_stamp_buffer()
 }
 #endif
 
+// Which kernel runs a one-launch pack: EMAVFI_ROUTE_WINDOW (deform_pack3_kernel), EMAVFI_ROUTE_GATHER (deform_gather3_kernel: same
+// operands, same output, no window) or kRouteAdaptive (the routed pack, deform_route3.inl, reading the route word `word`:
+// emavfi_forward_adaptive).  The two non-window kinds exist only where require_gather_route() holds.
+constexpr int kRouteAdaptive = 2;
+struct PackRoute { int kind = EMAVFI_ROUTE_WINDOW; const unsigned *word = nullptr; };
+
 int run_deform(const Plan &P, const Layer &L, const void *packed, const void *x, int x_ps, float *om, void *out,
                int out_ps, int cstore, int B, int H, int W, hipStream_t s, const void *zeros = nullptr, const Layer *off = nullptr,
                const void *x_tail = nullptr, int tail_ps = 0, int force_dtype = -1, int in_f16 = 0, int out_f16 = 0, void *out16 = nullptr, int out16_ps = 0,
-               unsigned *census = nullptr, int out16_lo_off = 0, bool gather = false, const unsigned *route = nullptr)
+               unsigned *census = nullptr, int out16_lo_off = 0, PackRoute route = {})
 {
     const int kd = force_dtype >= 0 ? force_dtype : P.dtype;
     DeformParams d{};
@@ -460,7 +466,7 @@ int run_deform(const Plan &P, const Layer &L, const void *packed, const void *x,
     d.x_ps = x_ps; d.out_ps = out_ps; d.H = H; d.W = W; d.B = B; d.cstore = cstore; d.cin_real = L.cin_take; d.ck = L.ck; d.nf = L.nf;
     d.cout_real = L.cout; d.pack3 = L.pack3; d.in_f16 = in_f16; d.out_f16 = out_f16;
     d.out16 = out16; d.out16_ps = out16_ps;
-    if (route) d.route = route;   // (shares out16's bytes: the routed pack has no fp16 side output)
+    if (route.kind == kRouteAdaptive) d.route = route.word;   // (shares out16's bytes: the routed pack has no fp16 side output)
 #if defined(EMAVFI_DEFORM_STAMPS) && EMAVFI_DEFORM_STAMPS
     {   // diagnostic build: EMAVFI_STAMP_PACK=i records only the i-th deformable launch of every 3 (default: every launch,
         // i.e. what is read back is the last pack of a forward)
@@ -477,10 +483,10 @@ int run_deform(const Plan &P, const Layer &L, const void *packed, const void *x,
         for (int i = 1; i < atoi(rep); ++i)
             if (const int rc = kd == EMAVFI_F32 ? launch_deform_f32(d, s) : kd == EMAVFI_F16 ? launch_deform_f16(d, s) : launch_deform_bf16(d, s)) return rc;
 #endif
-    // the routed pack (deform_route3.inl): the route word at `route` picks the window or the gather body; 16-bit kinds only
-    if (route) return kd == EMAVFI_F16 ? launch_deform_routed_f16(d, s) : kd == EMAVFI_BF16 ? launch_deform_routed_bf16(d, s) : -2;
+    // the routed pack (deform_route3.inl): the route word picks the window or the gather body; 16-bit kinds only
+    if (route.kind == kRouteAdaptive) return kd == EMAVFI_F16 ? launch_deform_routed_f16(d, s) : kd == EMAVFI_BF16 ? launch_deform_routed_bf16(d, s) : -2;
     // the window-free route of the one-launch pack (deform_gather3.inl): 16-bit kinds only, -2 (no instantiation) for anything else
-    if (gather) return kd == EMAVFI_F16 ? launch_deform_gather_f16(d, s) : kd == EMAVFI_BF16 ? launch_deform_gather_bf16(d, s) : -2;
+    if (route.kind == EMAVFI_ROUTE_GATHER) return kd == EMAVFI_F16 ? launch_deform_gather_f16(d, s) : kd == EMAVFI_BF16 ? launch_deform_gather_bf16(d, s) : -2;
     return kd == EMAVFI_F32 ? launch_deform_f32(d, s) : kd == EMAVFI_F16 ? launch_deform_f16(d, s) : launch_deform_bf16(d, s);
 }
 
@@ -561,15 +567,24 @@ struct Recorder {
     void *const *events = nullptr;           // 2 per launch: start, stop
     int n_events = 0, idx = 0;
     bool dry = false;                        // enumerate only, launch nothing
-    void *const *stage_events = nullptr;     // emavfi_forward_staged: up to 3 hipEvent_t recorded behind the front / the attention blocks / the reconstruction
+    void *const *stage_events = nullptr;     // up to 3 hipEvent_t recorded behind the front / the attention blocks / the reconstruction
 };
 
-// records stage event i of a staged forward on the launch stream (no-op for every other entry)
-#define EMAVFI_STAGE_EVENT(rec, i)                                                                              \
-    do {                                                                                                        \
-        if (!(rec).dry && (rec).stage_events && (rec).stage_events[i] &&                                        \
-            hipEventRecord((hipEvent_t)(rec).stage_events[i], s) != hipSuccess)                                 \
-            return fail(EMAVFI_E_LAUNCH, "forward_staged: hipEventRecord of stage event %d failed", (int)(i));  \
+// the one rule for the per-launch events of every entry that takes them: NULL = none; a non-NULL array needs n_events >= 2
+int set_events(Recorder &rec, void *const *events, int n_events, const char *what)
+{
+    if (events && n_events < 2) return fail(EMAVFI_E_ARG, "%s: events given, n_events must be >= 2", what);
+    rec.events = events;
+    rec.n_events = events ? n_events : 0;
+    return EMAVFI_OK;
+}
+
+// records stage event i of a forward on the launch stream (no-op without stage events)
+#define EMAVFI_STAGE_EVENT(rec, i)                                                                       \
+    do {                                                                                                 \
+        if (!(rec).dry && (rec).stage_events && (rec).stage_events[i] &&                                 \
+            hipEventRecord((hipEvent_t)(rec).stage_events[i], s) != hipSuccess)                          \
+            return fail(EMAVFI_E_LAUNCH, "forward: hipEventRecord of stage event %d failed", (int)(i));  \
     } while (0)
 
 const char *dtype_name(int dtype) { return dtype == EMAVFI_F32 ? "f32" : dtype == EMAVFI_F16 ? "f16" : "bf16"; }
@@ -633,45 +648,35 @@ bool pack_f16_link(const Plan &P, int i)
 // Whether block i may take the window-free route (deform_gather3.inl): exactly where the one-launch pack runs in the deform_pack3 layout
 // (16-bit modes at the reference width); fp32, EMAVFI_AMP16, EMAVFI_F32X3 and other widths keep their kernels
 bool pack_gather_ok(const Plan &P, int i) { return pack_fuses(P, i) && P.dcn[i].pack3 == 1; }
+// the one check that block i has the gather route (and with it the routed pack) in this plan
+int require_gather_route(const Plan &P, int i, const char *what)
+{
+    if (pack_gather_ok(P, i)) return EMAVFI_OK;
+    return fail(EMAVFI_E_UNSUPPORTED, "%s: attention block %d has no gather route in this mode (the one-launch pack of the 16-bit modes at the reference width only)",
+                what, i);
+}
 // 16-bit / fp32 models: x -> y (channels-last, pixel stride P.fps).  x_tail: the compact tail buffer (kTailPs channels per pixel) the first pack takes channels
-// 64.. from (or null); in_f16 / out_f16: the bf16 model's f16 hand-off (DeformParams).  route: EMAVFI_ROUTE_WINDOW (deform_pack3_kernel) or
-// EMAVFI_ROUTE_GATHER (deform_gather3_kernel: same operands, same output, no window - refused where pack_gather_ok does not hold) or
-// kRouteAdaptive (the routed pack, deform_route3.inl, reading the route word `route_word`: emavfi_forward_adaptive)
-constexpr int kRouteAdaptive = 2;
+// 64.. from (or null); in_f16 / out_f16: the bf16 model's f16 hand-off (DeformParams).  route: the kernel of the one-launch pack (PackRoute)
 int attention_block(const Plan &P, int i, const void *packed, const void *x, void *y, float *om, const void *x_tail, int in_f16, int out_f16,
-                    int B, int H, int W, hipStream_t s, Recorder &rec, unsigned *census = nullptr, int route = EMAVFI_ROUTE_WINDOW,
-                    const unsigned *route_word = nullptr)
+                    int B, int H, int W, hipStream_t s, Recorder &rec, unsigned *census = nullptr, PackRoute route = {})
 {
     const double px = (double)B * H * W, e = P.esize, cf = P.mid + 3;
     double fl, by;
     conv_work(P, P.off[i], B, H, W, 4.0, fl, by);
-    if (route == kRouteAdaptive) {
-        if (!pack_gather_ok(P, i)) return fail(EMAVFI_E_UNSUPPORTED, "attention block %d: the routed pack exists only where the one-launch pack runs", i);
-        char nm[96];
-        snprintf(nm, sizeof nm, "deform_routed<%s,ck=%d,nf=%d> offset_conv+dcn_v2", dtype_name(P.dtype), P.dcn[i].ck, P.dcn[i].nf);
-        // (the window route's algorithmic work: which body runs is decided on the device)
-        EMAVFI_STEP(rec, nm, fl + 2.0 * 9.0 * cf * cf * px, px * (2.0 * cf * e) + 9.0 * cf * (cf + 27.0) * e,
-                    run_deform(P, P.dcn[i], packed, x, P.fps, om, y, P.fps, P.fps, B, H, W, s, nullptr, P.has_offh ? &P.offh[i] : &P.off[i], x_tail, kTailPs,
-                               -1, in_f16, out_f16, nullptr, 0, census, 0, false, route_word));
-        return EMAVFI_OK;
-    }
-    if (route == EMAVFI_ROUTE_GATHER) {
-        if (!pack_gather_ok(P, i)) return fail(EMAVFI_E_UNSUPPORTED, "attention block %d: the gather route exists only where the one-launch pack runs (16-bit modes at the reference width)", i);
-        char nm[96];
-        snprintf(nm, sizeof nm, "deform_gather<%s,ck=%d,nf=%d> offset_conv+dcn_v2", dtype_name(P.dtype), P.dcn[i].ck, P.dcn[i].nf);
-        // corner pieces from global memory: 9 taps x 4 corners x one 144-byte pixel per output pixel (L1 / L2 traffic, not HBM)
-        EMAVFI_STEP(rec, nm, fl + 2.0 * 9.0 * cf * cf * px, px * (2.0 * cf * e) + 9.0 * cf * (cf + 27.0) * e,
-                    run_deform(P, P.dcn[i], packed, x, P.fps, om, y, P.fps, P.fps, B, H, W, s, nullptr, P.has_offh ? &P.offh[i] : &P.off[i], x_tail, kTailPs,
-                               -1, in_f16, out_f16, nullptr, 0, census, 0, true));
-        return EMAVFI_OK;
-    }
-    if (route != EMAVFI_ROUTE_WINDOW) return fail(EMAVFI_E_ARG, "attention block %d: unknown route %d", i, route);
+    if (route.kind != EMAVFI_ROUTE_WINDOW && route.kind != EMAVFI_ROUTE_GATHER && route.kind != kRouteAdaptive)
+        return fail(EMAVFI_E_ARG, "attention block %d: unknown route %d", i, route.kind);
+    if (route.kind != EMAVFI_ROUTE_WINDOW)
+        if (const int rc = require_gather_route(P, i, "attention block"); rc != EMAVFI_OK) return rc;
     if (pack_fuses(P, i)) {
         // one launch for the whole pack (ema_vfi.py:54-60): offset_conv on the staged window, then the DCN;
-        // the input is read once and the offsets / masks never leave the registers
-        EMAVFI_STEP(rec, deform_name(P, P.dcn[i]) + " offset_conv+dcn_v2", fl + 2.0 * 9.0 * cf * cf * px, px * (2.0 * cf * e) + 9.0 * cf * (cf + 27.0) * e,
+        // the input is read once and the offsets / masks never leave the registers.  Every route is listed with the window
+        // kernel's algorithmic work (the gather kernel's corner reads are L1 / L2 traffic, not HBM; the routed kernel picks its body on the device)
+        static const char *const kPrefix[] = {"deform<", "deform_gather<", "deform_routed<"};
+        char nm[96];
+        snprintf(nm, sizeof nm, "%s%s,ck=%d,nf=%d> offset_conv+dcn_v2", kPrefix[route.kind], dtype_name(P.dtype), P.dcn[i].ck, P.dcn[i].nf);
+        EMAVFI_STEP(rec, nm, fl + 2.0 * 9.0 * cf * cf * px, px * (2.0 * cf * e) + 9.0 * cf * (cf + 27.0) * e,
                     run_deform(P, P.dcn[i], packed, x, P.fps, om, y, P.fps, P.fps, B, H, W, s, nullptr, P.has_offh ? &P.offh[i] : &P.off[i], x_tail, kTailPs,
-                               -1, in_f16, out_f16, nullptr, 0, census));
+                               -1, in_f16, out_f16, nullptr, 0, census, 0, route));
     } else {
         if (x_tail || in_f16 || out_f16) return fail(EMAVFI_E_UNSUPPORTED, "attention block: split tail / f16 hand-off need the one-launch pack kernel");
         EMAVFI_STEP(rec, conv_name(P, P.off[i]) + " offset_conv", fl, by, run_conv(P, P.off[i], packed, x, P.fps, H, W, om, 32, 0, 32, EPI_OM, B, s));
@@ -783,15 +788,16 @@ BlobHeader expected_header(const Plan &P, int requested_dtype)
     return h;
 }
 
-// emavfi_forward_adaptive's part of a forward: the route state (device, include/emavfi.h) and the hysteresis thresholds
-struct Adapt { bool on = false; unsigned *state = nullptr; float enter = 0.0f, leave = 0.0f; };
+// The pack routes of one forward: the per-block gather mask (emavfi_forward_routed) or, adaptive, the route state (device,
+// include/emavfi.h; null when only enumerating) and the hysteresis thresholds (emavfi_forward_adaptive)
+struct Routes { unsigned gather_mask = 0; bool adaptive = false; unsigned *state = nullptr; float enter = 0.0f, leave = 0.0f; };
 // all (wave, tap) groups of one one-launch pack: the census denominator (emavfi_forward_census, route_select)
 static unsigned long long pack3_wave_taps(int B, int H, int W) { return (unsigned long long)B * ((H + 15) / 16) * ((W + 15) / 16) * 4ull * 9ull; }
 // a forward in this mode has routed packs: every block runs the one-launch pack of the deform_pack3 layout (16-bit modes at the
 // reference width; not EMAVFI_AMP16 / EMAVFI_F32X3, whose blocks run the fp32-family DCN)
 static bool adaptive_applies(const Plan &P)
 {
-    if (P.amp || P.nb < 1) return false;
+    if (P.nb < 1) return false;
     for (int i = 0; i < P.nb; ++i)
         if (!pack_gather_ok(P, i)) return false;
     return true;
@@ -799,18 +805,19 @@ static bool adaptive_applies(const Plan &P)
 
 int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes, const float *frame1,
                  const float *frame2, float *out, void *workspace, size_t workspace_bytes, int B, int H, int W, int dtype,
-                 float *const *taps, void *stream, Recorder &rec, unsigned gather_blocks = 0, const Adapt &adapt = Adapt{})
+                 float *const *taps, void *stream, Recorder &rec, const Routes &routes = Routes{})
 {
     Plan P;
     if (!build_plan(P, in_channels, mid_channels, num_blocks, dtype)) return fail(EMAVFI_E_UNSUPPORTED, "%s", P.why);
     // emavfi_forward_adaptive: every block of a mode with the one-launch pack runs the routed pack; elsewhere it is emavfi_forward
-    const bool adaptive = adapt.on && adaptive_applies(P);
+    const bool adaptive = routes.adaptive && adaptive_applies(P);
     // per-block route (emavfi_forward_routed): bit i sends attention block i to the window-free kernel
-    if (P.nb < 32 && (gather_blocks >> P.nb) != 0u)
-        return fail(EMAVFI_E_ARG, "forward: gather_blocks 0x%x names blocks at or above num_blocks = %d", gather_blocks, P.nb);
+    const unsigned gather_mask = routes.gather_mask;
+    if (P.nb < 32 && (gather_mask >> P.nb) != 0u)
+        return fail(EMAVFI_E_ARG, "forward: gather_blocks 0x%x names blocks at or above num_blocks = %d", gather_mask, P.nb);
     for (int i = 0; i < P.nb; ++i)
-        if (((gather_blocks >> i) & 1u) && (P.amp || !pack_gather_ok(P, i)))
-            return fail(EMAVFI_E_UNSUPPORTED, "forward: attention block %d has no gather route in this mode (the one-launch pack of the 16-bit modes at the reference width only)", i);
+        if ((gather_mask >> i) & 1u)
+            if (const int rc = require_gather_route(P, i, "forward"); rc != EMAVFI_OK) return rc;
     const int requested_dtype = dtype;
     dtype = P.dtype;  // the kernel storage type from here on (EMAVFI_AMP16 -> EMAVFI_F16, with P.amp set)
     if (B < 1 || H < 1 || W < 1) return fail(EMAVFI_E_ARG, "forward: B, H, W must be >= 1 (got %d, %d, %d)", B, H, W);
@@ -992,11 +999,11 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
 
         // --- multi-attention fusion: num_blocks x ModulatedDeformConvPack, no activation (ema_vfi.py:136-138)
         for (int i = 0; i < P.nb; ++i) {
+            const PackRoute route = adaptive ? PackRoute{kRouteAdaptive, routes.state ? routes.state + 8 + i : nullptr}
+                                             : PackRoute{((gather_mask >> i) & 1u) ? EMAVFI_ROUTE_GATHER : EMAVFI_ROUTE_WINDOW};
             if (const int rc = attention_block(P, i, packed, x, y, f.om, i == 0 && split_tail ? f.in16 : nullptr,
                                                (i == 0 ? feat16 : pack_f16_link(P, i - 1)) ? 1 : 0, pack_f16_link(P, i) ? 1 : 0, B, H, W, s, rec,
-                                               rec.dry ? nullptr : f.census + (size_t)i * DEFORM_CENSUS_SLOTS * 4,
-                                               adaptive ? kRouteAdaptive : ((gather_blocks >> i) & 1u) ? EMAVFI_ROUTE_GATHER : EMAVFI_ROUTE_WINDOW,
-                                               adaptive ? adapt.state + 8 + i : nullptr);
+                                               rec.dry ? nullptr : f.census + (size_t)i * DEFORM_CENSUS_SLOTS * 4, route);
                 rc != EMAVFI_OK)
                 return rc;
             if (!rec.dry && taps && taps[5 + i])
@@ -1008,7 +1015,7 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
             unsigned long long totals[kMaxBlocks] = {};
             for (int i = 0; i < P.nb; ++i) totals[i] = pack3_wave_taps(B, H, W);
             EMAVFI_STEP(rec, "route_select", 0.0, (double)P.nb * kCensusBlock + 128.0,
-                        launch_route_select(f.census, adapt.state, P.nb, totals, adapt.enter, adapt.leave, EMAVFI_ROUTE_MAGIC, s));
+                        launch_route_select(f.census, routes.state, P.nb, totals, routes.enter, routes.leave, EMAVFI_ROUTE_MAGIC, s));
         }
     }
 
@@ -1181,40 +1188,17 @@ int emavfi_forward(int in_channels, int mid_channels, int num_blocks, const void
                         dtype, taps, stream, rec);
 }
 
-int emavfi_forward_profiled(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes, const float *frame1,
-                            const float *frame2, float *out, void *workspace, size_t workspace_bytes, int B, int H, int W,
-                            int dtype, void *const *events, int n_events, void *stream)
-{
-    if (!events || n_events < 2) return fail(EMAVFI_E_ARG, "forward_profiled: events array required");
-    Recorder rec;
-    rec.events = events; rec.n_events = n_events;
-    return forward_impl(in_channels, mid_channels, num_blocks, packed, packed_bytes, frame1, frame2, out, workspace, workspace_bytes, B, H, W,
-                        dtype, nullptr, stream, rec);
-}
-
-int emavfi_forward_staged(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes, const float *frame1,
-                          const float *frame2, float *out, void *workspace, size_t workspace_bytes, int B, int H, int W, int dtype,
-                          void *const *stage_events, void *const *events, int n_events, void *stream)
-{
-    Recorder rec;
-    rec.stage_events = stage_events;
-    if (events) { rec.events = events; rec.n_events = n_events; }
-    return forward_impl(in_channels, mid_channels, num_blocks, packed, packed_bytes, frame1, frame2, out, workspace, workspace_bytes, B, H, W,
-                        dtype, nullptr, stream, rec);
-}
-
 int emavfi_forward_routed(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes, const float *frame1,
                           const float *frame2, float *out, void *workspace, size_t workspace_bytes, int B, int H, int W, int dtype,
                           float *const *taps, void *const *stage_events, void *const *events, int n_events, unsigned gather_blocks, void *stream)
 {
     Recorder rec;
     rec.stage_events = stage_events;
-    if (events) {
-        if (n_events < 2) return fail(EMAVFI_E_ARG, "forward_routed: events given, n_events must be >= 2");
-        rec.events = events; rec.n_events = n_events;
-    }
+    if (const int rc = set_events(rec, events, n_events, "forward_routed"); rc != EMAVFI_OK) return rc;
+    Routes routes;
+    routes.gather_mask = gather_blocks;
     return forward_impl(in_channels, mid_channels, num_blocks, packed, packed_bytes, frame1, frame2, out, workspace, workspace_bytes, B, H, W,
-                        dtype, taps, stream, rec, gather_blocks);
+                        dtype, taps, stream, rec, routes);
 }
 
 int emavfi_forward_launches(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype,
@@ -1223,16 +1207,14 @@ int emavfi_forward_launches(int in_channels, int mid_channels, int num_blocks, i
     return emavfi_forward_launches_routed(in_channels, mid_channels, num_blocks, B, H, W, dtype, 0u, names, names_bytes, flops, bytes, capacity);
 }
 
-static int list_launches(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, unsigned gather_blocks, bool adaptive,
+static int list_launches(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, const Routes &routes,
                          char *names, size_t names_bytes, double *flops, double *bytes, int capacity)
 {
     std::vector<LaunchRec> recs;
     Recorder rec;
     rec.recs = &recs; rec.dry = true;
-    Adapt adapt;
-    adapt.on = adaptive;
     const int rc = forward_impl(in_channels, mid_channels, num_blocks, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, B, H, W,
-                                dtype, nullptr, nullptr, rec, gather_blocks, adapt);
+                                dtype, nullptr, nullptr, rec, routes);
     if (rc != EMAVFI_OK) return rc;
     const int n = (int)recs.size();
     if (capacity <= 0) return n;
@@ -1255,13 +1237,17 @@ static int list_launches(int in_channels, int mid_channels, int num_blocks, int 
 int emavfi_forward_launches_routed(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, unsigned gather_blocks,
                                    char *names, size_t names_bytes, double *flops, double *bytes, int capacity)
 {
-    return list_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, gather_blocks, false, names, names_bytes, flops, bytes, capacity);
+    Routes routes;
+    routes.gather_mask = gather_blocks;
+    return list_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, routes, names, names_bytes, flops, bytes, capacity);
 }
 
 int emavfi_forward_launches_adaptive(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype,
                                      char *names, size_t names_bytes, double *flops, double *bytes, int capacity)
 {
-    return list_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, 0u, true, names, names_bytes, flops, bytes, capacity);
+    Routes routes;
+    routes.adaptive = true;
+    return list_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, routes, names, names_bytes, flops, bytes, capacity);
 }
 
 // ---- adaptive per-block route (include/emavfi.h): the states emavfi_route_state_init wrote, by address -> num_blocks.  The forward
@@ -1304,14 +1290,11 @@ int emavfi_forward_adaptive(int in_channels, int mid_channels, int num_blocks, c
     }
     Recorder rec;
     rec.stage_events = stage_events;
-    if (events) {
-        if (n_events < 2) return fail(EMAVFI_E_ARG, "forward_adaptive: events given, n_events must be >= 2");
-        rec.events = events; rec.n_events = n_events;
-    }
-    Adapt adapt;
-    adapt.on = true; adapt.state = (unsigned *)route_state; adapt.enter = enter_share; adapt.leave = leave_share;
+    if (const int rc = set_events(rec, events, n_events, "forward_adaptive"); rc != EMAVFI_OK) return rc;
+    Routes routes;
+    routes.adaptive = true; routes.state = (unsigned *)route_state; routes.enter = enter_share; routes.leave = leave_share;
     return forward_impl(in_channels, mid_channels, num_blocks, packed, packed_bytes, frame1, frame2, out, workspace, workspace_bytes, B, H, W,
-                        dtype, taps, stream, rec, 0u, adapt);
+                        dtype, taps, stream, rec, routes);
 }
 
 int emavfi_warp(const float *frame2, const float *flow, float *out, int B, int C, int H, int W, void *stream)
@@ -1536,8 +1519,8 @@ static int mdcn_impl(const float *x, const float *offset_weight, const float *of
     bool split; int in_f16, out_f16;
     if (const int rc = mdcn_plan(P, C, dtype, flags, split, in_f16, out_f16); rc != EMAVFI_OK) return rc;
     if (route != EMAVFI_ROUTE_WINDOW && route != EMAVFI_ROUTE_GATHER) return fail(EMAVFI_E_ARG, "mdcn: unknown route %d", route);
-    if (route == EMAVFI_ROUTE_GATHER && (P.amp || !pack_gather_ok(P, 0)))
-        return fail(EMAVFI_E_UNSUPPORTED, "mdcn: the gather route exists only where the one-launch pack runs (16-bit modes, C = 65..67)");
+    if (route == EMAVFI_ROUTE_GATHER)
+        if (const int rc = require_gather_route(P, 0, "mdcn"); rc != EMAVFI_OK) return rc;
     if (!x || !offset_weight || !offset_bias || !dcn_weight || !y || !workspace) return fail(EMAVFI_E_ARG, "mdcn: null pointer");
     if (B < 1 || H < 1 || W < 1) return fail(EMAVFI_E_ARG, "mdcn: B, H, W must be >= 1");
     if (!aligned16(x) || !aligned16(y) || !aligned16(workspace)) return fail(EMAVFI_E_ARG, "mdcn: pointers must be 16-byte aligned");
@@ -1573,7 +1556,8 @@ static int mdcn_impl(const float *x, const float *offset_weight, const float *of
     } else {
         EMAVFI_TRY(launch_nchw_to_cl(x, m.xcl, B, C, H, W, P.fps, xdt, s), "mdcn layout in");
     }
-    if (const int rc = attention_block(P, 0, m.blob, m.xcl, m.ycl, m.om, m.tail, in_f16, out_f16, B, H, W, s, rec, m.census, route); rc != EMAVFI_OK) return rc;
+    if (const int rc = attention_block(P, 0, m.blob, m.xcl, m.ycl, m.om, m.tail, in_f16, out_f16, B, H, W, s, rec, m.census, PackRoute{route}); rc != EMAVFI_OK)
+        return rc;
     EMAVFI_TRY(launch_cl_to_nchw(m.ycl, y, B, C, H, W, P.fps, 0, ydt, s), "mdcn layout out");
     return EMAVFI_OK;
 }
@@ -1585,25 +1569,12 @@ int emavfi_mdcn(const float *x, const float *offset_weight, const float *offset_
     return mdcn_impl(x, offset_weight, offset_bias, dcn_weight, dcn_bias, y, B, C, H, W, dtype, flags, workspace, workspace_bytes, stream, rec);
 }
 
-int emavfi_mdcn_profiled(const float *x, const float *offset_weight, const float *offset_bias, const float *dcn_weight, const float *dcn_bias, float *y,
-                         int B, int C, int H, int W, int dtype, int flags, void *workspace, size_t workspace_bytes, void *const *events, int n_events,
-                         void *stream)
-{
-    if (!events || n_events < 2) return fail(EMAVFI_E_ARG, "mdcn_profiled: events array required");
-    Recorder rec;
-    rec.events = events; rec.n_events = n_events;
-    return mdcn_impl(x, offset_weight, offset_bias, dcn_weight, dcn_bias, y, B, C, H, W, dtype, flags, workspace, workspace_bytes, stream, rec);
-}
-
 int emavfi_mdcn_routed(const float *x, const float *offset_weight, const float *offset_bias, const float *dcn_weight, const float *dcn_bias, float *y,
                        int B, int C, int H, int W, int dtype, int flags, int route, void *workspace, size_t workspace_bytes, void *const *events,
                        int n_events, void *stream)
 {
     Recorder rec;
-    if (events) {
-        if (n_events < 2) return fail(EMAVFI_E_ARG, "mdcn_routed: events given, n_events must be >= 2");
-        rec.events = events; rec.n_events = n_events;
-    }
+    if (const int rc = set_events(rec, events, n_events, "mdcn_routed"); rc != EMAVFI_OK) return rc;
     return mdcn_impl(x, offset_weight, offset_bias, dcn_weight, dcn_bias, y, B, C, H, W, dtype, flags, workspace, workspace_bytes, stream, rec, route);
 }
 
@@ -1624,7 +1595,7 @@ int emavfi_forward_census(int in_channels, int mid_channels, int num_blocks, int
     carve_forward(P, ws, f, B, H, W);
     if (ws.used > workspace_bytes) return fail(EMAVFI_E_WORKSPACE, "forward_census: this forward's workspace has %zu bytes, got %zu", ws.used, workspace_bytes);
     unsigned long long totals[kMaxBlocks] = {};
-    for (int i = 0; i < P.nb; ++i) totals[i] = pack_fuses(P, i) && P.dcn[i].pack3 == 1 ? pack3_wave_taps(B, H, W) : 0ull;
+    for (int i = 0; i < P.nb; ++i) totals[i] = pack_gather_ok(P, i) ? pack3_wave_taps(B, H, W) : 0ull;
     EMAVFI_TRY(launch_census_reduce(f.census, out, P.nb, totals, (hipStream_t)stream), "forward_census");
     return EMAVFI_OK;
 }
@@ -1641,7 +1612,7 @@ int emavfi_mdcn_census(int B, int C, int H, int W, int dtype, int flags, const v
     mdcn_carve(P, ws, m, B, H, W, split);
     if (ws.used > workspace_bytes) return fail(EMAVFI_E_WORKSPACE, "mdcn_census: this stage's workspace has %zu bytes, got %zu", ws.used, workspace_bytes);
     unsigned long long totals[kMaxBlocks] = {};
-    totals[0] = pack_fuses(P, 0) && P.dcn[0].pack3 == 1 ? pack3_wave_taps(B, H, W) : 0ull;
+    totals[0] = pack_gather_ok(P, 0) ? pack3_wave_taps(B, H, W) : 0ull;
     EMAVFI_TRY(launch_census_reduce(m.census, out, 1, totals, (hipStream_t)stream), "mdcn_census");
     return EMAVFI_OK;
 }

@@ -39,8 +39,6 @@ _PROTOTYPES = {
     "emavfi_packed_check": (c_int, [c_int] * 4 + [c_void_p, c_size_t]),
     "emavfi_forward": (c_int, [c_int] * 3 + [c_void_p, c_size_t] + [c_void_p] * 4 + [c_size_t] + [c_int] * 4 + [POINTER(c_void_p), c_void_p]),
     "emavfi_forward_launches": (c_int, [c_int] * 7 + [c_char_p, c_size_t, POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int]),
-    "emavfi_forward_profiled": (c_int, [c_int] * 3 + [c_void_p, c_size_t] + [c_void_p] * 4 + [c_size_t] + [c_int] * 4 + [POINTER(c_void_p), c_int, c_void_p]),
-    "emavfi_forward_staged": (c_int, [c_int] * 3 + [c_void_p, c_size_t] + [c_void_p] * 4 + [c_size_t] + [c_int] * 4 + [POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p]),
     "emavfi_warp": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),
     "emavfi_preprocess_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
     "emavfi_postprocess_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int, c_void_p]),
@@ -50,7 +48,6 @@ _PROTOTYPES = {
     "emavfi_deform_conv2d": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
     "emavfi_mdcn_workspace_bytes": (c_size_t, [c_int] * 6),
     "emavfi_mdcn": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
-    "emavfi_mdcn_profiled": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p, c_size_t, POINTER(c_void_p), c_int, c_void_p]),
     "emavfi_forward_census": (c_int, [c_int] * 7 + [c_void_p, c_size_t, c_void_p, c_void_p]),
     "emavfi_mdcn_census": (c_int, [c_int] * 6 + [c_void_p, c_size_t, c_void_p, c_void_p]),
     "emavfi_forward_routed": (c_int, [c_int] * 3 + [c_void_p, c_size_t] + [c_void_p] * 4 + [c_size_t] + [c_int] * 4
@@ -149,6 +146,12 @@ def dtype_code(name) -> int:
 def _stream():
     import torch
     return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _events_arg(_events):
+    """The `_events` measurement argument (bench.py): (c_void_p to an array of hipEvent_t, count) or None -> the C-ABI's
+    (events, n_events)."""
+    return (ctypes.cast(_events[0], POINTER(c_void_p)), _events[1]) if _events is not None else (None, 0)
 
 
 def _require_cuda(*tensors):
@@ -351,10 +354,10 @@ ROUTES = {"window": 0, "gather": 1}   # include/emavfi.h: EMAVFI_ROUTE_WINDOW / 
 
 def mdcn(x, offset_weight, offset_bias, dcn_weight, dcn_bias, dtype="fp32", flags=0, _events=None, route="window"):
     """ModulatedDeformConvPack.forward (reference ema_vfi.py:53-60) as ONE stage, routed as a block of the forward is
-    (include/emavfi.h, emavfi_mdcn): the one-launch kernel in the 16-bit modes at the reference width.
-    `_events` (bench.py): (ctypes array of hipEvent_t, count) bracketing the stage's own launches (emavfi_mdcn_profiled).
-    `route`: "window" (deform_pack3_kernel, the default) or "gather" (the window-free kernel, emavfi_mdcn_routed; 16-bit modes at
-    C = 65..67 only - elsewhere the C error is raised)."""
+    (include/emavfi.h, emavfi_mdcn_routed): the one-launch kernel in the 16-bit modes at the reference width.
+    `_events` (bench.py): (ctypes array of hipEvent_t, count) bracketing the stage's own launches.
+    `route`: "window" (deform_pack3_kernel, the default) or "gather" (the window-free kernel; 16-bit modes at C = 65..67 only -
+    elsewhere the C error is raised)."""
     if route not in ROUTES:
         raise ValueError(f"mdcn: route must be one of {sorted(ROUTES)}, got {route!r}")
     import torch
@@ -371,19 +374,11 @@ def mdcn(x, offset_weight, offset_bias, dcn_weight, dcn_bias, dtype="fp32", flag
         raise RuntimeError(f"emavfi_mdcn: {last_error()}")
     ws = workspace(n, x.device)
     y = torch.empty_like(x)
+    ev, nev = _events_arg(_events)
     with torch.cuda.device(x.device):
-        if route != "window":
-            ev, nev = (ctypes.cast(_events[0], POINTER(c_void_p)), _events[1]) if _events is not None else (None, 0)
-            check(L.emavfi_mdcn_routed(x.data_ptr(), ow.data_ptr(), ob.data_ptr(), dw.data_ptr(), db.data_ptr() if db is not None else None,
-                                       y.data_ptr(), B, C, H, W, dt, flags, ROUTES[route], ws.data_ptr(), ws.numel(), ev, nev, _stream()),
-                  "emavfi_mdcn_routed")
-        elif _events is not None:
-            check(L.emavfi_mdcn_profiled(x.data_ptr(), ow.data_ptr(), ob.data_ptr(), dw.data_ptr(), db.data_ptr() if db is not None else None,
-                                         y.data_ptr(), B, C, H, W, dt, flags, ws.data_ptr(), ws.numel(), ctypes.cast(_events[0], POINTER(c_void_p)),
-                                         _events[1], _stream()), "emavfi_mdcn_profiled")
-        else:
-            check(L.emavfi_mdcn(x.data_ptr(), ow.data_ptr(), ob.data_ptr(), dw.data_ptr(), db.data_ptr() if db is not None else None, y.data_ptr(),
-                                B, C, H, W, dt, flags, ws.data_ptr(), ws.numel(), _stream()), "emavfi_mdcn")
+        check(L.emavfi_mdcn_routed(x.data_ptr(), ow.data_ptr(), ob.data_ptr(), dw.data_ptr(), db.data_ptr() if db is not None else None,
+                                   y.data_ptr(), B, C, H, W, dt, flags, ROUTES[route], ws.data_ptr(), ws.numel(), ev, nev, _stream()),
+              "emavfi_mdcn_routed")
     return y
 
 
@@ -466,18 +461,17 @@ def forward_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, gath
     dt = dtype_code(dtype)
     if adaptive and gather_blocks:
         raise ValueError("forward_launches: adaptive and gather_blocks exclude each other")
+    model = (in_channels, mid_channels, num_blocks, B, H, W, dt)
     if adaptive:
-        entry, what = L.emavfi_forward_launches_adaptive, "emavfi_forward_launches_adaptive"
-    elif gather_blocks:
-        entry, what = (lambda *a: L.emavfi_forward_launches_routed(*a[:7], gather_blocks, *a[7:])), "emavfi_forward_launches_routed"
+        entry, what, args = L.emavfi_forward_launches_adaptive, "emavfi_forward_launches_adaptive", model
     else:
-        entry, what = L.emavfi_forward_launches, "emavfi_forward_launches"
-    n = entry(in_channels, mid_channels, num_blocks, B, H, W, dt, None, 0, None, None, 0)
+        entry, what, args = L.emavfi_forward_launches_routed, "emavfi_forward_launches_routed", model + (gather_blocks,)
+    n = entry(*args, None, 0, None, None, 0)
     if n < 0:
         raise RuntimeError(f"{what}: {last_error()}")
     names = ctypes.create_string_buffer(128 * n)
     fl, by = (ctypes.c_double * n)(), (ctypes.c_double * n)()
-    check(min(0, entry(in_channels, mid_channels, num_blocks, B, H, W, dt, names, len(names), fl, by, n)), what)
+    check(min(0, entry(*args, names, len(names), fl, by, n)), what)
     labels = names.value.decode().strip().split("\n")
     return [(labels[i], fl[i], by[i]) for i in range(n)]
 

@@ -25,6 +25,7 @@ import tempfile
 from collections import OrderedDict
 import ctypes
 from ctypes import POINTER, c_void_p, cast
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -37,6 +38,19 @@ PACK_POLICIES = ("window", "gather")
 # EMA_VFI.pack_adapt's (enter, leave) fix-up shares for EMAVFI_PACK_ADAPT=1: the crossover measured for one block at B = 8 x 720p
 # (profiles/r07_gather_route_kill.md) plus hysteresis
 PACK_ADAPT_DEFAULT = (0.75, 0.65)
+
+
+class _LastCall(NamedTuple):
+    """The last one-sequence forward of an EMA_VFI: what pack_census() / pack_routes() read back."""
+    device: torch.device
+    stream: int                  # the HIP stream handle it ran on
+    B: int
+    H: int
+    W: int
+    dtype: int
+    ws_bytes: int
+    ws_ptr: int                  # its workspace (the census lives there)
+    gather_mask: Optional[int]   # emavfi_forward_routed's mask, or None: an adaptive forward (the routes are in the route state)
 
 
 def parse_pack_adapt(value):
@@ -408,16 +422,15 @@ class EMA_VFI(nn.Module):
         forward measured and the route changes since the state was (re)set - or None for a block without a routed pack (fp32 / autocast
         modes, other widths).  One blocking D2H copy."""
         last = getattr(self, "_last_call", None)
-        if last is None or last[8] is not None:
+        if last is None or last.gather_mask is not None:
             raise RuntimeError("EMA_VFI.pack_routes: no adaptive one-sequence forward has run yet")
-        dev, stream, B, H, W, dt = last[:6]
-        if torch.cuda.current_stream(dev).cuda_stream != stream:
+        if torch.cuda.current_stream(last.device).cuda_stream != last.stream:
             raise RuntimeError("EMA_VFI.pack_routes: call it on the stream the forward ran on")
         routed = any(n.startswith("deform_routed") for n, _, _ in
-                     _lib.forward_launches(self.in_channels, self.mid_channels, self.num_blocks, B, H, W, dt, adaptive=True))
+                     _lib.forward_launches(self.in_channels, self.mid_channels, self.num_blocks, last.B, last.H, last.W, last.dtype, adaptive=True))
         if not routed:
             return [None] * self.num_blocks
-        w = self._route_states[(dev.index, stream)].cpu()
+        w = self._route_states[(last.device.index, last.stream)].cpu()
         ran, share, sw = int(w[3]), w[16:24].view(torch.float32), w[24:32]
         name = ("window", "gather")
         return [{"ran": name[(ran >> i) & 1], "next": name[int(w[8 + i]) & 1], "fixup_share": float(share[i]), "switches": int(sw[i])}
@@ -461,50 +474,13 @@ class EMA_VFI(nn.Module):
             pieces = 1   # a slice of the batch must start 16-byte aligned (include/emavfi.h): odd sample sizes run as one sequence
         if self._pack_adapt is not None:
             pieces = 1   # one route state per stream, one census per forward: the adaptive forward runs as one sequence
-        gmask = (1 << self.num_blocks) - 1 if self._pack_policy == "gather" else 0
+            gmask = None
+        else:
+            gmask = (1 << self.num_blocks) - 1 if self._pack_policy == "gather" else 0
         if pieces >= 2 and not return_taps and not torch.cuda.is_current_stream_capturing():
             self._forward_pipelined(L, packed, f1, f2, out, dt, pieces, _events, gmask)
-        elif self._pack_adapt is not None:
-            state = self._route_state(dev)
-            nws = L.emavfi_workspace_bytes(C, self.mid_channels, self.num_blocks, B, H, W, dt)
-            if nws == 0:
-                raise RuntimeError(f"EMA_VFI: {_lib.last_error()}")
-            ws = _lib.workspace(nws, dev)
-            enter, leave = self._pack_adapt
-            with torch.cuda.device(dev):
-                evp, nev = (cast(_events[0], POINTER(c_void_p)), _events[1]) if _events is not None else (None, 0)
-                _lib.check(L.emavfi_forward_adaptive(C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(), f1.data_ptr(),
-                                                     f2.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, dt, taps_arg, None,
-                                                     evp, nev, state.data_ptr(), enter, leave, _lib._stream()), "emavfi_forward_adaptive")
-            # (route None: the route of each block is in the state, pack_census / pack_routes read it there)
-            self._last_call = (dev, torch.cuda.current_stream(dev).cuda_stream, B, H, W, dt, nws, ws.data_ptr(), None)
-        elif self._pack_policy != "window":
-            nws = L.emavfi_workspace_bytes(C, self.mid_channels, self.num_blocks, B, H, W, dt)
-            if nws == 0:
-                raise RuntimeError(f"EMA_VFI: {_lib.last_error()}")
-            ws = _lib.workspace(nws, dev)
-            with torch.cuda.device(dev):
-                evp, nev = (cast(_events[0], POINTER(c_void_p)), _events[1]) if _events is not None else (None, 0)
-                _lib.check(L.emavfi_forward_routed(C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(), f1.data_ptr(),
-                                                   f2.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, dt, taps_arg, None,
-                                                   evp, nev, gmask, _lib._stream()), "emavfi_forward_routed")
-            self._last_call = (dev, torch.cuda.current_stream(dev).cuda_stream, B, H, W, dt, nws, ws.data_ptr(), gmask)
         else:
-            nws = L.emavfi_workspace_bytes(C, self.mid_channels, self.num_blocks, B, H, W, dt)
-            if nws == 0:
-                raise RuntimeError(f"EMA_VFI: {_lib.last_error()}")
-            ws = _lib.workspace(nws, dev)
-            with torch.cuda.device(dev):
-                if _events is not None:  # bench.py: (ctypes array of hipEvent_t, count) bracketing every launch
-                    _lib.check(L.emavfi_forward_profiled(C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(), f1.data_ptr(),
-                                                         f2.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, dt,
-                                                         cast(_events[0], POINTER(c_void_p)), _events[1], _lib._stream()),
-                               "emavfi_forward_profiled")
-                else:
-                    _lib.check(L.emavfi_forward(C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(), f1.data_ptr(),
-                                                f2.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, dt, taps_arg,
-                                                _lib._stream()), "emavfi_forward")
-            self._last_call = (dev, torch.cuda.current_stream(dev).cuda_stream, B, H, W, dt, nws, ws.data_ptr(), 0)
+            self._last_call = self._launch(L, packed, f1, f2, out, dt, gmask, taps_arg, None, _events)
         # under autocast the reference's reconstruction tail is fp16, so its frame is an fp16 tensor (the values computed
         # here are fp16-representable: the conversion is exact)
         out = out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
@@ -524,24 +500,47 @@ class EMA_VFI(nn.Module):
         last = getattr(self, "_last_call", None)
         if last is None:
             raise RuntimeError("EMA_VFI.pack_census: no one-sequence forward has run yet")
-        dev, stream, B, H, W, dt, nws, ws_ptr, gmask = last
+        dev, stream, B, H, W = last.device, last.stream, last.B, last.H, last.W
         if torch.cuda.current_stream(dev).cuda_stream != stream:
             raise RuntimeError("EMA_VFI.pack_census: call it on the stream the forward ran on")
-        ws = _lib.workspace(nws, dev)
-        if ws.data_ptr() != ws_ptr:
+        ws = _lib.workspace(last.ws_bytes, dev)
+        if ws.data_ptr() != last.ws_ptr:
             # the stream's workspace was replaced (a larger forward ran since): the counters of that forward are gone
             raise RuntimeError("EMA_VFI.pack_census: the workspace of the last forward has been replaced since; run the forward again")
         out = torch.zeros(self.num_blocks, 4, dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().emavfi_forward_census(self.in_channels, self.mid_channels, self.num_blocks, B, H, W, dt, ws.data_ptr(), ws.numel(),
-                                                         out.data_ptr(), _lib._stream()), "emavfi_forward_census")
+            _lib.check(_lib.load().emavfi_forward_census(self.in_channels, self.mid_channels, self.num_blocks, B, H, W, last.dtype, ws.data_ptr(),
+                                                         ws.numel(), out.data_ptr(), _lib._stream()), "emavfi_forward_census")
         rows = _lib._census_rows(out, B * H * W * 9)
+        gmask = last.gather_mask
         if gmask is None:   # an adaptive forward: the ran mask of this stream's route state
             gmask = int(self._route_states[(dev.index, stream)][3].item())
         for i, row in enumerate(rows):
             if row is not None:
                 row["route"] = "gather" if (gmask >> i) & 1 else "window"
         return rows
+
+    def _launch(self, L, packed, f1, f2, out, dt, gather_mask, taps=None, stage=None, _events=None):
+        """One forward of f1 / f2 into `out` on the current stream of their device: emavfi_forward_routed with `gather_mask`, or
+        emavfi_forward_adaptive when it is None (pack_adapt).  taps / stage: the C-ABI's tap and stage-event pointer arrays or None;
+        _events: (hipEvent_t array, count) or None.  Returns the call's _LastCall."""
+        B, C, H, W = f1.shape
+        dev = f1.device
+        state = self._route_state(dev) if gather_mask is None else None
+        nws = L.emavfi_workspace_bytes(C, self.mid_channels, self.num_blocks, B, H, W, dt)
+        if nws == 0:
+            raise RuntimeError(f"EMA_VFI: {_lib.last_error()}")
+        ws = _lib.workspace(nws, dev)
+        evp, nev = _lib._events_arg(_events)
+        args = (C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(), f1.data_ptr(), f2.data_ptr(), out.data_ptr(),
+                ws.data_ptr(), ws.numel(), B, H, W, dt, taps, stage, evp, nev)
+        with torch.cuda.device(dev):
+            if state is not None:
+                enter, leave = self._pack_adapt
+                _lib.check(L.emavfi_forward_adaptive(*args, state.data_ptr(), enter, leave, _lib._stream()), "emavfi_forward_adaptive")
+            else:
+                _lib.check(L.emavfi_forward_routed(*args, gather_mask, _lib._stream()), "emavfi_forward_routed")
+        return _LastCall(dev, torch.cuda.current_stream(dev).cuda_stream, B, H, W, dt, nws, ws.data_ptr(), gather_mask)
 
     def _forward_pipelined(self, L, packed, f1, f2, out, dt, pieces, _events=None, gather_blocks=0):
         """The batch as `pieces` contiguous slices alternating between the caller's stream and one side stream, piece k + 1 starting
@@ -583,24 +582,9 @@ class EMA_VFI(nn.Module):
                         hip.wait(s, front_prev)
                     front = hip.event(key + ("stage", k))
                     with torch.cuda.stream(s):
-                        nws = L.emavfi_workspace_bytes(C, self.mid_channels, self.num_blocks, b1 - b0, H, W, dt)
-                        if nws == 0:
-                            raise RuntimeError(f"EMA_VFI: {_lib.last_error()}")
-                        ws = _lib.workspace(nws, dev)
                         stage = (c_void_p * 3)(*[front if i == self.pipeline_stagger else None for i in range(3)])
-                        evp = None
-                        if _events is not None:
-                            evp = cast(c_void_p(_events[0].value + k * per * ctypes.sizeof(c_void_p)), POINTER(c_void_p))
-                        if gather_blocks:
-                            _lib.check(L.emavfi_forward_routed(C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(),
-                                                               f1[b0:b1].data_ptr(), f2[b0:b1].data_ptr(), out[b0:b1].data_ptr(), ws.data_ptr(),
-                                                               ws.numel(), b1 - b0, H, W, dt, None, cast(stage, POINTER(c_void_p)), evp, per,
-                                                               gather_blocks, c_void_p(s.cuda_stream)), "emavfi_forward_routed")
-                        else:
-                            _lib.check(L.emavfi_forward_staged(C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(),
-                                                               f1[b0:b1].data_ptr(), f2[b0:b1].data_ptr(), out[b0:b1].data_ptr(), ws.data_ptr(), ws.numel(),
-                                                               b1 - b0, H, W, dt, cast(stage, POINTER(c_void_p)), evp, per, c_void_p(s.cuda_stream)),
-                                       "emavfi_forward_staged")
+                        ev = (c_void_p(_events[0].value + k * per * ctypes.sizeof(c_void_p)), per) if _events is not None else None
+                        self._launch(L, packed, f1[b0:b1], f2[b0:b1], out[b0:b1], dt, gather_blocks, None, cast(stage, POINTER(c_void_p)), ev)
                     front_prev = front if self.pipeline_stagger >= 0 else None
             finally:
                 # also when a piece failed to enqueue: `out` and the frames are known to the caching allocator on the caller's stream
