@@ -1,0 +1,441 @@
+"""The convolution kernels gated PER ELEMENT against a float64 reference and the rounding model of tests/rounding_model.py (the
+kind of gate tests/test_gpu_mdcn.py has for the pack): operands pre-rounded to what the kernel stores, biases fp32, and per case
+  * bound: max(err / bound) <= 1.0 with bound = conv_bound(...) - derived there, nothing tuned;
+  * nearest rounding: at most 2 % of the elements differ from the storage rounding of the float64 value (the project's figure for
+    "rare last-place roundings only", tests/test_gpu_parity.py; the CPU's fp32 order is at <= 0.4 %), and every such element is ONE
+    unit in the last place away (plus floor(d / unit) where the terms cancel to a result whose unit is below the accumulation
+    term d: rounding_model.exact_match_share) - the gate that sees a truncating store where delta dominates the bound;
+  * finite, right shape.
+Every family conv_geometry() (video-frame-interpolation_amd/csrc/emavfi_api.hip) can select is run in bf16, fp16 and - where the family exists there - fp32, at the
+shapes where it changes behaviour.  The stage entry emavfi_conv3x3 reads the layout switches per call and reports no kernel name, so
+the family a case runs is asserted against family_of() below, a restatement of conv_geometry() + launch_conv16 / launch_conv_mfma16
+(csrc/conv3x3.inl, same directory): a case that drifts to another family fails before it runs.  Two entries of the families' table are NOT what their
+channel counts suggest: 67 -> 27 in the 16-bit types runs the 32x32x16 PERSISTENT kernel (conv3x3_persist_kernel<80, 1, 8>), and
+64 -> 2 with activation `none` through the stage entry runs conv3x3_persist16_kernel<64, 1, 2> - conv_light's 64-channel form needs
+the planar epilogue, which the stage entry selects for tanh01 only (in the forward the flow head is fused into conv_ring.inl).
+
+To keep the file's wall time the activations (`none`, `relu`) ALTERNATE over a channel pair's shapes instead of both running at every
+shape: an edge shape is seen under one activation per channel pair.  NOT run as single layers: conv_light's 64-channel planar form
+(the stage entry offers the planar epilogue with tanh01 for <= 4 outputs of 32 inputs only; it is the unfused flow head of the
+forward, compared there with the fused one by tests/test_gpu_parity.py) and the 16-bit CK = 80 tile kernel (67 -> 64 with
+EMAVFI_CONV_RING=0).
+
+Known answers with zero tolerance (weight packing and tap geometry): rounding_model.impulse_case, per family.
+Kernels that exist only inside a stage or the forward - conv_first.inl, conv_ring_first.inl, conv_ring2.inl (the `feat` tap), the fused
+tail conv_ring_tail.inl (lib.reconstruct), conv_wreg's fused tile-sum pool (lib.context), the fused flow head of conv_ring.inl (the `flow`
+tap) - are gated LAYER BY LAYER: the same layers are run one at a time through lib.conv3x3, every one against the single-layer model on
+the GPU's own previous output, and the stage's result is then held to the single-layer model of its LAST layer on the GPU's own
+intermediate (see layered_chain)."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from emavfi import EMA_VFI, lib, synth
+from rounding_model import (MISMATCH_CAP, U32, chain_bound, conv_model, quantum, conv_weights, exact_match_share, impulse_case, scaled_input, storage_round)
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ACT = {"none": lib.ACT_NONE, "relu": lib.ACT_RELU, "tanh01": lib.ACT_TANH01}
+ALL_SWITCHES = ("EMAVFI_CONV_MFMA16", "EMAVFI_CONV_RING", "EMAVFI_CONV_S2RING", "EMAVFI_CONV_WREG")
+
+
+def family_of(cin, cout, stride, dtype, env, act="none"):
+    """conv_geometry() + the 16-bit launcher restated: which kernel family emavfi_conv3x3 runs."""
+    on = lambda name: env.get(name, "1") != "0"
+    if dtype == "fp32":
+        return "tile"
+    pad, frags = (cin + 15) // 16 * 16, (cout + 31) // 32
+    if stride == 2 and pad == 64 and frags == 4 and on("EMAVFI_CONV_S2RING"):
+        return "s2ring"
+    if stride == 1 and 32 < cout <= 64 and 64 <= cin <= 67 and on("EMAVFI_CONV_RING"):
+        return "ring2" if cin == 64 else "ring3"
+    if 224 < cout <= 256 and pad >= 128 and on("EMAVFI_CONV_WREG") and pad % (64 if stride == 1 else 32) == 0:
+        return "wreg"
+    if stride == 2:
+        return "tile"
+    ck = pad if pad <= 80 else 64
+    nf = 4 if frags % 4 == 0 else (2 if frags % 2 == 0 else 1)
+    single = pad // ck == 1 and frags // nf == 1
+    if single and ck == 64 and nf in (1, 2) and on("EMAVFI_CONV_MFMA16"):
+        return "persist16"
+    if single and ck == 32 and nf == 1 and cout <= 4 and on("EMAVFI_CONV_MFMA16") and act == "tanh01":
+        return "light"
+    if single and (ck, nf) in ((64, 2), (64, 1), (80, 1)):
+        return "persist32"
+    return "tile"
+
+
+RING_SHAPES = [(1, 61), (2, 62), (3, 63), (17, 124), (17, 125)]   # widths around the 62-column strip pitch; heights 1, 2, 3, 17
+RING_SHAPES_B = [(1, 125), (2, 124), (3, 61), (17, 62), (17, 63)]   # the same widths and heights paired the other way round
+TILE_SHAPES = [(1, 1), (1, 70), (70, 1), (5, 7), (33, 47)]                                                           # tile remainders in both directions
+P16_SHAPES = [(16, 32), (17, 33), (75, 131)]
+NO_RING = {"EMAVFI_CONV_RING": "0"}
+OLD32 = {"EMAVFI_CONV_MFMA16": "0"}
+OLD32_NO_RING = {"EMAVFI_CONV_MFMA16": "0", "EMAVFI_CONV_RING": "0"}
+# family -> (dtypes, [(env, Cin, Cout, stride, shapes, activations cycled over the shapes)])
+FAMILIES = {
+    "tile": (("fp32", "bf16", "fp16"), [({}, 6, 64, 1, TILE_SHAPES, ("relu", "none")), ({}, 8, 8, 1, TILE_SHAPES, ("none", "relu")),
+                                        ({}, 8, 16, 2, TILE_SHAPES, ("relu", "none")), ({}, 11, 27, 1, TILE_SHAPES, ("none", "relu")),
+                                        ({}, 35, 32, 1, TILE_SHAPES, ("relu", "none")),
+                                        ({"EMAVFI_CONV_WREG": "0"}, 128, 256, 2, [(1, 5), (5, 7), (33, 47)], ("relu", "none"))]),
+    "tile_fp32_only": (("fp32",), [({}, 64, 64, 1, [(5, 7), (33, 47)], ("relu", "none")), ({}, 67, 64, 1, [(1, 70), (33, 47)], ("none", "relu")),
+                                   ({}, 64, 128, 2, [(33, 47)], ("relu",)), ({}, 32, 3, 1, [(1, 7), (21, 45)], ("tanh01",))]),
+    "persist16": (("bf16", "fp16"), [({}, 64, 32, 1, P16_SHAPES, ("relu", "none")), ({}, 64, 24, 1, P16_SHAPES, ("none", "relu")),
+                                     ({}, 64, 2, 1, P16_SHAPES, ("none",)), (NO_RING, 64, 64, 1, P16_SHAPES, ("relu", "none")),
+                                     (NO_RING, 64, 40, 1, P16_SHAPES[1:], ("none", "relu"))]),
+    "persist32": (("bf16", "fp16"), [(OLD32, 64, 32, 1, P16_SHAPES, ("relu", "none")), (OLD32, 64, 24, 1, P16_SHAPES[:2], ("none", "relu")),
+                                     (OLD32, 64, 2, 1, P16_SHAPES[1:], ("none",)), (OLD32_NO_RING, 64, 64, 1, P16_SHAPES, ("relu", "none")),
+                                     (OLD32_NO_RING, 64, 40, 1, P16_SHAPES[:2], ("none", "relu")), ({}, 67, 27, 1, TILE_SHAPES, ("none", "relu"))]),
+    "ring2": (("bf16", "fp16"), [({}, 64, 64, 1, RING_SHAPES + [(360, 64)], ("relu", "none")), ({}, 64, 48, 1, RING_SHAPES_B, ("none", "relu")),
+                                 ({}, 64, 33, 1, RING_SHAPES_B[2:], ("relu", "none"))]),
+    "ring3": (("bf16", "fp16"), [({}, 65, 64, 1, RING_SHAPES_B[:3], ("none", "relu")), ({}, 66, 40, 1, RING_SHAPES_B, ("relu", "none")),
+                                 ({}, 67, 64, 1, RING_SHAPES + [(360, 64)], ("relu", "none"))]),
+    "s2ring": (("bf16", "fp16"), [({}, 64, 128, 2, [(1, 7), (37, 53), (36, 52), (37, 52), (36, 53)], ("relu", "none")),
+                                  ({}, 64, 100, 2, [(1, 7), (37, 53), (36, 52)], ("none", "relu"))]),
+    "wreg": (("bf16", "fp16"), [({}, 128, 256, 2, [(1, 5), (1, 33), (19, 67), (37, 131)], ("relu", "none")), ({}, 256, 256, 1, [(1, 33), (19, 67)], ("relu", "none")),
+                                ({}, 192, 250, 1, [(1, 5), (19, 67)], ("none", "relu")), ({}, 160, 256, 2, [(1, 33), (19, 67)], ("none", "relu"))]),
+    "light": (("bf16", "fp16"), [({}, 32, 3, 1, [(1, 7), (21, 45), (75, 131)], ("tanh01",))]),
+}
+
+
+def set_env(monkeypatch, env):
+    for name in ALL_SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+
+
+def expect_family(family, cin, cout, stride, dtype, env, act):
+    want = "tile" if family == "tile_fp32_only" else family
+    assert family_of(cin, cout, stride, dtype, env, act) == want, (family, cin, cout, stride, dtype, env)
+
+
+def gate_layer(xs, ws, b, stride, act, dtype, label, fails):
+    """One layer through lib.conv3x3 against the model; prints the figures, appends to `fails` what is outside a gate."""
+    store = "fp32" if (dtype == "fp32" or act == "tanh01") else dtype
+    got = lib.conv3x3(xs.to(DEV), ws.to(DEV), b.to(DEV), stride=stride, act=ACT[act], dtype=dtype).cpu()
+    ref, bound, d = conv_model(xs, ws, b, stride, act, store, fp32_products=dtype == "fp32")
+    assert got.shape == ref.shape and torch.isfinite(got).all(), label
+    ratio = ((got.double() - ref).abs() / bound).max().item()
+    share, units = exact_match_share(got, ref, store, d) if store != "fp32" else (0.0, 0.0)
+    slack = ((d >= quantum(ref, store)) & (ref != 0)).double().mean().item() if store != "fp32" else 0.0   # non-zero results with floor(d / unit) > 0: last place not pinned
+    print(f"{label}: err / bound max {ratio:.3f}; mismatches {100 * share:.4f} % (<= {units:.0f} units); d >= unit in {100 * slack:.2f} %")
+    if ratio > 1.0:
+        fails.append(f"{label}: an element exceeds the rounding model's worst case ({ratio:.3f}x)")
+    if share > MISMATCH_CAP or units > 1.0:
+        fails.append(f"{label}: not a round-to-nearest store of the float64 value ({100 * share:.3f} % differ, up to {units:.0f} units)")
+    return got
+
+
+@pytest.mark.parametrize("family,dtype", [(f, d) for f in FAMILIES for d in FAMILIES[f][0]])
+def test_single_layers_stay_inside_the_rounding_model(family, dtype, monkeypatch):
+    """x ~ N(0, 1) scaled per input channel by 2^-3 .. 2^3, w ~ N(0, 1 / (9 Cin)), B = 2 (B = 1 above 4000 pixels), the
+    activations alternate over the shapes.  measured: see MEASURED at the end of this file."""
+    cases = FAMILIES[family][1]
+    fails = []
+    for env, cin, cout, stride, shapes, acts in cases:
+        set_env(monkeypatch, env)
+        for i, (H, W) in enumerate(shapes):
+            act = acts[i % len(acts)]
+            expect_family(family, cin, cout, stride, dtype, env, act)
+            B = 1 if H * W > 4000 else 2
+            g = torch.Generator().manual_seed(cin * 131 + cout + 7 * H + W)
+            xs = storage_round(scaled_input(g, B, cin, H, W), dtype)
+            w, b = conv_weights(g, cout, cin)
+            gate_layer(xs, storage_round(w, dtype), b, stride, act, dtype, f"{family} {dtype} {cin}->{cout} s{stride} {act} {B}x{H}x{W}", fails)
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+def test_the_im2col_tail_alone(dtype, monkeypatch):
+    """ring = 3 (65..67 -> 64): channels 0..63 are zero and only 64..66 carry data, so the result is the tail's alone (conv_ring.inl
+    adds the tail's im2col product first); same gates, and the output must not be the bias alone."""
+    set_env(monkeypatch, {})
+    fails = []
+    for cin, cout, (H, W) in ((67, 64, (17, 63)), (65, 64, (3, 125)), (66, 40, (17, 124))):
+        expect_family("ring3", cin, cout, 1, dtype, {}, "none")
+        g = torch.Generator().manual_seed(cin + H)
+        x = scaled_input(g, 2, cin, H, W)
+        x[:, :64] = 0
+        w, b = conv_weights(g, cout, cin)
+        xs, ws = storage_round(x, dtype), storage_round(w * 4, dtype)
+        got = gate_layer(xs, ws, b, 1, "none", dtype, f"tail only {dtype} {cin}->{cout} {H}x{W}", fails)
+        assert (got - b.view(1, -1, 1, 1)).abs().mean().item() > 0.05
+    assert not fails, "\n".join(fails)
+
+
+IMPULSE = [("tile", {}, 11, 27, 1), ("tile", {}, 8, 16, 2), ("tile", {"EMAVFI_CONV_WREG": "0"}, 128, 256, 2), ("persist16", {}, 64, 32, 1),
+           ("persist16", NO_RING, 64, 64, 1), ("persist32", OLD32, 64, 32, 1), ("persist32", OLD32_NO_RING, 64, 64, 1), ("persist32", {}, 67, 27, 1),
+           ("ring2", {}, 64, 64, 1), ("ring2", {}, 64, 33, 1), ("ring3", {}, 67, 64, 1), ("ring3", {}, 65, 40, 1), ("s2ring", {}, 64, 128, 2), ("s2ring", {}, 64, 100, 2),
+           ("wreg", {}, 128, 256, 2), ("wreg", {}, 256, 256, 1), ("wreg", {}, 192, 250, 1), ("light", {}, 32, 3, 1)]
+
+
+@pytest.mark.parametrize("case,dtype", [(c, d) for c in IMPULSE for d in ("bf16", "fp16", "fp32") if not (d == "fp32" and c[1])],
+                         ids=lambda v: v if isinstance(v, str) else f"{v[0]}-{v[2]}to{v[3]}s{v[4]}" + ("-old" if v[1] else ""))
+def test_unit_impulses_return_single_weights_exactly(case, dtype, monkeypatch):
+    """Integer weights in [-127, 127], zero bias, no activation, one unit impulse per input channel, three pixels apart: every output
+    element is 0 or exactly one w[o, c, i, j] - torch.equal with F.conv2d.  This pins every (cout, cin, tap) of each family's packed
+    fragment order.  The second image moves the field onto the last row and the last column; at stride 2 impulses at 3 k + 1 (first
+    image) and 3 k + 2 (second) lie on both parities.  The planar head exists through the stage entry with tanh01 only, which is not
+    exact: for the `light` family the known answer is tanh01 of the same single weights (scaled by 1 / 64), to TANH_TERM = 2^-21.
+    fp32 has one family, the tile kernel: it runs once per channel configuration (the cases without layout switches)."""
+    family, env, cin, cout, stride = case
+    act = "tanh01" if family == "light" else "none"
+    expect_family("tile" if dtype == "fp32" else family, cin, cout, stride, dtype, env, act)
+    set_env(monkeypatch, env)
+    g = torch.Generator().manual_seed(cin * 7 + cout)
+    for shift in (False, True):
+        x, w = impulse_case(cin, cout, stride, shift, g)
+        if family == "light":
+            w = w / 64       # (still exact in every type; keeps tanh away from saturation)
+        got = lib.conv3x3(x.to(DEV), w.to(DEV), torch.zeros(cout, device=DEV), stride=stride, act=ACT[act], dtype=dtype).cpu()
+        want = F.conv2d(x, w, padding=1, stride=stride)
+        if family == "light":
+            err = (got.double() - (torch.tanh(want.double()) + 1) / 2).abs().max().item()
+            assert err <= 2.0 ** -21, (shift, err)
+            continue
+        wrong = got != want
+        assert not wrong.any(), f"{case} {dtype} shift={shift}: {int(wrong.sum())} of {got.numel()} elements, first at {wrong.nonzero()[0].tolist()}"
+
+
+@pytest.fixture
+def switch():
+    old = lib.debug_switches()
+
+    def set_(bit, on):
+        lib.debug_switches(~bit, bit if on else 0)
+    yield set_
+    lib.debug_switches(0, old)
+
+
+def run_layer(a, L, dtype):
+    return lib.conv3x3(a.to(DEV), L["w"].to(DEV), L["b"].to(DEV), stride=L.get("stride", 1), act=ACT[L["act"]], dtype=dtype).cpu()
+
+
+def layered_chain(x, layers, dtype, label, fails, check=True):
+    """The layers of a stage run ONE AT A TIME through lib.conv3x3 (the unfused kernels of the same plan), each gated against the
+    single-layer model on the GPU's own previous output - so no bound has to absorb a possibly flipped intermediate rounding, and
+    every gate bites to half a unit of the store.  Returns the GPU's outputs of all layers."""
+    outs, a = [], x
+    for k, L in enumerate(layers):
+        if check:
+            a = gate_layer(a, L["w"], L["b"], L.get("stride", 1), L["act"], dtype, f"{label} layer {k}", fails)
+        else:
+            a = run_layer(a, L, dtype)
+        outs.append(a)
+    return outs
+
+
+def gate_last_layer(got, a_in, L, store, label, fails, rows=None):
+    """A stage's result against the single-layer model of its LAST layer on the GPU's own intermediate `a_in` (rows: a band of output
+    rows [r0, r1) only - the float64 reference of a band needs one more input row on either side)."""
+    H = a_in.shape[2]
+    r0, r1 = rows if rows is not None else (0, H)
+    lo, hi = max(r0 - 1, 0), min(r1 + 1, H)
+    ref, bound, d = conv_model(a_in[:, :, lo:hi], L["w"], L["b"], 1, L["act"], store)
+    ref, bound, d = (t[:, :, r0 - lo:r1 - lo] for t in (ref, bound, d))
+    g = got[:, :, r0:r1]
+    ratio = ((g.double() - ref).abs() / bound).max().item()
+    share, units = exact_match_share(g, ref, store, d) if store != "fp32" else (0.0, 0.0)
+    print(f"{label}: err / single-layer bound max {ratio:.3f}; mismatches {100 * share:.4f} % (<= {units:.0f} units)")
+    if ratio > 1.0:
+        fails.append(f"{label}: an element exceeds the single-layer bound on the GPU's own intermediate ({ratio:.3f}x)")
+    if share > MISMATCH_CAP or units > 1.0:
+        fails.append(f"{label}: not a round-to-nearest store ({100 * share:.3f} % differ, up to {units:.0f} units)")
+
+
+def recon_case(dtype, B, H, W):
+    g = torch.Generator().manual_seed(6400 + W)
+    fused = storage_round(torch.randn(B, 67, H, W, generator=g), dtype)
+    shapes, params, layers = ((64, 67, 1.0), (32, 64, 1.0), (3, 32, 1.5)), [], []
+    for k, (cout, cin, scale) in enumerate(shapes):
+        w = storage_round(torch.randn(cout, cin, 3, 3, generator=g) * (scale * (2.0 / (9 * cin)) ** 0.5), dtype)
+        b = torch.randn(cout, generator=g) * 0.1
+        params += [w, b]
+        layers.append({"w": w, "b": b, "act": "tanh01" if k == 2 else "relu", "store": "fp32" if k == 2 else dtype})
+    return fused, params, layers
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("shape", [(1, 75, 131), (1, 1, 7), (1, 2, 62), (1, 17, 124), (2, 40, 125)])
+def test_reconstruction_stage_layer_by_layer(shape, dtype, switch, monkeypatch):
+    """lib.reconstruct at mid_channels 64: r0 (67 -> 64, conv_ring.inl with the im2col tail) -> r1 (64 -> 32) -> r2 (32 -> 3, tanh01).
+    Where the intermediates are rounded, read from the kernels: r0's output is stored in the storage type after the ReLU; r1's rows are
+    rounded to the SAME type after bias and ReLU - in the fused kernel as they enter the LDS row ring (conv_ring_tail.inl, stage_a_out:
+    `(T)v[e]`), unfused as they are stored; the head accumulates in fp32 and returns fp32.
+      * the three layers one at a time (ring 3, conv3x3_persist16_kernel, conv_light_kernel), each inside the single-layer gates;
+      * TWO LAUNCHES (SW_NO_TAILFUSE: the same three kernels on the same operands): the frame inside the single-layer bound of the HEAD
+        on the GPU's own r1 - TANH_TERM + delta / 2, some 1e-5 on a frame in [0, 1], where the stage test's gate is 1.5e-2;
+      * FUSED (conv_ring_tail.inl): r1 is summed in another order and never leaves the chip, so a few of its roundings may flip and no
+        single-layer statement about the frame exists.  The frame is held to chain_bound over r1 -> r2 from the GPU's own r0 - ONE
+        rounded intermediate, rigorous, and coarse (a flip is possible wherever the worst-case delta reaches a boundary: reported) -
+        and the tight statement about it is the bit-level comparison with the two-launch path that tests/test_gpu_parity.py makes.
+    measured: see MEASURED."""
+    B, H, W = shape
+    set_env(monkeypatch, {})
+    fused, params, layers = recon_case(dtype, B, H, W)
+    fails = []
+    outs = layered_chain(fused, layers, dtype, f"reconstruct {dtype} {shape}", fails)
+    m = chain_bound(outs[0], layers[1:])
+    for fused_tail in (False, True):
+        switch(lib.SW_NO_TAILFUSE, not fused_tail)
+        names = [n for n, _, _ in lib.forward_launches(3, 64, 3, B, H, W, dtype)]
+        assert sum(n.startswith("conv3x3+tail") for n in names) == int(fused_tail)
+        got = lib.reconstruct(fused.to(DEV), [p.to(DEV) for p in params], dtype=dtype).cpu()
+        assert got.shape == m["ref"].shape and torch.isfinite(got).all()
+        if not fused_tail:
+            gate_last_layer(got, outs[1], layers[2], "fp32", f"reconstruct {dtype} {shape} two launches", fails)
+        err = (got.double() - m["ref"]).abs()
+        ratio = (err / m["bound"]).max().item()
+        print(f"reconstruct {dtype} {shape} fused={fused_tail}: max err {err.max().item():.3e} against the float64 r1 -> r2 of the GPU's r0; err / chain bound max {ratio:.4f}; "
+              f"r1 roundings that may flip {100 * m['flip_share'][0]:.1f} %")
+        if ratio > 1.0:
+            fails.append(f"reconstruct {dtype} {shape} fused={fused_tail}: outside the chain bound ({ratio:.3f}x)")
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("shape", [(2, 37, 53), (1, 1, 7), (1, 64, 96)])
+def test_context_stage_layer_by_layer(shape, dtype, switch, monkeypatch):
+    """lib.context at mid_channels 64: c0 (64 -> 128, stride-2 ring) -> c1 (128 -> 256, stride 2, conv_wreg) -> c2 (256 -> 256, conv_wreg)
+    -> mean over the pixels -> Linear, with c2's tile-sum pool fused (conv_wreg.inl adds "the values the tensor would have held (rounded
+    to T)") and stored + pooled (SW_NO_POOLFUSE).  All three outputs are rounded to the storage type after the ReLU, the pool and the
+    Linear are fp32 sums of those values.  The three layers one at a time inside the single-layer gates; then ctx of BOTH pool paths
+    against the float64 mean + Linear of the GPU's own c2 with the fp32-sum bound n 2^-24 sum|terms| (pool: n = pixels, one more
+    rounding for the division; Linear: 256 rounded products + the bias, 2 * 257) - no rounding of the storage type separates c2 from ctx,
+    so the bound is some 1e-5 relative where the stage test's gate is 2e-3.  In the bf16 model the stage keeps `feat` as f16 and runs c0
+    on the f16 instruction with bf16-rounded weights (Plan::feat16); the layer run alone takes the bf16 instruction: the same exact
+    products (the input is made representable in both types) - that the two orders of c0 agree is part of what the ctx gate checks.
+    measured: see MEASURED."""
+    B, H, W = shape
+    set_env(monkeypatch, {})
+    g = torch.Generator().manual_seed(64000 + H)
+    feat = storage_round(torch.randn(B, 64, H, W, generator=g).relu(), dtype)
+    feat = torch.where(feat < 2.0 ** -14, torch.zeros_like(feat), feat)        # (bf16 values below f16's normal range would lose bits as f16)
+    layers = []
+    for cout, cin, stride in ((128, 64, 2), (256, 128, 2), (256, 256, 1)):
+        w = storage_round(torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5, dtype)
+        layers.append({"w": w, "b": torch.randn(cout, generator=g) * 0.1, "stride": stride, "act": "relu", "store": dtype})
+    lw, lb = torch.randn(64, 256, generator=g) / 16, torch.randn(64, generator=g) * 0.1
+    fails = []
+    c2 = layered_chain(feat, layers, dtype, f"context {dtype} {shape}", fails)[2].double()
+    n = c2.shape[2] * c2.shape[3]
+    mean = c2.mean(dim=(2, 3))
+    d_mean = (n + 1) * U32 * c2.abs().mean(dim=(2, 3))
+    ref = mean @ lw.double().t() + lb.double()
+    bound = 2 * 257 * U32 * ((mean.abs() + d_mean) @ lw.double().abs().t() + lb.double().abs()) + d_mean @ lw.double().abs().t()
+    params = [t for L in layers for t in (L["w"], L["b"])] + [lw, lb]
+    for poolfuse in (True, False):
+        switch(lib.SW_NO_POOLFUSE, not poolfuse)
+        names = [nm for nm, _, _ in lib.forward_launches(3, 64, 3, B, H, W, dtype)]
+        assert sum("pool (tile sums)" in nm for nm in names) == int(poolfuse)
+        got = lib.context(feat.to(DEV), [p.to(DEV) for p in params], dtype=dtype).cpu()
+        assert got.shape == ref.shape and torch.isfinite(got).all()
+        ratio = ((got.double() - ref).abs() / bound).max().item()
+        print(f"context {dtype} {shape} poolfuse={poolfuse}: max err {(got.double() - ref).abs().max().item():.3e} (|ctx| <= {ref.abs().max().item():.3g}); err / bound max {ratio:.3f}")
+        if ratio > 1.0:
+            fails.append(f"context {dtype} {shape} poolfuse={poolfuse}: ctx outside the fp32-sum bound on the GPU's own c2 ({ratio:.3f}x)")
+    assert not fails, "\n".join(fails)
+
+
+def model_layer(sd, name, dtype, act="relu", store=None):
+    return {"w": storage_round(sd[name + ".weight"], dtype), "b": sd[name + ".bias"].float(), "act": act, "store": store or dtype}
+
+
+FEAT_SHAPES = [(1, 75, 131), (1, 1, 7), (1, 2, 62), (1, 3, 63), (1, 17, 124), (1, 360, 640)]
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("shape,kind", [(sh, k) for sh in FEAT_SHAPES for k in ("natural", "stress") if not (k == "stress" and sh[1] == 360)])   # (360 x 640: natural frames only)
+def test_feat_of_the_forward_layer_by_layer(shape, dtype, kind, monkeypatch):
+    """`feat` through the forward (return_taps): cat + feat_ext_conv1 + conv_block_0 in ONE launch (conv_first.inl's layer inside
+    conv_ring_first.inl), conv_block_1 + conv_block_2 in one (conv_ring2.inl) - kernels no stage entry reaches.  Every intermediate is
+    rounded to the storage type after its ReLU (in the LDS rings as in memory); in a bf16 model with the one-launch packs `feat` itself
+    is stored as saturating f16 (Plan::feat16), which the gate follows.  The four layers are run one at a time (tile kernel 6 -> 64,
+    the ring kernel three times) from the storage-rounded frames, each inside the single-layer gates; the forward's `feat` tap is then
+    held to the single-layer model of conv_block_2 on the GPU's own conv_block_1 output, bound AND last place.  This presumes what
+    tests/test_gpu_parity.py asserts bit for bit - the fused launches repeat the unfused kernels' arithmetic -; a fused kernel that
+    departed from it would flip roundings in front of the last layer and fail here at the elements they reach.  At 360 x 640 the
+    float64 reference is taken on four bands of 12 rows (top, a range boundary region, the middle, bottom) and the first three layers
+    are run but not gated (they are at the other shapes).  measured: see MEASURED."""
+    B, H, W = shape
+    set_env(monkeypatch, {})
+    sd = synth.synthetic_state_dict(seed=6)
+    f1, f2 = synth.synthetic_frames(41, B, H, W, kind)
+    model = EMA_VFI(mid_channels=64, compute_dtype=dtype).to(DEV).eval()
+    model.load_state_dict(sd, strict=True)
+    with torch.no_grad():
+        _, taps = model(f1.to(DEV), f2.to(DEV), return_taps=True)
+    feat = taps["feat"].float().cpu()
+    names = [n for n, _, _ in lib.forward_launches(3, 64, 3, B, H, W, dtype)]
+    assert sum(n.startswith("conv_first+conv3x3") for n in names) == 1 and sum(n.startswith("conv3x3+conv3x3") for n in names) == 1
+    layers = [model_layer(sd, "feat_ext_conv1.0", dtype)] + [model_layer(sd, f"feat_ext_blocks.conv_block_{i}.0", dtype) for i in range(3)]
+    x = storage_round(torch.cat([f1, f2], dim=1), dtype)
+    big = H * W > 20000
+    fails = []
+    outs = layered_chain(x, layers[:3], dtype, f"feat {kind} {dtype} {shape}", fails, check=not big)
+    store = "fp16" if dtype == "bf16" else dtype
+    for rows in ([(0, 12), (40, 52), (174, 186), (H - 12, H)] if big else [None]):
+        gate_last_layer(feat, outs[2], layers[3], store, f"feat tap {kind} {dtype} {shape} rows {rows}", fails, rows)
+    assert torch.isfinite(feat).all()
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("shape", [(2, 33, 70), (1, 1, 7), (1, 2, 62), (1, 17, 124)])
+def test_flow_from_the_forwards_own_taps(shape, dtype, switch, monkeypatch):
+    """`flow` from the GPU's own `feat` and `ctx` taps: motion_estimation.0 (the ring kernel on `feat`, the context half folded into a
+    per-border-class bias table in fp32) -> .1 -> .2, with the head fused into .1's launch (conv_ring.inl, HEAD) and as its own launch
+    (SW_NO_HEAD: conv_light_kernel's 64-channel form).  Neither .0's nor .1's output is visible from outside, and .0's fp32 bias table
+    cannot be handed to the single-layer entry, so NO layer-by-layer gate is possible here: the flow is held to chain_bound over the
+    three layers - .0 as a 128-channel layer whose context half is the fp32 ctx broadcast over the image (zero-padded like any input:
+    the border classes), counted with rounded products (2 n) because ctx is fp32; .0 and .1 rounded to the storage type after the
+    ReLU, the head fp32.  Rigorous and COARSE (two rounded intermediates: the bound is some 1e-1 of |flow|); the tight statement
+    about the fused head is its comparison with the two-launch path in tests/test_gpu_parity.py (2e-5).  measured: see MEASURED."""
+    B, H, W = shape
+    set_env(monkeypatch, {})
+    sd = synth.synthetic_state_dict(seed=5)
+    f1, f2 = synth.synthetic_frames(43, B, H, W, "natural")
+    l0 = model_layer(sd, "motion_estimation.0.0", dtype)
+    l0["fp32_products"] = True
+    layers = [l0, model_layer(sd, "motion_estimation.1.0", dtype), model_layer(sd, "motion_estimation.2", dtype, act="none", store="fp32")]
+    fails = []
+    for head in (True, False):
+        switch(lib.SW_NO_HEAD, not head)
+        model = EMA_VFI(mid_channels=64, compute_dtype=dtype).to(DEV).eval()
+        model.load_state_dict(sd, strict=True)
+        with torch.no_grad():
+            _, taps = model(f1.to(DEV), f2.to(DEV), return_taps=True)
+        names = [n for n, _, _ in lib.forward_launches(3, 64, 3, B, H, W, dtype)]
+        assert sum("+head" in n for n in names) == int(head)
+        feat, ctx, flow = (taps[k].float().cpu() for k in ("feat", "ctx", "flow"))
+        m = chain_bound(torch.cat([feat, ctx.view(B, 64, 1, 1).expand(B, 64, H, W)], dim=1), layers)
+        assert flow.shape == m["ref"].shape and torch.isfinite(flow).all()
+        err = (flow.double() - m["ref"]).abs()
+        ratio = (err / m["bound"]).max().item()
+        print(f"flow {dtype} {shape} head fused={head}: max err {err.max().item():.3e} (|flow| <= {m['ref'].abs().max().item():.3g}); err / chain bound max {ratio:.4f}")
+        if ratio > 1.0:
+            fails.append(f"flow {dtype} {shape} head fused={head}: outside the chain bound ({ratio:.3f}x)")
+    assert not fails, "\n".join(fails)
+
+
+# MEASURED (MI355X, this file's own output; per family the range of max(err / bound) over its cases, the largest mismatch share, and the
+# largest distance of a mismatch in units of the last place; every case also prints the share of non-zero results whose unit is below the
+# accumulation term d, i.e. where exact_match_share allows more than one unit - small results of cancelling terms, most at Cin >= 192 in f16):
+#   family        bf16                          fp16                          fp32
+#   tile          0.69 ... 0.993, 0.045 %, 1    0.61 ... 0.981, 0.134 %, 1    0.001 ... 0.058 (fp32 has no store rounding: no share)
+#   persist16     0.92 ... 0.966, 0.024 %, 1    0.67 ... 0.823, 0.147 %, 1
+#   persist32     0.71 ... 0.966, 0.027 %, 1    0.68 ... 0.823, 0.134 %, 1
+#   ring2         0.94 ... 0.970, 0.018 %, 1    0.74 ... 0.850, 0.107 %, 1
+#   ring3         0.91 ... 0.959, 0.015 %, 1    0.72 ... 0.810, 0.086 %, 1    (tail alone: 0.98 / 0.89 ... 0.92, 0.004 % / 0.031 %)
+#   s2ring        0.93 ... 0.969, 0.017 %, 1    0.69 ... 0.825, 0.090 %, 1
+#   wreg          0.81 ... 0.922, 0.023 %, 1    0.39 ... 0.641, 0.156 %, 1
+#   light         0.001 ... 0.004               0.002 ... 0.003               (fp32 planar output; the bound is TANH_TERM + delta / 2)
+# The 16-bit ratios sit just below 1 because the store's half unit is most of the bound and an element just above a power of two can use
+# all of it; the accumulation term itself is used to a few per cent (the fp32 column), i.e. the MFMA's fp32 accumulation stays far inside
+# n 2^-24 sum|terms|.  Every impulse case is exact.
+# Stages: the layers run one at a time <= 0.993 (bf16) / 0.985 (fp16), mismatches <= 0.22 %, one unit.  `feat` tap on the GPU's own
+# conv_block_1: 0.68 ... 0.81 / 0.66 ... 0.76, mismatches <= 0.043 %, one unit.  reconstruct, two launches, on the GPU's own r1: 0.002 / 0.004 of
+# the head's bound; fused and two launches against the r1 -> r2 chain bound from the GPU's r0: <= 0.20 / 0.045 (max err 1.8e-3 / 4.8e-4).
+# ctx of both pool paths on the GPU's own c2: <= 0.002 of the fp32-sum bound (max err 1.7e-7).  flow against its three-layer chain bound:
+# <= 0.026 / 0.006 (max err 3.1e-2 / 3.7e-3 px).

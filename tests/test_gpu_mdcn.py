@@ -26,18 +26,11 @@ import torch
 
 from emavfi import ModulatedDeformConvPack, lib
 from oracle import emavfi_oracle as oracle
+from rounding_model import storage_round
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 U16 = 2.0 ** -11
-
-
-def storage_round(t, dtype, as_f16=False):
-    if dtype == "fp32":
-        return t.clone()
-    if dtype == "bf16" and not as_f16:
-        return t.bfloat16().float()
-    return t.half().float()
 
 
 def weight_round(t, dtype):
