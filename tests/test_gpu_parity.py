@@ -164,6 +164,8 @@ def test_conv_wreg_random_shapes_match_aten():
 
 
 # ------------------------------------------------------------------ deformable conv (rows O, D)
+# (A smoke-level gate: Gaussian offsets, max|err| / max|ref|.  It cannot see a wrong corner weight in one border class or a sample lost
+# on one tile edge; the per-element, derived gate at exact lattice, border and window-edge offsets is tests/test_gpu_deform_lattice.py.)
 @pytest.mark.parametrize("dtype,tol", [("fp32", 3e-5), ("bf16", 3e-2), ("fp16", 4e-3)])
 @pytest.mark.parametrize("C,O,H,W,spread", [(67, 67, 19, 41, 2.0), (67, 67, 8, 32, 12.0), (11, 11, 23, 37, 1.5),
                                             (5, 7, 1, 1, 1.0), (19, 19, 9, 33, 3.0), (35, 35, 16, 16, 2.0)])
