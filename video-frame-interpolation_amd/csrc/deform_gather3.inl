@@ -6,7 +6,8 @@
 //
 //   * LDS holds only what offset_conv reads: the 16 x 16 tile plus a 1 px halo (18 x 18 pixels x 144 B = 46 656 B) and the 4.5 KiB
 //     third-fragment table, 51 264 B in all (the pack: 81 312 B for its 23 x 23 window).  No sample ever "leaves" anything.
-//   * offset_conv, the sigmoid and the sampling geometry are the pack's arithmetic, operation for operation.
+//   * offset_conv, the sigmoid, the sampling geometry, the tail contraction, the census record and the epilogue are the very
+//     text the pack's body runs (deform3_stages.inl): one definition each, so the two routes cannot drift apart.
 //   * Every tap gathers its corner pieces straight from global memory: lane (r, h) loads the four 16-byte corner pieces
 //     (k-group kg, half h) of pixel r of fragment row m with raw buffer loads.  A corner outside the image gets an offset beyond the
 //     buffer's range and reads 0 - exactly what the pack's window holds there (its DMA reads the zero page), so the blend runs on the
@@ -19,8 +20,6 @@
 //
 // Latency: the corner loads of a step go out four steps (half a tap) ahead through a ring of four operand buffers, across the tap
 // boundary; the sampling descriptors of all nine taps are computed up front as in the pack.
-// (offset_conv and the geometry are restated here rather than shared: they live in the body of deform_pack3_kernel, and lifting them
-// into helpers would change that kernel's code object - the pack stays exactly as it is.)
 #pragma once
 #include "deform_pack3.inl"
 
@@ -37,9 +36,6 @@ struct Gather3 {
     static_assert((unsigned long long)(1u << 24) * PSB < BAD, "out-of-image offsets must lie beyond every plane");
 };
 
-// window byte offset of plain tap t relative to tap 0 (taps past 8 re-read tap 8: finite data against zero weights)
-__host__ __device__ constexpr int gather3_tap_off(int t) { return t < 9 ? ((t / 3) * Gather3::TC + (t % 3)) * Gather3::PSB : (2 * Gather3::TC + 2) * Gather3::PSB; }
-
 template <typename TS>
 __global__ __launch_bounds__(256, 2) void deform_gather3_kernel(const DeformParams p)
 {
@@ -48,13 +44,8 @@ __global__ __launch_bounds__(256, 2) void deform_gather3_kernel(const DeformPara
 
 template <typename TS> static int launch_deform_gather3(const DeformParams &p, hipStream_t s)
 {
-    using C = Gather3;
     if (!p.off_w || p.pack3 != 1 || !deform_pack3_shape(p.ck, p.nf, p.cin_real, p.cout_real)) return -2;
     if ((long long)p.H * p.W >= (1LL << 24)) return (int)hipErrorInvalidValue;   // 24-bit pixel indices in the corner descriptors
     static PerDeviceOnce once;
-    if (const hipError_t e_ = set_lds_limit(once, reinterpret_cast<const void *>(&deform_gather3_kernel<TS>), C::LDS_BYTES); e_ != hipSuccess) return (int)e_;
-    const long long nwg = (long long)((p.W + C::TCOLS - 1) / C::TCOLS) * ((p.H + C::TROWS - 1) / C::TROWS) * p.B;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    deform_gather3_kernel<TS><<<(unsigned)nwg, C::THREADS, C::LDS_BYTES, s>>>(p);
-    return (int)hipGetLastError();
+    return deform3_launch<Gather3>(&deform_gather3_kernel<TS>, once, Gather3::LDS_BYTES, p, s);
 }

@@ -76,9 +76,6 @@ struct Pack3 {
     static_assert(ROWB + PSB + 8 * 16 + 15 < 65536, "corner offsets must fit the ds_read immediate");
 };
 
-// window byte offset of plain tap t relative to tap 0 (taps past 8 re-read tap 8: finite data against zero weights)
-__host__ __device__ constexpr int pack3_tap_off(int t) { return t < 9 ? ((t / 3) * Pack3::TC + (t % 3)) * Pack3::PSB : (2 * Pack3::TC + 2) * Pack3::PSB; }
-
 // Pins a point of the hand-made schedule: an empty volatile asm that "rewrites" the four partial sums (instruction selection
 // otherwise places plain arithmetic anywhere between its operands and its users, on either side of a scheduling fence - half of
 // the steps came out with their blend sunk behind their MFMAs), then the fence for the machine scheduler.  The asm emits no
@@ -89,6 +86,8 @@ __host__ __device__ constexpr int pack3_tap_off(int t) { return t < 9 ? ((t / 3)
         __builtin_amdgcn_sched_barrier(0);                                            \
     } while (0)
 
+#include "deform3_shared.inl"   // the stages this kernel's body has in common with the window-free route's (deform_gather3.inl)
+
 template <typename TS, bool FUSE_OFF>
 __global__ __launch_bounds__(256, 2) void deform_pack3_kernel(const DeformParams p)
 {
@@ -97,12 +96,6 @@ __global__ __launch_bounds__(256, 2) void deform_pack3_kernel(const DeformParams
 
 template <typename TS, bool FUSE_OFF> static int launch_deform_pack3(const DeformParams &p, hipStream_t s)
 {
-    using C = Pack3;
-    constexpr int LDS_REQ = EMAVFI_P3_ONE_WG ? 100 * 1024 : C::LDS_BYTES;
-    static PerDeviceOnce once;   // (the library is re-entrant and serves several devices per process)
-    if (const hipError_t e_ = set_lds_limit(once, reinterpret_cast<const void *>(&deform_pack3_kernel<TS, FUSE_OFF>), LDS_REQ); e_ != hipSuccess) return (int)e_;
-    const long long nwg = (long long)((p.W + C::TCOLS - 1) / C::TCOLS) * ((p.H + C::TROWS - 1) / C::TROWS) * p.B;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    deform_pack3_kernel<TS, FUSE_OFF><<<(unsigned)nwg, C::THREADS, LDS_REQ, s>>>(p);
-    return (int)hipGetLastError();
+    static PerDeviceOnce once;
+    return deform3_launch<Pack3>(&deform_pack3_kernel<TS, FUSE_OFF>, once, EMAVFI_P3_ONE_WG ? 100 * 1024 : Pack3::LDS_BYTES, p, s);
 }

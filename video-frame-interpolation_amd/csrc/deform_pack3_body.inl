@@ -1,6 +1,6 @@
-// The body of deform_pack3_kernel<TS, FUSE_OFF> (deform_pack3.inl), kept in a file of its own so that the routed pack
-// (deform_route3.inl) runs the same statements as its window branch while this kernel's code object stays what it was (a force-inlined
-// helper changed its register allocation).  Included inside a function body that defines TS, FUSE_OFF and the DeformParams `p`.
+// The body of deform_pack3_kernel<TS, FUSE_OFF> (deform_pack3.inl), the WINDOW route, kept in a file of its own so that the routed pack
+// (deform_route3.inl) runs the same statements as its window branch.  Included inside a function body that defines TS, FUSE_OFF and the
+// DeformParams `p`.  The stages it has in common with the gather body are included from deform3_stages.inl (deform3_shared.inl).
     using C = Pack3;
     constexpr int R = C::R;
     static_assert(sizeof(TS) == 2, "16-bit storage types only");
@@ -18,19 +18,8 @@
     unsigned long long sum_steps = 0, cnt_out = 0;
 #endif
 
-    // ---- tile of this workgroup (XCD-aware order: deform_pack.inl)
-    const int ntx = (W + C::TCOLS - 1) / C::TCOLS, nty = (H + C::TROWS - 1) / C::TROWS, nt = ntx * nty;
-    int tile_x, tile_y, b;
-    {
-        constexpr int SROWS = 4;
-        const int nwg = gridDim.x, grp = blockIdx.x & 7, kk = blockIdx.x >> 3, qq = nwg >> 3, rr = nwg & 7;
-        const int wg = (grp < rr ? grp * (qq + 1) : rr * (qq + 1) + (grp - rr) * qq) + kk;
-        b = wg / nt;
-        const int t = wg - b * nt, strip = t / (SROWS * ntx), tt = t - strip * SROWS * ntx;
-        const int rows = min(SROWS, nty - strip * SROWS);
-        tile_x = tt / rows;
-        tile_y = strip * SROWS + (tt - tile_x * rows);
-    }
+#define DEFORM3_STAGE DEFORM3_TILE
+#include "deform3_stages.inl"
     const unsigned ps_bytes = (unsigned)p.x_ps * 2u, tail_bytes = (unsigned)p.tail_ps * 2u;
     const int ty0 = tile_y * C::TROWS - 1 - R, tx0 = tile_x * C::TCOLS - 1 - R;
     const char *gplane = (const char *)p.x + (size_t)b * H * W * ps_bytes;
@@ -95,43 +84,12 @@
         }
     }
 
-    // ---- this lane's pixel in each of its wave's two fragments (2 rows x 16 columns; hardware ds_read_b128 lane groups
-    // get one row of 16 consecutive pixels each: deform_pack.inl)
-    const bool g2 = (r >= 4 && r < 12) || (r >= 16 && r < 20) || r >= 28;
-    const int fr_row = g2 ? 1 : 0;
-    const int fr_col = g2 ? (r < 12 ? r - 4 : (r < 20 ? r - 8 : r - 16)) : (r < 4 ? r : (r < 16 ? r - 8 : r - 12));
-    const int px_x = tile_x * C::TCOLS + fr_col;
-    int py_y[2], wrow[2];
-    bool in_img[2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        wrow[m] = (wave * 2 + m) * 2 + fr_row;
-        py_y[m] = tile_y * C::TROWS + wrow[m];
-        in_img[m] = py_y[m] < H && px_x < W;
-    }
-    const int my_y = h ? py_y[1] : py_y[0];
-    const bool my_in = h ? in_img[1] : in_img[0];
+#define DEFORM3_STAGE DEFORM3_LANE
+#include "deform3_stages.inl"
     const float *om_my = p.om + (((size_t)b * H + (my_in ? my_y : 0)) * W + (my_in ? px_x : 0)) * 32;
-    const float fy_base = (float)(my_y - 1), fx_base = (float)(px_x - 1);
-    const float fy_max = (float)(H + 1), fx_max = (float)(W + 1);
-    // LDS byte offset of this lane's piece (h) of the plain tap-0 pixel of fragment row m
-    unsigned xbase[2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) xbase[m] = (unsigned)(((wrow[m] + R) * C::TC + fr_col + R) * C::PSB + h * 16);
-    // The third output fragment (channels 64..66) runs on v_mfma_f32_16x16x32 (round 5: half the matrix-pipe cycles of the 32x32x16 it
-    // replaces, 4 accumulator registers per row instead of 16) on the SAME B register: read as a 16x16x32 operand, lane
-    // L = 32 h + r supplies column j = r & 15, K slice kb = 2 h + (r >> 4) - the two pixel halves of the fragment row sit in
-    // different K slices.  The A operand separates them again: row 4 ph + c holds W[64 + c][slice h] in K slice 2 h + ph and zeros in
-    // the other pixel half's slices, so D[4 ph + c][j] is channel 64 + c of pixel 16 ph + j - lane L < 32 ends with channels
-    // 64..67 of ITS OWN pixel in its four registers.  Same LDS table (rows 0..2 | zero row, two halves), another lane mapping.
-    // (Non-finite data: the other pixel's contribution is removed by ZERO weights, so an Inf / NaN blended value at pixel r +- 16 - reachable
-    // only through an f16 overflow - makes channels 64..66 of pixel r NaN too, where the 32x32x16 form and the reference confine it to the
-    // offending pixel.  Documented in include/emavfi.h; not masked: a frame with a non-finite activation is garbage either way - ADVICE r5.)
-    const int a3i = lane & 15, a3kb = lane >> 4;
-    const bool a3real = (a3i >> 2) < 2 && (a3i & 3) < 3 && (a3kb & 1) == (a3i >> 2);
-    const int a3row = a3real ? (a3i & 3) : 3, a3half = a3kb >> 1;
-    const unsigned w3lane = (unsigned)(C::W3_OFF + (a3row * 2 + a3half) * 16);
-    const int t3lane16 = (a3half * 32 + a3row) * 16;   // the same operand out of a 32x32x16 fragment of the blob (its row 3 is a zero row)
+    constexpr int HALO = R;
+#define DEFORM3_STAGE DEFORM3_LANE_CONST
+#include "deform3_stages.inl"
     DEFORM_STAMP(ts_converted);
     if (tid == 0) *reinterpret_cast<__attribute__((address_space(3))) unsigned *>((lds_char_t *)smem + C::SYNC_OFF) = 0u;   // (fix-up hand-shake below)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the window DMA has landed (hipcc emits this wait today; not relied upon - ADVICE r5)
@@ -140,93 +98,17 @@
 
     f32x16 omr[FUSE_OFF ? 2 : 1];
     if constexpr (FUSE_OFF) {
-        // ---- the pack's offset_conv (ema_vfi.py:41,56: 3x3, pad 1, 67 -> 27) on the staged window: 4 k-groups per tap
-        // on the window pieces as they lie, then the three tail channels of all nine taps as three im2col k-groups
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) omr[m][i] = p.off_bias[acc_channel(i, h)];
-        u32x4_t xq[2][2][4];
-        auto load_x = [&](auto tc, u32x4_t (&dst)[2][4]) {
-            constexpr int toff = pack3_tap_off(decltype(tc)::value);
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int kg = 0; kg < 4; ++kg) dst[m][kg] = lds_read16(lds_r + xbase[m] + (unsigned)(toff + kg * 32));
-        };
-        load_x(std::integral_constant<int, 0>{}, xq[0]);
-        auto off_tap = [&](auto tc) {
-            constexpr int tap = decltype(tc)::value;
-            if constexpr (tap < 7) {  // weight fragments two taps ahead
-#pragma unroll
-                for (int kg = 0; kg < 4; ++kg) ow[(tap + 2) % 3][kg] = *reinterpret_cast<const f16x8 *>(owbase_g + ((tap + 2) * 4 + kg) * 1024 + lane16);
-            }
-            if constexpr (tap < 8) load_x(std::integral_constant<int, tap + 1>{}, xq[(tap + 1) & 1]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int kg = 0; kg < 4; ++kg)
-                    if (!(EMAVFI_P3_ABL & 32) || kg == 0) mma_kg(omr[m], ow[tap % 3][kg], __builtin_bit_cast(f16x8, xq[tap & 1][m][kg]));
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        off_tap(std::integral_constant<int, 0>{}); off_tap(std::integral_constant<int, 1>{}); off_tap(std::integral_constant<int, 2>{});
-        off_tap(std::integral_constant<int, 3>{}); off_tap(std::integral_constant<int, 4>{}); off_tap(std::integral_constant<int, 5>{});
-        off_tap(std::integral_constant<int, 6>{}); off_tap(std::integral_constant<int, 7>{}); off_tap(std::integral_constant<int, 8>{});
-        // tail: k-group j, lane (r, h) holds K = 16j + 8h + e = tap slot 4j + 2h + (e >> 2), channel 64 + (e & 3)
-        {
-            f16x8 ot[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) ot[j] = *reinterpret_cast<const f16x8 *>(owbase_g + C::OFF_TAIL + j * 1024 + lane16);
-            u32x2_t ta[2][3][2];
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const unsigned tb = xbase[m] - (unsigned)(h * 16) + 128u;   // tail piece of the plain tap-0 pixel
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        const unsigned o = h ? (unsigned)pack3_tap_off(4 * j + 2 + u) : (unsigned)pack3_tap_off(4 * j + u);
-                        ta[m][j][u] = lds_read8(lds_r + tb + o);
-                    }
-            }
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const u32x4_t bq = {ta[m][j][0][0], ta[m][j][0][1], ta[m][j][1][0], ta[m][j][1][1]};
-                    mma_kg(omr[m], ot[j], __builtin_bit_cast(f16x8, bq));
-                }
-        }
-        // mask = sigmoid(third chunk), ema_vfi.py:59 (channels 18..26 after the pack-time routing)
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int c = acc_channel(i, h);
-                const float v = omr[m][i];
-                // v_exp_f32 + v_rcp_f32 (1 ulp each): the value becomes an f16 blend weight; the IEEE division and libm expf of
-                // the stand-alone layer cost ~25 instructions per value, 18 values per lane
-                const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896340736f));
-                omr[m][i] = (c >= 18 && c < 27) ? sg : v;
-            }
+        constexpr bool KG0_ONLY = (EMAVFI_P3_ABL & 32) != 0;
+#define DEFORM3_STAGE DEFORM3_OFFSET_CONV
+#include "deform3_stages.inl"
     }
 
     // ---- DCN.  Accumulators; the first weight fragments.
     f16x8 wq[2][2];  // [kg & 1][n]
 #pragma unroll
     for (int n = 0; n < 2; ++n) wq[0][n] = *reinterpret_cast<const f16x8 *>(wbase_g + n * 1024 + lane16);
-    f32x16 acc[2][2];
-    f32x4 acc3[2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[m][n][i] = p.bias[n * 32 + acc_channel(i, h)];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc3[m][e] = lane < 32 ? p.bias[64 + e] : 0.0f;
-    }
+#define DEFORM3_STAGE DEFORM3_ACC_INIT
+#include "deform3_stages.inl"
     DEFORM_STAMP(ts_offconv);
 
     // ---- sampling geometry of ALL NINE taps up front (fp32, compare-free clamps: NaN -> -2; positions <= -1 or >= size sample
@@ -250,28 +132,14 @@
         constexpr int tap = decltype(tc)::value, ti = tap / 3, tj = tap - 3 * ti;
         OmTap o;
         if constexpr (FUSE_OFF) {
-            // channel c of (row 0 | row 1) of this lane's pixels, delivered to (half 0 | half 1): one swap.
-            // swap(a, b) -> {(a.lo, b.lo), (a.hi, b.hi)}; the channel lives in half-lane (c >> 2) & 1, register (c & 3) + 4 * (c >> 3)
-            auto pick = [&](auto cc) {
-                constexpr int c = decltype(cc)::value;
-                constexpr int reg = (c & 3) + 4 * (c >> 3);
-                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(omr[0][reg]), __float_as_uint(omr[1][reg]), false, false);
-                return __uint_as_float(((c >> 2) & 1) ? sw[1] : sw[0]);
-            };
-            o.dy = pick(std::integral_constant<int, 2 * tap>{});
-            o.dx = pick(std::integral_constant<int, 2 * tap + 1>{});
-            o.mk = pick(std::integral_constant<int, 18 + tap>{});
-            if (!my_in) o.mk = 0.0f;   // pixels of the tile overhang contribute nothing (and are never stored)
+#define DEFORM3_STAGE DEFORM3_PICK
+#include "deform3_stages.inl"
         } else {
             o = load_om(om_my, tap, my_in);
         }
-        if (!EMAVFI_P3_NO_CENSUS) omax = fmaxf(omax, fmaxf(fabsf(o.dy), fabsf(o.dx)));   // (one v_max3_f32 with |.| modifiers; NaN offsets are ignored)
-        const float py = fminf(fmaxf((fy_base + (float)ti) + o.dy, -2.0f), fy_max);
-        const float px = fminf(fmaxf((fx_base + (float)tj) + o.dx, -2.0f), fx_max);
-        const float fy = floorf(py), fx = floorf(px);
-        const int hl = (int)fy, wl = (int)fx;
-        const float lh = py - fy, lw = px - fx, uh = 1.0f - lh, uw = 1.0f - lw;
-        const float w4[4] = {o.mk * (uh * uw), o.mk * (uh * lw), o.mk * (lh * uw), o.mk * (lh * lw)};
+        constexpr bool CENSUS = !EMAVFI_P3_NO_CENSUS, PIN = false;
+#define DEFORM3_STAGE DEFORM3_SAMPLE
+#include "deform3_stages.inl"
         // window-local top-left corner; all four corners inside the staged window <=> 0 <= ly0 <= TR-2 and 0 <= lx0 <= TC-2
         const int ly0 = hl - ty0, lx0 = wl - tx0;
         const bool inside = (unsigned)ly0 <= (unsigned)(C::TR - 2) && (unsigned)lx0 <= (unsigned)(C::TC - 2);
@@ -303,32 +171,8 @@
     geom_tap(std::integral_constant<int, 3>{}); geom_tap(std::integral_constant<int, 4>{}); geom_tap(std::integral_constant<int, 5>{});
     geom_tap(std::integral_constant<int, 6>{}); geom_tap(std::integral_constant<int, 7>{}); geom_tap(std::integral_constant<int, 8>{});
 
-    // ---- the tail channels of all nine taps: three im2col k-groups, contracted first.  Half-lane h holds its OWN row's values;
-    // one swap per dword hands tap slots (4j + 2h, 4j + 2h + 1) of row m to lane (r, h) of fragment m.
-    const char *wtl = wbase_g + C::DCN_TAIL;
-    auto tail_mma = [&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        f16x8 wt[3];
-#pragma unroll
-        for (int n = 0; n < 3; ++n) wt[n] = *reinterpret_cast<const f16x8 *>(wtl + (j * 3 + n) * 1024 + (n < 2 ? lane16 : t3lane16));
-        unsigned bm[2][4];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int d = 0; d < 2; ++d) {
-                const auto sw = __builtin_amdgcn_permlane32_swap(tl[4 * j + u][d], tl[4 * j + 2 + u][d], false, false);
-                bm[0][2 * u + d] = sw[0];
-                bm[1][2 * u + d] = sw[1];
-            }
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const f16x8 xf = __builtin_bit_cast(f16x8, u32x4_t{bm[m][0], bm[m][1], bm[m][2], bm[m][3]});
-#pragma unroll
-            for (int n = 0; n < 2; ++n) mma_kg(acc[m][n], wt[n], xf);
-            mma_k32(acc3[m], wt[2], xf);
-        }
-    };
-    tail_mma(std::integral_constant<int, 0>{}); tail_mma(std::integral_constant<int, 1>{}); tail_mma(std::integral_constant<int, 2>{});
+#define DEFORM3_STAGE DEFORM3_TAIL_MMA
+#include "deform3_stages.inl"
     DEFORM_STAMP(ts_geom_all);
 
     // ---- 9 taps x 4 k-groups x 2 rows: two fragments from global weight fragments, the third from the LDS table.
@@ -473,20 +317,23 @@
         const unsigned long long below = (1ull << lane) - 1ull;
         // (py, px, mask) of a parked lane -> clamped corner descriptor (top-left pixel | x1 - x0 << 24 | y1 - y0 << 25) and the
         // validity-masked corner weights; lanes without `sel` get zero weights
+        // (its floor and weight products are its own, not stage SAMPLE's: they start from the stored position and mask, and the
+        // products sit inside the validity selects)
         auto fix_geom = [&](int tap, bool sel, unsigned &desc, unsigned &w01h, unsigned &w23h) {
+            typedef bool valid_t;
             const unsigned g0 = gm0[tap], g1 = gm1[tap], g2 = gm2[tap];
             const float py = sel ? __uint_as_float(g0) : 0.0f, px = sel ? __uint_as_float(g1) : 0.0f;
             const float mk = sel ? __uint_as_float(g2) : 0.0f;
             const float fy = floorf(py), fx = floorf(px);
             const int hl = (int)fy, wl = (int)fx, hh = hl + 1, wh = wl + 1;
             const float lh = py - fy, lw = px - fx, uh = 1.0f - lh, uw = 1.0f - lw;
-            const int hlc = min(max(hl, 0), H - 1), wlc = min(max(wl, 0), W - 1);
-            const int hhc = min(max(hh, 0), H - 1), whc = min(max(wh, 0), W - 1);
-            const bool vhl = (unsigned)hl < (unsigned)H, vhh = (unsigned)hh < (unsigned)H;
-            const bool vwl = (unsigned)wl < (unsigned)W, vwh = (unsigned)wh < (unsigned)W;
+#define DEFORM3_STAGE DEFORM3_CORNERS
+#include "deform3_stages.inl"
             const float w4[4] = {vhl && vwl ? mk * (uh * uw) : 0.0f, vhl && vwh ? mk * (uh * lw) : 0.0f,
                                  vhh && vwl ? mk * (lh * uw) : 0.0f, vhh && vwh ? mk * (lh * lw) : 0.0f};
-            desc = (__umul24((unsigned)hlc, (unsigned)W) + (unsigned)wlc) | ((unsigned)(whc - wlc) << 24) | ((unsigned)(hhc - hlc) << 25);
+#define DEFORM3_STAGE DEFORM3_CORNER_DESC
+#include "deform3_stages.inl"
+            desc = cdesc;
             w01h = __builtin_bit_cast(unsigned, f16x2_t{(half_t)w4[0], (half_t)w4[1]});
             w23h = __builtin_bit_cast(unsigned, f16x2_t{(half_t)w4[2], (half_t)w4[3]});
         };
@@ -494,9 +341,8 @@
         auto dma = [&](const char *src, unsigned dst) {
             asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(__builtin_amdgcn_readfirstlane(dst)) : "memory", "m0");
         };
-#pragma unroll 1
-        for (unsigned left = fb_taps; left != 0; left &= left - 1)
-            n_parked += (unsigned)__popcll(__ballot(((lane_fb >> __builtin_ctz(left)) & 1u) != 0));
+#define DEFORM3_STAGE DEFORM3_COUNT_PARKED
+#include "deform3_stages.inl"
         const bool convert = std::is_same<TS, bf16_t>::value && !p.in_f16;
         const char *wtl_fx = wbase_g + C::DCN_TAIL;
         const unsigned my_slot = (unsigned)lane & 31u, hb = (unsigned)lane >> 5;
@@ -629,49 +475,14 @@
         }
     }
     DEFORM_STAMP(ts_loop);
-    // ---- census of this launch (emavfi_forward_census / emavfi_mdcn_census): (wave, tap) groups that took the fix-up, samples outside the
-    // window, and the largest |offset| of a wave that had one - ONLY such waves pay for it (a same-box A/B priced an unconditional
-    // wave reduction + atomic at 40-55 us per launch, 3-4 %: profiles/r06_experiments_that_lost.txt).  64 slots of {u32 x 4} per launch,
-    // no-return atomics.  A launch without a flagged wave reports max |offset| 0 = "every sample inside the +-2 px window".
+    // ---- census: only a wave that had a sample outside its window pays for it
     if (!EMAVFI_P3_NO_CENSUS && __builtin_expect(fb_taps != 0, 0) && p.census) {
-        float om = my_in ? omax : 0.0f;
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) om = fmaxf(om, __shfl_xor(om, sh));
-        if (lane == 0) {
-            unsigned *cs = p.census + (blockIdx.x & 63u) * 4u;
-            (void)__hip_atomic_fetch_add(cs, (unsigned)__popc(fb_taps), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            (void)__hip_atomic_fetch_add(cs + 1, n_parked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            (void)__hip_atomic_fetch_max(cs + 2, __float_as_uint(om), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+#define DEFORM3_STAGE DEFORM3_CENSUS_RECORD
+#include "deform3_stages.inl"
     }
 
-    // ---- epilogue (no activation: ema_vfi.py:136-138 chains the blocks directly)
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        if (!in_img[m]) continue;
-        TS *op = reinterpret_cast<TS *>(p.out) + (((size_t)b * H + py_y[m]) * W + px_x) * p.out_ps;
-        // the third fragment: lanes < 32 hold channels 64..67 of their own pixel; 68..71 have zero weights (their bias alone)
-        auto store_third = [&](auto *o16) {
-            typedef typename std::remove_pointer<decltype(o16)>::type O;
-            typedef __attribute__((ext_vector_type(2))) O pair_t;
-            if (p.cstore > 64 && h == 0) {
-                const pair_t q0 = {(O)acc3[m][0], (O)acc3[m][1]}, q1 = {(O)acc3[m][2], (O)acc3[m][3]};
-                const pair_t q2 = {(O)p.bias[68], (O)p.bias[69]}, q3 = {(O)p.bias[70], (O)p.bias[71]};
-                *reinterpret_cast<uint4 *>(o16 + 64) = make_uint4(__builtin_bit_cast(unsigned, q0), __builtin_bit_cast(unsigned, q1),
-                                                                  __builtin_bit_cast(unsigned, q2), __builtin_bit_cast(unsigned, q3));
-            }
-        };
-        if (std::is_same<TS, bf16_t>::value && p.out_f16) {
-            half_t *oh = reinterpret_cast<half_t *>(op);
-#pragma unroll
-            for (int n = 0; n < 2; ++n) store_frag(oh + n * 32, acc[m][n], h, p.cstore - n * 32, [](float v, int) { return v; });
-            store_third(oh);
-        } else {
-#pragma unroll
-            for (int n = 0; n < 2; ++n) store_frag(op + n * 32, acc[m][n], h, p.cstore - n * 32, [](float v, int) { return v; });
-            store_third(op);
-        }
-    }
+#define DEFORM3_STAGE DEFORM3_EPILOGUE
+#include "deform3_stages.inl"
 #if EMAVFI_DEFORM_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     DEFORM_STAMP(ts_done);

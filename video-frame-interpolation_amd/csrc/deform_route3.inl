@@ -1,7 +1,8 @@
 // The ROUTED one-launch ModulatedDeformConvPack (include/emavfi.h, emavfi_forward_adaptive): one kernel per 16-bit
 // storage type that reads its block's route word in device memory (DeformParams::route) and runs either deform_pack3_kernel<TS, true>'s
 // window body (EMAVFI_ROUTE_WINDOW = 0) or deform_gather3_kernel<TS>'s window-free body (EMAVFI_ROUTE_GATHER = 1), statement for statement
-// (deform_pack3_body.inl / deform_gather3_body.inl): same DeformParams forms, same output, same census record.  The word is written on
+// (deform_pack3_body.inl / deform_gather3_body.inl, their common stages in deform3_stages.inl): same DeformParams forms, same output,
+// same census record.  The word is written on
 // the device by the adaptive forward's route selector (misc_kernels.hip, route_select_kernel), so a captured graph or a stream of
 // batches changes routes without a host read.
 //
@@ -55,15 +56,15 @@ __global__ __launch_bounds__(256, 2) void deform_pack3_kernel<Route3<DEFORM_ROUT
 static int launch_deform_route3(const DeformParams &p, hipStream_t s)
 {
     using C = Pack3;
-    static_assert(C::THREADS == Gather3::THREADS && C::TROWS == Gather3::TROWS && C::TCOLS == Gather3::TCOLS && Gather3::LDS_BYTES <= C::LDS_BYTES,
+    using G = Gather3;
+    static_assert(C::THREADS == G::THREADS && C::WAVES == G::WAVES && C::TROWS == G::TROWS && C::TCOLS == G::TCOLS && G::LDS_BYTES <= C::LDS_BYTES,
                   "the two bodies share the grid, the block and the LDS request");
+    // what the shared stages (deform3_stages.inl) take from either layout: only the row pitch TC and W3_OFF may differ
+    static_assert(C::SP == G::SP && C::PSB == G::PSB, "one pixel record: 9 pieces of 16 bytes");
+    static_assert(C::W3_TAP == G::W3_TAP && C::W3_BYTES == G::W3_BYTES, "one third-fragment table");
+    static_assert(C::DCN_TAP == G::DCN_TAP && C::DCN_W3 == G::DCN_W3 && C::DCN_TAIL == G::DCN_TAIL && C::OFF_TAIL == G::OFF_TAIL, "one weight blob");
     if (!p.route || !p.off_w || p.pack3 != 1 || !deform_pack3_shape(p.ck, p.nf, p.cin_real, p.cout_real)) return -2;
     if ((long long)p.H * p.W >= (1LL << 24)) return (int)hipErrorInvalidValue;   // the gather body's 24-bit pixel indices
     static PerDeviceOnce once;
-    auto *k = &deform_pack3_kernel<Route3<DEFORM_ROUTE3_TS>, true>;
-    if (const hipError_t e_ = set_lds_limit(once, reinterpret_cast<const void *>(k), C::LDS_BYTES); e_ != hipSuccess) return (int)e_;
-    const long long nwg = (long long)((p.W + C::TCOLS - 1) / C::TCOLS) * ((p.H + C::TROWS - 1) / C::TROWS) * p.B;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    k<<<(unsigned)nwg, C::THREADS, C::LDS_BYTES, s>>>(p);
-    return (int)hipGetLastError();
+    return deform3_launch<C>(&deform_pack3_kernel<Route3<DEFORM_ROUTE3_TS>, true>, once, C::LDS_BYTES, p, s);
 }
