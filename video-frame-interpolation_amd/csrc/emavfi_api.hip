@@ -90,6 +90,7 @@ struct Layer {
     int ring = 0;              // ConvParams::ring: 1 = stride 2, 64 -> 128 (regular packing for ck 64, nf 4); 2 = 64 -> 64 (regular packing for
                                // ck 64, nf 2); 3 = 65..67 -> 64 (that + the im2col tail of channels 64..66, 6 KiB)
     bool first6 = false;       // feat_ext_conv1 at mid_channels 64, 16-bit: a second copy of the weights in conv_first.inl's layout (10 KiB)
+    bool fp32 = false;         // Plan::dcn32: fp32 weights, packed for and run by the fp32 kernels whatever the plan's storage type
     bool x3 = false;           // EMAVFI_F32X3: three virtual chunks per real one (w_hi, w_lo, w_hi), activations as [hi | lo] f16 halves
 };
 
@@ -317,7 +318,7 @@ bool build_plan(Plan &P, int in_ch, int mid, int nb, int dtype)
         for (int i = 0; i < nb && ok; ++i) {
             P.dcn32[i] = mk(P.dcn[i].param, f, f);
             ok = deform_geometry(P.dcn32[i], 4);
-
+            P.dcn32[i].fp32 = true;
             P.dcn32[i].w_off = o; o = rup256(o + P.dcn32[i].w_bytes);
             P.dcn32[i].b_off = o; o = rup256(o + (size_t)P.dcn32[i].coutpad * sizeof(float));
         }
@@ -368,66 +369,6 @@ bool build_plan(Plan &P, int in_ch, int mid, int nb, int dtype)
 }
 
 #if defined(EMAVFI_DEFORM_STAMPS) && EMAVFI_DEFORM_STAMPS
-unsigned long long *debug_stamp_buffer();
-#endif
-int run_conv(const Plan &P, const Layer &L, const void *packed, const void *in, int in_ps, int Hin, int Win, void *out,
-             int out_ps, int out_coff, int cstore, int epi, int B, hipStream_t s, const float *bias_table = nullptr,
-             float *planar = nullptr, int nplanes = 0, const void *zeros = nullptr, const Layer *head = nullptr,
-             const FirstParams *first = nullptr, int epi2 = 0, int out_alt = 0, const Layer *second = nullptr, float *pool_part = nullptr,
-             float *out32 = nullptr, int out32_ps = 0)
-{
-    ConvParams c{};
-    c.out32 = L.x3 ? out32 : nullptr; c.out32_ps = out32_ps;
-    c.pool_part = pool_part;
-    if (second) {   // conv_ring2.inl: `second` runs behind L in the same launch; out / out_ps / cstore / out_alt are ITS output's
-        c.w2 = (const char *)packed + second->w_off;
-        c.bias2 = (const float *)((const char *)packed + second->b_off);
-    }
-    c.epi2 = epi2;
-    c.out_alt = out_alt;
-    c.out_fill = (L.ring == 2 && !head && !first && out && out_coff == 0 && cstore == 64 && (size_t)out_ps * P.esize == 144) ? 1 : 0;   // (also the fused pair's second layer)
-    if (head) {   // conv_ring.inl / conv_ring_tail.inl: L's rows stay in LDS, the planar head `head` is computed from them (planar / nplanes are the head's)
-        c.head_w = (const char *)packed + head->w_off;
-        c.head_bias = (const float *)((const char *)packed + head->b_off);
-    }
-    // a single-chunk layer wider than its input's pixel stride (CK = 80 fed from the 72-channel fusion buffers) reads
-    // the missing pieces as zeros
-    if (L.nchunk == 1 && in_ps < L.ck) c.in_pieces = in_ps * P.esize / 16;
-    c.round16 = P.amp ? 1 : 0;
-    if (L.x3) {   // EMAVFI_F32X3: pixels are [hi | lo] halves of the widths the caller names
-        c.x3 = 1; c.x3_lo_off = in_ps; in_ps *= 2;
-        if (epi == EPI_NONE || epi == EPI_RELU) { c.out_lo_off = out_ps; out_ps *= 2; }   // (EPI_OM / planar outputs are fp32 as in every mode)
-    }
-    c.zeros = zeros ? zeros : (const char *)packed + P.zero_off;
-    c.in = in; c.out = out; c.out_planar = planar;
-    c.w = (const char *)packed + L.w_off;
-    c.bias = bias_table ? bias_table : (const float *)((const char *)packed + L.b_off);
-    c.in_ps = in_ps; c.out_ps = out_ps; c.out_coff = out_coff;
-    c.Hin = Hin; c.Win = Win;
-    c.Hout = (Hin + L.stride - 1) / L.stride; c.Wout = (Win + L.stride - 1) / L.stride;
-    c.B = B; c.nchunk = L.nchunk; c.npass = L.npass; c.cstore = cstore;
-    c.epi = epi; c.nplanes = nplanes; c.bias_mode = bias_table ? 1 : 0;
-    c.ck = L.ck; c.nf = L.nf; c.stride = L.stride; c.mfma16 = L.mfma16 ? 1 : 0; c.ring = L.ring;
-#if defined(EMAVFI_DEFORM_STAMPS) && EMAVFI_DEFORM_STAMPS
-    if (L.ring == 4 && !planar && !getenv("EMAVFI_STAMP_RING")) c.out_planar = reinterpret_cast<float *>(debug_stamp_buffer());   // diagnostic build: conv_wreg.inl's stamps (tools/wreg_stamps.py)
-    {   // diagnostic build: the LDS-ring kernels' stamps (tools/ring_stamps.py); EMAVFI_STAMP_RING = ring | tail | head | ringtail | ringfirst
-        const char *sel = getenv("EMAVFI_STAMP_RING");
-        const char *kind = first ? "ringfirst" : (head && L.ring == 2) ? "head" : (head && L.mfma16) ? "ringtail" : L.ring == 3 ? "tail" : (L.ring == 2 && !second) ? "ring" : "";
-        if (sel && kind[0] && strcmp(sel, kind) == 0) c.stamps = debug_stamp_buffer();
-    }
-#endif
-#if defined(EMAVFI_DEFORM_STAMPS) && EMAVFI_DEFORM_STAMPS
-    if (const char *rep = getenv("EMAVFI_DEBUG_REPEAT_CONV"))   // diagnostic build: as EMAVFI_DEBUG_REPEAT_PACK, for the plain layers
-        if (!first && !(L.f16_of_bf16 && !L.deform))
-            for (int i = 1; i < atoi(rep); ++i)
-                if (const int rc = P.dtype == EMAVFI_F32 ? launch_conv3x3_f32(c, s) : P.dtype == EMAVFI_F16 ? launch_conv3x3_f16(c, s) : launch_conv3x3_bf16(c, s)) return rc;
-#endif
-    if (first) return P.dtype == EMAVFI_F16 ? launch_conv_ringfirst_f16(*first, c, s) : launch_conv_ringfirst_bf16(*first, c, s);
-    if (L.f16_of_bf16 && !L.deform) return launch_conv3x3_f16(c, s);   // feat16: f16 activations in, bf16-rounded weights stored as f16
-    return P.dtype == EMAVFI_F32 ? launch_conv3x3_f32(c, s) : P.dtype == EMAVFI_F16 ? launch_conv3x3_f16(c, s) : launch_conv3x3_bf16(c, s);
-}
-
-#if defined(EMAVFI_DEFORM_STAMPS) && EMAVFI_DEFORM_STAMPS
 // diagnostic build only (never the shipped library): a lazily allocated stamp buffer and its reader
 unsigned long long *debug_stamp_buffer()
 {
@@ -438,35 +379,111 @@ unsigned long long *debug_stamp_buffer()
 }
 #endif
 
+inline const char *blob_at(const void *packed, size_t off) { return (const char *)packed + off; }   // Layer::w_off / b_off, Plan::zero_off
+
+// One conv launch as its call site names it, `ConvCall{}.from(...).to(...)`: a setter per group of operands that travel together, an
+// operand no setter names is absent.  The setters fill the call's half of the kernels' ConvParams, run_conv adds the layer's half.
+struct ConvCall {
+    ConvParams c{};
+    const Layer *head = nullptr, *second = nullptr;
+    const FirstParams *first = nullptr;
+    ConvCall &from(const void *p, int ps, int H, int W) { c.in = p; c.in_ps = ps; c.Hin = H; c.Win = W; return *this; }    // channels-last input, its pixel stride (elements), its size
+    // conv_ring_first.inl: feat_ext_conv1 on the frames runs in front of L in the same launch; its ps-channel pixels exist only as an LDS ring
+    ConvCall &from(const FirstParams &fp, int ps) { first = &fp; c.in_ps = ps; c.Hin = fp.H; c.Win = fp.W; return *this; }
+    ConvCall &to(void *p, int ps, int stored) { c.out = p; c.out_ps = ps; c.cstore = stored; return *this; }   // channels-last output, its pixel stride, the channels stored
+    ConvCall &to_planes(float *p, int n) { c.out_planar = p; c.nplanes = n; return *this; }                    // NCHW fp32 output (EPI_PLANAR*), the fused head's where there is one
+    ConvCall &to_pool_sums(float *p, int channels) { c.pool_part = p; c.out_ps = c.cstore = channels; return *this; }   // conv_wreg.inl: per-tile channel sums, no output tensor
+    ConvCall &to_f32(float *p, int ps) { c.out32 = p; c.out32_ps = ps; return *this; }                         // EMAVFI_F32X3: the fp32 side output (or null), its pixel stride
+    ConvCall &act(int epi) { c.epi = epi; return *this; }
+    ConvCall &bias_rows(const float *table) { c.bias = table; c.bias_mode = 1; return *this; }                 // per-sample, per-border-class bias rows instead of the layer's bias
+    // conv_ring.inl / conv_ring_tail.inl: L's rows stay in LDS, the planar head l is computed from them (conv_ring_tail.inl's with the epilogue epi)
+    ConvCall &then_head(const Layer &l, int epi = 0) { head = &l; c.epi2 = epi; return *this; }
+    ConvCall &then_layer(const Layer &l) { second = &l; return *this; }   // conv_ring2.inl: l runs behind L in the same launch; the output operands are ITS output's
+    ConvCall &other16(bool on) { c.out_alt = on ? 1 : 0; return *this; }  // ConvParams::out_alt
+};
+
+// the conv3x3 launcher of kernel type kd (behind conv_ring_first.inl's layer where `first` is given: 16-bit types only)
+int launch_conv(int kd, const FirstParams *first, const ConvParams &c, hipStream_t s)
+{
+    if (first) return kd == EMAVFI_F16 ? launch_conv_ringfirst_f16(*first, c, s) : launch_conv_ringfirst_bf16(*first, c, s);
+    return kd == EMAVFI_F32 ? launch_conv3x3_f32(c, s) : kd == EMAVFI_F16 ? launch_conv3x3_f16(c, s) : launch_conv3x3_bf16(c, s);
+}
+
+int run_conv(const Plan &P, const Layer &L, const void *packed, int B, hipStream_t s, const ConvCall &a)
+{
+    const bool head = a.head != nullptr, first = a.first != nullptr;
+    ConvParams c = a.c;
+    if (!L.x3) c.out32 = nullptr;
+    if (a.second) { c.w2 = blob_at(packed, a.second->w_off); c.bias2 = (const float *)blob_at(packed, a.second->b_off); }
+    c.out_fill = (L.ring == 2 && !head && !first && c.out && c.cstore == 64 && (size_t)c.out_ps * P.esize == 144) ? 1 : 0;   // (also the fused pair's second layer)
+    if (head) { c.head_w = blob_at(packed, a.head->w_off); c.head_bias = (const float *)blob_at(packed, a.head->b_off); }
+    // a single-chunk layer wider than its input's pixel stride (CK = 80 fed from the 72-channel fusion buffers) reads the missing pieces as zeros
+    if (L.nchunk == 1 && c.in_ps < L.ck) c.in_pieces = c.in_ps * P.esize / 16;
+    c.round16 = P.amp ? 1 : 0;
+    if (L.x3) {   // EMAVFI_F32X3: pixels are [hi | lo] halves of the widths the caller names
+        c.x3 = 1; c.x3_lo_off = c.in_ps; c.in_ps *= 2;
+        if (c.epi == EPI_NONE || c.epi == EPI_RELU) { c.out_lo_off = c.out_ps; c.out_ps *= 2; }   // (EPI_OM / planar outputs are fp32 as in every mode)
+    }
+    c.zeros = blob_at(packed, P.zero_off); c.w = blob_at(packed, L.w_off);
+    if (!c.bias_mode) c.bias = (const float *)blob_at(packed, L.b_off);
+    c.Hout = (c.Hin + L.stride - 1) / L.stride; c.Wout = (c.Win + L.stride - 1) / L.stride;   // (out_coff stays 0: no layer writes into the middle of a pixel)
+    c.B = B; c.nchunk = L.nchunk; c.npass = L.npass; c.ck = L.ck; c.nf = L.nf; c.stride = L.stride; c.mfma16 = L.mfma16 ? 1 : 0; c.ring = L.ring;
+    const bool f16_kernels = L.f16_of_bf16 && !L.deform;   // feat16: f16 activations in, bf16-rounded weights stored as f16
+    const int kd = f16_kernels ? (int)EMAVFI_F16 : P.dtype;
+#if defined(EMAVFI_DEFORM_STAMPS) && EMAVFI_DEFORM_STAMPS
+    if (L.ring == 4 && !a.c.out_planar && !getenv("EMAVFI_STAMP_RING")) c.out_planar = reinterpret_cast<float *>(debug_stamp_buffer());   // diagnostic build: conv_wreg.inl's stamps (tools/wreg_stamps.py)
+    {   // diagnostic build: the LDS-ring kernels' stamps (tools/ring_stamps.py); EMAVFI_STAMP_RING = ring | tail | head | ringtail | ringfirst
+        const char *sel = getenv("EMAVFI_STAMP_RING");
+        const char *kind = first ? "ringfirst" : (head && L.ring == 2) ? "head" : (head && L.mfma16) ? "ringtail" : L.ring == 3 ? "tail" : (L.ring == 2 && !a.second) ? "ring" : "";
+        if (sel && kind[0] && strcmp(sel, kind) == 0) c.stamps = debug_stamp_buffer();
+    }
+    if (const char *rep = getenv("EMAVFI_DEBUG_REPEAT_CONV"))   // diagnostic build: as EMAVFI_DEBUG_REPEAT_PACK, for the plain layers
+        if (!first && !f16_kernels)
+            for (int i = 1; i < atoi(rep); ++i)
+                if (const int rc = launch_conv(kd, nullptr, c, s)) return rc;
+#endif
+    return launch_conv(kd, a.first, c, s);
+}
+
 // Which kernel runs a one-launch pack: EMAVFI_ROUTE_WINDOW (deform_pack3_kernel), EMAVFI_ROUTE_GATHER (deform_gather3_kernel: same
 // operands, same output, no window) or kRouteAdaptive (the routed pack, deform_route3.inl, reading the route word `word`:
 // emavfi_forward_adaptive).  The two non-window kinds exist only where require_gather_route() holds.
 constexpr int kRouteAdaptive = 2;
 struct PackRoute { int kind = EMAVFI_ROUTE_WINDOW; const unsigned *word = nullptr; };
 
-int run_deform(const Plan &P, const Layer &L, const void *packed, const void *x, int x_ps, float *om, void *out,
-               int out_ps, int cstore, int B, int H, int W, hipStream_t s, const void *zeros = nullptr, const Layer *off = nullptr,
-               const void *x_tail = nullptr, int tail_ps = 0, int force_dtype = -1, int in_f16 = 0, int out_f16 = 0, void *out16 = nullptr, int out16_ps = 0,
-               unsigned *census = nullptr, int out16_lo_off = 0, PackRoute route = {})
-{
-    const int kd = force_dtype >= 0 ? force_dtype : P.dtype;
+// One deformable launch as its call site names it (as ConvCall, on DeformParams); a layer stores all out_ps channels of its output pixels
+struct DeformCall {
     DeformParams d{};
-    d.census = census;
-    d.out16_lo_off = out16_lo_off;
+    const Layer *off = nullptr;
+    int route = EMAVFI_ROUTE_WINDOW;
+    // channels-last input, its pixel stride (elements), its size; the offsets / masks: read, or written first by the fused pack
+    DeformCall &from(const void *p, int ps, int H, int W, float *om) { d.x = p; d.x_ps = ps; d.H = H; d.W = W; d.om = om; return *this; }
+    DeformCall &to(void *p, int ps) { d.out = p; d.out_ps = d.cstore = ps; return *this; }
+    // fp32 DCN: ALSO the 16-bit rounding (or null), its pixel stride and, EMAVFI_F32X3, the offset of its lo half
+    DeformCall &to_16(void *p, int ps, int lo_off) { d.out16 = p; d.out16_ps = ps; d.out16_lo_off = lo_off; return *this; }
+    DeformCall &fused(const Layer &l) { off = &l; return *this; }   // fused ModulatedDeformConvPack: the kernel computes om itself (l = offset_conv in the kernel's on-chip type)
+    DeformCall &tail(const void *p, int ps) { d.x_tail = p; d.tail_ps = ps; return *this; }   // split input: the compact tail buffer (or null), its pixel stride
+    DeformCall &f16_link(int in, int out) { d.in_f16 = in; d.out_f16 = out; return *this; }   // the bf16 model's f16 hand-off
+    // one-launch pack: its census slots and its kernel (the route word shares out16's bytes: the routed pack has no fp16 side output)
+    DeformCall &routed(unsigned *census, PackRoute r) { d.census = census; route = r.kind; if (r.kind == kRouteAdaptive) d.route = r.word; return *this; }
+};
+
+// the deformable launcher of kernel type kd on a route; the gather and the routed pack are 16-bit only: -2 (no instantiation) otherwise
+int launch_deform(int kd, int route, const DeformParams &d, hipStream_t s)
+{
+    if (route == kRouteAdaptive) return kd == EMAVFI_F16 ? launch_deform_routed_f16(d, s) : kd == EMAVFI_BF16 ? launch_deform_routed_bf16(d, s) : -2;
+    if (route == EMAVFI_ROUTE_GATHER) return kd == EMAVFI_F16 ? launch_deform_gather_f16(d, s) : kd == EMAVFI_BF16 ? launch_deform_gather_bf16(d, s) : -2;
+    return kd == EMAVFI_F32 ? launch_deform_f32(d, s) : kd == EMAVFI_F16 ? launch_deform_f16(d, s) : launch_deform_bf16(d, s);
+}
+
+int run_deform(const Plan &P, const Layer &L, const void *packed, int B, hipStream_t s, const DeformCall &a)
+{
+    const int kd = L.fp32 ? (int)EMAVFI_F32 : P.dtype;
+    DeformParams d = a.d;
     d.x3 = L.x3 && L.pack3 == 3 ? 1 : 0;
-    d.x = x; d.om = om; d.out = out;
-    d.x_tail = x_tail; d.tail_ps = tail_ps;
-    if (off) {  // fused ModulatedDeformConvPack: the kernel computes om itself (off = the copy in the kernel's on-chip type)
-        d.off_w = (const char *)packed + off->w_off;
-        d.off_bias = (const float *)((const char *)packed + off->b_off);
-    }
-    d.w = (const char *)packed + L.w_off;
-    d.bias = (const float *)((const char *)packed + L.b_off);
-    d.zeros = zeros ? zeros : (const char *)packed + P.zero_off;
-    d.x_ps = x_ps; d.out_ps = out_ps; d.H = H; d.W = W; d.B = B; d.cstore = cstore; d.cin_real = L.cin_take; d.ck = L.ck; d.nf = L.nf;
-    d.cout_real = L.cout; d.pack3 = L.pack3; d.in_f16 = in_f16; d.out_f16 = out_f16;
-    d.out16 = out16; d.out16_ps = out16_ps;
-    if (route.kind == kRouteAdaptive) d.route = route.word;   // (shares out16's bytes: the routed pack has no fp16 side output)
+    if (a.off) { d.off_w = blob_at(packed, a.off->w_off); d.off_bias = (const float *)blob_at(packed, a.off->b_off); }
+    d.zeros = blob_at(packed, P.zero_off); d.w = blob_at(packed, L.w_off); d.bias = (const float *)blob_at(packed, L.b_off);
+    d.B = B; d.cin_real = L.cin_take; d.cout_real = L.cout; d.ck = L.ck; d.nf = L.nf; d.pack3 = L.pack3;
 #if defined(EMAVFI_DEFORM_STAMPS) && EMAVFI_DEFORM_STAMPS
     {   // diagnostic build: EMAVFI_STAMP_PACK=i records only the i-th deformable launch of every 3 (default: every launch,
         // i.e. what is read back is the last pack of a forward)
@@ -475,31 +492,22 @@ int run_deform(const Plan &P, const Layer &L, const void *packed, const void *x,
         if ((!sel || (calls % 3) == atoi(sel)) && !getenv("EMAVFI_STAMP_RING")) d.stamps = debug_stamp_buffer();   // (the ring kernels' stamps share the buffer)
         ++calls;
     }
-#endif
-#if defined(EMAVFI_DEFORM_STAMPS) && EMAVFI_DEFORM_STAMPS
     // diagnostic build: EMAVFI_DEBUG_REPEAT_PACK=n launches the kernel n times back to back (same operands, same result: the input is
     // not the output) - what the board's power and clock are under THIS kernel alone (tools/power_per_kernel.py)
     if (const char *rep = getenv("EMAVFI_DEBUG_REPEAT_PACK"))
         for (int i = 1; i < atoi(rep); ++i)
-            if (const int rc = kd == EMAVFI_F32 ? launch_deform_f32(d, s) : kd == EMAVFI_F16 ? launch_deform_f16(d, s) : launch_deform_bf16(d, s)) return rc;
+            if (const int rc = launch_deform(kd, EMAVFI_ROUTE_WINDOW, d, s)) return rc;
 #endif
-    // the routed pack (deform_route3.inl): the route word picks the window or the gather body; 16-bit kinds only
-    if (route.kind == kRouteAdaptive) return kd == EMAVFI_F16 ? launch_deform_routed_f16(d, s) : kd == EMAVFI_BF16 ? launch_deform_routed_bf16(d, s) : -2;
-    // the window-free route of the one-launch pack (deform_gather3.inl): 16-bit kinds only, -2 (no instantiation) for anything else
-    if (route.kind == EMAVFI_ROUTE_GATHER) return kd == EMAVFI_F16 ? launch_deform_gather_f16(d, s) : kd == EMAVFI_BF16 ? launch_deform_gather_bf16(d, s) : -2;
-    return kd == EMAVFI_F32 ? launch_deform_f32(d, s) : kd == EMAVFI_F16 ? launch_deform_f16(d, s) : launch_deform_bf16(d, s);
+    return launch_deform(kd, a.route, d, s);
 }
 
+// (L.param, L.param + 1 of `params`: the layer's weight and bias; L.w_off / L.b_off: where they go in `packed`)
 int pack_layer(const Layer &L, const void *const *params, void *packed, int dtype, hipStream_t s, bool bias_f16 = false)
 {
     PackDesc d{L.cout, L.cin_raw, L.cin_off, L.cin_take, L.ck, L.nchunk, L.nf, L.npass, L.perm, L.f16_of_bf16 ? 1 : 0, bias_f16 ? 1 : 0};
-    d.mfma16 = L.mfma16 ? 1 : 0;
-    d.ring = L.ring;
-    d.first6 = L.first6 ? 1 : 0;
-    d.pack3 = L.pack3;
-    d.x3 = L.x3 ? 1 : 0;
+    d.mfma16 = L.mfma16 ? 1 : 0; d.ring = L.ring; d.first6 = L.first6 ? 1 : 0; d.pack3 = L.pack3; d.x3 = L.x3 ? 1 : 0;
     return launch_pack_conv((const float *)params[L.param], (const float *)params[L.param + 1], (char *)packed + L.w_off,
-                            (float *)((char *)packed + L.b_off), d, L.f16_of_bf16 ? (int)EMAVFI_F16 : dtype, s);
+                            (float *)((char *)packed + L.b_off), d, L.f16_of_bf16 ? (int)EMAVFI_F16 : L.fp32 ? (int)EMAVFI_F32 : dtype, s);
 }
 
 struct Workspace {
@@ -675,13 +683,13 @@ int attention_block(const Plan &P, int i, const void *packed, const void *x, voi
         char nm[96];
         snprintf(nm, sizeof nm, "%s%s,ck=%d,nf=%d> offset_conv+dcn_v2", kPrefix[route.kind], dtype_name(P.dtype), P.dcn[i].ck, P.dcn[i].nf);
         EMAVFI_STEP(rec, nm, fl + 2.0 * 9.0 * cf * cf * px, px * (2.0 * cf * e) + 9.0 * cf * (cf + 27.0) * e,
-                    run_deform(P, P.dcn[i], packed, x, P.fps, om, y, P.fps, P.fps, B, H, W, s, nullptr, P.has_offh ? &P.offh[i] : &P.off[i], x_tail, kTailPs,
-                               -1, in_f16, out_f16, nullptr, 0, census, 0, route));
+                    run_deform(P, P.dcn[i], packed, B, s, DeformCall{}.from(x, P.fps, H, W, om).to(y, P.fps).fused(P.has_offh ? P.offh[i] : P.off[i])
+                                                              .tail(x_tail, kTailPs).f16_link(in_f16, out_f16).routed(census, route)));
     } else {
         if (x_tail || in_f16 || out_f16) return fail(EMAVFI_E_UNSUPPORTED, "attention block: split tail / f16 hand-off need the one-launch pack kernel");
-        EMAVFI_STEP(rec, conv_name(P, P.off[i]) + " offset_conv", fl, by, run_conv(P, P.off[i], packed, x, P.fps, H, W, om, 32, 0, 32, EPI_OM, B, s));
+        EMAVFI_STEP(rec, conv_name(P, P.off[i]) + " offset_conv", fl, by, run_conv(P, P.off[i], packed, B, s, ConvCall{}.from(x, P.fps, H, W).to(om, 32, 32).act(EPI_OM)));
         EMAVFI_STEP(rec, deform_name(P, P.dcn[i]) + " dcn_v2", 2.0 * 9.0 * cf * cf * px, px * (2.0 * cf * e + 27.0 * 4.0) + 9.0 * cf * cf * e,
-                    run_deform(P, P.dcn[i], packed, x, P.fps, om, y, P.fps, P.fps, B, H, W, s));
+                    run_deform(P, P.dcn[i], packed, B, s, DeformCall{}.from(x, P.fps, H, W, om).to(y, P.fps)));
     }
     return EMAVFI_OK;
 }
@@ -696,14 +704,14 @@ int attention_block_amp(const Plan &P, int i, const void *packed, const void *x1
     const size_t npx = (size_t)B * H * W;
     double fl, by;
     conv_work(P, P.off[i], B, H, W, 4.0, fl, by);
-    EMAVFI_STEP(rec, conv_name(P, P.off[i]) + " offset_conv", fl, by, run_conv(P, P.off[i], packed, x16, P.fps, H, W, om, 32, 0, 32, EPI_OM, B, s));
+    EMAVFI_STEP(rec, conv_name(P, P.off[i]) + " offset_conv", fl, by, run_conv(P, P.off[i], packed, B, s, ConvCall{}.from(x16, P.fps, H, W).to(om, 32, 32).act(EPI_OM)));
     // (want16, not the pointer, decides: the enumeration-only pass has no buffers and must list the launches the real pass runs)
     const bool both = amp_dcn_writes_fp16(P, i) && want16;
     EMAVFI_STEP(rec, both ? (P.x3 ? "deform<f32,ck=80,nf=3> dcn_v2 (exact fp32; writes fp32 + its f16 hi / lo halves)" : "deform<f32,ck=80,nf=3> dcn_v2 (fp32 under autocast; writes fp32 + its fp16 rounding)")
                           : "deform<f32,ck=80,nf=3> dcn_v2 (fp32 under autocast)",
                 2.0 * 9.0 * cf * cf * px, px * (2.0 * cf * 4.0 + 27.0 * 4.0 + (both ? cf * 2.0 * (P.x3 ? 2 : 1) : 0.0)) + 9.0 * cf * cf * 4.0,
-                run_deform(P, P.dcn32[i], packed, xF, P.fpad, om, yF, P.fpad, P.fpad, B, H, W, s, nullptr, nullptr, nullptr, 0, EMAVFI_F32, 0, 0,
-                           both ? y16 : nullptr, P.fps * (P.x3 ? 2 : 1), nullptr, both && P.x3 ? P.fps : 0));
+                run_deform(P, P.dcn32[i], packed, B, s, DeformCall{}.from(xF, P.fpad, H, W, om).to(yF, P.fpad)
+                                                            .to_16(both ? y16 : nullptr, P.fps * (P.x3 ? 2 : 1), both && P.x3 ? P.fps : 0)));
     if (!both && want16)
         EMAVFI_STEP(rec, "fusion_round", 0, px * cf * 6.0, launch_convert_cl(yF, y16, npx, P.fpad, P.fps * (P.x3 ? 2 : 1), 0, P.fpad, 0, s, P.x3 ? P.fps : 0));
     return EMAVFI_OK;
@@ -718,24 +726,22 @@ int context_stage(const Plan &P, const void *packed, const void *feat_cl, const 
     double fl, by;
     conv_work(P, P.c0, B, H, W, e, fl, by);
     EMAVFI_STEP(rec, conv_name(P, P.c0) + " context_encoding.0", fl, by,
-                run_conv(P, P.c0, packed, feat_cl, P.fps, H, W, f.c1, f.p2, 0, f.p2, EPI_RELU, B, s, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0,
-                         P.feat16 ? 1 : 0));
+                run_conv(P, P.c0, packed, B, s, ConvCall{}.from(feat_cl, P.fps, H, W).to(f.c1, f.p2, f.p2).act(EPI_RELU).other16(P.feat16)));
     conv_work(P, P.c1, B, f.H2, f.W2, e, fl, by);
     EMAVFI_STEP(rec, conv_name(P, P.c1) + " context_encoding.1", fl, by,
-                run_conv(P, P.c1, packed, f.c1, f.p2, f.H2, f.W2, f.c2, f.p4, 0, f.p4, EPI_RELU, B, s));
+                run_conv(P, P.c1, packed, B, s, ConvCall{}.from(f.c1, f.p2, f.H2, f.W2).to(f.c2, f.p4, f.p4).act(EPI_RELU)));
     conv_work(P, P.c2, B, f.H4, f.W4, e, fl, by);
     // conv_wreg.inl at the reference width: the layer's only reader is the pool, so the kernel writes per-tile channel sums instead of the
     // tensor (no 236 MB store + read at B = 8 x 720p); avg_pool_partial then adds tiles instead of pixels.  EMAVFI_CONV_POOLFUSE=0: A/B
     const bool poolfuse = P.c2.ring == 4 && f.p4 == 256 && !(emavfi_switches() & SW_NO_POOLFUSE);
     if (poolfuse) {
         EMAVFI_STEP(rec, conv_name(P, P.c2) + " context_encoding.2 + pool (tile sums)", fl, by - (double)B * f.H4 * f.W4 * 4 * mid * e,
-                    run_conv(P, P.c2, packed, f.c2, f.p4, f.H4, f.W4, nullptr, f.p4, 0, f.p4, EPI_RELU, B, s, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr,
-                             f.tpart));
+                    run_conv(P, P.c2, packed, B, s, ConvCall{}.from(f.c2, f.p4, f.H4, f.W4).to_pool_sums(f.tpart, f.p4).act(EPI_RELU)));
         EMAVFI_STEP(rec, "avg_pool_partial", 0, (double)B * f.ntiles * 4 * mid * 4,
                     launch_pool_partial(f.tpart, f.part, B, f.ntiles, f.p4, f.p4, f.nparts2, EMAVFI_F32, s));
     } else {
         EMAVFI_STEP(rec, conv_name(P, P.c2) + " context_encoding.2", fl, by,
-                    run_conv(P, P.c2, packed, f.c2, f.p4, f.H4, f.W4, f.c3, f.p4, 0, f.p4, EPI_RELU, B, s));
+                    run_conv(P, P.c2, packed, B, s, ConvCall{}.from(f.c2, f.p4, f.H4, f.W4).to(f.c3, f.p4, f.p4).act(EPI_RELU)));
         const int hw = P.x3 ? 2 : 1;   // EMAVFI_F32X3: the hi and the lo halves are pooled as 2 x p4 channels and added in the fold
         EMAVFI_STEP(rec, "avg_pool_partial", 0, (double)B * f.H4 * f.W4 * 4 * mid * e * hw,
                     launch_pool_partial(f.c3, f.part, B, f.H4 * f.W4, hw * f.p4, hw * f.p4, f.nparts, dtype, s));
@@ -755,7 +761,7 @@ int reconstruction_stage(const Plan &P, const void *packed, const void *x, const
     double fl, by;
     conv_work(P, P.r0, B, H, W, e, fl, by);
     EMAVFI_STEP(rec, conv_name(P, P.r0) + " reconstruction.0", fl, by,
-                run_conv(P, P.r0, packed, x, P.fps, H, W, f.fA, P.p_mid, 0, P.p_mid, EPI_RELU, B, s));
+                run_conv(P, P.r0, packed, B, s, ConvCall{}.from(x, P.fps, H, W).to(f.fA, P.p_mid, P.p_mid).act(EPI_RELU)));
     // reconstruction.1 + .2 in one launch (conv_ring_tail.inl): .1's rows never leave the LDS.  EMAVFI_CONV_TAILFUSE=0: two
     if (P.r1.mfma16 && P.r1.ck == 64 && P.r1.nf == 1 && P.r1.cout == 32 && P.r1.ring == 0 && P.r2.mfma16 && P.r2.ck == 32 && P.r2.nf == 1 && P.r2.cout <= 3 &&
         !(sw & SW_NO_TAILFUSE)) {
@@ -765,14 +771,14 @@ int reconstruction_stage(const Plan &P, const void *packed, const void *x, const
         const double mid_bytes = (double)B * H * W * P.r1.cout * e;
         EMAVFI_STEP(rec, "conv3x3+tail<" + std::string(dtype_name(P.dtype)) + ",64->32->" + std::to_string(P.r2.cout) + "> reconstruction.1+.2(tanh)",
                     fl + fl2, by + by2 - 2 * mid_bytes,
-                    run_conv(P, P.r1, packed, f.fA, P.p_mid, H, W, nullptr, 0, 0, 0, EPI_RELU, B, s, nullptr, out, C, nullptr, &P.r2, nullptr, EPI_PLANAR_TANH01));
+                    run_conv(P, P.r1, packed, B, s, ConvCall{}.from(f.fA, P.p_mid, H, W).act(EPI_RELU).then_head(P.r2, EPI_PLANAR_TANH01).to_planes(out, C)));
     } else {
         conv_work(P, P.r1, B, H, W, e, fl, by);
         EMAVFI_STEP(rec, conv_name(P, P.r1) + " reconstruction.1", fl, by,
-                    run_conv(P, P.r1, packed, f.fA, P.p_mid, H, W, f.fB, f.p_half, 0, f.p_half, EPI_RELU, B, s));
+                    run_conv(P, P.r1, packed, B, s, ConvCall{}.from(f.fA, P.p_mid, H, W).to(f.fB, f.p_half, f.p_half).act(EPI_RELU)));
         conv_work(P, P.r2, B, H, W, 4.0, fl, by);
         EMAVFI_STEP(rec, conv_name(P, P.r2) + " reconstruction.2(tanh)", fl, by,
-                    run_conv(P, P.r2, packed, f.fB, f.p_half, H, W, nullptr, 0, 0, 0, EPI_PLANAR_TANH01, B, s, nullptr, out, C));
+                    run_conv(P, P.r2, packed, B, s, ConvCall{}.from(f.fB, f.p_half, H, W).act(EPI_PLANAR_TANH01).to_planes(out, C)));
     }
     return EMAVFI_OK;
 }
@@ -878,7 +884,7 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
                 conv_work(P, P.blk[0], B, H, W, e, fl2, by2);
                 EMAVFI_STEP(rec, std::string("conv_first+conv3x3<") + dtype_name(dtype) + ",6->64->64> cat+feat_ext_conv1+conv_block_0", fl + fl2,
                             px * (8.0 * C + mid * e) + 9.0 * 2 * C * mid * e + 9.0 * mid * mid * e,
-                            run_conv(P, P.blk[0], packed, nullptr, P.p_mid, H, W, dst, last ? P.fps : P.p_mid, 0, P.p_mid, EPI_RELU, B, s, nullptr, nullptr, 0, nullptr, nullptr, &fp));
+                            run_conv(P, P.blk[0], packed, B, s, ConvCall{}.from(fp, P.p_mid).to(dst, last ? P.fps : P.p_mid, P.p_mid).act(EPI_RELU)));
                 first_blk = 1;
                 cur = f.fB; nxt = f.fA;
             } else {
@@ -889,7 +895,7 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
             EMAVFI_STEP(rec, "pack_input", 0, px * (8.0 * C + 2.0 * C * e * (P.x3 ? 2 : 1)),
                         P.x3 ? launch_pack_input_x3(frame1, frame2, f.in16, B, C, H, W, 16, s) : launch_pack_input(frame1, frame2, f.in16, B, C, H, W, 16, dtype, s));
             EMAVFI_STEP(rec, conv_name(P, P.conv1) + " feat_ext_conv1", fl, by,
-                        run_conv(P, P.conv1, packed, f.in16, 16, H, W, f.fA, P.p_mid, 0, P.p_mid, EPI_RELU, B, s));
+                        run_conv(P, P.conv1, packed, B, s, ConvCall{}.from(f.in16, 16, H, W).to(f.fA, P.p_mid, P.p_mid).act(EPI_RELU)));
         }
     }
     for (int i = first_blk; i < P.nb; ++i) {
@@ -906,14 +912,14 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
             const double mid_bytes = (double)B * H * W * mid * e;   // the intermediate tensor is neither written nor read
             EMAVFI_STEP(rec, "conv3x3+conv3x3<" + std::string(dtype_name(dtype)) + ",64->64->64> feat_ext_blocks." + std::to_string(i) + "+" + std::to_string(j),
                         fl + fl2, by + by2 - 2 * mid_bytes,
-                        run_conv(P, P.blk[i], packed, cur, P.p_mid, H, W, dst, last ? P.fps : P.p_mid, 0, P.p_mid, EPI_RELU, B, s, nullptr, nullptr, 0, nullptr,
-                                 nullptr, nullptr, 0, last && feat16 ? 1 : 0, &P.blk[j]));
+                        run_conv(P, P.blk[i], packed, B, s, ConvCall{}.from(cur, P.p_mid, H, W).act(EPI_RELU).then_layer(P.blk[j])
+                                                                .to(dst, last ? P.fps : P.p_mid, P.p_mid).other16(last && feat16)));
             i = j;
         } else {
             // (EMAVFI_F32X3: the last block also writes `feat` in fp32 into the fusion tensor the exact DCN reads)
             EMAVFI_STEP(rec, conv_name(P, P.blk[i]) + " feat_ext_blocks", fl, by + (last && P.x3 ? px * mid * 4.0 : 0.0),
-                        run_conv(P, P.blk[i], packed, cur, P.p_mid, H, W, dst, last ? P.fps : P.p_mid, 0, P.p_mid, EPI_RELU, B, s, nullptr, nullptr, 0, nullptr,
-                                 nullptr, nullptr, 0, last && feat16 ? 1 : 0, nullptr, nullptr, last && P.x3 ? f.fuF0 : nullptr, P.fpad));
+                        run_conv(P, P.blk[i], packed, B, s, ConvCall{}.from(cur, P.p_mid, H, W).to(dst, last ? P.fps : P.p_mid, P.p_mid).act(EPI_RELU)
+                                                                .other16(last && feat16).to_f32(last && P.x3 ? f.fuF0 : nullptr, P.fpad)));
         }
         if (!last) { void *t = cur; cur = nxt; nxt = t; }
     }
@@ -929,8 +935,7 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
     // --- motion estimation (ema_vfi.py:124-126); the broadcast-context concat is a per-border-class bias
     conv_work(P, P.m0, B, H, W, e, fl, by);
     EMAVFI_STEP(rec, conv_name(P, P.m0) + " motion_estimation.0(ctx folded)", fl, by,
-                run_conv(P, P.m0, packed, f.fu0, P.fps, H, W, f.fA, P.p_mid, 0, P.p_mid, EPI_RELU, B, s, f.table, nullptr, 0, nullptr, nullptr, nullptr, 0,
-                         feat16 ? 1 : 0));
+                run_conv(P, P.m0, packed, B, s, ConvCall{}.from(f.fu0, P.fps, H, W).bias_rows(f.table).to(f.fA, P.p_mid, P.p_mid).act(EPI_RELU).other16(feat16)));
     // motion_estimation.1 + .2 in one launch (conv_ring.inl, HEAD): .1's rows never leave the LDS.  EMAVFI_CONV_HEAD=0: two launches
     if (P.m1.ring == 2 && P.m2.mfma16 && P.m2.ck == 64 && P.m2.nf == 1 && P.m2.cout <= 2 && !(sw & SW_NO_HEAD)) {
         double fl2, by2;
@@ -940,14 +945,14 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
         const double mid_bytes = (double)B * H * W * mid * e;
         EMAVFI_STEP(rec, "conv3x3+head<" + std::string(dtype_name(P.dtype)) + ",64->64->" + std::to_string(P.m2.cout) + "> motion_estimation.1+.2(flow)",
                     fl + fl2, by + by2 - 2 * mid_bytes,
-                    run_conv(P, P.m1, packed, f.fA, P.p_mid, H, W, nullptr, 0, 0, 0, EPI_RELU, B, s, nullptr, f.flow, 2, nullptr, &P.m2));
+                    run_conv(P, P.m1, packed, B, s, ConvCall{}.from(f.fA, P.p_mid, H, W).act(EPI_RELU).then_head(P.m2).to_planes(f.flow, 2)));
     } else {
         conv_work(P, P.m1, B, H, W, e, fl, by);
         EMAVFI_STEP(rec, conv_name(P, P.m1) + " motion_estimation.1", fl, by,
-                    run_conv(P, P.m1, packed, f.fA, P.p_mid, H, W, f.fB, P.p_mid, 0, P.p_mid, EPI_RELU, B, s));
+                    run_conv(P, P.m1, packed, B, s, ConvCall{}.from(f.fA, P.p_mid, H, W).to(f.fB, P.p_mid, P.p_mid).act(EPI_RELU)));
         conv_work(P, P.m2, B, H, W, 4.0, fl, by);
         EMAVFI_STEP(rec, conv_name(P, P.m2) + " motion_estimation.2(flow)", fl, by,
-                    run_conv(P, P.m2, packed, f.fB, P.p_mid, H, W, nullptr, 0, 0, 0, EPI_PLANAR, B, s, nullptr, f.flow, 2));
+                    run_conv(P, P.m2, packed, B, s, ConvCall{}.from(f.fB, P.p_mid, H, W).act(EPI_PLANAR).to_planes(f.flow, 2)));
     }
     if (!rec.dry && taps && taps[2])
         if (hipMemcpyAsync(taps[2], f.flow, npx * 2 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
@@ -1098,7 +1103,7 @@ int emavfi_pack_weights(int in_channels, int mid_channels, int num_blocks, const
         EMAVFI_TRY(pack_layer(P.off[i], params, packed, dtype, s, b16), "pack offset_conv");
         if (P.has_offh) EMAVFI_TRY(pack_layer(P.offh[i], params, packed, dtype, s), "pack offset_conv (f16 fragments)");
         EMAVFI_TRY(pack_layer(P.dcn[i], params, packed, dtype, s), "pack dcn_v2");
-        if (P.wide()) EMAVFI_TRY(pack_layer(P.dcn32[i], params, packed, EMAVFI_F32, s), "pack dcn_v2 (fp32 master weights)");
+        if (P.wide()) EMAVFI_TRY(pack_layer(P.dcn32[i], params, packed, dtype, s), "pack dcn_v2 (fp32 master weights)");
     }
     EMAVFI_TRY(pack_layer(P.r0, params, packed, dtype, s, b16), "pack recon0");
     EMAVFI_TRY(pack_layer(P.r1, params, packed, dtype, s, b16), "pack recon1");
@@ -1328,29 +1333,47 @@ int emavfi_postprocess_u8(const float *frames_nchw, unsigned char *out_hwc, int 
     return EMAVFI_OK;
 }
 
-// ---- stage-level entries (diagnostics / parity tests of single operators) ----
-static bool single_conv_layer(Layer &L, int Cin, int Cout, int stride, int esize, bool x3 = false)
+// ---- stage-level entries (diagnostics / parity tests of single operators): one layer, packed into the workspace and run inside one call ----
+// Their plan - the kernel storage type (EMAVFI_F32X3: the f16 kernels on [hi | lo] halves) and, from op_carve, the zero page - and
+// their layer, as the plan of a model lays it out: a bf16 DCN on the LDS-window kernel contracts bf16-rounded weights stored as f16
+static bool op_layer(Plan &P, Layer &L, bool deform, int Cin, int Cout, int stride, int dtype)
 {
+    P = Plan{};
+    P.x3 = dtype == EMAVFI_F32X3; P.dtype = P.x3 ? (int)EMAVFI_F16 : dtype; P.esize = P.dtype == EMAVFI_F32 ? 4 : 2;
     L = mk(0, Cout, Cin, stride);
-    return conv_geometry(L, esize, read_layout_env(), x3);   // stage-level entry: packs and runs inside one call
+    if (!deform) return conv_geometry(L, P.esize, read_layout_env(), P.x3);   // (the layout switches per call: packs and runs inside one call)
+    if (!deform_geometry(L, P.esize)) return false;
+    if (dtype != EMAVFI_F32 && deform_pack3_shape(L.ck, L.nf, L.cin_take, L.cout)) L.pack3 = 1;
+    if (dtype == EMAVFI_F32 && deform_f32w_shape(L.ck, L.nf, L.cin_take, L.cout)) L.pack3 = 3;
+    L.f16_of_bf16 = dtype == EMAVFI_BF16 && L.pack3 == 1;
+    return true;
+}
+// the workspace of both: channels-last input, offsets / masks (deformable), the packed layer - `packed` is the workspace itself, the
+// layer's and the plan's offsets are relative to it -, channels-last output, zero page
+struct OpBuffers { void *xcl, *ycl, *zpage; float *om; };
+static OpBuffers op_carve(Plan &P, Layer &L, Workspace &ws, int B, int H, int W)
+{
+    const size_t e = (size_t)P.esize * (L.x3 ? 2 : 1), px = (size_t)B * H * W;   // (EMAVFI_F32X3 convolution: [hi | lo] halves per pixel)
+    OpBuffers b{};
+    b.xcl = ws.take(px * L.cin_pad * e);
+    if (L.deform) b.om = (float *)ws.take(px * 32 * sizeof(float));
+    L.w_off = ws.used; ws.take(L.w_bytes);
+    L.b_off = ws.used; ws.take((size_t)L.coutpad * sizeof(float));
+    b.ycl = ws.take((size_t)B * ((H + L.stride - 1) / L.stride) * ((W + L.stride - 1) / L.stride) * rup(L.cout, 16) * e);
+    P.zero_off = ws.used; b.zpage = ws.take(256);
+    return b;
 }
 
 size_t emavfi_conv3x3_workspace_bytes(int B, int Cin, int Cout, int H, int W, int stride, int dtype)
 {
+    Plan P;
     Layer L;
-    const bool x3 = dtype == EMAVFI_F32X3;
-    const int e = dtype == EMAVFI_F32 ? 4 : 2;
-    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || (stride != 1 && stride != 2) || !single_conv_layer(L, Cin, Cout, stride, e, x3)) {
+    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || (stride != 1 && stride != 2) || !op_layer(P, L, false, Cin, Cout, stride, dtype)) {
         fail(EMAVFI_E_UNSUPPORTED, "conv3x3: no kernel instantiation for Cin=%d Cout=%d stride=%d", Cin, Cout, stride);
         return 0;
     }
-    const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
     Workspace ws{nullptr, 0, 0};
-    ws.take((size_t)B * H * W * L.cin_pad * e * (x3 ? 2 : 1));
-    ws.take(L.w_bytes);
-    ws.take((size_t)L.coutpad * sizeof(float));
-    ws.take((size_t)B * Ho * Wo * rup(Cout, 16) * e * (x3 ? 2 : 1));
-    ws.take(256);
+    op_carve(P, L, ws, B, H, W);
     return ws.used;
 }
 
@@ -1359,63 +1382,49 @@ int emavfi_conv3x3(const float *x, const float *weight, const float *bias, float
 {
     if (dtype != EMAVFI_F32 && dtype != EMAVFI_BF16 && dtype != EMAVFI_F16 && dtype != EMAVFI_F32X3) return fail(EMAVFI_E_ARG, "conv3x3: bad dtype %d", dtype);
     if (!x || !weight || !y || !workspace) return fail(EMAVFI_E_ARG, "conv3x3: null pointer");
-    const bool x3 = dtype == EMAVFI_F32X3;   // the three-term f16 split: [hi | lo] halves in, fp32-accurate result out
-    if (x3) dtype = EMAVFI_F16;
     if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || (stride != 1 && stride != 2)) return fail(EMAVFI_E_ARG, "conv3x3: bad shape");
     if (act < EMAVFI_ACT_NONE || act > EMAVFI_ACT_TANH01) return fail(EMAVFI_E_ARG, "conv3x3: bad activation %d", act);
     if (act == EMAVFI_ACT_TANH01 && Cout > 4) return fail(EMAVFI_E_UNSUPPORTED, "conv3x3: TANH01 epilogue needs Cout <= 4");
-    Plan P{};
-    P.dtype = dtype; P.esize = dtype == EMAVFI_F32 ? 4 : 2;
+    Plan P;
     Layer L;
-    if (!single_conv_layer(L, Cin, Cout, stride, P.esize, x3))
+    if (!op_layer(P, L, false, Cin, Cout, stride, dtype))
         return fail(EMAVFI_E_UNSUPPORTED, "conv3x3: no kernel instantiation for Cin=%d Cout=%d stride=%d", Cin, Cout, stride);
-    P.x3 = x3;
-    const int hw = x3 ? 2 : 1;
+    const bool x3 = P.x3;   // the three-term f16 split: [hi | lo] halves in, fp32-accurate result out; dtype: the kernel storage type from here on
+    dtype = P.dtype;
     // the kernels' DMA source offsets inside one sample are 32-bit (conv3x3.inl, conv_dma_src)
     if ((size_t)H * W * L.cin_pad * P.esize >= ((size_t)1 << 32)) return fail(EMAVFI_E_ARG, "conv3x3: one sample's input plane must be < 4 GiB");
     const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride, ops = rup(Cout, 16);
     Workspace ws{(char *)workspace, workspace_bytes, 0};
-    void *xcl = ws.take((size_t)B * H * W * L.cin_pad * P.esize * hw);
-    void *wp = ws.take(L.w_bytes);
-    float *bp = (float *)ws.take((size_t)L.coutpad * sizeof(float));
-    void *ycl = ws.take((size_t)B * Ho * Wo * ops * P.esize * hw);
-    void *zpage = ws.take(256);
+    const OpBuffers b = op_carve(P, L, ws, B, H, W);
     if (ws.used > workspace_bytes) return fail(EMAVFI_E_WORKSPACE, "conv3x3: workspace needs %zu bytes, got %zu", ws.used, workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
-    L.w_off = (char *)wp - (char *)workspace;
-    L.b_off = (char *)bp - (char *)workspace;
-    PackDesc d{L.cout, L.cin_raw, 0, L.cin_take, L.ck, L.nchunk, L.nf, L.npass, 0, 0};
-    d.mfma16 = L.mfma16 ? 1 : 0;
-    d.ring = L.ring;
-    d.x3 = x3 ? 1 : 0;
-    if (hipMemsetAsync(zpage, 0, 256, s) != hipSuccess) return fail(EMAVFI_E_LAUNCH, "conv3x3: zero page memset failed");
-    EMAVFI_TRY(launch_pack_conv(weight, bias, wp, bp, d, dtype, s), "conv3x3 pack");
-    EMAVFI_TRY(x3 ? launch_nchw_to_cl_x3(x, xcl, B, Cin, H, W, L.cin_pad, s) : launch_nchw_to_cl(x, xcl, B, Cin, H, W, L.cin_pad, dtype, s), "conv3x3 layout in");
+    const void *const params[2] = {weight, bias};
+    if (hipMemsetAsync(b.zpage, 0, 256, s) != hipSuccess) return fail(EMAVFI_E_LAUNCH, "conv3x3: zero page memset failed");
+    EMAVFI_TRY(pack_layer(L, params, workspace, dtype, s), "conv3x3 pack");
+    EMAVFI_TRY(x3 ? launch_nchw_to_cl_x3(x, b.xcl, B, Cin, H, W, L.cin_pad, s) : launch_nchw_to_cl(x, b.xcl, B, Cin, H, W, L.cin_pad, dtype, s), "conv3x3 layout in");
     if (act == EMAVFI_ACT_TANH01) {
-        EMAVFI_TRY(run_conv(P, L, workspace, xcl, L.cin_pad, H, W, nullptr, 0, 0, 0, EPI_PLANAR_TANH01, B, s, nullptr, y, Cout, zpage), "conv3x3");
+        EMAVFI_TRY(run_conv(P, L, workspace, B, s, ConvCall{}.from(b.xcl, L.cin_pad, H, W).act(EPI_PLANAR_TANH01).to_planes(y, Cout)), "conv3x3");
     } else {
-        EMAVFI_TRY(run_conv(P, L, workspace, xcl, L.cin_pad, H, W, ycl, ops, 0, ops, act == EMAVFI_ACT_RELU ? EPI_RELU : EPI_NONE, B, s, nullptr, nullptr, 0, zpage), "conv3x3");
-        EMAVFI_TRY(x3 ? launch_cl_to_nchw_x3(ycl, y, B, Cout, Ho, Wo, ops, 0, s) : launch_cl_to_nchw(ycl, y, B, Cout, Ho, Wo, ops, 0, dtype, s), "conv3x3 layout out");
+        EMAVFI_TRY(run_conv(P, L, workspace, B, s, ConvCall{}.from(b.xcl, L.cin_pad, H, W).to(b.ycl, ops, ops).act(act == EMAVFI_ACT_RELU ? EPI_RELU : EPI_NONE)), "conv3x3");
+        EMAVFI_TRY(x3 ? launch_cl_to_nchw_x3(b.ycl, y, B, Cout, Ho, Wo, ops, 0, s) : launch_cl_to_nchw(b.ycl, y, B, Cout, Ho, Wo, ops, 0, dtype, s), "conv3x3 layout out");
     }
     return EMAVFI_OK;
 }
 
 size_t emavfi_deform_conv2d_workspace_bytes(int B, int C, int O, int H, int W, int dtype)
 {
-    const int e = dtype == EMAVFI_F32 ? 4 : 2;
-    Layer L = mk(0, O, C);
-    if (B < 1 || C < 1 || O < 1 || H < 1 || W < 1 || !deform_geometry(L, e)) {
+    Plan P;
+    Layer L;
+    if (B < 1 || C < 1 || O < 1 || H < 1 || W < 1 || !op_layer(P, L, true, C, O, 1, dtype)) {
         fail(EMAVFI_E_UNSUPPORTED, "deform_conv2d: no kernel instantiation for C=%d O=%d", C, O);
         return 0;
     }
-    if ((size_t)H * W >= ((size_t)1 << 24) || (size_t)H * W * L.ck * e >= ((size_t)1 << 32)) {
+    if ((size_t)H * W >= ((size_t)1 << 24) || (size_t)H * W * L.ck * P.esize >= ((size_t)1 << 32)) {
         fail(EMAVFI_E_ARG, "deform_conv2d: H*W must be < 2^24 and one sample's input plane < 4 GiB");
         return 0;
     }
     Workspace ws{nullptr, 0, 0};
-    const size_t px = (size_t)B * H * W;
-    ws.take(px * L.ck * e); ws.take(px * 32 * sizeof(float)); ws.take(L.w_bytes);
-    ws.take((size_t)L.coutpad * sizeof(float)); ws.take(px * rup(O, 16) * e); ws.take(256);
+    op_carve(P, L, ws, B, H, W);
     return ws.used;
 }
 
@@ -1427,37 +1436,23 @@ int emavfi_deform_conv2d(const float *x, const float *offset, const float *mask,
     if (!x || !offset || !mask || !weight || !y || !workspace) return fail(EMAVFI_E_ARG, "deform_conv2d: null pointer");
     if (B < 1 || C < 1 || O < 1 || H < 1 || W < 1) return fail(EMAVFI_E_ARG, "deform_conv2d: bad shape");
     if ((size_t)H * W >= ((size_t)1 << 24)) return fail(EMAVFI_E_ARG, "deform_conv2d: H*W must be < 2^24");
-    Plan P{};
-    P.dtype = dtype; P.esize = dtype == EMAVFI_F32 ? 4 : 2;
-    Layer L = mk(0, O, C);
-    if (!deform_geometry(L, P.esize)) return fail(EMAVFI_E_UNSUPPORTED, "deform_conv2d: no kernel instantiation for C=%d O=%d", C, O);
+    Plan P;
+    Layer L;
+    if (!op_layer(P, L, true, C, O, 1, dtype)) return fail(EMAVFI_E_UNSUPPORTED, "deform_conv2d: no kernel instantiation for C=%d O=%d", C, O);
     if ((size_t)H * W * L.ck * P.esize >= ((size_t)1 << 32))
         return fail(EMAVFI_E_ARG, "deform_conv2d: one sample's input plane must be < 4 GiB (32-bit byte offsets in the gather)");
-    const size_t px = (size_t)B * H * W;
     const int ops = rup(O, 16);
     Workspace ws{(char *)workspace, workspace_bytes, 0};
-    void *xcl = ws.take(px * L.ck * P.esize);
-    float *om = (float *)ws.take(px * 32 * sizeof(float));
-    void *wp = ws.take(L.w_bytes);
-    float *bp = (float *)ws.take((size_t)L.coutpad * sizeof(float));
-    void *ycl = ws.take(px * ops * P.esize);
-    void *zpage = ws.take(256);
+    const OpBuffers b = op_carve(P, L, ws, B, H, W);
     if (ws.used > workspace_bytes) return fail(EMAVFI_E_WORKSPACE, "deform_conv2d: workspace needs %zu bytes, got %zu", ws.used, workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
-    L.w_off = (char *)wp - (char *)workspace;
-    L.b_off = (char *)bp - (char *)workspace;
-    // the 16-bit LDS-window kernel contracts in f16 on chip: a bf16 call packs its bf16-rounded weights as f16 fragments
-    if (dtype != EMAVFI_F32 && deform_pack3_shape(L.ck, L.nf, L.cin_take, L.cout)) L.pack3 = 1;
-    const bool h_of_b = dtype == EMAVFI_BF16 && L.pack3 == 1;   // the LDS-window kernel contracts bf16-rounded weights stored as f16
-    if (dtype == EMAVFI_F32 && deform_f32w_shape(L.ck, L.nf, L.cin_take, L.cout)) L.pack3 = 3;
-    PackDesc d{L.cout, L.cin_raw, 0, L.cin_take, L.ck, 1, L.nf, 1, 0, h_of_b ? 1 : 0};
-    d.pack3 = L.pack3;
-    if (hipMemsetAsync(zpage, 0, 256, s) != hipSuccess) return fail(EMAVFI_E_LAUNCH, "deform_conv2d: zero page memset failed");
-    EMAVFI_TRY(launch_pack_conv(weight, bias, wp, bp, d, h_of_b ? (int)EMAVFI_F16 : dtype, s), "deform pack");
-    EMAVFI_TRY(launch_nchw_to_cl(x, xcl, B, C, H, W, L.ck, dtype, s), "deform layout in");
-    EMAVFI_TRY(launch_om_from_nchw(offset, mask, om, B, H, W, s), "deform offsets");
-    EMAVFI_TRY(run_deform(P, L, workspace, xcl, L.ck, om, ycl, ops, ops, B, H, W, s, zpage), "deform_conv2d");
-    EMAVFI_TRY(launch_cl_to_nchw(ycl, y, B, O, H, W, ops, 0, dtype, s), "deform layout out");
+    const void *const params[2] = {weight, bias};
+    if (hipMemsetAsync(b.zpage, 0, 256, s) != hipSuccess) return fail(EMAVFI_E_LAUNCH, "deform_conv2d: zero page memset failed");
+    EMAVFI_TRY(pack_layer(L, params, workspace, dtype, s), "deform pack");
+    EMAVFI_TRY(launch_nchw_to_cl(x, b.xcl, B, C, H, W, L.ck, dtype, s), "deform layout in");
+    EMAVFI_TRY(launch_om_from_nchw(offset, mask, b.om, B, H, W, s), "deform offsets");
+    EMAVFI_TRY(run_deform(P, L, workspace, B, s, DeformCall{}.from(b.xcl, L.ck, H, W, b.om).to(b.ycl, ops)), "deform_conv2d");
+    EMAVFI_TRY(launch_cl_to_nchw(b.ycl, y, B, O, H, W, ops, 0, dtype, s), "deform layout out");
     return EMAVFI_OK;
 }
 
@@ -1541,7 +1536,7 @@ static int mdcn_impl(const float *x, const float *offset_weight, const float *of
     EMAVFI_TRY(pack_layer(P.off[0], params.data(), m.blob, kd, s, P.amp), "mdcn pack offset_conv");
     if (P.has_offh) EMAVFI_TRY(pack_layer(P.offh[0], params.data(), m.blob, kd, s), "mdcn pack offset_conv (f16 fragments)");
     EMAVFI_TRY(pack_layer(P.dcn[0], params.data(), m.blob, kd, s), "mdcn pack dcn_v2");
-    if (P.amp) EMAVFI_TRY(pack_layer(P.dcn32[0], params.data(), m.blob, EMAVFI_F32, s), "mdcn pack dcn_v2 (fp32 master weights)");
+    if (P.amp) EMAVFI_TRY(pack_layer(P.dcn32[0], params.data(), m.blob, kd, s), "mdcn pack dcn_v2 (fp32 master weights)");
     if (P.amp) {
         EMAVFI_TRY(launch_nchw_to_cl(x, m.xF, B, C, H, W, P.fpad, EMAVFI_F32, s), "mdcn layout in (fp32)");
         EMAVFI_TRY(launch_nchw_to_cl(x, m.xcl, B, C, H, W, P.fps, EMAVFI_F16, s), "mdcn layout in (fp16 rounding)");
