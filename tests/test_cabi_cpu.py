@@ -569,6 +569,119 @@ def test_switch_word_is_latched_and_settable():
     assert lib.debug_switches() == old
 
 
+# The launch names of emavfi_forward_launches for EMA_VFI(3, 64, 3) at 1 x 96 x 128, recorded from the library BEFORE the layers got
+# one named kernel route (csrc/common.h, ConvRoute): which layers fuse, which geometry (ck, nf, stride) each takes and which element
+# type its kernel reads, per mode, per layout switch and with every bit of the run-time switch word set.  bench.py and tools/ match
+# on these names.
+PINNED_LAUNCHES = {
+    "bf16": [
+        "conv_first+conv3x3<bf16,6->64->64> cat+feat_ext_conv1+conv_block_0", "conv3x3+conv3x3<bf16,64->64->64> feat_ext_blocks.1+2",
+        "conv3x3<f16,ck=64,nf=4,s=2> context_encoding.0", "conv3x3<bf16,ck=32,nf=8,s=2> context_encoding.1",
+        "conv3x3<bf16,ck=64,nf=8,s=1> context_encoding.2 + pool (tile sums)", "avg_pool_partial", "context_linear_fold",
+        "conv3x3<f16,ck=64,nf=2,s=1> motion_estimation.0(ctx folded)", "conv3x3+head<bf16,64->64->2> motion_estimation.1+.2(flow)",
+        "warp_fused<bf16>", "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2", "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2",
+        "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2", "conv3x3<bf16,ck=80,nf=2,s=1> reconstruction.0",
+        "conv3x3+tail<bf16,64->32->3> reconstruction.1+.2(tanh)", "blob_guard"],
+    "fp16": [
+        "conv_first+conv3x3<f16,6->64->64> cat+feat_ext_conv1+conv_block_0", "conv3x3+conv3x3<f16,64->64->64> feat_ext_blocks.1+2",
+        "conv3x3<f16,ck=64,nf=4,s=2> context_encoding.0", "conv3x3<f16,ck=32,nf=8,s=2> context_encoding.1",
+        "conv3x3<f16,ck=64,nf=8,s=1> context_encoding.2 + pool (tile sums)", "avg_pool_partial", "context_linear_fold",
+        "conv3x3<f16,ck=64,nf=2,s=1> motion_estimation.0(ctx folded)", "conv3x3+head<f16,64->64->2> motion_estimation.1+.2(flow)", "warp_fused<f16>",
+        "deform<f16,ck=80,nf=3> offset_conv+dcn_v2", "deform<f16,ck=80,nf=3> offset_conv+dcn_v2", "deform<f16,ck=80,nf=3> offset_conv+dcn_v2",
+        "conv3x3<f16,ck=80,nf=2,s=1> reconstruction.0", "conv3x3+tail<f16,64->32->3> reconstruction.1+.2(tanh)", "blob_guard"],
+    "fp32": [
+        "pack_input", "conv3x3<f32,ck=16,nf=2,s=1> feat_ext_conv1", "conv3x3<f32,ck=64,nf=2,s=1> feat_ext_blocks",
+        "conv3x3<f32,ck=64,nf=2,s=1> feat_ext_blocks", "conv3x3<f32,ck=64,nf=2,s=1> feat_ext_blocks",
+        "conv3x3<f32,ck=32,nf=4,s=2> context_encoding.0", "conv3x3<f32,ck=32,nf=4,s=2> context_encoding.1",
+        "conv3x3<f32,ck=64,nf=4,s=1> context_encoding.2", "avg_pool_partial", "context_linear_fold",
+        "conv3x3<f32,ck=64,nf=2,s=1> motion_estimation.0(ctx folded)", "conv3x3<f32,ck=64,nf=2,s=1> motion_estimation.1",
+        "conv3x3<f32,ck=64,nf=1,s=1> motion_estimation.2(flow)", "warp_fused<f32>", "conv3x3<f32,ck=72,nf=1,s=1> offset_conv",
+        "deform<f32,ck=80,nf=3> dcn_v2", "conv3x3<f32,ck=72,nf=1,s=1> offset_conv", "deform<f32,ck=80,nf=3> dcn_v2",
+        "conv3x3<f32,ck=72,nf=1,s=1> offset_conv", "deform<f32,ck=80,nf=3> dcn_v2", "conv3x3<f32,ck=72,nf=2,s=1> reconstruction.0",
+        "conv3x3<f32,ck=64,nf=1,s=1> reconstruction.1", "conv3x3<f32,ck=32,nf=1,s=1> reconstruction.2(tanh)", "blob_guard"],
+    "EMAVFI_CONV_MFMA16=0": [
+        "conv_first+conv3x3<bf16,6->64->64> cat+feat_ext_conv1+conv_block_0", "conv3x3+conv3x3<bf16,64->64->64> feat_ext_blocks.1+2",
+        "conv3x3<f16,ck=64,nf=4,s=2> context_encoding.0", "conv3x3<bf16,ck=32,nf=8,s=2> context_encoding.1",
+        "conv3x3<bf16,ck=64,nf=8,s=1> context_encoding.2 + pool (tile sums)", "avg_pool_partial", "context_linear_fold",
+        "conv3x3<f16,ck=64,nf=2,s=1> motion_estimation.0(ctx folded)", "conv3x3<bf16,ck=64,nf=2,s=1> motion_estimation.1",
+        "conv3x3<bf16,ck=64,nf=1,s=1> motion_estimation.2(flow)", "warp_fused<bf16>", "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2",
+        "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2", "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2", "conv3x3<bf16,ck=80,nf=2,s=1> reconstruction.0",
+        "conv3x3<bf16,ck=64,nf=1,s=1> reconstruction.1", "conv3x3<bf16,ck=32,nf=1,s=1> reconstruction.2(tanh)", "blob_guard"],
+    "EMAVFI_CONV_RING=0": [
+        "conv_first<bf16,6->64> cat+feat_ext_conv1", "conv3x3<bf16,ck=64,nf=2,s=1> feat_ext_blocks", "conv3x3<bf16,ck=64,nf=2,s=1> feat_ext_blocks",
+        "conv3x3<bf16,ck=64,nf=2,s=1> feat_ext_blocks", "conv3x3<bf16,ck=64,nf=4,s=2> context_encoding.0",
+        "conv3x3<bf16,ck=32,nf=8,s=2> context_encoding.1", "conv3x3<bf16,ck=64,nf=8,s=1> context_encoding.2 + pool (tile sums)", "avg_pool_partial",
+        "context_linear_fold", "conv3x3<bf16,ck=64,nf=2,s=1> motion_estimation.0(ctx folded)", "conv3x3<bf16,ck=64,nf=2,s=1> motion_estimation.1",
+        "conv3x3<bf16,ck=64,nf=1,s=1> motion_estimation.2(flow)", "warp_fused<bf16>", "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2",
+        "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2", "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2", "conv3x3<bf16,ck=80,nf=2,s=1> reconstruction.0",
+        "conv3x3+tail<bf16,64->32->3> reconstruction.1+.2(tanh)", "blob_guard"],
+    "EMAVFI_CONV_S2RING=0": [
+        "conv_first+conv3x3<bf16,6->64->64> cat+feat_ext_conv1+conv_block_0", "conv3x3+conv3x3<bf16,64->64->64> feat_ext_blocks.1+2",
+        "conv3x3<bf16,ck=32,nf=4,s=2> context_encoding.0", "conv3x3<bf16,ck=32,nf=8,s=2> context_encoding.1",
+        "conv3x3<bf16,ck=64,nf=8,s=1> context_encoding.2 + pool (tile sums)", "avg_pool_partial", "context_linear_fold",
+        "conv3x3<bf16,ck=64,nf=2,s=1> motion_estimation.0(ctx folded)", "conv3x3+head<bf16,64->64->2> motion_estimation.1+.2(flow)",
+        "warp_fused<bf16>", "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2", "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2",
+        "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2", "conv3x3<bf16,ck=80,nf=2,s=1> reconstruction.0",
+        "conv3x3+tail<bf16,64->32->3> reconstruction.1+.2(tanh)", "blob_guard"],
+    "EMAVFI_CONV_WREG=0": [
+        "conv_first+conv3x3<bf16,6->64->64> cat+feat_ext_conv1+conv_block_0", "conv3x3+conv3x3<bf16,64->64->64> feat_ext_blocks.1+2",
+        "conv3x3<f16,ck=64,nf=4,s=2> context_encoding.0", "conv3x3<bf16,ck=32,nf=8,s=2> context_encoding.1",
+        "conv3x3<bf16,ck=64,nf=4,s=1> context_encoding.2", "avg_pool_partial", "context_linear_fold",
+        "conv3x3<f16,ck=64,nf=2,s=1> motion_estimation.0(ctx folded)", "conv3x3+head<bf16,64->64->2> motion_estimation.1+.2(flow)",
+        "warp_fused<bf16>", "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2", "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2",
+        "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2", "conv3x3<bf16,ck=80,nf=2,s=1> reconstruction.0",
+        "conv3x3+tail<bf16,64->32->3> reconstruction.1+.2(tanh)", "blob_guard"],
+    "bf16, every switch bit": [
+        "pack_input", "conv3x3<bf16,ck=16,nf=2,s=1> feat_ext_conv1", "conv3x3<bf16,ck=64,nf=2,s=1> feat_ext_blocks",
+        "conv3x3<bf16,ck=64,nf=2,s=1> feat_ext_blocks", "conv3x3<bf16,ck=64,nf=2,s=1> feat_ext_blocks",
+        "conv3x3<f16,ck=64,nf=4,s=2> context_encoding.0", "conv3x3<bf16,ck=32,nf=8,s=2> context_encoding.1",
+        "conv3x3<bf16,ck=64,nf=8,s=1> context_encoding.2", "avg_pool_partial", "context_linear_fold",
+        "conv3x3<f16,ck=64,nf=2,s=1> motion_estimation.0(ctx folded)", "conv3x3<bf16,ck=64,nf=2,s=1> motion_estimation.1",
+        "conv3x3<bf16,ck=64,nf=1,s=1> motion_estimation.2(flow)", "warp_fused<bf16>", "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2",
+        "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2", "deform<bf16,ck=80,nf=3> offset_conv+dcn_v2", "conv3x3<bf16,ck=80,nf=2,s=1> reconstruction.0",
+        "conv3x3<bf16,ck=64,nf=1,s=1> reconstruction.1", "conv3x3<bf16,ck=32,nf=1,s=1> reconstruction.2(tanh)", "blob_guard"],
+}
+
+# a child without torch or a GPU: the layout switches are latched once per process, the enumeration launches nothing
+_LAUNCH_NAMES_CHILD = """
+import ctypes, json, sys
+L = ctypes.CDLL(sys.argv[1])
+fn = L.emavfi_forward_launches
+fn.restype = ctypes.c_int
+fn.argtypes = [ctypes.c_int] * 7 + [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+n = fn(3, 64, 3, 1, 96, 128, 1, None, 0, None, None, 0)
+buf = ctypes.create_string_buffer(128 * max(n, 1))
+assert n > 0 and fn(3, 64, 3, 1, 96, 128, 1, buf, len(buf), None, None, n) == n
+print(json.dumps(buf.value.decode().strip().split(chr(10))))
+"""
+
+
+def test_forward_launch_names_are_pinned_per_mode_and_switch():
+    import json
+    import subprocess
+    import sys
+    names = lambda dtype: [n for n, _, _ in lib.forward_launches(3, 64, 3, 1, 96, 128, dtype)]
+    layout = ("EMAVFI_CONV_MFMA16", "EMAVFI_CONV_RING", "EMAVFI_CONV_S2RING", "EMAVFI_CONV_WREG")
+    clean = {k: v for k, v in os.environ.items() if k not in layout}
+    children = {name: subprocess.Popen([sys.executable, "-c", _LAUNCH_NAMES_CHILD, lib.LIB_PATH], env=dict(clean, **{name: "0"}),
+                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for name in layout}
+    old = lib.debug_switches()
+    every = (lib.SW_NO_CONV_FIRST | lib.SW_NO_FIRSTRING | lib.SW_NO_HEAD | lib.SW_NO_TAILFUSE | lib.SW_NO_CONV_LIGHT | lib.SW_NO_PERSISTENT_CONV |
+             lib.SW_NO_RING2 | lib.SW_NO_POOLFUSE | lib.SW_RING_ONE_WG | lib.SW_NO_RING_CHUNK)
+    try:
+        lib.debug_switches(0, 0)
+        for dtype in ("bf16", "fp16", "fp32"):
+            assert names(dtype) == PINNED_LAUNCHES[dtype], dtype
+        lib.debug_switches(0, every)
+        assert names("bf16") == PINNED_LAUNCHES["bf16, every switch bit"]
+    finally:
+        lib.debug_switches(0, old)
+        results = {name: child.communicate(timeout=120) for name, child in children.items()}
+    for name, (out, err) in results.items():
+        assert children[name].returncode == 0, (name, err[-2000:])
+        assert json.loads(out) == PINNED_LAUNCHES[name + "=0"], name
+
+
 def test_host_check_runs_clean_under_asan_ubsan():
     """SURVEY.md section 5 (sanitizers) / VERDICT r3 item 9: `make asan` builds libemavfi_asan.so with AddressSanitizer +
     UndefinedBehaviorSanitizer in every HOST pass (the gfx950 device code stays uninstrumented: GPU ASan / XNACK do not exist on this

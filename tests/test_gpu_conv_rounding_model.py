@@ -8,7 +8,7 @@ kind of gate tests/test_gpu_mdcn.py has for the pack): operands pre-rounded to w
   * finite, right shape.
 Every family conv_geometry() (video-frame-interpolation_amd/csrc/emavfi_api.hip) can select is run in bf16, fp16 and - where the family exists there - fp32, at the
 shapes where it changes behaviour.  The stage entry emavfi_conv3x3 reads the layout switches per call and reports no kernel name, so
-the family a case runs is asserted against family_of() below, a restatement of conv_geometry() + launch_conv16 / launch_conv_mfma16
+the family a case runs is asserted against family_of() below, a restatement of conv_geometry() + launch_conv16's dispatch on the route
 (csrc/conv3x3.inl, same directory): a case that drifts to another family fails before it runs.  Two entries of the families' table are NOT what their
 channel counts suggest: 67 -> 27 in the 16-bit types runs the 32x32x16 PERSISTENT kernel (conv3x3_persist_kernel<80, 1, 8>), and
 64 -> 2 with activation `none` through the stage entry runs conv3x3_persist16_kernel<64, 1, 2> - conv_light's 64-channel form needs

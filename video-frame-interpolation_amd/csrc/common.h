@@ -1,6 +1,7 @@
 // Shared device-side types for libemavfi (gfx950 / CDNA4 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <atomic>
 
@@ -167,6 +168,21 @@ template <typename T, int CK> struct LdsPix {
 // ---- kernel parameter blocks (host fills, passed by value) ----
 enum { EPI_NONE = 0, EPI_RELU = 1, EPI_OM = 2, EPI_PLANAR = 3, EPI_PLANAR_TANH01 = 4 };
 
+// Which kernel family runs a convolution layer and, with it, how the layer's weights are packed: one value per (kernel, layout).
+// conv_geometry() (emavfi_api.hip) alone assigns it, launch_conv16() (conv3x3.inl) alone dispatches on it and resolves the run-time A/B
+// switches that move a route; pack_conv_kernel (misc_kernels.hip) writes the layout.  The fused variant of a route is the CALL's: w2, head_w, out_alt.
+enum ConvRoute {
+    CONV_TILE = 0,     // conv3x3_kernel: every shape, the only route of fp32 and EMAVFI_F32X3; [pass][chunk][tap][kg][nf][lane][16 B]
+    CONV_PERSIST,      // conv3x3_persist_kernel, that packing: (ck, nf) = (64, 2) (64, 1) (80, 1) at stride 1, one chunk, one pass, 16-bit
+    CONV_PERSIST16,    // conv3x3_persist16_kernel (16x16x32 MFMAs): 64 -> 5..64, [tap][k32][cout16 block][lane][16 B]; head_w: conv_ring_tail.inl
+    CONV_LIGHT,        // conv_light_kernel, the 16x16x32 packing: planar heads of <= 4 channels from 32 or 64
+    CONV_S2RING,       // conv3x3_s2ring_kernel: 64 -> 128 at stride 2, weights in registers, input rows through an LDS ring; regular packing (ck 64, nf 4)
+    CONV_RING,         // conv3x3_ring_kernel: 64 -> 33..64 at stride 1, regular packing (ck 64, nf 2); fused: conv_ring2.inl (w2), + head (head_w), conv_ring_first.inl
+    CONV_RING_TAIL3,   // the ring kernel with the im2col tail: 65..67 -> 33..64 (reconstruction.0); CONV_RING's packing of channels 0..63 + 6 KiB of
+                       // tail [j 3][nf 2][lane (r, h)][8]: W[32 nf + r][64 + (e & 3)][tap slot 4 j + 2 h + (e >> 2)]
+    CONV_WREG,         // conv3x3_wreg_kernel: -> 256 channels, weights streamed into registers, input tile in LDS; regular packing (nf 8)
+};
+
 struct ConvParams {
     const void *in;     // channels-last T
     void *out;          // channels-last T (EPI_NONE/RELU) or fp32 [px][32] (EPI_OM)
@@ -182,13 +198,10 @@ struct ConvParams {
     int ck, nf, stride;  // host-side template selectors
     int round16;         // EMAVFI_AMP16: fp32-stored results (flow, offsets / masks, the frame) hold fp16-rounded values and
                          // sigmoid / tanh / (t+1)/2 round after every op, as fp16 tensors do under autocast
-    int mfma16;          // weights packed for v_mfma_f32_16x16x32 (conv3x3_persist16_kernel): [tap][k32][cout16 block][lane][16 B]
-    int ring;            // weights in registers, input rows through an LDS ring: 1 = conv3x3_s2ring_kernel (64 -> 128 at stride 2, context_encoding.0),
-                         // 2 = conv3x3_ring_kernel (64 -> 64), 3 = the same with the im2col tail (65..67 -> 64: reconstruction.0);
-                         // 4 = conv3x3_wreg_kernel (conv_wreg.inl: -> 256 channels, weights streamed into registers, input tile in LDS)
-    const void *w2;          // conv_ring2.inl (ring == 2, both layers 64 -> 64): a SECOND conv_block behind this one in the same launch - its packed
+    int route;           // ConvRoute: read by the host launchers only, never by a kernel (the four bytes behind it are padding)
+    const void *w2;          // conv_ring2.inl (CONV_RING, both layers 64 -> 64): a SECOND conv_block behind this one in the same launch - its packed
     const float *bias2;      // weights (ring layout) and bias; `out*` / cstore / out_alt / out_fill then describe the second layer's output
-    const void *head_w;      // conv_ring.inl, ring == 2 only: fuse a 64 -> nplanes (<= 2) planar head (its weights in the 16x16x32 packing,
+    const void *head_w;      // conv_ring.inl, CONV_RING only: fuse a 64 -> nplanes (<= 2) planar head (its weights in the 16x16x32 packing,
     const float *head_bias;  // its bias) behind this layer: `out` is not written, `out_planar` gets the head (round16 applies)
     int out_alt;             // ring kernels (64 -> 64, 64 -> 128 stride 2), channels-last epilogue: store the OTHER 16-bit type (a bf16 kernel writes
                              // IEEE f16 bit patterns and vice versa).  bf16 model: `feat` lives as f16 (what the first pack wants on chip,
@@ -196,9 +209,9 @@ struct ConvParams {
     int out_fill;            // conv3x3_ring_kernel, 64 channels into 144-byte pixels (`feat` into the fusion tensor): also write the pixel's last
                              // 16 bytes (zeros).  128 of every 144 bytes leave a hole in every 128-byte line - partial-line writes that cost
                              // the layer ~240 us at B = 8 x 720p; the bytes belong to nobody yet (the warp writes them later, or never)
-    int epi2;                // conv_ring_tail.inl (64 -> 32 -> nplanes <= 3, this layer packed mfma16 with nf == 1): the head's epilogue
+    int epi2;                // conv_ring_tail.inl (64 -> 32 -> nplanes <= 3, this layer CONV_PERSIST16 with nf == 1): the head's epilogue
                              // (EPI_PLANAR or EPI_PLANAR_TANH01)
-    float *pool_part;    // conv_wreg.inl (ring == 4, 256 channels): do NOT store the layer's output, write the per-channel sums of every 4 x 32 pixel
+    float *pool_part;    // conv_wreg.inl (CONV_WREG, 256 channels): do NOT store the layer's output, write the per-channel sums of every 4 x 32 pixel
                          // tile instead: [B][tiles][256] floats (context_encoding.2 feeds AdaptiveAvgPool2d and nothing else)
     int in_pieces;       // 16-byte pieces of an input pixel (single-chunk layers) that exist in memory; 0 = all CK of them.
                          // Pieces beyond read as zeros: the 72-channel fusion buffers feed CK = 80 layers this way.
@@ -213,6 +226,18 @@ struct ConvParams {
     float *out32;   // x3 only: ALSO store the fp32 value, channels-last with pixel stride out32_ps (the last feature layer writes `feat` into the
     int out32_ps;   // fp32 fusion tensor the exact DCN reads: saves the widening pass' read of 1.9 GB at B = 8 x 720p)
 };
+static_assert(offsetof(ConvParams, w2) == 128 && sizeof(ConvParams) == 232, "a field that moves changes every convolution kernel's code object");
+
+// (CK, NF, stride) instantiations of the tile-per-workgroup kernel: conv_inst_exists() (emavfi_api.hip) and launch_conv_any() (conv3x3.inl) expand these
+#define EMAVFI_CONV_INSTANCES(X) \
+    X(16, 1, 1) X(16, 2, 1) X(32, 1, 1) X(48, 1, 1) X(64, 1, 1) X(64, 2, 1) X(64, 4, 1) X(80, 1, 1) X(80, 2, 1) \
+    X(16, 1, 2) X(32, 2, 2) X(32, 4, 2)
+// 16-bit types only: all eight output fragments of a stride-2 layer in one pass, 128 accumulator registers (EMAVFI_CONV_WREG=0: context_encoding.1)
+#define EMAVFI_CONV_INSTANCES_16(X) X(32, 8, 2)
+// fp32 only (k-groups of 8 channels): 65..72 input channels as 9 k-groups instead of 10 (offset_conv 67 -> 27, reconstruction.0 67 -> 64)
+#define EMAVFI_CONV_INSTANCES_F32(X) X(72, 1, 1) X(72, 2, 1)
+// (CK, NF) instantiations of deform_kernel, narrowest first: deform_geometry() takes the first that holds the layer, launch_deform_any() expands the list
+#define EMAVFI_DEFORM_INSTANCES(X) X(16, 1) X(32, 1) X(48, 2) X(80, 3)
 
 // In-kernel stamps of the LDS-ring convolution kernels (diagnostic build only; cdna_hip_programming.md section 7): s_memtime at the
 // seams of a row step, per-wave sums over all steps of all items, one row of eight u64 per (workgroup, wave) at the end of the
@@ -337,7 +362,7 @@ int device_cu_count();
 struct FirstParams;
 int launch_conv_first_bf16(const FirstParams &p, hipStream_t s);
 int launch_conv_first_f16(const FirstParams &p, hipStream_t s);
-// conv_ring_first.inl: feat_ext_conv1 + conv_block_0 in one launch (p: the 64 -> 64 layer, ring == 2; p.in is not read)
+// conv_ring_first.inl: feat_ext_conv1 + conv_block_0 in one launch (p: the 64 -> 64 layer, CONV_RING; p.in is not read)
 int launch_conv_ringfirst_bf16(const FirstParams &fp, const ConvParams &p, hipStream_t s);
 int launch_conv_ringfirst_f16(const FirstParams &fp, const ConvParams &p, hipStream_t s);
 int launch_conv3x3_f32(const ConvParams &p, hipStream_t s);

@@ -1,5 +1,5 @@
 // 3x3 convolution (pad 1, stride 1 or 2) as an implicit GEMM on the CDNA4 matrix cores.
-// Replaces nn.Conv2d at /root/reference/src/models/ema_vfi.py:7-14 (every conv / conv_block on
+// Replaces nn.Conv2d at the reference's src/models/ema_vfi.py:7-14 (every conv / conv_block on
 // the forward path: :73-76, :80-82, :90-92, :35-41, :103-105).
 //
 // One 256-thread workgroup (4 waves, one per SIMD) produces a tile of 4*MF rows x 32 columns of
@@ -22,17 +22,8 @@
 // LDS pixel stride is an odd number of 16-byte slots (LdsPix), so the ds_read_b128 operand
 // fetches of 32 consecutive pixels are bank-conflict free for stride 1.
 //
-// Kernels in this file (which layer runs where: launch_conv16 / launch_conv_mfma16 at the end):
-//   conv3x3_kernel            the tile-per-workgroup kernel described above (every shape; the only one for fp32, chunked K)
-//   conv3x3_s2ring_kernel     64 -> 128 at stride 2: weights in registers, input rows through an LDS ring (one strip per workgroup)
-//   conv3x3_ring_kernel       (conv_ring.inl) that structure at stride 1: the 64 -> 64 layers and reconstruction.0 (67 -> 64) (product)
-//   conv3x3_ringtail_kernel   (conv_ring_tail.inl) reconstruction.1 + .2 (64 -> 32 -> 3) through a second LDS ring (product)
-//   conv3x3_persist_kernel    persistent, nine taps' weights resident, 16 x 32 tiles, 8 waves in lock step (32x32x16 MFMAs)
-//   conv3x3_persist16_kernel  the same on v_mfma_f32_16x16x32 with an unpadded XOR-swizzled tile: 64 -> 32 and 64 -> planes when the fused
-//                             ring kernels are switched off, 64 -> 64 with EMAVFI_CONV_RING=0 (round 2's ping-pong variant of it,
-//                             conv3x3_pingpong16_kernel, was removed in round 4: the ring kernels replaced it in the product)
-//   (round 2's conv3x3_pingpong_kernel - the schedule on 32x32x16 MFMAs - and conv3x3_tail_kernel - reconstruction.1 + .2 through
-//    the LDS - were measurement-only experiments that lost and were removed in round 3)
+// Kernels in this file and the .inl files it includes: one per ConvRoute (common.h), which names them and their weight layouts.
+// Which layer takes which route: conv_geometry() (emavfi_api.hip); which kernel a call on a route runs: launch_conv16() at the end.
 #include "common.h"
 #include <cstdlib>
 #include <mutex>
@@ -565,7 +556,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv3x3_persist_kernel(const ConvP
 // The tile is stored unpadded with the XOR slot swizzle of the ping-pong kernel (a 16-lane ds_read_b128 group here mixes two
 // adjacent pieces of 8 + 8 consecutive pixels, which no padded stride serves without conflicts; the swizzle does for the
 // taps with dx = 0 and leaves a two-way conflict on a few lanes otherwise).  Weights come packed for this shape
-// (PackDesc::mfma16).  fp32 accumulation order inside a tap differs from the 32x32x16 kernels (32 channels per MFMA instead
+// (CONV_PERSIST16).  fp32 accumulation order inside a tap differs from the 32x32x16 kernels (32 channels per MFMA instead
 // of 16), so results agree with them to fp32 rounding, not bit for bit.
 // ------------------------------------------------------------------------------------------
 // Slot permutation of the unpadded 128-byte tile pixels of the two 16x16x32 kernels: the 16-byte piece c of tile pixel q is stored
@@ -761,23 +752,6 @@ template <typename T, int CK, int NF, int NB> static int launch_conv_persist16(c
 #include "conv_ring2.inl"
 #include "conv_ring_tail.inl"
 
-// weights packed for the 16x16x32 shape (ConvParams::mfma16): 64 -> 64 (four blocks), 64 -> 32 (two), 64 / 32 -> planes (one)
-template <typename T> static int launch_conv_mfma16(const ConvParams &p, hipStream_t s)
-{
-    if (p.head_w) return launch_conv_ringtail<T>(p, s);   // reconstruction.1 + .2 in one launch (conv_ring_tail.inl)
-    const bool planar = p.epi == EPI_PLANAR || p.epi == EPI_PLANAR_TANH01;
-    if (p.ck == 32 && p.stride == 1 && p.nchunk == 1 && p.npass == 1 && p.nf == 1 && planar && p.nplanes <= 4) return launch_conv_light<T, 32>(p, s);
-    if (p.ck != 64 || p.stride != 1 || p.nchunk != 1 || p.npass != 1) return -2;
-    if (!planar && p.epi != EPI_NONE && p.epi != EPI_RELU) return -2;
-    if (p.nf == 2 && !planar) return launch_conv_persist16<T, 64, 2, 4>(p, s);
-    if (p.nf == 1 && !planar) return launch_conv_persist16<T, 64, 1, 2>(p, s);
-    if (p.nf == 1 && planar && p.nplanes <= 4) {
-        if (!(emavfi_switches() & SW_NO_CONV_LIGHT)) return launch_conv_light<T, 64>(p, s);   // EMAVFI_CONV_LIGHT=0: the lock-step persistent kernel (A/B)
-        return launch_conv_persist16<T, 64, 1, 1>(p, s);
-    }
-    return -2;
-}
-
 template <typename T, int CK, int NF, int WAVES> static int launch_conv_persist(const ConvParams &p, hipStream_t s)
 {
     using C = ConvPersistCfg<T, CK, NF, WAVES>;
@@ -802,7 +776,6 @@ template <typename T, int CK, int NF, int WAVES> static int launch_conv_persist(
     conv3x3_persist_kernel<T, CK, NF, WAVES><<<ntiles < resident ? ntiles : resident, 64 * WAVES, C::LDS_BYTES, s>>>(p);
     return (int)hipGetLastError();
 }
-
 
 // ------------------------------------------------------------------------------------------
 // context_encoding.0 (64 -> 128, stride 2: ema_vfi.py:80): weights stationary in registers, input rows through an LDS ring.
@@ -978,43 +951,57 @@ template <typename T> static int launch_conv_s2ring(const ConvParams &p, hipStre
     return p.out_alt ? launch_conv_s2ring_t<T, true>(p, s) : launch_conv_s2ring_t<T, false>(p, s);
 }
 
-// (CK, NF, stride) instantiations of the tile-per-workgroup kernel (keep in sync with kConvInst in emavfi_api.hip)
-#define EMAVFI_CONV_INSTANCES(X) \
-    X(16, 1, 1) X(16, 2, 1) X(32, 1, 1) X(48, 1, 1) X(64, 1, 1) X(64, 2, 1) X(64, 4, 1) X(80, 1, 1) X(80, 2, 1) \
-    X(16, 1, 2) X(32, 2, 2) X(32, 4, 2)
-
+// the tile-per-workgroup kernel's instantiations: the lists of common.h
 template <typename T> static int launch_conv_any(const ConvParams &p, hipStream_t s)
 {
 #define X(CK_, NF_, ST_) \
     if (p.ck == CK_ && p.nf == NF_ && p.stride == ST_) return launch_conv_inst<T, CK_, NF_, ST_>(p, s);
     EMAVFI_CONV_INSTANCES(X)
-    if constexpr (sizeof(T) == 2) {  // 16-bit types only: eight output fragments in one pass (EMAVFI_CONV_WREG=0: context_encoding.1)
-        X(32, 8, 2)
-    }
-    if constexpr (sizeof(T) == 4) {  // fp32 only (k-groups of 8 channels): 65..72 input channels as 9 k-groups instead of 10 (round 6: the
-        X(72, 1, 1) X(72, 2, 1)      // fp32 layers are matrix-pipe-bound at the clock the board holds; offset_conv 67 -> 27, reconstruction.0 67 -> 64)
-    }
+    if constexpr (sizeof(T) == 2) { EMAVFI_CONV_INSTANCES_16(X) }
+    if constexpr (sizeof(T) == 4) { EMAVFI_CONV_INSTANCES_F32(X) }
 #undef X
     return -2;  // no instantiation
 }
 
 #include "conv_wreg.inl"
 
-// 16-bit launcher (bf16 / f16): full-resolution single-chunk layers go to the persistent, weights-resident kernel
-// (CK, NF, waves): 64->64, 64->32 / 64->2, 67->27 of the mid_channels = 64 model.
-template <typename T> static int launch_conv16(const ConvParams &p, hipStream_t s, bool no_persistent)
+// 16-bit launcher (bf16 / f16): the one dispatch on the layer's route (ConvRoute, common.h).  Inside a route the call's own operands
+// pick the fused variant; the two run-time A/B switches that move a route are resolved here and nowhere else.  (The kernels of a
+// translation unit are emitted in the order this function names them: moving a case reorders the code object, nothing else.)
+template <typename T> static int launch_conv16(const ConvParams &p, hipStream_t s)
 {
-    if (p.mfma16) return launch_conv_mfma16<T>(p, s);
-    if (p.ring == 1) return launch_conv_s2ring<T>(p, s);
-    if (p.ring == 4) return launch_conv_wreg<T>(p, s);
-    if (p.ring >= 2) return p.w2 ? launch_conv_ring2<T>(p, s) : launch_conv_ring<T>(p, s);
-    if (!no_persistent && p.stride == 1 && p.nchunk == 1 && p.npass == 1) {
-        // measured at B=8 x 720p in bf16 (us per launch, tile-per-workgroup -> persistent): 64->64 670 -> 644,
-        // 64->32 / 64->2 414 -> 370, 67->27 685 -> 557.  NOT used where it loses: 67->64 with 4 waves
-        // (771 -> 915: one 4-wave workgroup per CU cannot overlap its own phases), 6->64, 32->3 (no gain).
-        if (p.ck == 64 && p.nf == 2) return launch_conv_persist<T, 64, 2, 8>(p, s);
-        if (p.ck == 64 && p.nf == 1) return launch_conv_persist<T, 64, 1, 8>(p, s);
-        if (p.ck == 80 && p.nf == 1) return launch_conv_persist<T, 80, 1, 8>(p, s);
+    const unsigned sw = emavfi_switches();
+    const bool one = p.stride == 1 && p.nchunk == 1 && p.npass == 1;   // full resolution, one chunk, one pass
+    switch (p.route) {
+    case CONV_PERSIST16:   // 64 -> 64 (four 16-channel blocks), 64 -> 32 (two)
+    case CONV_LIGHT: {     // 64 / 32 -> planes (one); a channels-last call of such a layer (the stage entry) runs CONV_PERSIST16's kernel
+        if (p.head_w) return launch_conv_ringtail<T>(p, s);   // reconstruction.1 + .2 in one launch (conv_ring_tail.inl)
+        const bool head = p.route == CONV_LIGHT && (p.epi == EPI_PLANAR || p.epi == EPI_PLANAR_TANH01);
+        if (head && p.ck == 32 && one && p.nf == 1 && p.nplanes <= 4) return launch_conv_light<T, 32>(p, s);
+        if (p.ck != 64 || !one) return -2;
+        if (!head && p.epi != EPI_NONE && p.epi != EPI_RELU) return -2;
+        if (!head) return p.nf == 2 ? launch_conv_persist16<T, 64, 2, 4>(p, s) : p.nf == 1 ? launch_conv_persist16<T, 64, 1, 2>(p, s) : -2;
+        if (p.nf != 1 || p.nplanes > 4) return -2;
+        if (!(sw & SW_NO_CONV_LIGHT)) return launch_conv_light<T, 64>(p, s);
+        return launch_conv_persist16<T, 64, 1, 1>(p, s);   // EMAVFI_CONV_LIGHT=0: the lock-step persistent kernel (A/B)
     }
-    return launch_conv_any<T>(p, s);
+    case CONV_S2RING: return launch_conv_s2ring<T>(p, s);
+    case CONV_WREG: return launch_conv_wreg<T>(p, s);
+    case CONV_RING:
+    case CONV_RING_TAIL3: return p.w2 ? launch_conv_ring2<T>(p, s) : launch_conv_ring<T>(p, s);
+    case CONV_PERSIST:
+        if (!(sw & SW_NO_PERSISTENT_CONV)) {
+            // measured at B=8 x 720p in bf16 (us per launch, tile-per-workgroup -> persistent): 64->64 670 -> 644,
+            // 64->32 / 64->2 414 -> 370, 67->27 685 -> 557.  NOT used where it loses: 67->64 with 4 waves
+            // (771 -> 915: one 4-wave workgroup per CU cannot overlap its own phases), 6->64, 32->3 (no gain).
+            if (!one) return -2;
+            if (p.ck == 64 && p.nf == 2) return launch_conv_persist<T, 64, 2, 8>(p, s);
+            if (p.ck == 64 && p.nf == 1) return launch_conv_persist<T, 64, 1, 8>(p, s);
+            if (p.ck == 80 && p.nf == 1) return launch_conv_persist<T, 80, 1, 8>(p, s);
+            return -2;
+        }
+        [[fallthrough]];   // EMAVFI_NO_PERSISTENT_CONV: the tile-per-workgroup kernel (A/B switch for measurements)
+    case CONV_TILE: return launch_conv_any<T>(p, s);
+    }
+    return -2;
 }

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256, CK == 64 ? 2 : 3) void conv_light_kernel(const
     const char *zeros = (const char *)p.zeros;
     const unsigned pixbytes = (unsigned)p.in_ps * 2u;
 
-    // weights of the first 16-channel block: [tap][k32][block (2 packed, the first used)][lane][16 B] (PackDesc::mfma16)
+    // weights of the first 16-channel block: [tap][k32][block (2 packed, the first used)][lane][16 B] (CONV_LIGHT)
     vec wf[9][K32];
 #pragma unroll
     for (int t = 0; t < 9; ++t)

@@ -270,7 +270,7 @@ template <typename T, bool ALT> static int launch_conv_ring2_t(const ConvParams 
 
 template <typename T> static int launch_conv_ring2(const ConvParams &p, hipStream_t s)
 {
-    if (p.stride != 1 || p.nchunk != 1 || p.npass != 1 || p.nf != 2 || p.ring != 2 || p.bias_mode > 1 || !p.w2 || !p.bias2 || p.head_w ||
+    if (p.stride != 1 || p.nchunk != 1 || p.npass != 1 || p.nf != 2 || p.route != CONV_RING || p.bias_mode > 1 || !p.w2 || !p.bias2 || p.head_w ||
         (p.epi != EPI_NONE && p.epi != EPI_RELU))
         return -2;
     return p.out_alt ? launch_conv_ring2_t<T, true>(p, s) : launch_conv_ring2_t<T, false>(p, s);

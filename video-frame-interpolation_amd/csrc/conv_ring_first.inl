@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ringfirst_kernel(const FirstPa
 template <typename T> static int launch_conv_ringfirst_t(const FirstParams &fp, const ConvParams &p, hipStream_t s)
 {
     using C = RingFirstCfg<T>;
-    if (p.ring != 2 || p.stride != 1 || p.bias_mode != 0 || (p.epi != EPI_NONE && p.epi != EPI_RELU) || !fp.relu || fp.H != p.Hout || fp.W != p.Wout) return -2;
+    if (p.route != CONV_RING || p.stride != 1 || p.bias_mode != 0 || (p.epi != EPI_NONE && p.epi != EPI_RELU) || !fp.relu || fp.H != p.Hout || fp.W != p.Wout) return -2;
     static PerDeviceOnce once;   // (the library is re-entrant and serves several devices per process)
     if (const hipError_t e_ = set_lds_limit(once, reinterpret_cast<const void *>(&conv3x3_ringfirst_kernel<T>), C::LDS_BYTES); e_ != hipSuccess) return (int)e_;
     const int ncu = device_cu_count();

@@ -275,7 +275,7 @@ template <typename T, bool R16, bool TANH> static int launch_conv_ringtail_t(con
 
 template <typename T> static int launch_conv_ringtail(const ConvParams &p, hipStream_t s)
 {
-    if (!p.mfma16 || p.ck != 64 || p.nf != 1 || p.stride != 1 || p.bias_mode != 0 || (p.epi != EPI_NONE && p.epi != EPI_RELU) || !p.head_w || !p.head_bias ||
+    if (p.route != CONV_PERSIST16 || p.ck != 64 || p.nf != 1 || p.stride != 1 || p.bias_mode != 0 || (p.epi != EPI_NONE && p.epi != EPI_RELU) || !p.head_w || !p.head_bias ||
         !p.out_planar || p.nplanes < 1 || p.nplanes > 3)
         return -2;
     if (p.epi2 != EPI_PLANAR && p.epi2 != EPI_PLANAR_TANH01) return -2;

@@ -323,9 +323,7 @@ template <typename T, int CK, int NF> static int launch_deform_inst(const Deform
     return (int)hipGetLastError();
 }
 
-// (CK, NF): fusion widths mid+3 for mid in {8, 16, 32, 64} -> padded 16, 32, 48, 80.
-#define EMAVFI_DEFORM_INSTANCES(X) X(16, 1) X(32, 1) X(48, 2) X(80, 3)
-
+// (CK, NF), EMAVFI_DEFORM_INSTANCES of common.h: fusion widths mid+3 for mid in {8, 16, 32, 64} -> padded 16, 32, 48, 80.
 template <typename T> static int launch_deform_any(const DeformParams &p, hipStream_t s)
 {
 #define X(CK_, NF_) \

@@ -55,25 +55,14 @@ inline int rup(int v, int m) { return (v + m - 1) / m * m; }
 inline size_t rup256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// ---- which (CK, NF, stride) / (CK, NF) instantiations exist (keep in sync with the .inl lists) ----
-const int kConvInst[][3] = {{16, 1, 1}, {16, 2, 1}, {32, 1, 1}, {48, 1, 1}, {64, 1, 1}, {64, 2, 1},
-                            {64, 4, 1}, {80, 1, 1}, {80, 2, 1}, {16, 1, 2}, {32, 2, 2}, {32, 4, 2}};
-// 16-bit types only: all eight output fragments of a stride-2 layer in one pass (128 accumulator registers)
-const int kConvInst16[][3] = {{32, 8, 2}};
-// fp32 only: 65..72 input channels as nine k-groups of 8
-const int kConvInst32[][3] = {{72, 1, 1}, {72, 2, 1}};
-const int kDeformInst[][2] = {{16, 1}, {32, 1}, {48, 2}, {80, 3}};
-
+// whether the tile-per-workgroup kernel has the (CK, NF, stride) instantiation for elements of esize bytes (the lists of common.h)
 bool conv_inst_exists(int ck, int nf, int st, int esize)
 {
-    for (auto &i : kConvInst)
-        if (i[0] == ck && i[1] == nf && i[2] == st) return true;
-    if (esize == 2)
-        for (auto &i : kConvInst16)
-            if (i[0] == ck && i[1] == nf && i[2] == st) return true;
-    if (esize == 4)
-        for (auto &i : kConvInst32)
-            if (i[0] == ck && i[1] == nf && i[2] == st) return true;
+#define X(CK_, NF_, ST_) if (ck == CK_ && nf == NF_ && st == ST_) return true;
+    EMAVFI_CONV_INSTANCES(X)
+    if (esize == 2) { EMAVFI_CONV_INSTANCES_16(X) }
+    if (esize == 4) { EMAVFI_CONV_INSTANCES_F32(X) }
+#undef X
     return false;
 }
 
@@ -85,10 +74,8 @@ struct Layer {
     size_t w_off = 0, b_off = 0, w_bytes = 0;
     bool deform = false;
     bool f16_of_bf16 = false;  // bf16 model, layer consumed by deform_pack_kernel: bf16-rounded weights stored as f16
-    bool mfma16 = false;       // packed for and run by conv3x3_persist16_kernel (v_mfma_f32_16x16x32): 16-bit full-resolution 64 -> (1..64) layers
+    ConvRoute route = CONV_TILE;   // the layer's kernel family and weight layout (common.h); assigned by conv_geometry() and nowhere else
     int pack3 = 0;             // deform_pack3.inl layouts: 1 = DCN, 2 = offset_conv (f16 elements)
-    int ring = 0;              // ConvParams::ring: 1 = stride 2, 64 -> 128 (regular packing for ck 64, nf 4); 2 = 64 -> 64 (regular packing for
-                               // ck 64, nf 2); 3 = 65..67 -> 64 (that + the im2col tail of channels 64..66, 6 KiB)
     bool first6 = false;       // feat_ext_conv1 at mid_channels 64, 16-bit: a second copy of the weights in conv_first.inl's layout (10 KiB)
     bool fp32 = false;         // Plan::dcn32: fp32 weights, packed for and run by the fp32 kernels whatever the plan's storage type
     bool x3 = false;           // EMAVFI_F32X3: three virtual chunks per real one (w_hi, w_lo, w_hi), activations as [hi | lo] f16 halves
@@ -127,38 +114,34 @@ bool conv_geometry(Layer &L, int esize, const LayoutEnv &env_in, bool x3 = false
     // weight sets; the virtual chunks are appended at the end of this function
     const LayoutEnv env = x3 ? LayoutEnv{true, true, true, true} : env_in;
     L.x3 = false;
+    L.route = CONV_TILE;
     L.cin_pad = rup(L.cin_take, 16);
     // Stride-2 layers on the tile kernel: 32-channel chunks, two workgroups per CU (round 2 measured 64-channel chunks - every record read
     // once, but one workgroup per CU - SLOWER: 757 vs 513 us, 534 vs 513 us; that experiment and its instances were removed in round 4,
     // when conv_wreg.inl took the 256-channel layers)
     // 64 -> 128 at stride 2 (context_encoding.0): one 64-channel chunk, each wave keeps one output fragment's weights in registers
     // (conv3x3.inl, conv3x3_s2ring_kernel); EMAVFI_CONV_S2RING=0 keeps the 32-channel-chunk plan (changes the packing: set before packing)
-    const bool s2r_off = env.s2ring_off;
-    L.ring = (L.stride == 2 && esize == 2 && L.cin_pad == 64 && (L.cout + 31) / 32 == 4 && !s2r_off) ? 1 : 0;
-    if (L.ring) {
+    if (L.stride == 2 && esize == 2 && L.cin_pad == 64 && (L.cout + 31) / 32 == 4 && !env.s2ring_off) {
+        L.route = CONV_S2RING;
         L.ck = 64; L.nchunk = 1; L.nf = 4; L.npass = 1; L.coutpad = 128;
         L.w_bytes = (size_t)9 * 4 * 4 * 1024;
-        L.mfma16 = false;
         return true;
     }
     // 64 -> 64 and 65..67 -> 64 at stride 1 (feat_ext_blocks, motion_estimation.0 / .1, reconstruction.0): conv_ring.inl.
     // EMAVFI_CONV_RING=0 keeps round 2's plans (conv3x3_pingpong16_kernel / the CK = 80 tile kernel; changes the packing: set before packing)
-    const bool ring_off = env.ring_off;
-    if (L.stride == 1 && esize == 2 && L.cout > 32 && L.cout <= 64 && L.cin_take >= 64 && L.cin_take <= 67 && !ring_off) {
-        L.ring = L.cin_take == 64 ? 2 : 3;
+    if (L.stride == 1 && esize == 2 && L.cout > 32 && L.cout <= 64 && L.cin_take >= 64 && L.cin_take <= 67 && !env.ring_off) {
+        L.route = L.cin_take == 64 ? CONV_RING : CONV_RING_TAIL3;
         L.ck = L.cin_pad; L.nchunk = 1; L.nf = 2; L.npass = 1; L.coutpad = 64;
-        L.w_bytes = (size_t)9 * 4 * 2 * 1024 + (L.ring == 3 ? 3 * 2 * 1024 : 0);
-        L.mfma16 = false;
+        L.w_bytes = (size_t)9 * 4 * 2 * 1024 + (L.route == CONV_RING_TAIL3 ? 3 * 2 * 1024 : 0);
         return true;
     }
     // 256 output channels from >= 128 inputs (context_encoding.1 / .2 at mid_channels 64): conv_wreg.inl - all eight output fragments in one
     // pass, weights streamed into registers.  EMAVFI_CONV_WREG=0 keeps round 3's plans (changes the packing: set before packing)
     if (esize == 2 && L.cout > 224 && L.cout <= 256 && L.cin_pad >= 128 && !env.wreg_off &&
         ((L.stride == 1 && L.cin_pad % 64 == 0) || (L.stride == 2 && L.cin_pad % 32 == 0))) {
-        L.ring = 4;
+        L.route = CONV_WREG;
         L.ck = L.stride == 1 ? 64 : 32; L.nchunk = L.cin_pad / L.ck; L.nf = 8; L.npass = 1; L.coutpad = 256;
         L.w_bytes = (size_t)L.nchunk * 9 * (L.ck / 16) * 8 * 1024;
-        L.mfma16 = false;
         return true;
     }
     if (L.stride == 2) L.ck = (L.cin_pad % 32 == 0) ? 32 : 16;
@@ -181,14 +164,17 @@ bool conv_geometry(Layer &L, int esize, const LayoutEnv &env_in, bool x3 = false
     while (!conv_inst_exists(L.ck, L.nf, L.stride, esize) && L.nf > 1) { L.nf /= 2; L.npass = frags / L.nf; }
     if (!conv_inst_exists(L.ck, L.nf, L.stride, esize)) return false;
     L.w_bytes = (size_t)L.npass * L.nchunk * 9 * (L.ck * esize / 32) * L.nf * 1024;
-    // full-resolution 64-channel layers with two output fragments: the 16x16x32 MFMA shape (conv3x3.inl, conv3x3_persist16_kernel).
-    // EMAVFI_CONV_MFMA16=0 keeps the 32x32x16 kernels.
-    L.mfma16 = esize == 2 && L.stride == 1 && L.ck == 64 && (L.nf == 2 || L.nf == 1) && L.nchunk == 1 && L.npass == 1 && !env.m16_off;
-    // 32 -> <= 4 channels (reconstruction.2): the planar-head kernel on 16x16x32 (conv_light.inl) reads the same regrouped packing
-    if (esize == 2 && L.stride == 1 && L.ck == 32 && L.nf == 1 && L.nchunk == 1 && L.npass == 1 && L.cout <= 4 && !env.m16_off) L.mfma16 = true;
-    if (x3) {
-        if (esize != 2 || L.mfma16 || L.ring) return false;
+    // 16-bit full-resolution layers of one chunk and one pass leave the tile kernel (same w_bytes: the 16x16x32 packing regroups the elements):
+    const bool one = esize == 2 && L.stride == 1 && L.nchunk == 1 && L.npass == 1, head = L.nf == 1 && L.cout <= 4;
+    // 64 channels in, <= 64 out on 16x16x32 MFMAs, planar heads (motion_estimation.2, reconstruction.2) on conv_light.inl; EMAVFI_CONV_MFMA16=0:
+    // the 32x32x16 kernels, the persistent one where it beats the tile kernel (launch_conv16, conv3x3.inl: 64 -> 64, 64 -> 32 / 64 -> 2, 67 -> 27)
+    if (one && !env.m16_off && L.ck == 64 && (L.nf == 2 || L.nf == 1)) L.route = head ? CONV_LIGHT : CONV_PERSIST16;
+    else if (one && !env.m16_off && L.ck == 32 && head) L.route = CONV_LIGHT;
+    else if (one && ((L.ck == 64 && (L.nf == 2 || L.nf == 1)) || (L.ck == 80 && L.nf == 1))) L.route = CONV_PERSIST;
+    if (x3) {   // (every switch is off above: the route is CONV_TILE or CONV_PERSIST; three weight sets leave the tile kernel only)
+        if (esize != 2) return false;
         L.x3 = true;
+        L.route = CONV_TILE;
         L.nchunk *= 3;      // virtual chunks 3 c + t
         L.w_bytes *= 3;
     }
@@ -198,19 +184,28 @@ bool conv_geometry(Layer &L, int esize, const LayoutEnv &env_in, bool x3 = false
 bool deform_geometry(Layer &L, int esize)
 {
     const int cpad = rup(L.cin_take, 16), frags = (L.cout + 31) / 32;
-    for (auto &i : kDeformInst)
-        if (i[0] >= cpad && i[1] >= frags) {
-            L.cin_pad = L.ck = i[0];
-            L.nchunk = 1;
-            L.nf = i[1];
-            L.npass = 1;
-            L.coutpad = L.nf * 32;
-            L.w_bytes = (size_t)9 * (L.ck * esize / 32) * L.nf * 1024;
-            L.deform = true;
-            return true;
-        }
-    return false;
+    int ck = 0, nf = 0;   // the narrowest instantiation that holds the layer
+#define X(CK_, NF_) if (!ck && CK_ >= cpad && NF_ >= frags) { ck = CK_; nf = NF_; }
+    EMAVFI_DEFORM_INSTANCES(X)
+#undef X
+    if (!ck) return false;
+    L.cin_pad = L.ck = ck; L.nchunk = 1; L.nf = nf; L.npass = 1; L.coutpad = nf * 32;
+    L.w_bytes = (size_t)9 * (L.ck * esize / 32) * L.nf * 1024;
+    L.deform = true;
+    return true;
 }
+
+// ---- which layers run as ONE launch: the fusion rules, each stated once (sw: the switch word, common.h SW_*) ----
+// conv_ring2.inl: two consecutive 64 -> 64 layers, the tensor between them only an LDS ring
+bool can_pair(const Layer &a, const Layer &b, unsigned sw) { return a.route == CONV_RING && b.route == CONV_RING && !a.f16_of_bf16 && !b.f16_of_bf16 && !(sw & SW_NO_RING2); }
+// conv_ring_first.inl: the 64 -> 64 layer behind feat_ext_conv1 (conv_first.inl) in the same launch
+bool can_follow_first(const Layer &blk0, unsigned sw) { return blk0.route == CONV_RING && !(sw & SW_NO_FIRSTRING); }
+// conv_ring.inl, HEAD: a planar head of <= 2 channels computed from the 64 -> 64 layer's rows in LDS (motion_estimation.1 + .2)
+bool can_fuse_head(const Layer &a, const Layer &head, unsigned sw) { return a.route == CONV_RING && head.route == CONV_LIGHT && head.ck == 64 && head.cout <= 2 && !(sw & SW_NO_HEAD); }
+// conv_ring_tail.inl: 64 -> 32 -> <= 3 planes through a second LDS ring (reconstruction.1 + .2)
+bool can_fuse_tail(const Layer &r1, const Layer &r2, unsigned sw) { return r1.route == CONV_PERSIST16 && r1.nf == 1 && r1.cout == 32 && r2.route == CONV_LIGHT && r2.ck == 32 && r2.cout <= 3 && !(sw & SW_NO_TAILFUSE); }
+// conv_wreg.inl: per-tile channel sums of the p4 = 256 channels instead of the layer's output (context_encoding.2 feeds the pool only)
+bool can_pool_fuse(const Layer &c2, int p4, unsigned sw) { return c2.route == CONV_WREG && p4 == 256 && !(sw & SW_NO_POOLFUSE); }
 
 // bf16 model: consecutive one-launch packs hand each other f16 bit patterns (the window is f16 on chip anyway; the
 // receiving pack skips its in-LDS conversion pass).  EMAVFI_PACK_F16_CHAIN=0 keeps bf16 between them (A/B switch).
@@ -346,7 +341,7 @@ bool build_plan(Plan &P, int in_ch, int mid, int nb, int dtype)
         // the deform_pack3.inl layout where that kernel serves the shape (both 16-bit models); off[i] keeps the conv3x3 layout
         P.has_offh = true;
         // (feat16: see Plan; needs the ring kernels on both sides of `feat` and at least one block in front of the last one)
-        P.feat16 = dtype == EMAVFI_BF16 && pack_f16_chain() && nb >= 2 && P.blk[nb - 1].ring == 2 && P.c0.ring == 1 && P.m0.ring == 2 && P.fpad - mid == 16 &&
+        P.feat16 = dtype == EMAVFI_BF16 && pack_f16_chain() && nb >= 2 && P.blk[nb - 1].route == CONV_RING && P.c0.route == CONV_S2RING && P.m0.route == CONV_RING && P.fpad - mid == 16 &&
                    deform16_can_fuse_offset_conv(P.dcn[0].ck, P.dcn[0].nf, P.dcn[0].cin_take, P.off[0].ck, P.off[0].nf);   // (EMAVFI_NO_FUSED_OFFSET: once per process)
         if (P.feat16) P.c0.f16_of_bf16 = P.m0.f16_of_bf16 = true;
         for (int i = 0; i < nb && ok; ++i) {
@@ -415,7 +410,7 @@ int run_conv(const Plan &P, const Layer &L, const void *packed, int B, hipStream
     ConvParams c = a.c;
     if (!L.x3) c.out32 = nullptr;
     if (a.second) { c.w2 = blob_at(packed, a.second->w_off); c.bias2 = (const float *)blob_at(packed, a.second->b_off); }
-    c.out_fill = (L.ring == 2 && !head && !first && c.out && c.cstore == 64 && (size_t)c.out_ps * P.esize == 144) ? 1 : 0;   // (also the fused pair's second layer)
+    c.out_fill = (L.route == CONV_RING && !head && !first && c.out && c.cstore == 64 && (size_t)c.out_ps * P.esize == 144) ? 1 : 0;   // (also the fused pair's second layer)
     if (head) { c.head_w = blob_at(packed, a.head->w_off); c.head_bias = (const float *)blob_at(packed, a.head->b_off); }
     // a single-chunk layer wider than its input's pixel stride (CK = 80 fed from the 72-channel fusion buffers) reads the missing pieces as zeros
     if (L.nchunk == 1 && c.in_ps < L.ck) c.in_pieces = c.in_ps * P.esize / 16;
@@ -427,14 +422,15 @@ int run_conv(const Plan &P, const Layer &L, const void *packed, int B, hipStream
     c.zeros = blob_at(packed, P.zero_off); c.w = blob_at(packed, L.w_off);
     if (!c.bias_mode) c.bias = (const float *)blob_at(packed, L.b_off);
     c.Hout = (c.Hin + L.stride - 1) / L.stride; c.Wout = (c.Win + L.stride - 1) / L.stride;   // (out_coff stays 0: no layer writes into the middle of a pixel)
-    c.B = B; c.nchunk = L.nchunk; c.npass = L.npass; c.ck = L.ck; c.nf = L.nf; c.stride = L.stride; c.mfma16 = L.mfma16 ? 1 : 0; c.ring = L.ring;
+    c.B = B; c.nchunk = L.nchunk; c.npass = L.npass; c.ck = L.ck; c.nf = L.nf; c.stride = L.stride; c.route = L.route;
     const bool f16_kernels = L.f16_of_bf16 && !L.deform;   // feat16: f16 activations in, bf16-rounded weights stored as f16
     const int kd = f16_kernels ? (int)EMAVFI_F16 : P.dtype;
 #if defined(EMAVFI_DEFORM_STAMPS) && EMAVFI_DEFORM_STAMPS
-    if (L.ring == 4 && !a.c.out_planar && !getenv("EMAVFI_STAMP_RING")) c.out_planar = reinterpret_cast<float *>(debug_stamp_buffer());   // diagnostic build: conv_wreg.inl's stamps (tools/wreg_stamps.py)
+    if (L.route == CONV_WREG && !a.c.out_planar && !getenv("EMAVFI_STAMP_RING")) c.out_planar = reinterpret_cast<float *>(debug_stamp_buffer());   // diagnostic build: conv_wreg.inl's stamps (tools/wreg_stamps.py)
     {   // diagnostic build: the LDS-ring kernels' stamps (tools/ring_stamps.py); EMAVFI_STAMP_RING = ring | tail | head | ringtail | ringfirst
         const char *sel = getenv("EMAVFI_STAMP_RING");
-        const char *kind = first ? "ringfirst" : (head && L.ring == 2) ? "head" : (head && L.mfma16) ? "ringtail" : L.ring == 3 ? "tail" : (L.ring == 2 && !a.second) ? "ring" : "";
+        const char *kind = first ? "ringfirst" : head ? (L.route == CONV_RING ? "head" : L.route == CONV_PERSIST16 ? "ringtail" : "")
+                                                  : L.route == CONV_RING_TAIL3 ? "tail" : (L.route == CONV_RING && !a.second) ? "ring" : "";
         if (sel && kind[0] && strcmp(sel, kind) == 0) c.stamps = debug_stamp_buffer();
     }
     if (const char *rep = getenv("EMAVFI_DEBUG_REPEAT_CONV"))   // diagnostic build: as EMAVFI_DEBUG_REPEAT_PACK, for the plain layers
@@ -505,7 +501,7 @@ int run_deform(const Plan &P, const Layer &L, const void *packed, int B, hipStre
 int pack_layer(const Layer &L, const void *const *params, void *packed, int dtype, hipStream_t s, bool bias_f16 = false)
 {
     PackDesc d{L.cout, L.cin_raw, L.cin_off, L.cin_take, L.ck, L.nchunk, L.nf, L.npass, L.perm, L.f16_of_bf16 ? 1 : 0, bias_f16 ? 1 : 0};
-    d.mfma16 = L.mfma16 ? 1 : 0; d.ring = L.ring; d.first6 = L.first6 ? 1 : 0; d.pack3 = L.pack3; d.x3 = L.x3 ? 1 : 0;
+    d.route = L.route; d.first6 = L.first6 ? 1 : 0; d.pack3 = L.pack3; d.x3 = L.x3 ? 1 : 0;
     return launch_pack_conv((const float *)params[L.param], (const float *)params[L.param + 1], (char *)packed + L.w_off,
                             (float *)((char *)packed + L.b_off), d, L.f16_of_bf16 ? (int)EMAVFI_F16 : L.fp32 ? (int)EMAVFI_F32 : dtype, s);
 }
@@ -554,7 +550,7 @@ void carve_forward(const Plan &P, Workspace &ws, FwdBuffers &f, int B, int H, in
     f.ntiles = ((f.W4 + 31) / 32) * ((f.H4 + 3) / 4);   // conv_wreg_tiles()
     f.nparts2 = f.ntiles >= 32 ? (f.ntiles / 16 < 32 ? f.ntiles / 16 : 32) : 1;
     if (f.nparts2 > f.nparts) f.nparts2 = f.nparts;
-    f.tpart = P.c2.ring == 4 ? (float *)ws.take((size_t)B * f.ntiles * f.p4 * sizeof(float)) : nullptr;
+    f.tpart = P.c2.route == CONV_WREG ? (float *)ws.take((size_t)B * f.ntiles * f.p4 * sizeof(float)) : nullptr;
     f.ctx = (float *)ws.take((size_t)B * P.mid * sizeof(float));
     f.table = (float *)ws.take((size_t)B * 16 * P.m0.coutpad * sizeof(float));
     f.flow = (float *)ws.take(px * 2 * sizeof(float));
@@ -733,7 +729,7 @@ int context_stage(const Plan &P, const void *packed, const void *feat_cl, const 
     conv_work(P, P.c2, B, f.H4, f.W4, e, fl, by);
     // conv_wreg.inl at the reference width: the layer's only reader is the pool, so the kernel writes per-tile channel sums instead of the
     // tensor (no 236 MB store + read at B = 8 x 720p); avg_pool_partial then adds tiles instead of pixels.  EMAVFI_CONV_POOLFUSE=0: A/B
-    const bool poolfuse = P.c2.ring == 4 && f.p4 == 256 && !(emavfi_switches() & SW_NO_POOLFUSE);
+    const bool poolfuse = can_pool_fuse(P.c2, f.p4, emavfi_switches());
     if (poolfuse) {
         EMAVFI_STEP(rec, conv_name(P, P.c2) + " context_encoding.2 + pool (tile sums)", fl, by - (double)B * f.H4 * f.W4 * 4 * mid * e,
                     run_conv(P, P.c2, packed, B, s, ConvCall{}.from(f.c2, f.p4, f.H4, f.W4).to_pool_sums(f.tpart, f.p4).act(EPI_RELU)));
@@ -763,8 +759,7 @@ int reconstruction_stage(const Plan &P, const void *packed, const void *x, const
     EMAVFI_STEP(rec, conv_name(P, P.r0) + " reconstruction.0", fl, by,
                 run_conv(P, P.r0, packed, B, s, ConvCall{}.from(x, P.fps, H, W).to(f.fA, P.p_mid, P.p_mid).act(EPI_RELU)));
     // reconstruction.1 + .2 in one launch (conv_ring_tail.inl): .1's rows never leave the LDS.  EMAVFI_CONV_TAILFUSE=0: two
-    if (P.r1.mfma16 && P.r1.ck == 64 && P.r1.nf == 1 && P.r1.cout == 32 && P.r1.ring == 0 && P.r2.mfma16 && P.r2.ck == 32 && P.r2.nf == 1 && P.r2.cout <= 3 &&
-        !(sw & SW_NO_TAILFUSE)) {
+    if (can_fuse_tail(P.r1, P.r2, sw)) {
         double fl2, by2;
         conv_work(P, P.r1, B, H, W, e, fl, by);
         conv_work(P, P.r2, B, H, W, 4.0, fl2, by2);
@@ -875,7 +870,7 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
             const char *blob = (const char *)packed;
             FirstParams fp{frame1, frame2, f.fA, blob ? blob + P.conv1.w_off + P.conv1.w_bytes : nullptr,
                            blob ? (const float *)(blob + P.conv1.b_off) : nullptr, P.p_mid, H, W, B, 1};
-            if (P.nb >= 1 && P.blk[0].ring == 2 && !(sw & SW_NO_FIRSTRING)) {
+            if (P.nb >= 1 && can_follow_first(P.blk[0], sw)) {
                 // ... and feat_ext_blocks.conv_block_0 + ReLU behind it in the SAME launch (conv_ring_first.inl): feat_ext_conv1's
                 // tensor exists only as an LDS ring.  EMAVFI_CONV_FIRSTRING=0 (read per call): two launches
                 double fl2, by2;
@@ -901,7 +896,7 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
     for (int i = first_blk; i < P.nb; ++i) {
         // two consecutive conv_blocks as ONE launch (conv_ring2.inl): the tensor between them exists only as an LDS ring.
         // EMAVFI_CONV_RING2=0: one launch each
-        const bool pair = i + 1 < P.nb && P.blk[i].ring == 2 && P.blk[i + 1].ring == 2 && !P.blk[i].f16_of_bf16 && !P.blk[i + 1].f16_of_bf16 && !(sw & SW_NO_RING2);
+        const bool pair = i + 1 < P.nb && can_pair(P.blk[i], P.blk[i + 1], sw);
         const int j = pair ? i + 1 : i;   // the layer whose output leaves the launch
         const bool last = j == P.nb - 1;  // the last block writes feat straight into the fusion buffer
         void *dst = last ? f.fu0 : nxt;
@@ -937,7 +932,7 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
     EMAVFI_STEP(rec, conv_name(P, P.m0) + " motion_estimation.0(ctx folded)", fl, by,
                 run_conv(P, P.m0, packed, B, s, ConvCall{}.from(f.fu0, P.fps, H, W).bias_rows(f.table).to(f.fA, P.p_mid, P.p_mid).act(EPI_RELU).other16(feat16)));
     // motion_estimation.1 + .2 in one launch (conv_ring.inl, HEAD): .1's rows never leave the LDS.  EMAVFI_CONV_HEAD=0: two launches
-    if (P.m1.ring == 2 && P.m2.mfma16 && P.m2.ck == 64 && P.m2.nf == 1 && P.m2.cout <= 2 && !(sw & SW_NO_HEAD)) {
+    if (can_fuse_head(P.m1, P.m2, sw)) {
         double fl2, by2;
         conv_work(P, P.m1, B, H, W, e, fl, by);
         conv_work(P, P.m2, B, H, W, 4.0, fl2, by2);

@@ -12,9 +12,8 @@ struct PackDesc {
     int via_bf16;                          // 1 = round every weight to bf16 first, then store it in the packed type
                                            // (f16 fragments holding the bf16 model's weights exactly: deform_pack.inl)
     int bias_f16;                          // 1 = the fp32 bias table holds fp16-rounded values (autocast casts the bias too)
-    int mfma16;                            // 1 = fragments for v_mfma_f32_16x16x32: [tap][k32][cout16 block][lane (i, kb)][8 elements]
-    int ring;                              // Layer::ring; 3: the main fragments take input channels 0..63 (ck = 64) and conv_ring.inl's tail
-                                           // [j 3][nf 2][lane (r, h)][8] follows: W[32 nf + r][64 + (e & 3)][tap slot 4 j + 2 h + (e >> 2)]
+    int route;                             // ConvRoute (common.h): the layer's weight layout, written by pack_conv_kernel
+    int unused_;                           // (keeps first6 / x3 / pack3 where the other pack kernels' code objects read them)
     int first6;                            // conv_first.inl layout (6 -> 64, 16-bit): [kg 5][nf 2][lane (r, h)][8]: W[32 nf + r][channel e][tap 2 kg + h]
     int x3;                                // EMAVFI_F32X3: nchunk counts VIRTUAL chunks 3 c + t; t = 0, 2 carry f16(w), t = 1 carries f16(w - f16(w))
     int pack3;                             // deform_pack3.inl layouts (f16 elements, cin_take = 67): 1 = DCN 67 -> <= 67, 2 = offset_conv 67 -> 27;

@@ -45,7 +45,9 @@ __global__ void pack_conv_kernel(const float *__restrict__ w, const float *__res
                                  float *__restrict__ bp, PackDesc d)
 {
     constexpr int CHKG = DT<T>::CHKG, EPV = DT<T>::EPV;
-    if (d.ring == 3) { d.ck = 64; }   // channels 64.. go to the tail below
+    // the layouts beside the regular one (ConvRoute, common.h): fragments for v_mfma_f32_16x16x32, [tap][k32][cout16 block][lane (i, kb)][8 elements];
+    const bool k32 = d.route == CONV_PERSIST16 || d.route == CONV_LIGHT, tail3 = d.route == CONV_RING_TAIL3;
+    if (tail3) d.ck = 64;   // the main fragments take input channels 0..63, channels 64.. go to the tail below
     const int KG = d.ck / CHKG;
     const size_t total = (size_t)d.npass * d.nchunk * 9 * KG * d.nf * 64 * EPV;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
@@ -59,7 +61,7 @@ __global__ void pack_conv_kernel(const float *__restrict__ w, const float *__res
         const int pass = (int)t;
         int co = route_cout(pass * d.nf * 32 + n * 32 + (lane & 31), d.perm);
         int ci = chunk * d.ck + kg * CHKG + (lane >> 5) * EPV + e;
-        if (d.mfma16) {   // same number of elements, regrouped: (kg, n) enumerates (k32, cout16 block) = KG * nf = (KG / 2) * (2 nf)
+        if (k32) {   // same number of elements, regrouped: (kg, n) enumerates (k32, cout16 block) = KG * nf = (KG / 2) * (2 nf)
             const int flat = kg * d.nf + n, nb16 = 2 * d.nf, k32 = flat / nb16, blk = flat - k32 * nb16;
             co = route_cout(pass * d.nf * 32 + blk * 16 + (lane & 15), d.perm);
             ci = chunk * d.ck + k32 * 32 + (lane >> 4) * 8 + e;
@@ -76,7 +78,7 @@ __global__ void pack_conv_kernel(const float *__restrict__ w, const float *__res
         if (term == 1) v = v - (float)(T)v;   // the lo part of the weight
         wp[idx] = (T)v;
     }
-    if (d.ring == 3 && EPV == 8) {
+    if (tail3 && EPV == 8) {
         for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < (size_t)3 * 2 * 64 * 8; idx += (size_t)gridDim.x * blockDim.x) {
             size_t t = idx;
             const int e = t % 8; t /= 8;
