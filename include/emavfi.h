@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -260,6 +260,62 @@ int emavfi_preprocess_u8(const unsigned char *frames_hwc, float *out_nchw, int B
                          const float *mean, const float *std, void *stream);
 int emavfi_postprocess_u8(const float *frames_nchw, unsigned char *out_hwc, int B, int H, int W, int C,
                           const double *mean, const double *std, int denormalize, void *stream);
+
+/* NV12 frames, in and out: what video decoders produce - a full-resolution Y plane [H][W] and a half-resolution plane of interleaved
+ * U,V byte pairs [ceil(H/2)][ceil(W/2)][2], 1.5 bytes per pixel.  Both planes have their own pointer, their own row pitch and their own
+ * batch stride (bytes): the pitched surfaces of a hardware decoder are read / written in place.  Odd H and W are valid.  C = 3 only.
+ *
+ * COLOUR DEFINITION (the one place).  THIS IS THE PROJECT'S OWN DEFINITION: IT MAKES NO CLAIM OF BYTE PARITY WITH ANY OUTSIDE LIBRARY
+ * (swscale, OpenCV, a vendor's colour-conversion block ...); those differ among themselves in rounding and chroma siting.
+ * Standards: BT.601 Kr = 0.299, Kb = 0.114; BT.709 Kr = 0.2126, Kb = 0.0722; Kg = 1 - Kr - Kb.  All arithmetic is signed 32-bit integer
+ * fixed point with 20 fractional bits: every coefficient is floor(k * 2^20 + 0.5) of its real value k computed in double, `>> 20` is
+ * floor division by 2^20, clip is to 0..255.
+ *   Decode (NV12 -> bytes): pixel (y, x) uses the chroma pair (y >> 1, x >> 1) (nearest upsampling); u = U - 128, v = V - 128;
+ *     limited range: l = max(Y - 16, 0), CY = 255/219, s = 255/224;  full range: l = Y, CY = 1, s = 1;
+ *     CVR = 2(1-Kr)s, CUG = -2Kb(1-Kb)s/Kg, CVG = -2Kr(1-Kr)s/Kg, CUB = 2(1-Kb)s;
+ *     R = clip((CY l + CVR v + 2^19) >> 20), G = clip((CY l + CUG u + CVG v + 2^19) >> 20), B = clip((CY l + CUB u + 2^19) >> 20).
+ *   Encode (bytes -> NV12): limited range: t = 219/255, s' = 224/255, yoff = 16;  full range: t = 1, s' = 1, yoff = 0;
+ *     Y = clip(((YR R + YG G + YB B + 2^19) >> 20) + yoff) per pixel, (YR, YG, YB) = (Kr, Kg, Kb) t;
+ *     chroma from the rounded mean of the 2x2 block: each of r, g, b = (sum of 4 + 2) >> 2, coordinates past the last row / column
+ *     clamped (an odd edge block still has four samples);
+ *     U = clip(((UR r + UG g + UB b + 2^19) >> 20) + 128), (UR, UG, UB) = (-Kr/(2(1-Kb)), -Kg/(2(1-Kb)), 0.5) s';
+ *     V = clip(((VR r + VG g + VB b + 2^19) >> 20) + 128), (VR, VG, VB) = (0.5, -Kg/(2(1-Kr)), -Kb/(2(1-Kr))) s'.
+ *   The integer tables, decode {CY, CVR, CUG, CVG, CUB} and encode {YR, YG, YB, UR, UG, UB, VR, VG, VB} (the worst intermediate,
+ *   CY 239 + CUB 128 + 2^19 at BT.709 limited, is 5.8e8 < 2^31):
+ *     EMAVFI_YUV_BT601_LIMITED decode {1220945, 1673555, -410793, -852458, 2115221}
+ *                              encode {269262, 528618, 102662, -155423, -305128, 460551, 460551, -385654, -74897}
+ *     EMAVFI_YUV_BT601_FULL    decode {1048576, 1470104, -360853, -748826, 1858077}
+ *                              encode {313524, 615514, 119538, -176932, -347356, 524288, 524288, -439026, -85262}
+ *     EMAVFI_YUV_BT709_LIMITED decode {1220945, 1879825, -223607, -558796, 2215014}
+ *                              encode {191455, 644067, 65019, -105533, -355018, 460551, 460551, -418321, -42230}
+ *     EMAVFI_YUV_BT709_FULL    decode {1048576, 1651297, -196424, -490864, 1945738}
+ *                              encode {222927, 749942, 75707, -120138, -404150, 524288, 524288, -476214, -48074}
+ *   emavfi_yuv_coefficients (host only) returns them.
+ * `order`: which byte is channel 0 of the decoded / encoded pixel, i.e. which colour mean[0] / std[0] and plane 0 of the fp32 tensor
+ *   belong to.  EMAVFI_ORDER_BGR is what cv2 hands the reference - which then normalises BGR with RGB statistics; that quirk is kept,
+ *   it is the default of the Python layer -, EMAVFI_ORDER_RGB the alternative.
+ * emavfi_preprocess_nv12 is DEFINED as emavfi_preprocess_u8 (C = 3) applied to the decoded bytes (the same fp32 /255, - mean, / std with
+ *   true divisions in that order: bit for bit), emavfi_postprocess_nv12 as the encode of the bytes emavfi_postprocess_u8 would write (the
+ *   same float64 arithmetic, truncation and NaN -> 0).
+ * EMAVFI_E_ARG (never an abort): null pointers, y_pitch < W, uv_pitch < 2 ceil(W/2), for B > 1 a batch stride smaller than its plane, a
+ *   zero std, an unknown standard or order, a Y or UV pointer that is not 2-byte aligned.  The Y and UV pointers are device pointers or
+ *   pinned (device-mapped) host memory, as for the u8 entries; `mean` / `std`: host pointers to 3 values, fp32 / float64 as there.
+ * Nothing is allocated, nothing synchronises, all work goes on `stream`.  Access width: with both byte pointers, pitches and batch
+ *   strides multiples of 16, a 16-byte aligned fp32 pointer and W % 4 == 0, every full 2-row x 16-column block moves with 16-byte
+ *   accesses; everything else (and the right / bottom remainders) takes a scalar path with the same per-element arithmetic. */
+#define EMAVFI_YUV_BT601_LIMITED 0
+#define EMAVFI_YUV_BT601_FULL 1
+#define EMAVFI_YUV_BT709_LIMITED 2
+#define EMAVFI_YUV_BT709_FULL 3
+#define EMAVFI_ORDER_BGR 0
+#define EMAVFI_ORDER_RGB 1
+int emavfi_yuv_coefficients(int standard, int decode[5], int encode[9]);
+int emavfi_preprocess_nv12(const unsigned char *y, size_t y_pitch, size_t y_batch_stride, const unsigned char *uv, size_t uv_pitch,
+                           size_t uv_batch_stride, float *out_nchw, int B, int H, int W, int standard, int order,
+                           const float *mean, const float *std, void *stream);
+int emavfi_postprocess_nv12(const float *frames_nchw, unsigned char *y, size_t y_pitch, size_t y_batch_stride, unsigned char *uv,
+                            size_t uv_pitch, size_t uv_batch_stride, int B, int H, int W, int standard, int order,
+                            const double *mean, const double *std, int denormalize, void *stream);
 
 /* One conv / conv_block (ema_vfi.py:7-14): Conv2d(k=3, p=1, stride 1 or 2) + activation.
  * x [B,Cin,H,W], weight [Cout,Cin,3,3], bias [Cout], y [B,Cout,ceil(H/stride),ceil(W/stride)]. */

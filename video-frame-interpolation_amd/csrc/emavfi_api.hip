@@ -1328,6 +1328,61 @@ int emavfi_postprocess_u8(const float *frames_nchw, unsigned char *out_hwc, int 
     return EMAVFI_OK;
 }
 
+// ---- NV12 frames (include/emavfi.h, "NV12"): the checks both entries share, in an order that lets a caller without a device reach each
+static int nv12_check(const char *what, const void *y, size_t y_pitch, size_t y_bstride, const void *uv, size_t uv_pitch, size_t uv_bstride,
+                      const void *f32, int B, int H, int W, int standard, int order, const float *mean32, const float *std32, const double *mean64,
+                      const double *std64)
+{
+    if (!(mean32 && std32) && !(mean64 && std64)) return fail(EMAVFI_E_ARG, "%s: null mean / std", what);
+    if (B < 1 || H < 1 || W < 1) return fail(EMAVFI_E_ARG, "%s: B, H, W must be >= 1", what);
+    if (standard < EMAVFI_YUV_BT601_LIMITED || standard > EMAVFI_YUV_BT709_FULL)
+        return fail(EMAVFI_E_ARG, "%s: unknown standard %d (EMAVFI_YUV_BT601_LIMITED .. EMAVFI_YUV_BT709_FULL)", what, standard);
+    if (order != EMAVFI_ORDER_BGR && order != EMAVFI_ORDER_RGB)
+        return fail(EMAVFI_E_ARG, "%s: unknown order %d (EMAVFI_ORDER_BGR or EMAVFI_ORDER_RGB)", what, order);
+    const size_t uv_row = 2 * (((size_t)W + 1) / 2), uv_rows = ((size_t)H + 1) / 2;
+    if (y_pitch < (size_t)W) return fail(EMAVFI_E_ARG, "%s: y_pitch %zu is smaller than W = %d", what, y_pitch, W);
+    if (uv_pitch < uv_row) return fail(EMAVFI_E_ARG, "%s: uv_pitch %zu is smaller than 2 * ceil(W / 2) = %zu", what, uv_pitch, uv_row);
+    if (B > 1 && (y_bstride < (size_t)(H - 1) * y_pitch + (size_t)W || uv_bstride < (uv_rows - 1) * uv_pitch + uv_row))
+        return fail(EMAVFI_E_ARG, "%s: a batch stride (y %zu, uv %zu) is smaller than its plane", what, y_bstride, uv_bstride);
+    for (int c = 0; c < 3; ++c)
+        if (std32 ? !(std32[c] != 0.0f) : !(std64[c] != 0.0)) return fail(EMAVFI_E_ARG, "%s: std[%d] must be non-zero", what, c);
+    if (!y || !uv || !f32) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
+    if (((uintptr_t)y | (uintptr_t)uv) & 1) return fail(EMAVFI_E_ARG, "%s: the Y and UV pointers must be 2-byte aligned", what);
+    if ((uintptr_t)f32 & 3) return fail(EMAVFI_E_ARG, "%s: the fp32 pointer must be 4-byte aligned", what);
+    return EMAVFI_OK;
+}
+
+int emavfi_yuv_coefficients(int standard, int decode[5], int encode[9])
+{
+    if (standard < EMAVFI_YUV_BT601_LIMITED || standard > EMAVFI_YUV_BT709_FULL)
+        return fail(EMAVFI_E_ARG, "yuv_coefficients: unknown standard %d (EMAVFI_YUV_BT601_LIMITED .. EMAVFI_YUV_BT709_FULL)", standard);
+    if (!decode || !encode) return fail(EMAVFI_E_ARG, "yuv_coefficients: null pointer");
+    yuv_coefficients(standard, decode, encode);
+    return EMAVFI_OK;
+}
+
+int emavfi_preprocess_nv12(const unsigned char *y, size_t y_pitch, size_t y_batch_stride, const unsigned char *uv, size_t uv_pitch,
+                           size_t uv_batch_stride, float *out_nchw, int B, int H, int W, int standard, int order, const float *mean,
+                           const float *std, void *stream)
+{
+    if (const int rc = nv12_check("preprocess_nv12", y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, out_nchw, B, H, W, standard, order,
+                                  mean, std, nullptr, nullptr); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_preprocess_nv12(y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, out_nchw, B, H, W, standard, order, mean, std,
+                                      (hipStream_t)stream), "preprocess_nv12");
+    return EMAVFI_OK;
+}
+
+int emavfi_postprocess_nv12(const float *frames_nchw, unsigned char *y, size_t y_pitch, size_t y_batch_stride, unsigned char *uv, size_t uv_pitch,
+                            size_t uv_batch_stride, int B, int H, int W, int standard, int order, const double *mean, const double *std,
+                            int denormalize, void *stream)
+{
+    if (const int rc = nv12_check("postprocess_nv12", y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, frames_nchw, B, H, W, standard,
+                                  order, nullptr, nullptr, mean, std); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_postprocess_nv12(frames_nchw, y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, B, H, W, standard, order, mean, std,
+                                       denormalize ? 1 : 0, (hipStream_t)stream), "postprocess_nv12");
+    return EMAVFI_OK;
+}
+
 // ---- stage-level entries (diagnostics / parity tests of single operators): one layer, packed into the workspace and run inside one call ----
 // Their plan - the kernel storage type (EMAVFI_F32X3: the f16 kernels on [hi | lo] halves) and, from op_carve, the zero page - and
 // their layer, as the plan of a model lays it out: a bf16 DCN on the LDS-window kernel contracts bf16-rounded weights stored as f16

@@ -77,6 +77,13 @@ int launch_preprocess_u8(const unsigned char *src, float *dst, int B, int H, int
                          hipStream_t s);
 int launch_postprocess_u8(const float *src, unsigned char *dst, int B, int H, int W, int C, const double *mean, const double *stdv,
                           int denorm, hipStream_t s);
+// NV12 frames (include/emavfi.h): pitches and batch strides in bytes; standard / order are the header's codes, already validated
+void yuv_coefficients(int standard, int dec[5], int enc[9]);   // host only
+int launch_preprocess_nv12(const unsigned char *y, size_t y_pitch, size_t y_bstride, const unsigned char *uv, size_t uv_pitch, size_t uv_bstride,
+                           float *dst, int B, int H, int W, int standard, int order, const float *mean, const float *stdv, hipStream_t s);
+int launch_postprocess_nv12(const float *src, unsigned char *y, size_t y_pitch, size_t y_bstride, unsigned char *uv, size_t uv_pitch,
+                            size_t uv_bstride, int B, int H, int W, int standard, int order, const double *mean, const double *stdv, int denorm,
+                            hipStream_t s);
 // deform_pack3.inl's census: sums the 64 atomic slots of each of `nblocks` launches ([block][64][4] u32) into out[block][4] u64 =
 // {fix-up wave-taps, totals[block], samples outside the window, max |offset| as fp32 bits}
 int launch_census_reduce(const unsigned *census, unsigned long long *out, int nblocks, const unsigned long long *totals, hipStream_t s);

@@ -1273,6 +1273,228 @@ int launch_postprocess_u8(const float *src, unsigned char *dst, int B, int H, in
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// NV12 frames (include/emavfi.h, "NV12"): a pitched full-resolution Y plane and a pitched half-resolution plane of interleaved U,V
+// pairs, decoded to / encoded from the bytes the u8 kernels above read / write, in signed 32-bit fixed point with 20 fractional bits.
+//   preprocess_nv12  == preprocess_u8 of the decoded bytes (same fp32 /255, - mean, / std);
+//   postprocess_nv12 == the encode of the bytes postprocess_u8 would write (same float64 arithmetic, truncation, NaN -> 0).
+// One lane owns a block of 2 rows x 16 columns = 8 chroma pairs, in either of two forms with the same per-element arithmetic
+// (nv12_decode / nv12_byte / nv12_luma / nv12_chroma below):
+//   FAST   two 16-byte Y accesses, one 16-byte UV access, 16-byte accesses on the three fp32 planes; a wave's access to a row is
+//          consecutive addresses, every chroma pair is fetched / written once for its four pixels.  Conditions (nv12_fast_ok): both byte
+//          pointers, both pitches and both batch strides are multiples of 16, the fp32 pointer is 16-byte aligned and W % 4 == 0 (every
+//          fp32 row then starts on a 16-byte boundary) - and the block lies inside the frame (16 columns, 2 rows).
+//   SCALAR byte and dword accesses with the encode's edge clamp: every block when a FAST condition fails, otherwise the right (W % 16)
+//          and bottom (odd H) remainders only.
+// The byte side may be pinned host memory reached over PCIe, as for the u8 kernels.
+// ------------------------------------------------------------------------------------------
+struct YuvCoef { int dec[5], enc[9], limited, rgb; };   // tables of include/emavfi.h; limited: Y - 16 floor / + 16 offset; rgb: channel 0 is R
+
+void yuv_coefficients(int standard, int dec[5], int enc[9])
+{
+    const bool full = (standard & 1) != 0, bt709 = (standard >> 1) != 0;
+    const double kr = bt709 ? 0.2126 : 0.299, kb = bt709 ? 0.0722 : 0.114, kg = 1 - kr - kb;
+    const double cy = full ? 1.0 : 255.0 / 219, s = full ? 1.0 : 255.0 / 224, t = full ? 1.0 : 219.0 / 255, sp = full ? 1.0 : 224.0 / 255;
+    const double kd[5] = {cy, 2 * (1 - kr) * s, -2 * kb * (1 - kb) * s / kg, -2 * kr * (1 - kr) * s / kg, 2 * (1 - kb) * s};
+    const double ke[9] = {kr * t, kg * t, kb * t,
+                          -kr / (2 * (1 - kb)) * sp, -kg / (2 * (1 - kb)) * sp, 0.5 * sp,
+                          0.5 * sp, -kg / (2 * (1 - kr)) * sp, -kb / (2 * (1 - kr)) * sp};
+    for (int i = 0; i < 5; ++i) dec[i] = (int)floor(kd[i] * 1048576.0 + 0.5);
+    for (int i = 0; i < 9; ++i) enc[i] = (int)floor(ke[i] * 1048576.0 + 0.5);
+}
+static YuvCoef yuv_coef(int standard, int order)
+{
+    YuvCoef k{};
+    yuv_coefficients(standard, k.dec, k.enc);
+    k.limited = (standard & 1) == 0;
+    k.rgb = order == 1;
+    return k;
+}
+
+__device__ __forceinline__ int nv12_clip(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+// one pixel: (Y, U, V) -> the three bytes of the u8 layout, ch[0] = channel 0 of `order`
+__device__ __forceinline__ void nv12_decode(int Y, int U, int V, const YuvCoef &k, int ch[3])
+{
+    const int u = U - 128, v = V - 128, l = k.limited ? max(Y - 16, 0) : Y, yl = k.dec[0] * l + (1 << 19);
+    const int r = nv12_clip((yl + k.dec[1] * v) >> 20);
+    const int g = nv12_clip((yl + k.dec[2] * u + k.dec[3] * v) >> 20);
+    const int b = nv12_clip((yl + k.dec[4] * u) >> 20);
+    ch[0] = k.rgb ? r : b; ch[1] = g; ch[2] = k.rgb ? b : r;
+}
+__device__ __forceinline__ float nv12_norm(int byte, float mean, float stdv)
+{
+    const float v = (float)byte / 255.0f;   // preprocess_u8_kernel's two true divisions, same order
+    return (v - mean) / stdv;
+}
+// postprocess_u8_kernel's byte of one element
+__device__ __forceinline__ int nv12_byte(float x, double mean, double stdv, int denorm)
+{
+    double v = (double)x;
+    if (denorm) v = v * stdv + mean;
+    v = fmin(fmax(v, 0.0), 1.0) * 255.0;
+    return (int)(unsigned char)v;
+}
+__device__ __forceinline__ int nv12_luma(const int ch[3], const YuvCoef &k)
+{
+    const int r = k.rgb ? ch[0] : ch[2], g = ch[1], b = k.rgb ? ch[2] : ch[0];
+    return nv12_clip(((k.enc[0] * r + k.enc[1] * g + k.enc[2] * b + (1 << 19)) >> 20) + (k.limited ? 16 : 0));
+}
+// sum[c]: the 2x2 block's four bytes of channel c added up
+__device__ __forceinline__ void nv12_chroma(const int sum[3], const YuvCoef &k, int &U, int &V)
+{
+    const int m0 = (sum[0] + 2) >> 2, m1 = (sum[1] + 2) >> 2, m2 = (sum[2] + 2) >> 2;
+    const int r = k.rgb ? m0 : m2, g = m1, b = k.rgb ? m2 : m0;
+    U = nv12_clip(((k.enc[3] * r + k.enc[4] * g + k.enc[5] * b + (1 << 19)) >> 20) + 128);
+    V = nv12_clip(((k.enc[6] * r + k.enc[7] * g + k.enc[8] * b + (1 << 19)) >> 20) + 128);
+}
+
+struct Nv12Planes { size_t y_pitch, y_bstride, uv_pitch, uv_bstride; };
+
+__global__ __launch_bounds__(256) void preprocess_nv12_kernel(const unsigned char *__restrict__ ysrc, const unsigned char *__restrict__ uvsrc,
+                                                              float *__restrict__ dst, int B, int H, int W, Nv12Planes pl, Stats4 st,
+                                                              YuvCoef k, int fast)
+{
+    const size_t nbx = ((size_t)W + 15) / 16, nby = ((size_t)H + 1) / 2, plane = (size_t)H * W, total = (size_t)B * nby * nbx;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = i / (nby * nbx), rem = i - b * nby * nbx, by = rem / nbx;
+        const int y0 = (int)by * 2, x0 = (int)(rem - by * nbx) * 16;
+        const unsigned char *yp = ysrc + b * pl.y_bstride + (size_t)y0 * pl.y_pitch + x0;
+        const unsigned char *up = uvsrc + b * pl.uv_bstride + by * pl.uv_pitch + x0;   // pair x0 / 2 starts at byte x0
+        float *o = dst + b * 3 * plane + (size_t)y0 * W + x0;
+        if (fast && x0 + 16 <= W && y0 + 2 <= H) {
+            const uint4 uvq = *reinterpret_cast<const uint4 *>(up);
+            const unsigned uvw[4] = {uvq.x, uvq.y, uvq.z, uvq.w};
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const uint4 yq = *reinterpret_cast<const uint4 *>(yp + (size_t)r * pl.y_pitch);
+                const unsigned yw[4] = {yq.x, yq.y, yq.z, yq.w};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {   // 4 pixels = 2 chroma pairs = one dword of each plane
+                    f32x4 out[3];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const unsigned pair = uvw[q] >> (16 * (j >> 1));
+                        int ch[3];
+                        nv12_decode((int)((yw[q] >> (8 * j)) & 0xffu), (int)(pair & 0xffu), (int)((pair >> 8) & 0xffu), k, ch);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) out[c][j] = nv12_norm(ch[c], st.mean[c], st.stdv[c]);
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4 *>(o + c * plane + (size_t)r * W + q * 4) = out[c];
+                }
+            }
+            continue;
+        }
+        const int nx = min(16, W - x0), ny = min(2, H - y0);
+        for (int x = 0; x < nx; ++x) {
+            const int U = up[x & ~1], V = up[(x & ~1) + 1];
+            for (int r = 0; r < ny; ++r) {
+                int ch[3];
+                nv12_decode((int)yp[(size_t)r * pl.y_pitch + x], U, V, k, ch);
+                for (int c = 0; c < 3; ++c) o[c * plane + (size_t)r * W + x] = nv12_norm(ch[c], st.mean[c], st.stdv[c]);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void postprocess_nv12_kernel(const float *__restrict__ src, unsigned char *__restrict__ ydst,
+                                                               unsigned char *__restrict__ uvdst, int B, int H, int W, Nv12Planes pl,
+                                                               Stats4d st, YuvCoef k, int denorm, int fast)
+{
+    const size_t nbx = ((size_t)W + 15) / 16, nby = ((size_t)H + 1) / 2, plane = (size_t)H * W, total = (size_t)B * nby * nbx;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = i / (nby * nbx), rem = i - b * nby * nbx, by = rem / nbx;
+        const int y0 = (int)by * 2, x0 = (int)(rem - by * nbx) * 16;
+        unsigned char *yp = ydst + b * pl.y_bstride + (size_t)y0 * pl.y_pitch + x0;
+        unsigned char *up = uvdst + b * pl.uv_bstride + by * pl.uv_pitch + x0;
+        const float *s = src + b * 3 * plane;
+        if (fast && x0 + 16 <= W && y0 + 2 <= H) {
+            unsigned yw[2][4], uvw[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                int by8[2][4][3];   // [row][pixel][channel]
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const f32x4 x = *reinterpret_cast<const f32x4 *>(s + c * plane + (size_t)(y0 + r) * W + x0 + q * 4);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) by8[r][j][c] = nv12_byte(x[j], st.mean[c], st.stdv[c], denorm);
+                    }
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    unsigned w = 0u;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) w |= (unsigned)nv12_luma(by8[r][j], k) << (8 * j);
+                    yw[r][q] = w;
+                }
+                unsigned w = 0u;
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    int sum[3], U, V;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) sum[c] = by8[0][2 * p][c] + by8[0][2 * p + 1][c] + by8[1][2 * p][c] + by8[1][2 * p + 1][c];
+                    nv12_chroma(sum, k, U, V);
+                    w |= ((unsigned)U | ((unsigned)V << 8)) << (16 * p);
+                }
+                uvw[q] = w;
+            }
+            *reinterpret_cast<uint4 *>(yp) = make_uint4(yw[0][0], yw[0][1], yw[0][2], yw[0][3]);
+            *reinterpret_cast<uint4 *>(yp + pl.y_pitch) = make_uint4(yw[1][0], yw[1][1], yw[1][2], yw[1][3]);
+            *reinterpret_cast<uint4 *>(up) = make_uint4(uvw[0], uvw[1], uvw[2], uvw[3]);
+            continue;
+        }
+        const int nx = min(16, W - x0);
+        for (int x = 0; x < nx; x += 2) {
+            int sum[3] = {0, 0, 0}, U, V;
+            for (int r = 0; r < 2; ++r)
+                for (int dx = 0; dx < 2; ++dx) {
+                    const int yy = min(y0 + r, H - 1), xx = min(x0 + x + dx, W - 1);   // past the last row / column: clamped
+                    int ch[3];
+                    for (int c = 0; c < 3; ++c) {
+                        ch[c] = nv12_byte(s[c * plane + (size_t)yy * W + xx], st.mean[c], st.stdv[c], denorm);
+                        sum[c] += ch[c];
+                    }
+                    if (yy == y0 + r && xx == x0 + x + dx) yp[(size_t)r * pl.y_pitch + x + dx] = (unsigned char)nv12_luma(ch, k);
+                }
+            nv12_chroma(sum, k, U, V);
+            up[x] = (unsigned char)U;
+            up[x + 1] = (unsigned char)V;
+        }
+    }
+}
+
+static bool nv12_fast_ok(const void *y, const void *uv, const void *f32, int W, const Nv12Planes &pl)
+{
+    return (((uintptr_t)y | (uintptr_t)uv | (uintptr_t)f32 | pl.y_pitch | pl.y_bstride | pl.uv_pitch | pl.uv_bstride) & 15) == 0 && W % 4 == 0;
+}
+static int nv12_grid(int B, int H, int W)
+{
+    const size_t lanes = (size_t)B * (((size_t)H + 1) / 2) * (((size_t)W + 15) / 16);
+    return (int)std::min<size_t>((lanes + 255) / 256, (size_t)65535 * 4);
+}
+int launch_preprocess_nv12(const unsigned char *y, size_t y_pitch, size_t y_bstride, const unsigned char *uv, size_t uv_pitch, size_t uv_bstride,
+                           float *dst, int B, int H, int W, int standard, int order, const float *mean, const float *stdv, hipStream_t s)
+{
+    Stats4 st{};
+    for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
+    const Nv12Planes pl{y_pitch, y_bstride, uv_pitch, uv_bstride};
+    preprocess_nv12_kernel<<<nv12_grid(B, H, W), 256, 0, s>>>(y, uv, dst, B, H, W, pl, st, yuv_coef(standard, order),
+                                                              nv12_fast_ok(y, uv, dst, W, pl) ? 1 : 0);
+    return (int)hipGetLastError();
+}
+int launch_postprocess_nv12(const float *src, unsigned char *y, size_t y_pitch, size_t y_bstride, unsigned char *uv, size_t uv_pitch,
+                            size_t uv_bstride, int B, int H, int W, int standard, int order, const double *mean, const double *stdv, int denorm,
+                            hipStream_t s)
+{
+    Stats4d st{};
+    for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
+    const Nv12Planes pl{y_pitch, y_bstride, uv_pitch, uv_bstride};
+    postprocess_nv12_kernel<<<nv12_grid(B, H, W), 256, 0, s>>>(src, y, uv, B, H, W, pl, st, yuv_coef(standard, order), denorm,
+                                                               nv12_fast_ok(y, uv, src, W, pl) ? 1 : 0);
+    return (int)hipGetLastError();
+}
+
 // ---- census of the one-launch packs (deform_pack3.inl, DeformParams::census): one wave per block adds the 64 slots
 struct CensusTotals { unsigned long long t[8]; };
 __global__ void census_reduce_kernel(const unsigned *__restrict__ census, unsigned long long *__restrict__ out, CensusTotals totals)

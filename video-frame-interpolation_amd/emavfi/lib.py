@@ -42,6 +42,11 @@ _PROTOTYPES = {
     "emavfi_warp": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),
     "emavfi_preprocess_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
     "emavfi_postprocess_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int, c_void_p]),
+    "emavfi_yuv_coefficients": (c_int, [c_int, POINTER(c_int), POINTER(c_int)]),
+    "emavfi_preprocess_nv12": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p] + [c_int] * 5
+                               + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
+    "emavfi_postprocess_nv12": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 5
+                                + [POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int, c_void_p]),
     "emavfi_conv3x3_workspace_bytes": (c_size_t, [c_int] * 7),
     "emavfi_conv3x3": (c_int, [c_void_p] * 4 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p]),
     "emavfi_deform_conv2d_workspace_bytes": (c_size_t, [c_int] * 6),
@@ -533,3 +538,103 @@ def postprocess_u8(frames_nchw, denormalize=True, mean=IMAGENET_MEAN, std=IMAGEN
         check(load().emavfi_postprocess_u8(x.data_ptr(), out.data_ptr(), B, H, W, C, m, s, 1 if denormalize else 0, _stream()),
               "emavfi_postprocess_u8")
     return out
+
+
+# ---------------------------------------------------------------- NV12 frames (include/emavfi.h, "NV12")
+YUV_STANDARDS = {("bt601", False): 0, ("bt601", True): 1, ("bt709", False): 2, ("bt709", True): 3}   # EMAVFI_YUV_*
+ORDERS = {"bgr": 0, "rgb": 1}                                                                        # EMAVFI_ORDER_*
+
+
+def yuv_standard_code(standard="bt601", full_range=False) -> int:
+    try:
+        return YUV_STANDARDS[(str(standard).lower(), bool(full_range))]
+    except KeyError:
+        raise ValueError(f"yuv standard must be 'bt601' or 'bt709', got {standard!r}") from None
+
+
+def _order_code(order) -> int:
+    try:
+        return ORDERS[str(order).lower()]
+    except KeyError:
+        raise ValueError(f"order must be 'bgr' or 'rgb', got {order!r}") from None
+
+
+def yuv_coefficients(standard="bt601", full_range=False):
+    """The fixed-point tables of the colour definition (include/emavfi.h): (decode [CY, CVR, CUG, CVG, CUB],
+    encode [YR, YG, YB, UR, UG, UB, VR, VG, VB]), each floor(k * 2^20 + 0.5).  Host only."""
+    dec, enc = (c_int * 5)(), (c_int * 9)()
+    check(load().emavfi_yuv_coefficients(yuv_standard_code(standard, full_range), dec, enc), "emavfi_yuv_coefficients")
+    return list(dec), list(enc)
+
+
+def _nv12_planes(y, uv, what):
+    """Shapes, pitches and batch strides (bytes) of a Y [B,H,W] / UV [B,ceil(H/2),ceil(W/2),2] pair of uint8 tensors; rows and
+    batches may be strided, the innermost dimensions must be dense."""
+    import torch
+    for t in (y, uv):
+        _pinned_or_cuda(t, what)
+    if y.dtype != torch.uint8 or uv.dtype != torch.uint8 or y.dim() != 3 or uv.dim() != 4:
+        raise ValueError(f"{what}: uint8 y [B,H,W] and uv [B,ceil(H/2),ceil(W/2),2] expected")
+    B, H, W = y.shape
+    H2, W2 = (H + 1) // 2, (W + 1) // 2
+    if tuple(uv.shape) != (B, H2, W2, 2):
+        raise ValueError(f"{what}: uv must be [B,ceil(H/2),ceil(W/2),2] = {(B, H2, W2, 2)}, got {tuple(uv.shape)}")
+    if min(B, H, W) < 1:
+        raise ValueError(f"{what}: empty frames")
+    if y.is_cuda != uv.is_cuda or (y.is_cuda and y.device != uv.device):
+        raise ValueError(f"{what}: y and uv must live in the same memory")
+    if (W > 1 and y.stride(2) != 1) or uv.stride(3) != 1 or (W2 > 1 and uv.stride(2) != 2):
+        raise ValueError(f"{what}: the innermost dimensions of y and uv must be dense (only rows and batches may be strided)")
+    # a dimension of size 1 has no meaningful stride: the dense value stands in
+    y_pitch = y.stride(1) if H > 1 else W
+    uv_pitch = uv.stride(1) if H2 > 1 else 2 * W2
+    y_bs = y.stride(0) if B > 1 else y_pitch * H
+    uv_bs = uv.stride(0) if B > 1 else uv_pitch * H2
+    return B, H, W, y_pitch, y_bs, uv_pitch, uv_bs
+
+
+def preprocess_nv12(y, uv, standard="bt601", full_range=False, order="bgr", mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None, out=None):
+    """NV12 frames -> fp32 [B,3,H,W], defined as preprocess_u8 of the decoded bytes (include/emavfi.h, "NV12").
+    `y` uint8 [B,H,W], `uv` uint8 [B,ceil(H/2),ceil(W/2),2]: device tensors or pinned host tensors (read in place over PCIe; `device`
+    names the GPU), each may be strided in its row and batch dimensions - the pitches are taken from .stride().  `order`: which colour is
+    channel 0 ("bgr": what cv2 hands the reference).  `out`: a contiguous fp32 [B,3,H,W] device tensor to fill."""
+    import torch
+    B, H, W, yp, ybs, uvp, uvbs = _nv12_planes(y, uv, "preprocess_nv12")
+    st, od = yuv_standard_code(standard, full_range), _order_code(order)
+    dev = y.device if y.is_cuda else torch.device(device if device is not None else "cuda")
+    m, s = _stats(mean, std, 3)
+    if out is None:
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, H, W) and out.is_contiguous()):
+        raise ValueError("preprocess_nv12: out must be a contiguous fp32 [B,3,H,W] device tensor")
+    with torch.cuda.device(dev):
+        check(load().emavfi_preprocess_nv12(y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs, out.data_ptr(), B, H, W, st, od, m, s, _stream()),
+              "emavfi_preprocess_nv12")
+    return out
+
+
+def postprocess_nv12(frames_nchw, standard="bt601", full_range=False, order="bgr", denormalize=True, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                     out=None):
+    """fp32 [B,3,H,W] -> NV12 (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]), defined as the encode of the bytes postprocess_u8 would write
+    (include/emavfi.h, "NV12").  `out=(y, uv)`: device or pinned host tensors to fill, strided as for preprocess_nv12; bytes between
+    the rows of a pitched destination are left as they were."""
+    import torch
+    _require_cuda(frames_nchw)
+    x = _f32c(frames_nchw)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError("postprocess_nv12: [B,3,H,W] tensor expected")
+    B, _, H, W = x.shape
+    st, od = yuv_standard_code(standard, full_range), _order_code(order)
+    m, s = _stats(mean, std, 3, ctypes.c_double)
+    if out is None:
+        y = torch.empty(B, H, W, dtype=torch.uint8, device=x.device)
+        uv = torch.empty(B, (H + 1) // 2, (W + 1) // 2, 2, dtype=torch.uint8, device=x.device)
+    else:
+        y, uv = out
+    *shape, yp, ybs, uvp, uvbs = _nv12_planes(y, uv, "postprocess_nv12(out=)")
+    if tuple(shape) != (B, H, W):
+        raise ValueError(f"postprocess_nv12: out must be (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]) for frames {(B, H, W)}")
+    with torch.cuda.device(x.device):
+        check(load().emavfi_postprocess_nv12(x.data_ptr(), y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs, B, H, W, st, od, m, s,
+                                             1 if denormalize else 0, _stream()), "emavfi_postprocess_nv12")
+    return y, uv

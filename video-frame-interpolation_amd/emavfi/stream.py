@@ -35,6 +35,11 @@ SURVEY.md) and passes source frames through untouched; order and counts stay the
 ``numa="auto"`` (opt-in) places the host side of the harness on the CPUs of the device's NUMA node (``dist.numa_plan``): the
 staging pool's threads bind themselves to them, and the pinned buffers are allocated and first touched from one of those threads.
 Frames are the same either way.
+``pixel_format="nv12"`` (opt-in; the default ``"bgr24"`` is the reference's cv2 layout) takes and yields frames in the contiguous NV12
+layout video decoders produce - uint8 ``[H*3/2, W]``: H rows of Y, then H/2 rows of interleaved U,V pairs; even H and W - so the pinned
+slots and the SDMA copies move 1.5 bytes per pixel instead of 3.  Decode and encode run inside the device kernels
+(emavfi_preprocess_nv12 / _postprocess_nv12, colour definition: include/emavfi.h); ``yuv_standard`` / ``yuv_full_range`` pick one of the four
+standards.  Order, counts and scheduling are the same; a round-tripped source frame is decode -> normalise -> denormalise -> encode.
 """
 from __future__ import annotations
 
@@ -50,7 +55,7 @@ from . import lib as _lib
 class FrameInterpolator:
     def __init__(self, model, interpolation_factor: int = 1, frame_interval: int = 1, batch_pairs: int = 8,
                  reference_quirks: bool = True, mode: str = "reference", device=None, copy_out: bool = True, zero_copy: bool = False,
-                 numa: str = "off"):
+                 numa: str = "off", pixel_format: str = "bgr24", yuv_standard: str = "bt601", yuv_full_range: bool = False):
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
             raise ValueError("interpolation_factor >= 0, frame_interval >= 1, batch_pairs >= 1 required")
         if mode not in ("reference", "recursive"):
@@ -59,6 +64,11 @@ class FrameInterpolator:
             raise ValueError("recursive midpoints need interpolation_factor = 2^k - 1 (1, 3, 7, ...)")
         if numa not in ("off", "auto"):
             raise ValueError("numa must be 'off' or 'auto'")
+        if pixel_format not in ("bgr24", "nv12"):
+            raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames) or 'nv12' (uint8 [H*3/2, W] frames)")
+        _lib.yuv_standard_code(yuv_standard, yuv_full_range)   # raises on an unknown standard
+        self.pixel_format = pixel_format
+        self.yuv = {"standard": yuv_standard, "full_range": bool(yuv_full_range)}
         self.model = model
         self.factor = int(interpolation_factor)
         self.interval = int(frame_interval)
@@ -144,7 +154,11 @@ class FrameInterpolator:
     def _alloc(self, shape):
         if self._shape == shape:
             return
-        H, W, C = shape
+        if self.pixel_format == "nv12":
+            H, W, C = shape[0] * 2 // 3, shape[1], 3     # [H*3/2, W]: Y rows, then the UV rows
+        else:
+            H, W, C = shape
+        fs = tuple(shape)                                # a frame as it travels: [H, W, C] or [H*3/2, W]
         nb, nout = self.batch_pairs, max(self.factor if self.mode == "recursive" else 1, 1)
         self._shape = shape
         self._slots = []
@@ -152,18 +166,18 @@ class FrameInterpolator:
             if self._bound():
                 # pinned and first touched on a thread of the device's node (on the hosts measured the runtime already put pinned
                 # pages on the GPU's node whichever CPU asked: profiles/r09_numa_stream_ab.md)
-                pinned = self._copy_pool().submit(self._pinned_local, [(2 * nb, H, W, C), (nb * nout, H, W, C), (nb, H, W, C)]).result()
+                pinned = self._copy_pool().submit(self._pinned_local, [(2 * nb, *fs), (nb * nout, *fs), (nb, *fs)]).result()
             else:
-                pinned = [torch.empty(2 * nb, H, W, C, dtype=torch.uint8).pin_memory(),
-                          torch.empty(nb * nout, H, W, C, dtype=torch.uint8).pin_memory(),
-                          torch.empty(nb, H, W, C, dtype=torch.uint8).pin_memory()]
+                pinned = [torch.empty(2 * nb, *fs, dtype=torch.uint8).pin_memory(),
+                          torch.empty(nb * nout, *fs, dtype=torch.uint8).pin_memory(),
+                          torch.empty(nb, *fs, dtype=torch.uint8).pin_memory()]
             self._slots.append({
                 "h_in": pinned[0], "h_pred": pinned[1], "h_src": pinned[2],
                 "x": torch.empty(2 * nb, C, H, W, dtype=torch.float32, device=self.device),
                 # device-side images of the three pinned buffers (the SDMA copies' other end)
-                "d_in": torch.empty(2 * nb, H, W, C, dtype=torch.uint8, device=self.device),
-                "d_pred": torch.empty(nb * nout, H, W, C, dtype=torch.uint8, device=self.device),
-                "d_src": torch.empty(nb, H, W, C, dtype=torch.uint8, device=self.device),
+                "d_in": torch.empty(2 * nb, *fs, dtype=torch.uint8, device=self.device),
+                "d_pred": torch.empty(nb * nout, *fs, dtype=torch.uint8, device=self.device),
+                "d_src": torch.empty(nb, *fs, dtype=torch.uint8, device=self.device),
                 # consumed: the preprocess kernel has read h_in (the host may restage it); pre: x is ready; fwd: the forward has read x
                 # and written its predictions; done: the postprocess kernels have written h_pred / h_src (the host may drain them)
                 "consumed": torch.cuda.Event(), "pre": torch.cuda.Event(), "fwd": torch.cuda.Event(), "done": torch.cuda.Event(),
@@ -173,6 +187,27 @@ class FrameInterpolator:
         # those of the compute kernels (torch: lower number = higher priority)
         self._pre = _lib.side_stream(self.device, which=2, priority=-1)
         self._post = _lib.side_stream(self.device, which=3, priority=-1)
+
+    # ---- the two device kernels of a frame format: uint8 frames (a slot buffer's rows, device or pinned) <-> normalised fp32 NCHW
+    @staticmethod
+    def _planes(buf):
+        """Y [n,H,W] and UV [n,H/2,W/2,2] views of n contiguous NV12 frames [n, H*3/2, W]"""
+        H = buf.shape[1] * 2 // 3
+        return buf[:, :H], buf[:, H:].unflatten(2, (buf.shape[2] // 2, 2))
+
+    def _pre_kernel(self, buf, out=None, device=None):
+        if self.pixel_format == "nv12":
+            y, uv = self._planes(buf)
+            return _lib.preprocess_nv12(y, uv, self.yuv["standard"], self.yuv["full_range"], device=device, out=out)
+        return _lib.preprocess_u8(buf, device=device, out=out)
+
+    def _post_kernel(self, x, denormalize, out=None):
+        if self.pixel_format == "nv12":
+            if out is None:
+                out = torch.empty(x.shape[0], x.shape[2] * 3 // 2, x.shape[3], dtype=torch.uint8, device=x.device)
+            _lib.postprocess_nv12(x, self.yuv["standard"], self.yuv["full_range"], denormalize=denormalize, out=self._planes(out))
+            return out
+        return _lib.postprocess_u8(x, denormalize=denormalize, out=out)
 
     _pool = None
     _bound_pools = {}   # (node, cpus) -> a pool whose threads run on those CPUs only; the unbound pool above stays as it is
@@ -262,7 +297,7 @@ class FrameInterpolator:
             return torch.stack(rec(x1, x2, levels), dim=1)
 
     def run(self, frames, rank: int = 0, world: int = 1) -> Iterator[np.ndarray]:
-        """Yields uint8 HWC frames in the order the reference's writer receives them.
+        """Yields uint8 HWC frames (``pixel_format="nv12"``: uint8 [H*3/2, W] frames) in the order the reference's writer receives them.
 
         ``frames``: the whole stream - an iterable, or (sharded use) any object with ``len()`` and integer indexing, of which
         only this rank's segment ``[lo, hi)`` (``segment()``) is touched, e.g. a lazy video reader.  ``rank`` / ``world``:
@@ -277,9 +312,16 @@ class FrameInterpolator:
         pairs = mine
         frames = {i: np.ascontiguousarray(frames[i]) for i in range(lo, hi)}   # this rank's segment only
         first = frames[lo]
-        for f in frames.values():
-            if f.dtype != np.uint8 or f.ndim != 3 or f.shape != first.shape:
-                raise ValueError("FrameInterpolator.run: same-shape uint8 HWC frames expected")
+        if self.pixel_format == "nv12":
+            for f in frames.values():
+                if f.dtype != np.uint8 or f.ndim != 2 or f.shape != first.shape:
+                    raise ValueError("FrameInterpolator.run: same-shape uint8 [H*3/2, W] NV12 frames expected")
+            if first.shape[0] % 3 or first.shape[1] % 2:   # H = 2 * rows / 3 is then even
+                raise ValueError("FrameInterpolator.run: the packed NV12 layout [H*3/2, W] needs even H and W")
+        else:
+            for f in frames.values():
+                if f.dtype != np.uint8 or f.ndim != 3 or f.shape != first.shape:
+                    raise ValueError("FrameInterpolator.run: same-shape uint8 HWC frames expected")
         self._alloc(first.shape)
         main = torch.cuda.current_stream(self.device)
         # ramp-up: with three or more batches to come the FIRST one is half-size - the GPU starts after five staged frames instead of
@@ -314,18 +356,18 @@ class FrameInterpolator:
                 self._pre.wait_event(slot["fwd"])
                 self._pre.wait_event(slot["done"])
                 if self.zero_copy:
-                    x = _lib.preprocess_u8(slot["h_in"][:nup], device=self.device, out=slot["x"][:nup])   # distinct frames, read over PCIe, normalised once
+                    x = self._pre_kernel(slot["h_in"][:nup], device=self.device, out=slot["x"][:nup])   # distinct frames, read over PCIe, normalised once
                     slot["consumed"].record(self._pre)
                 else:
                     slot["d_in"][:nup].copy_(slot["h_in"][:nup], non_blocking=True)                       # hipMemcpyAsync pinned -> HBM (SDMA)
                     slot["consumed"].record(self._pre)
-                    x = _lib.preprocess_u8(slot["d_in"][:nup], out=slot["x"][:nup])                       # distinct frames, normalised once
+                    x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup])                         # distinct frames, normalised once
                 slot["pre"].record(self._pre)
                 src_here = self.quirks and not self.zero_copy and all(ia[k + 1] == ia[k] + 1 for k in range(n - 1))
                 if src_here:
                     # the reference's round trip of every pair's earlier frame (inference.py:187-188) depends on the preprocess only:
                     # it leaves from this lane, ahead of the forward, instead of queueing behind the predictions at the end of the batch
-                    _lib.postprocess_u8(x[ia[0]:ia[0] + n], denormalize=True, out=slot["d_src"][:n])
+                    self._post_kernel(x[ia[0]:ia[0] + n], True, out=slot["d_src"][:n])
                     slot["h_src"][:n].copy_(slot["d_src"][:n], non_blocking=True)
                     slot["src"].record(self._pre)
             main.wait_event(slot["pre"])
@@ -339,14 +381,14 @@ class FrameInterpolator:
                 if self.quirks and (x1.data_ptr() < slot["x"].data_ptr() or x1.data_ptr() >= slot["x"].data_ptr() + slot["x"].numel() * 4):
                     x1.record_stream(self._post)                              # a gathered copy (non-consecutive rows), not a view of the slot
                 if self.zero_copy:
-                    _lib.postprocess_u8(flat, denormalize=self.quirks, out=slot["h_pred"][:n * npred])
+                    self._post_kernel(flat, self.quirks, out=slot["h_pred"][:n * npred])
                     if self.quirks:
-                        _lib.postprocess_u8(x1, denormalize=True, out=slot["h_src"][:n])
+                        self._post_kernel(x1, True, out=slot["h_src"][:n])
                 else:
-                    _lib.postprocess_u8(flat, denormalize=self.quirks, out=slot["d_pred"][:n * npred])
+                    self._post_kernel(flat, self.quirks, out=slot["d_pred"][:n * npred])
                     slot["h_pred"][:n * npred].copy_(slot["d_pred"][:n * npred], non_blocking=True)       # HBM -> pinned (SDMA)
                     if self.quirks and not src_here:
-                        _lib.postprocess_u8(x1, denormalize=True, out=slot["d_src"][:n])
+                        self._post_kernel(x1, True, out=slot["d_src"][:n])
                         slot["h_src"][:n].copy_(slot["d_src"][:n], non_blocking=True)
                     if src_here:
                         self._post.wait_event(slot["src"])                    # `done` covers both lanes' writes into the pinned buffers
@@ -362,6 +404,6 @@ class FrameInterpolator:
             return
         if last_roundtrip and self.quirks:   # skip-branch ending: the reference writes the round-tripped frame
             src = torch.from_numpy(frames[last]).unsqueeze(0).to(self.device)
-            yield _lib.postprocess_u8(_lib.preprocess_u8(src), denormalize=True).cpu().numpy()[0]
+            yield self._post_kernel(self._pre_kernel(src), True).cpu().numpy()[0]
         else:
             yield frames[last]
