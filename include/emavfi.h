@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -316,6 +316,52 @@ int emavfi_preprocess_nv12(const unsigned char *y, size_t y_pitch, size_t y_batc
 int emavfi_postprocess_nv12(const float *frames_nchw, unsigned char *y, size_t y_pitch, size_t y_batch_stride, unsigned char *uv,
                             size_t uv_pitch, size_t uv_batch_stride, int B, int H, int W, int standard, int order,
                             const double *mean, const double *std, int denormalize, void *stream);
+
+/* Frames resized on the device: the reference's `--scale` step, cv2.resize(frame, (int(w * scale), int(h * scale))), inference.py:46 / :93-94,
+ * which it applies to every decoded frame before ToTensor / Normalize.
+ *
+ * RESIZE DEFINITION (the one place).  THIS IS THE PROJECT'S OWN DEFINITION: IT MAKES NO CLAIM OF BYTE PARITY WITH ANY OUTSIDE LIBRARY (OpenCV,
+ * swscale, ...).  The geometry is that of cv2.resize's default INTER_LINEAR and of F.interpolate(mode="bilinear", align_corners=False):
+ * half-pixel centres, clamped at the edges; the weights are quantised to 11 bits and all arithmetic is signed 32-bit integer, so host, oracle
+ * and device agree bit for bit.  Per axis, for destination length nd, source length ns and destination index d (`/` is floor division):
+ *     num = clamp((2d + 1) ns - nd, 0, 2 nd (ns - 1))
+ *     i0  = num / (2 nd)
+ *     fr  = num - i0 2 nd
+ *     w   = (fr 2048 + nd) / (2 nd)          (0 .. 2048)
+ *     i1  = min(i0 + 1, ns - 1)
+ * Per byte, with wx / wy the column / row weights and (x0, x1) / (y0, y1) the column / row indices:
+ *     v = ( (2048 - wy) ((2048 - wx) p[y0][x0] + wx p[y0][x1])
+ *         +         wy  ((2048 - wx) p[y1][x0] + wx p[y1][x1]) + 2^21 ) >> 22
+ * Each channel of an interleaved image is resized independently.  Every dimension is at most 16384 (EMAVFI_RESIZE_MAX_DIM): the largest
+ * intermediates, (2d + 1) ns and 2048 * 2048 * 255 + 2^21, then stay below 2^31.  Up-scaling and down-scaling both use this formula; there is
+ * no antialias filter (INTER_LINEAR has none either).  Consequences the tests pin: equal sizes return the input bytes; an exact 2:1 reduction
+ * is (a + b + c + d + 2) >> 2 of each 2x2 block; a constant image stays constant; |byte - real-valued bilinear| <= 0.5 + 255 * 2 * (0.5 / 2048)
+ * = 0.6245.
+ *
+ * emavfi_resize_u8: the primitive.  src [B][Hs][Ws][C] -> dst [B][Hd][Wd][C], interleaved bytes, C in 1..4 (1: a Y plane, 2: a UV plane, 3: a
+ *   BGR frame); each side has its own row pitch and batch stride in bytes.  Bytes between the rows of a pitched destination are left as they were.
+ * emavfi_preprocess_u8_resized: dense frames_hwc [B,Hs,Ws,C] -> out_nchw fp32 [B,C,Hd,Wd]; DEFINED as emavfi_preprocess_u8 applied to
+ *   emavfi_resize_u8's bytes, bit for bit.  ONE launch that reads the source once and never writes the resized bytes to memory - unless
+ *   `resized_hwc` (dense [B,Hd,Wd,C]; NULL skips it) asks for them: the frame the reference writes "as read" (inference.py:167) is the resized one.
+ * emavfi_preprocess_nv12_resized: pitched Y / UV planes at Hs x Ws -> out_nchw fp32 [B,3,Hd,Wd]; DEFINED as emavfi_preprocess_nv12 applied to
+ *   the Y plane resized as a 1-channel image to Hd x Wd and the UV plane resized as a 2-channel image from ceil(Hs/2) x ceil(Ws/2) to
+ *   ceil(Hd/2) x ceil(Wd/2), bit for bit.  ONE launch; optional pitched `y_out` / `uv_out` receive the resized planes (NULL skips either).
+ * EMAVFI_E_ARG (never an abort): a pitch smaller than its row, for B > 1 a batch stride smaller than its plane, a dimension below 1 or above
+ *   16384, C outside 1..4, a null required pointer, a zero std; for NV12 an unknown standard or order and planes that are not 2-byte aligned.
+ * The byte pointers are device pointers or pinned (device-mapped) host memory, as for the u8 entries; `mean` / `std`: host pointers, fp32.
+ * Nothing is allocated, nothing synchronises, all work goes on `stream`.  Access width: a workgroup stages the source span of its tile of the
+ *   destination in LDS - with 16-byte loads when the source pointer, pitch and batch stride are multiples of 16 - and stores fp32 with 16-byte
+ *   accesses when Wd % 4 == 0 and the fp32 pointer is 16-byte aligned; everything else takes byte / dword accesses with the same per-element
+ *   arithmetic. */
+#define EMAVFI_RESIZE_MAX_DIM 16384
+int emavfi_resize_u8(const unsigned char *src, size_t src_pitch, size_t src_batch_stride, unsigned char *dst, size_t dst_pitch,
+                     size_t dst_batch_stride, int B, int Hs, int Ws, int Hd, int Wd, int C, void *stream);
+int emavfi_preprocess_u8_resized(const unsigned char *frames_hwc, float *out_nchw, unsigned char *resized_hwc, int B, int Hs, int Ws, int Hd,
+                                 int Wd, int C, const float *mean, const float *std, void *stream);
+int emavfi_preprocess_nv12_resized(const unsigned char *y, size_t y_pitch, size_t y_batch_stride, const unsigned char *uv, size_t uv_pitch,
+                                   size_t uv_batch_stride, float *out_nchw, unsigned char *y_out, size_t y_out_pitch, size_t y_out_batch_stride,
+                                   unsigned char *uv_out, size_t uv_out_pitch, size_t uv_out_batch_stride, int B, int Hs, int Ws, int Hd, int Wd,
+                                   int standard, int order, const float *mean, const float *std, void *stream);
 
 /* One conv / conv_block (ema_vfi.py:7-14): Conv2d(k=3, p=1, stride 1 or 2) + activation.
  * x [B,Cin,H,W], weight [Cout,Cin,3,3], bias [Cout], y [B,Cout,ceil(H/stride),ceil(W/stride)]. */

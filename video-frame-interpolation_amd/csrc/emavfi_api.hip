@@ -1383,6 +1383,75 @@ int emavfi_postprocess_nv12(const float *frames_nchw, unsigned char *y, size_t y
     return EMAVFI_OK;
 }
 
+// ---- frames resized on the device (include/emavfi.h, "RESIZE DEFINITION"): checks in an order that lets a caller without a device reach each
+static int resize_dims_check(const char *what, int B, int Hs, int Ws, int Hd, int Wd)
+{
+    if (B < 1 || Hs < 1 || Ws < 1 || Hd < 1 || Wd < 1) return fail(EMAVFI_E_ARG, "%s: B, Hs, Ws, Hd, Wd must be >= 1", what);
+    if (Hs > EMAVFI_RESIZE_MAX_DIM || Ws > EMAVFI_RESIZE_MAX_DIM || Hd > EMAVFI_RESIZE_MAX_DIM || Wd > EMAVFI_RESIZE_MAX_DIM)
+        return fail(EMAVFI_E_ARG, "%s: a dimension (%d x %d -> %d x %d) is above 16384", what, Hs, Ws, Hd, Wd);
+    if (B > 65535) return fail(EMAVFI_E_ARG, "%s: B = %d is above 65535", what, B);
+    return EMAVFI_OK;
+}
+// one pitched byte plane of `rows` rows of `row` bytes
+static int resize_plane_check(const char *what, const char *name, size_t pitch, size_t bstride, size_t rows, size_t row, int B)
+{
+    if (pitch < row) return fail(EMAVFI_E_ARG, "%s: %s_pitch %zu is smaller than its row of %zu bytes", what, name, pitch, row);
+    if (B > 1 && bstride < (rows - 1) * pitch + row) return fail(EMAVFI_E_ARG, "%s: the %s batch stride %zu is smaller than its plane", what, name, bstride);
+    return EMAVFI_OK;
+}
+
+int emavfi_resize_u8(const unsigned char *src, size_t src_pitch, size_t src_batch_stride, unsigned char *dst, size_t dst_pitch,
+                     size_t dst_batch_stride, int B, int Hs, int Ws, int Hd, int Wd, int C, void *stream)
+{
+    if (const int rc = resize_dims_check("resize_u8", B, Hs, Ws, Hd, Wd); rc != EMAVFI_OK) return rc;
+    if (C < 1 || C > 4) return fail(EMAVFI_E_ARG, "resize_u8: C = %d (C must be 1..4)", C);
+    if (const int rc = resize_plane_check("resize_u8", "src", src_pitch, src_batch_stride, (size_t)Hs, (size_t)Ws * C, B); rc != EMAVFI_OK) return rc;
+    if (const int rc = resize_plane_check("resize_u8", "dst", dst_pitch, dst_batch_stride, (size_t)Hd, (size_t)Wd * C, B); rc != EMAVFI_OK) return rc;
+    if (!src || !dst) return fail(EMAVFI_E_ARG, "resize_u8: null pointer");
+    EMAVFI_TRY(launch_resize_u8(src, src_pitch, src_batch_stride, dst, dst_pitch, dst_batch_stride, nullptr, B, Hs, Ws, Hd, Wd, C, nullptr, nullptr,
+                                (hipStream_t)stream), "resize_u8");
+    return EMAVFI_OK;
+}
+
+int emavfi_preprocess_u8_resized(const unsigned char *frames_hwc, float *out_nchw, unsigned char *resized_hwc, int B, int Hs, int Ws, int Hd,
+                                 int Wd, int C, const float *mean, const float *std, void *stream)
+{
+    if (!mean || !std) return fail(EMAVFI_E_ARG, "preprocess_u8_resized: null mean / std");
+    if (const int rc = resize_dims_check("preprocess_u8_resized", B, Hs, Ws, Hd, Wd); rc != EMAVFI_OK) return rc;
+    if (C < 1 || C > 4) return fail(EMAVFI_E_ARG, "preprocess_u8_resized: C = %d (C must be 1..4)", C);
+    for (int c = 0; c < C; ++c)
+        if (!(std[c] != 0.0f)) return fail(EMAVFI_E_ARG, "preprocess_u8_resized: std[%d] must be non-zero", c);
+    if (!frames_hwc || !out_nchw) return fail(EMAVFI_E_ARG, "preprocess_u8_resized: null pointer");
+    if ((uintptr_t)out_nchw & 3) return fail(EMAVFI_E_ARG, "preprocess_u8_resized: the fp32 pointer must be 4-byte aligned");
+    const size_t srow = (size_t)Ws * C, drow = (size_t)Wd * C;
+    EMAVFI_TRY(launch_resize_u8(frames_hwc, srow, srow * Hs, resized_hwc, drow, drow * Hd, out_nchw, B, Hs, Ws, Hd, Wd, C, mean, std,
+                                (hipStream_t)stream), "preprocess_u8_resized");
+    return EMAVFI_OK;
+}
+
+int emavfi_preprocess_nv12_resized(const unsigned char *y, size_t y_pitch, size_t y_batch_stride, const unsigned char *uv, size_t uv_pitch,
+                                   size_t uv_batch_stride, float *out_nchw, unsigned char *y_out, size_t y_out_pitch, size_t y_out_batch_stride,
+                                   unsigned char *uv_out, size_t uv_out_pitch, size_t uv_out_batch_stride, int B, int Hs, int Ws, int Hd, int Wd,
+                                   int standard, int order, const float *mean, const float *std, void *stream)
+{
+    const char *const what = "preprocess_nv12_resized";
+    if (!mean || !std) return fail(EMAVFI_E_ARG, "%s: null mean / std", what);
+    if (const int rc = resize_dims_check(what, B, Hs, Ws, Hd, Wd); rc != EMAVFI_OK) return rc;
+    // the source planes: emavfi_preprocess_nv12's checks (standard, order, pitches, batch strides, std, null, alignment), under this entry's name
+    if (const int rc = nv12_check(what, y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, out_nchw, B, Hs, Ws, standard, order, mean, std,
+                                  nullptr, nullptr); rc != EMAVFI_OK) return rc;
+    const size_t uv_row = 2 * (((size_t)Wd + 1) / 2), uv_rows = ((size_t)Hd + 1) / 2;
+    if (y_out)
+        if (const int rc = resize_plane_check(what, "y_out", y_out_pitch, y_out_batch_stride, (size_t)Hd, (size_t)Wd, B); rc != EMAVFI_OK) return rc;
+    if (uv_out)
+        if (const int rc = resize_plane_check(what, "uv_out", uv_out_pitch, uv_out_batch_stride, uv_rows, uv_row, B); rc != EMAVFI_OK) return rc;
+    if (((uintptr_t)y_out | (uintptr_t)uv_out) & 1) return fail(EMAVFI_E_ARG, "%s: the y_out and uv_out pointers must be 2-byte aligned", what);
+    EMAVFI_TRY(launch_preprocess_nv12_resized(y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, out_nchw, y_out, y_out_pitch,
+                                              y_out_batch_stride, uv_out, uv_out_pitch, uv_out_batch_stride, B, Hs, Ws, Hd, Wd, standard, order, mean,
+                                              std, (hipStream_t)stream), "preprocess_nv12_resized");
+    return EMAVFI_OK;
+}
+
 // ---- stage-level entries (diagnostics / parity tests of single operators): one layer, packed into the workspace and run inside one call ----
 // Their plan - the kernel storage type (EMAVFI_F32X3: the f16 kernels on [hi | lo] halves) and, from op_carve, the zero page - and
 // their layer, as the plan of a model lays it out: a bf16 DCN on the LDS-window kernel contracts bf16-rounded weights stored as f16

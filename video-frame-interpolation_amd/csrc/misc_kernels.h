@@ -84,6 +84,14 @@ int launch_preprocess_nv12(const unsigned char *y, size_t y_pitch, size_t y_bstr
 int launch_postprocess_nv12(const float *src, unsigned char *y, size_t y_pitch, size_t y_bstride, unsigned char *uv, size_t uv_pitch,
                             size_t uv_bstride, int B, int H, int W, int standard, int order, const double *mean, const double *stdv, int denorm,
                             hipStream_t s);
+// frames resized on the device (include/emavfi.h, "RESIZE DEFINITION"): pitches and batch strides in bytes, arguments already validated.
+// launch_resize_u8: dst_u8 and / or dst_f32 (dense [B,C,Hd,Wd], normalised with mean / stdv) may be null - one launch writes what is asked for
+int launch_resize_u8(const unsigned char *src, size_t src_pitch, size_t src_bstride, unsigned char *dst_u8, size_t dst_pitch, size_t dst_bstride,
+                     float *dst_f32, int B, int Hs, int Ws, int Hd, int Wd, int C, const float *mean, const float *stdv, hipStream_t s);
+int launch_preprocess_nv12_resized(const unsigned char *y, size_t y_pitch, size_t y_bstride, const unsigned char *uv, size_t uv_pitch,
+                                   size_t uv_bstride, float *dst, unsigned char *y_out, size_t yo_pitch, size_t yo_bstride, unsigned char *uv_out,
+                                   size_t uvo_pitch, size_t uvo_bstride, int B, int Hs, int Ws, int Hd, int Wd, int standard, int order,
+                                   const float *mean, const float *stdv, hipStream_t s);
 // deform_pack3.inl's census: sums the 64 atomic slots of each of `nblocks` launches ([block][64][4] u32) into out[block][4] u64 =
 // {fix-up wave-taps, totals[block], samples outside the window, max |offset| as fp32 bits}
 int launch_census_reduce(const unsigned *census, unsigned long long *out, int nblocks, const unsigned long long *totals, hipStream_t s);

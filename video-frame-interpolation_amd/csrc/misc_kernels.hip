@@ -1495,6 +1495,286 @@ int launch_postprocess_nv12(const float *src, unsigned char *y, size_t y_pitch, 
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// Frames resized on the device (include/emavfi.h, "RESIZE DEFINITION"): the reference's cv2.resize(frame, (int(w * scale), int(h * scale)))
+// (inference.py:46), bilinear with half-pixel centres, 11-bit weights, signed 32-bit integer arithmetic.
+//   resize_u8_kernel<C>             interleaved bytes [B][Hs][Ws][C] -> bytes [B][Hd][Wd][C] and / or normalised fp32 [B][C][Hd][Wd]
+//                                   (= preprocess_u8 of the resized bytes) in one launch;
+//   preprocess_nv12_resized_kernel  Y resized as a 1-channel image, UV as a 2-channel image, then nv12_decode / nv12_norm per pixel
+//                                   (= preprocess_nv12 of the resized planes) in one launch.
+// A workgroup owns a tile of the DESTINATION.  It computes the tile's column table (x0, wx) and row table (y0, wy) once into LDS - the
+// integer divisions run per tile edge, not per pixel -, stages the source span the tile needs in LDS (every source byte is fetched once per
+// tile; neighbouring tiles share at most one row / column) and blends from there.  A lane owns 4 consecutive destination columns (x 2 rows
+// for NV12: two chroma pairs), so that an fp32 plane row is written 16 bytes per lane.  Two access forms, the same per-element arithmetic
+// (resize_axis / resize_blend / nv12_decode / nv12_norm):
+//   WIDE    16-byte source loads into LDS (source pointer, pitch and batch stride multiples of 16; only chunks that end inside the row -
+//           the rest of a row moves byte by byte, pitch padding is never read), 16-byte fp32 stores (Wd % 4 == 0, 16-byte aligned
+//           pointer), dword stores of the optional byte outputs (their pointers, pitches and batch strides multiples of 4);
+//   SCALAR  byte loads / dword fp32 stores / byte stores: whenever a condition above fails, and for the right remainder of a row.
+// A tile whose span does not fit RS_SPAN_BYTES (reductions beyond about 3:1) reads its four taps from global memory instead.
+// ------------------------------------------------------------------------------------------
+constexpr int RS_SPAN_BYTES = 40 * 1024;
+
+// one axis: destination index d of nd <- source indices i0, min(i0 + 1, ns - 1) with weight w / 2048 on the second
+__device__ __forceinline__ void resize_axis(int d, int nd, int ns, int &i0, int &w)
+{
+    const int hi = 2 * nd * (ns - 1);
+    int num = (2 * d + 1) * ns - nd;
+    num = num < 0 ? 0 : num > hi ? hi : num;
+    i0 = num / (2 * nd);
+    const int fr = num - i0 * 2 * nd;
+    w = (fr * 2048 + nd) / (2 * nd);
+}
+__device__ __forceinline__ int resize_blend(int p00, int p01, int p10, int p11, int wx, int wy)
+{
+    const int top = (2048 - wx) * p00 + wx * p01, bot = (2048 - wx) * p10 + wx * p11;
+    return ((2048 - wy) * top + wy * bot + (1 << 21)) >> 22;
+}
+// C interleaved channels of one destination pixel; row0 / row1 point at byte `sub` of the two source rows (LDS or global)
+template <int C>
+__device__ __forceinline__ void resize_pixel(const unsigned char *row0, const unsigned char *row1, int sub, int x0, int ns, int wx, int wy, int out[C])
+{
+    const int b0 = x0 * C - sub, b1 = min(x0 + 1, ns - 1) * C - sub;
+#pragma unroll
+    for (int c = 0; c < C; ++c) out[c] = resize_blend(row0[b0 + c], row0[b1 + c], row1[b0 + c], row1[b1 + c], wx, wy);
+}
+// Copies bytes [a0, hi) of rows r0 .. r0 + nrows - 1 of a pitched plane into LDS (row stride ls = (hi - a0) rounded up to 16).  hi <= rowbytes.
+// wide: a0, the plane's address and its pitch are multiples of 16, and a chunk that ends inside the row moves as one 16-byte access.
+__device__ __forceinline__ void resize_stage(unsigned char *lds, int ls, const unsigned char *plane, size_t pitch, int rowbytes, int r0, int nrows,
+                                             int a0, int hi, int wide)
+{
+    const int chunks = ls >> 4;
+    for (int i = threadIdx.x; i < nrows * chunks; i += blockDim.x) {
+        const int r = i / chunks, q = i - r * chunks, b0 = a0 + 16 * q;
+        const unsigned char *p = plane + (size_t)(r0 + r) * pitch + b0;
+        unsigned char *o = lds + r * ls + 16 * q;
+        if (wide && b0 + 16 <= rowbytes) {
+            *reinterpret_cast<uint4 *>(o) = *reinterpret_cast<const uint4 *>(p);
+        } else {
+            const int n = min(16, hi - b0);
+            for (int j = 0; j < n; ++j) o[j] = p[j];
+        }
+    }
+}
+// the span of one axis of a tile: source indices [lo, hi] the n destination entries of the table need
+__device__ __forceinline__ void resize_span(const int *i0, int n, int ns, int &lo, int &hi)
+{
+    lo = i0[0];
+    hi = min(i0[n - 1] + 1, ns - 1);
+}
+
+struct ResizeArgs {
+    const unsigned char *src; size_t src_pitch, src_bstride;
+    unsigned char *dst; size_t dst_pitch, dst_bstride;   // dst may be null
+    float *f32;                                          // may be null
+    int Hs, Ws, Hd, Wd, wide_src, wide_f32, wide_u8;
+};
+
+template <int C>
+__global__ __launch_bounds__(256) void resize_u8_kernel(ResizeArgs a, Stats4 st)
+{
+    constexpr int TW = 64, TH = 16;   // 16 x 16 lanes of 1 row x 4 columns
+    __shared__ __attribute__((aligned(16))) unsigned char span[RS_SPAN_BYTES];
+    __shared__ int cx0[TW], cwx[TW], ry0[TH], rwy[TH];
+    const int tid = threadIdx.x, X0 = blockIdx.x * TW, Y0 = blockIdx.y * TH;
+    const size_t b = blockIdx.z;
+    if (tid < TW) resize_axis(min(X0 + tid, a.Wd - 1), a.Wd, a.Ws, cx0[tid], cwx[tid]);
+    else if (tid < TW + TH) resize_axis(min(Y0 + tid - TW, a.Hd - 1), a.Hd, a.Hs, ry0[tid - TW], rwy[tid - TW]);
+    __syncthreads();
+    const int nx = min(TW, a.Wd - X0), ny = min(TH, a.Hd - Y0);
+    int ys_lo, ys_hi, xs_lo, xs_hi;
+    resize_span(ry0, ny, a.Hs, ys_lo, ys_hi);
+    resize_span(cx0, nx, a.Ws, xs_lo, xs_hi);
+    const int lo = xs_lo * C, hi = (xs_hi + 1) * C, a0 = a.wide_src ? (lo & ~15) : lo, ls = (hi - a0 + 15) & ~15, nrows = ys_hi - ys_lo + 1;
+    const unsigned char *plane = a.src + b * a.src_bstride;
+    const bool staged = (long long)nrows * ls <= RS_SPAN_BYTES;   // uniform over the workgroup
+    if (staged) {
+        resize_stage(span, ls, plane, a.src_pitch, a.Ws * C, ys_lo, nrows, a0, hi, a.wide_src);
+        __syncthreads();
+    }
+    const int r = tid >> 4, c4 = (tid & 15) * 4;
+    if (r >= ny || c4 >= nx) return;
+    const int n = min(4, nx - c4), y = Y0 + r, y0 = ry0[r], y1 = min(y0 + 1, a.Hs - 1), wy = rwy[r];
+    int v[4][C];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j < n) {
+            if (staged) resize_pixel<C>(span + (y0 - ys_lo) * ls, span + (y1 - ys_lo) * ls, a0, cx0[c4 + j], a.Ws, cwx[c4 + j], wy, v[j]);
+            else resize_pixel<C>(plane + (size_t)y0 * a.src_pitch, plane + (size_t)y1 * a.src_pitch, 0, cx0[c4 + j], a.Ws, cwx[c4 + j], wy, v[j]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < C; ++c) v[j][c] = 0;
+        }
+    }
+    if (a.dst) {
+        unsigned char *o = a.dst + b * a.dst_bstride + (size_t)y * a.dst_pitch + (size_t)(X0 + c4) * C;
+        if (a.wide_u8 && n == 4) {
+            unsigned w[C];
+#pragma unroll
+            for (int q = 0; q < C; ++q) w[q] = 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int c = 0; c < C; ++c) w[(j * C + c) >> 2] |= (unsigned)v[j][c] << (8 * ((j * C + c) & 3));
+#pragma unroll
+            for (int q = 0; q < C; ++q) reinterpret_cast<unsigned *>(o)[q] = w[q];
+        } else {
+            for (int j = 0; j < n; ++j)
+                for (int c = 0; c < C; ++c) o[j * C + c] = (unsigned char)v[j][c];
+        }
+    }
+    if (a.f32) {
+        const size_t dplane = (size_t)a.Hd * a.Wd;
+        float *o = a.f32 + b * C * dplane + (size_t)y * a.Wd + X0 + c4;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            if (a.wide_f32 && n == 4) {
+                *reinterpret_cast<f32x4 *>(o + c * dplane) = f32x4{nv12_norm(v[0][c], st.mean[c], st.stdv[c]), nv12_norm(v[1][c], st.mean[c], st.stdv[c]),
+                                                                   nv12_norm(v[2][c], st.mean[c], st.stdv[c]), nv12_norm(v[3][c], st.mean[c], st.stdv[c])};
+            } else {
+                for (int j = 0; j < n; ++j) o[c * dplane + j] = nv12_norm(v[j][c], st.mean[c], st.stdv[c]);
+            }
+        }
+    }
+}
+
+struct ResizeNv12Args {
+    const unsigned char *y, *uv; Nv12Planes in;
+    float *f32;
+    unsigned char *yo, *uvo; Nv12Planes out;             // yo / uvo may be null
+    int Hs, Ws, Hd, Wd, wide_src, wide_f32, wide_out;
+};
+
+__global__ __launch_bounds__(256) void preprocess_nv12_resized_kernel(ResizeNv12Args a, Stats4 st, YuvCoef k)
+{
+    constexpr int TW = 64, TH = 32;   // luma tile: 16 x 16 lanes of 2 rows x 4 columns = 2 chroma pairs each
+    __shared__ __attribute__((aligned(16))) unsigned char span[RS_SPAN_BYTES];
+    __shared__ int yx0[TW], ywx[TW], yy0[TH], ywy[TH], ux0[TW / 2], uwx[TW / 2], uy0[TH / 2], uwy[TH / 2];
+    const int tid = threadIdx.x, X0 = blockIdx.x * TW, Y0 = blockIdx.y * TH;
+    const size_t b = blockIdx.z;
+    const int Hs2 = (a.Hs + 1) / 2, Ws2 = (a.Ws + 1) / 2, Hd2 = (a.Hd + 1) / 2, Wd2 = (a.Wd + 1) / 2;
+    if (tid < 64) resize_axis(min(X0 + tid, a.Wd - 1), a.Wd, a.Ws, yx0[tid], ywx[tid]);
+    else if (tid < 96) resize_axis(min(Y0 + tid - 64, a.Hd - 1), a.Hd, a.Hs, yy0[tid - 64], ywy[tid - 64]);
+    else if (tid < 128) resize_axis(min(X0 / 2 + tid - 96, Wd2 - 1), Wd2, Ws2, ux0[tid - 96], uwx[tid - 96]);
+    else if (tid < 144) resize_axis(min(Y0 / 2 + tid - 128, Hd2 - 1), Hd2, Hs2, uy0[tid - 128], uwy[tid - 128]);
+    __syncthreads();
+    const int nx = min(TW, a.Wd - X0), ny = min(TH, a.Hd - Y0), nxc = (nx + 1) / 2, nyc = (ny + 1) / 2;
+    int ys_lo, ys_hi, xs_lo, xs_hi, us_lo, us_hi, ucs_lo, ucs_hi;
+    resize_span(yy0, ny, a.Hs, ys_lo, ys_hi);
+    resize_span(yx0, nx, a.Ws, xs_lo, xs_hi);
+    resize_span(uy0, nyc, Hs2, us_lo, us_hi);
+    resize_span(ux0, nxc, Ws2, ucs_lo, ucs_hi);
+    const int yhi = xs_hi + 1, ya0 = a.wide_src ? (xs_lo & ~15) : xs_lo, yls = (yhi - ya0 + 15) & ~15, yrows = ys_hi - ys_lo + 1;
+    const int uhi = (ucs_hi + 1) * 2, ua0 = a.wide_src ? ((ucs_lo * 2) & ~15) : ucs_lo * 2, uls = (uhi - ua0 + 15) & ~15, urows = us_hi - us_lo + 1;
+    const unsigned char *yplane = a.y + b * a.in.y_bstride, *uvplane = a.uv + b * a.in.uv_bstride;
+    unsigned char *const uspan = span + yrows * yls;
+    const bool staged = (long long)yrows * yls + (long long)urows * uls <= RS_SPAN_BYTES;   // uniform over the workgroup
+    if (staged) {
+        resize_stage(span, yls, yplane, a.in.y_pitch, a.Ws, ys_lo, yrows, ya0, yhi, a.wide_src);
+        resize_stage(uspan, uls, uvplane, a.in.uv_pitch, 2 * Ws2, us_lo, urows, ua0, uhi, a.wide_src);
+        __syncthreads();
+    }
+    const int r2 = tid >> 4, c4 = (tid & 15) * 4;
+    if (2 * r2 >= ny || c4 >= nx) return;
+    const int n = min(4, nx - c4), np = (n + 1) / 2, nr = min(2, ny - 2 * r2), cc = c4 / 2;
+    int UV[2][2] = {{128, 128}, {128, 128}};
+    {
+        const int y0 = uy0[r2], y1 = min(y0 + 1, Hs2 - 1), wy = uwy[r2];
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+            if (p < np) {
+                if (staged) resize_pixel<2>(uspan + (y0 - us_lo) * uls, uspan + (y1 - us_lo) * uls, ua0, ux0[cc + p], Ws2, uwx[cc + p], wy, UV[p]);
+                else resize_pixel<2>(uvplane + (size_t)y0 * a.in.uv_pitch, uvplane + (size_t)y1 * a.in.uv_pitch, 0, ux0[cc + p], Ws2, uwx[cc + p], wy, UV[p]);
+            }
+    }
+    if (a.uvo) {
+        unsigned char *o = a.uvo + b * a.out.uv_bstride + (size_t)(Y0 / 2 + r2) * a.out.uv_pitch + X0 + c4;   // pair (X0 + c4) / 2 starts at byte X0 + c4
+        if (a.wide_out && np == 2) {
+            *reinterpret_cast<unsigned *>(o) = (unsigned)UV[0][0] | ((unsigned)UV[0][1] << 8) | ((unsigned)UV[1][0] << 16) | ((unsigned)UV[1][1] << 24);
+        } else {
+            for (int p = 0; p < np; ++p) { o[2 * p] = (unsigned char)UV[p][0]; o[2 * p + 1] = (unsigned char)UV[p][1]; }
+        }
+    }
+    const size_t dplane = (size_t)a.Hd * a.Wd;
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+        if (rr >= nr) break;
+        const int r = 2 * r2 + rr, y = Y0 + r, y0 = yy0[r], y1 = min(y0 + 1, a.Hs - 1), wy = ywy[r];
+        int Y[4] = {0, 0, 0, 0};
+        float out[3][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j < n) {
+                if (staged) resize_pixel<1>(span + (y0 - ys_lo) * yls, span + (y1 - ys_lo) * yls, ya0, yx0[c4 + j], a.Ws, ywx[c4 + j], wy, &Y[j]);
+                else resize_pixel<1>(yplane + (size_t)y0 * a.in.y_pitch, yplane + (size_t)y1 * a.in.y_pitch, 0, yx0[c4 + j], a.Ws, ywx[c4 + j], wy, &Y[j]);
+            }
+            int ch[3];
+            nv12_decode(Y[j], UV[j >> 1][0], UV[j >> 1][1], k, ch);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[c][j] = nv12_norm(ch[c], st.mean[c], st.stdv[c]);
+        }
+        if (a.yo) {
+            unsigned char *o = a.yo + b * a.out.y_bstride + (size_t)y * a.out.y_pitch + X0 + c4;
+            if (a.wide_out && n == 4) {
+                *reinterpret_cast<unsigned *>(o) = (unsigned)Y[0] | ((unsigned)Y[1] << 8) | ((unsigned)Y[2] << 16) | ((unsigned)Y[3] << 24);
+            } else {
+                for (int j = 0; j < n; ++j) o[j] = (unsigned char)Y[j];
+            }
+        }
+        float *o = a.f32 + b * 3 * dplane + (size_t)y * a.Wd + X0 + c4;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (a.wide_f32 && n == 4) {
+                *reinterpret_cast<f32x4 *>(o + c * dplane) = f32x4{out[c][0], out[c][1], out[c][2], out[c][3]};
+            } else {
+                for (int j = 0; j < n; ++j) o[c * dplane + j] = out[c][j];
+            }
+        }
+    }
+}
+
+static bool mult_of(unsigned m, std::initializer_list<size_t> v)
+{
+    size_t acc = 0;
+    for (size_t x : v) acc |= x;
+    return (acc & (m - 1)) == 0;
+}
+int launch_resize_u8(const unsigned char *src, size_t src_pitch, size_t src_bstride, unsigned char *dst_u8, size_t dst_pitch, size_t dst_bstride,
+                     float *dst_f32, int B, int Hs, int Ws, int Hd, int Wd, int C, const float *mean, const float *stdv, hipStream_t s)
+{
+    Stats4 st{};
+    for (int c = 0; c < C && c < 4; ++c) { st.mean[c] = mean ? mean[c] : 0.0f; st.stdv[c] = stdv ? stdv[c] : 1.0f; }
+    ResizeArgs a{src, src_pitch, src_bstride, dst_u8, dst_pitch, dst_bstride, dst_f32, Hs, Ws, Hd, Wd, 0, 0, 0};
+    a.wide_src = mult_of(16, {(size_t)(uintptr_t)src, src_pitch, B > 1 ? src_bstride : 0});
+    a.wide_f32 = dst_f32 && mult_of(16, {(size_t)(uintptr_t)dst_f32}) && Wd % 4 == 0;
+    a.wide_u8 = dst_u8 && mult_of(4, {(size_t)(uintptr_t)dst_u8, dst_pitch, B > 1 ? dst_bstride : 0});
+    const dim3 grid((unsigned)((Wd + 63) / 64), (unsigned)((Hd + 15) / 16), (unsigned)B);
+    switch (C) {
+    case 1: resize_u8_kernel<1><<<grid, 256, 0, s>>>(a, st); break;
+    case 2: resize_u8_kernel<2><<<grid, 256, 0, s>>>(a, st); break;
+    case 3: resize_u8_kernel<3><<<grid, 256, 0, s>>>(a, st); break;
+    default: resize_u8_kernel<4><<<grid, 256, 0, s>>>(a, st); break;
+    }
+    return (int)hipGetLastError();
+}
+int launch_preprocess_nv12_resized(const unsigned char *y, size_t y_pitch, size_t y_bstride, const unsigned char *uv, size_t uv_pitch,
+                                   size_t uv_bstride, float *dst, unsigned char *y_out, size_t yo_pitch, size_t yo_bstride, unsigned char *uv_out,
+                                   size_t uvo_pitch, size_t uvo_bstride, int B, int Hs, int Ws, int Hd, int Wd, int standard, int order,
+                                   const float *mean, const float *stdv, hipStream_t s)
+{
+    Stats4 st{};
+    for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
+    ResizeNv12Args a{y, uv, Nv12Planes{y_pitch, y_bstride, uv_pitch, uv_bstride}, dst, y_out, uv_out, Nv12Planes{yo_pitch, yo_bstride, uvo_pitch, uvo_bstride},
+                     Hs, Ws, Hd, Wd, 0, 0, 0};
+    a.wide_src = mult_of(16, {(size_t)(uintptr_t)y, (size_t)(uintptr_t)uv, y_pitch, uv_pitch, B > 1 ? y_bstride : 0, B > 1 ? uv_bstride : 0});
+    a.wide_f32 = mult_of(16, {(size_t)(uintptr_t)dst}) && Wd % 4 == 0;
+    a.wide_out = mult_of(4, {y_out ? (size_t)(uintptr_t)y_out | yo_pitch | (B > 1 ? yo_bstride : 0) : 0,
+                             uv_out ? (size_t)(uintptr_t)uv_out | uvo_pitch | (B > 1 ? uvo_bstride : 0) : 0});
+    const dim3 grid((unsigned)((Wd + 63) / 64), (unsigned)((Hd + 31) / 32), (unsigned)B);
+    preprocess_nv12_resized_kernel<<<grid, 256, 0, s>>>(a, st, yuv_coef(standard, order));
+    return (int)hipGetLastError();
+}
+
 // ---- census of the one-launch packs (deform_pack3.inl, DeformParams::census): one wave per block adds the 64 slots
 struct CensusTotals { unsigned long long t[8]; };
 __global__ void census_reduce_kernel(const unsigned *__restrict__ census, unsigned long long *__restrict__ out, CensusTotals totals)

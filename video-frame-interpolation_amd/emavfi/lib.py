@@ -47,6 +47,11 @@ _PROTOTYPES = {
                                + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
     "emavfi_postprocess_nv12": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 5
                                 + [POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int, c_void_p]),
+    "emavfi_resize_u8": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 6 + [c_void_p]),
+    "emavfi_preprocess_u8_resized": (c_int, [c_void_p] * 3 + [c_int] * 6 + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
+    "emavfi_preprocess_nv12_resized": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p,
+                                               c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 7
+                                       + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
     "emavfi_conv3x3_workspace_bytes": (c_size_t, [c_int] * 7),
     "emavfi_conv3x3": (c_int, [c_void_p] * 4 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p]),
     "emavfi_deform_conv2d_workspace_bytes": (c_size_t, [c_int] * 6),
@@ -496,11 +501,25 @@ def _pinned_or_cuda(t, what):
         raise RuntimeError(f"{what}: a ROCm tensor or a PINNED host tensor (read / written by the kernel over PCIe) is expected")
 
 
-def preprocess_u8(frames_hwc, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None, out=None):
+def _resize_target(size, what):
+    """(Hd, Wd) of a `size=` argument, each 1 .. RESIZE_MAX_DIM"""
+    try:
+        Hd, Wd = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: size must be (Hd, Wd)") from None
+    if not (1 <= Hd <= RESIZE_MAX_DIM and 1 <= Wd <= RESIZE_MAX_DIM):
+        raise ValueError(f"{what}: size {(Hd, Wd)} must lie in 1..{RESIZE_MAX_DIM}")
+    return Hd, Wd
+
+
+def preprocess_u8(frames_hwc, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None, out=None, size=None, resized_out=None):
     """ToTensor + Normalize of reference inference.py:38-41 on the GPU: uint8 [B,H,W,C] -> fp32 [B,C,H,W].
     `frames_hwc` may be a pinned host tensor: the kernel then reads it in place over PCIe (no separate H2D copy;
     `device` names the GPU) - the caller keeps it unchanged until the kernel has run.  `out`: a contiguous fp32 [B,C,H,W] device
-    tensor to fill (the streaming harness keeps one per buffer slot, so nothing is allocated on its side streams)."""
+    tensor to fill (the streaming harness keeps one per buffer slot, so nothing is allocated on its side streams).
+    `size=(Hd, Wd)`: the frames are resized first (cv2.resize of inference.py:46; the resize definition of include/emavfi.h) in the same
+    launch - the result, fp32 [B,C,Hd,Wd], is preprocess_u8(resize_u8(frames_hwc, size)) bit for bit; `resized_out`: a contiguous uint8
+    [B,Hd,Wd,C] device tensor that then also receives the resized bytes."""
     import torch
     _pinned_or_cuda(frames_hwc, "preprocess_u8")
     if frames_hwc.dtype != torch.uint8 or frames_hwc.dim() != 4:
@@ -509,6 +528,21 @@ def preprocess_u8(frames_hwc, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None,
     dev = x.device if x.is_cuda else torch.device(device if device is not None else "cuda")
     B, H, W, C = x.shape
     m, s = _stats(mean, std, C)
+    if size is not None:
+        Hd, Wd = _resize_target(size, "preprocess_u8")
+        if out is None:
+            out = torch.empty(B, C, Hd, Wd, dtype=torch.float32, device=dev)
+        elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, C, Hd, Wd) and out.is_contiguous()):
+            raise ValueError("preprocess_u8: out must be a contiguous fp32 [B,C,Hd,Wd] device tensor")
+        if resized_out is not None and not (resized_out.is_cuda and resized_out.dtype == torch.uint8 and resized_out.is_contiguous()
+                                            and tuple(resized_out.shape) == (B, Hd, Wd, C)):
+            raise ValueError("preprocess_u8: resized_out must be a contiguous uint8 [B,Hd,Wd,C] device tensor")
+        with torch.cuda.device(dev):
+            check(load().emavfi_preprocess_u8_resized(x.data_ptr(), out.data_ptr(), resized_out.data_ptr() if resized_out is not None else None,
+                                                      B, H, W, Hd, Wd, C, m, s, _stream()), "emavfi_preprocess_u8_resized")
+        return out
+    if resized_out is not None:
+        raise ValueError("preprocess_u8: resized_out needs size=")
     if out is None:
         out = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
     elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, C, H, W) and out.is_contiguous()):
@@ -537,6 +571,43 @@ def postprocess_u8(frames_nchw, denormalize=True, mean=IMAGENET_MEAN, std=IMAGEN
     with torch.cuda.device(x.device):
         check(load().emavfi_postprocess_u8(x.data_ptr(), out.data_ptr(), B, H, W, C, m, s, 1 if denormalize else 0, _stream()),
               "emavfi_postprocess_u8")
+    return out
+
+
+# ---------------------------------------------------------------- frames resized on the device (include/emavfi.h, "RESIZE DEFINITION")
+RESIZE_MAX_DIM = 16384   # EMAVFI_RESIZE_MAX_DIM
+
+
+def _byte_image(t, what, shape=None):
+    """(pointer, pitch, batch stride) in bytes of a uint8 [B,H,W,C] image; rows and batches may be strided, a row must be dense"""
+    import torch
+    _pinned_or_cuda(t, what)
+    if t.dtype != torch.uint8 or t.dim() != 4 or min(t.shape) < 1:
+        raise ValueError(f"{what}: a non-empty uint8 [B,H,W,C] tensor expected")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: shape {tuple(shape)} expected, got {tuple(t.shape)}")
+    B, H, W, C = t.shape
+    if (C > 1 and t.stride(3) != 1) or (W > 1 and t.stride(2) != C):
+        raise ValueError(f"{what}: the rows must be dense (only rows and batches may be strided)")
+    pitch = t.stride(1) if H > 1 else W * C     # a dimension of size 1 has no meaningful stride: the dense value stands in
+    return t.data_ptr(), pitch, (t.stride(0) if B > 1 else pitch * H)
+
+
+def resize_u8(src, size, out=None, device=None):
+    """cv2.resize(frame, (Wd, Hd)) of reference inference.py:46 on the GPU, by THE PROJECT'S OWN DEFINITION (include/emavfi.h: bilinear,
+    half-pixel centres, 11-bit weights, integer arithmetic; no byte parity with cv2 is claimed): uint8 [B,Hs,Ws,C] -> uint8 [B,Hd,Wd,C],
+    C in 1..4, each channel on its own.  `src` / `out`: device tensors (src may be pinned host memory; `device` names the GPU) whose rows and
+    batches may be strided - pitches come from .stride(); bytes between the rows of a pitched `out` are left as they were."""
+    import torch
+    Hd, Wd = _resize_target(size, "resize_u8")
+    sp, spitch, sbs = _byte_image(src, "resize_u8")
+    B, Hs, Ws, C = src.shape
+    dev = src.device if src.is_cuda else torch.device(device if device is not None else "cuda")
+    if out is None:
+        out = torch.empty(B, Hd, Wd, C, dtype=torch.uint8, device=dev)
+    dp, dpitch, dbs = _byte_image(out, "resize_u8(out=)", (B, Hd, Wd, C))
+    with torch.cuda.device(dev):
+        check(load().emavfi_resize_u8(sp, spitch, sbs, dp, dpitch, dbs, B, Hs, Ws, Hd, Wd, C, _stream()), "emavfi_resize_u8")
     return out
 
 
@@ -593,16 +664,37 @@ def _nv12_planes(y, uv, what):
     return B, H, W, y_pitch, y_bs, uv_pitch, uv_bs
 
 
-def preprocess_nv12(y, uv, standard="bt601", full_range=False, order="bgr", mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None, out=None):
+def preprocess_nv12(y, uv, standard="bt601", full_range=False, order="bgr", mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None, out=None,
+                    size=None, resized_out=None):
     """NV12 frames -> fp32 [B,3,H,W], defined as preprocess_u8 of the decoded bytes (include/emavfi.h, "NV12").
     `y` uint8 [B,H,W], `uv` uint8 [B,ceil(H/2),ceil(W/2),2]: device tensors or pinned host tensors (read in place over PCIe; `device`
     names the GPU), each may be strided in its row and batch dimensions - the pitches are taken from .stride().  `order`: which colour is
-    channel 0 ("bgr": what cv2 hands the reference).  `out`: a contiguous fp32 [B,3,H,W] device tensor to fill."""
+    channel 0 ("bgr": what cv2 hands the reference).  `out`: a contiguous fp32 [B,3,H,W] device tensor to fill.
+    `size=(Hd, Wd)`: the planes are resized first in the same launch (Y as a 1-channel image to Hd x Wd, UV as a 2-channel image to
+    ceil(Hd/2) x ceil(Wd/2); the resize definition of include/emavfi.h) - the result, fp32 [B,3,Hd,Wd], is preprocess_nv12 of the
+    resize_u8-resized planes bit for bit; `resized_out=(y_out, uv_out)`: device tensors, strided like y / uv, either may be None, that then
+    also receive the resized planes."""
     import torch
     B, H, W, yp, ybs, uvp, uvbs = _nv12_planes(y, uv, "preprocess_nv12")
     st, od = yuv_standard_code(standard, full_range), _order_code(order)
     dev = y.device if y.is_cuda else torch.device(device if device is not None else "cuda")
     m, s = _stats(mean, std, 3)
+    if size is not None:
+        Hd, Wd = _resize_target(size, "preprocess_nv12")
+        Hd2, Wd2 = (Hd + 1) // 2, (Wd + 1) // 2
+        if out is None:
+            out = torch.empty(B, 3, Hd, Wd, dtype=torch.float32, device=dev)
+        elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, Hd, Wd) and out.is_contiguous()):
+            raise ValueError("preprocess_nv12: out must be a contiguous fp32 [B,3,Hd,Wd] device tensor")
+        yo, uvo = resized_out if resized_out is not None else (None, None)
+        ya = _byte_image(yo.unsqueeze(-1), "preprocess_nv12(resized_out=)", (B, Hd, Wd, 1)) if yo is not None else (None, 0, 0)
+        ua = _byte_image(uvo, "preprocess_nv12(resized_out=)", (B, Hd2, Wd2, 2)) if uvo is not None else (None, 0, 0)
+        with torch.cuda.device(dev):
+            check(load().emavfi_preprocess_nv12_resized(y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs, out.data_ptr(), *ya, *ua,
+                                                        B, H, W, Hd, Wd, st, od, m, s, _stream()), "emavfi_preprocess_nv12_resized")
+        return out
+    if resized_out is not None:
+        raise ValueError("preprocess_nv12: resized_out needs size=")
     if out is None:
         out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
     elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, H, W) and out.is_contiguous()):

@@ -1,8 +1,8 @@
 """Batched streaming harness around the native forward.
 
 Reproduces the call pattern and OUTPUT ORDER of the reference's hot loop
-(``/root/reference/inference.py:146-205``) for a sequence of already-resized uint8 HWC frames
-(video decode, ``cv2.resize`` and the video writer stay outside - they are host codec I/O):
+(``/root/reference/inference.py:146-205``) for a sequence of uint8 HWC frames (video decode and the video writer stay outside - they are
+host codec I/O; the reference's ``cv2.resize`` of every frame to ``--scale`` runs on the device when ``scale`` / ``size`` is given, see below):
 
     frame1 = first frame
     for every next frame2 (every ``frame_interval``-th loop turn, :161-164):
@@ -40,6 +40,13 @@ layout video decoders produce - uint8 ``[H*3/2, W]``: H rows of Y, then H/2 rows
 slots and the SDMA copies move 1.5 bytes per pixel instead of 3.  Decode and encode run inside the device kernels
 (emavfi_preprocess_nv12 / _postprocess_nv12, colour definition: include/emavfi.h); ``yuv_standard`` / ``yuv_full_range`` pick one of the four
 standards.  Order, counts and scheduling are the same; a round-tripped source frame is decode -> normalise -> denormalise -> encode.
+``scale=s`` (the reference's ``--scale``, inference.py:93-94: frames become ``(int(H * s), int(W * s))``) or ``size=(Hd, Wd)`` (mutually
+exclusive; opt-in) resizes every frame on the device, inside the launch that normalises it (emavfi_preprocess_u8_resized /
+_preprocess_nv12_resized; the resize definition is the project's own, include/emavfi.h - no byte parity with cv2 is claimed).  Frames are
+staged and copied at the source size; everything from the normalised tensor onward, and every yielded frame, has the destination size.  A
+frame the reference writes "as read" (:167, which there is the resized frame) and the source frames of ``reference_quirks=False`` are the
+device-resized bytes.  ``pixel_format="nv12"`` needs an even destination H and W.  With neither argument the harness takes frames that
+already have the size the model runs at, exactly as before.
 """
 from __future__ import annotations
 
@@ -55,7 +62,8 @@ from . import lib as _lib
 class FrameInterpolator:
     def __init__(self, model, interpolation_factor: int = 1, frame_interval: int = 1, batch_pairs: int = 8,
                  reference_quirks: bool = True, mode: str = "reference", device=None, copy_out: bool = True, zero_copy: bool = False,
-                 numa: str = "off", pixel_format: str = "bgr24", yuv_standard: str = "bt601", yuv_full_range: bool = False):
+                 numa: str = "off", pixel_format: str = "bgr24", yuv_standard: str = "bt601", yuv_full_range: bool = False,
+                 scale: Optional[float] = None, size=None):
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
             raise ValueError("interpolation_factor >= 0, frame_interval >= 1, batch_pairs >= 1 required")
         if mode not in ("reference", "recursive"):
@@ -67,6 +75,14 @@ class FrameInterpolator:
         if pixel_format not in ("bgr24", "nv12"):
             raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames) or 'nv12' (uint8 [H*3/2, W] frames)")
         _lib.yuv_standard_code(yuv_standard, yuv_full_range)   # raises on an unknown standard
+        if scale is not None and size is not None:
+            raise ValueError("scale and size are mutually exclusive")
+        if scale is not None and not scale > 0:
+            raise ValueError("scale must be positive")
+        if size is not None:
+            size = self.output_size(0, 0, size=size, pixel_format=pixel_format)   # validates; the source size does not matter here
+        self.scale, self.size = scale, size
+        self._resize = scale is not None or size is not None
         self.pixel_format = pixel_format
         self.yuv = {"standard": yuv_standard, "full_range": bool(yuv_full_range)}
         self.model = model
@@ -92,6 +108,28 @@ class FrameInterpolator:
             self.numa = numa_plan(self.device)
         else:
             self.numa = None
+
+    # ---- the size the model runs at (inference.py:93-94: width = int(w * scale), height = int(h * scale))
+    @staticmethod
+    def output_size(H: int, W: int, scale=None, size=None, pixel_format: str = "bgr24"):
+        """(Hd, Wd) of H x W source frames: ``size`` itself, ``(int(H * scale), int(W * scale))`` as the reference truncates, or (H, W).
+        ValueError for both arguments, a size outside 1..16384 and, for NV12, an odd destination H or W.  Pure host logic."""
+        if scale is not None and size is not None:
+            raise ValueError("scale and size are mutually exclusive")
+        if size is not None:
+            try:
+                Hd, Wd = (int(v) for v in size)
+            except (TypeError, ValueError):
+                raise ValueError("size must be (Hd, Wd)") from None
+        elif scale is not None:
+            Hd, Wd = int(H * scale), int(W * scale)
+        else:
+            return int(H), int(W)
+        if not (1 <= Hd <= _lib.RESIZE_MAX_DIM and 1 <= Wd <= _lib.RESIZE_MAX_DIM):
+            raise ValueError(f"the resized frame {(Hd, Wd)} must lie in 1..{_lib.RESIZE_MAX_DIM} per dimension")
+        if pixel_format == "nv12" and (Hd % 2 or Wd % 2):
+            raise ValueError(f"pixel_format='nv12': the packed [H*3/2, W] layout needs an even destination H and W, got {(Hd, Wd)}")
+        return Hd, Wd
 
     # ---- the reference's frame selection (inference.py:158-201), as (pairs, tail) over frame indices
     @staticmethod
@@ -155,10 +193,13 @@ class FrameInterpolator:
         if self._shape == shape:
             return
         if self.pixel_format == "nv12":
-            H, W, C = shape[0] * 2 // 3, shape[1], 3     # [H*3/2, W]: Y rows, then the UV rows
+            Hs, Ws, C = shape[0] * 2 // 3, shape[1], 3   # [H*3/2, W]: Y rows, then the UV rows
         else:
-            H, W, C = shape
-        fs = tuple(shape)                                # a frame as it travels: [H, W, C] or [H*3/2, W]
+            Hs, Ws, C = shape
+        fin = tuple(shape)                               # a frame as it arrives: [Hs, Ws, C] or [Hs*3/2, Ws]
+        H, W = self.output_size(Hs, Ws, self.scale, self.size, self.pixel_format)
+        self._dst = (H, W)
+        fs = (H * 3 // 2, W) if self.pixel_format == "nv12" else (H, W, C)   # a frame as it leaves, at the size the model runs at
         nb, nout = self.batch_pairs, max(self.factor if self.mode == "recursive" else 1, 1)
         self._shape = shape
         self._slots = []
@@ -166,16 +207,18 @@ class FrameInterpolator:
             if self._bound():
                 # pinned and first touched on a thread of the device's node (on the hosts measured the runtime already put pinned
                 # pages on the GPU's node whichever CPU asked: profiles/r09_numa_stream_ab.md)
-                pinned = self._copy_pool().submit(self._pinned_local, [(2 * nb, *fs), (nb * nout, *fs), (nb, *fs)]).result()
+                pinned = self._copy_pool().submit(self._pinned_local, [(2 * nb, *fin), (nb * nout, *fs), (nb, *fs)]).result()
             else:
-                pinned = [torch.empty(2 * nb, *fs, dtype=torch.uint8).pin_memory(),
+                pinned = [torch.empty(2 * nb, *fin, dtype=torch.uint8).pin_memory(),
                           torch.empty(nb * nout, *fs, dtype=torch.uint8).pin_memory(),
                           torch.empty(nb, *fs, dtype=torch.uint8).pin_memory()]
             self._slots.append({
                 "h_in": pinned[0], "h_pred": pinned[1], "h_src": pinned[2],
                 "x": torch.empty(2 * nb, C, H, W, dtype=torch.float32, device=self.device),
                 # device-side images of the three pinned buffers (the SDMA copies' other end)
-                "d_in": torch.empty(2 * nb, *fs, dtype=torch.uint8, device=self.device),
+                "d_in": torch.empty(2 * nb, *fin, dtype=torch.uint8, device=self.device),
+                # the resized bytes of the slot's frames, where frames leave as they arrived (reference_quirks=False) and arrive at another size
+                "d_rs": torch.empty(2 * nb, *fs, dtype=torch.uint8, device=self.device) if self._resize and not self.quirks else None,
                 "d_pred": torch.empty(nb * nout, *fs, dtype=torch.uint8, device=self.device),
                 "d_src": torch.empty(nb, *fs, dtype=torch.uint8, device=self.device),
                 # consumed: the preprocess kernel has read h_in (the host may restage it); pre: x is ready; fwd: the forward has read x
@@ -195,11 +238,26 @@ class FrameInterpolator:
         H = buf.shape[1] * 2 // 3
         return buf[:, :H], buf[:, H:].unflatten(2, (buf.shape[2] // 2, 2))
 
-    def _pre_kernel(self, buf, out=None, device=None):
+    def _pre_kernel(self, buf, out=None, device=None, resized=None):
+        """`resized`: with scale / size, a buffer of frames at the destination size that also receives the resized bytes"""
+        size = self._dst if self._resize else None
         if self.pixel_format == "nv12":
             y, uv = self._planes(buf)
-            return _lib.preprocess_nv12(y, uv, self.yuv["standard"], self.yuv["full_range"], device=device, out=out)
-        return _lib.preprocess_u8(buf, device=device, out=out)
+            return _lib.preprocess_nv12(y, uv, self.yuv["standard"], self.yuv["full_range"], device=device, out=out, size=size,
+                                        resized_out=self._planes(resized) if resized is not None else None)
+        return _lib.preprocess_u8(buf, device=device, out=out, size=size, resized_out=resized)
+
+    def _resized_bytes(self, frame):
+        """one source frame (numpy) at the destination size, as the device resizes it"""
+        src = torch.from_numpy(frame).unsqueeze(0).to(self.device)
+        if self.pixel_format == "nv12":
+            (H, W), (y, uv) = self._dst, self._planes(src)
+            out = torch.empty(1, H * 3 // 2, W, dtype=torch.uint8, device=self.device)
+            yo, uvo = self._planes(out)
+            _lib.resize_u8(y.unsqueeze(-1), (H, W), out=yo.unsqueeze(-1))
+            _lib.resize_u8(uv, (H // 2, W // 2), out=uvo)
+            return out.cpu().numpy()[0]
+        return _lib.resize_u8(src, self._dst).cpu().numpy()[0]
 
     def _post_kernel(self, x, denormalize, out=None):
         if self.pixel_format == "nv12":
@@ -268,9 +326,12 @@ class FrameInterpolator:
     @staticmethod
     def _rows(x, idx):
         """x[idx] without a device index tensor: a view when idx is a run of consecutive rows (the usual case:
-        consecutive pairs share frames), otherwise a stack of row views."""
+        consecutive pairs share frames), otherwise a stack of row views.  The forward takes 16-byte aligned tensors
+        (include/emavfi.h): where a frame is no multiple of four floats (C*H*W % 4 != 0, e.g. 23 x 37) a run that starts at
+        an odd row lies off that boundary and is copied into a fresh (aligned) tensor instead."""
         if all(idx[k + 1] == idx[k] + 1 for k in range(len(idx) - 1)):
-            return x[idx[0]:idx[0] + len(idx)]
+            rows = x[idx[0]:idx[0] + len(idx)]
+            return rows if rows.data_ptr() % 16 == 0 else rows.clone()
         return torch.stack([x[i] for i in idx])
 
     def _predict(self, x1, x2):
@@ -343,7 +404,7 @@ class FrameInterpolator:
                 else:
                     for _ in range(self.factor):
                         yield own(pred_h[k])
-                yield own(src_h[k]) if self.quirks else frames[a]
+                yield own(src_h[k]) if (self.quirks or self._resize) else frames[a]
 
         staged = self._stage(self._slots[0], frames, chunks[0]) if chunks else None
         prev = None
@@ -355,15 +416,21 @@ class FrameInterpolator:
                 # the slot's x was last read by the forward of batch ci - 2 (main) and by the round-trip postprocess of its frames (post)
                 self._pre.wait_event(slot["fwd"])
                 self._pre.wait_event(slot["done"])
+                rs = slot["d_rs"][:nup] if slot["d_rs"] is not None else None
                 if self.zero_copy:
-                    x = self._pre_kernel(slot["h_in"][:nup], device=self.device, out=slot["x"][:nup])   # distinct frames, read over PCIe, normalised once
+                    x = self._pre_kernel(slot["h_in"][:nup], device=self.device, out=slot["x"][:nup], resized=rs)   # distinct frames, read over PCIe, normalised once
                     slot["consumed"].record(self._pre)
                 else:
                     slot["d_in"][:nup].copy_(slot["h_in"][:nup], non_blocking=True)                       # hipMemcpyAsync pinned -> HBM (SDMA)
                     slot["consumed"].record(self._pre)
-                    x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup])                         # distinct frames, normalised once
+                    x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=rs)             # distinct frames, normalised once
                 slot["pre"].record(self._pre)
                 src_here = self.quirks and not self.zero_copy and all(ia[k + 1] == ia[k] + 1 for k in range(n - 1))
+                if rs is not None:
+                    # reference_quirks=False with a resize: every pair's earlier frame leaves as the preprocess kernel resized it
+                    for k in range(n):
+                        slot["h_src"][k].copy_(rs[ia[k]], non_blocking=True)
+                    slot["src"].record(self._pre)
                 if src_here:
                     # the reference's round trip of every pair's earlier frame (inference.py:187-188) depends on the preprocess only:
                     # it leaves from this lane, ahead of the forward, instead of queueing behind the predictions at the end of the batch
@@ -392,6 +459,8 @@ class FrameInterpolator:
                         slot["h_src"][:n].copy_(slot["d_src"][:n], non_blocking=True)
                     if src_here:
                         self._post.wait_event(slot["src"])                    # `done` covers both lanes' writes into the pinned buffers
+                if rs is not None:
+                    self._post.wait_event(slot["src"])
                 slot["done"].record(self._post)
             if ci + 1 < len(chunks):                  # host-side staging of the next batch overlaps this batch's compute
                 staged = self._stage(self._slots[(ci + 1) & 1], frames, chunks[ci + 1])
@@ -406,4 +475,4 @@ class FrameInterpolator:
             src = torch.from_numpy(frames[last]).unsqueeze(0).to(self.device)
             yield self._post_kernel(self._pre_kernel(src), True).cpu().numpy()[0]
         else:
-            yield frames[last]
+            yield self._resized_bytes(frames[last]) if self._resize else frames[last]
