@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -362,6 +362,52 @@ int emavfi_preprocess_nv12_resized(const unsigned char *y, size_t y_pitch, size_
                                    size_t uv_batch_stride, float *out_nchw, unsigned char *y_out, size_t y_out_pitch, size_t y_out_batch_stride,
                                    unsigned char *uv_out, size_t uv_out_pitch, size_t uv_out_batch_stride, int B, int Hs, int Ws, int Hd, int Wd,
                                    int standard, int order, const float *mean, const float *std, void *stream);
+
+/* Scene cuts, decided and applied on the device.  When frame a ends one shot and frame b starts the next, a motion-compensated blend of the two
+ * is a ghosted mixture; a video tool holds the earlier frame instead.  The reference has no such guard (inference.py:173-188 interpolates every
+ * pair); this is an addition, off unless asked for.  The decision is made from the frame bytes already on the device and applied there: the
+ * host learns of it only together with the frames it waits for anyway.
+ *
+ * SCENE CUT DEFINITION (the one place).  This is the project's own definition: it follows no outside tool's scene detector (Practical-RIFE,
+ * ffmpeg's minterpolate scd, ...) and claims agreement with none.  All arithmetic is unsigned 32-bit integer, `/` is floor division: host,
+ * oracle and device agree bit for bit.
+ *   Luma of a pixel.  C = 1: the byte itself (a Y plane, as NV12 stores it).  C = 3: (313524 R + 615514 G + 119538 B + 2^19) >> 20 - the
+ *     encode row of EMAVFI_YUV_BT601_FULL above; it sums to 2^20, so the result is 0..255 with no clip.  `order` (EMAVFI_ORDER_BGR /
+ *     EMAVFI_ORDER_RGB) says which byte is R; it is ignored (but still validated) at C = 1.
+ *   Signature of a frame: EMAVFI_SCENE_GRID x EMAVFI_SCENE_GRID = 32 x 32 cells, EMAVFI_SCENE_SIG_WORDS = 1024 u32.  Cell (i, j) covers rows
+ *     [i H / 32, (i + 1) H / 32) and columns [j W / 32, (j + 1) W / 32); with H < 32 or W < 32 some cells hold no pixel (empty cells).
+ *     sig[i 32 + j] = the sum of the luma over the cell, 0 for an empty cell.  H and W are 1..16384: the largest cell is 512 x 512 pixels,
+ *     so 16 sum + n / 2 <= 16 * 255 * 2^18 + 2^17 < 2^31.
+ *   Score of a pair: for every non-empty cell of n pixels m = (16 sum + n / 2) / n (the cell's mean in sixteenths of a count, 0..4080);
+ *     score = the sum over the cells of |m_a - m_b|, 0 .. 4080 cells with cells = min(H, 32) min(W, 32);  flag = score >= threshold.
+ *     `threshold` is in score units.  A caller who thinks of "the mean absolute difference of the two 32 x 32 thumbnails as a fraction of
+ *     full scale" passes ceil(fraction * 4080 * cells) (the Python layer's scene_threshold_units does).
+ *
+ * emavfi_luma_signature_u8: src [B][H][W][C] bytes, C = 1 or 3, rows `pitch` bytes apart, frames `batch_stride` bytes apart -> sig [B][1024]
+ *   u32 in device memory.  EVERY one of the B * 1024 words is written, whatever the buffer held before (empty cells: 0); a workgroup owns
+ *   the cells it stores, so there are no global atomics and nothing has to be zeroed first.
+ * emavfi_scene_flags: pair k < n compares the signatures at sig_a + k stride_a_words and sig_b + k stride_b_words (strides in u32 words: 0 -
+ *   every pair against the one signature - or at least 1024) of H x W frames; writes flags[k] = 0 / 1 and, unless `scores` is NULL, scores[k].
+ * emavfi_hold_frames_u8: for every k < n with flags[k] != 0 the frame_bytes bytes at alt + k alt_stride are copied over each of the `rep`
+ *   frames at dst + (k rep + r) dst_stride, r < rep.  Frames of unflagged pairs and bytes between frames are left as they were.
+ * EMAVFI_E_ARG (never an abort): a null required pointer, B, n or rep below 1 (or above 65535: B, n of emavfi_hold_frames_u8, rep), a
+ *   dimension below 1 or above 16384, C outside {1, 3}, an unknown order, a pitch smaller than its row, for B > 1 a batch stride smaller
+ *   than its plane, a u32 pointer that is not 4-byte aligned, a signature stride between 1 and 1023 words, frame_bytes of 0 or above
+ *   2^40, for n rep > 1 a dst_stride or alt_stride smaller than frame_bytes, size arithmetic that overflows size_t.
+ * The byte pointers are device pointers or pinned (device-mapped) host memory, as for the u8 entries; sig, flags and scores: device memory
+ *   (or pinned).  Nothing is allocated, nothing synchronises, all work goes on `stream`.  Access width: the signature kernel reads 16 pixels
+ *   per lane with 16-byte loads when the source pointer, the pitch and (B > 1) the batch stride are multiples of 16, and the right remainder
+ *   of a row - or everything, otherwise - byte by byte with the same per-element functions (csrc/scene_elem.h); the hold kernel copies
+ *   with 16-byte accesses when both frame addresses are 16-byte aligned (the last frame_bytes % 16 bytes: byte accesses), else byte by byte;
+ *   a workgroup whose pair is not flagged leaves at once. */
+#define EMAVFI_SCENE_GRID 32
+#define EMAVFI_SCENE_SIG_WORDS 1024
+int emavfi_luma_signature_u8(const unsigned char *src, size_t pitch, size_t batch_stride, int B, int H, int W, int C, int order, unsigned *sig,
+                             void *stream);
+int emavfi_scene_flags(const unsigned *sig_a, size_t stride_a_words, const unsigned *sig_b, size_t stride_b_words, int n, int H, int W,
+                       unsigned threshold, unsigned *flags, unsigned *scores, void *stream);
+int emavfi_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const unsigned char *alt, size_t alt_stride, const unsigned *flags, int n,
+                          size_t frame_bytes, void *stream);
 
 /* One conv / conv_block (ema_vfi.py:7-14): Conv2d(k=3, p=1, stride 1 or 2) + activation.
  * x [B,Cin,H,W], weight [Cout,Cin,3,3], bias [Cout], y [B,Cout,ceil(H/stride),ceil(W/stride)]. */

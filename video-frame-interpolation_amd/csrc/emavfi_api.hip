@@ -1452,6 +1452,79 @@ int emavfi_preprocess_nv12_resized(const unsigned char *y, size_t y_pitch, size_
     return EMAVFI_OK;
 }
 
+// ---- scene cuts on the device (include/emavfi.h, "SCENE CUT DEFINITION"): every check runs on the host, pointers are looked at last
+static int scene_dims_check(const char *what, int H, int W)
+{
+    if (H < 1 || W < 1) return fail(EMAVFI_E_ARG, "%s: H, W must be >= 1", what);
+    if (H > EMAVFI_RESIZE_MAX_DIM || W > EMAVFI_RESIZE_MAX_DIM) return fail(EMAVFI_E_ARG, "%s: a dimension (%d x %d) is above 16384", what, H, W);
+    return EMAVFI_OK;
+}
+
+int emavfi_luma_signature_u8(const unsigned char *src, size_t pitch, size_t batch_stride, int B, int H, int W, int C, int order, unsigned *sig,
+                             void *stream)
+{
+    const char *const what = "luma_signature_u8";
+    if (B < 1) return fail(EMAVFI_E_ARG, "%s: B must be >= 1", what);
+    if (B > 65535) return fail(EMAVFI_E_ARG, "%s: B = %d is above 65535", what, B);
+    if (const int rc = scene_dims_check(what, H, W); rc != EMAVFI_OK) return rc;
+    if (C != 1 && C != 3) return fail(EMAVFI_E_ARG, "%s: C = %d (C must be 1 or 3)", what, C);
+    if (order != EMAVFI_ORDER_BGR && order != EMAVFI_ORDER_RGB)
+        return fail(EMAVFI_E_ARG, "%s: unknown order %d (EMAVFI_ORDER_BGR or EMAVFI_ORDER_RGB)", what, order);
+    const size_t row = (size_t)W * C;
+    if (pitch < row) return fail(EMAVFI_E_ARG, "%s: pitch %zu is smaller than its row of %zu bytes", what, pitch, row);
+    size_t plane, span;
+    if (__builtin_mul_overflow((size_t)(H - 1), pitch, &plane) || __builtin_add_overflow(plane, row, &plane))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (pitch %zu)", what, pitch);
+    if (B > 1 && batch_stride < plane) return fail(EMAVFI_E_ARG, "%s: the batch stride %zu is smaller than its plane", what, batch_stride);
+    if (B > 1 && (__builtin_mul_overflow((size_t)(B - 1), batch_stride, &span) || __builtin_add_overflow(span, plane, &span)))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (batch stride %zu)", what, batch_stride);
+    if (!src || !sig) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
+    if ((uintptr_t)sig & 3) return fail(EMAVFI_E_ARG, "%s: the u32 pointer must be 4-byte aligned", what);
+    EMAVFI_TRY(launch_luma_signature_u8(src, pitch, batch_stride, B, H, W, C, order, sig, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+int emavfi_scene_flags(const unsigned *sig_a, size_t stride_a_words, const unsigned *sig_b, size_t stride_b_words, int n, int H, int W,
+                       unsigned threshold, unsigned *flags, unsigned *scores, void *stream)
+{
+    const char *const what = "scene_flags";
+    if (n < 1) return fail(EMAVFI_E_ARG, "%s: n must be >= 1", what);
+    if (const int rc = scene_dims_check(what, H, W); rc != EMAVFI_OK) return rc;
+    for (const size_t st : {stride_a_words, stride_b_words}) {
+        size_t span;
+        if (st != 0 && st < EMAVFI_SCENE_SIG_WORDS)
+            return fail(EMAVFI_E_ARG, "%s: a signature stride of %zu words is neither 0 nor at least %d", what, st, EMAVFI_SCENE_SIG_WORDS);
+        if (__builtin_mul_overflow((size_t)(n - 1), st, &span) || __builtin_add_overflow(span, (size_t)EMAVFI_SCENE_SIG_WORDS, &span) ||
+            __builtin_mul_overflow(span, sizeof(unsigned), &span))
+            return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (stride %zu words)", what, st);
+    }
+    if (!sig_a || !sig_b || !flags) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
+    if (((uintptr_t)sig_a | (uintptr_t)sig_b | (uintptr_t)flags | (uintptr_t)scores) & 3)
+        return fail(EMAVFI_E_ARG, "%s: the u32 pointers must be 4-byte aligned", what);
+    EMAVFI_TRY(launch_scene_flags(sig_a, stride_a_words, sig_b, stride_b_words, n, H, W, threshold, flags, scores, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+int emavfi_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const unsigned char *alt, size_t alt_stride, const unsigned *flags, int n,
+                          size_t frame_bytes, void *stream)
+{
+    const char *const what = "hold_frames_u8";
+    if (n < 1 || rep < 1) return fail(EMAVFI_E_ARG, "%s: n, rep must be >= 1", what);
+    if (n > 65535 || rep > 65535) return fail(EMAVFI_E_ARG, "%s: n = %d, rep = %d: above 65535", what, n, rep);
+    if (frame_bytes < 1) return fail(EMAVFI_E_ARG, "%s: frame_bytes must be >= 1", what);
+    if (frame_bytes > ((size_t)1 << 40)) return fail(EMAVFI_E_ARG, "%s: frame_bytes %zu is above 2^40", what, frame_bytes);
+    if ((size_t)n * rep > 1 && (dst_stride < frame_bytes || alt_stride < frame_bytes))
+        return fail(EMAVFI_E_ARG, "%s: a stride (dst %zu, alt %zu) is smaller than frame_bytes %zu", what, dst_stride, alt_stride, frame_bytes);
+    size_t span;
+    if (__builtin_mul_overflow((size_t)n * rep - 1, dst_stride, &span) || __builtin_add_overflow(span, frame_bytes, &span) ||
+        __builtin_mul_overflow((size_t)(n - 1), alt_stride, &span) || __builtin_add_overflow(span, frame_bytes, &span))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (strides dst %zu, alt %zu)", what, dst_stride, alt_stride);
+    if (!dst || !alt || !flags) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
+    if ((uintptr_t)flags & 3) return fail(EMAVFI_E_ARG, "%s: the u32 pointer must be 4-byte aligned", what);
+    EMAVFI_TRY(launch_hold_frames_u8(dst, dst_stride, rep, alt, alt_stride, flags, n, frame_bytes, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
 // ---- stage-level entries (diagnostics / parity tests of single operators): one layer, packed into the workspace and run inside one call ----
 // Their plan - the kernel storage type (EMAVFI_F32X3: the f16 kernels on [hi | lo] halves) and, from op_carve, the zero page - and
 // their layer, as the plan of a model lays it out: a bf16 DCN on the LDS-window kernel contracts bf16-rounded weights stored as f16

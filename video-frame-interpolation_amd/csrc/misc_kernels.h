@@ -92,6 +92,12 @@ int launch_preprocess_nv12_resized(const unsigned char *y, size_t y_pitch, size_
                                    size_t uv_bstride, float *dst, unsigned char *y_out, size_t yo_pitch, size_t yo_bstride, unsigned char *uv_out,
                                    size_t uvo_pitch, size_t uvo_bstride, int B, int Hs, int Ws, int Hd, int Wd, int standard, int order,
                                    const float *mean, const float *stdv, hipStream_t s);
+// scene cuts on the device (include/emavfi.h, "SCENE CUT DEFINITION"): arguments already validated; strides of sig_a / sig_b in u32 words
+int launch_luma_signature_u8(const unsigned char *src, size_t pitch, size_t bstride, int B, int H, int W, int C, int order, unsigned *sig, hipStream_t s);
+int launch_scene_flags(const unsigned *sig_a, size_t stride_a, const unsigned *sig_b, size_t stride_b, int n, int H, int W, unsigned threshold,
+                       unsigned *flags, unsigned *scores, hipStream_t s);
+int launch_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const unsigned char *alt, size_t alt_stride, const unsigned *flags, int n,
+                          size_t frame_bytes, hipStream_t s);
 // deform_pack3.inl's census: sums the 64 atomic slots of each of `nblocks` launches ([block][64][4] u32) into out[block][4] u64 =
 // {fix-up wave-taps, totals[block], samples outside the window, max |offset| as fp32 bits}
 int launch_census_reduce(const unsigned *census, unsigned long long *out, int nblocks, const unsigned long long *totals, hipStream_t s);

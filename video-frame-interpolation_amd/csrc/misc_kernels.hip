@@ -2,6 +2,7 @@
 // boundary, global-average-pool + context folding, and the backward bilinear warp.
 #include "common.h"
 #include "misc_kernels.h"
+#include "scene_elem.h"
 #include <atomic>
 #include <type_traits>
 #include <cstddef>
@@ -1772,6 +1773,162 @@ int launch_preprocess_nv12_resized(const unsigned char *y, size_t y_pitch, size_
                              uv_out ? (size_t)(uintptr_t)uv_out | uvo_pitch | (B > 1 ? uvo_bstride : 0) : 0});
     const dim3 grid((unsigned)((Wd + 63) / 64), (unsigned)((Hd + 31) / 32), (unsigned)B);
     preprocess_nv12_resized_kernel<<<grid, 256, 0, s>>>(a, st, yuv_coef(standard, order));
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Scene cuts decided and applied on the device (include/emavfi.h, "SCENE CUT DEFINITION"; per-element functions: scene_elem.h).
+//   luma_signature_kernel<C>  bytes [B][H][W][C] (C = 1: a Y plane, C = 3: interleaved colour) -> sig [B][32][32] u32, the luma sum of each cell.
+//                             The one pass that touches every byte.  Grid (32 cell rows, 4 groups of 8 cell columns, B): 1152 workgroups for
+//                             nine frames.  A workgroup OWNS the 8 cells it stores - no global atomics, no zeroing beforehand.  A lane takes
+//                             units of 16 pixels on the frame's 16-pixel lattice (so a unit starts on a 16-byte boundary of an aligned row) and
+//                             adds each cell's part of a unit into its own LDS slot [cell][lane] (plain LDS adds, nothing shared); at the end
+//                             32 lanes per cell sum the 256 slots and finish with a wave reduction.  A unit on the edge of the group is read by
+//                             both neighbours, each keeping its own columns.  Two access forms, the same per-element arithmetic:
+//                               WIDE    C 16-byte loads per unit (pointer, pitch and batch stride multiples of 16; only units that end inside the
+//                                       row - pitch padding is never read);
+//                               SCALAR  byte loads: whenever a condition above fails, and for the right remainder of a row.
+//   scene_flags_kernel        one workgroup per pair: sum over the cells of |mean_a - mean_b| -> scores[k], flags[k] = score >= threshold
+//   hold_frames_kernel        grid (32 KiB pieces of a frame, rep, n): a workgroup of an unflagged pair leaves at once; the others copy their
+//                             piece of alt[k] over frame k rep + r, 16 bytes per lane where both frame addresses allow, bytes elsewhere
+// ------------------------------------------------------------------------------------------
+constexpr int SG_CELLS = 8, SG_GROUPS = SCENE_GRID / SG_CELLS;
+struct SigArgs { const unsigned char *src; size_t pitch, bstride; unsigned *sig; int H, W, rgb, wide; };
+
+template <int C>
+__global__ __launch_bounds__(256) void luma_signature_kernel(SigArgs a)
+{
+    __shared__ unsigned slot[SG_CELLS * 256];
+    __shared__ int cb[SG_CELLS + 1];
+    const int tid = threadIdx.x, ci = blockIdx.x, g = blockIdx.y;
+    const size_t b = blockIdx.z;
+    const int y0 = scene_cell_bound(ci, a.H), y1 = scene_cell_bound(ci + 1, a.H);
+    if (tid <= SG_CELLS) cb[tid] = scene_cell_bound(g * SG_CELLS + tid, a.W);
+#pragma unroll
+    for (int k = 0; k < SG_CELLS; ++k) slot[k * 256 + tid] = 0u;
+    __syncthreads();
+    const int xlo = cb[0], xhi = cb[SG_CELLS];   // xhi <= W
+    if (y1 > y0 && xhi > xlo) {                  // uniform over the workgroup
+        const int u0 = xlo >> 4, nu = ((xhi + 15) >> 4) - u0, items = (y1 - y0) * nu;
+        const unsigned char *plane = a.src + b * a.bstride;
+        for (int t = tid; t < items; t += 256) {
+            const int r = t / nu, x0 = (u0 + (t - r * nu)) << 4;
+            const unsigned char *p = plane + (size_t)(y0 + r) * a.pitch + (size_t)x0 * C;
+            unsigned w[4 * C];
+            if (a.wide && x0 + 16 <= a.W) {
+#pragma unroll
+                for (int q = 0; q < C; ++q) {
+                    const uint4 v = reinterpret_cast<const uint4 *>(p)[q];
+                    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+                }
+            } else {
+                const int nb = min(16, a.W - x0) * C;
+#pragma unroll
+                for (int q = 0; q < 4 * C; ++q) w[q] = 0u;
+#pragma unroll
+                for (int k = 0; k < 16 * C; ++k)
+                    if (k < nb) w[k >> 2] |= (unsigned)p[k] << (8 * (k & 3));
+            }
+            int j = 0, hi = cb[1];
+            unsigned acc = 0u;
+#pragma unroll
+            for (int px = 0; px < 16; ++px) {
+                const int x = x0 + px;
+                if (x >= xlo && x < xhi) {
+                    while (x >= hi) {            // ends at j <= 7: x < xhi = cb[8]
+                        slot[j * 256 + tid] += acc;
+                        acc = 0u;
+                        ++j;
+                        hi = cb[j + 1];
+                    }
+                    if constexpr (C == 1) {
+                        acc += (w[px >> 2] >> (8 * (px & 3))) & 0xffu;
+                    } else {
+                        const int k = 3 * px;
+                        acc += scene_luma3((w[k >> 2] >> (8 * (k & 3))) & 0xffu, (w[(k + 1) >> 2] >> (8 * ((k + 1) & 3))) & 0xffu,
+                                           (w[(k + 2) >> 2] >> (8 * ((k + 2) & 3))) & 0xffu, a.rgb);
+                    }
+                }
+            }
+            slot[j * 256 + tid] += acc;
+        }
+    }
+    __syncthreads();
+    const int c = tid >> 5, l = tid & 31;
+    unsigned s = 0u;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += slot[c * 256 + l + 32 * k];
+#pragma unroll
+    for (int off = 16; off >= 1; off >>= 1) s += __shfl_xor(s, off, 32);
+    if (l == 0) a.sig[b * (SCENE_GRID * SCENE_GRID) + ci * SCENE_GRID + g * SG_CELLS + c] = s;
+}
+
+__global__ __launch_bounds__(256) void scene_flags_kernel(const unsigned *__restrict__ sig_a, size_t stride_a, const unsigned *__restrict__ sig_b,
+                                                          size_t stride_b, int H, int W, unsigned threshold, unsigned *__restrict__ flags,
+                                                          unsigned *__restrict__ scores)
+{
+    __shared__ unsigned part[4];
+    const int tid = threadIdx.x;
+    const size_t k = blockIdx.x;
+    const unsigned *sa = sig_a + k * stride_a, *sb = sig_b + k * stride_b;
+    unsigned s = 0u;
+    for (int c = tid; c < SCENE_GRID * SCENE_GRID; c += 256) {
+        const int i = c >> 5, j = c & 31;
+        const unsigned n = (unsigned)(scene_cell_bound(i + 1, H) - scene_cell_bound(i, H)) * (unsigned)(scene_cell_bound(j + 1, W) - scene_cell_bound(j, W));
+        if (n) {
+            const unsigned ma = scene_cell_mean(sa[c], n), mb = scene_cell_mean(sb[c], n);
+            s += ma > mb ? ma - mb : mb - ma;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    if ((tid & 63) == 0) part[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned score = part[0] + part[1] + part[2] + part[3];
+        flags[k] = score >= threshold ? 1u : 0u;
+        if (scores) scores[k] = score;
+    }
+}
+
+constexpr size_t HOLD_PIECE = 32768;   // bytes of a frame per workgroup, a multiple of 16
+__global__ __launch_bounds__(256) void hold_frames_kernel(unsigned char *dst, size_t dst_stride, int rep, const unsigned char *alt, size_t alt_stride,
+                                                          const unsigned *__restrict__ flags, size_t frame_bytes)
+{
+    const size_t k = blockIdx.z;
+    if (!flags[k]) return;
+    unsigned char *d = dst + (k * (size_t)rep + blockIdx.y) * dst_stride;
+    const unsigned char *s = alt + k * alt_stride;
+    const size_t lo = (size_t)blockIdx.x * HOLD_PIECE, hi = lo + HOLD_PIECE < frame_bytes ? lo + HOLD_PIECE : frame_bytes;
+    size_t x = lo + threadIdx.x;
+    if ((((uintptr_t)d | (uintptr_t)s) & 15) == 0) {
+        const size_t nv = (hi - lo) >> 4;
+        for (size_t q = threadIdx.x; q < nv; q += 256) reinterpret_cast<uint4 *>(d + lo)[q] = reinterpret_cast<const uint4 *>(s + lo)[q];
+        x += nv << 4;
+    }
+    for (; x < hi; x += 256) d[x] = s[x];
+}
+
+int launch_luma_signature_u8(const unsigned char *src, size_t pitch, size_t bstride, int B, int H, int W, int C, int order, unsigned *sig, hipStream_t s)
+{
+    SigArgs a{src, pitch, bstride, sig, H, W, order == 1, 0};
+    a.wide = mult_of(16, {(size_t)(uintptr_t)src, pitch, B > 1 ? bstride : 0});
+    const dim3 grid(SCENE_GRID, SG_GROUPS, (unsigned)B);
+    if (C == 1) luma_signature_kernel<1><<<grid, 256, 0, s>>>(a);
+    else luma_signature_kernel<3><<<grid, 256, 0, s>>>(a);
+    return (int)hipGetLastError();
+}
+int launch_scene_flags(const unsigned *sig_a, size_t stride_a, const unsigned *sig_b, size_t stride_b, int n, int H, int W, unsigned threshold,
+                       unsigned *flags, unsigned *scores, hipStream_t s)
+{
+    scene_flags_kernel<<<dim3((unsigned)n), 256, 0, s>>>(sig_a, stride_a, sig_b, stride_b, H, W, threshold, flags, scores);
+    return (int)hipGetLastError();
+}
+int launch_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const unsigned char *alt, size_t alt_stride, const unsigned *flags, int n,
+                          size_t frame_bytes, hipStream_t s)
+{
+    const dim3 grid((unsigned)((frame_bytes + HOLD_PIECE - 1) / HOLD_PIECE), (unsigned)rep, (unsigned)n);
+    hold_frames_kernel<<<grid, 256, 0, s>>>(dst, dst_stride, rep, alt, alt_stride, flags, frame_bytes);
     return (int)hipGetLastError();
 }
 

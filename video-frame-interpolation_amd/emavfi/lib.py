@@ -52,6 +52,9 @@ _PROTOTYPES = {
     "emavfi_preprocess_nv12_resized": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p,
                                                c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 7
                                        + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
+    "emavfi_luma_signature_u8": (c_int, [c_void_p, c_size_t, c_size_t] + [c_int] * 5 + [c_void_p, c_void_p]),
+    "emavfi_scene_flags": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t] + [c_int] * 3 + [ctypes.c_uint, c_void_p, c_void_p, c_void_p]),
+    "emavfi_hold_frames_u8": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p, c_int, c_size_t, c_void_p]),
     "emavfi_conv3x3_workspace_bytes": (c_size_t, [c_int] * 7),
     "emavfi_conv3x3": (c_int, [c_void_p] * 4 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p]),
     "emavfi_deform_conv2d_workspace_bytes": (c_size_t, [c_int] * 6),
@@ -730,3 +733,103 @@ def postprocess_nv12(frames_nchw, standard="bt601", full_range=False, order="bgr
         check(load().emavfi_postprocess_nv12(x.data_ptr(), y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs, B, H, W, st, od, m, s,
                                              1 if denormalize else 0, _stream()), "emavfi_postprocess_nv12")
     return y, uv
+
+
+# ---------------------------------------------------------------- scene cuts on the device (include/emavfi.h, "SCENE CUT DEFINITION")
+SCENE_GRID = 32          # EMAVFI_SCENE_GRID
+SCENE_SIG_WORDS = 1024   # EMAVFI_SCENE_SIG_WORDS
+
+
+def scene_threshold_units(fraction, H, W) -> int:
+    """The u32 threshold of scene_flags for "the mean absolute difference of the two 32 x 32 luma thumbnails reaches `fraction` of full
+    scale": ceil(fraction * 4080 * cells), cells = min(H, 32) * min(W, 32) (a cell's mean is kept in sixteenths of a count: 0..4080)."""
+    import math
+    if not (1 <= int(H) <= RESIZE_MAX_DIM and 1 <= int(W) <= RESIZE_MAX_DIM):
+        raise ValueError(f"scene_threshold_units: H, W must lie in 1..{RESIZE_MAX_DIM}")
+    fraction = float(fraction)
+    if not 0.0 <= fraction <= 1.0:
+        raise ValueError("scene_threshold_units: fraction must lie in 0..1")
+    return int(math.ceil(fraction * (4080 * min(int(H), SCENE_GRID) * min(int(W), SCENE_GRID))))
+
+
+def _u32_rows(t, what, n=None):
+    """(pointer, row stride in words, rows) of an int32 device tensor [rows, 1024] (or [1024]: one row) whose rows are dense"""
+    import torch
+    _require_cuda(t)
+    if t.dtype != torch.int32 or t.dim() not in (1, 2) or t.shape[-1] != SCENE_SIG_WORDS or t.stride(-1) != 1:
+        raise ValueError(f"{what}: an int32 device tensor [n, {SCENE_SIG_WORDS}] with dense rows expected")
+    rows = t.shape[0] if t.dim() == 2 else 1
+    if n is not None and rows not in (1, n):
+        raise ValueError(f"{what}: {n} rows (or one, compared with every pair) expected, got {rows}")
+    return t.data_ptr(), (t.stride(0) if t.dim() == 2 and rows > 1 else 0), rows
+
+
+def luma_signature_u8(frames, order="bgr", out=None, device=None):
+    """uint8 [B,H,W,C] frames, C = 1 (a Y plane) or 3 (interleaved colour, `order` says which byte is red) -> int32 [B,1024]: the luma sum of
+    each cell of a 32 x 32 grid over the frame (the scene-cut definition of include/emavfi.h; the sums fit 31 bits).  `frames`: a device
+    tensor or pinned host memory (`device` names the GPU), rows and batches may be strided.  `out`: a contiguous int32 [B,1024] device tensor
+    to fill - every word is written."""
+    import torch
+    sp, pitch, bs = _byte_image(frames, "luma_signature_u8")
+    B, H, W, C = frames.shape
+    dev = frames.device if frames.is_cuda else torch.device(device if device is not None else "cuda")
+    if out is None:
+        out = torch.empty(B, SCENE_SIG_WORDS, dtype=torch.int32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (B, SCENE_SIG_WORDS) and out.is_contiguous()):
+        raise ValueError(f"luma_signature_u8: out must be a contiguous int32 [B,{SCENE_SIG_WORDS}] device tensor")
+    with torch.cuda.device(dev):
+        check(load().emavfi_luma_signature_u8(sp, pitch, bs, B, H, W, C, _order_code(order), out.data_ptr(), _stream()), "emavfi_luma_signature_u8")
+    return out
+
+
+def scene_flags(sig_a, sig_b, size, threshold, flags=None, scores=None, with_scores=True):
+    """Per pair k: score = sum over the cells of |mean_a - mean_b| of two signatures of `size` = (H, W) frames, flag = score >= threshold
+    (an int in score units: scene_threshold_units).  `sig_a` / `sig_b`: int32 device tensors [n,1024], rows may be strided (a slice with a
+    step); a [1024] or [1,1024] tensor is compared with every pair.  Returns (flags, scores): int32 [n] device tensors (`flags=` / `scores=`
+    fill given ones; with_scores=False passes NULL and returns None for the scores)."""
+    import torch
+    H, W = (int(v) for v in size)
+    pa, sa, na = _u32_rows(sig_a, "scene_flags(sig_a)")
+    pb, sb, nb = _u32_rows(sig_b, "scene_flags(sig_b)")
+    n = max(na, nb)
+    if na not in (1, n) or nb not in (1, n):
+        raise ValueError(f"scene_flags: {na} and {nb} signatures do not pair up")
+    threshold = int(threshold)
+    if not 0 <= threshold < 2 ** 32:
+        raise ValueError("scene_flags: threshold must be a u32 in score units")
+    dev = sig_a.device
+
+    def vec(t, name):
+        if t is None:
+            return torch.empty(n, dtype=torch.int32, device=dev)
+        if not (t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (n,) and t.is_contiguous()):
+            raise ValueError(f"scene_flags: {name} must be a contiguous int32 [{n}] device tensor")
+        return t
+    flags = vec(flags, "flags")
+    scores = vec(scores, "scores") if (with_scores or scores is not None) else None
+    with torch.cuda.device(dev):
+        check(load().emavfi_scene_flags(pa, sa, pb, sb, n, H, W, threshold, flags.data_ptr(), scores.data_ptr() if scores is not None else None,
+                                        _stream()), "emavfi_scene_flags")
+    return flags, scores
+
+
+def hold_frames_u8(dst, alt, flags, rep=1):
+    """For every pair k with flags[k] != 0: frame alt[k] is copied over the frames dst[k * rep : (k + 1) * rep]; everything else is left as it
+    was.  `dst` uint8 [n * rep, ...], `alt` uint8 [n, ...]: device tensors or pinned host memory with the same
+    dense frame shape; their first dimension may be strided (a slice with a step).  `flags`: int32 [n] device tensor (scene_flags)."""
+    import torch
+    for t, what in ((dst, "hold_frames_u8(dst)"), (alt, "hold_frames_u8(alt)")):
+        _pinned_or_cuda(t, what)
+        if t.dtype != torch.uint8 or t.dim() < 2 or t.numel() == 0 or not t[0].is_contiguous():
+            raise ValueError(f"{what}: a non-empty uint8 [frames, ...] tensor with dense frames expected")
+    n, rep = alt.shape[0], int(rep)
+    if rep < 1 or dst.shape[0] != n * rep or tuple(dst.shape[1:]) != tuple(alt.shape[1:]):
+        raise ValueError(f"hold_frames_u8: dst {tuple(dst.shape)} is not rep = {rep} frames of alt's shape {tuple(alt.shape[1:])} per pair ({n} pairs)")
+    if not (flags.is_cuda and flags.dtype == torch.int32 and tuple(flags.shape) == (n,) and flags.is_contiguous()):
+        raise ValueError(f"hold_frames_u8: flags must be a contiguous int32 [{n}] device tensor")
+    fb = dst[0].numel()
+    ds = dst.stride(0) if dst.shape[0] > 1 else fb
+    as_ = alt.stride(0) if n > 1 else fb
+    with torch.cuda.device(flags.device):
+        check(load().emavfi_hold_frames_u8(dst.data_ptr(), ds, rep, alt.data_ptr(), as_, flags.data_ptr(), n, fb, _stream()), "emavfi_hold_frames_u8")
+    return dst

@@ -47,6 +47,15 @@ staged and copied at the source size; everything from the normalised tensor onwa
 frame the reference writes "as read" (:167, which there is the resized frame) and the source frames of ``reference_quirks=False`` are the
 device-resized bytes.  ``pixel_format="nv12"`` needs an even destination H and W.  With neither argument the harness takes frames that
 already have the size the model runs at, exactly as before.
+``scene_threshold=f`` (opt-in, a float in (0, 1]; not in the reference, which interpolates across cuts) holds the earlier frame across a hard
+cut: a pair whose 32 x 32 luma thumbnails differ by at least ``f`` of full scale on average (the scene-cut definition of include/emavfi.h;
+``lib.scene_threshold_units``) yields its earlier frame in place of each of its in-between frames.  The decision is made on the device from the
+staged bytes at their source size (NV12: the Y plane) on the pre lane, and applied on the post lane by overwriting the pair's prediction frames
+before they travel to the host; flags and scores ride to a small pinned buffer behind them and are read after the ``done`` wait the drain
+already performs - no new synchronisation point.  Order and counts of the output do not change; ``scene_cuts`` lists ``(i1, i2, score)`` of
+the flagged pairs of the last ``run`` (global frame indices, in order), ``scene_scores`` every pair's.  Known waste: the forwards of a flagged
+pair (in recursive mode all of its midpoints) are still computed and then overwritten - skipping them would need a read-back before the
+forward is enqueued.
 """
 from __future__ import annotations
 
@@ -63,7 +72,7 @@ class FrameInterpolator:
     def __init__(self, model, interpolation_factor: int = 1, frame_interval: int = 1, batch_pairs: int = 8,
                  reference_quirks: bool = True, mode: str = "reference", device=None, copy_out: bool = True, zero_copy: bool = False,
                  numa: str = "off", pixel_format: str = "bgr24", yuv_standard: str = "bt601", yuv_full_range: bool = False,
-                 scale: Optional[float] = None, size=None):
+                 scale: Optional[float] = None, size=None, scene_threshold: Optional[float] = None):
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
             raise ValueError("interpolation_factor >= 0, frame_interval >= 1, batch_pairs >= 1 required")
         if mode not in ("reference", "recursive"):
@@ -81,6 +90,12 @@ class FrameInterpolator:
             raise ValueError("scale must be positive")
         if size is not None:
             size = self.output_size(0, 0, size=size, pixel_format=pixel_format)   # validates; the source size does not matter here
+        if scene_threshold is not None and (isinstance(scene_threshold, bool) or not isinstance(scene_threshold, (int, float))
+                                            or not 0 < scene_threshold <= 1):
+            raise ValueError("scene_threshold must be None (off) or a float in (0, 1]: the mean absolute thumbnail difference, as a fraction "
+                             "of full scale, at which a pair counts as a cut")
+        self.scene = float(scene_threshold) if scene_threshold is not None else None
+        self.scene_cuts, self.scene_scores = [], []   # (i1, i2, score) of the flagged pairs / of every pair of the last run()
         self.scale, self.size = scale, size
         self._resize = scale is not None or size is not None
         self.pixel_format = pixel_format
@@ -226,6 +241,12 @@ class FrameInterpolator:
                 "consumed": torch.cuda.Event(), "pre": torch.cuda.Event(), "fwd": torch.cuda.Event(), "done": torch.cuda.Event(),
                 "src": torch.cuda.Event(),
             })
+            if self.scene is not None:
+                # signatures of the slot's staged frames; flags (row 0) and scores (row 1) of its pairs, on the device and pinned
+                self._slots[-1].update({"sig": torch.empty(2 * nb, _lib.SCENE_SIG_WORDS, dtype=torch.int32, device=self.device),
+                                        "fs": torch.zeros(2, nb, dtype=torch.int32, device=self.device),
+                                        "h_fs": torch.zeros(2, nb, dtype=torch.int32).pin_memory()})
+        self._scene_units = _lib.scene_threshold_units(self.scene, Hs, Ws) if self.scene is not None else None
         # high-priority lanes: a 9-frame preprocess needs < 1 % of the CUs' time, the priority gets its workgroups dispatched between
         # those of the compute kernels (torch: lower number = higher priority)
         self._pre = _lib.side_stream(self.device, which=2, priority=-1)
@@ -246,6 +267,38 @@ class FrameInterpolator:
             return _lib.preprocess_nv12(y, uv, self.yuv["standard"], self.yuv["full_range"], device=device, out=out, size=size,
                                         resized_out=self._planes(resized) if resized is not None else None)
         return _lib.preprocess_u8(buf, device=device, out=out, size=size, resized_out=resized)
+
+    # ---- scene cuts (include/emavfi.h, "SCENE CUT DEFINITION"): signatures and flags on the pre lane, the hold on the post lane
+    @staticmethod
+    def _run(buf, idx):
+        """buf[idx] as ONE strided view when idx is an arithmetic run with a positive step, else None"""
+        step = idx[1] - idx[0] if len(idx) > 1 else 1
+        if step < 1 or any(idx[k + 1] - idx[k] != step for k in range(len(idx) - 1)):
+            return None
+        return buf[idx[0]:idx[-1] + 1:step]
+
+    def _scene_decide(self, slot, buf, ia, ib):
+        """signatures of the staged frames `buf` (source size; NV12: the Y plane as a 1-channel image of pitch W), then every pair's flag and score"""
+        n, sig = len(ia), slot["sig"][:buf.shape[0]]
+        img = self._planes(buf)[0].unsqueeze(-1) if self.pixel_format == "nv12" else buf
+        _lib.luma_signature_u8(img, out=sig, device=self.device)
+        size = (img.shape[1], img.shape[2])
+        a, b = self._run(sig, ia), self._run(sig, ib)
+        if a is not None and b is not None:
+            _lib.scene_flags(a, b, size, self._scene_units, flags=slot["fs"][0, :n], scores=slot["fs"][1, :n])
+        else:
+            for k in range(n):
+                _lib.scene_flags(sig[ia[k]], sig[ib[k]], size, self._scene_units, flags=slot["fs"][0, k:k + 1], scores=slot["fs"][1, k:k + 1])
+
+    def _scene_hold(self, slot, dst, alt_buf, idx, rep):
+        """flagged pairs: frame alt_buf[idx[k]] over the `rep` frames of pair k in dst"""
+        n, flags = len(idx), slot["fs"][0]
+        alt = self._run(alt_buf, idx)
+        if alt is not None:
+            _lib.hold_frames_u8(dst[:n * rep], alt, flags[:n], rep)
+        else:
+            for k in range(n):
+                _lib.hold_frames_u8(dst[k * rep:(k + 1) * rep], alt_buf[idx[k]:idx[k] + 1], flags[k:k + 1], rep)
 
     def _resized_bytes(self, frame):
         """one source frame (numpy) at the destination size, as the device resizes it"""
@@ -384,6 +437,7 @@ class FrameInterpolator:
                 if f.dtype != np.uint8 or f.ndim != 3 or f.shape != first.shape:
                     raise ValueError("FrameInterpolator.run: same-shape uint8 HWC frames expected")
         self._alloc(first.shape)
+        self.scene_cuts, self.scene_scores = [], []
         main = torch.cuda.current_stream(self.device)
         # ramp-up: with three or more batches to come the FIRST one is half-size - the GPU starts after five staged frames instead of
         # nine, and (64 pairs at batch 8: 4 + 7 x 8 + 4) the last one's drain is half as long; every other batch is full.  Per-sample
@@ -397,6 +451,12 @@ class FrameInterpolator:
             slot["done"].synchronize()            # this batch's frames have been written into the pinned buffers
             pred_h, src_h = slot["h_pred"].numpy(), slot["h_src"].numpy()
             own = (lambda v: v.copy()) if self.copy_out else (lambda v: v)
+            if self.scene is not None:            # written behind the frames, ahead of `done`
+                fs = slot["h_fs"].numpy()
+                for k, (a, b) in enumerate(chunk):
+                    self.scene_scores.append((a, b, int(fs[1, k])))
+                    if fs[0, k]:
+                        self.scene_cuts.append((a, b, int(fs[1, k])))
             for k, (a, _) in enumerate(chunk):
                 if self.mode == "recursive":
                     for j in range(npred):
@@ -419,11 +479,19 @@ class FrameInterpolator:
                 rs = slot["d_rs"][:nup] if slot["d_rs"] is not None else None
                 if self.zero_copy:
                     x = self._pre_kernel(slot["h_in"][:nup], device=self.device, out=slot["x"][:nup], resized=rs)   # distinct frames, read over PCIe, normalised once
+                    if self.scene is not None:
+                        self._scene_decide(slot, slot["h_in"][:nup], ia, ib)
+                        if not self.quirks and rs is None:
+                            # the bytes a held frame is made of are the staged input rows, which the host restages once `consumed` fires
+                            for k in range(n):
+                                slot["d_src"][k].copy_(slot["h_in"][ia[k]], non_blocking=True)
                     slot["consumed"].record(self._pre)
                 else:
                     slot["d_in"][:nup].copy_(slot["h_in"][:nup], non_blocking=True)                       # hipMemcpyAsync pinned -> HBM (SDMA)
                     slot["consumed"].record(self._pre)
                     x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=rs)             # distinct frames, normalised once
+                    if self.scene is not None:
+                        self._scene_decide(slot, slot["d_in"][:nup], ia, ib)
                 slot["pre"].record(self._pre)
                 src_here = self.quirks and not self.zero_copy and all(ia[k + 1] == ia[k] + 1 for k in range(n - 1))
                 if rs is not None:
@@ -453,7 +521,8 @@ class FrameInterpolator:
                         self._post_kernel(x1, True, out=slot["h_src"][:n])
                 else:
                     self._post_kernel(flat, self.quirks, out=slot["d_pred"][:n * npred])
-                    slot["h_pred"][:n * npred].copy_(slot["d_pred"][:n * npred], non_blocking=True)       # HBM -> pinned (SDMA)
+                    if self.scene is None:
+                        slot["h_pred"][:n * npred].copy_(slot["d_pred"][:n * npred], non_blocking=True)   # HBM -> pinned (SDMA)
                     if self.quirks and not src_here:
                         self._post_kernel(x1, True, out=slot["d_src"][:n])
                         slot["h_src"][:n].copy_(slot["d_src"][:n], non_blocking=True)
@@ -461,6 +530,21 @@ class FrameInterpolator:
                         self._post.wait_event(slot["src"])                    # `done` covers both lanes' writes into the pinned buffers
                 if rs is not None:
                     self._post.wait_event(slot["src"])
+                if self.scene is not None:
+                    # every source of a held frame is complete here: d_src / h_src (this lane, or the `src` event above), d_rs and d_in (the
+                    # `pre` event the forward waited for).  The prediction frames of a flagged pair become the bytes emitted as its earlier frame
+                    dst = slot["h_pred"] if self.zero_copy else slot["d_pred"]
+                    if self.quirks:
+                        self._scene_hold(slot, dst, slot["h_src"] if self.zero_copy else slot["d_src"], list(range(n)), npred)
+                    elif rs is not None:
+                        self._scene_hold(slot, dst, rs, ia, npred)
+                    elif self.zero_copy:
+                        self._scene_hold(slot, dst, slot["d_src"], list(range(n)), npred)
+                    else:
+                        self._scene_hold(slot, dst, slot["d_in"], ia, npred)
+                    if not self.zero_copy:
+                        slot["h_pred"][:n * npred].copy_(slot["d_pred"][:n * npred], non_blocking=True)   # HBM -> pinned (SDMA), after the hold
+                    slot["h_fs"].copy_(slot["fs"], non_blocking=True)
                 slot["done"].record(self._post)
             if ci + 1 < len(chunks):                  # host-side staging of the next batch overlaps this batch's compute
                 staged = self._stage(self._slots[(ci + 1) & 1], frames, chunks[ci + 1])
