@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -408,6 +408,51 @@ int emavfi_scene_flags(const unsigned *sig_a, size_t stride_a_words, const unsig
                        unsigned threshold, unsigned *flags, unsigned *scores, void *stream);
 int emavfi_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const unsigned char *alt, size_t alt_stride, const unsigned *flags, int n,
                           size_t frame_bytes, void *stream);
+
+/* Frame metrics on the device: how close is image a (an interpolated frame) to image b (the held-out true frame)?  The reference has no
+ * evaluation script (its README names PSNR and SSIM against held-out ground-truth frames as the way to judge a model and calls an eval.py a
+ * future improvement); this is an addition.  Two byte images stay where they are; a few 64-bit words per image pair come back.
+ *
+ * FRAME METRIC DEFINITION (the one place).  Inputs: two byte images a, b [B][H][W][C], C = 1..4, H and W 1..16384, each side with its own row
+ * pitch and batch stride; every channel is scored on its own.  Host, oracle and device agree bit for bit.
+ *   SSE.  sse[c] = the sum over the H W pixels of (a - b)^2, an unsigned 64-bit integer (at most 255^2 * 16384^2 < 2^46).  PSNR is host
+ *     arithmetic on it: 10 log10(255^2 n / sse) over n samples, inf for sse == 0.
+ *   SSIM follows Wang et al. 2004: an 11 x 11 Gaussian window of sigma 1.5 (EMAVFI_METRICS_WINDOW), K1 = 0.01, K2 = 0.03, L = 255, population
+ *     covariance, only windows that lie wholly inside the image, the mean over the (H - 10)(W - 10) windows.  The weights are quantised so
+ *     that the moments are exact integers: per axis g = {67, 498, 2359, 7167, 13960, 17434, 13960, 7167, 2359, 498, 67}, which is
+ *     floor(g_real 65536 + 0.5) of the normalised Gaussian with the centre raised by one so that the sum is exactly 65536; the 2-D weight is
+ *     w = g[i] g[j], summing to 2^32.  Per window the moments are
+ *         A = sum w a,  B = sum w b,  Axx = sum w a^2,  Ayy = sum w b^2,  Axy = sum w a b.
+ *     After one axis each fits 32 bits unsigned (65025 * 65536 < 2^32); after both each is below 65025 * 2^32 < 2^48, so its conversion to
+ *     double is exact.  The tail runs in IEEE double precision, no contraction, in exactly this operation order:
+ *         a = A 2^-32; b = B 2^-32; axx = Axx 2^-32; ayy = Ayy 2^-32; axy = Axy 2^-32        (exact)
+ *         aa = a a; bb = b b; ab = a b
+ *         sx = axx - aa; sy = ayy - bb; sxy = axy - ab
+ *         num = (2 ab + C1) (2 sxy + C2)
+ *         den = ((aa + bb) + C1) ((sx + sy) + C2)
+ *         m = num / den
+ *         q = (int64) floor(m 4294967296.0)
+ *     with C1, C2 the doubles nearest 6.5025 and 58.5225.  ssimq[c] = the sum of q over the windows, a signed 64-bit integer of magnitude at
+ *     most 2^32 * 16384^2 = 2^60; an integer sum, so it does not depend on the order or grouping of the reduction.  The SSIM of a channel is
+ *     ssimq / (2^32 windows).  With H < 11 or W < 11 there is no window: ssimq = 0 (the Python layer reports nan); this is not an error.
+ *     Against the real-valued-Gaussian SSIM the quantised weights moved the result by at most 4.8e-6 on the four 40 x 56 image pairs of
+ *     tests/test_metrics_cpu.py.
+ *
+ * emavfi_frame_metrics_u8: out [B][C][2] 64-bit words {sse, ssimq} in device or pinned memory.  EVERY one of the B C 2 words is written,
+ *   whatever the buffer held before; the caller zeroes nothing.  `workspace`: at least emavfi_frame_metrics_workspace_bytes(B, H, W, C) bytes
+ *   of device memory (0 from that query: arguments it refuses); it receives each workgroup's partial sums, which a small second launch adds
+ *   - no atomics, and integer sums are the same in any grouping.  Nothing is allocated, nothing synchronises, all work goes on `stream`.
+ * EMAVFI_E_ARG (never an abort): a null pointer, B below 1 (or above 65535), a dimension outside 1..16384, C outside 1..4, a pitch smaller
+ *   than its row, for B > 1 a batch stride smaller than its plane, an `out` or workspace that is not 8-byte aligned, size arithmetic that
+ *   overflows size_t.  EMAVFI_E_WORKSPACE: a workspace that is too small.
+ * a and b are device pointers or pinned (device-mapped) host memory, as for the other u8 entries.  Access width: a workgroup stages its tile of
+ *   an image with 16-byte loads when that image's pointer, pitch and (B > 1) batch stride are multiples of 16 (only units that end inside the
+ *   row: pitch padding is never read), else byte by byte; both forms feed the same per-element functions (csrc/metrics_elem.h). */
+#define EMAVFI_METRICS_WINDOW 11
+size_t emavfi_frame_metrics_workspace_bytes(int B, int H, int W, int C);
+int emavfi_frame_metrics_u8(const unsigned char *a, size_t a_pitch, size_t a_batch_stride, const unsigned char *b, size_t b_pitch,
+                            size_t b_batch_stride, int B, int H, int W, int C, long long *out, void *workspace, size_t workspace_bytes,
+                            void *stream);
 
 /* One conv / conv_block (ema_vfi.py:7-14): Conv2d(k=3, p=1, stride 1 or 2) + activation.
  * x [B,Cin,H,W], weight [Cout,Cin,3,3], bias [Cout], y [B,Cout,ceil(H/stride),ceil(W/stride)]. */

@@ -1525,6 +1525,52 @@ int emavfi_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const 
     return EMAVFI_OK;
 }
 
+// ---- frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION"): every check runs on the host, pointers are looked at last
+static int metrics_shape_check(const char *what, int B, int H, int W, int C)
+{
+    if (B < 1) return fail(EMAVFI_E_ARG, "%s: B must be >= 1", what);
+    if (B > 65535) return fail(EMAVFI_E_ARG, "%s: B = %d is above 65535", what, B);
+    if (const int rc = scene_dims_check(what, H, W); rc != EMAVFI_OK) return rc;
+    if (C < 1 || C > 4) return fail(EMAVFI_E_ARG, "%s: C = %d (C must be 1..4)", what, C);
+    return EMAVFI_OK;
+}
+
+size_t emavfi_frame_metrics_workspace_bytes(int B, int H, int W, int C)
+{
+    if (metrics_shape_check("frame_metrics_workspace_bytes", B, H, W, C) != EMAVFI_OK) return 0;
+    int tx, ty;
+    frame_metrics_tiles(H, W, &tx, &ty);
+    return (size_t)B * C * tx * ty * 2 * sizeof(unsigned long long);   // at most 65535 * 4 * 512 * 512 * 16 < 2^41
+}
+
+int emavfi_frame_metrics_u8(const unsigned char *a, size_t a_pitch, size_t a_batch_stride, const unsigned char *b, size_t b_pitch,
+                            size_t b_batch_stride, int B, int H, int W, int C, long long *out, void *workspace, size_t workspace_bytes,
+                            void *stream)
+{
+    const char *const what = "frame_metrics_u8";
+    if (const int rc = metrics_shape_check(what, B, H, W, C); rc != EMAVFI_OK) return rc;
+    const size_t row = (size_t)W * C;
+    const size_t pitch[2] = {a_pitch, b_pitch}, bstride[2] = {a_batch_stride, b_batch_stride};
+    for (int i = 0; i < 2; ++i) {
+        const char *const side = i ? "b" : "a";
+        if (pitch[i] < row) return fail(EMAVFI_E_ARG, "%s: the pitch of %s, %zu, is smaller than its row of %zu bytes", what, side, pitch[i], row);
+        size_t plane, span;
+        if (__builtin_mul_overflow((size_t)(H - 1), pitch[i], &plane) || __builtin_add_overflow(plane, row, &plane))
+            return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (pitch of %s %zu)", what, side, pitch[i]);
+        if (B > 1 && bstride[i] < plane)
+            return fail(EMAVFI_E_ARG, "%s: the batch stride of %s, %zu, is smaller than its plane", what, side, bstride[i]);
+        if (B > 1 && (__builtin_mul_overflow((size_t)(B - 1), bstride[i], &span) || __builtin_add_overflow(span, plane, &span)))
+            return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (batch stride of %s %zu)", what, side, bstride[i]);
+    }
+    if (!a || !b || !out || !workspace) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
+    if (((uintptr_t)out | (uintptr_t)workspace) & 7) return fail(EMAVFI_E_ARG, "%s: out and the workspace must be 8-byte aligned", what);
+    const size_t need = emavfi_frame_metrics_workspace_bytes(B, H, W, C);
+    if (workspace_bytes < need) return fail(EMAVFI_E_WORKSPACE, "%s: workspace needs %zu bytes, got %zu", what, need, workspace_bytes);
+    EMAVFI_TRY(launch_frame_metrics_u8(a, a_pitch, a_batch_stride, b, b_pitch, b_batch_stride, B, H, W, C, (unsigned long long *)out, (unsigned long long *)workspace,
+                                       (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
 // ---- stage-level entries (diagnostics / parity tests of single operators): one layer, packed into the workspace and run inside one call ----
 // Their plan - the kernel storage type (EMAVFI_F32X3: the f16 kernels on [hi | lo] halves) and, from op_carve, the zero page - and
 // their layer, as the plan of a model lays it out: a bf16 DCN on the LDS-window kernel contracts bf16-rounded weights stored as f16

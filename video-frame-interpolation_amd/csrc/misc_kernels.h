@@ -98,6 +98,11 @@ int launch_scene_flags(const unsigned *sig_a, size_t stride_a, const unsigned *s
                        unsigned *flags, unsigned *scores, hipStream_t s);
 int launch_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const unsigned char *alt, size_t alt_stride, const unsigned *flags, int n,
                           size_t frame_bytes, hipStream_t s);
+// frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION"): arguments already validated; `part` holds 2 u64 per (b, c, tile)
+// of frame_metrics_tiles' tx * ty tiles (32 x 32 windows each; one tile where an axis has no window)
+void frame_metrics_tiles(int H, int W, int *tx, int *ty);
+int launch_frame_metrics_u8(const unsigned char *a, size_t a_pitch, size_t a_bstride, const unsigned char *b, size_t b_pitch, size_t b_bstride, int B,
+                            int H, int W, int C, unsigned long long *out, unsigned long long *part, hipStream_t s);
 // deform_pack3.inl's census: sums the 64 atomic slots of each of `nblocks` launches ([block][64][4] u32) into out[block][4] u64 =
 // {fix-up wave-taps, totals[block], samples outside the window, max |offset| as fp32 bits}
 int launch_census_reduce(const unsigned *census, unsigned long long *out, int nblocks, const unsigned long long *totals, hipStream_t s);

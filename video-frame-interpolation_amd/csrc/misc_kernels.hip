@@ -3,6 +3,7 @@
 #include "common.h"
 #include "misc_kernels.h"
 #include "scene_elem.h"
+#include "metrics_elem.h"
 #include <atomic>
 #include <type_traits>
 #include <cstddef>
@@ -1929,6 +1930,177 @@ int launch_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const 
 {
     const dim3 grid((unsigned)((frame_bytes + HOLD_PIECE - 1) / HOLD_PIECE), (unsigned)rep, (unsigned)n);
     hold_frames_kernel<<<grid, 256, 0, s>>>(dst, dst_stride, rep, alt, alt_stride, flags, frame_bytes);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION"; per-element functions: metrics_elem.h): per image pair and
+// channel the sum of squared differences and the sum of the windows' quantised SSIM.
+//   frame_metrics_kernel   grid (tiles of 32 windows along x, along y, B), 256 threads.  A workgroup OWNS the 32 x 32 windows of its tile and
+//                          the 32 x 32 pixels at the tile's origin (the last tile of an axis: every pixel up to the edge), so each window and
+//                          each SSE pixel is counted exactly once; an image with no window (H or W below 11) is one tile that only sums
+//                          squared differences.  Stages: (1) the tile's 42 x 42 pixels of BOTH images go to LDS as they lie in memory
+//                          (channels interleaved; 192 bytes per row: 42 pixels of 4 channels and up to 15 bytes of alignment slack), with
+//                          16-byte loads where pointer, pitch and batch stride allow and the unit ends inside the row, else byte by byte - pitch
+//                          padding is never read; then per channel (2) the squared differences of the owned pixels and the row pass: a lane
+//                          per (row, window column) writes the five 11-tap sums as u32 words [moment][row][32 columns]; (3) the column pass:
+//                          lane = window column, 8 groups of 4 window rows; a lane walks 14 rows of its column and feeds each word to the (up
+//                          to 4) windows it belongs to, in u64.  The 32 lanes of a half-wave read 32 consecutive words of one row: no bank
+//                          conflict, whatever the row stride; (4) the double-precision tail per window, q summed as int64; (5) integer
+//                          reduction over the workgroup -> part[b][c][tile] = {sse, ssimq}.  Integer sums: the grouping does not matter.
+//   frame_metrics_finish   one workgroup per (b, c) adds the tiles' partial sums -> out[b][c] = {sse, ssimq}: every word of `out` is written
+// ------------------------------------------------------------------------------------------
+constexpr int MT = 32, MROWS = MT + METRICS_HALO, MLROW = 192;
+static_assert(MROWS * 4 + 15 <= MLROW && MLROW % 16 == 0, "a staged row: 42 pixels of 4 channels behind at most 15 bytes of alignment slack");
+struct MetricArgs {
+    const unsigned char *img[2];
+    size_t pitch[2], bstride[2];
+    unsigned long long *part;
+    int H, W, C, wide[2];
+};
+
+template <typename T> __device__ inline T metrics_block_sum(T v, T *red, int tid)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    const T s = red[0] + red[1] + red[2] + red[3];
+    __syncthreads();
+    return s;
+}
+
+__global__ __launch_bounds__(256) void frame_metrics_kernel(MetricArgs p)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char px[2][MROWS * MLROW];
+    __shared__ unsigned rw[5 * MROWS * MT];
+    __shared__ unsigned long long red_u[4];
+    __shared__ long long red_q[4];
+    const int tid = threadIdx.x, C = p.C;
+    const int x0 = blockIdx.x * MT, y0 = blockIdx.y * MT;
+    const int nwx = max(p.W - METRICS_HALO, 0), nwy = max(p.H - METRICS_HALO, 0);
+    const int wx = min(max(nwx - x0, 0), MT), wy = min(max(nwy - y0, 0), MT);       // windows of this tile
+    const int ncols = min(MROWS, p.W - x0), nrows = min(MROWS, p.H - y0);          // staged pixels: >= 1 each
+    const int ow = blockIdx.x + 1 == gridDim.x ? p.W - x0 : MT, oh = blockIdx.y + 1 == gridDim.y ? p.H - y0 : MT;   // owned pixels: <= staged
+    const int rowbytes = p.W * C, bx0 = x0 * C, bx1 = (x0 + ncols) * C;
+    int off[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const unsigned char *base = p.img[i] + (size_t)blockIdx.z * p.bstride[i] + (size_t)y0 * p.pitch[i];
+        if (p.wide[i]) {
+            const int ax0 = bx0 & ~15, nu = (bx1 - ax0 + 15) >> 4;   // <= 12 units
+            off[i] = bx0 - ax0;
+            for (int t = tid; t < nrows * nu; t += 256) {
+                const int r = t / nu, u = t - r * nu, g0 = ax0 + 16 * u;
+                const unsigned char *src = base + (size_t)r * p.pitch[i] + g0;
+                unsigned char *dst = &px[i][r * MLROW + 16 * u];
+                if (g0 + 16 <= rowbytes) {
+                    *reinterpret_cast<uint4 *>(dst) = *reinterpret_cast<const uint4 *>(src);
+                } else {
+                    for (int k = 0; k < rowbytes - g0; ++k) dst[k] = src[k];
+                }
+            }
+        } else {
+            const int nb = bx1 - bx0;   // <= 168
+            off[i] = 0;
+            for (int t = tid; t < nrows * nb; t += 256) {
+                const int r = t / nb, k = t - r * nb;
+                px[i][r * MLROW + k] = base[(size_t)r * p.pitch[i] + bx0 + k];
+            }
+        }
+    }
+    __syncthreads();
+    const int tile = blockIdx.y * gridDim.x + blockIdx.x, ntiles = gridDim.x * gridDim.y;
+    const bool windows = wx > 0 && wy > 0;
+    for (int c = 0; c < C; ++c) {
+        const unsigned char *la = &px[0][off[0] + c], *lb = &px[1][off[1] + c];
+        unsigned long long sse = 0ull;
+        for (int t = tid; t < oh * ow; t += 256) {
+            const int r = t / ow, x = t - r * ow;
+            sse += metrics_sqdiff(la[r * MLROW + x * C], lb[r * MLROW + x * C]);
+        }
+        if (windows) {
+            for (int t = tid; t < (wy + METRICS_HALO) * MT; t += 256) {
+                const int r = t >> 5, x = t & (MT - 1);
+                if (x < wx) {
+                    unsigned m[5];
+                    metrics_row5(la + r * MLROW + x * C, lb + r * MLROW + x * C, C, m);
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) rw[(k * MROWS + r) * MT + x] = m[k];
+                }
+            }
+        }
+        __syncthreads();
+        long long q = 0;
+        const int x = tid & (MT - 1), yb = (tid >> 5) * 4;
+        if (windows && x < wx && yb < wy) {
+            unsigned long long acc[4][5];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int m = 0; m < 5; ++m) acc[k][m] = 0ull;
+#pragma unroll
+            for (int r = 0; r < 4 + METRICS_HALO; ++r) {       // rows yb + r <= 41: inside rw; rows past wy + 9 feed discarded windows only
+                unsigned v[5];
+#pragma unroll
+                for (int m = 0; m < 5; ++m) v[m] = rw[(m * MROWS + yb + r) * MT + x];
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (r - k >= 0 && r - k < METRICS_WIN) {
+#pragma unroll
+                        for (int m = 0; m < 5; ++m) acc[k][m] = metrics_col_tap(acc[k][m], r - k, v[m]);
+                    }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (yb + k < wy) q += metrics_tail(acc[k][0], acc[k][1], acc[k][2], acc[k][3], acc[k][4]);
+        }
+        const unsigned long long sse_all = metrics_block_sum(sse, red_u, tid);
+        const long long q_all = metrics_block_sum(q, red_q, tid);
+        if (tid == 0) {
+            unsigned long long *o = p.part + (((size_t)blockIdx.z * C + c) * ntiles + tile) * 2;
+            o[0] = sse_all;
+            o[1] = (unsigned long long)q_all;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void frame_metrics_finish(const unsigned long long *__restrict__ part, int ntiles, unsigned long long *__restrict__ out)
+{
+    __shared__ unsigned long long red_u[4];
+    __shared__ long long red_q[4];
+    const int tid = threadIdx.x;
+    const unsigned long long *src = part + (size_t)blockIdx.x * ntiles * 2;
+    unsigned long long sse = 0ull;
+    long long q = 0;
+    for (int t = tid; t < ntiles; t += 256) {
+        sse += src[2 * t];
+        q += (long long)src[2 * t + 1];
+    }
+    const unsigned long long sse_all = metrics_block_sum(sse, red_u, tid);
+    const long long q_all = metrics_block_sum(q, red_q, tid);
+    if (tid == 0) {
+        out[(size_t)blockIdx.x * 2] = sse_all;
+        out[(size_t)blockIdx.x * 2 + 1] = (unsigned long long)q_all;
+    }
+}
+
+void frame_metrics_tiles(int H, int W, int *tx, int *ty)
+{
+    *tx = W > METRICS_HALO ? (W - METRICS_HALO + MT - 1) / MT : 1;
+    *ty = H > METRICS_HALO ? (H - METRICS_HALO + MT - 1) / MT : 1;
+}
+int launch_frame_metrics_u8(const unsigned char *a, size_t a_pitch, size_t a_bstride, const unsigned char *b, size_t b_pitch, size_t b_bstride, int B,
+                            int H, int W, int C, unsigned long long *out, unsigned long long *part, hipStream_t s)
+{
+    int tx, ty;
+    frame_metrics_tiles(H, W, &tx, &ty);
+    MetricArgs p{{a, b}, {a_pitch, b_pitch}, {B > 1 ? a_bstride : 0, B > 1 ? b_bstride : 0}, part, H, W, C, {0, 0}};
+    p.wide[0] = mult_of(16, {(size_t)(uintptr_t)a, a_pitch, B > 1 ? a_bstride : 0});
+    p.wide[1] = mult_of(16, {(size_t)(uintptr_t)b, b_pitch, B > 1 ? b_bstride : 0});
+    frame_metrics_kernel<<<dim3((unsigned)tx, (unsigned)ty, (unsigned)B), 256, 0, s>>>(p);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
+    frame_metrics_finish<<<dim3((unsigned)(B * C)), 256, 0, s>>>(part, tx * ty, out);
     return (int)hipGetLastError();
 }
 

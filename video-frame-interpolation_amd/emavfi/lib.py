@@ -55,6 +55,9 @@ _PROTOTYPES = {
     "emavfi_luma_signature_u8": (c_int, [c_void_p, c_size_t, c_size_t] + [c_int] * 5 + [c_void_p, c_void_p]),
     "emavfi_scene_flags": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t] + [c_int] * 3 + [ctypes.c_uint, c_void_p, c_void_p, c_void_p]),
     "emavfi_hold_frames_u8": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p, c_int, c_size_t, c_void_p]),
+    "emavfi_frame_metrics_workspace_bytes": (c_size_t, [c_int] * 4),
+    "emavfi_frame_metrics_u8": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 4
+                                + [c_void_p, c_void_p, c_size_t, c_void_p]),
     "emavfi_conv3x3_workspace_bytes": (c_size_t, [c_int] * 7),
     "emavfi_conv3x3": (c_int, [c_void_p] * 4 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p]),
     "emavfi_deform_conv2d_workspace_bytes": (c_size_t, [c_int] * 6),
@@ -833,3 +836,47 @@ def hold_frames_u8(dst, alt, flags, rep=1):
     with torch.cuda.device(flags.device):
         check(load().emavfi_hold_frames_u8(dst.data_ptr(), ds, rep, alt.data_ptr(), as_, flags.data_ptr(), n, fb, _stream()), "emavfi_hold_frames_u8")
     return dst
+
+
+# ---------------------------------------------------------------- frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION")
+METRICS_WINDOW = 11      # EMAVFI_METRICS_WINDOW
+
+
+def frame_metrics_u8(a, b, out=None, device=None):
+    """Scores image a against image b per channel: uint8 [B,H,W,C] each, C = 1..4 -> int64 [B,C,2] = {sse, ssimq} (the frame-metric definition
+    of include/emavfi.h: the sum of squared differences, and the sum over the 11 x 11 windows of floor(ssim * 2^32)); `psnr` and `ssim` turn
+    the two into the usual figures.  `a` / `b`: device tensors or pinned host memory (`device` names the GPU), rows and batches may be
+    strided, each side on its own.  `out`: a contiguous int64 [B,C,2] device or pinned tensor to fill - every word is written."""
+    import torch
+    ap, apitch, abs_ = _byte_image(a, "frame_metrics_u8(a)")
+    bp, bpitch, bbs = _byte_image(b, "frame_metrics_u8(b)", a.shape)
+    B, H, W, C = a.shape
+    dev = next((t.device for t in (a, b) if t.is_cuda), None) or torch.device(device if device is not None else "cuda")
+    if out is None:
+        out = torch.empty(B, C, 2, dtype=torch.int64, device=dev)
+    else:
+        _pinned_or_cuda(out, "frame_metrics_u8(out=)")
+        if out.dtype != torch.int64 or tuple(out.shape) != (B, C, 2) or not out.is_contiguous():
+            raise ValueError("frame_metrics_u8: out must be a contiguous int64 [B,C,2] tensor")
+    with torch.cuda.device(dev):
+        need = load().emavfi_frame_metrics_workspace_bytes(B, H, W, C)
+        ws = workspace(need, dev)
+        check(load().emavfi_frame_metrics_u8(ap, apitch, abs_, bp, bpitch, bbs, B, H, W, C, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+              "emavfi_frame_metrics_u8")
+    return out
+
+
+def psnr(sse, n) -> float:
+    """10 log10(255^2 n / sse) over n samples; inf for sse == 0.  Pure host arithmetic."""
+    import math
+    sse, n = int(sse), int(n)
+    if sse < 0 or n < 1:
+        raise ValueError("psnr: sse >= 0 and n >= 1 expected")
+    return math.inf if sse == 0 else 10.0 * math.log10(255.0 * 255.0 * n / sse)
+
+
+def ssim(ssimq, H, W) -> float:
+    """ssimq / (2^32 windows) with windows = (H - 10)(W - 10); nan where H or W is below 11 (no window).  Pure host arithmetic."""
+    import math
+    n = max(int(H) - METRICS_WINDOW + 1, 0) * max(int(W) - METRICS_WINDOW + 1, 0)
+    return math.nan if n == 0 else int(ssimq) / (4294967296.0 * n)

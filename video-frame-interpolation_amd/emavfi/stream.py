@@ -56,16 +56,71 @@ already performs - no new synchronisation point.  Order and counts of the output
 the flagged pairs of the last ``run`` (global frame indices, in order), ``scene_scores`` every pair's.  Known waste: the forwards of a flagged
 pair (in recursive mode all of its midpoints) are still computed and then overwritten - skipping them would need a read-back before the
 forward is enqueued.
+``evaluate(frames, every=1)`` scores the model by the held-out protocol instead of emitting frames: every target frame ``t`` is interpolated
+from ``t - 1`` and ``t + 1`` and compared with the true ``t`` on the device (the frame-metric definition of include/emavfi.h: per-channel sum
+of squared differences and 11 x 11 Gaussian-window SSIM); only the metric words travel to the host, behind the ``done`` event the drain
+waits for anyway.
 """
 from __future__ import annotations
 
 import os
-from typing import Iterable, Iterator, List, Optional
+from typing import Iterable, Iterator, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import lib as _lib
+
+
+class FrameScore(NamedTuple):
+    """One held-out target of ``FrameInterpolator.evaluate``: frame ``t`` interpolated from ``t - 1`` and ``t + 1`` against the true ``t``.
+    ``sse`` / ``ssimq``: the device's integers per channel; ``psnr`` / ``ssim``: the figures per channel; ``sse_all`` / ``psnr_all``: over
+    all channels' samples; ``ssim_all``: the mean over the channels (nan below 11 pixels per side)."""
+    t: int
+    sse: Tuple[int, ...]
+    ssimq: Tuple[int, ...]
+    psnr: Tuple[float, ...]
+    ssim: Tuple[float, ...]
+    sse_all: int
+    psnr_all: float
+    ssim_all: float
+
+
+class Evaluation:
+    """What ``FrameInterpolator.evaluate`` returns: ``size`` = (H, W) the frames were scored at, ``channels`` (1 for NV12: the Y plane),
+    ``targets`` = one ``FrameScore`` per target in order, and the clip means ``psnr`` / ``ssim`` of the targets' overall figures (nan for an
+    empty clip).  Iterating or indexing goes over ``targets``."""
+
+    def __init__(self, size, channels, targets=()):
+        self.size, self.channels, self.targets = (int(size[0]), int(size[1])), int(channels), list(targets)
+
+    def add(self, t, words):
+        """words: [channels][2] integers {sse, ssimq} as emavfi_frame_metrics_u8 wrote them"""
+        (H, W), C = self.size, self.channels
+        sse, ssimq = tuple(int(w[0]) for w in words), tuple(int(w[1]) for w in words)
+        ssim = tuple(_lib.ssim(q, H, W) for q in ssimq)
+        self.targets.append(FrameScore(int(t), sse, ssimq, tuple(_lib.psnr(v, H * W) for v in sse), ssim, sum(sse),
+                                       _lib.psnr(sum(sse), H * W * C), sum(ssim) / C))
+
+    def __len__(self):
+        return len(self.targets)
+
+    def __iter__(self):
+        return iter(self.targets)
+
+    def __getitem__(self, k):
+        return self.targets[k]
+
+    @property
+    def psnr(self):
+        return sum(r.psnr_all for r in self.targets) / len(self.targets) if self.targets else float("nan")
+
+    @property
+    def ssim(self):
+        return sum(r.ssim_all for r in self.targets) / len(self.targets) if self.targets else float("nan")
+
+    def __repr__(self):
+        return f"Evaluation({len(self.targets)} targets at {self.size[0]} x {self.size[1]} x {self.channels}: psnr {self.psnr:.3f} dB, ssim {self.ssim:.5f})"
 
 
 class FrameInterpolator:
@@ -110,6 +165,7 @@ class FrameInterpolator:
         if self.device.type != "cuda":
             raise RuntimeError("FrameInterpolator needs the model on a ROCm device (no CPU path)")
         self._shape = None
+        self._per = 0
         self._norm = None
         # False: yield views into the pinned result buffers instead of fresh arrays (valid until the generator is
         # advanced again - enough for a writer that consumes each frame at once; saves a page-faulting 2.8-6 MB
@@ -203,10 +259,27 @@ class FrameInterpolator:
             plan.append(("tail", last, bool(last_roundtrip and reference_quirks)))
         return plan
 
+    @staticmethod
+    def evaluation_plan(n_frames: int, every: int = 1, rank: int = 0, world: int = 1):
+        """What ``evaluate(frames, every, rank, world)`` scores, in order: ``(t, t - 1, t + 1)`` - target ``t`` interpolated from its two
+        neighbours - for this rank's contiguous share (``dist.shard_range``) of the targets ``t = 1, 1 + every, ...`` with ``t <= n_frames - 2``.
+        Concatenating the ranks' plans in rank order gives the single-process plan.  Pure host logic (no device needed)."""
+        from .dist import shard_range
+        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+            raise ValueError("evaluate: every must be an integer >= 1")
+        if n_frames < 0:
+            raise ValueError("evaluate: n_frames must be >= 0")
+        targets = list(range(1, n_frames - 1, every))
+        a, b = shard_range(len(targets), rank, world)
+        return [(t, t - 1, t + 1) for t in targets[a:b]]
+
     # ---- buffers: two slots of pinned host memory the kernels read / write in place, the preprocessed frames of a slot in HBM
-    def _alloc(self, shape):
-        if self._shape == shape:
+    def _alloc(self, shape, per=2):
+        """`per`: staged frames per item of a batch - 2 for run()'s pairs, 3 for evaluate()'s (earlier, target, later); buffers made for
+        evaluate() also serve run()"""
+        if self._shape == shape and self._per >= per:
             return
+        self._per = per
         if self.pixel_format == "nv12":
             Hs, Ws, C = shape[0] * 2 // 3, shape[1], 3   # [H*3/2, W]: Y rows, then the UV rows
         else:
@@ -222,18 +295,18 @@ class FrameInterpolator:
             if self._bound():
                 # pinned and first touched on a thread of the device's node (on the hosts measured the runtime already put pinned
                 # pages on the GPU's node whichever CPU asked: profiles/r09_numa_stream_ab.md)
-                pinned = self._copy_pool().submit(self._pinned_local, [(2 * nb, *fin), (nb * nout, *fs), (nb, *fs)]).result()
+                pinned = self._copy_pool().submit(self._pinned_local, [(per * nb, *fin), (nb * nout, *fs), (nb, *fs)]).result()
             else:
-                pinned = [torch.empty(2 * nb, *fin, dtype=torch.uint8).pin_memory(),
+                pinned = [torch.empty(per * nb, *fin, dtype=torch.uint8).pin_memory(),
                           torch.empty(nb * nout, *fs, dtype=torch.uint8).pin_memory(),
                           torch.empty(nb, *fs, dtype=torch.uint8).pin_memory()]
             self._slots.append({
                 "h_in": pinned[0], "h_pred": pinned[1], "h_src": pinned[2],
-                "x": torch.empty(2 * nb, C, H, W, dtype=torch.float32, device=self.device),
+                "x": torch.empty(per * nb, C, H, W, dtype=torch.float32, device=self.device),
                 # device-side images of the three pinned buffers (the SDMA copies' other end)
-                "d_in": torch.empty(2 * nb, *fin, dtype=torch.uint8, device=self.device),
+                "d_in": torch.empty(per * nb, *fin, dtype=torch.uint8, device=self.device),
                 # the resized bytes of the slot's frames, where frames leave as they arrived (reference_quirks=False) and arrive at another size
-                "d_rs": torch.empty(2 * nb, *fs, dtype=torch.uint8, device=self.device) if self._resize and not self.quirks else None,
+                "d_rs": torch.empty(per * nb, *fs, dtype=torch.uint8, device=self.device) if self._resize and not self.quirks else None,
                 "d_pred": torch.empty(nb * nout, *fs, dtype=torch.uint8, device=self.device),
                 "d_src": torch.empty(nb, *fs, dtype=torch.uint8, device=self.device),
                 # consumed: the preprocess kernel has read h_in (the host may restage it); pre: x is ready; fwd: the forward has read x
@@ -241,9 +314,16 @@ class FrameInterpolator:
                 "consumed": torch.cuda.Event(), "pre": torch.cuda.Event(), "fwd": torch.cuda.Event(), "done": torch.cuda.Event(),
                 "src": torch.cuda.Event(),
             })
+            if per > 2:
+                # evaluate(): the resized bytes of the staged frames whatever reference_quirks says (the ground truth at the size the model
+                # runs at), and the metric words {sse, ssimq} per target and channel, on the device and pinned
+                mc = 1 if self.pixel_format == "nv12" else C
+                self._slots[-1].update({"e_rs": torch.empty(per * nb, *fs, dtype=torch.uint8, device=self.device) if self._resize else None,
+                                        "met": torch.zeros(nb, mc, 2, dtype=torch.int64, device=self.device),
+                                        "h_met": torch.zeros(nb, mc, 2, dtype=torch.int64).pin_memory()})
             if self.scene is not None:
                 # signatures of the slot's staged frames; flags (row 0) and scores (row 1) of its pairs, on the device and pinned
-                self._slots[-1].update({"sig": torch.empty(2 * nb, _lib.SCENE_SIG_WORDS, dtype=torch.int32, device=self.device),
+                self._slots[-1].update({"sig": torch.empty(per * nb, _lib.SCENE_SIG_WORDS, dtype=torch.int32, device=self.device),
                                         "fs": torch.zeros(2, nb, dtype=torch.int32, device=self.device),
                                         "h_fs": torch.zeros(2, nb, dtype=torch.int32).pin_memory()})
         self._scene_units = _lib.scene_threshold_units(self.scene, Hs, Ws) if self.scene is not None else None
@@ -354,10 +434,10 @@ class FrameInterpolator:
 
     def _stage(self, slot, frames, chunk):
         """Copy the distinct frames of `chunk` into the slot's pinned input buffer.
-        Returns (number of staged frames, positions of each pair's first / second frame)."""
+        Returns (number of staged frames, positions of each pair's first / second frame); a chunk of triples: three position lists."""
         order, pos = [], {}
-        for a, b in chunk:
-            for f in (a, b):
+        for item in chunk:
+            for f in item:
                 if f not in pos:
                     pos[f] = len(order)
                     order.append(f)
@@ -374,7 +454,7 @@ class FrameInterpolator:
                 np.copyto(h_in[i], frames[f])
         # positions stay on the host: a device index tensor would be a synchronous pageable copy on the
         # main stream, i.e. the host would block behind the compute it has just enqueued
-        return len(order), [pos[a] for a, _ in chunk], [pos[b] for _, b in chunk]
+        return (len(order), *([pos[item[k]] for item in chunk] for k in range(len(chunk[0]))))
 
     @staticmethod
     def _rows(x, idx):
@@ -410,6 +490,18 @@ class FrameInterpolator:
             levels = (self.factor + 1).bit_length() - 1
             return torch.stack(rec(x1, x2, levels), dim=1)
 
+    def _check_frames(self, frames, first, what):
+        if self.pixel_format == "nv12":
+            for f in frames.values():
+                if f.dtype != np.uint8 or f.ndim != 2 or f.shape != first.shape:
+                    raise ValueError(f"FrameInterpolator.{what}: same-shape uint8 [H*3/2, W] NV12 frames expected")
+            if first.shape[0] % 3 or first.shape[1] % 2:   # H = 2 * rows / 3 is then even
+                raise ValueError(f"FrameInterpolator.{what}: the packed NV12 layout [H*3/2, W] needs even H and W")
+        else:
+            for f in frames.values():
+                if f.dtype != np.uint8 or f.ndim != 3 or f.shape != first.shape:
+                    raise ValueError(f"FrameInterpolator.{what}: same-shape uint8 HWC frames expected")
+
     def run(self, frames, rank: int = 0, world: int = 1) -> Iterator[np.ndarray]:
         """Yields uint8 HWC frames (``pixel_format="nv12"``: uint8 [H*3/2, W] frames) in the order the reference's writer receives them.
 
@@ -426,16 +518,7 @@ class FrameInterpolator:
         pairs = mine
         frames = {i: np.ascontiguousarray(frames[i]) for i in range(lo, hi)}   # this rank's segment only
         first = frames[lo]
-        if self.pixel_format == "nv12":
-            for f in frames.values():
-                if f.dtype != np.uint8 or f.ndim != 2 or f.shape != first.shape:
-                    raise ValueError("FrameInterpolator.run: same-shape uint8 [H*3/2, W] NV12 frames expected")
-            if first.shape[0] % 3 or first.shape[1] % 2:   # H = 2 * rows / 3 is then even
-                raise ValueError("FrameInterpolator.run: the packed NV12 layout [H*3/2, W] needs even H and W")
-        else:
-            for f in frames.values():
-                if f.dtype != np.uint8 or f.ndim != 3 or f.shape != first.shape:
-                    raise ValueError("FrameInterpolator.run: same-shape uint8 HWC frames expected")
+        self._check_frames(frames, first, "run")
         self._alloc(first.shape)
         self.scene_cuts, self.scene_scores = [], []
         main = torch.cuda.current_stream(self.device)
@@ -560,3 +643,81 @@ class FrameInterpolator:
             yield self._post_kernel(self._pre_kernel(src), True).cpu().numpy()[0]
         else:
             yield self._resized_bytes(frames[last]) if self._resize else frames[last]
+
+    def evaluate(self, frames, every: int = 1, rank: int = 0, world: int = 1) -> Evaluation:
+        """Scores the model on a clip by the held-out protocol and returns an ``Evaluation``: every target ``t = 1, 1 + every, ...`` with
+        ``t <= n - 2`` is interpolated from frames ``t - 1`` and ``t + 1`` and compared with the true frame ``t`` (``evaluation_plan``).
+
+        Everything is decided on the device.  The forwards are batched through the same slots, lanes and events as ``run()``
+        (``batch_pairs`` targets per batch); the prediction is turned into bytes by the postprocess kernel with ``denormalize`` off - the
+        model's output lies in [0, 1], and de-normalising it as ``reference_quirks`` does would score the reference's quirk instead of the
+        model - and scored by ``emavfi_frame_metrics_u8`` against the bytes of frame ``t`` as they sit on the device at the size the
+        model runs at (with ``scale`` / ``size``: the device-resized bytes).  ``pixel_format="nv12"``: the Y planes are scored as a
+        one-channel image (PSNR-Y / SSIM-Y); chroma is not scored.  Only the metric words travel to a small pinned buffer, read after the
+        ``done`` wait of the drain; no frame returns to the host.  The staged frames always reach the device by copy (``zero_copy`` is a
+        property of ``run()``'s transport).  ``interpolation_factor``, ``mode``, ``reference_quirks``, ``frame_interval`` and
+        ``scene_threshold`` do not affect ``evaluate``: a target has one midpoint and is never held.
+
+        ``frames`` / ``rank`` / ``world`` as for ``run()``: a rank touches only the frames of its contiguous share of the targets, and
+        the ranks' ``targets`` concatenated in rank order are the single-process result."""
+        if not (hasattr(frames, "__len__") and hasattr(frames, "__getitem__")):
+            frames = list(frames)
+        plan = self.evaluation_plan(len(frames), every, rank, world)
+        if not plan:                               # fewer than three frames, or a rank without a share: nothing is touched, size (0, 0)
+            return Evaluation((0, 0), 1 if self.pixel_format == "nv12" else 3)
+        frames = {i: np.ascontiguousarray(frames[i]) for i in sorted({f for item in plan for f in item})}   # this rank's frames only
+        first = frames[plan[0][1]]
+        self._check_frames(frames, first, "evaluate")
+        self._alloc(first.shape, per=3)
+        nv12 = self.pixel_format == "nv12"
+        H, W = self._dst
+        result = Evaluation((H, W), 1 if nv12 else first.shape[2])
+        main = torch.cuda.current_stream(self.device)
+        bp = self.batch_pairs
+        chunks = [[(a, t, b) for t, a, b in plan[i:i + bp]] for i in range(0, len(plan), bp)]
+
+        def image(buf):
+            """the scored image of frames at the size the model runs at: the Y plane of NV12 frames as one channel"""
+            return buf[:, :H].unsqueeze(-1) if nv12 else buf
+
+        def drain(slot, chunk):
+            slot["done"].synchronize()            # this batch's metric words have been written into the pinned buffer
+            words = slot["h_met"].numpy()
+            for k, (_, t, _) in enumerate(chunk):
+                result.add(t, words[k].tolist())
+
+        staged = self._stage(self._slots[0], frames, chunks[0])
+        prev = None
+        for ci, chunk in enumerate(chunks):
+            slot = self._slots[ci & 1]
+            nup, ia, it, ib = staged
+            n = len(chunk)
+            with torch.cuda.stream(self._pre):
+                self._pre.wait_event(slot["fwd"])
+                self._pre.wait_event(slot["done"])     # also: the metric kernel of batch ci - 2 has read d_in / e_rs
+                rs = slot["e_rs"][:nup] if slot["e_rs"] is not None else None
+                slot["d_in"][:nup].copy_(slot["h_in"][:nup], non_blocking=True)
+                slot["consumed"].record(self._pre)
+                x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=rs)
+                slot["pre"].record(self._pre)
+            main.wait_event(slot["pre"])
+            x1, x2 = self._rows(x, ia), self._rows(x, ib)
+            with torch.no_grad():
+                pred = self.model(x1, x2)                                     # [n, 3, H, W], on the caller's stream
+            slot["fwd"].record(main)
+            with torch.cuda.stream(self._post):
+                self._post.wait_event(slot["fwd"])
+                pred.record_stream(self._post)
+                self._post_kernel(pred, False, out=slot["d_pred"][:n])
+                truth = image(rs if rs is not None else slot["d_in"][:nup])
+                step = it[1] - it[0] if n > 1 else 1                          # the targets' rows are an arithmetic run: frames are staged in order
+                _lib.frame_metrics_u8(image(slot["d_pred"][:n]), truth[it[0]:it[-1] + 1:step], out=slot["met"][:n])
+                slot["h_met"][:n].copy_(slot["met"][:n], non_blocking=True)
+                slot["done"].record(self._post)
+            if ci + 1 < len(chunks):
+                staged = self._stage(self._slots[(ci + 1) & 1], frames, chunks[ci + 1])
+            if prev is not None:
+                drain(*prev)
+            prev = (slot, chunk)
+        drain(*prev)
+        return result
