@@ -317,6 +317,49 @@ int emavfi_postprocess_nv12(const float *frames_nchw, unsigned char *y, size_t y
                             size_t uv_pitch, size_t uv_batch_stride, int B, int H, int W, int standard, int order,
                             const double *mean, const double *std, int denormalize, void *stream);
 
+/* HIGH BIT DEPTH frames, in and out: P010, P012 and P016 - what decoders of HEVC Main10, AV1 10-bit and HDR / UHD material produce.  NV12's
+ * layout with 16-bit little-endian words: a Y plane [H][W] of words and a plane of interleaved U,V word pairs [ceil(H/2)][ceil(W/2)][2], each
+ * plane with its own pointer, row pitch and batch stride, all in BYTES.  `depth` d is 10, 12 or 16; the sample of a word is word >> (16 - d):
+ * the low 16 - d bits are ignored on read and written as zero.  Odd H and W are valid.  The reference has no counterpart (cv2 is 8-bit).
+ *
+ * HIGH BIT DEPTH COLOUR DEFINITION (the one place).  THE PROJECT'S OWN DEFINITION, AS FOR NV12: NO CLAIM OF PARITY WITH ANY OUTSIDE LIBRARY.
+ * Constants: P = 2^d - 1, mid = 2^(d-1); limited range: yoff = 16 2^(d-8), Yr = 219 2^(d-8), Cr = 224 2^(d-8); full range: yoff = 0, Yr = Cr = P.
+ * Standards: the four codes of NV12 plus EMAVFI_YUV_BT2020_LIMITED / _FULL (BT.2020 non-constant luminance: Kr = 0.2627, Kb = 0.0593), which
+ *   only the entries of this section accept: the 8-bit entries and emavfi_yuv_coefficients keep refusing them.
+ * Coefficients: the NV12 formulas above with 255/219 -> P/Yr, 255/224 -> P/Cr, 219/255 -> Yr/P, 224/255 -> Cr/P, each floor(k 2^20 + 0.5) of
+ *   its real value k computed in double.  emavfi_yuv_coefficients_depth (host only) returns them as decode {CY, CVR, CUG, CVG, CUB} and encode
+ *   {YR, YG, YB, UR, UG, UB, VR, VG, VB}; it also takes depth 8, where it returns exactly emavfi_yuv_coefficients' tables.  For
+ *     EMAVFI_YUV_BT2020_LIMITED at depth 10: decode {1224536, 1765394, -197003, -684025, 2252416}
+ *                                            encode {235879, 608777, 53246, -128236, -330964, 459200, 459200, -422268, -36933}
+ * Arithmetic: signed 64-BIT integer fixed point with 20 fractional bits (the worst decode intermediate is 3.6e9 at depth 10 and 2.3e11 at
+ *   depth 16: NV12's 32 bits do not hold it); `>> 20` is floor division by 2^20, clip is to 0..P.
+ *   Decode, per pixel: the chroma pair of pixel (y, x) is (y >> 1, x >> 1); l = max(Y - yoff, 0), u = U - mid, v = V - mid;
+ *     R = clip((CY l + CVR v + 2^19) >> 20), G = clip((CY l + CUG u + CVG v + 2^19) >> 20), B = clip((CY l + CUB u + 2^19) >> 20):
+ *     three d-bit integers, not bytes.
+ *   Encode: Y = clip(((YR R + YG G + YB B + 2^19) >> 20) + yoff) per pixel; chroma from the rounded mean of the 2x2 block of d-bit integers,
+ *     each of r, g, b = (sum of 4 + 2) >> 2, coordinates past the last row / column clamped;
+ *     U = clip(((UR r + UG g + UB b + 2^19) >> 20) + mid), V = clip(((VR r + VG g + VB b + 2^19) >> 20) + mid).
+ * emavfi_preprocess_p010 is DEFINED as fp32 ((float(v) / float(P)) - mean[c]) / std[c] of the decoded integers v: true divisions in that
+ *   order, emavfi_preprocess_u8's arithmetic with 255 -> P.  emavfi_postprocess_p010 is DEFINED as the encode of the integers
+ *   trunc(clip(x std + mean, 0, 1) P) in float64, NaN -> 0, `denormalize` = 0 skipping the affine step: emavfi_postprocess_u8's arithmetic
+ *   with 255 -> P.  `order`, `mean`, `std`: as for NV12.
+ * EMAVFI_E_ARG (never an abort), the message naming the argument: a null pointer; depth outside {10, 12, 16}; a standard outside 0..5; an
+ *   unknown order; y_pitch < 2 W or odd; uv_pitch < 4 ceil(W/2) or no multiple of 4; a Y pointer that is not 2-byte, a UV pointer that is not
+ *   4-byte aligned; for B > 1 a batch stride smaller than its plane (or one that breaks its plane's alignment); a zero std; B, H or W below 1.
+ * The Y and UV pointers are device pointers or pinned (device-mapped) host memory.  Nothing is allocated, nothing synchronises, all work goes
+ *   on `stream`.  Access width: with both word pointers, pitches and batch strides multiples of 16, a 16-byte aligned fp32 pointer and
+ *   W % 4 == 0, every full 2-row x 8-column block moves with 16-byte accesses (two of Y, one of UV, twelve of fp32); everything else (and the
+ *   right / bottom remainders) takes a scalar path with the same per-element arithmetic (csrc/p010_elem.h). */
+#define EMAVFI_YUV_BT2020_LIMITED 4
+#define EMAVFI_YUV_BT2020_FULL 5
+int emavfi_yuv_coefficients_depth(int standard, int depth, int decode[5], int encode[9]);
+int emavfi_preprocess_p010(const void *y, size_t y_pitch, size_t y_batch_stride, const void *uv, size_t uv_pitch, size_t uv_batch_stride,
+                           float *out_nchw, int B, int H, int W, int depth, int standard, int order, const float *mean, const float *std,
+                           void *stream);
+int emavfi_postprocess_p010(const float *frames_nchw, void *y, size_t y_pitch, size_t y_batch_stride, void *uv, size_t uv_pitch,
+                            size_t uv_batch_stride, int B, int H, int W, int depth, int standard, int order, const double *mean,
+                            const double *std, int denormalize, void *stream);
+
 /* Frames resized on the device: the reference's `--scale` step, cv2.resize(frame, (int(w * scale), int(h * scale))), inference.py:46 / :93-94,
  * which it applies to every decoded frame before ToTensor / Normalize.
  *

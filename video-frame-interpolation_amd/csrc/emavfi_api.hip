@@ -1383,6 +1383,69 @@ int emavfi_postprocess_nv12(const float *frames_nchw, unsigned char *y, size_t y
     return EMAVFI_OK;
 }
 
+// ---- 16-bit-word frames (include/emavfi.h, "HIGH BIT DEPTH"): the checks both entries share, in nv12_check's order; sizes are compared in 128 bits
+static int p010_check(const char *what, const void *y, size_t y_pitch, size_t y_bstride, const void *uv, size_t uv_pitch, size_t uv_bstride,
+                      const void *f32, int B, int H, int W, int depth, int standard, int order, const float *mean32, const float *std32,
+                      const double *mean64, const double *std64)
+{
+    typedef unsigned __int128 u128;
+    if (!(mean32 && std32) && !(mean64 && std64)) return fail(EMAVFI_E_ARG, "%s: null mean / std", what);
+    if (B < 1 || H < 1 || W < 1) return fail(EMAVFI_E_ARG, "%s: B, H, W must be >= 1", what);
+    if (depth != 10 && depth != 12 && depth != 16) return fail(EMAVFI_E_ARG, "%s: depth %d is not 10, 12 or 16 (P010, P012, P016)", what, depth);
+    if (standard < EMAVFI_YUV_BT601_LIMITED || standard > EMAVFI_YUV_BT2020_FULL)
+        return fail(EMAVFI_E_ARG, "%s: unknown standard %d (EMAVFI_YUV_BT601_LIMITED .. EMAVFI_YUV_BT2020_FULL)", what, standard);
+    if (order != EMAVFI_ORDER_BGR && order != EMAVFI_ORDER_RGB)
+        return fail(EMAVFI_E_ARG, "%s: unknown order %d (EMAVFI_ORDER_BGR or EMAVFI_ORDER_RGB)", what, order);
+    const size_t y_row = 2 * (size_t)W, uv_row = 4 * (((size_t)W + 1) / 2), uv_rows = ((size_t)H + 1) / 2;
+    if (y_pitch < y_row || (y_pitch & 1)) return fail(EMAVFI_E_ARG, "%s: y_pitch %zu must be even and at least 2 W = %zu bytes", what, y_pitch, y_row);
+    if (uv_pitch < uv_row || (uv_pitch & 3))
+        return fail(EMAVFI_E_ARG, "%s: uv_pitch %zu must be a multiple of 4 and at least 4 * ceil(W / 2) = %zu bytes", what, uv_pitch, uv_row);
+    if (B > 1 && ((u128)y_bstride < (u128)(H - 1) * y_pitch + y_row || (u128)uv_bstride < (u128)(uv_rows - 1) * uv_pitch + uv_row))
+        return fail(EMAVFI_E_ARG, "%s: a batch stride (y %zu, uv %zu) is smaller than its plane", what, y_bstride, uv_bstride);
+    if (B > 1 && ((y_bstride & 1) || (uv_bstride & 3)))
+        return fail(EMAVFI_E_ARG, "%s: a batch stride (y %zu, uv %zu) breaks the alignment of its plane (2 / 4 bytes)", what, y_bstride, uv_bstride);
+    for (int c = 0; c < 3; ++c)
+        if (std32 ? !(std32[c] != 0.0f) : !(std64[c] != 0.0)) return fail(EMAVFI_E_ARG, "%s: std[%d] must be non-zero", what, c);
+    if (!y || !uv || !f32) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
+    if ((uintptr_t)y & 1) return fail(EMAVFI_E_ARG, "%s: the Y pointer must be 2-byte aligned", what);
+    if ((uintptr_t)uv & 3) return fail(EMAVFI_E_ARG, "%s: the UV pointer must be 4-byte aligned", what);
+    if ((uintptr_t)f32 & 3) return fail(EMAVFI_E_ARG, "%s: the fp32 pointer must be 4-byte aligned", what);
+    return EMAVFI_OK;
+}
+
+int emavfi_yuv_coefficients_depth(int standard, int depth, int decode[5], int encode[9])
+{
+    if (standard < EMAVFI_YUV_BT601_LIMITED || standard > EMAVFI_YUV_BT2020_FULL)
+        return fail(EMAVFI_E_ARG, "yuv_coefficients_depth: unknown standard %d (EMAVFI_YUV_BT601_LIMITED .. EMAVFI_YUV_BT2020_FULL)", standard);
+    if (depth != 8 && depth != 10 && depth != 12 && depth != 16)
+        return fail(EMAVFI_E_ARG, "yuv_coefficients_depth: depth %d is not 8, 10, 12 or 16", depth);
+    if (!decode || !encode) return fail(EMAVFI_E_ARG, "yuv_coefficients_depth: null pointer");
+    yuv_coefficients_depth(standard, depth, decode, encode);
+    return EMAVFI_OK;
+}
+
+int emavfi_preprocess_p010(const void *y, size_t y_pitch, size_t y_batch_stride, const void *uv, size_t uv_pitch, size_t uv_batch_stride,
+                           float *out_nchw, int B, int H, int W, int depth, int standard, int order, const float *mean, const float *std,
+                           void *stream)
+{
+    if (const int rc = p010_check("preprocess_p010", y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, out_nchw, B, H, W, depth, standard,
+                                  order, mean, std, nullptr, nullptr); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_preprocess_p010(y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, out_nchw, B, H, W, depth, standard, order, mean,
+                                      std, (hipStream_t)stream), "preprocess_p010");
+    return EMAVFI_OK;
+}
+
+int emavfi_postprocess_p010(const float *frames_nchw, void *y, size_t y_pitch, size_t y_batch_stride, void *uv, size_t uv_pitch,
+                            size_t uv_batch_stride, int B, int H, int W, int depth, int standard, int order, const double *mean,
+                            const double *std, int denormalize, void *stream)
+{
+    if (const int rc = p010_check("postprocess_p010", y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, frames_nchw, B, H, W, depth,
+                                  standard, order, nullptr, nullptr, mean, std); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_postprocess_p010(frames_nchw, y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, B, H, W, depth, standard, order,
+                                       mean, std, denormalize ? 1 : 0, (hipStream_t)stream), "postprocess_p010");
+    return EMAVFI_OK;
+}
+
 // ---- frames resized on the device (include/emavfi.h, "RESIZE DEFINITION"): checks in an order that lets a caller without a device reach each
 static int resize_dims_check(const char *what, int B, int Hs, int Ws, int Hd, int Wd)
 {

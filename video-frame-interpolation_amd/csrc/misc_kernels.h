@@ -84,6 +84,13 @@ int launch_preprocess_nv12(const unsigned char *y, size_t y_pitch, size_t y_bstr
 int launch_postprocess_nv12(const float *src, unsigned char *y, size_t y_pitch, size_t y_bstride, unsigned char *uv, size_t uv_pitch,
                             size_t uv_bstride, int B, int H, int W, int standard, int order, const double *mean, const double *stdv, int denorm,
                             hipStream_t s);
+// 16-bit-word frames, P010 / P012 / P016 (include/emavfi.h, "HIGH BIT DEPTH"): pitches and batch strides in bytes; depth / standard / order
+// already validated.  yuv_coefficients_depth also takes depth 8, where it returns yuv_coefficients' tables
+void yuv_coefficients_depth(int standard, int depth, int dec[5], int enc[9]);   // host only
+int launch_preprocess_p010(const void *y, size_t y_pitch, size_t y_bstride, const void *uv, size_t uv_pitch, size_t uv_bstride, float *dst, int B,
+                           int H, int W, int depth, int standard, int order, const float *mean, const float *stdv, hipStream_t s);
+int launch_postprocess_p010(const float *src, void *y, size_t y_pitch, size_t y_bstride, void *uv, size_t uv_pitch, size_t uv_bstride, int B, int H,
+                            int W, int depth, int standard, int order, const double *mean, const double *stdv, int denorm, hipStream_t s);
 // frames resized on the device (include/emavfi.h, "RESIZE DEFINITION"): pitches and batch strides in bytes, arguments already validated.
 // launch_resize_u8: dst_u8 and / or dst_f32 (dense [B,C,Hd,Wd], normalised with mean / stdv) may be null - one launch writes what is asked for
 int launch_resize_u8(const unsigned char *src, size_t src_pitch, size_t src_bstride, unsigned char *dst_u8, size_t dst_pitch, size_t dst_bstride,

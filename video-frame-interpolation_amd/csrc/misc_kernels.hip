@@ -4,6 +4,7 @@
 #include "misc_kernels.h"
 #include "scene_elem.h"
 #include "metrics_elem.h"
+#include "p010_elem.h"
 #include <atomic>
 #include <type_traits>
 #include <cstddef>
@@ -1494,6 +1495,183 @@ int launch_postprocess_nv12(const float *src, unsigned char *y, size_t y_pitch, 
     const Nv12Planes pl{y_pitch, y_bstride, uv_pitch, uv_bstride};
     postprocess_nv12_kernel<<<nv12_grid(B, H, W), 256, 0, s>>>(src, y, uv, B, H, W, pl, st, yuv_coef(standard, order), denorm,
                                                                nv12_fast_ok(y, uv, src, W, pl) ? 1 : 0);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// 16-bit-word frames, P010 / P012 / P016 (include/emavfi.h, "HIGH BIT DEPTH"): NV12's layout with one little-endian word per sample, the
+// sample in the word's top `depth` bits.  The colour arithmetic is p010_elem.h's (signed 64-bit fixed point, 20 fractional bits; the float
+// side is the u8 kernels' with 255 -> P), the same text the host check runs.
+// One lane owns a block of 2 rows x 8 columns = 4 chroma pairs, in either of two forms with the same per-element arithmetic:
+//   FAST   two 16-byte Y accesses, one 16-byte UV access (each pair serves its four pixels), twelve 16-byte accesses on the fp32 planes.
+//          Conditions (nv12_fast_ok): both word pointers, both pitches and both batch strides are multiples of 16, the fp32 pointer is
+//          16-byte aligned and W % 4 == 0 - and the block lies inside the frame (8 columns, 2 rows).
+//   SCALAR word and dword accesses with the encode's edge clamp: every block when a FAST condition fails, otherwise the right (W % 8)
+//          and bottom (odd H) remainders only.
+// No LDS, no waiting, one block per lane and a grid-stride loop: the launches are short-lived beside the persistent convolutions.
+// ------------------------------------------------------------------------------------------
+void yuv_coefficients_depth(int standard, int depth, int dec[5], int enc[9])
+{
+    const bool full = (standard & 1) != 0;
+    const int matrix = standard >> 1;   // 0 BT.601, 1 BT.709, 2 BT.2020 (non-constant luminance)
+    const double kr = matrix == 2 ? 0.2627 : matrix == 1 ? 0.2126 : 0.299, kb = matrix == 2 ? 0.0593 : matrix == 1 ? 0.0722 : 0.114, kg = 1 - kr - kb;
+    const double P = (double)((1 << depth) - 1), Yr = full ? P : (double)(219 << (depth - 8)), Cr = full ? P : (double)(224 << (depth - 8));
+    const double cy = P / Yr, s = P / Cr, t = Yr / P, sp = Cr / P;
+    const double kd[5] = {cy, 2 * (1 - kr) * s, -2 * kb * (1 - kb) * s / kg, -2 * kr * (1 - kr) * s / kg, 2 * (1 - kb) * s};
+    const double ke[9] = {kr * t, kg * t, kb * t,
+                          -kr / (2 * (1 - kb)) * sp, -kg / (2 * (1 - kb)) * sp, 0.5 * sp,
+                          0.5 * sp, -kg / (2 * (1 - kr)) * sp, -kb / (2 * (1 - kr)) * sp};
+    for (int i = 0; i < 5; ++i) dec[i] = (int)floor(kd[i] * 1048576.0 + 0.5);
+    for (int i = 0; i < 9; ++i) enc[i] = (int)floor(ke[i] * 1048576.0 + 0.5);
+}
+static P010Coef p010_coef(int standard, int depth, int order)
+{
+    P010Coef k{};
+    yuv_coefficients_depth(standard, depth, k.dec, k.enc);
+    p010_constants(depth, (standard & 1) == 0, k);
+    k.rgb = order == 1;
+    return k;
+}
+
+__global__ __launch_bounds__(256) void preprocess_p010_kernel(const unsigned char *__restrict__ ysrc, const unsigned char *__restrict__ uvsrc,
+                                                              float *__restrict__ dst, int B, int H, int W, Nv12Planes pl, Stats4 st,
+                                                              P010Coef k, int fast)
+{
+    const size_t nbx = ((size_t)W + 7) / 8, nby = ((size_t)H + 1) / 2, plane = (size_t)H * W, total = (size_t)B * nby * nbx;
+    const float P = (float)k.P;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = i / (nby * nbx), rem = i - b * nby * nbx, by = rem / nbx;
+        const int y0 = (int)by * 2, x0 = (int)(rem - by * nbx) * 8;
+        const unsigned char *yp = ysrc + b * pl.y_bstride + (size_t)y0 * pl.y_pitch + (size_t)x0 * 2;
+        const unsigned char *up = uvsrc + b * pl.uv_bstride + by * pl.uv_pitch + (size_t)x0 * 2;   // pair x0 / 2 starts at byte 2 x0
+        float *o = dst + b * 3 * plane + (size_t)y0 * W + x0;
+        if (fast && x0 + 8 <= W && y0 + 2 <= H) {
+            const uint4 uvq = *reinterpret_cast<const uint4 *>(up);
+            const unsigned uvw[4] = {uvq.x, uvq.y, uvq.z, uvq.w};   // one pair per dword: U low, V high
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const uint4 yq = *reinterpret_cast<const uint4 *>(yp + (size_t)r * pl.y_pitch);
+                const unsigned yw[4] = {yq.x, yq.y, yq.z, yq.w};    // two pixels per dword
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {   // 4 pixels = 2 chroma pairs = one 16-byte access of each fp32 plane
+                    f32x4 out[3];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int p = q * 4 + j;
+                        const unsigned pair = uvw[p >> 1];
+                        int ch[3];
+                        p010_decode(p010_sample(yw[p >> 1] >> (16 * (p & 1)), k), p010_sample(pair, k), p010_sample(pair >> 16, k), k, ch);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) out[c][j] = p010_norm(ch[c], P, st.mean[c], st.stdv[c]);
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4 *>(o + c * plane + (size_t)r * W + q * 4) = out[c];
+                }
+            }
+            continue;
+        }
+        const int nx = min(8, W - x0), ny = min(2, H - y0);
+        for (int x = 0; x < nx; ++x) {
+            const unsigned short *pr = reinterpret_cast<const unsigned short *>(up) + (x & ~1);
+            const int U = p010_sample(pr[0], k), V = p010_sample(pr[1], k);
+            for (int r = 0; r < ny; ++r) {
+                int ch[3];
+                p010_decode(p010_sample(*reinterpret_cast<const unsigned short *>(yp + (size_t)r * pl.y_pitch + 2 * x), k), U, V, k, ch);
+                for (int c = 0; c < 3; ++c) o[c * plane + (size_t)r * W + x] = p010_norm(ch[c], P, st.mean[c], st.stdv[c]);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void postprocess_p010_kernel(const float *__restrict__ src, unsigned char *__restrict__ ydst,
+                                                               unsigned char *__restrict__ uvdst, int B, int H, int W, Nv12Planes pl,
+                                                               Stats4d st, P010Coef k, int denorm, int fast)
+{
+    const size_t nbx = ((size_t)W + 7) / 8, nby = ((size_t)H + 1) / 2, plane = (size_t)H * W, total = (size_t)B * nby * nbx;
+    const double P = (double)k.P;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = i / (nby * nbx), rem = i - b * nby * nbx, by = rem / nbx;
+        const int y0 = (int)by * 2, x0 = (int)(rem - by * nbx) * 8;
+        unsigned char *yp = ydst + b * pl.y_bstride + (size_t)y0 * pl.y_pitch + (size_t)x0 * 2;
+        unsigned char *up = uvdst + b * pl.uv_bstride + by * pl.uv_pitch + (size_t)x0 * 2;
+        const float *s = src + b * 3 * plane;
+        if (fast && x0 + 8 <= W && y0 + 2 <= H) {
+            unsigned yw[2][4], uvw[4];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                int v[2][4][3];   // [row][pixel][channel]
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const f32x4 x = *reinterpret_cast<const f32x4 *>(s + c * plane + (size_t)(y0 + r) * W + x0 + q * 4);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v[r][j][c] = p010_quant(x[j], st.mean[c], st.stdv[c], denorm, P);
+                    }
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int h = 0; h < 2; ++h)   // the low bits of every word: zero
+                        yw[r][q * 2 + h] = ((unsigned)p010_luma(v[r][2 * h], k) << k.shift) | ((unsigned)p010_luma(v[r][2 * h + 1], k) << (k.shift + 16));
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    int sum[3], U, V;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) sum[c] = v[0][2 * p][c] + v[0][2 * p + 1][c] + v[1][2 * p][c] + v[1][2 * p + 1][c];
+                    p010_chroma(sum, k, U, V);
+                    uvw[q * 2 + p] = ((unsigned)U << k.shift) | ((unsigned)V << (k.shift + 16));
+                }
+            }
+            *reinterpret_cast<uint4 *>(yp) = make_uint4(yw[0][0], yw[0][1], yw[0][2], yw[0][3]);
+            *reinterpret_cast<uint4 *>(yp + pl.y_pitch) = make_uint4(yw[1][0], yw[1][1], yw[1][2], yw[1][3]);
+            *reinterpret_cast<uint4 *>(up) = make_uint4(uvw[0], uvw[1], uvw[2], uvw[3]);
+            continue;
+        }
+        const int nx = min(8, W - x0);
+        for (int x = 0; x < nx; x += 2) {
+            int sum[3] = {0, 0, 0}, U, V;
+            for (int r = 0; r < 2; ++r)
+                for (int dx = 0; dx < 2; ++dx) {
+                    const int yy = min(y0 + r, H - 1), xx = min(x0 + x + dx, W - 1);   // past the last row / column: clamped
+                    int ch[3];
+                    for (int c = 0; c < 3; ++c) {
+                        ch[c] = p010_quant(s[c * plane + (size_t)yy * W + xx], st.mean[c], st.stdv[c], denorm, P);
+                        sum[c] += ch[c];
+                    }
+                    if (yy == y0 + r && xx == x0 + x + dx)
+                        *reinterpret_cast<unsigned short *>(yp + (size_t)r * pl.y_pitch + 2 * (x + dx)) = (unsigned short)(p010_luma(ch, k) << k.shift);
+                }
+            p010_chroma(sum, k, U, V);
+            unsigned short *pr = reinterpret_cast<unsigned short *>(up) + x;
+            pr[0] = (unsigned short)(U << k.shift);
+            pr[1] = (unsigned short)(V << k.shift);
+        }
+    }
+}
+
+static int p010_grid(int B, int H, int W)
+{
+    const size_t lanes = (size_t)B * (((size_t)H + 1) / 2) * (((size_t)W + 7) / 8);
+    return (int)std::min<size_t>((lanes + 255) / 256, (size_t)65535 * 4);
+}
+int launch_preprocess_p010(const void *y, size_t y_pitch, size_t y_bstride, const void *uv, size_t uv_pitch, size_t uv_bstride, float *dst, int B,
+                           int H, int W, int depth, int standard, int order, const float *mean, const float *stdv, hipStream_t s)
+{
+    Stats4 st{};
+    for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
+    const Nv12Planes pl{y_pitch, y_bstride, uv_pitch, uv_bstride};
+    preprocess_p010_kernel<<<p010_grid(B, H, W), 256, 0, s>>>((const unsigned char *)y, (const unsigned char *)uv, dst, B, H, W, pl, st,
+                                                              p010_coef(standard, depth, order), nv12_fast_ok(y, uv, dst, W, pl) ? 1 : 0);
+    return (int)hipGetLastError();
+}
+int launch_postprocess_p010(const float *src, void *y, size_t y_pitch, size_t y_bstride, void *uv, size_t uv_pitch, size_t uv_bstride, int B, int H,
+                            int W, int depth, int standard, int order, const double *mean, const double *stdv, int denorm, hipStream_t s)
+{
+    Stats4d st{};
+    for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
+    const Nv12Planes pl{y_pitch, y_bstride, uv_pitch, uv_bstride};
+    postprocess_p010_kernel<<<p010_grid(B, H, W), 256, 0, s>>>(src, (unsigned char *)y, (unsigned char *)uv, B, H, W, pl, st,
+                                                               p010_coef(standard, depth, order), denorm, nv12_fast_ok(y, uv, src, W, pl) ? 1 : 0);
     return (int)hipGetLastError();
 }
 

@@ -47,6 +47,11 @@ _PROTOTYPES = {
                                + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
     "emavfi_postprocess_nv12": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 5
                                 + [POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int, c_void_p]),
+    "emavfi_yuv_coefficients_depth": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "emavfi_preprocess_p010": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p] + [c_int] * 6
+                               + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
+    "emavfi_postprocess_p010": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 6
+                                + [POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int, c_void_p]),
     "emavfi_resize_u8": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 6 + [c_void_p]),
     "emavfi_preprocess_u8_resized": (c_int, [c_void_p] * 3 + [c_int] * 6 + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
     "emavfi_preprocess_nv12_resized": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p,
@@ -636,11 +641,16 @@ def _order_code(order) -> int:
         raise ValueError(f"order must be 'bgr' or 'rgb', got {order!r}") from None
 
 
-def yuv_coefficients(standard="bt601", full_range=False):
+def yuv_coefficients(standard="bt601", full_range=False, depth=8):
     """The fixed-point tables of the colour definition (include/emavfi.h): (decode [CY, CVR, CUG, CVG, CUB],
-    encode [YR, YG, YB, UR, UG, UB, VR, VG, VB]), each floor(k * 2^20 + 0.5).  Host only."""
+    encode [YR, YG, YB, UR, UG, UB, VR, VG, VB]), each floor(k * 2^20 + 0.5).  Host only.  `depth` 10, 12 or 16: the tables of the
+    high-bit-depth definition, which also knows "bt2020"."""
     dec, enc = (c_int * 5)(), (c_int * 9)()
-    check(load().emavfi_yuv_coefficients(yuv_standard_code(standard, full_range), dec, enc), "emavfi_yuv_coefficients")
+    if depth == 8:
+        check(load().emavfi_yuv_coefficients(yuv_standard_code(standard, full_range), dec, enc), "emavfi_yuv_coefficients")
+    else:
+        check(load().emavfi_yuv_coefficients_depth(yuv_standard_code_deep(standard, full_range), _depth(depth), dec, enc),
+              "emavfi_yuv_coefficients_depth")
     return list(dec), list(enc)
 
 
@@ -737,6 +747,128 @@ def postprocess_nv12(frames_nchw, standard="bt601", full_range=False, order="bgr
                                              1 if denormalize else 0, _stream()), "emavfi_postprocess_nv12")
     return y, uv
 
+
+# ---------------------------------------------------------------- 16-bit-word frames, P010 / P012 / P016 (include/emavfi.h, "HIGH BIT DEPTH")
+YUV_STANDARDS_DEEP = {**YUV_STANDARDS, ("bt2020", False): 4, ("bt2020", True): 5}         # EMAVFI_YUV_*, BT.2020 included
+DEPTHS = {"p010": 10, "p012": 12, "p016": 16}                                             # pixel format -> bits per sample
+_word = None
+
+
+def yuv_standard_code_deep(standard="bt601", full_range=False) -> int:
+    """the standard's code for the high-bit-depth entries, the only ones that accept BT.2020"""
+    try:
+        return YUV_STANDARDS_DEEP[(str(standard).lower(), bool(full_range))]
+    except KeyError:
+        raise ValueError(f"yuv standard must be 'bt601', 'bt709' or 'bt2020', got {standard!r}") from None
+
+
+def _depth(depth) -> int:
+    if isinstance(depth, bool) or depth not in (10, 12, 16):
+        raise ValueError(f"depth must be 10, 12 or 16 (P010, P012, P016), got {depth!r}")
+    return int(depth)
+
+
+def word_dtype():
+    """the torch dtype of a 16-bit sample word: torch.uint16 where this torch can allocate, view and copy it, else torch.int16 (the same
+    bits; the kernels only ever see the pointer)"""
+    global _word
+    if _word is None:
+        import torch
+        try:
+            t = torch.zeros(4, dtype=torch.uint16)
+            torch.empty(4, dtype=torch.uint16).copy_(t)
+            assert t.view(torch.uint8).numel() == 8 and t.numpy().dtype.itemsize == 2
+            _word = torch.uint16
+        except Exception:
+            _word = torch.int16
+    return _word
+
+
+def _words(t, device):
+    """a numpy uint16 array becomes a device tensor of words (one upload); tensors pass through"""
+    import numpy as np
+    import torch
+    if isinstance(t, np.ndarray):
+        if t.dtype != np.uint16:
+            raise ValueError("numpy planes must be uint16")
+        dev = torch.device(device if device is not None else "cuda")
+        return torch.from_numpy(np.ascontiguousarray(t).view(np.int16)).to(dev).view(word_dtype())
+    return t
+
+
+def _p010_planes(y, uv, what):
+    """Shapes, pitches and batch strides (BYTES) of a Y [B,H,W] / UV [B,ceil(H/2),ceil(W/2),2] pair of 16-bit tensors; rows and batches
+    may be strided, the innermost dimensions must be dense."""
+    for t in (y, uv):
+        _pinned_or_cuda(t, what)
+    if y.element_size() != 2 or uv.element_size() != 2 or y.dtype.is_floating_point or uv.dtype.is_floating_point or y.dim() != 3 or uv.dim() != 4:
+        raise ValueError(f"{what}: 16-bit integer y [B,H,W] and uv [B,ceil(H/2),ceil(W/2),2] expected (torch.uint16 or torch.int16)")
+    B, H, W = y.shape
+    H2, W2 = (H + 1) // 2, (W + 1) // 2
+    if tuple(uv.shape) != (B, H2, W2, 2):
+        raise ValueError(f"{what}: uv must be [B,ceil(H/2),ceil(W/2),2] = {(B, H2, W2, 2)}, got {tuple(uv.shape)}")
+    if min(B, H, W) < 1:
+        raise ValueError(f"{what}: empty frames")
+    if y.is_cuda != uv.is_cuda or (y.is_cuda and y.device != uv.device):
+        raise ValueError(f"{what}: y and uv must live in the same memory")
+    if (W > 1 and y.stride(2) != 1) or uv.stride(3) != 1 or (W2 > 1 and uv.stride(2) != 2):
+        raise ValueError(f"{what}: the innermost dimensions of y and uv must be dense (only rows and batches may be strided)")
+    y_pitch = 2 * (y.stride(1) if H > 1 else W)
+    uv_pitch = 2 * (uv.stride(1) if H2 > 1 else 2 * W2)
+    y_bs = 2 * y.stride(0) if B > 1 else y_pitch * H
+    uv_bs = 2 * uv.stride(0) if B > 1 else uv_pitch * H2
+    return B, H, W, y_pitch, y_bs, uv_pitch, uv_bs
+
+
+def preprocess_p010(y, uv, depth=10, standard="bt601", full_range=False, order="bgr", mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None,
+                    out=None):
+    """P010 / P012 / P016 frames (`depth` 10 / 12 / 16) -> fp32 [B,3,H,W]: ((v / P) - mean) / std of the decoded `depth`-bit integers
+    (include/emavfi.h, "HIGH BIT DEPTH").  `y` [B,H,W] and `uv` [B,ceil(H/2),ceil(W/2),2] hold one 16-bit word per sample, the sample in
+    the word's top bits: device tensors or pinned host tensors (read in place over PCIe; `device` names the GPU) of `word_dtype()` or
+    torch.int16, strided in their row and batch dimensions as for preprocess_nv12; numpy uint16 arrays are uploaded first.  `standard`
+    also takes "bt2020"."""
+    import torch
+    y, uv = _words(y, device), _words(uv, device)
+    B, H, W, yp, ybs, uvp, uvbs = _p010_planes(y, uv, "preprocess_p010")
+    d, st, od = _depth(depth), yuv_standard_code_deep(standard, full_range), _order_code(order)
+    dev = y.device if y.is_cuda else torch.device(device if device is not None else "cuda")
+    m, s = _stats(mean, std, 3)
+    if out is None:
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, H, W) and out.is_contiguous()):
+        raise ValueError("preprocess_p010: out must be a contiguous fp32 [B,3,H,W] device tensor")
+    with torch.cuda.device(dev):
+        check(load().emavfi_preprocess_p010(y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs, out.data_ptr(), B, H, W, d, st, od, m, s, _stream()),
+              "emavfi_preprocess_p010")
+    return out
+
+
+def postprocess_p010(frames_nchw, depth=10, standard="bt601", full_range=False, order="bgr", denormalize=True, mean=IMAGENET_MEAN,
+                     std=IMAGENET_STD, out=None):
+    """fp32 [B,3,H,W] -> P010 / P012 / P016 planes (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]) of 16-bit words: the encode of the integers
+    trunc(clip(x std + mean, 0, 1) P) (include/emavfi.h, "HIGH BIT DEPTH"); the low 16 - depth bits of every word are zero.
+    `out=(y, uv)`: device or pinned host tensors to fill, strided as for preprocess_p010; bytes between the rows of a pitched destination
+    are left as they were.  Without `out` the planes are dense device tensors of `word_dtype()`."""
+    import torch
+    _require_cuda(frames_nchw)
+    x = _f32c(frames_nchw)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError("postprocess_p010: [B,3,H,W] tensor expected")
+    B, _, H, W = x.shape
+    d, st, od = _depth(depth), yuv_standard_code_deep(standard, full_range), _order_code(order)
+    m, s = _stats(mean, std, 3, ctypes.c_double)
+    if out is None:
+        y = torch.empty(B, H, W, dtype=word_dtype(), device=x.device)
+        uv = torch.empty(B, (H + 1) // 2, (W + 1) // 2, 2, dtype=word_dtype(), device=x.device)
+    else:
+        y, uv = out
+    *shape, yp, ybs, uvp, uvbs = _p010_planes(y, uv, "postprocess_p010(out=)")
+    if tuple(shape) != (B, H, W):
+        raise ValueError(f"postprocess_p010: out must be (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]) for frames {(B, H, W)}")
+    with torch.cuda.device(x.device):
+        check(load().emavfi_postprocess_p010(x.data_ptr(), y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs, B, H, W, d, st, od, m, s,
+                                             1 if denormalize else 0, _stream()), "emavfi_postprocess_p010")
+    return y, uv
 
 # ---------------------------------------------------------------- scene cuts on the device (include/emavfi.h, "SCENE CUT DEFINITION")
 SCENE_GRID = 32          # EMAVFI_SCENE_GRID

@@ -40,6 +40,12 @@ layout video decoders produce - uint8 ``[H*3/2, W]``: H rows of Y, then H/2 rows
 slots and the SDMA copies move 1.5 bytes per pixel instead of 3.  Decode and encode run inside the device kernels
 (emavfi_preprocess_nv12 / _postprocess_nv12, colour definition: include/emavfi.h); ``yuv_standard`` / ``yuv_full_range`` pick one of the four
 standards.  Order, counts and scheduling are the same; a round-tripped source frame is decode -> normalise -> denormalise -> encode.
+``pixel_format="p010"`` / ``"p012"`` / ``"p016"`` (opt-in) is the same layout with one 16-bit word per sample, the sample in the word's top
+10 / 12 / 16 bits - what decoders of 10-bit and HDR material produce: frames in and out are numpy uint16 ``[H*3/2, W]``, even H and W.  Nothing
+is crushed to 8 bits on the way: emavfi_preprocess_p010 / _postprocess_p010 decode to and encode from ``depth``-bit integers (the high-bit-depth
+definition of include/emavfi.h); ``yuv_standard`` additionally takes ``"bt2020"`` for these formats only.  The slots stay bytes, with rows of
+2 W bytes, and are reinterpreted as words at the kernel boundary; staging, copies, order and counts are NV12's.  ``scale`` / ``size``,
+``scene_threshold`` and ``evaluate()`` are refused with these formats: the resize, signature and metric kernels read bytes.
 ``scale=s`` (the reference's ``--scale``, inference.py:93-94: frames become ``(int(H * s), int(W * s))``) or ``size=(Hd, Wd)`` (mutually
 exclusive; opt-in) resizes every frame on the device, inside the launch that normalises it (emavfi_preprocess_u8_resized /
 _preprocess_nv12_resized; the resize definition is the project's own, include/emavfi.h - no byte parity with cv2 is claimed).  Frames are
@@ -124,6 +130,8 @@ class Evaluation:
 
 
 class FrameInterpolator:
+    _depth = 0   # bits per sample of a 16-bit-word pixel format ("p010": 10, ...); 0 for the byte formats
+
     def __init__(self, model, interpolation_factor: int = 1, frame_interval: int = 1, batch_pairs: int = 8,
                  reference_quirks: bool = True, mode: str = "reference", device=None, copy_out: bool = True, zero_copy: bool = False,
                  numa: str = "off", pixel_format: str = "bgr24", yuv_standard: str = "bt601", yuv_full_range: bool = False,
@@ -136,9 +144,19 @@ class FrameInterpolator:
             raise ValueError("recursive midpoints need interpolation_factor = 2^k - 1 (1, 3, 7, ...)")
         if numa not in ("off", "auto"):
             raise ValueError("numa must be 'off' or 'auto'")
-        if pixel_format not in ("bgr24", "nv12"):
-            raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames) or 'nv12' (uint8 [H*3/2, W] frames)")
-        _lib.yuv_standard_code(yuv_standard, yuv_full_range)   # raises on an unknown standard
+        if pixel_format not in ("bgr24", "nv12", *_lib.DEPTHS):
+            raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames), 'nv12' (uint8 [H*3/2, W] frames) or 'p010' / 'p012' / 'p016' "
+                             "(uint16 [H*3/2, W] frames)")
+        self._depth = _lib.DEPTHS.get(pixel_format, 0)         # bits per sample of a 16-bit-word format, 0 for the byte formats
+        if self._depth:
+            _lib.yuv_standard_code_deep(yuv_standard, yuv_full_range)   # raises on an unknown standard; knows "bt2020"
+            if scale is not None or size is not None:
+                raise ValueError(f"pixel_format={pixel_format!r} with scale / size: the resize kernels read bytes (16-bit frames are not resized)")
+            if scene_threshold is not None:
+                raise ValueError(f"pixel_format={pixel_format!r} with scene_threshold: the signature kernel reads bytes (16-bit frames are not "
+                                 "scanned for cuts)")
+        else:
+            _lib.yuv_standard_code(yuv_standard, yuv_full_range)   # raises on an unknown standard
         if scale is not None and size is not None:
             raise ValueError("scale and size are mutually exclusive")
         if scale is not None and not scale > 0:
@@ -280,14 +298,17 @@ class FrameInterpolator:
         if self._shape == shape and self._per >= per:
             return
         self._per = per
-        if self.pixel_format == "nv12":
+        if self._depth:
+            Hs, Ws, C = shape[0] * 2 // 3, shape[1] // 2, 3   # the bytes of [H*3/2, W] words: rows of 2 W bytes
+        elif self.pixel_format == "nv12":
             Hs, Ws, C = shape[0] * 2 // 3, shape[1], 3   # [H*3/2, W]: Y rows, then the UV rows
         else:
             Hs, Ws, C = shape
         fin = tuple(shape)                               # a frame as it arrives: [Hs, Ws, C] or [Hs*3/2, Ws]
         H, W = self.output_size(Hs, Ws, self.scale, self.size, self.pixel_format)
         self._dst = (H, W)
-        fs = (H * 3 // 2, W) if self.pixel_format == "nv12" else (H, W, C)   # a frame as it leaves, at the size the model runs at
+        # a frame as it leaves, at the size the model runs at
+        fs = fin if self._depth else (H * 3 // 2, W) if self.pixel_format == "nv12" else (H, W, C)
         nb, nout = self.batch_pairs, max(self.factor if self.mode == "recursive" else 1, 1)
         self._shape = shape
         self._slots = []
@@ -339,9 +360,18 @@ class FrameInterpolator:
         H = buf.shape[1] * 2 // 3
         return buf[:, :H], buf[:, H:].unflatten(2, (buf.shape[2] // 2, 2))
 
+    @staticmethod
+    def _planes16(buf):
+        """Y [n,H,W] and UV [n,H/2,W/2,2] views, as 16-bit words, of the bytes [n, H*3/2, 2 W] of n contiguous P010 / P012 / P016 frames"""
+        H = buf.shape[1] * 2 // 3
+        return buf[:, :H].view(torch.int16), buf[:, H:].view(torch.int16).unflatten(2, (buf.shape[2] // 4, 2))
+
     def _pre_kernel(self, buf, out=None, device=None, resized=None):
         """`resized`: with scale / size, a buffer of frames at the destination size that also receives the resized bytes"""
         size = self._dst if self._resize else None
+        if self._depth:
+            y, uv = self._planes16(buf)
+            return _lib.preprocess_p010(y, uv, self._depth, self.yuv["standard"], self.yuv["full_range"], device=device, out=out)
         if self.pixel_format == "nv12":
             y, uv = self._planes(buf)
             return _lib.preprocess_nv12(y, uv, self.yuv["standard"], self.yuv["full_range"], device=device, out=out, size=size,
@@ -393,6 +423,11 @@ class FrameInterpolator:
         return _lib.resize_u8(src, self._dst).cpu().numpy()[0]
 
     def _post_kernel(self, x, denormalize, out=None):
+        if self._depth:
+            if out is None:
+                out = torch.empty(x.shape[0], x.shape[2] * 3 // 2, x.shape[3] * 2, dtype=torch.uint8, device=x.device)
+            _lib.postprocess_p010(x, self._depth, self.yuv["standard"], self.yuv["full_range"], denormalize=denormalize, out=self._planes16(out))
+            return out
         if self.pixel_format == "nv12":
             if out is None:
                 out = torch.empty(x.shape[0], x.shape[2] * 3 // 2, x.shape[3], dtype=torch.uint8, device=x.device)
@@ -491,6 +526,13 @@ class FrameInterpolator:
             return torch.stack(rec(x1, x2, levels), dim=1)
 
     def _check_frames(self, frames, first, what):
+        if self._depth:
+            for f in frames.values():
+                if f.dtype != np.uint16 or f.ndim != 2 or f.shape != first.shape:
+                    raise ValueError(f"FrameInterpolator.{what}: same-shape uint16 [H*3/2, W] {self.pixel_format.upper()} frames expected")
+            if first.shape[0] % 3 or first.shape[1] % 2:
+                raise ValueError(f"FrameInterpolator.{what}: the packed {self.pixel_format.upper()} layout [H*3/2, W] needs even H and W")
+            return
         if self.pixel_format == "nv12":
             for f in frames.values():
                 if f.dtype != np.uint8 or f.ndim != 2 or f.shape != first.shape:
@@ -503,7 +545,8 @@ class FrameInterpolator:
                     raise ValueError(f"FrameInterpolator.{what}: same-shape uint8 HWC frames expected")
 
     def run(self, frames, rank: int = 0, world: int = 1) -> Iterator[np.ndarray]:
-        """Yields uint8 HWC frames (``pixel_format="nv12"``: uint8 [H*3/2, W] frames) in the order the reference's writer receives them.
+        """Yields uint8 HWC frames (``pixel_format="nv12"``: uint8 [H*3/2, W] frames; ``"p010"`` / ``"p012"`` / ``"p016"``: uint16 [H*3/2, W]
+        frames) in the order the reference's writer receives them.
 
         ``frames``: the whole stream - an iterable, or (sharded use) any object with ``len()`` and integer indexing, of which
         only this rank's segment ``[lo, hi)`` (``segment()``) is touched, e.g. a lazy video reader.  ``rank`` / ``world``:
@@ -519,6 +562,11 @@ class FrameInterpolator:
         frames = {i: np.ascontiguousarray(frames[i]) for i in range(lo, hi)}   # this rank's segment only
         first = frames[lo]
         self._check_frames(frames, first, "run")
+        if self._depth:
+            # from here on a frame is its bytes, [H*3/2, 2 W]; `words` turns what is yielded back into uint16 [H*3/2, W] (a view: no copy)
+            frames = {i: f.view(np.uint8) for i, f in frames.items()}
+            first = frames[lo]
+        words = (lambda v: v.view(np.uint16)) if self._depth else (lambda v: v)
         self._alloc(first.shape)
         self.scene_cuts, self.scene_scores = [], []
         main = torch.cuda.current_stream(self.device)
@@ -533,7 +581,7 @@ class FrameInterpolator:
         def drain(slot, chunk):
             slot["done"].synchronize()            # this batch's frames have been written into the pinned buffers
             pred_h, src_h = slot["h_pred"].numpy(), slot["h_src"].numpy()
-            own = (lambda v: v.copy()) if self.copy_out else (lambda v: v)
+            own = (lambda v: words(v).copy()) if self.copy_out else words
             if self.scene is not None:            # written behind the frames, ahead of `done`
                 fs = slot["h_fs"].numpy()
                 for k, (a, b) in enumerate(chunk):
@@ -547,7 +595,7 @@ class FrameInterpolator:
                 else:
                     for _ in range(self.factor):
                         yield own(pred_h[k])
-                yield own(src_h[k]) if (self.quirks or self._resize) else frames[a]
+                yield own(src_h[k]) if (self.quirks or self._resize) else words(frames[a])
 
         staged = self._stage(self._slots[0], frames, chunks[0]) if chunks else None
         prev = None
@@ -640,9 +688,9 @@ class FrameInterpolator:
             return
         if last_roundtrip and self.quirks:   # skip-branch ending: the reference writes the round-tripped frame
             src = torch.from_numpy(frames[last]).unsqueeze(0).to(self.device)
-            yield self._post_kernel(self._pre_kernel(src), True).cpu().numpy()[0]
+            yield words(self._post_kernel(self._pre_kernel(src), True).cpu().numpy()[0])
         else:
-            yield self._resized_bytes(frames[last]) if self._resize else frames[last]
+            yield self._resized_bytes(frames[last]) if self._resize else words(frames[last])
 
     def evaluate(self, frames, every: int = 1, rank: int = 0, world: int = 1) -> Evaluation:
         """Scores the model on a clip by the held-out protocol and returns an ``Evaluation``: every target ``t = 1, 1 + every, ...`` with
@@ -660,6 +708,8 @@ class FrameInterpolator:
 
         ``frames`` / ``rank`` / ``world`` as for ``run()``: a rank touches only the frames of its contiguous share of the targets, and
         the ranks' ``targets`` concatenated in rank order are the single-process result."""
+        if self._depth:
+            raise ValueError(f"evaluate() with pixel_format={self.pixel_format!r}: the metric kernel reads bytes (16-bit frames are not scored)")
         if not (hasattr(frames, "__len__") and hasattr(frames, "__getitem__")):
             frames = list(frames)
         plan = self.evaluation_plan(len(frames), every, rank, world)
