@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -359,6 +359,36 @@ int emavfi_preprocess_p010(const void *y, size_t y_pitch, size_t y_batch_stride,
 int emavfi_postprocess_p010(const float *frames_nchw, void *y, size_t y_pitch, size_t y_batch_stride, void *uv, size_t uv_pitch,
                             size_t uv_batch_stride, int B, int H, int W, int depth, int standard, int order, const double *mean,
                             const double *std, int denormalize, void *stream);
+
+/* PLANAR 4:2:0 frames, in and out: what software decoders produce (yuv420p, yuv420p10le ...) and what a YUV4MPEG2 stream holds - a Y plane
+ * [H][W], a U plane and a V plane of [ceil(H/2)][ceil(W/2)] samples each.  Every plane has its own pointer, row pitch and batch stride, all in
+ * BYTES; odd H and W are valid; YV12 is the caller swapping the U and V arguments.  `depth` is 8, 10, 12 or 16.  Depth 8: one byte per sample.
+ * Depth d > 8: one 16-bit little-endian word per sample with the sample in the word's LOW d bits (the yuv420p10le convention, Y4M's C420p10;
+ * P010 keeps it in the top bits): a word is masked to its low d bits on read, the high 16 - d bits are written as zero.
+ *
+ * DEFINITION BY COMPOSITION: there is no new colour definition.
+ *   depth 8:  emavfi_preprocess_yuv420p / emavfi_postprocess_yuv420p are DEFINED as emavfi_preprocess_nv12 / emavfi_postprocess_nv12 on the
+ *     chroma plane uv[i][j] = {U[i][j], V[i][j]}, bit for bit.  Standards 0..3.
+ *   depth d > 8: they are DEFINED as emavfi_preprocess_p010 / emavfi_postprocess_p010 at that depth on the words (w & (2^d - 1)) << (16 - d);
+ *     the written words are those entries' words >> (16 - d).  Standards 0..5 (BT.2020 included).
+ *   `order`, `mean`, `std`, NaN -> 0, truncation and `denormalize`: as in those entries.
+ * EMAVFI_E_ARG (never an abort), the message naming the argument: a null pointer; depth outside {8, 10, 12, 16}; a standard outside its range
+ *   for that depth; an unknown order; y_pitch / u_pitch / v_pitch smaller than its row (W, ceil(W/2), ceil(W/2) samples); at depth > 8 an odd
+ *   pitch or a Y / U / V pointer that is not 2-byte aligned; for B > 1 a batch stride smaller than its plane (at depth > 8: or odd); a zero std;
+ *   B, H or W below 1; an fp32 pointer that is not 4-byte aligned.
+ * The Y, U and V pointers are device pointers or pinned (device-mapped) host memory.  Nothing is allocated, nothing synchronises, all work goes
+ *   on `stream`.  Access width: with the Y pointer, its pitch and (B > 1) its batch stride multiples of 16, those of U and of V multiples of 8,
+ *   a 16-byte aligned fp32 pointer and W % 4 == 0, every full block of 2 rows x 16 BYTES of Y (NV12's / P010's block: 16 columns at depth 8, 8
+ *   above) moves with two 16-byte accesses of Y, twelve / twenty-four of fp32 and one 8-BYTE access of U and of V - a planar chroma row is half
+ *   as wide as NV12's; chroma is 0.5 - 1 of the 13.5 - 15 bytes per pixel, so it takes the narrower access and the fp32 side, which carries 12,
+ *   keeps NV12's / P010's pattern (profiles/r15_yuv420p_y4m.md times this block beside one twice as wide with 16-byte chroma accesses; 1280 x 720 and 1920 x 1080 frames stored densely plane after plane qualify at every depth); everything else (and the
+ *   right / bottom remainders) takes a scalar path with the same per-element arithmetic.  Pitch padding is never read or written. */
+int emavfi_preprocess_yuv420p(const void *y, size_t y_pitch, size_t y_batch_stride, const void *u, size_t u_pitch, size_t u_batch_stride,
+                              const void *v, size_t v_pitch, size_t v_batch_stride, float *out_nchw, int B, int H, int W, int depth,
+                              int standard, int order, const float *mean, const float *std, void *stream);
+int emavfi_postprocess_yuv420p(const float *frames_nchw, void *y, size_t y_pitch, size_t y_batch_stride, void *u, size_t u_pitch,
+                               size_t u_batch_stride, void *v, size_t v_pitch, size_t v_batch_stride, int B, int H, int W, int depth,
+                               int standard, int order, const double *mean, const double *std, int denormalize, void *stream);
 
 /* Frames resized on the device: the reference's `--scale` step, cv2.resize(frame, (int(w * scale), int(h * scale))), inference.py:46 / :93-94,
  * which it applies to every decoded frame before ToTensor / Normalize.

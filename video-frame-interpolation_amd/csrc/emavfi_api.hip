@@ -1446,6 +1446,71 @@ int emavfi_postprocess_p010(const float *frames_nchw, void *y, size_t y_pitch, s
     return EMAVFI_OK;
 }
 
+// ---- planar 4:2:0 frames (include/emavfi.h, "PLANAR 4:2:0"): the checks both entries share, in nv12_check's order; sizes are compared in 128 bits
+static int yuv420p_check(const char *what, const void *const ptr[3], const size_t pitch[3], const size_t bstride[3], const void *f32, int B, int H,
+                         int W, int depth, int standard, int order, const float *mean32, const float *std32, const double *mean64,
+                         const double *std64)
+{
+    typedef unsigned __int128 u128;
+    static const char *const name[3] = {"y", "u", "v"};
+    if (!(mean32 && std32) && !(mean64 && std64)) return fail(EMAVFI_E_ARG, "%s: null mean / std", what);
+    if (B < 1 || H < 1 || W < 1) return fail(EMAVFI_E_ARG, "%s: B, H, W must be >= 1", what);
+    if (depth != 8 && depth != 10 && depth != 12 && depth != 16) return fail(EMAVFI_E_ARG, "%s: depth %d is not 8, 10, 12 or 16", what, depth);
+    const int last = depth == 8 ? EMAVFI_YUV_BT709_FULL : EMAVFI_YUV_BT2020_FULL;
+    if (standard < EMAVFI_YUV_BT601_LIMITED || standard > last)
+        return fail(EMAVFI_E_ARG, "%s: unknown standard %d at depth %d (EMAVFI_YUV_BT601_LIMITED .. %s)", what, standard, depth,
+                    depth == 8 ? "EMAVFI_YUV_BT709_FULL" : "EMAVFI_YUV_BT2020_FULL");
+    if (order != EMAVFI_ORDER_BGR && order != EMAVFI_ORDER_RGB)
+        return fail(EMAVFI_E_ARG, "%s: unknown order %d (EMAVFI_ORDER_BGR or EMAVFI_ORDER_RGB)", what, order);
+    const size_t es = depth == 8 ? 1 : 2;   // bytes per sample
+    const size_t row[3] = {es * (size_t)W, es * (((size_t)W + 1) / 2), es * (((size_t)W + 1) / 2)};
+    const size_t rows[3] = {(size_t)H, ((size_t)H + 1) / 2, ((size_t)H + 1) / 2};
+    for (int p = 0; p < 3; ++p) {
+        if (pitch[p] < row[p]) return fail(EMAVFI_E_ARG, "%s: %s_pitch %zu is smaller than its row of %zu bytes", what, name[p], pitch[p], row[p]);
+        if (es == 2 && (pitch[p] & 1)) return fail(EMAVFI_E_ARG, "%s: %s_pitch %zu must be even at depth %d", what, name[p], pitch[p], depth);
+    }
+    for (int p = 0; p < 3 && B > 1; ++p) {
+        if ((u128)bstride[p] < (u128)(rows[p] - 1) * pitch[p] + row[p])
+            return fail(EMAVFI_E_ARG, "%s: the %s batch stride %zu is smaller than its plane", what, name[p], bstride[p]);
+        if (es == 2 && (bstride[p] & 1))
+            return fail(EMAVFI_E_ARG, "%s: the %s batch stride %zu must be even at depth %d (it breaks the alignment of its plane)", what, name[p],
+                        bstride[p], depth);
+    }
+    for (int c = 0; c < 3; ++c)
+        if (std32 ? !(std32[c] != 0.0f) : !(std64[c] != 0.0)) return fail(EMAVFI_E_ARG, "%s: std[%d] must be non-zero", what, c);
+    if (!ptr[0] || !ptr[1] || !ptr[2] || !f32) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
+    for (int p = 0; p < 3; ++p)
+        if (es == 2 && ((uintptr_t)ptr[p] & 1)) return fail(EMAVFI_E_ARG, "%s: the %s pointer must be 2-byte aligned at depth %d", what, name[p], depth);
+    if ((uintptr_t)f32 & 3) return fail(EMAVFI_E_ARG, "%s: the fp32 pointer must be 4-byte aligned", what);
+    return EMAVFI_OK;
+}
+
+int emavfi_preprocess_yuv420p(const void *y, size_t y_pitch, size_t y_batch_stride, const void *u, size_t u_pitch, size_t u_batch_stride,
+                              const void *v, size_t v_pitch, size_t v_batch_stride, float *out_nchw, int B, int H, int W, int depth,
+                              int standard, int order, const float *mean, const float *std, void *stream)
+{
+    const void *const ptr[3] = {y, u, v};
+    const size_t pitch[3] = {y_pitch, u_pitch, v_pitch}, bstride[3] = {y_batch_stride, u_batch_stride, v_batch_stride};
+    if (const int rc = yuv420p_check("preprocess_yuv420p", ptr, pitch, bstride, out_nchw, B, H, W, depth, standard, order, mean, std, nullptr,
+                                     nullptr); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_preprocess_yuv420p(y, y_pitch, y_batch_stride, u, u_pitch, u_batch_stride, v, v_pitch, v_batch_stride, out_nchw, B, H, W,
+                                         depth, standard, order, mean, std, (hipStream_t)stream), "preprocess_yuv420p");
+    return EMAVFI_OK;
+}
+
+int emavfi_postprocess_yuv420p(const float *frames_nchw, void *y, size_t y_pitch, size_t y_batch_stride, void *u, size_t u_pitch,
+                               size_t u_batch_stride, void *v, size_t v_pitch, size_t v_batch_stride, int B, int H, int W, int depth,
+                               int standard, int order, const double *mean, const double *std, int denormalize, void *stream)
+{
+    const void *const ptr[3] = {y, u, v};
+    const size_t pitch[3] = {y_pitch, u_pitch, v_pitch}, bstride[3] = {y_batch_stride, u_batch_stride, v_batch_stride};
+    if (const int rc = yuv420p_check("postprocess_yuv420p", ptr, pitch, bstride, frames_nchw, B, H, W, depth, standard, order, nullptr, nullptr,
+                                     mean, std); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_postprocess_yuv420p(frames_nchw, y, y_pitch, y_batch_stride, u, u_pitch, u_batch_stride, v, v_pitch, v_batch_stride, B, H,
+                                          W, depth, standard, order, mean, std, denormalize ? 1 : 0, (hipStream_t)stream), "postprocess_yuv420p");
+    return EMAVFI_OK;
+}
+
 // ---- frames resized on the device (include/emavfi.h, "RESIZE DEFINITION"): checks in an order that lets a caller without a device reach each
 static int resize_dims_check(const char *what, int B, int Hs, int Ws, int Hd, int Wd)
 {

@@ -91,6 +91,14 @@ int launch_preprocess_p010(const void *y, size_t y_pitch, size_t y_bstride, cons
                            int H, int W, int depth, int standard, int order, const float *mean, const float *stdv, hipStream_t s);
 int launch_postprocess_p010(const float *src, void *y, size_t y_pitch, size_t y_bstride, void *uv, size_t uv_pitch, size_t uv_bstride, int B, int H,
                             int W, int depth, int standard, int order, const double *mean, const double *stdv, int denorm, hipStream_t s);
+// planar 4:2:0 frames (include/emavfi.h, "PLANAR 4:2:0"): three planes, pitches and batch strides in bytes; depth 8 (bytes) or 10 / 12 / 16
+// (words, the sample in the low bits); depth / standard / order already validated
+int launch_preprocess_yuv420p(const void *y, size_t y_pitch, size_t y_bstride, const void *u, size_t u_pitch, size_t u_bstride, const void *v,
+                              size_t v_pitch, size_t v_bstride, float *dst, int B, int H, int W, int depth, int standard, int order,
+                              const float *mean, const float *stdv, hipStream_t s);
+int launch_postprocess_yuv420p(const float *src, void *y, size_t y_pitch, size_t y_bstride, void *u, size_t u_pitch, size_t u_bstride, void *v,
+                               size_t v_pitch, size_t v_bstride, int B, int H, int W, int depth, int standard, int order, const double *mean,
+                               const double *stdv, int denorm, hipStream_t s);
 // frames resized on the device (include/emavfi.h, "RESIZE DEFINITION"): pitches and batch strides in bytes, arguments already validated.
 // launch_resize_u8: dst_u8 and / or dst_f32 (dense [B,C,Hd,Wd], normalised with mean / stdv) may be null - one launch writes what is asked for
 int launch_resize_u8(const unsigned char *src, size_t src_pitch, size_t src_bstride, unsigned char *dst_u8, size_t dst_pitch, size_t dst_bstride,

@@ -5,6 +5,7 @@
 #include "scene_elem.h"
 #include "metrics_elem.h"
 #include "p010_elem.h"
+#include "yuv420p_elem.h"
 #include <atomic>
 #include <type_traits>
 #include <cstddef>
@@ -1672,6 +1673,239 @@ int launch_postprocess_p010(const float *src, void *y, size_t y_pitch, size_t y_
     const Nv12Planes pl{y_pitch, y_bstride, uv_pitch, uv_bstride};
     postprocess_p010_kernel<<<p010_grid(B, H, W), 256, 0, s>>>(src, (unsigned char *)y, (unsigned char *)uv, B, H, W, pl, st,
                                                                p010_coef(standard, depth, order), denorm, nv12_fast_ok(y, uv, src, W, pl) ? 1 : 0);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Planar 4:2:0 frames (include/emavfi.h, "PLANAR 4:2:0"): a Y plane and separate half-resolution U and V planes, bytes (depth 8) or 16-bit
+// words with the sample in the LOW `depth` bits.  Nothing is computed here that NV12 / P010 do not compute: depth 8 calls nv12_decode / _norm /
+// _byte / _luma / _chroma, the deeper formats p010_elem.h's functions; only where a sample sits differs (yuv420p_elem.h).
+// One lane owns NV12's / P010's block, 2 rows x 16 BYTES of Y = NX columns (16 at depth 8, 8 above), and the NX / 2 samples = 8 bytes of a U and
+// of a V row under it.  A planar chroma row is half as wide as NV12's, so either the chroma accesses halve or the block doubles.  Chroma is
+// 0.5 - 1 of the 13.5 - 15 bytes per pixel, 12 are fp32: chroma takes the narrower access, and the fp32 side keeps NV12's / P010's pattern.
+// The other choice, 2 rows x 32 bytes of Y with 16-byte chroma accesses, is kept as a measurement variant only - `make TAG=_block32
+// EXTRA=-DEMAVFI_YUV420P_BLOCK32=1` builds libemavfi_block32.so, which tools/bench_yuv420p.py --ab-lib times beside the product library in one
+// process; profiles/r15_yuv420p_y4m.md holds both.  The product build never defines the macro.
+//   FAST   two 16-byte Y accesses, one 8-byte U and one 8-byte V access, 16-byte accesses on the three fp32 planes.  Conditions
+//          (yuv420p_fast_ok): the Y pointer, its pitch and (B > 1) its batch stride are multiples of 16, those of U and V multiples of 8, the fp32
+//          pointer is 16-byte aligned and W % 4 == 0 - and the block lies inside the frame (NX columns, 2 rows).
+//   SCALAR sample and dword accesses with the encode's edge clamp: every block when a FAST condition fails, otherwise the right (W % NX)
+//          and bottom (odd H) remainders only.
+// No LDS, no waiting, one block per lane and a grid-stride loop, as for NV12 / P010.
+// ------------------------------------------------------------------------------------------
+struct Yuv420pPlanes { size_t y_pitch, y_bstride, u_pitch, u_bstride, v_pitch, v_bstride; };
+#ifdef EMAVFI_YUV420P_BLOCK32
+constexpr int kYuv420pRowBytes = 32;   // measurement variant: 2 rows x 32 bytes of Y, 16 bytes of U and of V
+#else
+constexpr int kYuv420pRowBytes = 16;   // bytes of a Y row in a lane's block; half as many of a U and of a V row
+#endif
+// N = 2, 4 or 8 consecutive dwords at an address aligned to min(4 N, 16) bytes, moved 8 or 16 bytes at a time
+template <int N> __device__ __forceinline__ void load_dwords(const unsigned char *p, unsigned (&w)[N])
+{
+    if constexpr (N == 2) {
+        const uint2 q = *reinterpret_cast<const uint2 *>(p);
+        w[0] = q.x; w[1] = q.y;
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; i += 4) {
+            const uint4 q = *reinterpret_cast<const uint4 *>(p + 4 * i);
+            w[i] = q.x; w[i + 1] = q.y; w[i + 2] = q.z; w[i + 3] = q.w;
+        }
+    }
+}
+template <int N> __device__ __forceinline__ void store_dwords(unsigned char *p, const unsigned (&w)[N])
+{
+    if constexpr (N == 2) {
+        *reinterpret_cast<uint2 *>(p) = make_uint2(w[0], w[1]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; i += 4) *reinterpret_cast<uint4 *>(p + 4 * i) = make_uint4(w[i], w[i + 1], w[i + 2], w[i + 3]);
+    }
+}
+
+// the two sample formats: the type in memory and the per-element functions the samples go through
+struct Planar8 {
+    typedef unsigned char T;
+    YuvCoef k;
+    __device__ __forceinline__ int sample(unsigned w) const { return yuv420p_sample(w, 255); }
+    __device__ __forceinline__ void decode(int Y, int U, int V, int ch[3]) const { nv12_decode(Y, U, V, k, ch); }
+    __device__ __forceinline__ float norm(int v, float mean, float stdv) const { return nv12_norm(v, mean, stdv); }
+    __device__ __forceinline__ int quant(float x, double mean, double stdv, int denorm) const { return nv12_byte(x, mean, stdv, denorm); }
+    __device__ __forceinline__ int luma(const int ch[3]) const { return nv12_luma(ch, k); }
+    __device__ __forceinline__ void chroma(const int sum[3], int &U, int &V) const { nv12_chroma(sum, k, U, V); }
+};
+struct Planar16 {
+    typedef unsigned short T;
+    P010Coef k;
+    __device__ __forceinline__ int sample(unsigned w) const { return yuv420p_sample(w, k.P); }
+    __device__ __forceinline__ void decode(int Y, int U, int V, int ch[3]) const { p010_decode(Y, U, V, k, ch); }
+    __device__ __forceinline__ float norm(int v, float mean, float stdv) const { return p010_norm(v, (float)k.P, mean, stdv); }
+    __device__ __forceinline__ int quant(float x, double mean, double stdv, int denorm) const { return p010_quant(x, mean, stdv, denorm, (double)k.P); }
+    __device__ __forceinline__ int luma(const int ch[3]) const { return p010_luma(ch, k); }
+    __device__ __forceinline__ void chroma(const int sum[3], int &U, int &V) const { p010_chroma(sum, k, U, V); }
+};
+
+template <class F>
+__global__ __launch_bounds__(256) void preprocess_yuv420p_kernel(const unsigned char *__restrict__ ysrc, const unsigned char *__restrict__ usrc,
+                                                                 const unsigned char *__restrict__ vsrc, float *__restrict__ dst, int B, int H,
+                                                                 int W, Yuv420pPlanes pl, Stats4 st, F f, int fast)
+{
+    typedef typename F::T T;
+    constexpr int ES = (int)sizeof(T), BITS = 8 * ES, NX = kYuv420pRowBytes / ES, NW = kYuv420pRowBytes / 4;
+    const size_t nbx = ((size_t)W + NX - 1) / NX, nby = ((size_t)H + 1) / 2, plane = (size_t)H * W, total = (size_t)B * nby * nbx;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = i / (nby * nbx), rem = i - b * nby * nbx, by = rem / nbx;
+        const int y0 = (int)by * 2, x0 = (int)(rem - by * nbx) * NX;
+        const unsigned char *yp = ysrc + b * pl.y_bstride + (size_t)y0 * pl.y_pitch + (size_t)x0 * ES;
+        const unsigned char *up = usrc + b * pl.u_bstride + by * pl.u_pitch + (size_t)(x0 / 2) * ES;   // chroma sample x0 / 2 of row y0 / 2
+        const unsigned char *vp = vsrc + b * pl.v_bstride + by * pl.v_pitch + (size_t)(x0 / 2) * ES;
+        float *o = dst + b * 3 * plane + (size_t)y0 * W + x0;
+        if (fast && x0 + NX <= W && y0 + 2 <= H) {
+            unsigned uw[NW / 2], vw[NW / 2];
+            load_dwords(up, uw);
+            load_dwords(vp, vw);
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                unsigned yw[NW];
+                load_dwords(yp + (size_t)r * pl.y_pitch, yw);
+#pragma unroll
+                for (int q = 0; q < NX / 4; ++q) {   // 4 pixels = 2 chroma samples of each plane = one 16-byte access of each fp32 plane
+                    f32x4 out[3];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int p = q * 4 + j;
+                        int ch[3];
+                        f.decode(f.sample(yuv420p_get<BITS>(yw, p)), f.sample(yuv420p_get<BITS>(uw, p >> 1)), f.sample(yuv420p_get<BITS>(vw, p >> 1)), ch);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) out[c][j] = f.norm(ch[c], st.mean[c], st.stdv[c]);
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4 *>(o + c * plane + (size_t)r * W + q * 4) = out[c];
+                }
+            }
+            continue;
+        }
+        const int nx = min(NX, W - x0), ny = min(2, H - y0);
+        for (int x = 0; x < nx; ++x) {
+            const int U = f.sample(reinterpret_cast<const T *>(up)[x >> 1]), V = f.sample(reinterpret_cast<const T *>(vp)[x >> 1]);
+            for (int r = 0; r < ny; ++r) {
+                int ch[3];
+                f.decode(f.sample(reinterpret_cast<const T *>(yp + (size_t)r * pl.y_pitch)[x]), U, V, ch);
+                for (int c = 0; c < 3; ++c) o[c * plane + (size_t)r * W + x] = f.norm(ch[c], st.mean[c], st.stdv[c]);
+            }
+        }
+    }
+}
+
+template <class F>
+__global__ __launch_bounds__(256) void postprocess_yuv420p_kernel(const float *__restrict__ src, unsigned char *__restrict__ ydst,
+                                                                  unsigned char *__restrict__ udst, unsigned char *__restrict__ vdst, int B, int H,
+                                                                  int W, Yuv420pPlanes pl, Stats4d st, F f, int denorm, int fast)
+{
+    typedef typename F::T T;
+    constexpr int ES = (int)sizeof(T), BITS = 8 * ES, NX = kYuv420pRowBytes / ES, NW = kYuv420pRowBytes / 4;
+    const size_t nbx = ((size_t)W + NX - 1) / NX, nby = ((size_t)H + 1) / 2, plane = (size_t)H * W, total = (size_t)B * nby * nbx;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = i / (nby * nbx), rem = i - b * nby * nbx, by = rem / nbx;
+        const int y0 = (int)by * 2, x0 = (int)(rem - by * nbx) * NX;
+        unsigned char *yp = ydst + b * pl.y_bstride + (size_t)y0 * pl.y_pitch + (size_t)x0 * ES;
+        unsigned char *up = udst + b * pl.u_bstride + by * pl.u_pitch + (size_t)(x0 / 2) * ES;
+        unsigned char *vp = vdst + b * pl.v_bstride + by * pl.v_pitch + (size_t)(x0 / 2) * ES;
+        const float *s = src + b * 3 * plane;
+        if (fast && x0 + NX <= W && y0 + 2 <= H) {
+            unsigned yw[2][NW] = {}, uw[NW / 2] = {}, vw[NW / 2] = {};   // at depth > 8 the high bits of every word stay zero
+#pragma unroll
+            for (int q = 0; q < NX / 4; ++q) {
+                int v[2][4][3];   // [row][pixel][channel]
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const f32x4 x = *reinterpret_cast<const f32x4 *>(s + c * plane + (size_t)(y0 + r) * W + x0 + q * 4);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v[r][j][c] = f.quant(x[j], st.mean[c], st.stdv[c], denorm);
+                    }
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) yuv420p_put<BITS>(yw[r], q * 4 + j, (unsigned)f.luma(v[r][j]));
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    int sum[3], U, V;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) sum[c] = v[0][2 * p][c] + v[0][2 * p + 1][c] + v[1][2 * p][c] + v[1][2 * p + 1][c];
+                    f.chroma(sum, U, V);
+                    yuv420p_put<BITS>(uw, q * 2 + p, (unsigned)U);
+                    yuv420p_put<BITS>(vw, q * 2 + p, (unsigned)V);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 2; ++r) store_dwords(yp + (size_t)r * pl.y_pitch, yw[r]);
+            store_dwords(up, uw);
+            store_dwords(vp, vw);
+            continue;
+        }
+        const int nx = min(NX, W - x0);
+        for (int x = 0; x < nx; x += 2) {
+            int sum[3] = {0, 0, 0}, U, V;
+            for (int r = 0; r < 2; ++r)
+                for (int dx = 0; dx < 2; ++dx) {
+                    const int yy = min(y0 + r, H - 1), xx = min(x0 + x + dx, W - 1);   // past the last row / column: clamped
+                    int ch[3];
+                    for (int c = 0; c < 3; ++c) {
+                        ch[c] = f.quant(s[c * plane + (size_t)yy * W + xx], st.mean[c], st.stdv[c], denorm);
+                        sum[c] += ch[c];
+                    }
+                    if (yy == y0 + r && xx == x0 + x + dx) reinterpret_cast<T *>(yp + (size_t)r * pl.y_pitch)[x + dx] = (T)f.luma(ch);
+                }
+            f.chroma(sum, U, V);
+            reinterpret_cast<T *>(up)[x >> 1] = (T)U;
+            reinterpret_cast<T *>(vp)[x >> 1] = (T)V;
+        }
+    }
+}
+
+static bool yuv420p_fast_ok(const void *y, const void *u, const void *v, const void *f32, int B, int W, const Yuv420pPlanes &pl)
+{
+    const size_t ybs = B > 1 ? pl.y_bstride : 0, cbs = B > 1 ? pl.u_bstride | pl.v_bstride : 0;
+    const size_t cmask = kYuv420pRowBytes / 2 - 1;   // a lane's chroma access: 8 bytes
+    return (((uintptr_t)y | (uintptr_t)f32 | pl.y_pitch | ybs) & 15) == 0 && (((uintptr_t)u | (uintptr_t)v | pl.u_pitch | pl.v_pitch | cbs) & cmask) == 0 &&
+           W % 4 == 0;
+}
+static int yuv420p_grid(int B, int H, int W, int depth)
+{
+    const size_t nx = kYuv420pRowBytes / (depth == 8 ? 1 : 2), lanes = (size_t)B * (((size_t)H + 1) / 2) * (((size_t)W + nx - 1) / nx);
+    return (int)std::min<size_t>((lanes + 255) / 256, (size_t)65535 * 4);
+}
+int launch_preprocess_yuv420p(const void *y, size_t y_pitch, size_t y_bstride, const void *u, size_t u_pitch, size_t u_bstride, const void *v,
+                              size_t v_pitch, size_t v_bstride, float *dst, int B, int H, int W, int depth, int standard, int order,
+                              const float *mean, const float *stdv, hipStream_t s)
+{
+    Stats4 st{};
+    for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
+    const Yuv420pPlanes pl{y_pitch, y_bstride, u_pitch, u_bstride, v_pitch, v_bstride};
+    const unsigned char *yb = (const unsigned char *)y, *ub = (const unsigned char *)u, *vb = (const unsigned char *)v;
+    const int grid = yuv420p_grid(B, H, W, depth), fast = yuv420p_fast_ok(y, u, v, dst, B, W, pl) ? 1 : 0;
+    if (depth == 8)
+        preprocess_yuv420p_kernel<Planar8><<<grid, 256, 0, s>>>(yb, ub, vb, dst, B, H, W, pl, st, Planar8{yuv_coef(standard, order)}, fast);
+    else
+        preprocess_yuv420p_kernel<Planar16><<<grid, 256, 0, s>>>(yb, ub, vb, dst, B, H, W, pl, st, Planar16{p010_coef(standard, depth, order)}, fast);
+    return (int)hipGetLastError();
+}
+int launch_postprocess_yuv420p(const float *src, void *y, size_t y_pitch, size_t y_bstride, void *u, size_t u_pitch, size_t u_bstride, void *v,
+                               size_t v_pitch, size_t v_bstride, int B, int H, int W, int depth, int standard, int order, const double *mean,
+                               const double *stdv, int denorm, hipStream_t s)
+{
+    Stats4d st{};
+    for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
+    const Yuv420pPlanes pl{y_pitch, y_bstride, u_pitch, u_bstride, v_pitch, v_bstride};
+    unsigned char *yb = (unsigned char *)y, *ub = (unsigned char *)u, *vb = (unsigned char *)v;
+    const int grid = yuv420p_grid(B, H, W, depth), fast = yuv420p_fast_ok(y, u, v, src, B, W, pl) ? 1 : 0;
+    if (depth == 8)
+        postprocess_yuv420p_kernel<Planar8><<<grid, 256, 0, s>>>(src, yb, ub, vb, B, H, W, pl, st, Planar8{yuv_coef(standard, order)}, denorm, fast);
+    else
+        postprocess_yuv420p_kernel<Planar16><<<grid, 256, 0, s>>>(src, yb, ub, vb, B, H, W, pl, st, Planar16{p010_coef(standard, depth, order)}, denorm,
+                                                                  fast);
     return (int)hipGetLastError();
 }
 

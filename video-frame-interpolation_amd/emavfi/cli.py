@@ -1,0 +1,115 @@
+"""``python -m emavfi IN.y4m OUT.y4m``: the reference's command line (inference.py) around the device-side harness.
+
+A YUV4MPEG2 stream goes in, the interpolated stream comes out; ``-`` is stdin / stdout, so any video file reaches it through ffmpeg pipes
+(INTEGRATION.md).  The pixel format comes from the stream's colour-space tag; frames travel through ``FrameInterpolator.run_chunked`` in
+bounded memory, planar 4:2:0 all the way (``emavfi.y4m``).  Single process, single GPU.  ``--evaluate`` is the exception to the bound:
+``FrameInterpolator.evaluate`` indexes its clip, so the whole clip is read into host memory first.
+
+Defaults that DIFFER from inference.py, on purpose:
+  * no resize: the reference halves every frame (``--scale 0.5``); here ``--scale`` / ``--size`` are opt-in;
+  * ``reference_quirks`` off: the reference de-normalises a model output that is already in [0, 1];
+    ``--reference-quirks`` brings that back.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+
+from . import y4m
+
+_EPILOG = """defaults that differ from the reference's inference.py: frames are NOT resized (the reference halves them: pass --scale 0.5 for
+that) and --reference-quirks is off (the reference de-normalises a model output that is already in [0, 1])."""
+
+
+def _size(text):
+    try:
+        h, w = (int(v) for v in text.lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError("HxW expected, e.g. 360x640") from None
+    return h, w
+
+
+def parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m emavfi", description="Interpolate a YUV4MPEG2 (.y4m) stream on an MI355X.", epilog=_EPILOG)
+    p.add_argument("input", help="input .y4m ('-': stdin)")
+    p.add_argument("output", nargs="?", help="output .y4m ('-': stdout); not needed with --evaluate")
+    w = p.add_mutually_exclusive_group(required=True)
+    w.add_argument("--weights", metavar="FILE", help="a state_dict with the reference's keys (torch.save)")
+    w.add_argument("--synthetic-weights", metavar="SEED", type=int, help="deterministic synthetic weights (the reference ships none)")
+    p.add_argument("--dtype", default="bf16", help="compute dtype of the forward (default: bf16)")
+    p.add_argument("--mid-channels", type=int, default=64)
+    p.add_argument("--target-fps", type=float, default=None, help="as in inference.py: factor = round(target / fps - 1)")
+    p.add_argument("--max-interpolation-factor", type=int, default=4, help="without --target-fps: the factor in 1..MAX that brings the rate closest to 60")
+    p.add_argument("--factor", type=int, default=None, help="the interpolation factor itself (overrides --target-fps)")
+    p.add_argument("--frame-interval", type=int, default=1)
+    p.add_argument("--mode", choices=("reference", "recursive"), default="reference")
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--scale", type=float, default=None, help="resize every frame on the device (default: no resize; the reference: 0.5)")
+    g.add_argument("--size", type=_size, default=None, metavar="HxW", help="resize every frame on the device to H x W")
+    p.add_argument("--scene-threshold", type=float, default=None, help="hold the earlier frame across cuts (8-bit streams)")
+    p.add_argument("--batch-pairs", type=int, default=8)
+    p.add_argument("--chunk-pairs", type=int, default=64, help="frame pairs per chunk: at most chunk_pairs * frame_interval + 1 source frames are held")
+    p.add_argument("--yuv-standard", default="bt601", help="bt601, bt709 or (10 / 12 / 16-bit streams) bt2020")
+    p.add_argument("--full-range", action="store_true")
+    p.add_argument("--reference-quirks", action="store_true", help="de-normalise the model output as the reference does (default: off)")
+    p.add_argument("--evaluate", action="store_true", help="score the model on the clip (held-out PSNR / SSIM of the Y plane); writes no video; holds the WHOLE clip in host memory")
+    p.add_argument("--every", type=int, default=1, help="with --evaluate: every N-th frame is a target")
+    return p
+
+
+def _run(args) -> int:
+    import torch
+    from . import EMA_VFI, FrameInterpolator, synth
+
+    if not args.evaluate and args.output is None:
+        raise ValueError("an output stream is needed (or --evaluate)")
+    with y4m.Y4MReader(args.input) as reader:
+        head = reader.header
+        if args.factor is not None:
+            factor = args.factor
+        else:
+            factor, _ = y4m.choose_factor(head.fps, args.target_fps, args.max_interpolation_factor)
+        if factor < 0:
+            raise ValueError(f"the interpolation factor {factor} is negative (the target rate lies below the stream's {head.fps:g} fps)")
+        if not torch.cuda.is_available():
+            raise RuntimeError("no ROCm device: this project has no CPU path")
+        dev = torch.device("cuda")
+        if args.weights is not None:
+            sd = torch.load(args.weights, map_location="cpu", weights_only=True)   # a plain state_dict: nothing else is unpickled
+        else:
+            sd = synth.synthetic_state_dict(seed=args.synthetic_weights, mid_channels=args.mid_channels)
+        model = EMA_VFI(mid_channels=args.mid_channels, compute_dtype=args.dtype).to(dev).eval()
+        model.load_state_dict(sd, strict=True)
+        fi = FrameInterpolator(model, interpolation_factor=factor, frame_interval=args.frame_interval, batch_pairs=args.batch_pairs,
+                               reference_quirks=args.reference_quirks, mode=args.mode, pixel_format=head.pixel_format,
+                               yuv_standard=args.yuv_standard, yuv_full_range=args.full_range, scale=args.scale, size=args.size,
+                               scene_threshold=args.scene_threshold, copy_out=False)
+        if args.evaluate:
+            print(fi.evaluate(list(reader), every=args.every))      # evaluate() indexes the clip: all of it is held
+            return 0
+        dst = fi.output_size(head.height, head.width, args.scale, args.size, head.pixel_format)
+        out_head = head.for_output(factor, dst if (args.scale is not None or args.size is not None) else None)
+        with y4m.Y4MWriter(args.output, out_head) as writer:
+            for frame in fi.run_chunked(reader, chunk_pairs=args.chunk_pairs):
+                writer.write(frame)
+        if args.output != "-":
+            print(f"{reader.frames_read} frames in, {writer.frames_written} frames out at {out_head.fps_num}:{out_head.fps_den} fps "
+                  f"({out_head.width} x {out_head.height}, {head.pixel_format}, factor {factor})", file=sys.stderr)
+    return 0
+
+
+def main(argv=None) -> int:
+    """Runs the command line in-process; returns the exit code (0, or non-zero with the message on stderr for refused input)."""
+    try:
+        args = parser().parse_args(argv)
+    except SystemExit as e:      # argparse has printed its message
+        return int(e.code or 0)
+    try:
+        return _run(args)
+    except (ValueError, RuntimeError, OSError) as e:
+        print(f"emavfi: {e}", file=sys.stderr)
+        return 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

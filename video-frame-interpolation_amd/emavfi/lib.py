@@ -52,6 +52,10 @@ _PROTOTYPES = {
                                + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
     "emavfi_postprocess_p010": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 6
                                 + [POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int, c_void_p]),
+    "emavfi_preprocess_yuv420p": (c_int, [c_void_p, c_size_t, c_size_t] * 3 + [c_void_p] + [c_int] * 6
+                                  + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
+    "emavfi_postprocess_yuv420p": (c_int, [c_void_p] + [c_void_p, c_size_t, c_size_t] * 3 + [c_int] * 6
+                                   + [POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int, c_void_p]),
     "emavfi_resize_u8": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 6 + [c_void_p]),
     "emavfi_preprocess_u8_resized": (c_int, [c_void_p] * 3 + [c_int] * 6 + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
     "emavfi_preprocess_nv12_resized": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p,
@@ -869,6 +873,107 @@ def postprocess_p010(frames_nchw, depth=10, standard="bt601", full_range=False, 
         check(load().emavfi_postprocess_p010(x.data_ptr(), y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs, B, H, W, d, st, od, m, s,
                                              1 if denormalize else 0, _stream()), "emavfi_postprocess_p010")
     return y, uv
+
+# ---------------------------------------------------------------- planar 4:2:0 frames (include/emavfi.h, "PLANAR 4:2:0")
+PLANAR_DEPTHS = {"yuv420p8": 8, "yuv420p10": 10, "yuv420p12": 12, "yuv420p16": 16}      # pixel format -> bits per sample
+
+
+def _planar_depth(depth) -> int:
+    if isinstance(depth, bool) or depth not in (8, 10, 12, 16):
+        raise ValueError(f"depth must be 8, 10, 12 or 16, got {depth!r}")
+    return int(depth)
+
+
+def _yuv420p_planes(y, u, v, depth, what):
+    """Shapes and, per plane, (pointer, pitch, batch stride) in BYTES of a Y [B,H,W] / U, V [B,ceil(H/2),ceil(W/2)] triple: uint8 tensors
+    at depth 8, 16-bit integer tensors above; rows and batches may be strided, a row must be dense."""
+    import torch
+    es = 1 if depth == 8 else 2
+    for name, t in (("y", y), ("u", u), ("v", v)):
+        _pinned_or_cuda(t, what)
+        if t.dim() != 3:
+            raise ValueError(f"{what}: {name} must be a 3-d tensor (y [B,H,W]; u, v [B,ceil(H/2),ceil(W/2)]), got {t.dim()} dimensions")
+        if es == 1 and t.dtype != torch.uint8:
+            raise ValueError(f"{what}: {name} must be uint8 at depth 8, got {t.dtype}")
+        if es == 2 and (t.element_size() != 2 or t.dtype.is_floating_point):
+            raise ValueError(f"{what}: {name} must hold 16-bit integers at depth {depth} (torch.uint16 or torch.int16), got {t.dtype}")
+    B, H, W = y.shape
+    if min(B, H, W) < 1:
+        raise ValueError(f"{what}: y is empty")
+    H2, W2 = (H + 1) // 2, (W + 1) // 2
+    planes = []
+    for name, t, (h, w) in (("y", y, (H, W)), ("u", u, (H2, W2)), ("v", v, (H2, W2))):
+        if tuple(t.shape) != (B, h, w):
+            raise ValueError(f"{what}: {name} must be {(B, h, w)} for y {(B, H, W)}, got {tuple(t.shape)}")
+        if t.is_cuda != y.is_cuda or (t.is_cuda and t.device != y.device):
+            raise ValueError(f"{what}: {name} and y must live in the same memory")
+        if w > 1 and t.stride(2) != 1:
+            raise ValueError(f"{what}: the rows of {name} must be dense (only rows and batches may be strided)")
+        # a dimension of size 1 has no meaningful stride: the dense value stands in
+        pitch = es * (t.stride(1) if h > 1 else w)
+        planes += [t.data_ptr(), pitch, es * t.stride(0) if B > 1 else pitch * h]
+    return B, H, W, planes
+
+
+def preprocess_yuv420p(y, u, v, depth=8, standard="bt601", full_range=False, order="bgr", mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None,
+                       out=None):
+    """Planar 4:2:0 frames -> fp32 [B,3,H,W] (include/emavfi.h, "PLANAR 4:2:0"): `y` [B,H,W], `u` and `v` [B,ceil(H/2),ceil(W/2)].
+    `depth` 8: uint8 tensors, the result is preprocess_nv12 of the interleaved chroma planes bit for bit.  `depth` 10 / 12 / 16: 16-bit
+    tensors (`word_dtype()` or torch.int16; numpy uint16 arrays are uploaded first) with the sample in the word's LOW bits - yuv420p10le,
+    Y4M's C420p10 -, the result is preprocess_p010 of the words shifted to the top; `standard` then also takes "bt2020".  Device tensors or
+    pinned host tensors (read in place over PCIe; `device` names the GPU), each plane strided in its row and batch dimensions on its own.
+    YV12 is the caller swapping `u` and `v`.  `out`: a contiguous fp32 [B,3,H,W] device tensor to fill."""
+    import torch
+    d = _planar_depth(depth)
+    if d > 8:
+        y, u, v = _words(y, device), _words(u, device), _words(v, device)
+    B, H, W, planes = _yuv420p_planes(y, u, v, d, "preprocess_yuv420p")
+    st = yuv_standard_code(standard, full_range) if d == 8 else yuv_standard_code_deep(standard, full_range)
+    od = _order_code(order)
+    dev = y.device if y.is_cuda else torch.device(device if device is not None else "cuda")
+    m, s = _stats(mean, std, 3)
+    if out is None:
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, H, W) and out.is_contiguous()):
+        raise ValueError("preprocess_yuv420p: out must be a contiguous fp32 [B,3,H,W] device tensor")
+    with torch.cuda.device(dev):
+        check(load().emavfi_preprocess_yuv420p(*planes, out.data_ptr(), B, H, W, d, st, od, m, s, _stream()), "emavfi_preprocess_yuv420p")
+    return out
+
+
+def postprocess_yuv420p(frames_nchw, depth=8, standard="bt601", full_range=False, order="bgr", denormalize=True, mean=IMAGENET_MEAN,
+                        std=IMAGENET_STD, out=None):
+    """fp32 [B,3,H,W] -> planar 4:2:0 (y [B,H,W], u and v [B,ceil(H/2),ceil(W/2)]): at `depth` 8 the bytes postprocess_nv12 writes,
+    de-interleaved; at 10 / 12 / 16 the words postprocess_p010 writes, shifted down into the LOW bits (the high bits are zero).
+    `out=(y, u, v)`: device or pinned host tensors to fill, strided as for preprocess_yuv420p; bytes between the rows of a pitched
+    destination are left as they were.  Without `out` the planes are dense device tensors (uint8 / `word_dtype()`)."""
+    import torch
+    _require_cuda(frames_nchw)
+    x = _f32c(frames_nchw)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError("postprocess_yuv420p: [B,3,H,W] tensor expected")
+    B, _, H, W = x.shape
+    d = _planar_depth(depth)
+    st = yuv_standard_code(standard, full_range) if d == 8 else yuv_standard_code_deep(standard, full_range)
+    od = _order_code(order)
+    m, s = _stats(mean, std, 3, ctypes.c_double)
+    if out is None:
+        dt = torch.uint8 if d == 8 else word_dtype()
+        y = torch.empty(B, H, W, dtype=dt, device=x.device)
+        u = torch.empty(B, (H + 1) // 2, (W + 1) // 2, dtype=dt, device=x.device)
+        v = torch.empty_like(u)
+    else:
+        try:
+            y, u, v = out
+        except (TypeError, ValueError):
+            raise ValueError("postprocess_yuv420p: out must be the three planes (y, u, v)") from None
+    *shape, planes = _yuv420p_planes(y, u, v, d, "postprocess_yuv420p(out=)")
+    if tuple(shape) != (B, H, W):
+        raise ValueError(f"postprocess_yuv420p: out must be (y [B,H,W], u, v [B,ceil(H/2),ceil(W/2)]) for frames {(B, H, W)}")
+    with torch.cuda.device(x.device):
+        check(load().emavfi_postprocess_yuv420p(x.data_ptr(), *planes, B, H, W, d, st, od, m, s, 1 if denormalize else 0, _stream()),
+              "emavfi_postprocess_yuv420p")
+    return y, u, v
 
 # ---------------------------------------------------------------- scene cuts on the device (include/emavfi.h, "SCENE CUT DEFINITION")
 SCENE_GRID = 32          # EMAVFI_SCENE_GRID

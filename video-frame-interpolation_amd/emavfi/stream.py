@@ -62,6 +62,16 @@ already performs - no new synchronisation point.  Order and counts of the output
 the flagged pairs of the last ``run`` (global frame indices, in order), ``scene_scores`` every pair's.  Known waste: the forwards of a flagged
 pair (in recursive mode all of its midpoints) are still computed and then overwritten - skipping them would need a read-back before the
 forward is enqueued.
+``pixel_format="yuv420p8"`` / ``"yuv420p10"`` / ``"yuv420p12"`` / ``"yuv420p16"`` (opt-in) takes and yields PLANAR 4:2:0 frames as a YUV4MPEG2
+stream and every software decoder hold them (``emavfi.y4m``): one contiguous buffer of H rows of Y, then the dense U plane, then the dense V
+plane - numpy ``[H*3/2, W]``, uint8 at depth 8, uint16 with the sample in the word's LOW bits above; even H and W.  The slot has NV12's / P010's
+byte size, so staging, copies, order and counts are theirs; only the plane views and the two kernels differ (emavfi_preprocess_yuv420p /
+_postprocess_yuv420p, defined by composition on the NV12 / P010 entries: a planar stream is the NV12 / P010 stream de-interleaved).
+``"yuv420p8"`` supports ``scene_threshold`` and ``evaluate()`` as NV12 does (the Y plane) and ``scale`` / ``size`` by three emavfi_resize_u8
+launches (Y, U, V as one-channel images) into a resized planar buffer ahead of the preprocess kernel - the same bytes as NV12's resized
+planes, since channels are resized independently; the deeper planar formats refuse all three as P010 does.
+``run_chunked(frames, chunk_pairs=64)`` is ``run()`` over an iterable of unknown length - a pipe - in bounded memory: at most
+``chunk_pairs * frame_interval + 1`` source frames are held, and the yielded sequence is ``run(list(frames))``'s byte for byte.
 ``evaluate(frames, every=1)`` scores the model by the held-out protocol instead of emitting frames: every target frame ``t`` is interpolated
 from ``t - 1`` and ``t + 1`` and compared with the true ``t`` on the device (the frame-metric definition of include/emavfi.h: per-channel sum
 of squared differences and 11 x 11 Gaussian-window SSIM); only the metric words travel to the host, behind the ``done`` event the drain
@@ -131,6 +141,7 @@ class Evaluation:
 
 class FrameInterpolator:
     _depth = 0   # bits per sample of a 16-bit-word pixel format ("p010": 10, ...); 0 for the byte formats
+    _planar = _yuv8 = False
 
     def __init__(self, model, interpolation_factor: int = 1, frame_interval: int = 1, batch_pairs: int = 8,
                  reference_quirks: bool = True, mode: str = "reference", device=None, copy_out: bool = True, zero_copy: bool = False,
@@ -144,10 +155,13 @@ class FrameInterpolator:
             raise ValueError("recursive midpoints need interpolation_factor = 2^k - 1 (1, 3, 7, ...)")
         if numa not in ("off", "auto"):
             raise ValueError("numa must be 'off' or 'auto'")
-        if pixel_format not in ("bgr24", "nv12", *_lib.DEPTHS):
-            raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames), 'nv12' (uint8 [H*3/2, W] frames) or 'p010' / 'p012' / 'p016' "
-                             "(uint16 [H*3/2, W] frames)")
-        self._depth = _lib.DEPTHS.get(pixel_format, 0)         # bits per sample of a 16-bit-word format, 0 for the byte formats
+        if pixel_format not in ("bgr24", "nv12", *_lib.DEPTHS, *_lib.PLANAR_DEPTHS):
+            raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames), 'nv12' (uint8 [H*3/2, W] frames), 'p010' / 'p012' / 'p016' "
+                             "(uint16 [H*3/2, W] frames) or planar 'yuv420p8' (uint8) / 'yuv420p10' / 'yuv420p12' / 'yuv420p16' (uint16)")
+        self._planar = pixel_format in _lib.PLANAR_DEPTHS      # Y, U, V planes one after the other instead of Y and interleaved UV
+        self._yuv8 = pixel_format in ("nv12", "yuv420p8")      # byte frames [H*3/2, W] whose first H rows are the Y plane
+        # bits per sample of a 16-bit-word format, 0 for the byte formats
+        self._depth = _lib.DEPTHS.get(pixel_format, 0) or (0 if self._yuv8 else _lib.PLANAR_DEPTHS.get(pixel_format, 0))
         if self._depth:
             _lib.yuv_standard_code_deep(yuv_standard, yuv_full_range)   # raises on an unknown standard; knows "bt2020"
             if scale is not None or size is not None:
@@ -216,8 +230,8 @@ class FrameInterpolator:
             return int(H), int(W)
         if not (1 <= Hd <= _lib.RESIZE_MAX_DIM and 1 <= Wd <= _lib.RESIZE_MAX_DIM):
             raise ValueError(f"the resized frame {(Hd, Wd)} must lie in 1..{_lib.RESIZE_MAX_DIM} per dimension")
-        if pixel_format == "nv12" and (Hd % 2 or Wd % 2):
-            raise ValueError(f"pixel_format='nv12': the packed [H*3/2, W] layout needs an even destination H and W, got {(Hd, Wd)}")
+        if pixel_format in ("nv12", "yuv420p8") and (Hd % 2 or Wd % 2):
+            raise ValueError(f"pixel_format={pixel_format!r}: the packed [H*3/2, W] layout needs an even destination H and W, got {(Hd, Wd)}")
         return Hd, Wd
 
     # ---- the reference's frame selection (inference.py:158-201), as (pairs, tail) over frame indices
@@ -300,15 +314,15 @@ class FrameInterpolator:
         self._per = per
         if self._depth:
             Hs, Ws, C = shape[0] * 2 // 3, shape[1] // 2, 3   # the bytes of [H*3/2, W] words: rows of 2 W bytes
-        elif self.pixel_format == "nv12":
-            Hs, Ws, C = shape[0] * 2 // 3, shape[1], 3   # [H*3/2, W]: Y rows, then the UV rows
+        elif self._yuv8:
+            Hs, Ws, C = shape[0] * 2 // 3, shape[1], 3   # [H*3/2, W]: Y rows, then the UV rows (planar: the U plane, then the V plane)
         else:
             Hs, Ws, C = shape
         fin = tuple(shape)                               # a frame as it arrives: [Hs, Ws, C] or [Hs*3/2, Ws]
         H, W = self.output_size(Hs, Ws, self.scale, self.size, self.pixel_format)
         self._dst = (H, W)
         # a frame as it leaves, at the size the model runs at
-        fs = fin if self._depth else (H * 3 // 2, W) if self.pixel_format == "nv12" else (H, W, C)
+        fs = fin if self._depth else (H * 3 // 2, W) if self._yuv8 else (H, W, C)
         nb, nout = self.batch_pairs, max(self.factor if self.mode == "recursive" else 1, 1)
         self._shape = shape
         self._slots = []
@@ -328,6 +342,8 @@ class FrameInterpolator:
                 "d_in": torch.empty(per * nb, *fin, dtype=torch.uint8, device=self.device),
                 # the resized bytes of the slot's frames, where frames leave as they arrived (reference_quirks=False) and arrive at another size
                 "d_rs": torch.empty(per * nb, *fs, dtype=torch.uint8, device=self.device) if self._resize and not self.quirks else None,
+                # planar frames are resized into a buffer of their own ahead of the preprocess kernel: this one where neither d_rs nor e_rs serves
+                "p_rs": torch.empty(per * nb, *fs, dtype=torch.uint8, device=self.device) if self._planar and self._resize and self.quirks else None,
                 "d_pred": torch.empty(nb * nout, *fs, dtype=torch.uint8, device=self.device),
                 "d_src": torch.empty(nb, *fs, dtype=torch.uint8, device=self.device),
                 # consumed: the preprocess kernel has read h_in (the host may restage it); pre: x is ready; fwd: the forward has read x
@@ -338,7 +354,7 @@ class FrameInterpolator:
             if per > 2:
                 # evaluate(): the resized bytes of the staged frames whatever reference_quirks says (the ground truth at the size the model
                 # runs at), and the metric words {sse, ssimq} per target and channel, on the device and pinned
-                mc = 1 if self.pixel_format == "nv12" else C
+                mc = 1 if self._yuv8 else C
                 self._slots[-1].update({"e_rs": torch.empty(per * nb, *fs, dtype=torch.uint8, device=self.device) if self._resize else None,
                                         "met": torch.zeros(nb, mc, 2, dtype=torch.int64, device=self.device),
                                         "h_met": torch.zeros(nb, mc, 2, dtype=torch.int64).pin_memory()})
@@ -366,9 +382,32 @@ class FrameInterpolator:
         H = buf.shape[1] * 2 // 3
         return buf[:, :H].view(torch.int16), buf[:, H:].view(torch.int16).unflatten(2, (buf.shape[2] // 4, 2))
 
+    def _planes3(self, buf):
+        """Y [n,H,W], U and V [n,H/2,W/2] views of n contiguous planar 4:2:0 frames: bytes [n, H*3/2, W] or, as 16-bit words, the bytes
+        [n, H*3/2, 2 W] of the deeper formats.  The chroma planes are dense: they need not start on a row of `buf`."""
+        n, H = buf.shape[0], buf.shape[1] * 2 // 3
+        y, c = buf[:, :H], buf[:, H:]
+        if self._depth:
+            y, c = y.view(torch.int16), c.view(torch.int16)
+        c = c.view(n, 2, H // 2, c.shape[2] // 2)
+        return y, c[:, 0], c[:, 1]
+
+    def _resize_planar(self, src, dst, device=None):
+        """the three planes of `src` resized into those of `dst`, each as a one-channel image (chroma to H/2 x W/2)"""
+        for a, b in zip(self._planes3(src), self._planes3(dst)):
+            _lib.resize_u8(a.unsqueeze(-1), (b.shape[1], b.shape[2]), out=b.unsqueeze(-1), device=device)
+
     def _pre_kernel(self, buf, out=None, device=None, resized=None):
-        """`resized`: with scale / size, a buffer of frames at the destination size that also receives the resized bytes"""
+        """`resized`: with scale / size, a buffer of frames at the destination size that also receives the resized bytes (planar frames
+        are resized into it first: without one, a fresh buffer is made)"""
         size = self._dst if self._resize else None
+        if self._planar:
+            if size is not None:
+                if resized is None:
+                    resized = torch.empty(buf.shape[0], size[0] * 3 // 2, size[1], dtype=torch.uint8, device=device if device is not None else buf.device)
+                self._resize_planar(buf, resized, device)
+                buf = resized
+            return _lib.preprocess_yuv420p(*self._planes3(buf), self._depth or 8, self.yuv["standard"], self.yuv["full_range"], device=device, out=out)
         if self._depth:
             y, uv = self._planes16(buf)
             return _lib.preprocess_p010(y, uv, self._depth, self.yuv["standard"], self.yuv["full_range"], device=device, out=out)
@@ -390,7 +429,7 @@ class FrameInterpolator:
     def _scene_decide(self, slot, buf, ia, ib):
         """signatures of the staged frames `buf` (source size; NV12: the Y plane as a 1-channel image of pitch W), then every pair's flag and score"""
         n, sig = len(ia), slot["sig"][:buf.shape[0]]
-        img = self._planes(buf)[0].unsqueeze(-1) if self.pixel_format == "nv12" else buf
+        img = self._planes(buf)[0].unsqueeze(-1) if self._yuv8 else buf
         _lib.luma_signature_u8(img, out=sig, device=self.device)
         size = (img.shape[1], img.shape[2])
         a, b = self._run(sig, ia), self._run(sig, ib)
@@ -413,6 +452,10 @@ class FrameInterpolator:
     def _resized_bytes(self, frame):
         """one source frame (numpy) at the destination size, as the device resizes it"""
         src = torch.from_numpy(frame).unsqueeze(0).to(self.device)
+        if self._planar:
+            out = torch.empty(1, self._dst[0] * 3 // 2, self._dst[1], dtype=torch.uint8, device=self.device)
+            self._resize_planar(src, out)
+            return out.cpu().numpy()[0]
         if self.pixel_format == "nv12":
             (H, W), (y, uv) = self._dst, self._planes(src)
             out = torch.empty(1, H * 3 // 2, W, dtype=torch.uint8, device=self.device)
@@ -423,6 +466,12 @@ class FrameInterpolator:
         return _lib.resize_u8(src, self._dst).cpu().numpy()[0]
 
     def _post_kernel(self, x, denormalize, out=None):
+        if self._planar:
+            if out is None:
+                out = torch.empty(x.shape[0], x.shape[2] * 3 // 2, x.shape[3] * (2 if self._depth else 1), dtype=torch.uint8, device=x.device)
+            _lib.postprocess_yuv420p(x, self._depth or 8, self.yuv["standard"], self.yuv["full_range"], denormalize=denormalize,
+                                     out=self._planes3(out))
+            return out
         if self._depth:
             if out is None:
                 out = torch.empty(x.shape[0], x.shape[2] * 3 // 2, x.shape[3] * 2, dtype=torch.uint8, device=x.device)
@@ -533,18 +582,19 @@ class FrameInterpolator:
             if first.shape[0] % 3 or first.shape[1] % 2:
                 raise ValueError(f"FrameInterpolator.{what}: the packed {self.pixel_format.upper()} layout [H*3/2, W] needs even H and W")
             return
-        if self.pixel_format == "nv12":
+        if self._yuv8:
+            name = self.pixel_format.upper() if self._planar else "NV12"
             for f in frames.values():
                 if f.dtype != np.uint8 or f.ndim != 2 or f.shape != first.shape:
-                    raise ValueError(f"FrameInterpolator.{what}: same-shape uint8 [H*3/2, W] NV12 frames expected")
+                    raise ValueError(f"FrameInterpolator.{what}: same-shape uint8 [H*3/2, W] {name} frames expected")
             if first.shape[0] % 3 or first.shape[1] % 2:   # H = 2 * rows / 3 is then even
-                raise ValueError(f"FrameInterpolator.{what}: the packed NV12 layout [H*3/2, W] needs even H and W")
+                raise ValueError(f"FrameInterpolator.{what}: the packed {name} layout [H*3/2, W] needs even H and W")
         else:
             for f in frames.values():
                 if f.dtype != np.uint8 or f.ndim != 3 or f.shape != first.shape:
                     raise ValueError(f"FrameInterpolator.{what}: same-shape uint8 HWC frames expected")
 
-    def run(self, frames, rank: int = 0, world: int = 1) -> Iterator[np.ndarray]:
+    def run(self, frames, rank: int = 0, world: int = 1, *, _emit_tail: bool = True) -> Iterator[np.ndarray]:
         """Yields uint8 HWC frames (``pixel_format="nv12"``: uint8 [H*3/2, W] frames; ``"p010"`` / ``"p012"`` / ``"p016"``: uint16 [H*3/2, W]
         frames) in the order the reference's writer receives them.
 
@@ -608,8 +658,9 @@ class FrameInterpolator:
                 self._pre.wait_event(slot["fwd"])
                 self._pre.wait_event(slot["done"])
                 rs = slot["d_rs"][:nup] if slot["d_rs"] is not None else None
+                rz = slot["p_rs"][:nup] if slot["p_rs"] is not None else rs   # where the preprocess leaves resized bytes; `rs`: they are emitted
                 if self.zero_copy:
-                    x = self._pre_kernel(slot["h_in"][:nup], device=self.device, out=slot["x"][:nup], resized=rs)   # distinct frames, read over PCIe, normalised once
+                    x = self._pre_kernel(slot["h_in"][:nup], device=self.device, out=slot["x"][:nup], resized=rz)   # distinct frames, read over PCIe, normalised once
                     if self.scene is not None:
                         self._scene_decide(slot, slot["h_in"][:nup], ia, ib)
                         if not self.quirks and rs is None:
@@ -620,7 +671,7 @@ class FrameInterpolator:
                 else:
                     slot["d_in"][:nup].copy_(slot["h_in"][:nup], non_blocking=True)                       # hipMemcpyAsync pinned -> HBM (SDMA)
                     slot["consumed"].record(self._pre)
-                    x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=rs)             # distinct frames, normalised once
+                    x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=rz)             # distinct frames, normalised once
                     if self.scene is not None:
                         self._scene_decide(slot, slot["d_in"][:nup], ia, ib)
                 slot["pre"].record(self._pre)
@@ -684,13 +735,58 @@ class FrameInterpolator:
             prev = (slot, chunk)
         if prev is not None:
             yield from drain(*prev)
-        if not tail:                         # the stream's final frame belongs to the highest rank
+        if not tail or not _emit_tail:       # the stream's final frame belongs to the highest rank (run_chunked: to the last chunk)
             return
         if last_roundtrip and self.quirks:   # skip-branch ending: the reference writes the round-tripped frame
             src = torch.from_numpy(frames[last]).unsqueeze(0).to(self.device)
             yield words(self._post_kernel(self._pre_kernel(src), True).cpu().numpy()[0])
         else:
             yield self._resized_bytes(frames[last]) if self._resize else words(frames[last])
+
+    @staticmethod
+    def chunk_plan(n_frames: int, frame_interval: int, chunk_pairs: int = 64):
+        """How ``run_chunked`` cuts a stream of ``n_frames`` frames: ``[(lo, hi, final)]`` - chunk c holds the global frames ``[lo, hi)`` =
+        ``[c L, c L + L]`` with ``L = chunk_pairs * frame_interval`` (consecutive chunks share one frame; every chunk starts on a multiple of
+        ``frame_interval``, which keeps the reference's ``frame_num % frame_interval`` phase), runs through ``run()`` on its own, and only the
+        ``final`` one emits its tail frame.  A stream that ends on a chunk boundary has a final chunk of one frame: the tail alone.  Pure host
+        logic (no device needed)."""
+        if frame_interval < 1 or chunk_pairs < 1:
+            raise ValueError("frame_interval >= 1 and chunk_pairs >= 1 required")
+        L, lo, plan = chunk_pairs * frame_interval, 0, []
+        while lo < n_frames:
+            if lo + L + 1 <= n_frames:
+                plan.append((lo, lo + L + 1, False))
+                lo += L
+            else:
+                plan.append((lo, n_frames, True))
+                break
+        return plan
+
+    def run_chunked(self, frames: Iterable[np.ndarray], chunk_pairs: int = 64) -> Iterator[np.ndarray]:
+        """``run(list(frames))``, byte for byte, over any iterable - no ``len()``, so a pipe works - holding at most
+        ``chunk_pairs * frame_interval + 1`` source frames: the stream is cut as ``chunk_plan`` says, each chunk goes through ``run()``,
+        and the tail frame of every chunk but the last is neither yielded nor computed.  ``scene_cuts`` / ``scene_scores`` accumulate over
+        the chunks with global frame indices.  Single process: a stream of unknown length cannot be sharded over ranks."""
+        if isinstance(chunk_pairs, bool) or not isinstance(chunk_pairs, int) or chunk_pairs < 1:
+            raise ValueError("run_chunked: chunk_pairs must be an integer >= 1")
+        L, it, held, lo = chunk_pairs * self.interval, iter(frames), [], 0
+        cuts, scores = [], []
+        self.scene_cuts, self.scene_scores = [], []
+        while True:
+            for f in it:
+                held.append(f)
+                if len(held) == L + 1:
+                    break
+            final = len(held) < L + 1          # the stream ended inside this chunk (a full chunk is never final: its last frame starts the next)
+            if held:
+                self.scene_cuts, self.scene_scores = [], []     # this chunk's own, whatever run() does with them
+                yield from self.run(held, _emit_tail=final)
+                cuts += [(a + lo, b + lo, sc) for a, b, sc in self.scene_cuts]
+                scores += [(a + lo, b + lo, sc) for a, b, sc in self.scene_scores]
+                self.scene_cuts, self.scene_scores = list(cuts), list(scores)
+            if final:
+                return
+            held, lo = held[-1:], lo + L
 
     def evaluate(self, frames, every: int = 1, rank: int = 0, world: int = 1) -> Evaluation:
         """Scores the model on a clip by the held-out protocol and returns an ``Evaluation``: every target ``t = 1, 1 + every, ...`` with
@@ -714,12 +810,12 @@ class FrameInterpolator:
             frames = list(frames)
         plan = self.evaluation_plan(len(frames), every, rank, world)
         if not plan:                               # fewer than three frames, or a rank without a share: nothing is touched, size (0, 0)
-            return Evaluation((0, 0), 1 if self.pixel_format == "nv12" else 3)
+            return Evaluation((0, 0), 1 if self._yuv8 else 3)
         frames = {i: np.ascontiguousarray(frames[i]) for i in sorted({f for item in plan for f in item})}   # this rank's frames only
         first = frames[plan[0][1]]
         self._check_frames(frames, first, "evaluate")
         self._alloc(first.shape, per=3)
-        nv12 = self.pixel_format == "nv12"
+        nv12 = self._yuv8                         # the Y plane is the first H rows of NV12 and of planar frames alike
         H, W = self._dst
         result = Evaluation((H, W), 1 if nv12 else first.shape[2])
         main = torch.cuda.current_stream(self.device)
