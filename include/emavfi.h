@@ -158,7 +158,22 @@ int emavfi_packed_check(int in_channels, int mid_channels, int num_blocks, int d
  * `taps` is NULL, or 5 + num_blocks device pointers (any may be NULL) that receive NCHW fp32
  * copies of the intermediates the golden vectors hold:
  *   [0] feat [B,mid,H,W]  [1] ctx [B,mid]  [2] flow [B,2,H,W]  [3] warped [B,in_channels,H,W]
- *   [4] reserved  [5+i] output of attention block i [B,mid+3,H,W]. */
+ *   [4] reserved  [5+i] output of attention block i [B,mid+3,H,W].
+ *
+ * THE WORKSPACE CONTRACT, for this and every other entry that takes (workspace, workspace_bytes) - emavfi_forward*, emavfi_conv3x3,
+ * emavfi_deform_conv2d, emavfi_mdcn*, emavfi_context, emavfi_reconstruct, emavfi_frame_metrics_u8 - with the size its
+ * *_workspace_bytes function reports for the same arguments:
+ *   - the contents of the workspace on entry are ARBITRARY: hipMalloc'ed and never written, another call's activations, NaN bit
+ *     patterns (0 x NaN is NaN on the matrix pipe, so "finite data against zero weights" is not a property the caller owes);
+ *   - an entry reads no byte of the workspace that the same call has not written, and no byte outside any buffer it is given, that
+ *     can change a result: whatever a kernel over-fetches (pad lanes, spare tap slots, slack behind the last pixel) is either
+ *     written by the call first or discarded before it meets arithmetic; no index, bound or route is ever taken from such a byte;
+ *   - an entry writes nothing outside [workspace, workspace + the reported size) and outside the outputs' own shapes; fewer bytes
+ *     than reported are refused with EMAVFI_E_WORKSPACE before any device work;
+ *   - on exit only the census (emavfi_forward_census, emavfi_mdcn_census) is defined, until the next call on that workspace; every
+ *     other byte is scratch.
+ * tests/test_gpu_workspace.py holds every entry to this: exact-size, guard-banded workspaces pre-filled with 0x00, 0xFF and 0x7B must
+ * give bit-identical outputs, taps and census words. */
 size_t emavfi_workspace_bytes(int in_channels, int mid_channels, int num_blocks,
                               int B, int H, int W, int dtype);
 int emavfi_forward(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes,

@@ -550,6 +550,57 @@ def test_mdcn_entry_validates_its_arguments():
     assert L.emavfi_mdcn(fake, fake, fake, fake, fake, fake, 1, 67, 8, 8, lib.BF16, 0, fake, 16, None) == -3
 
 
+def test_every_compute_entry_refuses_a_short_workspace_before_any_device_work():
+    """need - 1 and 0 bytes: EMAVFI_E_WORKSPACE (-3) and a message that names the bytes needed and the bytes given.  Every pointer here is
+    fake and never dereferenced: the size check runs before the entry's first HIP call.  emavfi_forward_adaptive needs a route state emavfi_route_state_init wrote on a
+    device and emavfi_frame_metrics_u8 has its own test (tests/test_metrics_cpu.py); the adaptive forward's refusal is in
+    tests/test_gpu_workspace.py."""
+    L = lib.load()
+    fake = ctypes.c_void_p(256)
+    B, H, W = 2, 23, 37
+    entries = []
+    for dt in (lib.F32, lib.BF16, lib.F16, lib.AMP16, lib.F32X3):
+        need = L.emavfi_workspace_bytes(3, 64, 3, B, H, W, dt)
+        blob = L.emavfi_packed_bytes(3, 64, 3, dt)
+        entries.append((f"forward dtype {dt}", need, lambda n, dt=dt, blob=blob: L.emavfi_forward(
+            3, 64, 3, fake, blob, fake, fake, fake, fake, n, B, H, W, dt, None, None)))
+        entries.append((f"forward_routed dtype {dt}", need, lambda n, dt=dt, blob=blob: L.emavfi_forward_routed(
+            3, 64, 3, fake, blob, fake, fake, fake, fake, n, B, H, W, dt, None, None, None, 0, 0, None)))
+        entries.append((f"forward_census dtype {dt}", need, lambda n, dt=dt: L.emavfi_forward_census(3, 64, 3, B, H, W, dt, fake, n, fake, None)))
+    for dt in (lib.F32, lib.BF16, lib.F16, lib.AMP16):
+        need = L.emavfi_context_workspace_bytes(B, 64, H, W, dt)
+        assert need == L.emavfi_reconstruct_workspace_bytes(B, 64, H, W, dt)
+        params = (ctypes.c_void_p * 8)(*[256] * 8)
+        pp = ctypes.cast(params, ctypes.POINTER(ctypes.c_void_p))
+        entries.append((f"context dtype {dt}", need, lambda n, dt=dt, pp=pp: L.emavfi_context(fake, pp, fake, B, 64, H, W, dt, fake, n, None)))
+        entries.append((f"reconstruct dtype {dt}", need, lambda n, dt=dt, pp=pp: L.emavfi_reconstruct(fake, pp, fake, B, 64, H, W, dt, fake, n, None)))
+        for flags in (0, lib.MDCN_SPLIT_TAIL) if dt in (lib.BF16, lib.F16) else (0,):
+            need = L.emavfi_mdcn_workspace_bytes(B, 67, H, W, dt, flags)
+            entries.append((f"mdcn dtype {dt} flags {flags}", need, lambda n, dt=dt, flags=flags: L.emavfi_mdcn(
+                fake, fake, fake, fake, fake, fake, B, 67, H, W, dt, flags, fake, n, None)))
+            entries.append((f"mdcn_routed dtype {dt} flags {flags}", need, lambda n, dt=dt, flags=flags: L.emavfi_mdcn_routed(
+                fake, fake, fake, fake, fake, fake, B, 67, H, W, dt, flags, 0, fake, n, None, 0, None)))
+            entries.append((f"mdcn_census dtype {dt} flags {flags}", need, lambda n, dt=dt, flags=flags: L.emavfi_mdcn_census(
+                B, 67, H, W, dt, flags, fake, n, fake, None)))
+    for dt in (lib.F32, lib.BF16, lib.F16, lib.F32X3):
+        for cin, cout, stride in ((11, 27, 1), (64, 64, 1), (64, 128, 2)):
+            need = L.emavfi_conv3x3_workspace_bytes(B, cin, cout, H, W, stride, dt)
+            entries.append((f"conv3x3 dtype {dt} {cin}->{cout} s{stride}", need, lambda n, dt=dt, a=(cin, cout, H, W, stride): L.emavfi_conv3x3(
+                fake, fake, fake, fake, B, *a, 0, dt, fake, n, None)))
+    for dt in (lib.F32, lib.BF16, lib.F16):
+        for C in (67, 11):
+            need = L.emavfi_deform_conv2d_workspace_bytes(B, C, C, H, W, dt)
+            entries.append((f"deform_conv2d dtype {dt} C {C}", need, lambda n, dt=dt, C=C: L.emavfi_deform_conv2d(
+                fake, fake, fake, fake, fake, fake, B, C, C, H, W, dt, fake, n, None)))
+    assert len(entries) >= 50
+    for what, need, call in entries:
+        assert need > 0 and need % 256 == 0, (what, need, lib.last_error())
+        for short in (need - 1, 0):
+            rc = call(short)
+            msg = lib.last_error()
+            assert rc == -3 and f"{need} bytes" in msg and f"got {short}" in msg, (what, short, rc, msg)
+
+
 def test_switch_word_is_latched_and_settable():
     """the launch-sequence switches are read from the environment once; tests flip them through emavfi_debug_switches."""
     L = lib.load()

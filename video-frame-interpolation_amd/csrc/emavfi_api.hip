@@ -516,9 +516,12 @@ constexpr size_t kCensusBytes = (size_t)kMaxBlocks * kCensusBlock;
 
 // The compact tail of the fusion input (channels mid .. mid + 2, the warped frame): FOUR 16-bit channels = 8 bytes per pixel (round 6; was 8
 // channels = 16 bytes).  The pack kernel's window DMA fetches 16 bytes per pixel from it - the pixel's tail and its right neighbour's,
-// which land in channels 68..71 of the window slot: finite values against zero weights, never read by the 8-byte tail reads - so the
-// buffer keeps 8 bytes of slack behind its last pixel (it lives in the 16-channel packed-input buffer: plenty).  The warp then moves
-// 8 + 12 + 8 = 28 bytes per pixel instead of 36.
+// which land in channels 68..71 of the window slot.  No arithmetic ever sees those 8 bytes, whatever they hold (for the last pixel of the
+// buffer they are slack that nothing in this mode writes: the workspace contract of include/emavfi.h owes no finite data there): every
+// LDS read of a slot's tail is 8 bytes wide (deform3_stages.inl, lds_read8: channels 64..67 only), and channels 68..71 of the OUTPUT are
+// stored from the bias alone (its epilogue).  The over-fetch only has to stay inside the allocation, so the buffer keeps 8 bytes of
+// slack behind its last pixel (it lives in the 16-channel packed-input buffer: plenty).  The warp then moves 8 + 12 + 8 = 28 bytes per
+// pixel instead of 36.
 constexpr int kTailPs = 4;
 
 struct FwdBuffers {
