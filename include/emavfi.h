@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -496,6 +496,60 @@ int emavfi_scene_flags(const unsigned *sig_a, size_t stride_a_words, const unsig
                        unsigned threshold, unsigned *flags, unsigned *scores, void *stream);
 int emavfi_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const unsigned char *alt, size_t alt_stride, const unsigned *flags, int n,
                           size_t frame_bytes, void *stream);
+
+/* Frame-rate conversion.  The model produces midpoints only, so an output frame at an arbitrary time is assembled from the dyadic tree of
+ * recursive midpoints between two source frames: a schedule the host knows ahead of time, and a selection or blend of already emitted frames
+ * on the device.  The reference multiplies a frame rate by an integer and nothing else (inference.py:117: `--target-fps 60` on a 24 fps clip
+ * writes 72 fps); this is an addition, off unless asked for.
+ *
+ * TEMPORAL RESAMPLE DEFINITION (the one place).  This is the project's own definition: it claims agreement with no outside tool (ffmpeg's
+ * fps / minterpolate / framerate filters, ...).  All arithmetic is integer, `/` is floor division: host, oracle and device agree bit for bit.
+ *   Time grid.  The input rate Fi and the output rate Fo are positive rationals with Fo >= Fi; P / Q = Fi / Fo in lowest terms (P <= Q).
+ *     Output frame k = 0, 1, ... sits at source time k P / Q, in source-frame intervals: s = k P / Q, r = k P - s Q (0 <= r < Q).  A clip of
+ *     n frames yields k = 0 .. ((n - 1) Q) / P, that is ((n - 1) Q) / P + 1 frames; n = 0 yields nothing, n = 1 the one frame.  r = 0 is
+ *     source frame s itself.
+ *   Nodes.  Depth D in 1..5, G = 2^D.  Node j (0 < j < G) of the pair (s, s + 1) is the recursive midpoint the harness's mode "recursive"
+ *     with factor G - 1 emits as its j-th prediction: the model's midpoint of node j - (j & -j) and node j + (j & -j) (its parents), with
+ *     the same fp32 recursion and the same re-normalisation of a midpoint before it is fed back.  Node 0 is source s, node G source s + 1.
+ *   method "nearest": j = (2 r G + Q) / (2 Q) (0..G; a tie goes to the later node).  The output is node j.
+ *   method "blend": j0 = (r G) / Q, e = r G - j0 Q, w = (256 e + Q / 2) / Q (0..256).  Per sample out = ((256 - w) A + w B + 128) >> 8 with
+ *     A = node j0, B = node j0 + 1.  w = 0 is A alone and w = 256 is B alone: the other frame is not needed.  A sample is a byte, or the
+ *     depth-bit value (word >> shift) & (2^depth - 1) of a 16-bit little-endian word, written back as v << shift.  The blend acts on the
+ *     frames AS EMITTED: it is the same arithmetic for bgr24, NV12, P01x (shift = 16 - depth) and the planar formats (shift = 0), and it
+ *     ignores the plane structure.  A blend mixes two model outputs 1 / G of a source interval apart; it is no motion compensation.
+ *   Needed nodes of a pair: the nodes its outputs use, closed under parents; only these are computed.  24 -> 60 (P / Q = 2 / 5), D = 3,
+ *     n = 5, blend, as (k, s, j0, j1, w) - j1 = j0 where w = 0:
+ *       (0,0,0,0,0) (1,0,3,4,51) (2,0,6,7,102) (3,1,1,2,154) (4,1,4,5,205) (5,2,0,0,0) (6,2,3,4,51) (7,2,6,7,102) (8,3,1,2,154) (9,3,4,5,205)
+ *       (10,4,0,0,0); needed nodes {2,3,4,6,7} for even pairs, {1,2,4,5,6} for odd pairs: 5 forwards per pair.  Nearest picks nodes 3, 6 | 2, 5
+ *       and needs {2,3,4,6} / {2,4,5,6}: 4 per pair.  30 -> 60 needs one forward per pair at any D, a ratio of 1 none.
+ *   Scene cuts (SCENE CUT DEFINITION above).  Every output with r > 0 of a flagged pair is source frame s.
+ *
+ * emavfi_resample_frames assembles n_out output frames, in emission order, at dst + k dst_stride from two pools of dense frames of
+ *   frame_bytes bytes each: `srcs` (n_srcs source frames as emitted, src_stride bytes apart) and `nodes` (n_nodes post-processed node
+ *   frames, node_stride apart; a pool of 0 frames may be NULL).  `table` is a HOST pointer to n_out entries {a, b, w, f, h}: a, b = a frame
+ *   index, plus EMAVFI_RESAMPLE_NODES when it counts in `nodes`; w = 0..256; f = 0, or 1 + an index into the device array `flags` of
+ *   n_flags u32 (may be NULL: then no entry is held); h = the index in `srcs` of the frame to hold.  The table is read and validated
+ *   before the call returns and nothing of it is retained: it travels as kernel arguments, EMAVFI_RESAMPLE_LAUNCH_CAP = 64 entries per
+ *   launch, so n_out entries take ceil(n_out / 64) launches.  Per entry:
+ *     flags != NULL, f != 0 and flags[f - 1] != 0: srcs[h] is copied;  else w = 0: a is copied;  else w = 256: b is copied;  else every
+ *     sample is blended.  A copy never reads (nor forms the address of) the frame it does not use; bytes between output frames are left as
+ *     they were.  sample_bytes 1 takes depth 8 and shift 0; sample_bytes 2 takes depth 10, 12 or 16 and shift 0 .. 16 - depth.
+ * EMAVFI_E_ARG (never an abort), the message naming the argument: a null dst or table, a null pool or flags with a count above 0, n_out below
+ *   1, a negative count, sample_bytes outside {1, 2}, a depth or shift outside the above, frame_bytes of 0 or above 2^40 or odd at
+ *   sample_bytes 2, a stride (of dst, or of a pool that has frames) below frame_bytes or odd at sample_bytes 2, size arithmetic that
+ *   overflows size_t, a dst / srcs / nodes pointer that is not 2-byte aligned at sample_bytes 2, a flags pointer that is not 4-byte aligned,
+ *   dst overlapping either pool, and per entry an a or b outside its pool (also where w makes it unused), w above 256, f beyond n_flags,
+ *   for f != 0 an h outside srcs.
+ * The frame pointers are device pointers or pinned (device-mapped) host memory, `flags` device (or pinned) memory.  Nothing is allocated,
+ *   nothing synchronises, all work goes on `stream`.  Access width: an entry moves 16 bytes per lane where every frame address IT USES
+ *   (dst and a, b or srcs[h]) is 16-byte aligned - the last frame_bytes % 16 bytes: bytes / words -, else bytes (sample_bytes 1) or words
+ *   throughout; all forms run the same per-element functions (csrc/resample_elem.h).  The kernel is short-lived and waits on nothing. */
+#define EMAVFI_RESAMPLE_NODES 0x80000000u
+#define EMAVFI_RESAMPLE_LAUNCH_CAP 64
+typedef struct { unsigned a, b, w, f, h; } emavfi_resample_entry;
+int emavfi_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
+                           const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_resample_entry *table,
+                           const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift, void *stream);
 
 /* Frame metrics on the device: how close is image a (an interpolated frame) to image b (the held-out true frame)?  The reference has no
  * evaluation script (its README names PSNR and SSIM against held-out ground-truth frames as the way to judge a model and calls an eval.py a

@@ -4,6 +4,7 @@
 #include "../../include/emavfi.h"
 #include "common.h"
 #include "misc_kernels.h"
+#include "resample_elem.h"
 #include "conv_first.inl"
 
 #include <atomic>
@@ -1653,6 +1654,76 @@ int emavfi_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const 
     if (!dst || !alt || !flags) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
     if ((uintptr_t)flags & 3) return fail(EMAVFI_E_ARG, "%s: the u32 pointer must be 4-byte aligned", what);
     EMAVFI_TRY(launch_hold_frames_u8(dst, dst_stride, rep, alt, alt_stride, flags, n, frame_bytes, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+// ---- temporal resampling (include/emavfi.h, "TEMPORAL RESAMPLE DEFINITION"): every check runs on the host, the table is read here and not kept
+static_assert(sizeof(emavfi_resample_entry) == sizeof(ResampleEntry) && EMAVFI_RESAMPLE_LAUNCH_CAP == RESAMPLE_CAP &&
+              EMAVFI_RESAMPLE_NODES == RESAMPLE_POOL_NODES, "header, misc_kernels.h and resample_elem.h disagree");
+
+// bytes from the first byte of frame 0 to the last byte of frame n - 1; false when the arithmetic overflows
+static bool resample_span(int n, size_t stride, size_t frame_bytes, size_t *span)
+{
+    return !(__builtin_mul_overflow((size_t)(n - 1), stride, span) || __builtin_add_overflow(*span, frame_bytes, span));
+}
+
+int emavfi_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
+                           const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_resample_entry *table,
+                           const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift, void *stream)
+{
+    const char *const what = "resample_frames";
+    if (n_out < 1) return fail(EMAVFI_E_ARG, "%s: n_out must be >= 1", what);
+    if (n_srcs < 0 || n_nodes < 0 || n_flags < 0) return fail(EMAVFI_E_ARG, "%s: n_srcs, n_nodes, n_flags must be >= 0", what);
+    if (sample_bytes != 1 && sample_bytes != 2) return fail(EMAVFI_E_ARG, "%s: sample_bytes = %d (sample_bytes must be 1 or 2)", what, sample_bytes);
+    if (sample_bytes == 1 ? depth != 8 : (depth != 10 && depth != 12 && depth != 16))
+        return fail(EMAVFI_E_ARG, "%s: depth = %d (depth must be 8 at sample_bytes 1 and 10, 12 or 16 at sample_bytes 2)", what, depth);
+    if (shift < 0 || shift > 8 * sample_bytes - depth)
+        return fail(EMAVFI_E_ARG, "%s: shift = %d (shift must lie in 0..%d at depth %d)", what, shift, 8 * sample_bytes - depth, depth);
+    if (frame_bytes < 1) return fail(EMAVFI_E_ARG, "%s: frame_bytes must be >= 1", what);
+    if (frame_bytes > ((size_t)1 << 40)) return fail(EMAVFI_E_ARG, "%s: frame_bytes %zu is above 2^40", what, frame_bytes);
+    const size_t odd = sample_bytes == 2 ? 1 : 0;
+    if (frame_bytes & odd) return fail(EMAVFI_E_ARG, "%s: frame_bytes %zu is odd at sample_bytes 2", what, frame_bytes);
+    const struct { const char *name; size_t stride; int n; } pools[3] = {{"dst_stride", dst_stride, n_out}, {"src_stride", src_stride, n_srcs},
+                                                                         {"node_stride", node_stride, n_nodes}};
+    size_t span[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) {
+        if (pools[k].n < 1) continue;
+        if (pools[k].stride < frame_bytes)
+            return fail(EMAVFI_E_ARG, "%s: %s %zu is smaller than frame_bytes %zu", what, pools[k].name, pools[k].stride, frame_bytes);
+        if (pools[k].stride & odd) return fail(EMAVFI_E_ARG, "%s: %s %zu is odd at sample_bytes 2", what, pools[k].name, pools[k].stride);
+        if (!resample_span(pools[k].n, pools[k].stride, frame_bytes, &span[k]))
+            return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (%s %zu)", what, pools[k].name, pools[k].stride);
+    }
+    if (!dst) return fail(EMAVFI_E_ARG, "%s: null pointer dst", what);
+    if (!table) return fail(EMAVFI_E_ARG, "%s: null pointer table", what);
+    if (n_srcs > 0 && !srcs) return fail(EMAVFI_E_ARG, "%s: null pointer srcs with n_srcs = %d", what, n_srcs);
+    if (n_nodes > 0 && !nodes) return fail(EMAVFI_E_ARG, "%s: null pointer nodes with n_nodes = %d", what, n_nodes);
+    if (n_flags > 0 && !flags) return fail(EMAVFI_E_ARG, "%s: null pointer flags with n_flags = %d", what, n_flags);
+    if (((uintptr_t)dst | (uintptr_t)srcs | (uintptr_t)nodes) & odd)
+        return fail(EMAVFI_E_ARG, "%s: the frame pointers dst, srcs, nodes must be 2-byte aligned at sample_bytes 2", what);
+    if ((uintptr_t)flags & 3) return fail(EMAVFI_E_ARG, "%s: the u32 pointer flags must be 4-byte aligned", what);
+    const uintptr_t d0 = (uintptr_t)dst;
+    const uintptr_t base[3] = {d0, (uintptr_t)srcs, (uintptr_t)nodes};
+    for (int k = 1; k < 3; ++k)
+        if (pools[k].n > 0 && d0 < base[k] + span[k] && base[k] < d0 + span[0])
+            return fail(EMAVFI_E_ARG, "%s: dst overlaps %s", what, k == 1 ? "srcs" : "nodes");
+    for (int k = 0; k < n_out; ++k) {
+        const emavfi_resample_entry &e = table[k];
+        if (e.w > 256u) return fail(EMAVFI_E_ARG, "%s: table[%d].w = %u is above 256", what, k, e.w);
+        const unsigned idx[2] = {e.a, e.b};
+        for (int q = 0; q < 2; ++q) {
+            const bool node = idx[q] & EMAVFI_RESAMPLE_NODES;
+            const unsigned i = idx[q] & ~EMAVFI_RESAMPLE_NODES;
+            if (i >= (unsigned)(node ? n_nodes : n_srcs))
+                return fail(EMAVFI_E_ARG, "%s: table[%d].%c = %s index %u is outside its pool of %d frames", what, k, q ? 'b' : 'a',
+                            node ? "nodes" : "srcs", i, node ? n_nodes : n_srcs);
+        }
+        if (e.f > (unsigned)n_flags) return fail(EMAVFI_E_ARG, "%s: table[%d].f = %u is beyond n_flags = %d", what, k, e.f, n_flags);
+        if (e.f != 0 && e.h >= (unsigned)n_srcs)
+            return fail(EMAVFI_E_ARG, "%s: table[%d].h = %u is outside the srcs pool of %d frames", what, k, e.h, n_srcs);
+    }
+    EMAVFI_TRY(launch_resample_frames(dst, dst_stride, n_out, srcs, src_stride, nodes, node_stride, reinterpret_cast<const ResampleEntry *>(table),
+                                      flags, frame_bytes, sample_bytes, depth, shift, (hipStream_t)stream), what);
     return EMAVFI_OK;
 }
 

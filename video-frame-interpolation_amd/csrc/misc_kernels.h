@@ -113,6 +113,12 @@ int launch_scene_flags(const unsigned *sig_a, size_t stride_a, const unsigned *s
                        unsigned *flags, unsigned *scores, hipStream_t s);
 int launch_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const unsigned char *alt, size_t alt_stride, const unsigned *flags, int n,
                           size_t frame_bytes, hipStream_t s);
+// temporal resampling (include/emavfi.h, "TEMPORAL RESAMPLE DEFINITION"): arguments already validated; `table` is a HOST pointer, read
+// before the call returns and passed on as kernel arguments, RESAMPLE_CAP (resample_elem.h) entries per launch
+struct ResampleEntry { unsigned a, b, w, f, h; };   // emavfi_resample_entry
+int launch_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride,
+                           const unsigned char *nodes, size_t node_stride, const ResampleEntry *table, const unsigned *flags, size_t frame_bytes,
+                           int sample_bytes, int depth, int shift, hipStream_t s);
 // frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION"): arguments already validated; `part` holds 2 u64 per (b, c, tile)
 // of frame_metrics_tiles' tx * ty tiles (32 x 32 windows each; one tile where an axis has no window)
 void frame_metrics_tiles(int H, int W, int *tx, int *ty);

@@ -3,6 +3,7 @@
 #include "common.h"
 #include "misc_kernels.h"
 #include "scene_elem.h"
+#include "resample_elem.h"
 #include "metrics_elem.h"
 #include "p010_elem.h"
 #include "yuv420p_elem.h"
@@ -2343,6 +2344,94 @@ int launch_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const 
     const dim3 grid((unsigned)((frame_bytes + HOLD_PIECE - 1) / HOLD_PIECE), (unsigned)rep, (unsigned)n);
     hold_frames_kernel<<<grid, 256, 0, s>>>(dst, dst_stride, rep, alt, alt_stride, flags, frame_bytes);
     return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Temporal resampling: the output frames of a batch assembled from its source and node frames (include/emavfi.h, "TEMPORAL RESAMPLE
+// DEFINITION"; per-element functions: resample_elem.h).
+//   resample_frames_kernel   grid (32 KiB pieces of a frame, entries of this launch).  The table travels as kernel arguments, at most
+//                            RESAMPLE_CAP entries per launch; a workgroup reads its entry (and, for an entry with a flag index, that one
+//                            flag word), and then either copies its piece of ONE frame - a held, w = 0 or w = 256 entry never forms the
+//                            address of the frame it does not use - or blends its piece of two.  16 bytes per lane where every frame
+//                            address the entry uses is 16-byte aligned (the last frame_bytes % 16 bytes: bytes / words), else bytes / words
+//                            throughout, through the same per-element functions.  Nothing waits on anything: no LDS, no atomics.
+// ------------------------------------------------------------------------------------------
+struct ResampleArgs {
+    unsigned char *dst;              // the first output frame of THIS launch
+    size_t dst_stride;
+    const unsigned char *srcs;
+    size_t src_stride;
+    const unsigned char *nodes;
+    size_t node_stride;
+    const unsigned *flags;
+    size_t frame_bytes;
+    int sample_bytes, shift;
+    unsigned mask;
+    ResampleEntry e[RESAMPLE_CAP];
+};
+static_assert(sizeof(ResampleArgs) <= 2048, "the table must fit the kernel argument segment");
+
+__global__ __launch_bounds__(256) void resample_frames_kernel(ResampleArgs p)
+{
+    const ResampleEntry e = p.e[blockIdx.y];
+    unsigned ia = e.a, w = e.w;
+    if (p.flags && e.f && p.flags[e.f - 1]) { ia = e.h; w = 0u; }     // held: source frame h (pool bit clear)
+    else if (w == 256u) { ia = e.b; w = 0u; }                         // b alone
+    const auto frame = [&](unsigned i) {
+        return (i & RESAMPLE_POOL_NODES) ? p.nodes + (size_t)(i & ~RESAMPLE_POOL_NODES) * p.node_stride : p.srcs + (size_t)i * p.src_stride;
+    };
+    unsigned char *d = p.dst + (size_t)blockIdx.y * p.dst_stride;
+    const unsigned char *a = frame(ia);
+    const size_t lo = (size_t)blockIdx.x * HOLD_PIECE, hi = lo + HOLD_PIECE < p.frame_bytes ? lo + HOLD_PIECE : p.frame_bytes;
+    size_t x = lo;
+    if (w == 0u) {
+        if ((((uintptr_t)d | (uintptr_t)a) & 15) == 0) {
+            const size_t nv = (hi - lo) >> 4;
+            for (size_t q = threadIdx.x; q < nv; q += 256) reinterpret_cast<uint4 *>(d + lo)[q] = reinterpret_cast<const uint4 *>(a + lo)[q];
+            x += nv << 4;
+        }
+        for (x += threadIdx.x; x < hi; x += 256) d[x] = a[x];
+        return;
+    }
+    const unsigned char *b = frame(e.b);
+    if ((((uintptr_t)d | (uintptr_t)a | (uintptr_t)b) & 15) == 0) {
+        const size_t nv = (hi - lo) >> 4;
+        for (size_t q = threadIdx.x; q < nv; q += 256) {
+            const uint4 va = reinterpret_cast<const uint4 *>(a + lo)[q], vb = reinterpret_cast<const uint4 *>(b + lo)[q];
+            uint4 r;
+            r.x = resample_blend_dword(va.x, vb.x, w, p.sample_bytes, p.mask, p.shift);
+            r.y = resample_blend_dword(va.y, vb.y, w, p.sample_bytes, p.mask, p.shift);
+            r.z = resample_blend_dword(va.z, vb.z, w, p.sample_bytes, p.mask, p.shift);
+            r.w = resample_blend_dword(va.w, vb.w, w, p.sample_bytes, p.mask, p.shift);
+            reinterpret_cast<uint4 *>(d + lo)[q] = r;
+        }
+        x += nv << 4;
+    }
+    if (p.sample_bytes == 1) {
+        for (x += threadIdx.x; x < hi; x += 256) d[x] = (unsigned char)resample_blend(a[x], b[x], w);
+    } else {                                                          // frame_bytes, lo and every frame address are even
+        for (x += 2 * (size_t)threadIdx.x; x < hi; x += 512)
+            *reinterpret_cast<unsigned short *>(d + x) = (unsigned short)resample_blend_word(
+                *reinterpret_cast<const unsigned short *>(a + x), *reinterpret_cast<const unsigned short *>(b + x), w, p.mask, p.shift);
+    }
+}
+
+int launch_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride,
+                           const unsigned char *nodes, size_t node_stride, const ResampleEntry *table, const unsigned *flags, size_t frame_bytes,
+                           int sample_bytes, int depth, int shift, hipStream_t s)
+{
+    ResampleArgs p{};
+    p.dst_stride = dst_stride; p.srcs = srcs; p.src_stride = src_stride; p.nodes = nodes; p.node_stride = node_stride;
+    p.flags = flags; p.frame_bytes = frame_bytes; p.sample_bytes = sample_bytes; p.shift = shift; p.mask = (1u << depth) - 1u;
+    const unsigned pieces = (unsigned)((frame_bytes + HOLD_PIECE - 1) / HOLD_PIECE);
+    for (int first = 0; first < n_out; first += RESAMPLE_CAP) {
+        const int n = n_out - first < RESAMPLE_CAP ? n_out - first : RESAMPLE_CAP;
+        p.dst = dst + (size_t)first * dst_stride;
+        for (int k = 0; k < n; ++k) p.e[k] = table[first + k];
+        resample_frames_kernel<<<dim3(pieces, (unsigned)n), 256, 0, s>>>(p);
+        if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
+    }
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------

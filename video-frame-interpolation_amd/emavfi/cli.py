@@ -29,6 +29,13 @@ def _size(text):
     return h, w
 
 
+def _rate(text):
+    try:
+        return y4m.parse_rate(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m emavfi", description="Interpolate a YUV4MPEG2 (.y4m) stream on an MI355X.", epilog=_EPILOG)
     p.add_argument("input", help="input .y4m ('-': stdin)")
@@ -42,7 +49,14 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--max-interpolation-factor", type=int, default=4, help="without --target-fps: the factor in 1..MAX that brings the rate closest to 60")
     p.add_argument("--factor", type=int, default=None, help="the interpolation factor itself (overrides --target-fps)")
     p.add_argument("--frame-interval", type=int, default=1)
-    p.add_argument("--mode", choices=("reference", "recursive"), default="reference")
+    p.add_argument("--mode", choices=("reference", "recursive"), default=None, help="default: reference")
+    p.add_argument("--output-fps", type=_rate, default=None, metavar="RATE",
+                   help="convert to exactly this frame rate (60, 59.94, 60000/1001 or 60000:1001; at least the stream's): frames in temporal "
+                        "order, assembled from recursive midpoints; excludes --target-fps, --factor, --mode, --reference-quirks and a "
+                        "--frame-interval other than 1")
+    p.add_argument("--resample", choices=("nearest", "blend"), default="nearest",
+                   help="with --output-fps: the closest midpoint (default), or the two around the output time mixed")
+    p.add_argument("--resample-depth", type=int, default=3, metavar="D", help="with --output-fps: midpoints down to 1 / 2^D of a frame interval (1..5, default 3)")
     g = p.add_mutually_exclusive_group()
     g.add_argument("--scale", type=float, default=None, help="resize every frame on the device (default: no resize; the reference: 0.5)")
     g.add_argument("--size", type=_size, default=None, metavar="HxW", help="resize every frame on the device to H x W")
@@ -63,9 +77,21 @@ def _run(args) -> int:
 
     if not args.evaluate and args.output is None:
         raise ValueError("an output stream is needed (or --evaluate)")
+    resample = args.output_fps is not None
+    if resample:
+        for given, name in ((args.target_fps is not None, "--target-fps"), (args.factor is not None, "--factor"),
+                            (args.mode is not None, "--mode"), (args.reference_quirks, "--reference-quirks"),
+                            (args.frame_interval != 1, "--frame-interval other than 1")):
+            if given:
+                raise ValueError(f"--output-fps excludes {name}: the output rate alone decides which frames are written")
+    mode = "resample" if resample else (args.mode or "reference")
     with y4m.Y4MReader(args.input) as reader:
         head = reader.header
-        if args.factor is not None:
+        if resample:
+            factor = 1
+            if args.output_fps < head.rate:
+                raise ValueError(f"--output-fps {args.output_fps} lies below the stream's {head.rate} fps: frames are interpolated, never dropped")
+        elif args.factor is not None:
             factor = args.factor
         else:
             factor, _ = y4m.choose_factor(head.fps, args.target_fps, args.max_interpolation_factor)
@@ -81,20 +107,24 @@ def _run(args) -> int:
         model = EMA_VFI(mid_channels=args.mid_channels, compute_dtype=args.dtype).to(dev).eval()
         model.load_state_dict(sd, strict=True)
         fi = FrameInterpolator(model, interpolation_factor=factor, frame_interval=args.frame_interval, batch_pairs=args.batch_pairs,
-                               reference_quirks=args.reference_quirks, mode=args.mode, pixel_format=head.pixel_format,
+                               reference_quirks=args.reference_quirks, mode=mode, pixel_format=head.pixel_format,
                                yuv_standard=args.yuv_standard, yuv_full_range=args.full_range, scale=args.scale, size=args.size,
-                               scene_threshold=args.scene_threshold, copy_out=False)
+                               scene_threshold=args.scene_threshold, copy_out=False,
+                               **(dict(rate_in=head.rate, rate_out=args.output_fps, resample_depth=args.resample_depth,
+                                       resample_method=args.resample) if resample else {}))
         if args.evaluate:
             print(fi.evaluate(list(reader), every=args.every))      # evaluate() indexes the clip: all of it is held
             return 0
         dst = fi.output_size(head.height, head.width, args.scale, args.size, head.pixel_format)
-        out_head = head.for_output(factor, dst if (args.scale is not None or args.size is not None) else None)
+        out_size = dst if (args.scale is not None or args.size is not None) else None
+        out_head = head.for_output_rate(args.output_fps, out_size) if resample else head.for_output(factor, out_size)
         with y4m.Y4MWriter(args.output, out_head) as writer:
             for frame in fi.run_chunked(reader, chunk_pairs=args.chunk_pairs):
                 writer.write(frame)
         if args.output != "-":
             print(f"{reader.frames_read} frames in, {writer.frames_written} frames out at {out_head.fps_num}:{out_head.fps_den} fps "
-                  f"({out_head.width} x {out_head.height}, {head.pixel_format}, factor {factor})", file=sys.stderr)
+                  f"({out_head.width} x {out_head.height}, {head.pixel_format}, "
+                  + (f"{args.resample} at depth {args.resample_depth})" if resample else f"factor {factor})"), file=sys.stderr)
     return 0
 
 

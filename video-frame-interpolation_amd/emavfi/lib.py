@@ -64,6 +64,8 @@ _PROTOTYPES = {
     "emavfi_luma_signature_u8": (c_int, [c_void_p, c_size_t, c_size_t] + [c_int] * 5 + [c_void_p, c_void_p]),
     "emavfi_scene_flags": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t] + [c_int] * 3 + [ctypes.c_uint, c_void_p, c_void_p, c_void_p]),
     "emavfi_hold_frames_u8": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p, c_int, c_size_t, c_void_p]),
+    "emavfi_resample_frames": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int,
+                                       c_size_t, c_int, c_int, c_int, c_void_p]),
     "emavfi_frame_metrics_workspace_bytes": (c_size_t, [c_int] * 4),
     "emavfi_frame_metrics_u8": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 4
                                 + [c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -1072,6 +1074,57 @@ def hold_frames_u8(dst, alt, flags, rep=1):
     as_ = alt.stride(0) if n > 1 else fb
     with torch.cuda.device(flags.device):
         check(load().emavfi_hold_frames_u8(dst.data_ptr(), ds, rep, alt.data_ptr(), as_, flags.data_ptr(), n, fb, _stream()), "emavfi_hold_frames_u8")
+    return dst
+
+
+# ---------------------------------------------------------------- temporal resampling (include/emavfi.h, "TEMPORAL RESAMPLE DEFINITION")
+RESAMPLE_NODES = 0x80000000     # EMAVFI_RESAMPLE_NODES: the pool bit of a table entry's a / b
+RESAMPLE_LAUNCH_CAP = 64        # EMAVFI_RESAMPLE_LAUNCH_CAP: table entries per launch
+RESAMPLE_MAX_DEPTH = 5          # the deepest dyadic tree of the definition: G = 32
+
+
+class ResampleEntry(ctypes.Structure):
+    """emavfi_resample_entry"""
+    _fields_ = [("a", ctypes.c_uint), ("b", ctypes.c_uint), ("w", ctypes.c_uint), ("f", ctypes.c_uint), ("h", ctypes.c_uint)]
+
+
+def resample_sample_format(pixel_format):
+    """(sample_bytes, depth, shift) of the samples of a harness pixel format as emavfi_resample_frames takes them: bytes; P01x words with the
+    sample in the top bits; planar words with it in the low bits"""
+    if pixel_format in DEPTHS:
+        return 2, DEPTHS[pixel_format], 16 - DEPTHS[pixel_format]
+    d = PLANAR_DEPTHS.get(pixel_format, 8)
+    return (1, 8, 0) if d == 8 else (2, d, 0)
+
+
+def resample_frames(dst, srcs, nodes, table, flags=None, sample_bytes=1, depth=8, shift=0):
+    """Assembles the frames of `dst` from two pools of frames, one table entry per output (the temporal resample definition of
+    include/emavfi.h).  `dst` uint8 [n_out, ...], `srcs` uint8 [n_srcs, ...], `nodes` uint8 [n_nodes, ...] or None: device tensors or pinned
+    host memory with the same dense frame shape, their first dimension may be strided.  `table`: n_out tuples (a, b, w, f, h) - a, b: a frame
+    index in `srcs`, or RESAMPLE_NODES + an index in `nodes`; w 0..256; f: 0, or 1 + an index into `flags`; h: the `srcs` frame a flagged
+    entry holds.  `flags`: an int32 device tensor or None.  16-bit frames travel as their bytes with sample_bytes = 2 and the sample's
+    `depth` and `shift`.  The table is consumed before the call returns."""
+    import torch
+    pools = [(dst, "resample_frames(dst)"), (srcs, "resample_frames(srcs)")] + ([(nodes, "resample_frames(nodes)")] if nodes is not None else [])
+    for t, what in pools:
+        _pinned_or_cuda(t, what)
+        if t.dtype != torch.uint8 or t.dim() < 2 or t.numel() == 0 or not t[0].is_contiguous() or tuple(t.shape[1:]) != tuple(dst.shape[1:]):
+            raise ValueError(f"{what}: a non-empty uint8 [frames, ...] tensor with dense frames of dst's frame shape expected")
+    table = list(table)
+    if len(table) != dst.shape[0]:
+        raise ValueError(f"resample_frames: {len(table)} table entries for {dst.shape[0]} output frames")
+    if flags is not None and not (flags.is_cuda and flags.dtype == torch.int32 and flags.dim() == 1 and flags.is_contiguous()):
+        raise ValueError("resample_frames: flags must be a contiguous int32 [n] device tensor")
+    fb = dst[0].numel()
+    stride = lambda t: t.stride(0) if t.shape[0] > 1 else fb     # a dimension of size 1 has no meaningful stride
+    arr = (ResampleEntry * len(table))(*(ResampleEntry(*(int(v) for v in e)) for e in table))
+    dev = next((t.device for t, _ in pools if t.is_cuda), None) or (flags.device if flags is not None else torch.device("cuda"))
+    with torch.cuda.device(dev):
+        check(load().emavfi_resample_frames(dst.data_ptr(), stride(dst), len(table), srcs.data_ptr(), stride(srcs), srcs.shape[0],
+                                            nodes.data_ptr() if nodes is not None else None, stride(nodes) if nodes is not None else 0,
+                                            nodes.shape[0] if nodes is not None else 0, ctypes.cast(arr, c_void_p),
+                                            flags.data_ptr() if flags is not None else None, flags.numel() if flags is not None else 0,
+                                            fb, int(sample_bytes), int(depth), int(shift), _stream()), "emavfi_resample_frames")
     return dst
 
 

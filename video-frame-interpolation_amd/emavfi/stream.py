@@ -76,11 +76,23 @@ planes, since channels are resized independently; the deeper planar formats refu
 from ``t - 1`` and ``t + 1`` and compared with the true ``t`` on the device (the frame-metric definition of include/emavfi.h: per-channel sum
 of squared differences and 11 x 11 Gaussian-window SSIM); only the metric words travel to the host, behind the ``done`` event the drain
 waits for anyway.
+``mode="resample"`` (opt-in, not in the reference, whose ``--target-fps`` only multiplies the rate by an integer) converts the stream from
+``rate_in`` to ANY ``rate_out >= rate_in`` - 24 -> 60, 25 -> 60, 30000/1001 -> 60 (both: anything ``fractions.Fraction`` accepts; pass decimals as
+strings).  Output ``k`` sits at source time ``k * rate_in / rate_out`` (the temporal resample definition of include/emavfi.h, all integer) and is
+served from the dyadic tree of recursive midpoints of its pair, ``resample_depth`` (1..5, default 3) levels deep: ``resample_method="nearest"``
+(default) takes the closest node, ``"blend"`` mixes the two nodes around the output time per sample, as emitted.  ``run()`` yields frames in
+TEMPORAL order - a source frame, then the in-betweens that follow it.  Only the nodes a pair's outputs use are computed (``resample_plan``), one
+model call per tree level per batch; every node is post-processed once, and one ``emavfi_resample_frames`` call on the post lane assembles the
+batch's output frames - source frames included - into the buffer that leaves for the host, holding the earlier frame of a flagged pair when
+``scene_threshold`` is set.  ``run_chunked`` and ``run(frames, rank, world)`` work as before on the global time grid.  Needs
+``reference_quirks=False`` (the constructor's default is the reference's behaviour, which this is not), ``frame_interval=1``, the default
+``interpolation_factor`` and ``zero_copy=False``; all pixel formats work, ``scale`` / ``size`` on the byte formats; ``evaluate()`` is unaffected.
 """
 from __future__ import annotations
 
 import os
-from typing import Iterable, Iterator, List, NamedTuple, Optional, Tuple
+from fractions import Fraction
+from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -139,18 +151,54 @@ class Evaluation:
         return f"Evaluation({len(self.targets)} targets at {self.size[0]} x {self.size[1]} x {self.channels}: psnr {self.psnr:.3f} dB, ssim {self.ssim:.5f})"
 
 
+class ResamplePlan(NamedTuple):
+    """What ``FrameInterpolator.resample_plan`` returns.  ``outputs``: ``(k, s, j0, j1, w)`` per output frame in emission order - output
+    ``k`` lies in the pair ``(s, s + 1)`` and is node ``j0`` (``w`` = 0, then ``j1 == j0``) or the blend of nodes ``j0`` and ``j1`` with
+    weight ``w`` in 1..255 (a ``w`` of 256 is normalised to node ``j1`` alone); node 0 is source ``s``, node ``G`` source ``s + 1``.
+    ``pairs``: ``{s: levels}`` for every pair this rank computes, ``levels[l]`` = the needed nodes of recursion level ``l + 1`` (level 1 is
+    the midpoint ``G / 2``), ascending - one forward each.  ``P`` / ``Q``: ``rate_in / rate_out`` in lowest terms; ``G`` = 2^depth."""
+    outputs: List[Tuple[int, int, int, int, int]]
+    pairs: Dict[int, List[List[int]]]
+    P: int
+    Q: int
+    G: int
+
+    @property
+    def forwards(self) -> int:
+        return sum(len(lv) for levels in self.pairs.values() for lv in levels)
+
+
 class FrameInterpolator:
     _depth = 0   # bits per sample of a 16-bit-word pixel format ("p010": 10, ...); 0 for the byte formats
     _planar = _yuv8 = False
+    mode = "reference"
 
     def __init__(self, model, interpolation_factor: int = 1, frame_interval: int = 1, batch_pairs: int = 8,
                  reference_quirks: bool = True, mode: str = "reference", device=None, copy_out: bool = True, zero_copy: bool = False,
                  numa: str = "off", pixel_format: str = "bgr24", yuv_standard: str = "bt601", yuv_full_range: bool = False,
-                 scale: Optional[float] = None, size=None, scene_threshold: Optional[float] = None):
+                 scale: Optional[float] = None, size=None, scene_threshold: Optional[float] = None,
+                 rate_in=None, rate_out=None, resample_depth: int = 3, resample_method: str = "nearest"):
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
             raise ValueError("interpolation_factor >= 0, frame_interval >= 1, batch_pairs >= 1 required")
-        if mode not in ("reference", "recursive"):
-            raise ValueError("mode must be 'reference' (the reference's repeated identical prediction) or 'recursive'")
+        if mode not in ("reference", "recursive", "resample"):
+            raise ValueError("mode must be 'reference' (the reference's repeated identical prediction), 'recursive' or 'resample' (any output "
+                             "frame rate: rate_in, rate_out)")
+        if mode == "resample":
+            if reference_quirks:
+                raise ValueError("mode='resample' with reference_quirks=True: frame-rate conversion is not the reference's behaviour (pass "
+                                 "reference_quirks=False)")
+            if frame_interval != 1:
+                raise ValueError("mode='resample' with frame_interval != 1: the time grid counts every source frame")
+            if interpolation_factor != 1:
+                raise ValueError("mode='resample' with an interpolation_factor: the number of in-between frames follows from rate_in and rate_out")
+            if zero_copy:
+                raise ValueError("mode='resample' with zero_copy=True: the output frames are assembled in device memory and leave by copy")
+            if rate_in is None or rate_out is None:
+                raise ValueError("mode='resample' needs rate_in and rate_out")
+            self._ratio = self.resample_ratio(rate_in, rate_out)
+            self.resample_depth, self.resample_method = self._resample_args(resample_depth, resample_method)
+        elif rate_in is not None or rate_out is not None:
+            raise ValueError("rate_in / rate_out belong to mode='resample'")
         if mode == "recursive" and (interpolation_factor + 1) & interpolation_factor:
             raise ValueError("recursive midpoints need interpolation_factor = 2^k - 1 (1, 3, 7, ...)")
         if numa not in ("off", "auto"):
@@ -253,8 +301,82 @@ class FrameInterpolator:
             cur, nxt = nxt, nxt + 1      # in the skip branch the reference also advances frame1
 
     def count_outputs(self, n_frames: int) -> int:
+        if self.mode == "resample":
+            P, Q = self._ratio
+            return 0 if n_frames <= 0 else ((n_frames - 1) * Q) // P + 1
         pairs, last, _ = self.schedule(n_frames, self.interval)
         return 0 if last is None else len(pairs) * (self.factor + 1) + 1
+
+    # ---- frame-rate conversion (include/emavfi.h, "TEMPORAL RESAMPLE DEFINITION"): the schedule, pure host logic over integers
+    @staticmethod
+    def resample_ratio(rate_in, rate_out):
+        """(P, Q) with P / Q = rate_in / rate_out in lowest terms.  Each rate: anything ``fractions.Fraction`` accepts (60, "59.94",
+        "60000/1001", Fraction(30000, 1001), ...; a float is taken at its exact binary value, so pass decimals as strings).  ValueError for a
+        rate that is no positive rational and for ``rate_out < rate_in``."""
+        try:
+            fi, fo = Fraction(rate_in), Fraction(rate_out)
+        except (TypeError, ValueError, ZeroDivisionError):
+            raise ValueError(f"rate_in / rate_out must be rationals (60, '59.94', '60000/1001', ...), got {rate_in!r} and {rate_out!r}") from None
+        if fi <= 0 or fo <= 0:
+            raise ValueError(f"rate_in and rate_out must be positive, got {rate_in!r} and {rate_out!r}")
+        if fo < fi:
+            raise ValueError(f"rate_out {fo} lies below rate_in {fi}: frames are interpolated, never dropped")
+        ratio = fi / fo
+        return ratio.numerator, ratio.denominator
+
+    @staticmethod
+    def _resample_args(depth, method):
+        if isinstance(depth, bool) or not isinstance(depth, int) or not 1 <= depth <= _lib.RESAMPLE_MAX_DEPTH:
+            raise ValueError(f"resample_depth must be an integer in 1..{_lib.RESAMPLE_MAX_DEPTH} (the dyadic tree has 2^depth - 1 nodes per pair)")
+        if method not in ("nearest", "blend"):
+            raise ValueError("resample_method must be 'nearest' (the closest node) or 'blend' (the two nodes around the output time, mixed)")
+        return depth, method
+
+    @staticmethod
+    def resample_span(P: int, Q: int, depth: int, method: str, lo: int, hi: int):
+        """The outputs ``(k, s, j0, j1, w)`` whose pair index ``s = k P / Q`` lies in ``[lo, hi)``, in order (``ResamplePlan.outputs``).  The
+        grid is global: a span needs neither the clip's length nor the spans before it."""
+        G, outs = 1 << depth, []
+        for k in range(-((-lo * Q) // P), -((-hi * Q) // P)):      # ceil(lo Q / P) .. ceil(hi Q / P) - 1
+            s = (k * P) // Q
+            r = k * P - s * Q
+            if method == "nearest":
+                j = (2 * r * G + Q) // (2 * Q)
+                outs.append((k, s, j, j, 0))
+            else:
+                j0 = (r * G) // Q
+                w = (256 * (r * G - j0 * Q) + Q // 2) // Q
+                outs.append((k, s, j0 + 1, j0 + 1, 0) if w == 256 else (k, s, j0, j0, 0) if w == 0 else (k, s, j0, j0 + 1, w))
+        return outs
+
+    @staticmethod
+    def resample_needed(nodes, depth: int):
+        """The nodes to compute for a pair whose outputs use ``nodes``: those in 1..G-1, closed under parents (``j -+ (j & -j)``), by level -
+        ``levels[l]`` holds the needed nodes ``j`` with ``j & -j == G >> (l + 1)``, ascending."""
+        G, need, todo = 1 << depth, set(), [j for j in nodes if 0 < j < (1 << depth)]
+        while todo:
+            j = todo.pop()
+            if j not in need:
+                need.add(j)
+                todo += [p for p in (j - (j & -j), j + (j & -j)) if 0 < p < G]
+        return [sorted(j for j in need if j & -j == G >> (l + 1)) for l in range(depth)]
+
+    @staticmethod
+    def resample_plan(n_frames: int, rate_in, rate_out, depth: int = 3, method: str = "nearest", rank: int = 0, world: int = 1) -> ResamplePlan:
+        """What ``run(frames, rank, world)`` yields in mode "resample", symbolically and in order, and what it computes: a ``ResamplePlan``.
+        A rank emits the outputs whose pair lies in its contiguous slice of the ``n_frames - 1`` pairs (``dist.shard_range``); the last rank
+        also emits the output that falls on the last frame, if there is one.  Pure host logic (no device needed)."""
+        from .dist import shard_range
+        P, Q = FrameInterpolator.resample_ratio(rate_in, rate_out)
+        depth, method = FrameInterpolator._resample_args(depth, method)
+        if n_frames <= 0:
+            return ResamplePlan([], {}, P, Q, 1 << depth)
+        a, b = shard_range(n_frames - 1, rank, world)
+        outs = FrameInterpolator.resample_span(P, Q, depth, method, a, b)
+        pairs = {s: FrameInterpolator.resample_needed({j for _, s2, j0, j1, _ in outs if s2 == s for j in (j0, j1)}, depth) for s in range(a, b)}
+        if rank == world - 1 and ((n_frames - 1) * Q) % P == 0:
+            outs.append((((n_frames - 1) * Q) // P, n_frames - 1, 0, 0, 0))
+        return ResamplePlan(outs, pairs, P, Q, 1 << depth)
 
     # ---- segment sharding (SURVEY.md section 8e, BASELINE configs[4]): one process per GPU, each with a contiguous
     # run of the stream's frame pairs.  No exchange between ranks: a pair's two frames are all a forward needs.
@@ -594,15 +716,21 @@ class FrameInterpolator:
                 if f.dtype != np.uint8 or f.ndim != 3 or f.shape != first.shape:
                     raise ValueError(f"FrameInterpolator.{what}: same-shape uint8 HWC frames expected")
 
-    def run(self, frames, rank: int = 0, world: int = 1, *, _emit_tail: bool = True) -> Iterator[np.ndarray]:
+    def run(self, frames, rank: int = 0, world: int = 1, *, _emit_tail: bool = True, _base: int = 0) -> Iterator[np.ndarray]:
         """Yields uint8 HWC frames (``pixel_format="nv12"``: uint8 [H*3/2, W] frames; ``"p010"`` / ``"p012"`` / ``"p016"``: uint16 [H*3/2, W]
         frames) in the order the reference's writer receives them.
 
         ``frames``: the whole stream - an iterable, or (sharded use) any object with ``len()`` and integer indexing, of which
         only this rank's segment ``[lo, hi)`` (``segment()``) is touched, e.g. a lazy video reader.  ``rank`` / ``world``:
-        this process's share (one process per GPU); the default is the whole stream."""
+        this process's share (one process per GPU); the default is the whole stream.
+
+        ``mode="resample"``: the frames of the stream at ``rate_out`` in TEMPORAL order - a source frame before the in-between frames that
+        follow it, not the reference's predictions-first order (``resample_plan``)."""
         if not (hasattr(frames, "__len__") and hasattr(frames, "__getitem__")):
             frames = list(frames)
+        if self.mode == "resample":
+            yield from self._run_resample(frames, rank, world, _emit_tail, _base)
+            return
         n_total = len(frames)
         mine, lo, hi, tail = self.segment(n_total, self.interval, rank, world)
         pairs, last, last_roundtrip = self.schedule(n_total, self.interval)
@@ -743,6 +871,148 @@ class FrameInterpolator:
         else:
             yield self._resized_bytes(frames[last]) if self._resize else words(frames[last])
 
+    # ---- mode "resample": forwards level by level over the pairs that need the node, nodes post-processed once, outputs assembled on the post lane
+    def _resample_forwards(self, x, ia, ib, levels):
+        """levels[l] = [(pair of the batch, node)] of recursion level l + 1, in node-buffer order -> the model's output per non-empty level
+        ([len(levels[l]), 3, H, W]).  The recursion and the re-normalisation of a midpoint are ``_predict``'s."""
+        G, outs, norm = 1 << self.resample_depth, [], {}
+        if self._norm is None:
+            self._norm = (torch.tensor(_lib.IMAGENET_MEAN, device=x.device).view(1, 3, 1, 1),
+                          torch.tensor(_lib.IMAGENET_STD, device=x.device).view(1, 3, 1, 1))
+        mean, std = self._norm
+
+        def node(k, j):
+            return x[ia[k]] if j == 0 else x[ib[k]] if j == G else norm[(k, j)]
+
+        with torch.no_grad():
+            for l, items in enumerate(levels):
+                if not items:
+                    break                    # a needed node has needed parents: below an empty level there is nothing
+                step = G >> (l + 1)
+                if l == 0:
+                    x1, x2 = self._rows(x, [ia[k] for k, _ in items]), self._rows(x, [ib[k] for k, _ in items])
+                else:
+                    x1, x2 = torch.stack([node(k, j - step) for k, j in items]), torch.stack([node(k, j + step) for k, j in items])
+                m = self.model(x1, x2)
+                outs.append(m)
+                if l + 1 < len(levels) and levels[l + 1]:
+                    mn = (m - mean) / std
+                    for i, item in enumerate(items):
+                        norm[item] = mn[i]
+        return outs
+
+    def _resample_batch(self, chunk, outs_of, ia, ib):
+        """One batch's host-side schedule: (levels, table, n_nodes).  `chunk`: its pairs (s, s + 1), local frame indices; `outs_of[s]`: the
+        outputs (r, j0, j1, w) of pair s in order; ia / ib: the staged rows of each pair's frames.  Node frames are numbered level by level, pair
+        by pair - the order the forwards produce them in."""
+        D, G = self.resample_depth, 1 << self.resample_depth
+        needed = [self.resample_needed({j for _, j0, j1, _ in outs_of[s] for j in (j0, j1)}, D) for s, _ in chunk]
+        levels = [[(k, j) for k in range(len(chunk)) for j in needed[k][l]] for l in range(D)]
+        index = {item: i for i, item in enumerate(item for lv in levels for item in lv)}
+        table = []
+        for k, (s, _) in enumerate(chunk):
+            ref = lambda j: ia[k] if j == 0 else ib[k] if j == G else _lib.RESAMPLE_NODES | index[(k, j)]
+            for r, j0, j1, w in outs_of[s]:
+                table.append((ref(j0), ref(j1), w, k + 1 if (self.scene is not None and r > 0) else 0, ia[k]))
+        return levels, table, len(index)
+
+    def _run_resample(self, frames, rank, world, emit_tail, base):
+        from .dist import shard_range
+        n_total = len(frames)
+        if n_total <= 0:
+            return
+        (P, Q), D, G = self._ratio, self.resample_depth, 1 << self.resample_depth
+        a, b = shard_range(n_total - 1, rank, world)
+        last = n_total - 1
+        tail = emit_tail and rank == world - 1 and ((base + last) * Q) % P == 0     # an output falls on the last frame: r = 0, the frame itself
+        if b <= a and not tail:
+            return
+        frames = {i: np.ascontiguousarray(frames[i]) for i in sorted(set(range(a, b + 1) if b > a else ()) | ({last} if tail else set()))}
+        first = next(iter(frames.values()))
+        self._check_frames(frames, first, "run")
+        if self._depth:
+            frames = {i: f.view(np.uint8) for i, f in frames.items()}
+            first = next(iter(frames.values()))
+        words = (lambda v: v.view(np.uint16)) if self._depth else (lambda v: v)
+        self._alloc(first.shape)
+        self.scene_cuts, self.scene_scores = [], []
+        outs_of = {s: [] for s in range(a, b)}
+        for k, s, j0, j1, w in self.resample_span(P, Q, D, self.resample_method, base + a, base + b):
+            outs_of[s - base].append((k * P - s * Q, j0, j1, w))
+        bp = self.batch_pairs
+        chunks = [[(s, s + 1) for s in range(i, min(i + bp, b))] for i in range(a, b, bp)]
+        fmt = _lib.resample_sample_format(self.pixel_format)
+        main = torch.cuda.current_stream(self.device)
+        if chunks:
+            # the node and emission buffers of a slot hold the largest batch of this run
+            sizes = [(sum(len(outs_of[s]) for s, _ in c), sum(len(lv) for s, _ in c for lv in self.resample_needed(
+                {j for _, j0, j1, _ in outs_of[s] for j in (j0, j1)}, D))) for c in chunks]
+            n_emit, n_node = max(o for o, _ in sizes), max(1, max(n for _, n in sizes))
+            for slot in self._slots:
+                fs = tuple(slot["d_src"].shape[1:])
+                if "d_emit" not in slot or slot["d_emit"].shape[0] < n_emit or slot["d_node"].shape[0] < n_node:
+                    slot.update({"d_node": torch.empty(n_node, *fs, dtype=torch.uint8, device=self.device),
+                                 "d_emit": torch.empty(n_emit, *fs, dtype=torch.uint8, device=self.device),
+                                 "h_emit": torch.empty(n_emit, *fs, dtype=torch.uint8).pin_memory()})
+
+        def drain(slot, chunk, n_out):
+            slot["done"].synchronize()            # this batch's frames have been written into the pinned buffer
+            emit_h = slot["h_emit"].numpy()
+            own = (lambda v: words(v).copy()) if self.copy_out else words
+            if self.scene is not None:            # written behind the frames, ahead of `done`
+                fs = slot["h_fs"].numpy()
+                for k, (s, s2) in enumerate(chunk):
+                    self.scene_scores.append((s, s2, int(fs[1, k])))
+                    if fs[0, k]:
+                        self.scene_cuts.append((s, s2, int(fs[1, k])))
+            for i in range(n_out):
+                yield own(emit_h[i])
+
+        staged = self._stage(self._slots[0], frames, chunks[0]) if chunks else None
+        prev = None
+        for ci, chunk in enumerate(chunks):
+            slot = self._slots[ci & 1]
+            nup, ia, ib = staged
+            levels, table, n_nodes = self._resample_batch(chunk, outs_of, ia, ib)
+            with torch.cuda.stream(self._pre):
+                self._pre.wait_event(slot["fwd"])       # the slot's x was last read by the forwards of batch ci - 2 ...
+                self._pre.wait_event(slot["done"])      # ... and its d_in / d_rs by that batch's assembly
+                rs = slot["d_rs"][:nup] if slot["d_rs"] is not None else None
+                slot["d_in"][:nup].copy_(slot["h_in"][:nup], non_blocking=True)                       # hipMemcpyAsync pinned -> HBM (SDMA)
+                slot["consumed"].record(self._pre)
+                x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=rs)
+                if self.scene is not None:
+                    self._scene_decide(slot, slot["d_in"][:nup], ia, ib)
+                slot["pre"].record(self._pre)
+            main.wait_event(slot["pre"])
+            preds = self._resample_forwards(x, ia, ib, levels)                                        # on the caller's stream
+            slot["fwd"].record(main)
+            with torch.cuda.stream(self._post):
+                self._post.wait_event(slot["fwd"])
+                off = 0
+                for m in preds:                                                                       # every node becomes bytes once
+                    m.record_stream(self._post)
+                    self._post_kernel(m, False, out=slot["d_node"][off:off + m.shape[0]])
+                    off += m.shape[0]
+                assert off == n_nodes
+                # the source frames as emitted: the staged bytes, or the bytes the preprocess kernel resized them to
+                _lib.resample_frames(slot["d_emit"][:len(table)], rs if rs is not None else slot["d_in"][:nup],
+                                     slot["d_node"][:off] if off else None, table,
+                                     flags=slot["fs"][0] if self.scene is not None else None, sample_bytes=fmt[0], depth=fmt[1], shift=fmt[2])
+                slot["h_emit"][:len(table)].copy_(slot["d_emit"][:len(table)], non_blocking=True)     # HBM -> pinned (SDMA)
+                if self.scene is not None:
+                    slot["h_fs"].copy_(slot["fs"], non_blocking=True)
+                slot["done"].record(self._post)
+            if ci + 1 < len(chunks):                  # host-side staging of the next batch overlaps this batch's compute
+                staged = self._stage(self._slots[(ci + 1) & 1], frames, chunks[ci + 1])
+            if prev is not None:
+                yield from drain(*prev)
+            prev = (slot, chunk, len(table))
+        if prev is not None:
+            yield from drain(*prev)
+        if tail:
+            yield self._resized_bytes(frames[last]) if self._resize else words(frames[last])
+
     @staticmethod
     def chunk_plan(n_frames: int, frame_interval: int, chunk_pairs: int = 64):
         """How ``run_chunked`` cuts a stream of ``n_frames`` frames: ``[(lo, hi, final)]`` - chunk c holds the global frames ``[lo, hi)`` =
@@ -780,7 +1050,8 @@ class FrameInterpolator:
             final = len(held) < L + 1          # the stream ended inside this chunk (a full chunk is never final: its last frame starts the next)
             if held:
                 self.scene_cuts, self.scene_scores = [], []     # this chunk's own, whatever run() does with them
-                yield from self.run(held, _emit_tail=final)
+                # mode "resample": the time grid is global, so a chunk is told where it starts
+                yield from self.run(held, _emit_tail=final, **({"_base": lo} if self.mode == "resample" else {}))
                 cuts += [(a + lo, b + lo, sc) for a, b, sc in self.scene_cuts]
                 scores += [(a + lo, b + lo, sc) for a, b, sc in self.scene_scores]
                 self.scene_cuts, self.scene_scores = list(cuts), list(scores)

@@ -15,6 +15,7 @@ re-packed on the host in either direction.  Only progressive 4:2:0 with even W a
 from __future__ import annotations
 
 import sys
+from fractions import Fraction
 from math import gcd
 from typing import Iterator, NamedTuple, Optional, Tuple
 
@@ -88,6 +89,38 @@ class Y4MHeader(NamedTuple):
             h = h._replace(height=int(size[0]), width=int(size[1]))
             check_header(h)
         return h
+
+    @property
+    def rate(self) -> Fraction:
+        """F as an exact rational"""
+        return Fraction(self.fps_num, self.fps_den)
+
+    def for_output_rate(self, rate, size=None) -> "Y4MHeader":
+        """The header of a stream converted to the frame rate ``rate`` (anything ``fractions.Fraction`` accepts): F becomes exactly that
+        rational, reduced; W, H and everything else as ``for_output`` treats them."""
+        try:
+            rate = Fraction(rate)
+        except (TypeError, ValueError, ZeroDivisionError):
+            raise ValueError(f"frame rate {rate!r} is refused: a positive rational expected") from None
+        if rate <= 0:
+            raise ValueError(f"frame rate {rate} is refused: it must be positive")
+        h = self._replace(fps_num=rate.numerator, fps_den=rate.denominator)
+        if size is not None:
+            h = h._replace(height=int(size[0]), width=int(size[1]))
+            check_header(h)
+        return h
+
+
+def parse_rate(text) -> Fraction:
+    """A frame rate as the command line and a Y4M header spell it - ``60``, ``59.94``, ``60000/1001`` or ``60000:1001`` - as an exact
+    positive ``Fraction`` (a decimal is taken digit for digit: ``59.94`` is 2997/50, not 60000/1001).  ValueError otherwise."""
+    try:
+        rate = Fraction(str(text).strip().replace(":", "/"))
+    except (ValueError, ZeroDivisionError):
+        raise ValueError(f"frame rate {text!r} is refused: 60, 59.94, 60000/1001 or 60000:1001 expected") from None
+    if rate <= 0:
+        raise ValueError(f"frame rate {text!r} is refused: it must be positive")
+    return rate
 
 
 def check_header(h: Y4MHeader) -> None:
