@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -550,6 +550,60 @@ typedef struct { unsigned a, b, w, f, h; } emavfi_resample_entry;
 int emavfi_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
                            const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_resample_entry *table,
                            const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift, void *stream);
+
+/* Duplicate frames.  The resampler above puts every output frame at its true time and assumes that every INPUT frame sits at its true time
+ * too.  24 fps film in a 30 fps stream, animation drawn on twos, screen captures and anything that went through a frame-rate filter break
+ * that: some frames are copies of the frame before them, an (A, A) pair yields A again, and the motion A -> B is squeezed into one interval.
+ * The reference has no guard for this (inference.py:173-188 interpolates every pair); this is an addition, off unless asked for.  The copies
+ * are found on the device, dropped, and the resampler interpolates across the gap they leave.
+ *
+ * DUPLICATE FRAME DEFINITION (the one place).  This is the project's own definition: it follows no outside tool's de-duplication (ffmpeg's
+ * mpdecimate, ...) and claims agreement with none.  All arithmetic is integer, `/` is floor division: host, oracle and device agree bit for bit.
+ *   Sample.  A byte, or (word >> shift) & (2^depth - 1) of a 16-bit little-endian word: depth 10, 12 or 16 and shift 0 .. 16 - depth, the
+ *     triple emavfi_resample_frames takes (sample_bytes 1: depth 8, shift 0).
+ *   Luma.  C = 1: the sample itself.  C = 3 (bytes only): the luma of the SCENE CUT DEFINITION, with the same `order` argument.
+ *   Cells.  The scene grid: EMAVFI_SCENE_GRID x EMAVFI_SCENE_GRID = 32 x 32 cells with the same bounds - cell (i, j) covers rows
+ *     [i H / 32, (i + 1) H / 32) and columns [j W / 32, (j + 1) W / 32); with H < 32 or W < 32 some cells hold no pixel (empty cells).
+ *   Per cell of n pixels.  sad = the sum of |luma_a - luma_b|, an unsigned 64-bit integer: at most 65535 * 2^18, so 16 sad < 2^38.
+ *     m = (16 sad + n - 1) / n: the CEILING of the cell's mean absolute difference in sixteenths of a count.  m = 0 exactly when the cell's
+ *     luma is identical; m <= 16 (2^depth - 1) <= 1 048 560 fits u32.  An empty cell gives 0.
+ *   Score of a pair: the MAXIMUM of m over the cells.  (The sum would let coding noise spread over 1024 cells outvote the one cell in which
+ *     something moved; the scene signature, which compares cell means, cannot see a small moving object at all.)
+ *   Duplicate: score <= threshold, `threshold` in score units.  A caller who thinks of a fraction f of full scale passes
+ *     floor(f * 16 * (2^depth - 1)), depth 8 for bytes (the Python layer's dedup_threshold_units does).  A threshold of 0 flags exactly the
+ *     pairs whose luma is bit-identical.
+ *   Schedule (extends the TEMPORAL RESAMPLE DEFINITION; host-side integers).  Of n source frames, frame t >= 1 is DROPPED when the pair
+ *     (t - 1, t) is flagged, unless it is KEPT regardless: t = 0, the last frame, t % span = 0 (span: 64 by default, on the global frame index -
+ *     a chunk of a chunked run then sees exactly what the whole clip would), and the frame that follows max_run dropped frames in a row
+ *     (max_run: 3 by default; it bounds the drift and the gap).  Consecutive kept frames t_i < t_i+1 form a gap of m = t_i+1 - t_i intervals,
+ *     1 <= m <= max_run + 1.  The output count and times are unchanged: output k has s = k P / Q, r = k P - s Q, and is served from the gap
+ *     with t_i <= s < t_i+1 at R = (s - t_i) Q + r over the denominator m Q, in a tree of depth D_m = D + ceil(log2 m), G_m = 2^D_m - never
+ *     coarser than 1 / 2^D of a SOURCE interval.  The formulas above apply with r -> R, Q -> m Q, G -> G_m:
+ *       nearest: j = (2 R G_m + m Q) / (2 m Q);  blend: j0 = (R G_m) / (m Q), e = R G_m - j0 m Q, w = (256 e + m Q / 2) / (m Q).
+ *     R = 0 is source t_i itself; m = 1 is the TEMPORAL RESAMPLE DEFINITION word for word.  Needed nodes are closed under parents, as before.
+ *     D + ceil(log2(max_run + 1)) must not exceed 5, the deepest tree.  Scene cuts are decided on the kept pair (t_i, t_i+1): a flagged gap
+ *     yields t_i for every output with R > 0.  A ratio of 1 is valid: the dropped frames are replaced by interpolated ones.
+ *
+ * emavfi_frame_diff_cells: pair k < n compares image k of `a` ([n][H][W][C] samples, rows a_pitch BYTES apart, images a_batch_stride BYTES
+ *   apart) with image k of `b` and writes cells[k][1024] = m.  EVERY one of the n * 1024 words is written, whatever the buffer held before
+ *   (empty cells: 0); a workgroup owns the cells it stores, so there are no global atomics and nothing has to be zeroed first.  `a` and `b`
+ *   may overlap - both are only read: the consecutive frames of one buffer of B frames are b = a + batch_stride, n = B - 1.
+ * emavfi_duplicate_flags: pair k < n reads the 1024 words at cells + k stride_words; writes flags[k] = 0 / 1 and, unless `scores` is NULL,
+ *   scores[k] = the maximum.
+ * EMAVFI_E_ARG (never an abort): the refusals of emavfi_luma_signature_u8 (a null required pointer, n below 1, n of emavfi_frame_diff_cells
+ *   above 65535, a dimension below 1 or above 16384, C outside {1, 3}, an unknown order, a pitch smaller than its row, for n > 1 a batch
+ *   stride smaller than its plane, a u32 pointer that is not 4-byte aligned, size arithmetic that overflows size_t), and: sample_bytes outside
+ *   {1, 2}, a depth or shift outside the above, C = 3 at sample_bytes 2, and at sample_bytes 2 an odd pitch, (n > 1) an odd batch stride or an
+ *   image pointer that is not 2-byte aligned; for emavfi_duplicate_flags a stride below 1024 words.
+ * The image pointers are device pointers or pinned (device-mapped) host memory; cells, flags and scores: device memory (or pinned).  Nothing
+ *   is allocated, nothing synchronises, all work goes on `stream`.  Access width, per image: 16 pixels per lane with 16-byte loads when that
+ *   image's pointer, pitch and (n > 1) batch stride are multiples of 16, and the right remainder of a row - or everything, otherwise - byte by
+ *   byte with the same per-element functions (csrc/dedup_elem.h, csrc/scene_elem.h).  Per-lane partial sums are 32-bit (at most 8240 pixels
+ *   per lane), a cell's total is 64-bit.  Both kernels are short-lived and wait on nothing. */
+int emavfi_frame_diff_cells(const unsigned char *a, size_t a_pitch, size_t a_batch_stride, const unsigned char *b, size_t b_pitch,
+                            size_t b_batch_stride, int n, int H, int W, int C, int order, int sample_bytes, int depth, int shift,
+                            unsigned *cells, void *stream);
+int emavfi_duplicate_flags(const unsigned *cells, size_t stride_words, int n, unsigned threshold, unsigned *flags, unsigned *scores, void *stream);
 
 /* Frame metrics on the device: how close is image a (an interpolated frame) to image b (the held-out true frame)?  The reference has no
  * evaluation script (its README names PSNR and SSIM against held-out ground-truth frames as the way to judge a model and calls an eval.py a

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "misc_kernels.h"
 #include "resample_elem.h"
+#include "dedup_elem.h"
 #include "conv_first.inl"
 
 #include <atomic>
@@ -1654,6 +1655,64 @@ int emavfi_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const 
     if (!dst || !alt || !flags) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
     if ((uintptr_t)flags & 3) return fail(EMAVFI_E_ARG, "%s: the u32 pointer must be 4-byte aligned", what);
     EMAVFI_TRY(launch_hold_frames_u8(dst, dst_stride, rep, alt, alt_stride, flags, n, frame_bytes, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+// ---- duplicate frames (include/emavfi.h, "DUPLICATE FRAME DEFINITION"): every check runs on the host, pointers are looked at last
+static_assert(DEDUP_CELLS == EMAVFI_SCENE_SIG_WORDS, "header and dedup_elem.h disagree");
+
+int emavfi_frame_diff_cells(const unsigned char *a, size_t a_pitch, size_t a_batch_stride, const unsigned char *b, size_t b_pitch,
+                            size_t b_batch_stride, int n, int H, int W, int C, int order, int sample_bytes, int depth, int shift,
+                            unsigned *cells, void *stream)
+{
+    const char *const what = "frame_diff_cells";
+    if (n < 1) return fail(EMAVFI_E_ARG, "%s: n must be >= 1", what);
+    if (n > 65535) return fail(EMAVFI_E_ARG, "%s: n = %d is above 65535", what, n);
+    if (const int rc = scene_dims_check(what, H, W); rc != EMAVFI_OK) return rc;
+    if (C != 1 && C != 3) return fail(EMAVFI_E_ARG, "%s: C = %d (C must be 1 or 3)", what, C);
+    if (order != EMAVFI_ORDER_BGR && order != EMAVFI_ORDER_RGB)
+        return fail(EMAVFI_E_ARG, "%s: unknown order %d (EMAVFI_ORDER_BGR or EMAVFI_ORDER_RGB)", what, order);
+    if (sample_bytes != 1 && sample_bytes != 2) return fail(EMAVFI_E_ARG, "%s: sample_bytes = %d (sample_bytes must be 1 or 2)", what, sample_bytes);
+    if (sample_bytes == 1 ? depth != 8 : (depth != 10 && depth != 12 && depth != 16))
+        return fail(EMAVFI_E_ARG, "%s: depth = %d (depth must be 8 at sample_bytes 1 and 10, 12 or 16 at sample_bytes 2)", what, depth);
+    if (shift < 0 || shift > 8 * sample_bytes - depth)
+        return fail(EMAVFI_E_ARG, "%s: shift = %d (shift must lie in 0..%d at depth %d)", what, shift, 8 * sample_bytes - depth, depth);
+    if (C == 3 && sample_bytes == 2) return fail(EMAVFI_E_ARG, "%s: C = 3 at sample_bytes 2 (interleaved colour is scored as bytes only)", what);
+    const size_t odd = sample_bytes == 2 ? 1 : 0, row = (size_t)W * C * sample_bytes;
+    const struct { const char *name; size_t pitch, bstride; } side[2] = {{"a", a_pitch, a_batch_stride}, {"b", b_pitch, b_batch_stride}};
+    for (const auto &sd : side) {
+        if (sd.pitch < row) return fail(EMAVFI_E_ARG, "%s: %s_pitch %zu is smaller than its row of %zu bytes", what, sd.name, sd.pitch, row);
+        if (sd.pitch & odd) return fail(EMAVFI_E_ARG, "%s: %s_pitch %zu is odd at sample_bytes 2", what, sd.name, sd.pitch);
+        size_t plane, span;
+        if (__builtin_mul_overflow((size_t)(H - 1), sd.pitch, &plane) || __builtin_add_overflow(plane, row, &plane))
+            return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (%s_pitch %zu)", what, sd.name, sd.pitch);
+        if (n > 1 && sd.bstride < plane)
+            return fail(EMAVFI_E_ARG, "%s: the batch stride %s_batch_stride %zu is smaller than its plane", what, sd.name, sd.bstride);
+        if (n > 1 && (sd.bstride & odd)) return fail(EMAVFI_E_ARG, "%s: %s_batch_stride %zu is odd at sample_bytes 2", what, sd.name, sd.bstride);
+        if (n > 1 && (__builtin_mul_overflow((size_t)(n - 1), sd.bstride, &span) || __builtin_add_overflow(span, plane, &span)))
+            return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (%s_batch_stride %zu)", what, sd.name, sd.bstride);
+    }
+    if (!a || !b || !cells) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
+    if (((uintptr_t)a | (uintptr_t)b) & odd) return fail(EMAVFI_E_ARG, "%s: the image pointers a, b must be 2-byte aligned at sample_bytes 2", what);
+    if ((uintptr_t)cells & 3) return fail(EMAVFI_E_ARG, "%s: the u32 pointer must be 4-byte aligned", what);
+    EMAVFI_TRY(launch_frame_diff_cells(a, a_pitch, a_batch_stride, b, b_pitch, b_batch_stride, n, H, W, C, order, sample_bytes, depth, shift, cells,
+                                       (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+int emavfi_duplicate_flags(const unsigned *cells, size_t stride_words, int n, unsigned threshold, unsigned *flags, unsigned *scores, void *stream)
+{
+    const char *const what = "duplicate_flags";
+    if (n < 1) return fail(EMAVFI_E_ARG, "%s: n must be >= 1", what);
+    if (stride_words < EMAVFI_SCENE_SIG_WORDS)
+        return fail(EMAVFI_E_ARG, "%s: a stride of %zu words is below %d", what, stride_words, EMAVFI_SCENE_SIG_WORDS);
+    size_t span;
+    if (__builtin_mul_overflow((size_t)(n - 1), stride_words, &span) || __builtin_add_overflow(span, (size_t)EMAVFI_SCENE_SIG_WORDS, &span) ||
+        __builtin_mul_overflow(span, sizeof(unsigned), &span))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (stride %zu words)", what, stride_words);
+    if (!cells || !flags) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
+    if (((uintptr_t)cells | (uintptr_t)flags | (uintptr_t)scores) & 3) return fail(EMAVFI_E_ARG, "%s: the u32 pointers must be 4-byte aligned", what);
+    EMAVFI_TRY(launch_duplicate_flags(cells, stride_words, n, threshold, flags, scores, (hipStream_t)stream), what);
     return EMAVFI_OK;
 }
 

@@ -113,6 +113,10 @@ int launch_scene_flags(const unsigned *sig_a, size_t stride_a, const unsigned *s
                        unsigned *flags, unsigned *scores, hipStream_t s);
 int launch_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const unsigned char *alt, size_t alt_stride, const unsigned *flags, int n,
                           size_t frame_bytes, hipStream_t s);
+// duplicate frames (include/emavfi.h, "DUPLICATE FRAME DEFINITION"): arguments already validated
+int launch_frame_diff_cells(const unsigned char *a, size_t a_pitch, size_t a_bstride, const unsigned char *b, size_t b_pitch, size_t b_bstride, int n,
+                            int H, int W, int C, int order, int sample_bytes, int depth, int shift, unsigned *cells, hipStream_t s);
+int launch_duplicate_flags(const unsigned *cells, size_t stride, int n, unsigned threshold, unsigned *flags, unsigned *scores, hipStream_t s);
 // temporal resampling (include/emavfi.h, "TEMPORAL RESAMPLE DEFINITION"): arguments already validated; `table` is a HOST pointer, read
 // before the call returns and passed on as kernel arguments, RESAMPLE_CAP (resample_elem.h) entries per launch
 struct ResampleEntry { unsigned a, b, w, f, h; };   // emavfi_resample_entry

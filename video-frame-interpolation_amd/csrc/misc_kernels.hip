@@ -4,6 +4,7 @@
 #include "misc_kernels.h"
 #include "scene_elem.h"
 #include "resample_elem.h"
+#include "dedup_elem.h"
 #include "metrics_elem.h"
 #include "p010_elem.h"
 #include "yuv420p_elem.h"
@@ -2343,6 +2344,151 @@ int launch_hold_frames_u8(unsigned char *dst, size_t dst_stride, int rep, const 
 {
     const dim3 grid((unsigned)((frame_bytes + HOLD_PIECE - 1) / HOLD_PIECE), (unsigned)rep, (unsigned)n);
     hold_frames_kernel<<<grid, 256, 0, s>>>(dst, dst_stride, rep, alt, alt_stride, flags, frame_bytes);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Duplicate frames found on the device (include/emavfi.h, "DUPLICATE FRAME DEFINITION"; per-element functions: dedup_elem.h and, for the
+// cells and the 3-byte luma, scene_elem.h).
+//   frame_diff_cells_kernel<BPP>  two images of BPP bytes per pixel (1: C = 1 bytes, 2: C = 1 words, 3: C = 3 bytes) -> cells [n][32][32] u32, per
+//                                 cell the ceiling of the mean absolute luma difference in sixteenths of a count.  The structure is the
+//                                 signature kernel's: grid (32 cell rows, 4 groups of 8 cell columns, n), a workgroup OWNS the 8 cells it
+//                                 stores - no global atomics, no zeroing -, a lane takes units of 16 pixels on the frame's 16-pixel lattice
+//                                 and adds each cell's part of a unit into its own LDS slot [cell][lane].  Per image, two access forms with
+//                                 the same per-element arithmetic:
+//                                   WIDE    BPP 16-byte loads per unit (pointer, pitch and batch stride multiples of 16; only units that end
+//                                           inside the row - pitch padding is never read);
+//                                   SCALAR  byte loads: whenever a condition above fails, and for the right remainder of a row.
+//                                 A slot is u32: a workgroup has at most 512 rows x 257 units (a group spans at most 4096 columns and may
+//                                 start inside a unit), so a lane takes at most ceil(512 * 257 / 256) = 515 units = 8240 pixels, and
+//                                 8240 * 65535 < 2^30 even when every one of them falls into one cell.  The cell total over the 256 slots
+//                                 is 64-bit (a 257 x 256 cell of 16-bit samples already passes 2^32).  Reads both images once, waits on nothing.
+//   duplicate_flags_kernel        one workgroup per pair: the maximum over the 1024 cells -> scores[k], flags[k] = score <= threshold
+// ------------------------------------------------------------------------------------------
+struct DiffArgs { const unsigned char *img[2]; size_t pitch[2], bstride[2]; unsigned *cells; int H, W, rgb, wide[2], shift; unsigned mask; };
+
+// the 16 pixels of one unit as they lie in memory, little-endian in w; nb: the bytes of the unit that lie inside the row (the rest reads as 0)
+template <int BPP>
+__device__ inline void diff_load_unit(const unsigned char *p, bool wide, int nb, unsigned (&w)[4 * BPP])
+{
+    if (wide) {
+#pragma unroll
+        for (int q = 0; q < BPP; ++q) {
+            const uint4 v = reinterpret_cast<const uint4 *>(p)[q];
+            w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4 * BPP; ++q) w[q] = 0u;
+#pragma unroll
+        for (int k = 0; k < 16 * BPP; ++k)
+            if (k < nb) w[k >> 2] |= (unsigned)p[k] << (8 * (k & 3));
+    }
+}
+
+template <int BPP>
+__device__ inline unsigned diff_luma(const unsigned (&w)[4 * BPP], int px, unsigned mask, int shift, int rgb)
+{
+    if constexpr (BPP == 1) {
+        return dedup_sample((w[px >> 2] >> (8 * (px & 3))) & 0xffu, mask, shift);
+    } else if constexpr (BPP == 2) {
+        return dedup_sample((w[px >> 1] >> (16 * (px & 1))) & 0xffffu, mask, shift);
+    } else {
+        const int k = 3 * px;
+        return scene_luma3((w[k >> 2] >> (8 * (k & 3))) & 0xffu, (w[(k + 1) >> 2] >> (8 * ((k + 1) & 3))) & 0xffu,
+                           (w[(k + 2) >> 2] >> (8 * ((k + 2) & 3))) & 0xffu, rgb);
+    }
+}
+
+template <int BPP>
+__global__ __launch_bounds__(256) void frame_diff_cells_kernel(DiffArgs a)
+{
+    __shared__ unsigned slot[SG_CELLS * 256];
+    __shared__ int cb[SG_CELLS + 1];
+    const int tid = threadIdx.x, ci = blockIdx.x, g = blockIdx.y;
+    const size_t b = blockIdx.z;
+    const int y0 = scene_cell_bound(ci, a.H), y1 = scene_cell_bound(ci + 1, a.H);
+    if (tid <= SG_CELLS) cb[tid] = scene_cell_bound(g * SG_CELLS + tid, a.W);
+#pragma unroll
+    for (int k = 0; k < SG_CELLS; ++k) slot[k * 256 + tid] = 0u;
+    __syncthreads();
+    const int xlo = cb[0], xhi = cb[SG_CELLS];   // xhi <= W
+    if (y1 > y0 && xhi > xlo) {                  // uniform over the workgroup
+        const int u0 = xlo >> 4, nu = ((xhi + 15) >> 4) - u0, items = (y1 - y0) * nu;
+        const unsigned char *pa = a.img[0] + b * a.bstride[0], *pb = a.img[1] + b * a.bstride[1];
+        for (int t = tid; t < items; t += 256) {
+            const int r = t / nu, x0 = (u0 + (t - r * nu)) << 4;      // x0 < xhi <= W
+            const bool inside = x0 + 16 <= a.W;
+            const int nb = min(16, a.W - x0) * BPP;
+            unsigned wa[4 * BPP], wb[4 * BPP];
+            diff_load_unit<BPP>(pa + (size_t)(y0 + r) * a.pitch[0] + (size_t)x0 * BPP, a.wide[0] && inside, nb, wa);
+            diff_load_unit<BPP>(pb + (size_t)(y0 + r) * a.pitch[1] + (size_t)x0 * BPP, a.wide[1] && inside, nb, wb);
+            int j = 0, hi = cb[1];
+            unsigned acc = 0u;
+#pragma unroll
+            for (int px = 0; px < 16; ++px) {
+                const int x = x0 + px;
+                if (x >= xlo && x < xhi) {
+                    while (x >= hi) {            // ends at j <= 7: x < xhi = cb[8]
+                        slot[j * 256 + tid] += acc;
+                        acc = 0u;
+                        ++j;
+                        hi = cb[j + 1];
+                    }
+                    acc += dedup_absdiff(diff_luma<BPP>(wa, px, a.mask, a.shift, a.rgb), diff_luma<BPP>(wb, px, a.mask, a.shift, a.rgb));
+                }
+            }
+            slot[j * 256 + tid] += acc;
+        }
+    }
+    __syncthreads();
+    const int c = tid >> 5, l = tid & 31;
+    unsigned long long s = 0ull;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += slot[c * 256 + l + 32 * k];
+#pragma unroll
+    for (int off = 16; off >= 1; off >>= 1) s += __shfl_xor(s, off, 32);
+    if (l == 0) {
+        const unsigned n = (unsigned)(y1 - y0) * (unsigned)(cb[c + 1] - cb[c]);
+        a.cells[b * DEDUP_CELLS + ci * SCENE_GRID + g * SG_CELLS + c] = n ? dedup_cell_measure(s, n) : 0u;
+    }
+}
+
+__global__ __launch_bounds__(256) void duplicate_flags_kernel(const unsigned *__restrict__ cells, size_t stride, unsigned threshold,
+                                                              unsigned *__restrict__ flags, unsigned *__restrict__ scores)
+{
+    __shared__ unsigned part[4];
+    const int tid = threadIdx.x;
+    const size_t k = blockIdx.x;
+    const unsigned *c = cells + k * stride;
+    unsigned m = 0u;
+    for (int i = tid; i < DEDUP_CELLS; i += 256) m = max(m, c[i]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) m = max(m, (unsigned)__shfl_xor(m, off, 64));
+    if ((tid & 63) == 0) part[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned score = max(max(part[0], part[1]), max(part[2], part[3]));
+        flags[k] = score <= threshold ? 1u : 0u;
+        if (scores) scores[k] = score;
+    }
+}
+
+int launch_frame_diff_cells(const unsigned char *a, size_t a_pitch, size_t a_bstride, const unsigned char *b, size_t b_pitch, size_t b_bstride, int n,
+                            int H, int W, int C, int order, int sample_bytes, int depth, int shift, unsigned *cells, hipStream_t s)
+{
+    DiffArgs p{{a, b}, {a_pitch, b_pitch}, {a_bstride, b_bstride}, cells, H, W, order == 1, {0, 0}, shift, (1u << depth) - 1u};
+    p.wide[0] = mult_of(16, {(size_t)(uintptr_t)a, a_pitch, n > 1 ? a_bstride : 0});
+    p.wide[1] = mult_of(16, {(size_t)(uintptr_t)b, b_pitch, n > 1 ? b_bstride : 0});
+    const dim3 grid(SCENE_GRID, SG_GROUPS, (unsigned)n);
+    if (C == 3) frame_diff_cells_kernel<3><<<grid, 256, 0, s>>>(p);
+    else if (sample_bytes == 2) frame_diff_cells_kernel<2><<<grid, 256, 0, s>>>(p);
+    else frame_diff_cells_kernel<1><<<grid, 256, 0, s>>>(p);
+    return (int)hipGetLastError();
+}
+int launch_duplicate_flags(const unsigned *cells, size_t stride, int n, unsigned threshold, unsigned *flags, unsigned *scores, hipStream_t s)
+{
+    duplicate_flags_kernel<<<dim3((unsigned)n), 256, 0, s>>>(cells, stride, threshold, flags, scores);
     return (int)hipGetLastError();
 }
 

@@ -57,6 +57,10 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--resample", choices=("nearest", "blend"), default="nearest",
                    help="with --output-fps: the closest midpoint (default), or the two around the output time mixed")
     p.add_argument("--resample-depth", type=int, default=3, metavar="D", help="with --output-fps: midpoints down to 1 / 2^D of a frame interval (1..5, default 3)")
+    p.add_argument("--dedup", type=float, default=None, metavar="FRACTION",
+                   help="with --output-fps: drop frames that copy the frame before them and interpolate across the gap; a frame is a copy when no "
+                        "cell's mean absolute luma difference exceeds FRACTION of full scale (0: bit-identical luma only; no default is claimed)")
+    p.add_argument("--dedup-max-run", type=int, default=None, metavar="N", help="with --dedup: at most N frames in a row are dropped (default 3)")
     g = p.add_mutually_exclusive_group()
     g.add_argument("--scale", type=float, default=None, help="resize every frame on the device (default: no resize; the reference: 0.5)")
     g.add_argument("--size", type=_size, default=None, metavar="HxW", help="resize every frame on the device to H x W")
@@ -84,6 +88,12 @@ def _run(args) -> int:
                             (args.frame_interval != 1, "--frame-interval other than 1")):
             if given:
                 raise ValueError(f"--output-fps excludes {name}: the output rate alone decides which frames are written")
+    else:
+        for given, name in ((args.dedup is not None, "--dedup"), (args.dedup_max_run is not None, "--dedup-max-run")):
+            if given:
+                raise ValueError(f"{name} needs --output-fps: dropped frames are replaced on the resampler's time grid")
+    if args.dedup_max_run is not None and args.dedup is None:
+        raise ValueError("--dedup-max-run needs --dedup FRACTION")
     mode = "resample" if resample else (args.mode or "reference")
     with y4m.Y4MReader(args.input) as reader:
         head = reader.header
@@ -111,7 +121,9 @@ def _run(args) -> int:
                                yuv_standard=args.yuv_standard, yuv_full_range=args.full_range, scale=args.scale, size=args.size,
                                scene_threshold=args.scene_threshold, copy_out=False,
                                **(dict(rate_in=head.rate, rate_out=args.output_fps, resample_depth=args.resample_depth,
-                                       resample_method=args.resample) if resample else {}))
+                                       resample_method=args.resample) if resample else {}),
+                               **(dict(dedup_threshold=args.dedup, dedup_max_run=3 if args.dedup_max_run is None else args.dedup_max_run)
+                                  if args.dedup is not None else {}))
         if args.evaluate:
             print(fi.evaluate(list(reader), every=args.every))      # evaluate() indexes the clip: all of it is held
             return 0
@@ -124,7 +136,8 @@ def _run(args) -> int:
         if args.output != "-":
             print(f"{reader.frames_read} frames in, {writer.frames_written} frames out at {out_head.fps_num}:{out_head.fps_den} fps "
                   f"({out_head.width} x {out_head.height}, {head.pixel_format}, "
-                  + (f"{args.resample} at depth {args.resample_depth})" if resample else f"factor {factor})"), file=sys.stderr)
+                  + (f"{args.resample} at depth {args.resample_depth})" if resample else f"factor {factor})")
+                  + (f", {len(fi.duplicates)} duplicate frames dropped" if args.dedup is not None else ""), file=sys.stderr)
     return 0
 
 

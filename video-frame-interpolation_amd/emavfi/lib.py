@@ -66,6 +66,8 @@ _PROTOTYPES = {
     "emavfi_hold_frames_u8": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p, c_int, c_size_t, c_void_p]),
     "emavfi_resample_frames": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int,
                                        c_size_t, c_int, c_int, c_int, c_void_p]),
+    "emavfi_frame_diff_cells": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 8 + [c_void_p, c_void_p]),
+    "emavfi_duplicate_flags": (c_int, [c_void_p, c_size_t, c_int, ctypes.c_uint, c_void_p, c_void_p, c_void_p]),
     "emavfi_frame_metrics_workspace_bytes": (c_size_t, [c_int] * 4),
     "emavfi_frame_metrics_u8": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 4
                                 + [c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -1126,6 +1128,95 @@ def resample_frames(dst, srcs, nodes, table, flags=None, sample_bytes=1, depth=8
                                             flags.data_ptr() if flags is not None else None, flags.numel() if flags is not None else 0,
                                             fb, int(sample_bytes), int(depth), int(shift), _stream()), "emavfi_resample_frames")
     return dst
+
+
+# ---------------------------------------------------------------- duplicate frames (include/emavfi.h, "DUPLICATE FRAME DEFINITION")
+def dedup_threshold_units(fraction, depth=8) -> int:
+    """The u32 threshold of duplicate_flags for "no cell's mean absolute luma difference exceeds `fraction` of full scale":
+    floor(fraction * 16 * (2^depth - 1)) (a cell's measure is kept in sixteenths of a count); depth 8 for byte frames.  0 flags exactly the
+    pairs whose luma is bit-identical."""
+    import math
+    if isinstance(fraction, bool) or not isinstance(fraction, (int, float)) or not 0.0 <= fraction <= 1.0:
+        raise ValueError("dedup_threshold_units: fraction must be a number in 0..1")
+    if isinstance(depth, bool) or depth not in (8, 10, 12, 16):
+        raise ValueError("dedup_threshold_units: depth must be 8, 10, 12 or 16")
+    return int(math.floor(float(fraction) * (16 * ((1 << depth) - 1))))
+
+
+def _sample_image(t, what, shape=None):
+    """(pointer, pitch, batch stride in BYTES, sample_bytes) of an image batch [n,H,W,C] of bytes (uint8, C = 1 or 3) or of 16-bit words
+    ([n,H,W] or [n,H,W,1], torch.uint16 / torch.int16); rows and batches may be strided, a row must be dense"""
+    import torch
+    _pinned_or_cuda(t, what)
+    if t.dtype == torch.uint8:
+        sb = 1
+    elif t.element_size() == 2 and not t.dtype.is_floating_point:
+        sb = 2
+        if t.dim() == 3:
+            t = t.unsqueeze(-1)
+    else:
+        raise ValueError(f"{what}: uint8 [n,H,W,C] or 16-bit integer [n,H,W] images expected, got {t.dtype}")
+    if t.dim() != 4 or min(t.shape) < 1:
+        raise ValueError(f"{what}: a non-empty [n,H,W,C] image batch expected")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: shape {tuple(shape)} expected, got {tuple(t.shape)}")
+    n, H, W, C = t.shape
+    if (C > 1 and t.stride(3) != 1) or (W > 1 and t.stride(2) != C):
+        raise ValueError(f"{what}: the rows must be dense (only rows and batches may be strided)")
+    pitch = t.stride(1) if H > 1 else W * C     # in samples; a dimension of size 1 has no meaningful stride: the dense value stands in
+    return t.data_ptr(), pitch * sb, (t.stride(0) if n > 1 else pitch * H) * sb, sb, tuple(t.shape)
+
+
+def frame_diff_cells(a, b, order="bgr", depth=None, shift=0, out=None, device=None):
+    """Per pair k and cell of the 32 x 32 scene grid: the ceiling of the mean absolute luma difference of image k of `a` and image k of `b`
+    in sixteenths of a count (the duplicate-frame definition of include/emavfi.h) -> int32 [n,1024].  `a` / `b`: uint8 [n,H,W,C], C = 1 (a
+    Y plane) or 3 (interleaved colour, `order` says which byte is red), or 16-bit integer [n,H,W] planes whose samples are
+    (word >> shift) & (2^depth - 1), depth 10, 12 or 16; device tensors or pinned host memory (`device` names the GPU), rows and batches
+    may be strided, and the two may overlap (frames[:-1] against frames[1:]).  `out`: a contiguous int32 [n,1024] device tensor to fill -
+    every word is written."""
+    import torch
+    pa, apitch, abs_, sb, shape = _sample_image(a, "frame_diff_cells(a)")
+    pb, bpitch, bbs, sb2, _ = _sample_image(b, "frame_diff_cells(b)", shape)
+    if sb != sb2:
+        raise ValueError("frame_diff_cells: a and b must hold the same kind of sample")
+    n, H, W, C = shape
+    depth = (8 if sb == 1 else 16) if depth is None else int(depth)
+    dev = next((t.device for t in (a, b) if t.is_cuda), None) or torch.device(device if device is not None else "cuda")
+    if out is None:
+        out = torch.empty(n, SCENE_SIG_WORDS, dtype=torch.int32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (n, SCENE_SIG_WORDS) and out.is_contiguous()):
+        raise ValueError(f"frame_diff_cells: out must be a contiguous int32 [n,{SCENE_SIG_WORDS}] device tensor")
+    with torch.cuda.device(dev):
+        check(load().emavfi_frame_diff_cells(pa, apitch, abs_, pb, bpitch, bbs, n, H, W, C, _order_code(order), sb, depth, int(shift),
+                                             out.data_ptr(), _stream()), "emavfi_frame_diff_cells")
+    return out
+
+
+def duplicate_flags(cells, threshold, flags=None, scores=None, with_scores=True):
+    """Per pair k: score = the maximum of its 1024 cell measures (frame_diff_cells), flag = score <= threshold (an int in score units:
+    dedup_threshold_units).  `cells`: an int32 device tensor [n,1024] with dense rows (the rows may be strided).  Returns (flags, scores):
+    int32 [n] device tensors (`flags=` / `scores=` fill given ones; with_scores=False passes NULL and returns None for the scores)."""
+    import torch
+    _require_cuda(cells)
+    if cells.dtype != torch.int32 or cells.dim() != 2 or cells.shape[0] < 1 or cells.shape[1] != SCENE_SIG_WORDS or cells.stride(1) != 1:
+        raise ValueError(f"duplicate_flags: an int32 device tensor [n, {SCENE_SIG_WORDS}] with dense rows expected")
+    n = cells.shape[0]
+    threshold = int(threshold)
+    if not 0 <= threshold < 2 ** 32:
+        raise ValueError("duplicate_flags: threshold must be a u32 in score units")
+
+    def vec(t, name):
+        if t is None:
+            return torch.empty(n, dtype=torch.int32, device=cells.device)
+        if not (t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (n,) and t.is_contiguous()):
+            raise ValueError(f"duplicate_flags: {name} must be a contiguous int32 [{n}] device tensor")
+        return t
+    flags = vec(flags, "flags")
+    scores = vec(scores, "scores") if (with_scores or scores is not None) else None
+    with torch.cuda.device(cells.device):
+        check(load().emavfi_duplicate_flags(cells.data_ptr(), cells.stride(0) if n > 1 else SCENE_SIG_WORDS, n, threshold, flags.data_ptr(),
+                                            scores.data_ptr() if scores is not None else None, _stream()), "emavfi_duplicate_flags")
+    return flags, scores
 
 
 # ---------------------------------------------------------------- frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION")

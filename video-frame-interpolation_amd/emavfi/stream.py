@@ -87,6 +87,16 @@ batch's output frames - source frames included - into the buffer that leaves for
 ``scene_threshold`` is set.  ``run_chunked`` and ``run(frames, rank, world)`` work as before on the global time grid.  Needs
 ``reference_quirks=False`` (the constructor's default is the reference's behaviour, which this is not), ``frame_interval=1``, the default
 ``interpolation_factor`` and ``zero_copy=False``; all pixel formats work, ``scale`` / ``size`` on the byte formats; ``evaluate()`` is unaffected.
+``dedup_threshold`` (opt-in, mode "resample" only; a fraction in [0, 1], 0 = bit-identical luma) drops frames that copy the frame before them -
+24 fps film in a 30 fps stream, animation on twos, screen captures - and interpolates across the gap instead of yielding the copy again (the
+duplicate-frame definition of include/emavfi.h: per cell of the 32 x 32 scene grid the mean absolute luma difference, the MAXIMUM over the
+cells; all ten pixel formats, scored as staged, at source size).  Output count and times do not change; an output inside a gap of ``m``
+source intervals comes from that gap's tree, ``ceil(log2 m)`` levels deeper (``dedup_kept``, ``resample_plan_dedup``).  ``dedup_max_run``
+(default 3) bounds the dropped frames in a row, ``dedup_span`` (default 64) keeps every frame whose global index it divides, so that
+``run_chunked`` with a ``chunk_pairs`` that is a multiple of it sees what the whole clip would.  The set of forwards depends on the flags, so
+- unlike the scene decision - the host reads them before it plans: a pre-pass uploads the call's frames in slot-sized batches, scores the
+consecutive pairs and waits ONCE per ``run()`` call (once per chunk in ``run_chunked``); the source frames cross PCIe twice.  ``duplicates``
+lists ``(t, score)`` of the dropped frames, ``dedup_scores`` of every scored pair ``(t - 1, t)``, with global indices.  One process only.
 """
 from __future__ import annotations
 
@@ -168,7 +178,26 @@ class ResamplePlan(NamedTuple):
         return sum(len(lv) for levels in self.pairs.values() for lv in levels)
 
 
+class DedupPlan(NamedTuple):
+    """What ``FrameInterpolator.resample_plan_dedup`` returns.  ``outputs``: ``(k, t_i, m, j0, j1, w)`` per output frame in emission order -
+    output ``k`` is served from the gap of ``m`` source intervals that starts at the kept frame ``t_i`` (a global index) and is node ``j0``
+    (``w`` = 0, then ``j1 == j0``) or the blend of nodes ``j0`` and ``j1`` of that gap's tree of depth ``D + ceil(log2 m)``; node 0 is source
+    ``t_i``, node ``2^(D + ceil(log2 m))`` source ``t_i + m``.  ``gaps``: ``{t_i: (m, levels)}``, ``levels[l]`` = the needed nodes of
+    recursion level ``l + 1``, ascending - one forward each.  ``P`` / ``Q``: ``rate_in / rate_out`` in lowest terms; ``D``: the depth asked for."""
+    outputs: List[Tuple[int, int, int, int, int, int]]
+    gaps: Dict[int, Tuple[int, List[List[int]]]]
+    P: int
+    Q: int
+    D: int
+
+    @property
+    def forwards(self) -> int:
+        return sum(len(lv) for _, levels in self.gaps.values() for lv in levels)
+
+
 class FrameInterpolator:
+    dedup = None   # the duplicate threshold in score units (lib.dedup_threshold_units); None: duplicates are not looked for
+    dedup_max_run, dedup_span = 3, 64
     _depth = 0   # bits per sample of a 16-bit-word pixel format ("p010": 10, ...); 0 for the byte formats
     _planar = _yuv8 = False
     mode = "reference"
@@ -177,7 +206,8 @@ class FrameInterpolator:
                  reference_quirks: bool = True, mode: str = "reference", device=None, copy_out: bool = True, zero_copy: bool = False,
                  numa: str = "off", pixel_format: str = "bgr24", yuv_standard: str = "bt601", yuv_full_range: bool = False,
                  scale: Optional[float] = None, size=None, scene_threshold: Optional[float] = None,
-                 rate_in=None, rate_out=None, resample_depth: int = 3, resample_method: str = "nearest"):
+                 rate_in=None, rate_out=None, resample_depth: int = 3, resample_method: str = "nearest",
+                 dedup_threshold: Optional[float] = None, dedup_max_run: int = 3, dedup_span: int = 64):
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
             raise ValueError("interpolation_factor >= 0, frame_interval >= 1, batch_pairs >= 1 required")
         if mode not in ("reference", "recursive", "resample"):
@@ -199,6 +229,8 @@ class FrameInterpolator:
             self.resample_depth, self.resample_method = self._resample_args(resample_depth, resample_method)
         elif rate_in is not None or rate_out is not None:
             raise ValueError("rate_in / rate_out belong to mode='resample'")
+        if mode != "resample" and (dedup_threshold is not None or dedup_max_run != 3 or dedup_span != 64):
+            raise ValueError("dedup_threshold / dedup_max_run / dedup_span belong to mode='resample': dropped frames are replaced on its time grid")
         if mode == "recursive" and (interpolation_factor + 1) & interpolation_factor:
             raise ValueError("recursive midpoints need interpolation_factor = 2^k - 1 (1, 3, 7, ...)")
         if numa not in ("off", "auto"):
@@ -219,6 +251,16 @@ class FrameInterpolator:
                                  "scanned for cuts)")
         else:
             _lib.yuv_standard_code(yuv_standard, yuv_full_range)   # raises on an unknown standard
+        if mode == "resample":
+            self.dedup_max_run, self.dedup_span = self._dedup_args(dedup_max_run, dedup_span,
+                                                                   self.resample_depth if dedup_threshold is not None else None)
+            if dedup_threshold is not None:
+                if isinstance(dedup_threshold, bool) or not isinstance(dedup_threshold, (int, float)) or not 0 <= dedup_threshold <= 1:
+                    raise ValueError("dedup_threshold must be None (off) or a number in [0, 1]: the largest mean absolute luma difference of a "
+                                     "cell, as a fraction of full scale, at which a frame still counts as a copy of the frame before it (0: "
+                                     "bit-identical luma only)")
+                self.dedup = _lib.dedup_threshold_units(dedup_threshold, self._depth or 8)
+        self.duplicates, self.dedup_scores = [], []   # (t, score) of the dropped frames / of every scored pair (t - 1, t), global indices
         if scale is not None and size is not None:
             raise ValueError("scale and size are mutually exclusive")
         if scale is not None and not scale > 0:
@@ -377,6 +419,77 @@ class FrameInterpolator:
         if rank == world - 1 and ((n_frames - 1) * Q) % P == 0:
             outs.append((((n_frames - 1) * Q) // P, n_frames - 1, 0, 0, 0))
         return ResamplePlan(outs, pairs, P, Q, 1 << depth)
+
+    # ---- duplicate frames (include/emavfi.h, "DUPLICATE FRAME DEFINITION", Schedule): pure host logic over integers
+    @staticmethod
+    def _dedup_args(max_run, span, depth=None):
+        for name, v in (("dedup_max_run", max_run), ("dedup_span", span)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{name} must be an integer >= 1")
+        if depth is not None and depth + max_run.bit_length() > _lib.RESAMPLE_MAX_DEPTH:
+            raise ValueError(f"resample_depth {depth} with dedup_max_run {max_run}: a gap of {max_run + 1} intervals needs a tree of depth "
+                             f"{depth + max_run.bit_length()}, above the deepest one ({_lib.RESAMPLE_MAX_DEPTH}); lower either")
+        return max_run, span
+
+    @staticmethod
+    def dedup_kept(flags, n_frames: int, base: int = 0, max_run: int = 3, span: int = 64):
+        """The kept frames (local indices, ascending) of ``n_frames`` source frames whose first has the global index ``base``:
+        ``flags[t - 1]`` says that the pair ``(t - 1, t)`` was flagged as duplicates.  Frame ``t`` is dropped when its pair is flagged, unless it
+        is frame 0, the last frame, a frame with ``(base + t) % span == 0``, or the frame that follows ``max_run`` dropped frames in a row."""
+        max_run, span = FrameInterpolator._dedup_args(max_run, span)
+        flags, n = [bool(f) for f in flags], int(n_frames)
+        if n < 0 or base < 0 or len(flags) != max(n - 1, 0):
+            raise ValueError(f"dedup_kept: {n} frames have {max(n - 1, 0)} pairs, got {len(flags)} flags (n_frames >= 0, base >= 0)")
+        kept, run = [], 0
+        for t in range(n):
+            if t == 0 or t == n - 1 or (base + t) % span == 0 or run >= max_run or not flags[t - 1]:
+                kept.append(t)
+                run = 0
+            else:
+                run += 1
+        return kept
+
+    @staticmethod
+    def resample_gap(P: int, Q: int, depth: int, method: str, t0: int, t1: int):
+        """The outputs ``(k, t0, m, j0, j1, w)`` served from the gap of ``m = t1 - t0`` source intervals between the kept frames ``t0 < t1``
+        (global indices): those with ``t0 <= k P / Q < t1``, at ``R = k P - t0 Q`` over ``m Q`` in a tree of depth ``depth + ceil(log2 m)``.
+        With ``m`` = 1 these are ``resample_span``'s."""
+        m = t1 - t0
+        G, den, outs = 1 << (depth + (m - 1).bit_length()), m * Q, []
+        for k in range(-((-t0 * Q) // P), -((-t1 * Q) // P)):      # ceil(t0 Q / P) .. ceil(t1 Q / P) - 1
+            R = k * P - t0 * Q
+            if method == "nearest":
+                j = (2 * R * G + den) // (2 * den)
+                outs.append((k, t0, m, j, j, 0))
+            else:
+                j0 = (R * G) // den
+                w = (256 * (R * G - j0 * den) + den // 2) // den
+                outs.append((k, t0, m, j0 + 1, j0 + 1, 0) if w == 256 else (k, t0, m, j0, j0, 0) if w == 0 else (k, t0, m, j0, j0 + 1, w))
+        return outs
+
+    @staticmethod
+    def resample_plan_dedup(kept, rate_in, rate_out, depth: int = 3, method: str = "nearest", base: int = 0, tail: bool = True) -> DedupPlan:
+        """What ``run(frames)`` yields in mode "resample" once the frames outside ``kept`` (``dedup_kept``: local indices, the first frame has
+        the global index ``base``) are dropped, symbolically and in order, and what it computes: a ``DedupPlan`` on the global grid.  The
+        output count and times are ``resample_plan``'s; ``tail``: the output that falls on the last kept frame, if there is one, is part of
+        the plan (``run_chunked`` emits it with the final chunk only).  Pure host logic (no device needed)."""
+        P, Q = FrameInterpolator.resample_ratio(rate_in, rate_out)
+        depth, method = FrameInterpolator._resample_args(depth, method)
+        kept = [int(t) for t in kept]
+        if base < 0 or any(t < 0 for t in kept[:1]) or any(b <= a for a, b in zip(kept, kept[1:])):
+            raise ValueError("resample_plan_dedup: kept must be ascending frame indices >= 0, base >= 0")
+        outs, gaps = [], {}
+        for t0, t1 in zip(kept, kept[1:]):
+            dm = depth + (t1 - t0 - 1).bit_length()
+            if dm > _lib.RESAMPLE_MAX_DEPTH:
+                raise ValueError(f"resample_plan_dedup: the gap ({t0}, {t1}) needs a tree of depth {dm}, above the deepest one "
+                                 f"({_lib.RESAMPLE_MAX_DEPTH}): lower depth or dedup_max_run")
+            mine = FrameInterpolator.resample_gap(P, Q, depth, method, base + t0, base + t1)
+            outs += mine
+            gaps[base + t0] = (t1 - t0, FrameInterpolator.resample_needed({j for o in mine for j in o[3:5]}, dm))
+        if tail and kept and ((base + kept[-1]) * Q) % P == 0:
+            outs.append((((base + kept[-1]) * Q) // P, base + kept[-1], 1, 0, 0, 0))
+        return DedupPlan(outs, gaps, P, Q, depth)
 
     # ---- segment sharding (SURVEY.md section 8e, BASELINE configs[4]): one process per GPU, each with a contiguous
     # run of the stream's frame pairs.  No exchange between ranks: a pair's two frames are all a forward needs.
@@ -729,6 +842,8 @@ class FrameInterpolator:
         if not (hasattr(frames, "__len__") and hasattr(frames, "__getitem__")):
             frames = list(frames)
         if self.mode == "resample":
+            if self.dedup is not None and world != 1:
+                raise ValueError("run: world > 1 with dedup_threshold: a shard boundary is no anchor of the duplicate schedule (one process)")
             yield from self._run_resample(frames, rank, world, _emit_tail, _base)
             return
         n_total = len(frames)
@@ -872,27 +987,29 @@ class FrameInterpolator:
             yield self._resized_bytes(frames[last]) if self._resize else words(frames[last])
 
     # ---- mode "resample": forwards level by level over the pairs that need the node, nodes post-processed once, outputs assembled on the post lane
-    def _resample_forwards(self, x, ia, ib, levels):
+    def _resample_forwards(self, x, ia, ib, levels, depths):
         """levels[l] = [(pair of the batch, node)] of recursion level l + 1, in node-buffer order -> the model's output per non-empty level
-        ([len(levels[l]), 3, H, W]).  The recursion and the re-normalisation of a midpoint are ``_predict``'s."""
-        G, outs, norm = 1 << self.resample_depth, [], {}
+        ([len(levels[l]), 3, H, W]); depths[k]: the depth of pair k's tree (a gap of m source intervals: D + ceil(log2 m)).  The recursion and
+        the re-normalisation of a midpoint are ``_predict``'s."""
+        outs, norm = [], {}
         if self._norm is None:
             self._norm = (torch.tensor(_lib.IMAGENET_MEAN, device=x.device).view(1, 3, 1, 1),
                           torch.tensor(_lib.IMAGENET_STD, device=x.device).view(1, 3, 1, 1))
         mean, std = self._norm
 
         def node(k, j):
-            return x[ia[k]] if j == 0 else x[ib[k]] if j == G else norm[(k, j)]
+            return x[ia[k]] if j == 0 else x[ib[k]] if j == 1 << depths[k] else norm[(k, j)]
 
         with torch.no_grad():
             for l, items in enumerate(levels):
                 if not items:
                     break                    # a needed node has needed parents: below an empty level there is nothing
-                step = G >> (l + 1)
+                step = [(1 << depths[k]) >> (l + 1) for k, _ in items]
                 if l == 0:
                     x1, x2 = self._rows(x, [ia[k] for k, _ in items]), self._rows(x, [ib[k] for k, _ in items])
                 else:
-                    x1, x2 = torch.stack([node(k, j - step) for k, j in items]), torch.stack([node(k, j + step) for k, j in items])
+                    x1 = torch.stack([node(k, j - st) for (k, j), st in zip(items, step)])
+                    x2 = torch.stack([node(k, j + st) for (k, j), st in zip(items, step)])
                 m = self.model(x1, x2)
                 outs.append(m)
                 if l + 1 < len(levels) and levels[l + 1]:
@@ -902,19 +1019,60 @@ class FrameInterpolator:
         return outs
 
     def _resample_batch(self, chunk, outs_of, ia, ib):
-        """One batch's host-side schedule: (levels, table, n_nodes).  `chunk`: its pairs (s, s + 1), local frame indices; `outs_of[s]`: the
-        outputs (r, j0, j1, w) of pair s in order; ia / ib: the staged rows of each pair's frames.  Node frames are numbered level by level, pair
-        by pair - the order the forwards produce them in."""
-        D, G = self.resample_depth, 1 << self.resample_depth
-        needed = [self.resample_needed({j for _, j0, j1, _ in outs_of[s] for j in (j0, j1)}, D) for s, _ in chunk]
-        levels = [[(k, j) for k in range(len(chunk)) for j in needed[k][l]] for l in range(D)]
+        """One batch's host-side schedule: (levels, table, n_nodes, depths).  `chunk`: its pairs (s, s + m) of kept frames, local frame indices
+        (m = 1 unless duplicates were dropped between them); `outs_of[s]`: the outputs (R, j0, j1, w) of pair s in order; ia / ib: the staged
+        rows of each pair's frames.  A pair's tree has depth D + ceil(log2 m); the levels run to the deepest tree of the batch.  Node frames
+        are numbered level by level, pair by pair - the order the forwards produce them in."""
+        depths = [self.resample_depth + (s2 - s - 1).bit_length() for s, s2 in chunk]
+        needed = [self.resample_needed({j for _, j0, j1, _ in outs_of[s] for j in (j0, j1)}, depths[k]) for k, (s, _) in enumerate(chunk)]
+        levels = [[(k, j) for k in range(len(chunk)) if l < depths[k] for j in needed[k][l]] for l in range(max(depths))]
         index = {item: i for i, item in enumerate(item for lv in levels for item in lv)}
         table = []
         for k, (s, _) in enumerate(chunk):
-            ref = lambda j: ia[k] if j == 0 else ib[k] if j == G else _lib.RESAMPLE_NODES | index[(k, j)]
+            ref = lambda j: ia[k] if j == 0 else ib[k] if j == 1 << depths[k] else _lib.RESAMPLE_NODES | index[(k, j)]
             for r, j0, j1, w in outs_of[s]:
                 table.append((ref(j0), ref(j1), w, k + 1 if (self.scene is not None and r > 0) else 0, ia[k]))
-        return levels, table, len(index)
+        return levels, table, len(index), depths
+
+    def _dedup_image(self, buf):
+        """the staged frames `buf` as the duplicate measure reads them, at source size: interleaved colour, or the Y plane as a 1-channel image
+        (bytes of pitch W, or the 16-bit words of the deeper formats)"""
+        if self._depth:
+            return buf[:, :buf.shape[1] * 2 // 3].view(torch.int16)
+        return self._planes(buf)[0].unsqueeze(-1) if self._yuv8 else buf
+
+    def _dedup_scan(self, frames, lo, hi):
+        """The pre-pass of a run() with dedup_threshold: frames lo .. hi go to the device in slot-sized batches (consecutive batches share one
+        frame), every consecutive pair is scored, flags and scores come back with ONE host wait.  Returns (flags, scores) of the pairs
+        (lo, lo + 1) .. (hi - 1, hi).  The frames cross PCIe here and again in the batch loop that follows."""
+        n = hi - lo
+        cap = self._slots[0]["d_in"].shape[0]                   # >= 2 frames
+        dd = getattr(self, "_dd", None)
+        if dd is None or dd["cap"] < cap or dd["fs"].shape[1] < n:
+            size = max(n, dd["fs"].shape[1] if dd is not None else 0)
+            dd = self._dd = {"cap": cap, "cells": torch.empty(cap - 1, _lib.SCENE_SIG_WORDS, dtype=torch.int32, device=self.device),
+                             "fs": torch.zeros(2, size, dtype=torch.int32, device=self.device),
+                             "h_fs": torch.zeros(2, size, dtype=torch.int32).pin_memory(), "ready": torch.cuda.Event()}
+        _, depth, shift = _lib.resample_sample_format(self.pixel_format)
+        self._pre.wait_stream(torch.cuda.current_stream(self.device))     # buffers made on the caller's stream are used on the pre lane
+        for bi, f0 in enumerate(range(lo, hi, cap - 1)):
+            f1 = min(f0 + cap - 1, hi)
+            nfr, slot = f1 - f0 + 1, self._slots[bi & 1]
+            self._stage(slot, frames, [tuple(range(f0, f1 + 1))])           # waits until the slot's previous upload has been read
+            with torch.cuda.stream(self._pre):
+                self._pre.wait_event(slot["fwd"])
+                self._pre.wait_event(slot["done"])
+                slot["d_in"][:nfr].copy_(slot["h_in"][:nfr], non_blocking=True)
+                slot["consumed"].record(self._pre)
+                img = self._dedup_image(slot["d_in"][:nfr])
+                cells = _lib.frame_diff_cells(img[:-1], img[1:], depth=depth, shift=shift, out=dd["cells"][:nfr - 1])
+                _lib.duplicate_flags(cells, self.dedup, flags=dd["fs"][0, f0 - lo:f1 - lo], scores=dd["fs"][1, f0 - lo:f1 - lo])
+        with torch.cuda.stream(self._pre):
+            dd["h_fs"].copy_(dd["fs"], non_blocking=True)
+            dd["ready"].record(self._pre)
+        dd["ready"].synchronize()                                         # the one host wait: the plan depends on the flags
+        got = dd["h_fs"].numpy()
+        return [int(v) for v in got[0, :n]], [int(v) & 0xFFFFFFFF for v in got[1, :n]]
 
     def _run_resample(self, frames, rank, world, emit_tail, base):
         from .dist import shard_range
@@ -936,17 +1094,26 @@ class FrameInterpolator:
         words = (lambda v: v.view(np.uint16)) if self._depth else (lambda v: v)
         self._alloc(first.shape)
         self.scene_cuts, self.scene_scores = [], []
-        outs_of = {s: [] for s in range(a, b)}
-        for k, s, j0, j1, w in self.resample_span(P, Q, D, self.resample_method, base + a, base + b):
-            outs_of[s - base].append((k * P - s * Q, j0, j1, w))
+        self.duplicates, self.dedup_scores = [], []
+        kept = list(range(a, b + 1)) if b > a else []
+        if self.dedup is not None and b > a:
+            # the set of forwards depends on the flags: the host reads them before it plans (one wait per run() call)
+            flags, scores = self._dedup_scan(frames, a, b)
+            kept = [a + t for t in self.dedup_kept(flags, b - a + 1, base + a, self.dedup_max_run, self.dedup_span)]
+            self.dedup_scores = [(base + a + 1 + i, sc) for i, sc in enumerate(scores)]
+            keep = set(kept)
+            self.duplicates = [(base + t, scores[t - a - 1]) for t in range(a + 1, b + 1) if t not in keep]
+        gaps = list(zip(kept, kept[1:]))          # without duplicates: the pairs (s, s + 1), and resample_gap is resample_span
+        outs_of = {t0: [(k * P - (base + t0) * Q, j0, j1, w) for k, _, _, j0, j1, w in
+                        self.resample_gap(P, Q, D, self.resample_method, base + t0, base + t1)] for t0, t1 in gaps}
         bp = self.batch_pairs
-        chunks = [[(s, s + 1) for s in range(i, min(i + bp, b))] for i in range(a, b, bp)]
+        chunks = [gaps[i:i + bp] for i in range(0, len(gaps), bp)]
         fmt = _lib.resample_sample_format(self.pixel_format)
         main = torch.cuda.current_stream(self.device)
         if chunks:
             # the node and emission buffers of a slot hold the largest batch of this run
-            sizes = [(sum(len(outs_of[s]) for s, _ in c), sum(len(lv) for s, _ in c for lv in self.resample_needed(
-                {j for _, j0, j1, _ in outs_of[s] for j in (j0, j1)}, D))) for c in chunks]
+            sizes = [(sum(len(outs_of[s]) for s, _ in c), sum(len(lv) for s, s2 in c for lv in self.resample_needed(
+                {j for _, j0, j1, _ in outs_of[s] for j in (j0, j1)}, D + (s2 - s - 1).bit_length()))) for c in chunks]
             n_emit, n_node = max(o for o, _ in sizes), max(1, max(n for _, n in sizes))
             for slot in self._slots:
                 fs = tuple(slot["d_src"].shape[1:])
@@ -973,7 +1140,7 @@ class FrameInterpolator:
         for ci, chunk in enumerate(chunks):
             slot = self._slots[ci & 1]
             nup, ia, ib = staged
-            levels, table, n_nodes = self._resample_batch(chunk, outs_of, ia, ib)
+            levels, table, n_nodes, depths = self._resample_batch(chunk, outs_of, ia, ib)
             with torch.cuda.stream(self._pre):
                 self._pre.wait_event(slot["fwd"])       # the slot's x was last read by the forwards of batch ci - 2 ...
                 self._pre.wait_event(slot["done"])      # ... and its d_in / d_rs by that batch's assembly
@@ -985,7 +1152,7 @@ class FrameInterpolator:
                     self._scene_decide(slot, slot["d_in"][:nup], ia, ib)
                 slot["pre"].record(self._pre)
             main.wait_event(slot["pre"])
-            preds = self._resample_forwards(x, ia, ib, levels)                                        # on the caller's stream
+            preds = self._resample_forwards(x, ia, ib, levels, depths)                                     # on the caller's stream
             slot["fwd"].record(main)
             with torch.cuda.stream(self._post):
                 self._post.wait_event(slot["fwd"])
@@ -1035,13 +1202,18 @@ class FrameInterpolator:
     def run_chunked(self, frames: Iterable[np.ndarray], chunk_pairs: int = 64) -> Iterator[np.ndarray]:
         """``run(list(frames))``, byte for byte, over any iterable - no ``len()``, so a pipe works - holding at most
         ``chunk_pairs * frame_interval + 1`` source frames: the stream is cut as ``chunk_plan`` says, each chunk goes through ``run()``,
-        and the tail frame of every chunk but the last is neither yielded nor computed.  ``scene_cuts`` / ``scene_scores`` accumulate over
-        the chunks with global frame indices.  Single process: a stream of unknown length cannot be sharded over ranks."""
+        and the tail frame of every chunk but the last is neither yielded nor computed.  ``scene_cuts`` / ``scene_scores`` (and ``duplicates`` /
+        ``dedup_scores``) accumulate over the chunks with global frame indices.  With ``dedup_threshold`` set, ``chunk_pairs`` must be a
+        multiple of ``dedup_span``, and every chunk costs one host wait.  Single process: a stream of unknown length cannot be sharded over ranks."""
         if isinstance(chunk_pairs, bool) or not isinstance(chunk_pairs, int) or chunk_pairs < 1:
             raise ValueError("run_chunked: chunk_pairs must be an integer >= 1")
+        if self.dedup is not None and chunk_pairs % self.dedup_span:
+            raise ValueError(f"run_chunked: chunk_pairs = {chunk_pairs} with dedup_threshold must be a multiple of dedup_span = {self.dedup_span}: "
+                             "every chunk then starts and ends on a frame that is kept regardless, and sees what the whole clip would")
         L, it, held, lo = chunk_pairs * self.interval, iter(frames), [], 0
-        cuts, scores = [], []
+        cuts, scores, dups, dscores = [], [], [], []
         self.scene_cuts, self.scene_scores = [], []
+        self.duplicates, self.dedup_scores = [], []
         while True:
             for f in it:
                 held.append(f)
@@ -1055,6 +1227,9 @@ class FrameInterpolator:
                 cuts += [(a + lo, b + lo, sc) for a, b, sc in self.scene_cuts]
                 scores += [(a + lo, b + lo, sc) for a, b, sc in self.scene_scores]
                 self.scene_cuts, self.scene_scores = list(cuts), list(scores)
+                dups += self.duplicates                         # global indices already: run() was told where the chunk starts
+                dscores += self.dedup_scores
+                self.duplicates, self.dedup_scores = list(dups), list(dscores)
             if final:
                 return
             held, lo = held[-1:], lo + L
