@@ -100,6 +100,31 @@ extern "C" {
 #define EMAVFI_E_WORKSPACE (-3)   /* workspace or packed buffer too small */
 #define EMAVFI_E_LAUNCH (-4)      /* hipGetLastError() after a launch */
 
+/*
+ * SIZE LIMITS (the one place).  Sample bases, batch strides and every pitched 8 / 16-bit entry's pitches and strides are 64-bit.  INSIDE
+ * one sample the kernels keep narrow arithmetic on purpose: 32-bit byte offsets, 24-bit pixel indices.  The entries check what that needs
+ * BEFORE any pointer is touched and return EMAVFI_E_ARG with the limit in the message; the *_workspace_bytes queries and the launch lists
+ * are size_t / double throughout and exceed 2^32 at ordinary 4K batches.
+ *   "plane" = H * W * (channels padded as the kernels store them) * (bytes of the WIDEST element the mode keeps of that tensor): the
+ *   fusion tensor of mid_channels + 3 channels padded to a multiple of 16 (80 at the reference width), 2 bytes in EMAVFI_BF16 /
+ *   EMAVFI_F16, 4 bytes in EMAVFI_F32, EMAVFI_AMP16 and EMAVFI_F32X3 (which also keep it in fp32).
+ *     emavfi_forward*, emavfi_mdcn*, emavfi_context, emavfi_reconstruct (+ their queries, launch lists and census entries):
+ *                          B*H*W < 2^31, H*W < 2^24, plane < 4 GiB.  At the reference width: 16-bit modes up to 2^24 - 1 pixels a frame
+ *                          (4095 x 4096: a 2.4 GB plane), 4-byte modes up to 13 421 772 pixels (3840 x 2160 is 8 294 400).
+ *     emavfi_conv3x3:      INPUT plane (Cin padded to 16; fp32 65..72 -> 72) < 4 GiB; no limit on H*W or B*H*W; no limit on the output
+ *                          plane - every kernel writes through 64-bit addresses.  EMAVFI_F32X3 runs the tile kernel alone, whose input
+ *                          addresses are 64-bit as well: its plane is counted in f16 halves (2 bytes), i.e. the real [hi | lo] plane is
+ *                          < 8 GiB.
+ *     emavfi_deform_conv2d: H*W < 2^24, input plane (C padded to the kernel's width: 80 for 65..80) < 4 GiB.
+ *     emavfi_warp:         H*W < 2^31 (32-bit pixel offsets inside one fp32 plane); B and C are not limited.
+ *   Of these, two statements rest on READING the kernels, not on a run: "no limit on the output plane" was run for the tile kernel
+ *   (6 -> 64, a 4.3 GB output plane) - for the other families (an output larger than a < 4 GiB input needs Cout > Cin: conv_wreg's 128 ->
+ *   256 at stride 1) it follows from `obase` / `orow` being size_t arithmetic in conv_wreg.inl, conv_ring*.inl and conv3x3.inl; and the
+ *   EMAVFI_F32X3 plane was run just under and just over 4 GiB (4.0004 GiB), not between there and 8 GiB.
+ * Run at these sizes, with offsets past 2^31 inside a sample and past 2^32 in total: tests/test_gpu_large.py; the limits themselves, last
+ * admitted and first refused value: tests/test_cabi_cpu.py, tests/host/host_check.cpp.
+ */
+
 /* Activation selector of emavfi_conv3x3 (conv vs conv_block, ema_vfi.py:7-14). */
 #define EMAVFI_ACT_NONE 0
 #define EMAVFI_ACT_RELU 1

@@ -150,6 +150,65 @@ int main()
         CHECK(emavfi_reconstruct(ff, six, fo, 1, 64, 16, 16, EMAVFI_BF16, fake, 16, nullptr) == EMAVFI_E_WORKSPACE);
         CHECK(emavfi_reconstruct(ff, six, fo, 1, 64, 4096, 4096, EMAVFI_BF16, fake, 16, nullptr) == EMAVFI_E_ARG);
     }
+    // SIZE LIMITS (include/emavfi.h): the last admitted and the first refused value per entry and mode, on the host.  Admitted sizes
+    // go through the dry launch list, the *_workspace_bytes queries (more than 2^32, as size_t) and the entry with a 0-byte workspace
+    // (EMAVFI_E_WORKSPACE: the size guards let it pass); refused sizes are EMAVFI_E_ARG with the limit in the message.  H = 1: H*W = W.
+    {
+        const int hw24 = 1 << 24, plane4 = (int)(((size_t)1 << 32) / 320);   // 80 channels x 4 bytes: 4 GiB - 256 bytes of pixels
+        const size_t big = (size_t)1 << 32, huge = (size_t)1 << 60;
+        for (int dt : modes) {
+            const bool wide = dt == EMAVFI_F32 || dt == EMAVFI_AMP16 || dt == EMAVFI_F32X3;
+            const int last = wide ? plane4 : hw24 - 1;
+            const char *why = wide ? "4 GiB" : "2^24";
+            CHECK(emavfi_forward_launches(3, 64, 3, 1, 1, last, dt, nullptr, 0, nullptr, nullptr, 0) > 10);
+            CHECK(emavfi_workspace_bytes(3, 64, 3, 1, 1, last, dt) > big);
+            CHECK(emavfi_forward_launches(3, 64, 3, 1, 1, last + 1, dt, nullptr, 0, nullptr, nullptr, 0) == EMAVFI_E_ARG && strstr(emavfi_last_error(), why));
+            CHECK(emavfi_forward_launches(3, 64, 3, 0x7fffffff, 1, 1, dt, nullptr, 0, nullptr, nullptr, 0) > 10);
+            CHECK(emavfi_forward_launches(3, 64, 3, 1 << 30, 1, 2, dt, nullptr, 0, nullptr, nullptr, 0) == EMAVFI_E_ARG && strstr(emavfi_last_error(), "2^31"));
+            const size_t blob = emavfi_packed_bytes(3, 64, 3, dt);
+            CHECK(emavfi_forward(3, 64, 3, fake, blob, ff, ff, fo, fake, 0, 1, 1, last, dt, nullptr, nullptr) == EMAVFI_E_WORKSPACE);
+            CHECK(emavfi_forward(3, 64, 3, fake, blob, ff, ff, fo, fake, huge, 1, 1, last + 1, dt, nullptr, nullptr) == EMAVFI_E_ARG && strstr(emavfi_last_error(), why));
+            CHECK(emavfi_workspace_bytes(3, 64, 3, 2, 2160, 3840, dt) > big);
+        }
+        const float *eight[8] = {ff, ff, ff, ff, ff, ff, ff, ff};
+        for (int dt : dtypes) {
+            const bool wide = dt == EMAVFI_F32 || dt == EMAVFI_AMP16;
+            const int last = wide ? plane4 : hw24 - 1;
+            const char *why = wide ? "4 GiB" : "2^24";
+            CHECK(emavfi_mdcn_workspace_bytes(1, 67, 1, last, dt, 0) > big);
+            CHECK(emavfi_mdcn(ff, ff, ff, ff, ff, fo, 1, 67, 1, last, dt, 0, fake, 0, nullptr) == EMAVFI_E_WORKSPACE);
+            CHECK(emavfi_mdcn(ff, ff, ff, ff, ff, fo, 1, 67, 1, last + 1, dt, 0, fake, 0, nullptr) == EMAVFI_E_ARG && strstr(emavfi_last_error(), why));
+            CHECK(emavfi_mdcn(ff, ff, ff, ff, ff, fo, 1 << 30, 67, 1, 2, dt, 0, fake, 0, nullptr) == EMAVFI_E_ARG && strstr(emavfi_last_error(), "2^31"));
+            CHECK(emavfi_context_workspace_bytes(1, 64, 1, last, dt) > big && emavfi_reconstruct_workspace_bytes(1, 64, 1, last, dt) > big);
+            CHECK(emavfi_context(ff, eight, fo, 1, 64, 1, last, dt, fake, 0, nullptr) == EMAVFI_E_WORKSPACE);
+            CHECK(emavfi_reconstruct(ff, eight, fo, 1, 64, 1, last, dt, fake, 0, nullptr) == EMAVFI_E_WORKSPACE);
+            CHECK(emavfi_context_workspace_bytes(1, 64, 1, last + 1, dt) == 0 && strstr(emavfi_last_error(), why));
+            CHECK(emavfi_reconstruct(ff, eight, fo, 1, 64, 1, last + 1, dt, fake, huge, nullptr) == EMAVFI_E_ARG && strstr(emavfi_last_error(), why));
+            CHECK(emavfi_context_workspace_bytes(1 << 30, 64, 1, 2, dt) == 0 && strstr(emavfi_last_error(), "2^31"));
+        }
+        // conv3x3: the input plane per dtype (EMAVFI_F32X3 counts its f16 halves: 64-bit addresses on the tile kernel), no limit on H*W,
+        // none on the output plane (6 -> 64: four times the input, written with 64-bit addresses)
+        const int conv_dt[4] = {EMAVFI_BF16, EMAVFI_F16, EMAVFI_F32, EMAVFI_F32X3}, conv_px[4] = {128, 128, 256, 128};
+        for (int i = 0; i < 4; ++i) {
+            const int last = (int)(big / conv_px[i]) - 1;
+            CHECK(emavfi_conv3x3(ff, ff, ff, fo, 1, 64, 64, 1, last, 1, 0, conv_dt[i], fake, 0, nullptr) == EMAVFI_E_WORKSPACE);
+            CHECK(emavfi_conv3x3_workspace_bytes(1, 64, 64, 1, last, 1, conv_dt[i]) > big);
+            CHECK(emavfi_conv3x3(ff, ff, ff, fo, 1, 64, 64, 1, last + 1, 1, 0, conv_dt[i], fake, 0, nullptr) == EMAVFI_E_ARG && strstr(emavfi_last_error(), "input plane must be < 4 GiB"));
+        }
+        CHECK(emavfi_conv3x3(ff, ff, ff, fo, 1, 6, 64, 1, (int)(big / 32) - 1, 1, 0, EMAVFI_BF16, fake, 0, nullptr) == EMAVFI_E_WORKSPACE);
+        CHECK(emavfi_conv3x3(ff, ff, ff, fo, 1, 6, 64, 1, (int)(big / 32), 1, 0, EMAVFI_BF16, fake, 0, nullptr) == EMAVFI_E_ARG);
+        const int dcn_dt[3] = {EMAVFI_BF16, EMAVFI_F16, EMAVFI_F32}, dcn_last[3] = {hw24 - 1, hw24 - 1, plane4};
+        for (int i = 0; i < 3; ++i) {
+            CHECK(emavfi_deform_conv2d_workspace_bytes(1, 67, 67, 1, dcn_last[i], dcn_dt[i]) > big);
+            CHECK(emavfi_deform_conv2d(ff, ff, ff, ff, ff, fo, 1, 67, 67, 1, dcn_last[i], dcn_dt[i], fake, 0, nullptr) == EMAVFI_E_WORKSPACE);
+            CHECK(emavfi_deform_conv2d_workspace_bytes(1, 67, 67, 1, dcn_last[i] + 1, dcn_dt[i]) == 0);
+            CHECK(emavfi_deform_conv2d(ff, ff, ff, ff, ff, fo, 1, 67, 67, 1, dcn_last[i] + 1, dcn_dt[i], fake, huge, nullptr) == EMAVFI_E_ARG);
+        }
+        // warp has no workspace: a misaligned pointer is refused after the size guard, with another message
+        const float *odd = (const float *)(uintptr_t)260;
+        CHECK(emavfi_warp(odd, ff, fo, 1, 3, 1, 0x7fffffff, nullptr) == EMAVFI_E_ARG && strstr(emavfi_last_error(), "16-byte aligned"));
+        CHECK(emavfi_warp(odd, ff, fo, 1, 3, 2, 1 << 30, nullptr) == EMAVFI_E_ARG && strstr(emavfi_last_error(), "H*W must be < 2^31"));
+    }
     CHECK(emavfi_pack_weights(3, 64, 3, nullptr, 40, fake, 1 << 20, EMAVFI_BF16, nullptr) == EMAVFI_E_ARG);
     std::vector<const void *> params(40, fake);
     CHECK(emavfi_pack_weights(3, 64, 3, params.data(), 39, fake, (size_t)1 << 30, EMAVFI_BF16, nullptr) == EMAVFI_E_ARG);

@@ -601,6 +601,100 @@ def test_every_compute_entry_refuses_a_short_workspace_before_any_device_work():
             assert rc == -3 and f"{need} bytes" in msg and f"got {short}" in msg, (what, short, rc, msg)
 
 
+def test_size_limits_admit_their_last_value_and_refuse_the_next():
+    """include/emavfi.h, SIZE LIMITS: per entry and per mode the last admitted and the first refused value.  Nothing is launched and no
+    pointer is touched: admitted sizes go through the dry launch list and the *_workspace_bytes queries, or through the entry with
+    a workspace of 0 bytes - EMAVFI_E_WORKSPACE (-3) then proves that the size guards let it pass -; refused sizes return EMAVFI_E_ARG
+    (-1) with a message that names the limit.  H = 1 keeps the products exact: H*W = W.  At mid_channels 64 a pixel of the fusion plane
+    is 80 channels: 160 bytes in the 16-bit modes (H*W < 2^24 binds first), 320 bytes where the plane also exists in fp32 - fp32, amp16
+    and fp32x3 count 4 bytes per element - so 4 GiB - 256 bytes = 13 421 772 pixels is admitted and 13 421 773 is not."""
+    L = lib.load()
+    fake = ctypes.c_void_p(256)
+    launches = lambda B, H, W, dt: L.emavfi_forward_launches(3, 64, 3, B, H, W, dt, None, 0, None, None, 0)
+    HW24, PLANE4 = 1 << 24, (1 << 32) // 320
+    assert PLANE4 * 320 == (1 << 32) - 256
+    for dt in (lib.F32, lib.BF16, lib.F16, lib.AMP16, lib.F32X3):
+        wide = dt in (lib.F32, lib.AMP16, lib.F32X3)
+        last, first, why = (PLANE4, PLANE4 + 1, "4 GiB") if wide else (HW24 - 1, HW24, "2^24")
+        assert launches(1, 1, last, dt) > 10, (dt, lib.last_error())
+        need = L.emavfi_workspace_bytes(3, 64, 3, 1, 1, last, dt)
+        assert need > 1 << 32 and need % 256 == 0                      # (a size_t through ctypes, not an int)
+        assert launches(1, 1, first, dt) == -1 and why in lib.last_error(), (dt, lib.last_error())
+        # B*H*W: 2^31 - 1 is prime, so the last admitted product is B = 2^31 - 1 frames of one pixel
+        assert launches((1 << 31) - 1, 1, 1, dt) > 10, (dt, lib.last_error())
+        assert launches(1 << 30, 1, 2, dt) == -1 and "2^31" in lib.last_error()
+        blob = L.emavfi_packed_bytes(3, 64, 3, dt)
+        assert L.emavfi_forward(3, 64, 3, fake, blob, fake, fake, fake, fake, 0, 1, 1, last, dt, None, None) == -3
+        assert L.emavfi_forward(3, 64, 3, fake, blob, fake, fake, fake, fake, 1 << 60, 1, 1, first, dt, None, None) == -1 and why in lib.last_error()
+        # 4K batches: the sizes tests/test_gpu_large.py is about are admitted, and their workspace is counted in 64 bits
+        assert launches(4 if not wide else 2, 2160, 3840, dt) > 10
+        assert L.emavfi_workspace_bytes(3, 64, 3, 2, 2160, 3840, dt) > 1 << 32
+    # the stage queries EQUAL their carve-up arithmetic (emavfi_api.hip op_carve / mdcn_carve, Workspace::take: every buffer starts on
+    # a multiple of 256 bytes), restated exactly at sizes where every large term passes 2^32
+    def carve(parts):
+        used = 0
+        for nbytes in parts:
+            used = (used + nbytes + 255) // 256 * 256
+        return used
+    px = 2 * 4033 * 4160
+    # conv3x3 64 -> 64: channels-last input, packed weights (npass * nchunk * 9 taps * (ck * esize / 32) * nf KiB; ring route 9 * 4 * 2
+    # KiB; fp32x3 three weight sets and [hi | lo] pixels), coutpad = 64 fp32 biases, channels-last output, the 256-byte zero page
+    for dt, pixbytes, wbytes in ((lib.BF16, 128, 9 * 4 * 2 * 1024), (lib.F16, 128, 9 * 4 * 2 * 1024), (lib.F32, 256, 9 * 8 * 2 * 1024), (lib.F32X3, 256, 3 * 9 * 4 * 2 * 1024)):
+        n = L.emavfi_conv3x3_workspace_bytes(2, 64, 64, 4033, 4160, 1, dt)
+        assert n > 1 << 32 and n == carve([px * pixbytes, wbytes, 64 * 4, px * pixbytes, 256]), (dt, n)
+    px = 2 * 2160 * 3840
+    # deform_conv2d 67 -> 67: 80-channel pixels in and out, 32 floats of offsets and masks per pixel, 9 taps * (80 * esize / 32) * 3
+    # fragments KiB of weights, 96 biases
+    for dt, e in ((lib.BF16, 2), (lib.F16, 2), (lib.F32, 4)):
+        n = L.emavfi_deform_conv2d_workspace_bytes(2, 67, 67, 2160, 3840, dt)
+        assert n > 1 << 32 and n == carve([px * 80 * e, px * 128, 9 * (80 * e // 32) * 3 * 1024, 96 * 4, px * 80 * e, 256]), (dt, n)
+    # mdcn at C = 67: the one-block blob, input and output pixels (72 channels in the 16-bit modes, 80 in fp32 and - as 16-bit - under
+    # amp16, which adds two fp32 planes of 80 channels), the offset / mask records, one launch's census (64 slots of 16 bytes)
+    for dt, pixbytes, wide in ((lib.BF16, 144, 0), (lib.F16, 144, 0), (lib.F32, 320, 0), (lib.AMP16, 160, 2)):
+        n = L.emavfi_mdcn_workspace_bytes(2, 67, 2160, 3840, dt, 0)
+        assert n > 1 << 32 and n == carve([L.emavfi_packed_bytes(3, 64, 1, dt), px * pixbytes, px * pixbytes, px * 128] + [px * 320] * wide + [1024]), (dt, n)
+    # stage entries: mdcn, context, reconstruct (no fp32x3 there)
+    params = (ctypes.c_void_p * 8)(*[256] * 8)
+    pp = ctypes.cast(params, ctypes.POINTER(ctypes.c_void_p))
+    for dt in (lib.F32, lib.BF16, lib.F16, lib.AMP16):
+        wide = dt in (lib.F32, lib.AMP16)
+        last, first, why = (PLANE4, PLANE4 + 1, "4 GiB") if wide else (HW24 - 1, HW24, "2^24")
+        assert L.emavfi_mdcn_workspace_bytes(1, 67, 1, last, dt, 0) > 1 << 32
+        assert L.emavfi_mdcn(fake, fake, fake, fake, fake, fake, 1, 67, 1, last, dt, 0, fake, 0, None) == -3, lib.last_error()
+        assert L.emavfi_mdcn(fake, fake, fake, fake, fake, fake, 1, 67, 1, first, dt, 0, fake, 0, None) == -1 and why in lib.last_error()
+        assert L.emavfi_mdcn(fake, fake, fake, fake, fake, fake, (1 << 31) - 1, 67, 1, 1, dt, 0, fake, 0, None) == -3
+        assert L.emavfi_mdcn(fake, fake, fake, fake, fake, fake, 1 << 30, 67, 1, 2, dt, 0, fake, 0, None) == -1 and "2^31" in lib.last_error()
+        for name, query, entry in (("context", L.emavfi_context_workspace_bytes, L.emavfi_context), ("reconstruct", L.emavfi_reconstruct_workspace_bytes, L.emavfi_reconstruct)):
+            assert query(1, 64, 1, last, dt) > 1 << 32, (name, dt, lib.last_error())
+            assert entry(fake, pp, fake, 1, 64, 1, last, dt, fake, 0, None) == -3, (name, dt, lib.last_error())
+            assert query(1, 64, 1, first, dt) == 0 and why in lib.last_error()
+            assert entry(fake, pp, fake, 1, 64, 1, first, dt, fake, 1 << 60, None) == -1 and why in lib.last_error()
+            assert query((1 << 31) - 1, 64, 1, 1, dt) > 1 << 32
+            assert query(1 << 30, 64, 1, 2, dt) == 0 and "2^31" in lib.last_error()
+    # conv3x3: the INPUT plane per dtype, no limit on H*W.  64 input channels are 128 bytes per pixel in the 16-bit types, 256 in fp32.
+    # EMAVFI_F32X3 pixels travel as [hi | lo] f16 halves (256 real bytes), always on the tile kernel, whose addresses are 64-bit: its
+    # plane is counted in halves - 128 bytes -, i.e. the real plane stays below 8 GiB (run at 4.0 GiB + by tests/test_gpu_large.py)
+    conv = lambda n, dt, cin=64, cout=64: L.emavfi_conv3x3(fake, fake, fake, fake, 1, cin, cout, 1, n, 1, 0, dt, fake, 0, None)
+    for dt, pixbytes in ((lib.BF16, 128), (lib.F16, 128), (lib.F32, 256), (lib.F32X3, 128)):
+        last = (1 << 32) // pixbytes - 1
+        assert last >= HW24 - 1 and last * pixbytes == (1 << 32) - pixbytes
+        assert conv(last, dt) == -3, (dt, lib.last_error())
+        assert L.emavfi_conv3x3_workspace_bytes(1, 64, 64, 1, last, 1, dt) > 1 << 32
+        assert conv(last + 1, dt) == -1 and "input plane must be < 4 GiB" in lib.last_error(), (dt, lib.last_error())
+    # only the input plane counts: 6 -> 64 has an output plane four times its input, written with 64-bit addresses (same GPU test)
+    assert conv((1 << 32) // 32 - 1, lib.BF16, 6, 64) == -3 and conv((1 << 32) // 32, lib.BF16, 6, 64) == -1
+    # deform_conv2d: H*W < 2^24 and the input plane (67 -> 80 channels: 160 / 320 bytes per pixel)
+    for dt, last, first, why in ((lib.BF16, HW24 - 1, HW24, "2^24"), (lib.F16, HW24 - 1, HW24, "2^24"), (lib.F32, PLANE4, PLANE4 + 1, "4 GiB")):
+        assert L.emavfi_deform_conv2d_workspace_bytes(1, 67, 67, 1, last, dt) > 1 << 32
+        assert L.emavfi_deform_conv2d(fake, fake, fake, fake, fake, fake, 1, 67, 67, 1, last, dt, fake, 0, None) == -3
+        assert L.emavfi_deform_conv2d_workspace_bytes(1, 67, 67, 1, first, dt) == 0 and why in lib.last_error()
+        assert L.emavfi_deform_conv2d(fake, fake, fake, fake, fake, fake, 1, 67, 67, 1, first, dt, fake, 1 << 60, None) == -1 and why in lib.last_error()
+    # warp: H*W < 2^31.  The entry has no workspace: a misaligned pointer is refused AFTER the size guard, with another message
+    odd = ctypes.c_void_p(260)
+    assert L.emavfi_warp(odd, fake, fake, 1, 3, 1, (1 << 31) - 1, None) == -1 and "16-byte aligned" in lib.last_error()
+    assert L.emavfi_warp(odd, fake, fake, 1, 3, 2, 1 << 30, None) == -1 and "H*W must be < 2^31" in lib.last_error()
+
+
 def test_switch_word_is_latched_and_settable():
     """the launch-sequence switches are read from the environment once; tests flip them through emavfi_debug_switches."""
     L = lib.load()

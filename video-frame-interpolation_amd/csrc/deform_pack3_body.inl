@@ -385,9 +385,11 @@
                 const unsigned d = table[my_slot];
                 const bool live = my_slot < n_ent;
                 const unsigned cpa = (d & 0xffffffu) + (hb && ((d >> 25) & 1u) ? (unsigned)W : 0u), cpb = cpa + ((d >> 24) & 1u);
-                const char *pa = live ? gplane + (size_t)__umul24(cpa, ps_bytes) : zeros, *pb = live ? gplane + (size_t)__umul24(cpb, ps_bytes) : zeros;
-                const char *ta = !live ? zeros : (tplane ? tplane + (size_t)__umul24(cpa, tail_bytes) : pa + 128);
-                const char *tb = !live ? zeros : (tplane ? tplane + (size_t)__umul24(cpb, tail_bytes) : pb + 128);
+                // (HIP declares __umul24 as returning int: widened directly, an offset with bit 31 set - a plane above 2 GiB - would be
+                // sign-extended and the corner fetched from 4 GiB below it; through unsigned it is zero-extended)
+                const char *pa = live ? gplane + (size_t)(unsigned)__umul24(cpa, ps_bytes) : zeros, *pb = live ? gplane + (size_t)(unsigned)__umul24(cpb, ps_bytes) : zeros;
+                const char *ta = !live ? zeros : (tplane ? tplane + (size_t)(unsigned)__umul24(cpa, tail_bytes) : pa + 128);
+                const char *tb = !live ? zeros : (tplane ? tplane + (size_t)(unsigned)__umul24(cpb, tail_bytes) : pb + 128);
                 const unsigned step = live ? 16u : 0u;
                 const unsigned dst0 = lds0 + arena;
 #pragma unroll

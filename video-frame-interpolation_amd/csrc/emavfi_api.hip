@@ -1306,7 +1306,7 @@ int emavfi_warp(const float *frame2, const float *flow, float *out, int B, int C
 {
     if (!frame2 || !flow || !out) return fail(EMAVFI_E_ARG, "warp: null pointer");
     if (B < 1 || C < 1 || H < 1 || W < 1) return fail(EMAVFI_E_ARG, "warp: B, C, H, W must be >= 1");
-    if ((size_t)H * W >= ((size_t)1 << 31)) return fail(EMAVFI_E_ARG, "warp: H*W too large");
+    if ((size_t)H * W >= ((size_t)1 << 31)) return fail(EMAVFI_E_ARG, "warp: H*W must be < 2^31 (32-bit pixel offsets inside a plane)");
     if (!aligned16(frame2) || !aligned16(flow) || !aligned16(out)) return fail(EMAVFI_E_ARG, "warp: pointers must be 16-byte aligned");
     EMAVFI_TRY(launch_warp_nchw(frame2, flow, out, B, C, H, W, (hipStream_t)stream), "warp");
     return EMAVFI_OK;
