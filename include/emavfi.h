@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -629,6 +629,58 @@ int emavfi_frame_diff_cells(const unsigned char *a, size_t a_pitch, size_t a_bat
                             size_t b_batch_stride, int n, int H, int W, int C, int order, int sample_bytes, int depth, int shift,
                             unsigned *cells, void *stream);
 int emavfi_duplicate_flags(const unsigned *cells, size_t stride_words, int n, unsigned threshold, unsigned *flags, unsigned *scores, void *stream);
+
+/* Static regions.  Channel logos, subtitles, scoreboards, game HUDs, letterbox bars and the unchanged background of screen captures and
+ * animation are bit-identical, or nearly so, in both frames of a pair, yet the forward pushes them through a flow warp and three deformable
+ * convolutions, and whatever the model does next to a moving object leaks into pixels whose true midpoint is known exactly: the pixel itself.
+ * The reference has no guard for this (inference.py:173-188 writes the prediction as it comes); this is an addition, off unless asked for.
+ *
+ * STATIC REGION DEFINITION (the one place).  This is the project's own definition: it claims agreement with no outside tool.  All arithmetic is
+ * integer: host, oracle and device agree bit for bit.
+ *   Frame layouts.  A frame is dense, with no pitch, as the harness emits it; sample_bytes is 1 or 2.
+ *     EMAVFI_LAYOUT_INTERLEAVED: [H][W][C] samples, C in 1..4.
+ *     EMAVFI_LAYOUT_NV12: [H][W] Y samples, then [H/2][W/2] pairs {U, V}.
+ *     EMAVFI_LAYOUT_I420: the Y plane, then the U plane [H/2][W/2], then the V plane [H/2][W/2].
+ *     The two 4:2:0 layouts need an even H and W.
+ *   Sample.  A byte, or (word >> shift) & (2^depth - 1) of a 16-bit little-endian word: depth 10, 12 or 16 and shift 0 .. 16 - depth, the
+ *     triple emavfi_resample_frames / emavfi_frame_diff_cells take (sample_bytes 1: depth 8, shift 0).
+ *   same(y, x) of two frames a, b with `tol` in sample units.  Interleaved: every one of the C samples of the pixel has |sa - sb| <= tol.
+ *     4:2:0: the Y sample at (y, x) is within tol, and the U and the V sample at (y >> 1, x >> 1) are within tol.
+ *   core(y, x) for a radius r in 0..EMAVFI_STATIC_MAX_RADIUS: same(y', x') holds for every y' in [max(0, y - r), min(H - 1, y + r)] and every
+ *     x' in [max(0, x - r), min(W - 1, x + r)].  The window is clipped to the frame: the frame edge never erodes, so letterbox bars survive.
+ *   Applied to a destination frame d (a post-processed prediction for the pair (a, b)).  Interleaved: at every core pixel the C samples of d
+ *     become a's.  4:2:0, luma: the Y sample of d becomes a's at every core pixel.  4:2:0, chroma: the chroma sample (i, j), U and V alike,
+ *     becomes a's exactly when all four luma pixels (2 i + {0, 1}, 2 j + {0, 1}) are core.  A replaced 16-bit sample receives a's WHOLE word
+ *     (the bits outside the sample included).  Every other byte of d is left as it was, and d is never read.
+ *   Consequences: r = 0 gives core == same; a == b makes d a copy of a; one differing sample in otherwise equal frames leaves a hole of
+ *     (2 r + 1)^2 pixels clipped at the frame; core is monotone: it shrinks as r grows and grows with tol.
+ *
+ * emavfi_static_guard_frames applies the definition to n_dst destination frames at dst + k dst_stride; entry k of `table`, a HOST pointer to
+ *   n_dst entries {a, b}, names the two frames of `srcs` (n_srcs dense frames, src_stride bytes apart) that frame k is guarded against.  The
+ *   table is read and validated before the call returns and nothing of it is retained: it travels as kernel arguments,
+ *   EMAVFI_RESAMPLE_LAUNCH_CAP = 64 entries per launch.  counts (device memory, n_dst u32; may be NULL): counts[k] = the number of core
+ *   pixels of entry k.  EVERY one of the n_dst words is defined on exit whatever the buffer held before: a launch ahead of the guard clears
+ *   them on `stream` and the workgroups add their tiles' integer sums - the order does not matter.  C is ignored, but still validated (it
+ *   must be 1), at a 4:2:0 layout, as `order` is where C = 1 elsewhere.
+ * EMAVFI_E_ARG (never an abort), the message naming the argument: a null dst, srcs or table; n_dst or n_srcs below 1; H or W outside 1..16384,
+ *   or odd at a 4:2:0 layout; an unknown layout; C outside 1..4, or other than 1 at a 4:2:0 layout; sample_bytes, depth or shift outside the
+ *   above; a radius outside 0..16; a tol above 2^depth - 1; a stride below the frame's bytes, or odd at sample_bytes 2; a dst / srcs pointer
+ *   that is not 2-byte aligned at sample_bytes 2, a counts pointer that is not 4-byte aligned; size arithmetic that overflows size_t; dst
+ *   overlapping srcs; an entry index outside srcs.
+ * The frame pointers are device pointers or pinned (device-mapped) host memory.  Nothing is allocated, nothing synchronises, there is no
+ *   workspace, all work goes on `stream`.  A workgroup owns a tile of 64 x 128 pixels of one destination frame, reads a and b there plus an
+ *   r-wide halo, clipped to the frame - no byte beyond a frame is read -, erodes in LDS, rows then columns, and stores a's samples (read a
+ *   second time, from cache) at the replaced positions.  Access width: 16-byte loads and stores where the three frame addresses of the entry,
+ *   every plane's offset and every plane's row bytes are multiples of 16, else bytes / words throughout; both forms run the same per-element
+ *   functions (csrc/static_elem.h).  The kernel is short-lived and waits on nothing. */
+#define EMAVFI_LAYOUT_INTERLEAVED 0
+#define EMAVFI_LAYOUT_NV12 1
+#define EMAVFI_LAYOUT_I420 2
+#define EMAVFI_STATIC_MAX_RADIUS 16
+typedef struct { unsigned a, b; } emavfi_static_entry;   /* indices into srcs */
+int emavfi_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst, const unsigned char *srcs, size_t src_stride, int n_srcs,
+                               const emavfi_static_entry *table, int H, int W, int layout, int C, int sample_bytes, int depth, int shift,
+                               int radius, unsigned tol, unsigned *counts, void *stream);
 
 /* Frame metrics on the device: how close is image a (an interpolated frame) to image b (the held-out true frame)?  The reference has no
  * evaluation script (its README names PSNR and SSIM against held-out ground-truth frames as the way to judge a model and calls an eval.py a

@@ -6,6 +6,7 @@
 #include "misc_kernels.h"
 #include "resample_elem.h"
 #include "dedup_elem.h"
+#include "static_elem.h"
 #include "conv_first.inl"
 
 #include <atomic>
@@ -1783,6 +1784,68 @@ int emavfi_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, con
     }
     EMAVFI_TRY(launch_resample_frames(dst, dst_stride, n_out, srcs, src_stride, nodes, node_stride, reinterpret_cast<const ResampleEntry *>(table),
                                       flags, frame_bytes, sample_bytes, depth, shift, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+// ---- static regions (include/emavfi.h, "STATIC REGION DEFINITION"): every check runs on the host, the table is read here and not kept
+static_assert(sizeof(emavfi_static_entry) == sizeof(StaticEntry) && EMAVFI_RESAMPLE_LAUNCH_CAP == STATIC_CAP &&
+              EMAVFI_STATIC_MAX_RADIUS == STATIC_MAX_RADIUS && EMAVFI_LAYOUT_INTERLEAVED == STATIC_LAYOUT_INTERLEAVED &&
+              EMAVFI_LAYOUT_NV12 == STATIC_LAYOUT_NV12 && EMAVFI_LAYOUT_I420 == STATIC_LAYOUT_I420, "header, misc_kernels.h and static_elem.h disagree");
+
+int emavfi_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst, const unsigned char *srcs, size_t src_stride, int n_srcs,
+                               const emavfi_static_entry *table, int H, int W, int layout, int C, int sample_bytes, int depth, int shift,
+                               int radius, unsigned tol, unsigned *counts, void *stream)
+{
+    const char *const what = "static_guard_frames";
+    if (n_dst < 1) return fail(EMAVFI_E_ARG, "%s: n_dst must be >= 1", what);
+    if (n_srcs < 1) return fail(EMAVFI_E_ARG, "%s: n_srcs must be >= 1", what);
+    if (const int rc = scene_dims_check(what, H, W); rc != EMAVFI_OK) return rc;
+    if (layout != EMAVFI_LAYOUT_INTERLEAVED && layout != EMAVFI_LAYOUT_NV12 && layout != EMAVFI_LAYOUT_I420)
+        return fail(EMAVFI_E_ARG, "%s: unknown layout %d (EMAVFI_LAYOUT_INTERLEAVED, EMAVFI_LAYOUT_NV12 or EMAVFI_LAYOUT_I420)", what, layout);
+    if (layout != EMAVFI_LAYOUT_INTERLEAVED && ((H | W) & 1))
+        return fail(EMAVFI_E_ARG, "%s: H = %d, W = %d: a 4:2:0 layout needs an even H and W", what, H, W);
+    if (C < 1 || C > 4) return fail(EMAVFI_E_ARG, "%s: C = %d (C must be 1..4)", what, C);
+    if (layout != EMAVFI_LAYOUT_INTERLEAVED && C != 1) return fail(EMAVFI_E_ARG, "%s: C = %d at a 4:2:0 layout (C must be 1 there)", what, C);
+    if (sample_bytes != 1 && sample_bytes != 2) return fail(EMAVFI_E_ARG, "%s: sample_bytes = %d (sample_bytes must be 1 or 2)", what, sample_bytes);
+    if (sample_bytes == 1 ? depth != 8 : (depth != 10 && depth != 12 && depth != 16))
+        return fail(EMAVFI_E_ARG, "%s: depth = %d (depth must be 8 at sample_bytes 1 and 10, 12 or 16 at sample_bytes 2)", what, depth);
+    if (shift < 0 || shift > 8 * sample_bytes - depth)
+        return fail(EMAVFI_E_ARG, "%s: shift = %d (shift must lie in 0..%d at depth %d)", what, shift, 8 * sample_bytes - depth, depth);
+    if (radius < 0 || radius > EMAVFI_STATIC_MAX_RADIUS)
+        return fail(EMAVFI_E_ARG, "%s: radius = %d (radius must lie in 0..%d)", what, radius, EMAVFI_STATIC_MAX_RADIUS);
+    if (tol > (1u << depth) - 1u) return fail(EMAVFI_E_ARG, "%s: tol = %u is above 2^depth - 1 = %u", what, tol, (1u << depth) - 1u);
+    StaticPlane planes[3];
+    size_t frame_bytes;                                   // at most 16384^2 * 4 * 2 = 2^31
+    static_planes(layout, C, H, W, sample_bytes, planes, &frame_bytes);
+    const size_t odd = sample_bytes == 2 ? 1 : 0;
+    const struct { const char *name; size_t stride; int n; } pools[2] = {{"dst_stride", dst_stride, n_dst}, {"src_stride", src_stride, n_srcs}};
+    size_t span[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+        if (pools[k].stride < frame_bytes)
+            return fail(EMAVFI_E_ARG, "%s: %s %zu is smaller than the frame's %zu bytes", what, pools[k].name, pools[k].stride, frame_bytes);
+        if (pools[k].stride & odd) return fail(EMAVFI_E_ARG, "%s: %s %zu is odd at sample_bytes 2", what, pools[k].name, pools[k].stride);
+        if (!resample_span(pools[k].n, pools[k].stride, frame_bytes, &span[k]))
+            return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (%s %zu)", what, pools[k].name, pools[k].stride);
+    }
+    size_t count_bytes;
+    if (__builtin_mul_overflow((size_t)n_dst, sizeof(unsigned), &count_bytes)) return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (n_dst)", what);
+    if (!dst) return fail(EMAVFI_E_ARG, "%s: null pointer dst", what);
+    if (!srcs) return fail(EMAVFI_E_ARG, "%s: null pointer srcs", what);
+    if (!table) return fail(EMAVFI_E_ARG, "%s: null pointer table", what);
+    if (((uintptr_t)dst | (uintptr_t)srcs) & odd)
+        return fail(EMAVFI_E_ARG, "%s: the frame pointers dst, srcs must be 2-byte aligned at sample_bytes 2", what);
+    if ((uintptr_t)counts & 3) return fail(EMAVFI_E_ARG, "%s: the u32 pointer counts must be 4-byte aligned", what);
+    const uintptr_t d0 = (uintptr_t)dst, s0 = (uintptr_t)srcs;
+    if (d0 + span[0] < d0 || s0 + span[1] < s0) return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (a pool wraps the address space)", what);
+    if (d0 < s0 + span[1] && s0 < d0 + span[0]) return fail(EMAVFI_E_ARG, "%s: dst overlaps srcs", what);
+    for (int k = 0; k < n_dst; ++k) {
+        if (table[k].a >= (unsigned)n_srcs)
+            return fail(EMAVFI_E_ARG, "%s: table[%d].a = %u is outside srcs (%d frames)", what, k, table[k].a, n_srcs);
+        if (table[k].b >= (unsigned)n_srcs)
+            return fail(EMAVFI_E_ARG, "%s: table[%d].b = %u is outside srcs (%d frames)", what, k, table[k].b, n_srcs);
+    }
+    EMAVFI_TRY(launch_static_guard_frames(dst, dst_stride, n_dst, srcs, src_stride, reinterpret_cast<const StaticEntry *>(table), H, W, layout, C,
+                                          sample_bytes, depth, shift, radius, tol, counts, (hipStream_t)stream), what);
     return EMAVFI_OK;
 }
 

@@ -123,6 +123,12 @@ struct ResampleEntry { unsigned a, b, w, f, h; };   // emavfi_resample_entry
 int launch_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride,
                            const unsigned char *nodes, size_t node_stride, const ResampleEntry *table, const unsigned *flags, size_t frame_bytes,
                            int sample_bytes, int depth, int shift, hipStream_t s);
+// static regions held on the device (include/emavfi.h, "STATIC REGION DEFINITION"): arguments already validated; `table` is a HOST pointer, read
+// before the call returns and passed on as kernel arguments, STATIC_CAP (static_elem.h) entries per launch; `counts` may be null
+struct StaticEntry { unsigned a, b; };   // emavfi_static_entry
+int launch_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst, const unsigned char *srcs, size_t src_stride,
+                               const StaticEntry *table, int H, int W, int layout, int C, int sample_bytes, int depth, int shift, int radius,
+                               unsigned tol, unsigned *counts, hipStream_t s);
 // frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION"): arguments already validated; `part` holds 2 u64 per (b, c, tile)
 // of frame_metrics_tiles' tx * ty tiles (32 x 32 windows each; one tile where an axis has no window)
 void frame_metrics_tiles(int H, int W, int *tx, int *ty);

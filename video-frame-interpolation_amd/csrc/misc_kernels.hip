@@ -5,6 +5,7 @@
 #include "scene_elem.h"
 #include "resample_elem.h"
 #include "dedup_elem.h"
+#include "static_elem.h"
 #include "metrics_elem.h"
 #include "p010_elem.h"
 #include "yuv420p_elem.h"
@@ -2575,6 +2576,245 @@ int launch_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, con
         p.dst = dst + (size_t)first * dst_stride;
         for (int k = 0; k < n; ++k) p.e[k] = table[first + k];
         resample_frames_kernel<<<dim3(pieces, (unsigned)n), 256, 0, s>>>(p);
+        if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Static regions held on the device (include/emavfi.h, "STATIC REGION DEFINITION"; per-element functions: static_elem.h).
+//   static_guard_kernel   grid (tiles along x, tiles along y, entries of this launch), 256 threads.  The table travels as kernel arguments,
+//                         at most STATIC_CAP entries per launch.  A workgroup owns a tile of ST_TH x ST_TW = 64 x 128 luma pixels of ONE
+//                         destination frame.  Chosen against 160 KiB of LDS per CU and wave64: the `bad` map of the tile plus its halo is
+//                         one byte per pixel, (64 + 32) rows x (128 + 32 + 4) bytes = 15.4 KiB (the row stride of 41 dwords lets the 64 lanes
+//                         of a wave, one row each, hit 64 different banks), the row-eroded map (64 + 32) x (128 + 4) = 12.4 KiB: 27.8 KiB,
+//                         5 workgroups = 20 waves per CU.  At r = 16 the tile plus halo is 96 x 160 pixels, 1.875 x the tile, so with d's
+//                         stores the traffic is at most (2 * 1.875 + 1) / 3 = 1.58 x what the definition obliges; at r = 4 1.13 x.
+//                         Stages: (1) `bad` = 0; (2) every plane's samples of a and b inside the tile plus halo, CLIPPED to the frame, are
+//                         compared and a differing sample marks its pixel - a 4:2:0 chroma sample the (up to four) luma pixels it covers, so
+//                         the chroma comparison is folded in at luma resolution; positions outside the frame stay 0, which is the clipped
+//                         window; (3) erosion along rows, then along columns, each by a running count over the 2 r + 1 window (a lane walks 32
+//                         outputs: 2 r + 1 + 64 LDS reads, not 32 (2 r + 1)); the column pass leaves the `core` map of the tile in the `bad`
+//                         buffer and counts the tile's core pixels, one atomic add per wave into counts[k] (cleared by a launch of its own
+//                         ahead: an integer sum, the order does not matter); (4) a's samples are stored at the replaced positions of d.
+//                         a's tile is read a second time here, right after stage (2) read it (keeping it in LDS would cost up to 64 KiB);
+//                         d is never read, so a 16-byte unit is stored whole only when every sample of it is replaced, else sample by sample.
+//                         Access width: 16-byte loads and stores when the three frame addresses of the entry, every plane's offset and
+//                         every plane's row bytes are multiples of 16 (a tile's samples are then whole units; a halo unit may reach past
+//                         the halo but never past its row); else bytes / words throughout.  Both forms run the same per-element functions.
+//                         No byte beyond a frame is read.  Short-lived, waits on nothing.
+// ------------------------------------------------------------------------------------------
+constexpr int ST_TH = 64, ST_TW = 128;
+constexpr int ST_RH = ST_TH + 2 * STATIC_MAX_RADIUS;            // rows of the tile plus halo
+constexpr int ST_BS = ST_TW + 2 * STATIC_MAX_RADIUS + 4;        // row stride of `bad`: 164 bytes = 41 dwords
+constexpr int ST_ES = ST_TW + 4;                                // row stride of the row-eroded map: 33 dwords
+static_assert(ST_TH % 32 == 0 && ST_TW == 128 && (ST_TH & 1) == 0, "the passes below walk 32 outputs per lane, 128 columns per 2 x 128 threads");
+
+struct StaticArgs {
+    unsigned char *dst;              // the first destination frame of THIS launch
+    size_t dst_stride;
+    const unsigned char *srcs;
+    size_t src_stride;
+    unsigned *counts;                // the first count of THIS launch, or null
+    StaticPlane plane[3];
+    int n_planes, H, W, sb, shift, radius, wide;
+    unsigned mask, tol;
+    unsigned a[STATIC_CAP], b[STATIC_CAP];
+};
+static_assert(sizeof(StaticArgs) <= 2048, "the table must fit the kernel argument segment");
+
+__global__ __launch_bounds__(256) void static_counts_clear_kernel(unsigned *__restrict__ counts, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) counts[i] = 0u;
+}
+
+// sample k of a 16-byte unit held as four little-endian dwords
+template <int SB>
+__device__ __forceinline__ unsigned static_unit_sample(const uint4 &v, int k)
+{
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+    if constexpr (SB == 1) return (w[k >> 2] >> (8 * (k & 3))) & 0xffu;
+    else return (w[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+}
+
+template <int SB>
+__global__ __launch_bounds__(256) void static_guard_kernel(StaticArgs p)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char bad[ST_RH * ST_BS];      // stage (3) on: core [ST_TH][ST_TW]
+    __shared__ __attribute__((aligned(16))) unsigned char rowbad[ST_RH * ST_ES];
+    constexpr int NS = 16 / SB;                                  // samples of a 16-byte unit
+    const int tid = threadIdx.x, r = p.radius;
+    const unsigned e = blockIdx.z;
+    const int tx0 = blockIdx.x * ST_TW, ty0 = blockIdx.y * ST_TH;
+    const int tx1 = min(tx0 + ST_TW, p.W), ty1 = min(ty0 + ST_TH, p.H);           // the tile, clipped: [ty0, ty1) x [tx0, tx1)
+    const int X0 = static_window_lo(tx0, r), X1 = static_window_hi(tx1 - 1, r, p.W) + 1;
+    const int Y0 = static_window_lo(ty0, r), Y1 = static_window_hi(ty1 - 1, r, p.H) + 1;   // the tile plus halo, clipped to the frame
+    const int ox = tx0 - r, oy = ty0 - r, RW = ST_TW + 2 * r, RH = ST_TH + 2 * r;  // the LDS map: RH x RW pixels from (oy, ox)
+    const unsigned char *fa = p.srcs + (size_t)p.a[e] * p.src_stride, *fb = p.srcs + (size_t)p.b[e] * p.src_stride;
+    unsigned char *fd = p.dst + (size_t)e * p.dst_stride;
+    const bool wide = p.wide && ((((uintptr_t)fa | (uintptr_t)fb | (uintptr_t)fd) & 15) == 0);
+
+    for (int i = tid; i < ST_RH * ST_BS / 4; i += 256) reinterpret_cast<unsigned *>(bad)[i] = 0u;
+    __syncthreads();
+
+    // (2) a differing sample marks the luma pixel(s) it belongs to
+    const auto mark1 = [&](int y, int x) {
+        const int ly = y - oy, lx = x - ox;
+        if (ly >= 0 && ly < RH && lx >= 0 && lx < RW) bad[ly * ST_BS + lx] = 1;
+    };
+    const auto mark = [&](int row, int px, int sub) {
+        if (!sub) mark1(row, px);
+        else { mark1(2 * row, 2 * px); mark1(2 * row, 2 * px + 1); mark1(2 * row + 1, 2 * px); mark1(2 * row + 1, 2 * px + 1); }
+    };
+    const auto differ = [&](unsigned wa, unsigned wb) {
+        return !static_within(static_sample(wa, p.mask, p.shift), static_sample(wb, p.mask, p.shift), p.tol);
+    };
+    for (int q = 0; q < p.n_planes; ++q) {
+        const StaticPlane pl = p.plane[q];
+        const int row0 = Y0 >> pl.sub, nrows = ((Y1 - 1) >> pl.sub) + 1 - row0;
+        const int s0 = (X0 >> pl.sub) * pl.div, s1 = (((X1 - 1) >> pl.sub) + 1) * pl.div;   // the samples of a row: s1 <= pl.samples
+        const size_t rb = (size_t)pl.samples * SB;
+        if (wide) {
+            const int b0 = (s0 * SB) & ~15, b1 = (s1 * SB + 15) & ~15;                      // rb is a multiple of 16: b1 <= rb
+            const int nu = (b1 - b0) >> 4, items = nrows * nu;
+            for (int t = tid; t < items; t += 256) {
+                const int rr = t / nu, u = t - rr * nu, row = row0 + rr;
+                const size_t off = pl.offset + (size_t)row * rb + (size_t)(b0 + 16 * u);
+                const uint4 va = *reinterpret_cast<const uint4 *>(fa + off), vb = *reinterpret_cast<const uint4 *>(fb + off);
+                const int s = (b0 + 16 * u) / SB;
+                int px = s / pl.div, rem = s - px * pl.div;
+#pragma unroll
+                for (int k = 0; k < NS; ++k) {
+                    if (differ(static_unit_sample<SB>(va, k), static_unit_sample<SB>(vb, k))) mark(row, px, pl.sub);
+                    if (++rem == pl.div) { rem = 0; ++px; }
+                }
+            }
+        } else {
+            const int ns = s1 - s0, items = nrows * ns;
+            for (int t = tid; t < items; t += 256) {
+                const int rr = t / ns, s = s0 + (t - rr * ns), row = row0 + rr;
+                const size_t off = pl.offset + (size_t)row * rb + (size_t)s * SB;
+                unsigned wa, wb;
+                if constexpr (SB == 1) { wa = fa[off]; wb = fb[off]; }
+                else { wa = *reinterpret_cast<const unsigned short *>(fa + off); wb = *reinterpret_cast<const unsigned short *>(fb + off); }
+                if (differ(wa, wb)) mark(row, s / pl.div, pl.sub);
+            }
+        }
+    }
+    __syncthreads();
+
+    // (3) rows: lane = (row, 32 columns); a running count over the 2 r + 1 window
+    for (int t = tid; t < 4 * RH; t += 256) {
+        const int row = t % RH, seg = t / RH;
+        const unsigned char *br = bad + row * ST_BS + seg * 32;
+        unsigned char *er = rowbad + row * ST_ES + seg * 32;
+        int cnt = 0;
+        for (int k = 0; k <= 2 * r; ++k) cnt += br[k];
+        for (int x = 0; x < 32; ++x) {
+            er[x] = cnt ? 1 : 0;
+            if (x < 31) cnt += (int)br[x + 2 * r + 1] - (int)br[x];      // at most column 96 + 30 + 33 = 159 of RW = 128 + 2 r
+        }
+    }
+    __syncthreads();
+    // columns: lane = (column, 32 rows); the core map replaces `bad`, which the row pass has finished reading
+    unsigned char *const core = bad;
+    {
+        const int x = tid & (ST_TW - 1);
+        unsigned n = 0u;
+        for (int seg = tid >> 7; seg < ST_TH / 32; seg += 2) {
+            const unsigned char *cr = rowbad + seg * 32 * ST_ES + x;
+            int cnt = 0;
+            for (int k = 0; k <= 2 * r; ++k) cnt += cr[k * ST_ES];
+            for (int y = 0; y < 32; ++y) {
+                const int yy = seg * 32 + y;
+                const bool c = cnt == 0;
+                core[yy * ST_TW + x] = c ? 1 : 0;
+                n += (c && tx0 + x < tx1 && ty0 + yy < ty1) ? 1u : 0u;
+                if (y < 31) cnt += (int)cr[(y + 2 * r + 1) * ST_ES] - (int)cr[y * ST_ES];   // at most row 32 + 30 + 33 = 95 of RH = 64 + 2 r
+            }
+        }
+        if (p.counts) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) n += __shfl_xor(n, off, 64);
+            if ((tid & 63) == 0 && n) atomicAdd(p.counts + e, n);
+        }
+    }
+    __syncthreads();
+
+    // (4) a's samples at the replaced positions of d
+    const auto core_at = [&](int y, int x) { return core[(y - ty0) * ST_TW + (x - tx0)] != 0; };
+    const auto replaced = [&](int row, int px, int sub) {
+        if (!sub) return core_at(row, px);
+        return static_chroma_core(core_at(2 * row, 2 * px), core_at(2 * row, 2 * px + 1), core_at(2 * row + 1, 2 * px), core_at(2 * row + 1, 2 * px + 1));
+    };
+    for (int q = 0; q < p.n_planes; ++q) {
+        const StaticPlane pl = p.plane[q];
+        const int row0 = ty0 >> pl.sub, nrows = (ty1 >> pl.sub) - row0;                     // 4:2:0: ty0, ty1 even
+        const int s0 = (tx0 >> pl.sub) * pl.div, s1 = (tx1 >> pl.sub) * pl.div;
+        const size_t rb = (size_t)pl.samples * SB;
+        if (wide) {
+            const int nu = ((s1 - s0) * SB) >> 4, items = nrows * nu;                       // whole units: s0 SB and s1 SB are multiples of 16
+            for (int t = tid; t < items; t += 256) {
+                const int rr = t / nu, u = t - rr * nu, row = row0 + rr;
+                const int s = s0 + u * NS;
+                int px = s / pl.div, rem = s - px * pl.div;
+                unsigned flags = 0u;
+#pragma unroll
+                for (int k = 0; k < NS; ++k) {
+                    flags |= (replaced(row, px, pl.sub) ? 1u : 0u) << k;
+                    if (++rem == pl.div) { rem = 0; ++px; }
+                }
+                if (!flags) continue;
+                const size_t off = pl.offset + (size_t)row * rb + (size_t)s * SB;
+                const uint4 va = *reinterpret_cast<const uint4 *>(fa + off);
+                if (flags == (1u << NS) - 1u) {
+                    *reinterpret_cast<uint4 *>(fd + off) = va;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < NS; ++k)
+                        if (flags >> k & 1u) {
+                            if constexpr (SB == 1) fd[off + k] = (unsigned char)static_unit_sample<SB>(va, k);
+                            else *reinterpret_cast<unsigned short *>(fd + off + 2 * k) = (unsigned short)static_unit_sample<SB>(va, k);
+                        }
+                }
+            }
+        } else {
+            const int ns = s1 - s0, items = nrows * ns;
+            for (int t = tid; t < items; t += 256) {
+                const int rr = t / ns, s = s0 + (t - rr * ns), row = row0 + rr;
+                if (!replaced(row, s / pl.div, pl.sub)) continue;
+                const size_t off = pl.offset + (size_t)row * rb + (size_t)s * SB;
+                if constexpr (SB == 1) fd[off] = fa[off];
+                else *reinterpret_cast<unsigned short *>(fd + off) = *reinterpret_cast<const unsigned short *>(fa + off);
+            }
+        }
+    }
+}
+
+int launch_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst, const unsigned char *srcs, size_t src_stride,
+                               const StaticEntry *table, int H, int W, int layout, int C, int sample_bytes, int depth, int shift, int radius,
+                               unsigned tol, unsigned *counts, hipStream_t s)
+{
+    StaticArgs p{};
+    size_t frame_bytes;
+    p.n_planes = static_planes(layout, C, H, W, sample_bytes, p.plane, &frame_bytes);
+    p.dst_stride = dst_stride; p.srcs = srcs; p.src_stride = src_stride;
+    p.H = H; p.W = W; p.sb = sample_bytes; p.shift = shift; p.radius = radius; p.mask = (1u << depth) - 1u; p.tol = tol;
+    p.wide = 1;
+    for (int q = 0; q < p.n_planes; ++q) p.wide = p.wide && mult_of(16, {p.plane[q].offset, (size_t)p.plane[q].samples * sample_bytes});
+    if (counts) {
+        static_counts_clear_kernel<<<dim3((unsigned)((n_dst + 255) / 256)), 256, 0, s>>>(counts, n_dst);
+        if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
+    }
+    const dim3 tiles((unsigned)((W + ST_TW - 1) / ST_TW), (unsigned)((H + ST_TH - 1) / ST_TH));
+    for (int first = 0; first < n_dst; first += STATIC_CAP) {
+        const int n = n_dst - first < STATIC_CAP ? n_dst - first : STATIC_CAP;
+        p.dst = dst + (size_t)first * dst_stride;
+        p.counts = counts ? counts + first : nullptr;
+        for (int k = 0; k < n; ++k) { p.a[k] = table[first + k].a; p.b[k] = table[first + k].b; }
+        if (sample_bytes == 1) static_guard_kernel<1><<<dim3(tiles.x, tiles.y, (unsigned)n), 256, 0, s>>>(p);
+        else static_guard_kernel<2><<<dim3(tiles.x, tiles.y, (unsigned)n), 256, 0, s>>>(p);
         if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
     }
     return 0;

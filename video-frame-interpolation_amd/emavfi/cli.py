@@ -65,6 +65,11 @@ def parser() -> argparse.ArgumentParser:
     g.add_argument("--scale", type=float, default=None, help="resize every frame on the device (default: no resize; the reference: 0.5)")
     g.add_argument("--size", type=_size, default=None, metavar="HxW", help="resize every frame on the device to H x W")
     p.add_argument("--scene-threshold", type=float, default=None, help="hold the earlier frame across cuts (8-bit streams)")
+    p.add_argument("--static-guard", type=int, default=None, metavar="R",
+                   help="hold static regions (overlays, subtitles, letterbox bars): a pixel whose window of radius R (0..16) is the same in both "
+                        "source frames keeps the earlier frame's samples (no default is claimed); excludes --reference-quirks")
+    p.add_argument("--static-tolerance", type=float, default=None, metavar="FRACTION",
+                   help="with --static-guard: samples that differ by at most FRACTION of full scale count as the same (default 0: bit-equal only)")
     p.add_argument("--batch-pairs", type=int, default=8)
     p.add_argument("--chunk-pairs", type=int, default=64, help="frame pairs per chunk: at most chunk_pairs * frame_interval + 1 source frames are held")
     p.add_argument("--yuv-standard", default="bt601", help="bt601, bt709 or (10 / 12 / 16-bit streams) bt2020")
@@ -92,6 +97,15 @@ def _run(args) -> int:
         for given, name in ((args.dedup is not None, "--dedup"), (args.dedup_max_run is not None, "--dedup-max-run")):
             if given:
                 raise ValueError(f"{name} needs --output-fps: dropped frames are replaced on the resampler's time grid")
+    if args.static_tolerance is not None and args.static_guard is None:
+        raise ValueError("--static-tolerance needs --static-guard R")
+    if args.static_guard is not None and args.reference_quirks:
+        raise ValueError("--static-guard excludes --reference-quirks: exact source pixels pasted into the quirk's de-normalised prediction would "
+                         "show as patches")
+    if args.static_guard is not None and not 0 <= args.static_guard <= 16:
+        raise ValueError("--static-guard R: the radius must lie in 0..16")
+    if args.static_tolerance is not None and not 0.0 <= args.static_tolerance <= 1.0:
+        raise ValueError("--static-tolerance FRACTION: a fraction of full scale in 0..1")
     if args.dedup_max_run is not None and args.dedup is None:
         raise ValueError("--dedup-max-run needs --dedup FRACTION")
     mode = "resample" if resample else (args.mode or "reference")
@@ -123,7 +137,9 @@ def _run(args) -> int:
                                **(dict(rate_in=head.rate, rate_out=args.output_fps, resample_depth=args.resample_depth,
                                        resample_method=args.resample) if resample else {}),
                                **(dict(dedup_threshold=args.dedup, dedup_max_run=3 if args.dedup_max_run is None else args.dedup_max_run)
-                                  if args.dedup is not None else {}))
+                                  if args.dedup is not None else {}),
+                               **(dict(static_guard=args.static_guard, static_tolerance=args.static_tolerance or 0.0)
+                                  if args.static_guard is not None else {}))
         if args.evaluate:
             print(fi.evaluate(list(reader), every=args.every))      # evaluate() indexes the clip: all of it is held
             return 0
@@ -137,7 +153,9 @@ def _run(args) -> int:
             print(f"{reader.frames_read} frames in, {writer.frames_written} frames out at {out_head.fps_num}:{out_head.fps_den} fps "
                   f"({out_head.width} x {out_head.height}, {head.pixel_format}, "
                   + (f"{args.resample} at depth {args.resample_depth})" if resample else f"factor {factor})")
-                  + (f", {len(fi.duplicates)} duplicate frames dropped" if args.dedup is not None else ""), file=sys.stderr)
+                  + (f", {len(fi.duplicates)} duplicate frames dropped" if args.dedup is not None else "")
+                  + (f", static guard held {100.0 * sum(fi.static_share) / max(len(fi.static_share), 1):.2f} % of the predictions' pixels on average"
+                     if args.static_guard is not None else ""), file=sys.stderr)
     return 0
 
 

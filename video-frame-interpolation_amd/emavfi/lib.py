@@ -68,6 +68,8 @@ _PROTOTYPES = {
                                        c_size_t, c_int, c_int, c_int, c_void_p]),
     "emavfi_frame_diff_cells": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 8 + [c_void_p, c_void_p]),
     "emavfi_duplicate_flags": (c_int, [c_void_p, c_size_t, c_int, ctypes.c_uint, c_void_p, c_void_p, c_void_p]),
+    "emavfi_static_guard_frames": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p] + [c_int] * 8
+                                   + [ctypes.c_uint, c_void_p, c_void_p]),
     "emavfi_frame_metrics_workspace_bytes": (c_size_t, [c_int] * 4),
     "emavfi_frame_metrics_u8": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 4
                                 + [c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -1217,6 +1219,74 @@ def duplicate_flags(cells, threshold, flags=None, scores=None, with_scores=True)
         check(load().emavfi_duplicate_flags(cells.data_ptr(), cells.stride(0) if n > 1 else SCENE_SIG_WORDS, n, threshold, flags.data_ptr(),
                                             scores.data_ptr() if scores is not None else None, _stream()), "emavfi_duplicate_flags")
     return flags, scores
+
+
+# ---------------------------------------------------------------- static regions (include/emavfi.h, "STATIC REGION DEFINITION")
+LAYOUT_INTERLEAVED, LAYOUT_NV12, LAYOUT_I420 = 0, 1, 2   # EMAVFI_LAYOUT_*
+LAYOUTS = {"interleaved": LAYOUT_INTERLEAVED, "nv12": LAYOUT_NV12, "i420": LAYOUT_I420}
+STATIC_MAX_RADIUS = 16                                   # EMAVFI_STATIC_MAX_RADIUS
+
+
+class StaticEntry(ctypes.Structure):
+    """emavfi_static_entry"""
+    _fields_ = [("a", ctypes.c_uint), ("b", ctypes.c_uint)]
+
+
+def static_tolerance_units(fraction, depth=8) -> int:
+    """The `tol` of static_guard_frames for "two samples that differ by at most `fraction` of full scale count as the same":
+    floor(fraction * (2^depth - 1)); depth 8 for byte frames.  0 accepts bit-equal samples only."""
+    import math
+    if isinstance(fraction, bool) or not isinstance(fraction, (int, float)) or not 0.0 <= fraction <= 1.0:
+        raise ValueError("static_tolerance_units: fraction must be a number in 0..1")
+    if isinstance(depth, bool) or depth not in (8, 10, 12, 16):
+        raise ValueError("static_tolerance_units: depth must be 8, 10, 12 or 16")
+    return int(math.floor(float(fraction) * ((1 << depth) - 1)))
+
+
+def static_frame_format(pixel_format):
+    """(layout, C, sample_bytes, depth, shift) of a harness pixel format as emavfi_static_guard_frames takes it: "bgr24" is interleaved
+    bytes of 3 channels; "nv12" / "p01x" the NV12 layout (P01x: words with the sample in the top bits); "yuv420pN" the I420 layout (words
+    with the sample in the low bits above 8 bits)"""
+    if pixel_format == "bgr24":
+        return LAYOUT_INTERLEAVED, 3, 1, 8, 0
+    if pixel_format != "nv12" and pixel_format not in DEPTHS and pixel_format not in PLANAR_DEPTHS:
+        raise ValueError(f"static_frame_format: unknown pixel_format {pixel_format!r}")
+    return (LAYOUT_I420 if pixel_format in PLANAR_DEPTHS else LAYOUT_NV12, 1, *resample_sample_format(pixel_format))
+
+
+def static_guard_frames(dst, srcs, table, size, layout=LAYOUT_INTERLEAVED, C=1, sample_bytes=1, depth=8, shift=0, radius=0, tol=0, counts=None):
+    """Holds the static regions of `dst`'s frames (the static region definition of include/emavfi.h): frame k of `dst` - a post-processed
+    prediction for the pair table[k] = (a, b) of frames of `srcs` - receives a's samples wherever a and b agree within `tol` (sample units:
+    static_tolerance_units) over the whole window of `radius` around the pixel; every other byte is left as it was.  `dst` uint8
+    [n_dst, ...], `srcs` uint8 [n_srcs, ...]: device tensors or pinned host memory with the same dense frame shape, the bytes of `size` =
+    (H, W) frames of `layout` (a name of LAYOUTS or its code; C channels when interleaved); their first dimension may be strided.  16-bit
+    frames travel as their bytes with sample_bytes = 2 and the sample's `depth` and `shift`.  `counts`: None, or a contiguous int32
+    [n_dst] device tensor that receives every entry's number of core pixels.  The table is consumed before the call returns."""
+    import torch
+    H, W = (int(v) for v in size)
+    layout = LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+    for t, what in ((dst, "static_guard_frames(dst)"), (srcs, "static_guard_frames(srcs)")):
+        _pinned_or_cuda(t, what)
+        if t.dtype != torch.uint8 or t.dim() < 2 or t.numel() == 0 or not t[0].is_contiguous() or tuple(t.shape[1:]) != tuple(dst.shape[1:]):
+            raise ValueError(f"{what}: a non-empty uint8 [frames, ...] tensor with dense frames of dst's frame shape expected")
+    table = list(table)
+    if len(table) != dst.shape[0]:
+        raise ValueError(f"static_guard_frames: {len(table)} table entries for {dst.shape[0]} destination frames")
+    fb = dst[0].numel()
+    want = H * W * int(sample_bytes) * (int(C) if layout == LAYOUT_INTERLEAVED else 3) // (1 if layout == LAYOUT_INTERLEAVED else 2)
+    if fb != want:
+        raise ValueError(f"static_guard_frames: a frame of {fb} bytes is not a {H} x {W} frame of this layout ({want} bytes)")
+    if counts is not None and not (counts.is_cuda and counts.dtype == torch.int32 and tuple(counts.shape) == (len(table),) and counts.is_contiguous()):
+        raise ValueError(f"static_guard_frames: counts must be a contiguous int32 [{len(table)}] device tensor")
+    stride = lambda t: t.stride(0) if t.shape[0] > 1 else fb     # a dimension of size 1 has no meaningful stride
+    arr = (StaticEntry * len(table))(*(StaticEntry(int(a), int(b)) for a, b in table))
+    dev = next((t.device for t in (dst, srcs) if t.is_cuda), None) or (counts.device if counts is not None else torch.device("cuda"))
+    with torch.cuda.device(dev):
+        check(load().emavfi_static_guard_frames(dst.data_ptr(), stride(dst), len(table), srcs.data_ptr(), stride(srcs), srcs.shape[0],
+                                                ctypes.cast(arr, c_void_p), H, W, layout, int(C), int(sample_bytes), int(depth), int(shift),
+                                                int(radius), int(tol), counts.data_ptr() if counts is not None else None, _stream()),
+              "emavfi_static_guard_frames")
+    return dst
 
 
 # ---------------------------------------------------------------- frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION")

@@ -97,6 +97,19 @@ source intervals comes from that gap's tree, ``ceil(log2 m)`` levels deeper (``d
 - unlike the scene decision - the host reads them before it plans: a pre-pass uploads the call's frames in slot-sized batches, scores the
 consecutive pairs and waits ONCE per ``run()`` call (once per chunk in ``run_chunked``); the source frames cross PCIe twice.  ``duplicates``
 lists ``(t, score)`` of the dropped frames, ``dedup_scores`` of every scored pair ``(t - 1, t)``, with global indices.  One process only.
+``static_guard=r`` (opt-in, an int radius in 0..16; not in the reference, which writes the prediction as it comes) holds the static regions
+of a pair - channel logos, subtitles, scoreboards, letterbox bars, the unchanged background of screen captures: a pixel whose whole window of
+radius ``r``, clipped to the frame, is the same in both source frames keeps the EARLIER frame's samples in every prediction of the pair (the
+static region definition of include/emavfi.h; 4:2:0 chroma where all four luma pixels it covers qualify).  ``static_tolerance`` (a fraction of
+full scale in [0, 1], default 0: bit-equal samples only; ``lib.static_tolerance_units``) widens "the same".  No default radius or tolerance is
+claimed.  The guard runs on the post lane, on the frames AS EMITTED, at the size the model runs at: the prediction bytes are compared with the
+staged source bytes (with ``scale`` / ``size``: the device-resized ones) by one ``emavfi_static_guard_frames`` call per batch, ahead of the
+scene hold (the order cannot change the result: a held frame is the earlier frame everywhere); in mode "resample" every node frame is guarded
+against its gap's two kept source frames before ``emavfi_resample_frames`` selects or blends.  The recursion's fp32 inputs stay unguarded.
+``static_share`` lists, per emitted prediction of the last ``run()`` (mode "resample": per emitted frame made of node frames), the share of
+its pixels that were held; the counts ride to a small pinned buffer behind the frames and are read after the ``done`` wait the drain already
+performs - no new synchronisation point.  Refused with ``reference_quirks=True`` (exact source pixels pasted into the quirk's de-normalised
+prediction would show as patches) and with ``zero_copy=True``; ``evaluate()`` is unaffected.  All ten pixel formats work.
 """
 from __future__ import annotations
 
@@ -198,6 +211,8 @@ class DedupPlan(NamedTuple):
 class FrameInterpolator:
     dedup = None   # the duplicate threshold in score units (lib.dedup_threshold_units); None: duplicates are not looked for
     dedup_max_run, dedup_span = 3, 64
+    static_guard = None   # the radius of the static-region guard (include/emavfi.h, "STATIC REGION DEFINITION"); None: off
+    static_tol = 0        # its tolerance in sample units (lib.static_tolerance_units)
     _depth = 0   # bits per sample of a 16-bit-word pixel format ("p010": 10, ...); 0 for the byte formats
     _planar = _yuv8 = False
     mode = "reference"
@@ -207,7 +222,8 @@ class FrameInterpolator:
                  numa: str = "off", pixel_format: str = "bgr24", yuv_standard: str = "bt601", yuv_full_range: bool = False,
                  scale: Optional[float] = None, size=None, scene_threshold: Optional[float] = None,
                  rate_in=None, rate_out=None, resample_depth: int = 3, resample_method: str = "nearest",
-                 dedup_threshold: Optional[float] = None, dedup_max_run: int = 3, dedup_span: int = 64):
+                 dedup_threshold: Optional[float] = None, dedup_max_run: int = 3, dedup_span: int = 64,
+                 static_guard: Optional[int] = None, static_tolerance: float = 0.0):
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
             raise ValueError("interpolation_factor >= 0, frame_interval >= 1, batch_pairs >= 1 required")
         if mode not in ("reference", "recursive", "resample"):
@@ -261,6 +277,23 @@ class FrameInterpolator:
                                      "bit-identical luma only)")
                 self.dedup = _lib.dedup_threshold_units(dedup_threshold, self._depth or 8)
         self.duplicates, self.dedup_scores = [], []   # (t, score) of the dropped frames / of every scored pair (t - 1, t), global indices
+        if isinstance(static_tolerance, bool) or not isinstance(static_tolerance, (int, float)) or not 0 <= static_tolerance <= 1:
+            raise ValueError("static_tolerance must be a number in [0, 1]: the largest difference of two samples, as a fraction of full scale, "
+                             "at which they still count as the same (0: bit-equal only)")
+        if static_guard is None:
+            if static_tolerance != 0:
+                raise ValueError("static_tolerance without static_guard: the tolerance belongs to the static-region guard (pass a radius)")
+        else:
+            if isinstance(static_guard, bool) or not isinstance(static_guard, int) or not 0 <= static_guard <= _lib.STATIC_MAX_RADIUS:
+                raise ValueError(f"static_guard must be None (off) or an integer radius in 0..{_lib.STATIC_MAX_RADIUS}")
+            if reference_quirks:
+                raise ValueError("static_guard with reference_quirks=True: exact source pixels pasted into the quirk's de-normalised prediction "
+                                 "would show as patches (pass reference_quirks=False)")
+            if zero_copy:
+                raise ValueError("static_guard with zero_copy=True: the guard compares and patches frames in device memory, which leave by copy")
+            self.static_guard = static_guard
+            self.static_tol = _lib.static_tolerance_units(static_tolerance, self._depth or 8)
+        self.static_share = []   # per emitted prediction of the last run(): the share of its pixels the guard held
         if scale is not None and size is not None:
             raise ValueError("scale and size are mutually exclusive")
         if scale is not None and not scale > 0:
@@ -593,6 +626,10 @@ class FrameInterpolator:
                 self._slots[-1].update({"e_rs": torch.empty(per * nb, *fs, dtype=torch.uint8, device=self.device) if self._resize else None,
                                         "met": torch.zeros(nb, mc, 2, dtype=torch.int64, device=self.device),
                                         "h_met": torch.zeros(nb, mc, 2, dtype=torch.int64).pin_memory()})
+            if self.static_guard is not None:
+                # core pixel counts of the slot's prediction frames, on the device and pinned
+                self._slots[-1].update({"sg": torch.zeros(nb * nout, dtype=torch.int32, device=self.device),
+                                        "h_sg": torch.zeros(nb * nout, dtype=torch.int32).pin_memory()})
             if self.scene is not None:
                 # signatures of the slot's staged frames; flags (row 0) and scores (row 1) of its pairs, on the device and pinned
                 self._slots[-1].update({"sig": torch.empty(per * nb, _lib.SCENE_SIG_WORDS, dtype=torch.int32, device=self.device),
@@ -683,6 +720,18 @@ class FrameInterpolator:
         else:
             for k in range(n):
                 _lib.hold_frames_u8(dst[k * rep:(k + 1) * rep], alt_buf[idx[k]:idx[k] + 1], flags[k:k + 1], rep)
+
+    def _static_hold(self, slot, dst, srcs, table):
+        """the static regions of the pairs `table` = [(a, b)] (rows of `srcs`, the source frames as emitted) held in the prediction frames
+        `dst`; the core pixel counts follow the frames to the slot's pinned buffer"""
+        n = len(table)
+        if slot["sg"].shape[0] < n:     # mode "resample": a batch has as many node frames as its plan needs
+            slot["sg"] = torch.zeros(n, dtype=torch.int32, device=self.device)
+            slot["h_sg"] = torch.zeros(n, dtype=torch.int32).pin_memory()
+        layout, C, sb, depth, shift = _lib.static_frame_format(self.pixel_format)
+        _lib.static_guard_frames(dst[:n], srcs, table, self._dst, layout=layout, C=C, sample_bytes=sb, depth=depth, shift=shift,
+                                 radius=self.static_guard, tol=self.static_tol, counts=slot["sg"][:n])
+        slot["h_sg"][:n].copy_(slot["sg"][:n], non_blocking=True)
 
     def _resized_bytes(self, frame):
         """one source frame (numpy) at the destination size, as the device resizes it"""
@@ -862,6 +911,7 @@ class FrameInterpolator:
         words = (lambda v: v.view(np.uint16)) if self._depth else (lambda v: v)
         self._alloc(first.shape)
         self.scene_cuts, self.scene_scores = [], []
+        self.static_share = []
         main = torch.cuda.current_stream(self.device)
         # ramp-up: with three or more batches to come the FIRST one is half-size - the GPU starts after five staged frames instead of
         # nine, and (64 pairs at batch 8: 4 + 7 x 8 + 4) the last one's drain is half as long; every other batch is full.  Per-sample
@@ -881,12 +931,18 @@ class FrameInterpolator:
                     self.scene_scores.append((a, b, int(fs[1, k])))
                     if fs[0, k]:
                         self.scene_cuts.append((a, b, int(fs[1, k])))
+            if self.static_guard is not None:     # written behind the frames, ahead of `done`
+                sg, area = slot["h_sg"].numpy(), float(self._dst[0] * self._dst[1])
             for k, (a, _) in enumerate(chunk):
                 if self.mode == "recursive":
                     for j in range(npred):
+                        if self.static_guard is not None:
+                            self.static_share.append(int(sg[k * npred + j]) / area)
                         yield own(pred_h[k * npred + j])
                 else:
                     for _ in range(self.factor):
+                        if self.static_guard is not None:
+                            self.static_share.append(int(sg[k]) / area)
                         yield own(pred_h[k])
                 yield own(src_h[k]) if (self.quirks or self._resize) else words(frames[a])
 
@@ -946,6 +1002,11 @@ class FrameInterpolator:
                         self._post_kernel(x1, True, out=slot["h_src"][:n])
                 else:
                     self._post_kernel(flat, self.quirks, out=slot["d_pred"][:n * npred])
+                    if self.static_guard is not None:
+                        # every prediction of pair k against the pair's two source frames as emitted; d_in / d_rs are complete: the
+                        # forward waited for `pre`
+                        self._static_hold(slot, slot["d_pred"], rs if rs is not None else slot["d_in"][:nup],
+                                          [(ia[k], ib[k]) for k in range(n) for _ in range(npred)])
                     if self.scene is None:
                         slot["h_pred"][:n * npred].copy_(slot["d_pred"][:n * npred], non_blocking=True)   # HBM -> pinned (SDMA)
                     if self.quirks and not src_here:
@@ -1095,6 +1156,7 @@ class FrameInterpolator:
         self._alloc(first.shape)
         self.scene_cuts, self.scene_scores = [], []
         self.duplicates, self.dedup_scores = [], []
+        self.static_share = []
         kept = list(range(a, b + 1)) if b > a else []
         if self.dedup is not None and b > a:
             # the set of forwards depends on the flags: the host reads them before it plans (one wait per run() call)
@@ -1122,9 +1184,12 @@ class FrameInterpolator:
                                  "d_emit": torch.empty(n_emit, *fs, dtype=torch.uint8, device=self.device),
                                  "h_emit": torch.empty(n_emit, *fs, dtype=torch.uint8).pin_memory()})
 
-        def drain(slot, chunk, n_out):
+        def drain(slot, chunk, n_out, first_node):
             slot["done"].synchronize()            # this batch's frames have been written into the pinned buffer
             emit_h = slot["h_emit"].numpy()
+            if self.static_guard is not None:     # written behind the frames, ahead of `done`: an emitted frame made of node frames has its
+                sg, area = slot["h_sg"].numpy(), float(self._dst[0] * self._dst[1])     # gap's share (core depends on the two sources only)
+                self.static_share += [int(sg[i]) / area for i in first_node]
             own = (lambda v: words(v).copy()) if self.copy_out else words
             if self.scene is not None:            # written behind the frames, ahead of `done`
                 fs = slot["h_fs"].numpy()
@@ -1162,6 +1227,16 @@ class FrameInterpolator:
                     self._post_kernel(m, False, out=slot["d_node"][off:off + m.shape[0]])
                     off += m.shape[0]
                 assert off == n_nodes
+                first_node = []
+                if self.static_guard is not None and off:
+                    # every node frame against its gap's two kept source frames, before the outputs are selected or blended
+                    gap_of = [k for lv in levels for k, _ in lv]
+                    self._static_hold(slot, slot["d_node"], rs if rs is not None else slot["d_in"][:nup], [(ia[k], ib[k]) for k in gap_of])
+                    first = {}
+                    for i, k in enumerate(gap_of):
+                        first.setdefault(k, i)
+                    # an entry's last field is its gap's first staged row, ia[k]: distinct per gap
+                    first_node = [first[ia.index(e[4])] for e in table if (e[0] | e[1]) & _lib.RESAMPLE_NODES]
                 # the source frames as emitted: the staged bytes, or the bytes the preprocess kernel resized them to
                 _lib.resample_frames(slot["d_emit"][:len(table)], rs if rs is not None else slot["d_in"][:nup],
                                      slot["d_node"][:off] if off else None, table,
@@ -1174,7 +1249,7 @@ class FrameInterpolator:
                 staged = self._stage(self._slots[(ci + 1) & 1], frames, chunks[ci + 1])
             if prev is not None:
                 yield from drain(*prev)
-            prev = (slot, chunk, len(table))
+            prev = (slot, chunk, len(table), first_node)
         if prev is not None:
             yield from drain(*prev)
         if tail:
@@ -1211,9 +1286,10 @@ class FrameInterpolator:
             raise ValueError(f"run_chunked: chunk_pairs = {chunk_pairs} with dedup_threshold must be a multiple of dedup_span = {self.dedup_span}: "
                              "every chunk then starts and ends on a frame that is kept regardless, and sees what the whole clip would")
         L, it, held, lo = chunk_pairs * self.interval, iter(frames), [], 0
-        cuts, scores, dups, dscores = [], [], [], []
+        cuts, scores, dups, dscores, shares = [], [], [], [], []
         self.scene_cuts, self.scene_scores = [], []
         self.duplicates, self.dedup_scores = [], []
+        self.static_share = []
         while True:
             for f in it:
                 held.append(f)
@@ -1230,6 +1306,8 @@ class FrameInterpolator:
                 dups += self.duplicates                         # global indices already: run() was told where the chunk starts
                 dscores += self.dedup_scores
                 self.duplicates, self.dedup_scores = list(dups), list(dscores)
+                shares += self.static_share
+                self.static_share = list(shares)
             if final:
                 return
             held, lo = held[-1:], lo + L
@@ -1246,7 +1324,8 @@ class FrameInterpolator:
         one-channel image (PSNR-Y / SSIM-Y); chroma is not scored.  Only the metric words travel to a small pinned buffer, read after the
         ``done`` wait of the drain; no frame returns to the host.  The staged frames always reach the device by copy (``zero_copy`` is a
         property of ``run()``'s transport).  ``interpolation_factor``, ``mode``, ``reference_quirks``, ``frame_interval`` and
-        ``scene_threshold`` do not affect ``evaluate``: a target has one midpoint and is never held.
+        ``scene_threshold`` do not affect ``evaluate``: a target has one midpoint and is never held.  ``static_guard`` does not either: the
+        model's own prediction is scored, not the guarded frame.
 
         ``frames`` / ``rank`` / ``world`` as for ``run()``: a rank touches only the frames of its contiguous share of the targets, and
         the ranks' ``targets`` concatenated in rank order are the single-process result."""
