@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -681,6 +681,58 @@ typedef struct { unsigned a, b; } emavfi_static_entry;   /* indices into srcs */
 int emavfi_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst, const unsigned char *srcs, size_t src_stride, int n_srcs,
                                const emavfi_static_entry *table, int H, int W, int layout, int C, int sample_bytes, int depth, int shift,
                                int radius, unsigned tol, unsigned *counts, void *stream);
+
+/* Test-time ensembling.  The forward estimates one flow and warps only frame2 (ema_vfi.py:130), so F(a, b) and F(b, a) are two different
+ * "midpoints" of the same pair, and its stride-2 context path and zero padding make it non-equivariant under mirroring.  The usual remedy
+ * (RIFE: --ensemble; EMA-VFI's authors: TTA) runs the pair reversed and / or mirrored, maps each prediction back and averages.  The reference
+ * has none (inference.py:158-160 calls the model once); this is an addition, off unless asked for.  No quality claim is made: what the
+ * definition below buys, bit for bit, is an interpolator that is exactly symmetric in time and exactly equivariant under flips.  The
+ * composition (which forwards run, on which inputs) lives in the Python layer (EMA_VFI.ensemble); the two entries here are the device work
+ * a C integrator needs beside emavfi_forward_routed.
+ *
+ * ENSEMBLE DEFINITION (the one place).  This is the project's own definition: it claims agreement with no outside tool.
+ *   Flip codes.  EMAVFI_FLIP_H = 1 maps column x to W - 1 - x; EMAVFI_FLIP_V = 2 maps row y to H - 1 - y; 3 applies both; 0 is the identity.
+ *     phi_f is the map on fp32 [planes][H][W] tensors: (phi_f t)[p][y][x] = t[p][f & 2 ? H - 1 - y : y][f & 1 ? W - 1 - x : x].  Every
+ *     phi_f is its own inverse.
+ *   F(a, b) is the plain forward's fp32 result (under EMAVFI_AMP16: before the final conversion of the frame to fp16).
+ *   A member is a pair (tensor m_k, flip f_k); its value at output position p is m_k[phi_{f_k} p].
+ *   The mean of n in {1, 2, 4, 8} members is a balanced pairwise tree in the order given; every + is one IEEE fp32 addition, and the tree is
+ *     then multiplied ONCE by the exact constant 1 / n (n = 1: the member's value itself):
+ *       n = 1: m0        n = 2: m0 + m1        n = 4: (m0 + m1) + (m2 + m3)        n = 8: ((m0 + m1) + (m2 + m3)) + ((m4 + m5) + (m6 + m7))
+ *     No reassociation, no contraction, no fast-math.  A NaN in any member gives NaN.
+ *   The ensembles, with P_f(a, b) = F(phi_f a, phi_f b) read through flip f (the member (F(phi_f a, phi_f b), f)):
+ *       "reverse":  (F(a, b), 0), (F(b, a), 0)
+ *       "flip":     P_0(a, b), P_3(a, b), P_1(a, b), P_2(a, b)
+ *       "full":     the four of "flip" for (a, b), then the same four for (b, a)
+ *   Why this order, and why nobody may tidy it.  fp32 addition is commutative but not associative, so a symmetry of the inputs leaves the
+ *     bits alone only if it maps the tree onto itself.  (1) Swapping a and b swaps the two members of "reverse" - one commutative addition -
+ *     and swaps the two halves of "full" - its top addition.  (2) Flipping both inputs by g turns P_f into P_{f ^ g} read at the flipped
+ *     position (phi_f phi_g = phi_{f ^ g}).  The pairing {identity, HV}, {H, V} is closed under that: g = HV (3) swaps the members WITHIN
+ *     each pair, g = H (1) or V (2) swaps the two pairs whole.  Either way every addition sees the same two operands, perhaps exchanged.
+ *     (The flips form a group under xor and two pairs are always the cosets of one of its subgroups, so another pairing would be
+ *     equivariant too - with other bits: the order above is the definition.)  What is NOT equivariant is an unbalanced sum: left to
+ *     right, ((P_0 + P_3) + P_1) + P_2 turns under g = H into ((P_1 + P_2) + P_0) + P_3, other additions altogether.
+ *     Hence "reverse" and "full" give ens(a, b) == ens(b, a) and "flip" and "full" give ens(phi_g a, phi_g b) == phi_g ens(a, b), bit for bit,
+ *     for any deterministic F at all - which the plain forward is for a fixed route (EMA_VFI.pack_adapt unset).
+ *
+ * emavfi_flip_f32: dst = phi_flip src; flip = 0 is a copy.
+ * emavfi_ensemble_mean_f32: out = the tree mean above of the n members (members[k], flips[k]).  `members` and `flips` are HOST arrays of n
+ *   entries, read and validated before the call returns; they travel as kernel arguments and nothing of them is retained.
+ * Both: dense fp32 [planes][H][W], H and W in 1..16384; planes * H * W is addressed with 64 bits (indices inside a plane are 32-bit).  The
+ *   tensors are device pointers or pinned (device-mapped) host memory.  Nothing is allocated, nothing synchronises, there is no workspace,
+ *   all work goes on `stream`; every word of dst / out is written and nothing else is.
+ * EMAVFI_E_ARG (never an abort), the message naming the argument: a null pointer (src, dst, out, members, flips or a members[k]); n outside
+ *   {1, 2, 4, 8}; a flip outside 0..3; planes of 0; a dimension outside 1..16384; a pointer that is not 4-byte aligned; size arithmetic
+ *   that overflows size_t; dst overlapping src, or out overlapping any member.
+ * Access width: 16-byte loads and stores, 4 consecutive output columns per lane, when W % 4 == 0 and every pointer of the call is 16-byte
+ *   aligned; a member flipped along H is then read as the mirrored 16-byte unit with its four lanes reversed in registers.  Everything else
+ *   takes a scalar path built from the same per-element functions (csrc/ensemble_elem.h).  Both kernels are pure streaming and short-lived:
+ *   the grid follows the element count, nothing waits on anything. */
+#define EMAVFI_FLIP_H 1
+#define EMAVFI_FLIP_V 2
+#define EMAVFI_ENSEMBLE_MAX_MEMBERS 8
+int emavfi_flip_f32(const float *src, float *dst, size_t planes, int H, int W, int flip, void *stream);
+int emavfi_ensemble_mean_f32(const float *const *members, const int *flips, int n, float *out, size_t planes, int H, int W, void *stream);
 
 /* Frame metrics on the device: how close is image a (an interpolated frame) to image b (the held-out true frame)?  The reference has no
  * evaluation script (its README names PSNR and SSIM against held-out ground-truth frames as the way to judge a model and calls an eval.py a

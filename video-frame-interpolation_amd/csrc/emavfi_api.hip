@@ -7,6 +7,7 @@
 #include "resample_elem.h"
 #include "dedup_elem.h"
 #include "static_elem.h"
+#include "ensemble_elem.h"
 #include "conv_first.inl"
 
 #include <atomic>
@@ -1846,6 +1847,66 @@ int emavfi_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst,
     }
     EMAVFI_TRY(launch_static_guard_frames(dst, dst_stride, n_dst, srcs, src_stride, reinterpret_cast<const StaticEntry *>(table), H, W, layout, C,
                                           sample_bytes, depth, shift, radius, tol, counts, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+// ---- test-time ensembling (include/emavfi.h, "ENSEMBLE DEFINITION"): every check runs on the host, the member list is read here and not kept
+static_assert(EMAVFI_FLIP_H == ENSEMBLE_FLIP_H && EMAVFI_FLIP_V == ENSEMBLE_FLIP_V && EMAVFI_ENSEMBLE_MAX_MEMBERS == ENSEMBLE_MAX_MEMBERS,
+              "header and ensemble_elem.h disagree");
+
+// the bytes of a dense fp32 [planes][H][W] tensor, refused where the arithmetic overflows size_t
+static int ensemble_shape_check(const char *what, size_t planes, int H, int W, size_t *bytes)
+{
+    if (planes < 1) return fail(EMAVFI_E_ARG, "%s: planes must be >= 1", what);
+    if (const int rc = scene_dims_check(what, H, W); rc != EMAVFI_OK) return rc;
+    if (__builtin_mul_overflow(planes, (size_t)H * W * sizeof(float), bytes))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (planes %zu)", what, planes);
+    return EMAVFI_OK;
+}
+
+// a tensor of `bytes` bytes at p: 4-byte aligned, inside the address space
+static int ensemble_pointer_check(const char *what, const char *name, int index, const void *p, size_t bytes)
+{
+    char label[32];
+    if (index >= 0) snprintf(label, sizeof label, "%s[%d]", name, index);
+    else snprintf(label, sizeof label, "%s", name);
+    if (!p) return fail(EMAVFI_E_ARG, "%s: null pointer %s", what, label);
+    if ((uintptr_t)p & 3) return fail(EMAVFI_E_ARG, "%s: the fp32 pointer %s must be 4-byte aligned", what, label);
+    if ((uintptr_t)p + bytes < (uintptr_t)p) return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (%s wraps the address space)", what, label);
+    return EMAVFI_OK;
+}
+
+int emavfi_flip_f32(const float *src, float *dst, size_t planes, int H, int W, int flip, void *stream)
+{
+    const char *const what = "flip_f32";
+    size_t bytes;
+    if (const int rc = ensemble_shape_check(what, planes, H, W, &bytes); rc != EMAVFI_OK) return rc;
+    if (!ensemble_flip_ok(flip)) return fail(EMAVFI_E_ARG, "%s: flip = %d (flip must lie in 0..3: EMAVFI_FLIP_H | EMAVFI_FLIP_V)", what, flip);
+    if (const int rc = ensemble_pointer_check(what, "src", -1, src, bytes); rc != EMAVFI_OK) return rc;
+    if (const int rc = ensemble_pointer_check(what, "dst", -1, dst, bytes); rc != EMAVFI_OK) return rc;
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+    if (d0 < s0 + bytes && s0 < d0 + bytes) return fail(EMAVFI_E_ARG, "%s: dst overlaps src", what);
+    EMAVFI_TRY(launch_flip_f32(src, dst, planes, H, W, flip, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+int emavfi_ensemble_mean_f32(const float *const *members, const int *flips, int n, float *out, size_t planes, int H, int W, void *stream)
+{
+    const char *const what = "ensemble_mean_f32";
+    if (!ensemble_count_ok(n)) return fail(EMAVFI_E_ARG, "%s: n = %d (n must be 1, 2, 4 or 8)", what, n);
+    size_t bytes;
+    if (const int rc = ensemble_shape_check(what, planes, H, W, &bytes); rc != EMAVFI_OK) return rc;
+    if (!members) return fail(EMAVFI_E_ARG, "%s: null pointer members", what);
+    if (!flips) return fail(EMAVFI_E_ARG, "%s: null pointer flips", what);
+    if (const int rc = ensemble_pointer_check(what, "out", -1, out, bytes); rc != EMAVFI_OK) return rc;
+    const uintptr_t o0 = (uintptr_t)out;
+    for (int k = 0; k < n; ++k) {
+        if (!ensemble_flip_ok(flips[k])) return fail(EMAVFI_E_ARG, "%s: flips[%d] = %d (a flip must lie in 0..3)", what, k, flips[k]);
+        if (const int rc = ensemble_pointer_check(what, "members", k, members[k], bytes); rc != EMAVFI_OK) return rc;
+        const uintptr_t m0 = (uintptr_t)members[k];
+        if (o0 < m0 + bytes && m0 < o0 + bytes) return fail(EMAVFI_E_ARG, "%s: out overlaps members[%d]", what, k);
+    }
+    EMAVFI_TRY(launch_ensemble_mean_f32(members, flips, n, out, planes, H, W, (hipStream_t)stream), what);
     return EMAVFI_OK;
 }
 

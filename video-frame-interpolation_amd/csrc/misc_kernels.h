@@ -129,6 +129,10 @@ struct StaticEntry { unsigned a, b; };   // emavfi_static_entry
 int launch_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst, const unsigned char *srcs, size_t src_stride,
                                const StaticEntry *table, int H, int W, int layout, int C, int sample_bytes, int depth, int shift, int radius,
                                unsigned tol, unsigned *counts, hipStream_t s);
+// test-time ensembling (include/emavfi.h, "ENSEMBLE DEFINITION"): arguments already validated; `members` and `flips` are HOST arrays of n
+// entries, read before the call returns and passed on as kernel arguments
+int launch_flip_f32(const float *src, float *dst, size_t planes, int H, int W, int flip, hipStream_t s);
+int launch_ensemble_mean_f32(const float *const *members, const int *flips, int n, float *out, size_t planes, int H, int W, hipStream_t s);
 // frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION"): arguments already validated; `part` holds 2 u64 per (b, c, tile)
 // of frame_metrics_tiles' tx * ty tiles (32 x 32 windows each; one tile where an axis has no window)
 void frame_metrics_tiles(int H, int W, int *tx, int *ty);

@@ -6,6 +6,7 @@
 #include "resample_elem.h"
 #include "dedup_elem.h"
 #include "static_elem.h"
+#include "ensemble_elem.h"
 #include "metrics_elem.h"
 #include "p010_elem.h"
 #include "yuv420p_elem.h"
@@ -2818,6 +2819,113 @@ int launch_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst,
         if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Test-time ensembling (include/emavfi.h, "ENSEMBLE DEFINITION"; per-element functions: ensemble_elem.h).
+//   flip_f32_kernel        dst = the flipped src: the body below with one member and no arithmetic.
+//   ensemble_mean_kernel   out = the tree mean of N members, each read through its own flip.
+//                          Both: grid (pieces of a plane, planes - at most 65535 rows of the grid, a workgroup walks the planes beyond), 256
+//                          threads, pure streaming: no LDS, no atomics, nothing waits on anything, the grid follows the element count.  A lane
+//                          owns U units of one plane, 256 units apart, and issues the loads of all of them before the first use: 4 loads in
+//                          flight per lane (8 at N = 8).  Wide form (W % 4 == 0 and every pointer 16-byte aligned, so every plane and every
+//                          row starts on a unit): a unit is 4 output columns, one 16-byte store; a member flipped along H is read as the
+//                          MIRRORED unit of its row and its four lanes are reversed in registers, so loads stay 16 bytes wide and a wave
+//                          still covers one contiguous 1 KiB run, walked downwards.  Scalar form: a unit is one element.  The members and
+//                          flips travel as kernel arguments (scalar registers after unrolling).  Plane offsets are 64-bit, indices inside a
+//                          plane (at most 2^28 elements) 32-bit.
+// ------------------------------------------------------------------------------------------
+struct EnsembleArgs {
+    const float *m[ENSEMBLE_MAX_MEMBERS];
+    int flip[ENSEMBLE_MAX_MEMBERS];
+    float *out;
+    size_t planes, plane_elems;
+    int H, W;
+};
+
+template <int N, int U, bool WIDE>
+__device__ __forceinline__ void ensemble_body(const EnsembleArgs &p)
+{
+    using T = std::conditional_t<WIDE, float4, float>;
+    const unsigned Wu = (unsigned)(WIDE ? p.W >> 2 : p.W), units = (unsigned)p.H * Wu;
+    const unsigned u0 = blockIdx.x * (256u * U) + threadIdx.x;
+    for (size_t pl = blockIdx.y; pl < p.planes; pl += gridDim.y) {
+        const size_t base = pl * p.plane_elems;
+        T v[U][N];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const unsigned u = u0 + 256u * k;
+            if (u >= units) continue;
+            const int y = (int)(u / Wu), q = (int)(u - (unsigned)y * Wu);
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+                v[k][i] = reinterpret_cast<const T *>(p.m[i] + base)[ensemble_src_unit(y, q, p.H, (int)Wu, p.flip[i])];
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const unsigned u = u0 + 256u * k;
+            if (u >= units) continue;
+            if constexpr (WIDE) {
+                float a[N], b[N], c[N], d[N];
+#pragma unroll
+                for (int i = 0; i < N; ++i) {
+                    const EnsembleUnit e = ensemble_lanes(EnsembleUnit{v[k][i].x, v[k][i].y, v[k][i].z, v[k][i].w}, p.flip[i]);
+                    a[i] = e.x; b[i] = e.y; c[i] = e.z; d[i] = e.w;
+                }
+                reinterpret_cast<float4 *>(p.out + base)[u] = make_float4(ensemble_mean(a, N), ensemble_mean(b, N), ensemble_mean(c, N), ensemble_mean(d, N));
+            } else {
+                (p.out + base)[u] = ensemble_mean(v[k], N);
+            }
+        }
+    }
+}
+
+template <bool WIDE> __global__ __launch_bounds__(256) void flip_f32_kernel(EnsembleArgs p) { ensemble_body<1, 4, WIDE>(p); }
+constexpr int ensemble_units(int n) { return n >= 4 ? 1 : 4 / n; }
+template <int N, bool WIDE> __global__ __launch_bounds__(256) void ensemble_mean_kernel(EnsembleArgs p) { ensemble_body<N, ensemble_units(N), WIDE>(p); }
+
+static bool ensemble_wide(const EnsembleArgs &p, int n)
+{
+    uintptr_t bits = (uintptr_t)p.out | (uintptr_t)(p.W & 3);
+    for (int i = 0; i < n; ++i) bits |= (uintptr_t)p.m[i];
+    return (bits & 15) == 0;
+}
+
+static dim3 ensemble_grid(const EnsembleArgs &p, bool wide, int per_lane)
+{
+    const size_t units = (size_t)p.H * (size_t)(wide ? p.W >> 2 : p.W), per_wg = 256u * (size_t)per_lane;   // units <= 2^28
+    return dim3((unsigned)((units + per_wg - 1) / per_wg), (unsigned)(p.planes < 65535 ? p.planes : 65535));
+}
+
+int launch_flip_f32(const float *src, float *dst, size_t planes, int H, int W, int flip, hipStream_t s)
+{
+    EnsembleArgs p{};
+    p.m[0] = src; p.flip[0] = flip; p.out = dst; p.planes = planes; p.plane_elems = (size_t)H * W; p.H = H; p.W = W;
+    const bool wide = ensemble_wide(p, 1);
+    if (wide) flip_f32_kernel<true><<<ensemble_grid(p, true, 4), 256, 0, s>>>(p);
+    else flip_f32_kernel<false><<<ensemble_grid(p, false, 4), 256, 0, s>>>(p);
+    return (int)hipGetLastError();
+}
+
+template <int N> static void launch_ensemble_mean_n(const EnsembleArgs &p, hipStream_t s)
+{
+    if (ensemble_wide(p, N)) ensemble_mean_kernel<N, true><<<ensemble_grid(p, true, ensemble_units(N)), 256, 0, s>>>(p);
+    else ensemble_mean_kernel<N, false><<<ensemble_grid(p, false, ensemble_units(N)), 256, 0, s>>>(p);
+}
+
+int launch_ensemble_mean_f32(const float *const *members, const int *flips, int n, float *out, size_t planes, int H, int W, hipStream_t s)
+{
+    EnsembleArgs p{};
+    for (int i = 0; i < n; ++i) { p.m[i] = members[i]; p.flip[i] = flips[i]; }
+    p.out = out; p.planes = planes; p.plane_elems = (size_t)H * W; p.H = H; p.W = W;
+    switch (n) {
+    case 1: launch_ensemble_mean_n<1>(p, s); break;
+    case 2: launch_ensemble_mean_n<2>(p, s); break;
+    case 4: launch_ensemble_mean_n<4>(p, s); break;
+    case 8: launch_ensemble_mean_n<8>(p, s); break;
+    default: return -2;
+    }
+    return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------

@@ -70,6 +70,10 @@ def parser() -> argparse.ArgumentParser:
                         "source frames keeps the earlier frame's samples (no default is claimed); excludes --reference-quirks")
     p.add_argument("--static-tolerance", type=float, default=None, metavar="FRACTION",
                    help="with --static-guard: samples that differ by at most FRACTION of full scale count as the same (default 0: bit-equal only)")
+    p.add_argument("--ensemble", choices=("reverse", "flip", "full"), default=None,
+                   help="test-time ensembling of every forward: the pair and the reversed pair (reverse: 2 forwards, symmetric in time), the "
+                        "pair under the four mirrorings (flip: 4 forwards, equivariant under flips) or both (full: 8 forwards); no quality "
+                        "claim is made, --evaluate tells what it buys on a clip")
     p.add_argument("--batch-pairs", type=int, default=8)
     p.add_argument("--chunk-pairs", type=int, default=64, help="frame pairs per chunk: at most chunk_pairs * frame_interval + 1 source frames are held")
     p.add_argument("--yuv-standard", default="bt601", help="bt601, bt709 or (10 / 12 / 16-bit streams) bt2020")
@@ -139,7 +143,8 @@ def _run(args) -> int:
                                **(dict(dedup_threshold=args.dedup, dedup_max_run=3 if args.dedup_max_run is None else args.dedup_max_run)
                                   if args.dedup is not None else {}),
                                **(dict(static_guard=args.static_guard, static_tolerance=args.static_tolerance or 0.0)
-                                  if args.static_guard is not None else {}))
+                                  if args.static_guard is not None else {}),
+                               ensemble=args.ensemble)
         if args.evaluate:
             print(fi.evaluate(list(reader), every=args.every))      # evaluate() indexes the clip: all of it is held
             return 0
@@ -155,7 +160,8 @@ def _run(args) -> int:
                   + (f"{args.resample} at depth {args.resample_depth})" if resample else f"factor {factor})")
                   + (f", {len(fi.duplicates)} duplicate frames dropped" if args.dedup is not None else "")
                   + (f", static guard held {100.0 * sum(fi.static_share) / max(len(fi.static_share), 1):.2f} % of the predictions' pixels on average"
-                     if args.static_guard is not None else ""), file=sys.stderr)
+                     if args.static_guard is not None else "")
+                  + (f", ensemble {args.ensemble}" if args.ensemble is not None else ""), file=sys.stderr)
     return 0
 
 

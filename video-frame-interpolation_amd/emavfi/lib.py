@@ -70,6 +70,8 @@ _PROTOTYPES = {
     "emavfi_duplicate_flags": (c_int, [c_void_p, c_size_t, c_int, ctypes.c_uint, c_void_p, c_void_p, c_void_p]),
     "emavfi_static_guard_frames": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p] + [c_int] * 8
                                    + [ctypes.c_uint, c_void_p, c_void_p]),
+    "emavfi_flip_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "emavfi_ensemble_mean_f32": (c_int, [POINTER(c_void_p), POINTER(c_int), c_int, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "emavfi_frame_metrics_workspace_bytes": (c_size_t, [c_int] * 4),
     "emavfi_frame_metrics_u8": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 4
                                 + [c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -1287,6 +1289,65 @@ def static_guard_frames(dst, srcs, table, size, layout=LAYOUT_INTERLEAVED, C=1, 
                                                 int(radius), int(tol), counts.data_ptr() if counts is not None else None, _stream()),
               "emavfi_static_guard_frames")
     return dst
+
+
+# ---------------------------------------------------------------- test-time ensembling (include/emavfi.h, "ENSEMBLE DEFINITION")
+FLIP_H, FLIP_V = 1, 2                            # EMAVFI_FLIP_H, EMAVFI_FLIP_V; 3 = both, 0 = the identity
+ENSEMBLES = (None, "reverse", "flip", "full")    # EMA_VFI.ensemble
+ENSEMBLE_FLIPS = (0, 3, 1, 2)                    # the member order of "flip" and of each half of "full": the pairs {identity, HV}, {H, V}
+
+
+def _ensemble_planes(t, what):
+    """(planes, H, W) of a dense fp32 [..., H, W] tensor on the device or in pinned host memory"""
+    import torch
+    _pinned_or_cuda(t, what)
+    if t.dtype != torch.float32 or t.dim() < 2 or t.numel() == 0 or not t.is_contiguous():
+        raise ValueError(f"{what}: a non-empty contiguous float32 [..., H, W] tensor expected")
+    H, W = int(t.shape[-2]), int(t.shape[-1])
+    return t.numel() // (H * W), H, W
+
+
+def flip_f32(x, flip, out=None):
+    """out = x mirrored over its last two dimensions (the ensemble definition of include/emavfi.h): flip & FLIP_H maps column x to W - 1 - x,
+    flip & FLIP_V row y to H - 1 - y; 0 is a copy.  `x`, `out`: contiguous float32 [..., H, W] of one shape, device tensors or pinned host
+    memory, not overlapping.  Runs on the current stream; returns `out`."""
+    import torch
+    planes, H, W = _ensemble_planes(x, "flip_f32(x)")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device if x.is_cuda else "cuda")
+    elif _ensemble_planes(out, "flip_f32(out)") != (planes, H, W) or out.shape != x.shape:
+        raise ValueError(f"flip_f32: out {tuple(out.shape)} is not of x's shape {tuple(x.shape)}")
+    dev = next((t.device for t in (x, out) if t.is_cuda), None) or torch.device("cuda")
+    with torch.cuda.device(dev):
+        check(load().emavfi_flip_f32(x.data_ptr(), out.data_ptr(), planes, H, W, int(flip), _stream()), "emavfi_flip_f32")
+    return out
+
+
+def ensemble_mean_f32(members, flips, out=None):
+    """out = the tree mean of n in {1, 2, 4, 8} members, member k read through flips[k] (the ensemble definition of include/emavfi.h): a
+    balanced pairwise tree of fp32 additions in the order given, then one multiplication by 1 / n.  `members`: contiguous float32
+    [..., H, W] tensors of one shape, device tensors or pinned host memory; `out` the same, overlapping none of them.  The lists are
+    consumed before the call returns.  Runs on the current stream; returns `out`."""
+    import torch
+    members, flips = list(members), [int(f) for f in flips]
+    if not members or len(members) != len(flips):
+        raise ValueError(f"ensemble_mean_f32: {len(members)} members for {len(flips)} flips")
+    planes, H, W = _ensemble_planes(members[0], "ensemble_mean_f32(members[0])")
+    for k, m in enumerate(members[1:], 1):
+        if _ensemble_planes(m, f"ensemble_mean_f32(members[{k}])") != (planes, H, W) or m.shape != members[0].shape:
+            raise ValueError(f"ensemble_mean_f32: members[{k}] {tuple(m.shape)} is not of members[0]'s shape {tuple(members[0].shape)}")
+    if out is None:
+        out = torch.empty(members[0].shape, dtype=torch.float32, device=next((m.device for m in members if m.is_cuda), "cuda"))
+    elif _ensemble_planes(out, "ensemble_mean_f32(out)") != (planes, H, W) or out.shape != members[0].shape:
+        raise ValueError(f"ensemble_mean_f32: out {tuple(out.shape)} is not of the members' shape {tuple(members[0].shape)}")
+    n = len(members)
+    ptrs = (c_void_p * n)(*(m.data_ptr() for m in members))
+    codes = (c_int * n)(*flips)
+    dev = next((t.device for t in (out, *members) if t.is_cuda), None) or torch.device("cuda")
+    with torch.cuda.device(dev):
+        check(load().emavfi_ensemble_mean_f32(ctypes.cast(ptrs, POINTER(c_void_p)), ctypes.cast(codes, POINTER(c_int)), n, out.data_ptr(),
+                                              planes, H, W, _stream()), "emavfi_ensemble_mean_f32")
+    return out
 
 
 # ---------------------------------------------------------------- frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION")

@@ -38,6 +38,9 @@ PACK_POLICIES = ("window", "gather")
 # EMA_VFI.pack_adapt's (enter, leave) fix-up shares for EMAVFI_PACK_ADAPT=1: the crossover measured for one block at B = 8 x 720p
 # (profiles/r07_gather_route_kill.md) plus hysteresis
 PACK_ADAPT_DEFAULT = (0.75, 0.65)
+# EMA_VFI.ensemble ("Ensembling"; include/emavfi.h, "ENSEMBLE DEFINITION")
+ENSEMBLES = _lib.ENSEMBLES
+_MODEL_ENSEMBLE = object()   # forward(ensemble=): "what the model's attribute says"
 
 
 class _LastCall(NamedTuple):
@@ -171,6 +174,7 @@ class EMA_VFI(nn.Module):
         self._route_states = {}   # (device index, stream handle) -> route state (include/emavfi.h), created by the first adaptive forward
         self.pack_policy = os.environ.get("EMAVFI_PACK_POLICY", "window")
         self.pack_adapt = os.environ.get("EMAVFI_PACK_ADAPT")
+        self.ensemble = None
         m = mid_channels
         self.feat_ext_conv1 = conv_block(in_channels * 2, m)
         self.feat_ext_blocks = nn.Sequential(OrderedDict(
@@ -386,6 +390,25 @@ class EMA_VFI(nn.Module):
     def pack_adapt(self, value):
         self._pack_adapt = parse_pack_adapt(value)
 
+    @property
+    def ensemble(self):
+        """Test-time ensembling of forward() ("Ensembling"; include/emavfi.h, "ENSEMBLE DEFINITION"): None (default: the
+        plain forward, every launch and byte as without the attribute), "reverse" (the pair and the reversed pair: 2 forwards, exactly
+        symmetric in time), "flip" (the pair under the four mirrorings: 4 forwards, exactly equivariant under flips) or "full" (both: 8
+        forwards).  The members are plain forwards of the same batch; the mirrored inputs and the tree mean run on the device
+        (emavfi_flip_f32, emavfi_ensemble_mean_f32); no host synchronisation is added."""
+        return self._ensemble
+
+    @ensemble.setter
+    def ensemble(self, value):
+        self._ensemble = self._check_ensemble(value)
+
+    @staticmethod
+    def _check_ensemble(value):
+        if value is not None and (not isinstance(value, str) or value not in ENSEMBLES):
+            raise ValueError(f"EMA_VFI.ensemble must be one of {ENSEMBLES}, got {value!r}")
+        return value
+
     def _start_mask(self):
         return (1 << self.num_blocks) - 1 if self._pack_policy == "gather" else 0
 
@@ -437,7 +460,12 @@ class EMA_VFI(nn.Module):
                 for i in range(self.num_blocks)]
 
     # ------------------------------------------------------------------ forward
-    def forward(self, frame1, frame2, return_taps=False, _events=None):
+    def forward(self, frame1, frame2, return_taps=False, _events=None, ensemble=_MODEL_ENSEMBLE):
+        """ema_vfi.py:110-147.  `ensemble`: one of ENSEMBLES for this call alone (FrameInterpolator passes its own); by default the
+        model's attribute decides."""
+        ensemble = self._ensemble if ensemble is _MODEL_ENSEMBLE else self._check_ensemble(ensemble)
+        if ensemble is not None and return_taps:
+            raise ValueError("EMA_VFI.forward: return_taps=True with an ensemble: the taps belong to one forward (set ensemble=None)")
         if frame1.shape != frame2.shape or frame1.dim() != 4 or frame1.shape[1] != self.in_channels:
             raise ValueError(f"EMA_VFI.forward: two [B,{self.in_channels},H,W] tensors expected, got "
                              f"{tuple(frame1.shape)} and {tuple(frame2.shape)}")
@@ -458,6 +486,9 @@ class EMA_VFI(nn.Module):
         B, C, H, W = f1.shape
         L = _lib.load()
         packed = self.packed_weights(dt, dev)
+        if ensemble is not None:
+            out = self._forward_ensemble(L, packed, f1, f2, dt, ensemble, _events)
+            return out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
         out = torch.empty_like(f1)
         taps_arg, taps = None, None
         if return_taps:
@@ -469,6 +500,19 @@ class EMA_VFI(nn.Module):
                 taps[f"fused_{i}"] = torch.empty(B, m + 3, H, W, device=dev)
                 ptrs.append(taps[f"fused_{i}"].data_ptr())
             taps_arg = cast((c_void_p * len(ptrs))(*ptrs), POINTER(c_void_p))
+        self._forward_f32(L, packed, f1, f2, out, dt, taps_arg, _events)
+        # under autocast the reference's reconstruction tail is fp16, so its frame is an fp16 tensor (the values computed
+        # here are fp16-representable: the conversion is exact)
+        out = out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
+        if return_taps:
+            taps["out"] = out
+            return out, taps
+        return out
+
+    def _forward_f32(self, L, packed, f1, f2, out, dt, taps_arg=None, _events=None):
+        """F(f1, f2) of the ensemble definition: the plain forward of two checked fp32 contiguous batches into the fp32 `out`, as one
+        sequence of launches or pipelined over two streams"""
+        B, C, H, W = f1.shape
         pieces = min(int(self.pipeline), B)
         if (C * H * W) % 4 != 0:
             pieces = 1   # a slice of the batch must start 16-byte aligned (include/emavfi.h): odd sample sizes run as one sequence
@@ -477,17 +521,27 @@ class EMA_VFI(nn.Module):
             gmask = None
         else:
             gmask = (1 << self.num_blocks) - 1 if self._pack_policy == "gather" else 0
-        if pieces >= 2 and not return_taps and not torch.cuda.is_current_stream_capturing():
+        if pieces >= 2 and taps_arg is None and not torch.cuda.is_current_stream_capturing():
             self._forward_pipelined(L, packed, f1, f2, out, dt, pieces, _events, gmask)
         else:
             self._last_call = self._launch(L, packed, f1, f2, out, dt, gmask, taps_arg, None, _events)
-        # under autocast the reference's reconstruction tail is fp16, so its frame is an fp16 tensor (the values computed
-        # here are fp16-representable: the conversion is exact)
-        out = out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
-        if return_taps:
-            taps["out"] = out
-            return out, taps
-        return out
+
+    def _forward_ensemble(self, L, packed, f1, f2, dt, ensemble, _events=None):
+        """The fp32 ensemble of include/emavfi.h, "ENSEMBLE DEFINITION": its members are plain forwards of the same batch, issued in the
+        definition's member order (under pack_adapt every one of them advances the route state, as the same calls made by hand would).
+        Run one after the other and not as one larger batch: the result is the composition by construction, whatever the kernels do
+        across a batch, and eight 720p batches of 8 would not share a workspace anyway.  `_events` bracket the first member's launches."""
+        flips = (0,) if ensemble == "reverse" else _lib.ENSEMBLE_FLIPS
+        mirrored = {f: (_lib.flip_f32(f1, f), _lib.flip_f32(f2, f)) if f else (f1, f2) for f in flips}
+        members, codes = [], []
+        for reverse in ((False,) if ensemble == "flip" else (False, True)):
+            for f in flips:
+                x1, x2 = mirrored[f][::-1] if reverse else mirrored[f]
+                m = torch.empty_like(f1)
+                self._forward_f32(L, packed, x1, x2, m, dt, None, _events if not members else None)
+                members.append(m)
+                codes.append(f)
+        return _lib.ensemble_mean_f32(members, codes)
 
     def pack_census(self):
         """What the one-launch ModulatedDeformConvPack kernels of the LAST one-sequence forward on the current stream counted while

@@ -110,6 +110,11 @@ against its gap's two kept source frames before ``emavfi_resample_frames`` selec
 its pixels that were held; the counts ride to a small pinned buffer behind the frames and are read after the ``done`` wait the drain already
 performs - no new synchronisation point.  Refused with ``reference_quirks=True`` (exact source pixels pasted into the quirk's de-normalised
 prediction would show as patches) and with ``zero_copy=True``; ``evaluate()`` is unaffected.  All ten pixel formats work.
+``ensemble="reverse" | "flip" | "full"`` (opt-in; not in the reference, which calls the model once per pair) runs EVERY forward the harness
+issues - all three modes, the recursion's inner midpoints, ``evaluate()``, with any of the options above - as the test-time ensemble of
+include/emavfi.h ("ENSEMBLE DEFINITION"; ``EMA_VFI.ensemble``): 2, 4 or 8 plain forwards of the same batch, averaged on the device.  It is
+passed with each call, so the model's own attribute is neither read nor changed; ``None`` (default) leaves the decision to that attribute.
+With "reverse" or "full" every prediction is exactly symmetric in time: the reversed clip yields the reversed predictions, byte for byte.
 """
 from __future__ import annotations
 
@@ -213,6 +218,7 @@ class FrameInterpolator:
     dedup_max_run, dedup_span = 3, 64
     static_guard = None   # the radius of the static-region guard (include/emavfi.h, "STATIC REGION DEFINITION"); None: off
     static_tol = 0        # its tolerance in sample units (lib.static_tolerance_units)
+    ensemble = None       # test-time ensembling of every forward (EMA_VFI.ensemble); None: what the model's attribute says
     _depth = 0   # bits per sample of a 16-bit-word pixel format ("p010": 10, ...); 0 for the byte formats
     _planar = _yuv8 = False
     mode = "reference"
@@ -223,7 +229,7 @@ class FrameInterpolator:
                  scale: Optional[float] = None, size=None, scene_threshold: Optional[float] = None,
                  rate_in=None, rate_out=None, resample_depth: int = 3, resample_method: str = "nearest",
                  dedup_threshold: Optional[float] = None, dedup_max_run: int = 3, dedup_span: int = 64,
-                 static_guard: Optional[int] = None, static_tolerance: float = 0.0):
+                 static_guard: Optional[int] = None, static_tolerance: float = 0.0, ensemble: Optional[str] = None):
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
             raise ValueError("interpolation_factor >= 0, frame_interval >= 1, batch_pairs >= 1 required")
         if mode not in ("reference", "recursive", "resample"):
@@ -251,6 +257,9 @@ class FrameInterpolator:
             raise ValueError("recursive midpoints need interpolation_factor = 2^k - 1 (1, 3, 7, ...)")
         if numa not in ("off", "auto"):
             raise ValueError("numa must be 'off' or 'auto'")
+        if ensemble is not None and (not isinstance(ensemble, str) or ensemble not in _lib.ENSEMBLES):
+            raise ValueError(f"ensemble must be one of {_lib.ENSEMBLES} (None: what the model's attribute says), got {ensemble!r}")
+        self.ensemble = ensemble
         if pixel_format not in ("bgr24", "nv12", *_lib.DEPTHS, *_lib.PLANAR_DEPTHS):
             raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames), 'nv12' (uint8 [H*3/2, W] frames), 'p010' / 'p012' / 'p016' "
                              "(uint16 [H*3/2, W] frames) or planar 'yuv420p8' (uint8) / 'yuv420p10' / 'yuv420p12' / 'yuv420p16' (uint16)")
@@ -835,11 +844,16 @@ class FrameInterpolator:
             return rows if rows.data_ptr() % 16 == 0 else rows.clone()
         return torch.stack([x[i] for i in idx])
 
+    def _forward(self, a, b):
+        """One forward of the model, every mode's and evaluate()'s: under the harness's own `ensemble` where one was given - for this call
+        alone, the model's attribute stays as it is -, else as the model's attribute says."""
+        return self.model(a, b) if self.ensemble is None else self.model(a, b, ensemble=self.ensemble)
+
     def _predict(self, x1, x2):
         """[n, k, 3, H, W] predictions per pair: k = 1 (reference mode) or `factor` recursive midpoints."""
         with torch.no_grad():
             if self.mode == "reference" or self.factor <= 1:
-                return self.model(x1, x2).unsqueeze(1)
+                return self._forward(x1, x2).unsqueeze(1)
             # the model consumes normalised frames and returns [0,1] images: re-normalise midpoints to recurse.
             # The constants are created once: torch.tensor(..., device=) is a synchronous pageable copy, i.e. the host
             # would block behind the forward it has just enqueued and stop staging / draining beside it.
@@ -849,7 +863,7 @@ class FrameInterpolator:
             mean, std = self._norm
 
             def rec(a, b, depth):
-                m = self.model(a, b)
+                m = self._forward(a, b)
                 if depth == 1:
                     return [m]
                 mn = (m - mean) / std
@@ -1071,7 +1085,7 @@ class FrameInterpolator:
                 else:
                     x1 = torch.stack([node(k, j - st) for (k, j), st in zip(items, step)])
                     x2 = torch.stack([node(k, j + st) for (k, j), st in zip(items, step)])
-                m = self.model(x1, x2)
+                m = self._forward(x1, x2)
                 outs.append(m)
                 if l + 1 < len(levels) and levels[l + 1]:
                     mn = (m - mean) / std
@@ -1374,7 +1388,7 @@ class FrameInterpolator:
             main.wait_event(slot["pre"])
             x1, x2 = self._rows(x, ia), self._rows(x, ib)
             with torch.no_grad():
-                pred = self.model(x1, x2)                                     # [n, 3, H, W], on the caller's stream
+                pred = self._forward(x1, x2)                                     # [n, 3, H, W], on the caller's stream
             slot["fwd"].record(main)
             with torch.cuda.stream(self._post):
                 self._post.wait_event(slot["fwd"])
