@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -733,6 +733,54 @@ int emavfi_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst,
 #define EMAVFI_ENSEMBLE_MAX_MEMBERS 8
 int emavfi_flip_f32(const float *src, float *dst, size_t planes, int H, int W, int flip, void *stream);
 int emavfi_ensemble_mean_f32(const float *const *members, const int *flips, int n, float *out, size_t planes, int H, int W, void *stream);
+
+/* Frame borders.  Every operator of the forward takes the outside of the picture as zero: the backward warp is grid_sample with zeros
+ * padding (ema_vfi.py:162-169), the deformable blocks return 0 for a sample at h <= -1 || h >= H, and every convolution zero-pads.  In the
+ * normalised domain zero is the mean grey, so wherever the picture continues past the frame (a pan, an object entering or leaving) the
+ * in-between frames carry a band along the edge that the source frames do not.  The usual remedy of interpolation tools is to extend the
+ * frame past its edge, run the model on the larger frame and crop.  The reference has no such step; this is an addition, off unless asked
+ * for, and no quality claim is made.  The composition lives in the Python layer (EMA_VFI.border); the two entries here are the device work
+ * a C integrator needs beside emavfi_forward_routed.
+ *
+ * BORDER DEFINITION (the one place).  This is the project's own definition: it claims agreement with no outside tool (the two index maps
+ *   happen to be numpy.pad's "edge" and "reflect", which the tests use to check their oracle).
+ *   A border is (N, mode): N pixels added on each of the four sides, N in 0..EMAVFI_BORDER_MAX.
+ *   pad_{N,mode} maps fp32 [planes][H][W] to [planes][H + 2N][W + 2N]:  dst[p][y][x] = src[p][iy(y - N)][ix(x - N)], with the index map
+ *   i -> index in 0..n - 1 of an axis of n samples (n = H for iy, n = W for ix):
+ *     EMAVFI_BORDER_REPLICATE = 0:  min(max(i, 0), n - 1).
+ *     EMAVFI_BORDER_REFLECT = 1 (the edge sample is not repeated):  n == 1: 0.  Otherwise p = 2 (n - 1), m = ((i mod p) + p) mod p, and
+ *       the index is m where m <= n - 1, else p - m.  The periodic form stays defined for N > n - 1 (several reflections).
+ *   crop_N maps [planes][H + 2N][W + 2N] back to [planes][H][W]:  dst[p][y][x] = src[p][y + N][x + N].  Hence crop_N pad_{N,mode} is the
+ *     identity, and N = 0 makes both a copy.
+ *   Both are pure moves of 32-bit words: every bit pattern survives (NaN payloads, -0.0, infinities).
+ *   The bordered forward is crop_N(G(pad a, pad b)), G being the plain forward F of the ENSEMBLE DEFINITION, or the ensemble of it where
+ *     one is set.  Everything is taken in fp32, before the final conversion of the frame (fp16 under EMAVFI_AMP16, the input dtype
+ *     otherwise).  The padded frame is an ordinary frame to the forward: the SIZE LIMITS apply to (H + 2N) x (W + 2N).
+ *   Padding commutes with the four mirrorings, pad(phi_f t) = phi_f pad(t) - both index maps are symmetric under i -> n - 1 - i -, cropping
+ *     likewise, and neither looks at which input it is given.  So a flip of both inputs, or their exchange, reaches the ensemble as the
+ *     same flip or exchange of the padded inputs, and the ensemble's exact symmetry in time and exact flip equivariance carry over to
+ *     the bordered ensemble bit for bit.
+ *
+ * emavfi_border_pad_f32: dst = pad_{N,mode} src.  emavfi_border_crop_f32: dst = crop_N src.  H and W are the size of the PICTURE (the
+ *   unpadded tensor) in both entries: the source of a pad, the destination of a crop.
+ * Both: dense fp32 tensors; every dimension of either tensor in 1..16384 (so H + 2N and W + 2N are bounded as well); planes * H * W is
+ *   addressed with 64 bits (indices inside a plane are 32-bit).  The tensors are device pointers or pinned (device-mapped) host memory.
+ *   Nothing is allocated, nothing synchronises, there is no workspace, all work goes on `stream`; every word of dst is written and
+ *   nothing else is.
+ * EMAVFI_E_ARG (never an abort), the message naming the argument: a null pointer; N outside 0..EMAVFI_BORDER_MAX; a mode other than the
+ *   two above; planes of 0; a dimension of either tensor outside 1..16384; a pointer that is not 4-byte aligned; size arithmetic that
+ *   overflows size_t; dst overlapping src.
+ * Access width: one 16-byte store of 4 consecutive destination columns per lane when the destination's row length % 4 == 0 and dst is
+ *   16-byte aligned; the four values are one 16-byte load where the unit lies wholly inside the picture and src is 16-byte aligned, the
+ *   source's row length % 4 == 0 and N % 4 == 0, and four scalar loads through the index map otherwise (the border columns, the units that
+ *   straddle the picture's edge, a misaligned interior).  Everything else takes a scalar path built from the same per-element functions
+ *   (csrc/border_elem.h).  Both kernels are pure streaming and short-lived: the grid follows the destination's element count, nothing
+ *   waits on anything. */
+#define EMAVFI_BORDER_REPLICATE 0
+#define EMAVFI_BORDER_REFLECT 1
+#define EMAVFI_BORDER_MAX 64
+int emavfi_border_pad_f32(const float *src, float *dst, size_t planes, int H, int W, int N, int mode, void *stream);
+int emavfi_border_crop_f32(const float *src, float *dst, size_t planes, int H, int W, int N, void *stream);
 
 /* Frame metrics on the device: how close is image a (an interpolated frame) to image b (the held-out true frame)?  The reference has no
  * evaluation script (its README names PSNR and SSIM against held-out ground-truth frames as the way to judge a model and calls an eval.py a

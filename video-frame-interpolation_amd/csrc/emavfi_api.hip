@@ -8,6 +8,7 @@
 #include "dedup_elem.h"
 #include "static_elem.h"
 #include "ensemble_elem.h"
+#include "border_elem.h"
 #include "conv_first.inl"
 
 #include <atomic>
@@ -1907,6 +1908,58 @@ int emavfi_ensemble_mean_f32(const float *const *members, const int *flips, int 
         if (o0 < m0 + bytes && m0 < o0 + bytes) return fail(EMAVFI_E_ARG, "%s: out overlaps members[%d]", what, k);
     }
     EMAVFI_TRY(launch_ensemble_mean_f32(members, flips, n, out, planes, H, W, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+// ---- frame borders (include/emavfi.h, "BORDER DEFINITION"): every check runs on the host; H, W are the picture's size in both entries
+static_assert(EMAVFI_BORDER_REPLICATE == BORDER_REPLICATE && EMAVFI_BORDER_REFLECT == BORDER_REFLECT && EMAVFI_BORDER_MAX == BORDER_MAX
+              && EMAVFI_RESIZE_MAX_DIM == BORDER_MAX_DIM, "header and border_elem.h disagree");
+
+// the bytes of the picture [planes][H][W] and of its extension [planes][H + 2N][W + 2N], refused where a size or the arithmetic is out of range
+static int border_shape_check(const char *what, size_t planes, int H, int W, int N, size_t *picture_bytes, size_t *padded_bytes)
+{
+    if (planes < 1) return fail(EMAVFI_E_ARG, "%s: planes must be >= 1", what);
+    if (const int rc = scene_dims_check(what, H, W); rc != EMAVFI_OK) return rc;
+    if (!border_n_ok(N)) return fail(EMAVFI_E_ARG, "%s: N = %d (N must lie in 0..%d: EMAVFI_BORDER_MAX)", what, N, BORDER_MAX);
+    const int Hp = border_padded_dim(H, N), Wp = border_padded_dim(W, N);
+    if (!border_dim_ok(Hp) || !border_dim_ok(Wp))
+        return fail(EMAVFI_E_ARG, "%s: a dimension of the padded tensor (%d x %d: %d x %d with N = %d) is above 16384", what, Hp, Wp, H, W, N);
+    if (__builtin_mul_overflow(planes, (size_t)H * W * sizeof(float), picture_bytes)
+        || __builtin_mul_overflow(planes, (size_t)Hp * Wp * sizeof(float), padded_bytes))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (planes %zu)", what, planes);
+    return EMAVFI_OK;
+}
+
+static int border_overlap_check(const char *what, const void *src, size_t src_bytes, const void *dst, size_t dst_bytes)
+{
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+    if (d0 < s0 + src_bytes && s0 < d0 + dst_bytes) return fail(EMAVFI_E_ARG, "%s: dst overlaps src", what);
+    return EMAVFI_OK;
+}
+
+int emavfi_border_pad_f32(const float *src, float *dst, size_t planes, int H, int W, int N, int mode, void *stream)
+{
+    const char *const what = "border_pad_f32";
+    size_t picture, padded;
+    if (const int rc = border_shape_check(what, planes, H, W, N, &picture, &padded); rc != EMAVFI_OK) return rc;
+    if (!border_mode_ok(mode))
+        return fail(EMAVFI_E_ARG, "%s: mode = %d (mode must be EMAVFI_BORDER_REPLICATE = 0 or EMAVFI_BORDER_REFLECT = 1)", what, mode);
+    if (const int rc = ensemble_pointer_check(what, "src", -1, src, picture); rc != EMAVFI_OK) return rc;
+    if (const int rc = ensemble_pointer_check(what, "dst", -1, dst, padded); rc != EMAVFI_OK) return rc;
+    if (const int rc = border_overlap_check(what, src, picture, dst, padded); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_border_pad_f32(src, dst, planes, H, W, N, mode, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+int emavfi_border_crop_f32(const float *src, float *dst, size_t planes, int H, int W, int N, void *stream)
+{
+    const char *const what = "border_crop_f32";
+    size_t picture, padded;
+    if (const int rc = border_shape_check(what, planes, H, W, N, &picture, &padded); rc != EMAVFI_OK) return rc;
+    if (const int rc = ensemble_pointer_check(what, "src", -1, src, padded); rc != EMAVFI_OK) return rc;
+    if (const int rc = ensemble_pointer_check(what, "dst", -1, dst, picture); rc != EMAVFI_OK) return rc;
+    if (const int rc = border_overlap_check(what, src, padded, dst, picture); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_border_crop_f32(src, dst, planes, H, W, N, (hipStream_t)stream), what);
     return EMAVFI_OK;
 }
 

@@ -133,6 +133,9 @@ int launch_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst,
 // entries, read before the call returns and passed on as kernel arguments
 int launch_flip_f32(const float *src, float *dst, size_t planes, int H, int W, int flip, hipStream_t s);
 int launch_ensemble_mean_f32(const float *const *members, const int *flips, int n, float *out, size_t planes, int H, int W, hipStream_t s);
+// frame borders (include/emavfi.h, "BORDER DEFINITION"): arguments already validated; H, W are the picture's size in both
+int launch_border_pad_f32(const float *src, float *dst, size_t planes, int H, int W, int N, int mode, hipStream_t s);
+int launch_border_crop_f32(const float *src, float *dst, size_t planes, int H, int W, int N, hipStream_t s);
 // frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION"): arguments already validated; `part` holds 2 u64 per (b, c, tile)
 // of frame_metrics_tiles' tx * ty tiles (32 x 32 windows each; one tile where an axis has no window)
 void frame_metrics_tiles(int H, int W, int *tx, int *ty);

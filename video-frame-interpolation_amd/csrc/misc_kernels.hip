@@ -7,6 +7,7 @@
 #include "dedup_elem.h"
 #include "static_elem.h"
 #include "ensemble_elem.h"
+#include "border_elem.h"
 #include "metrics_elem.h"
 #include "p010_elem.h"
 #include "yuv420p_elem.h"
@@ -2925,6 +2926,102 @@ int launch_ensemble_mean_f32(const float *const *members, const int *flips, int 
     case 8: launch_ensemble_mean_n<8>(p, s); break;
     default: return -2;
     }
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Frame borders (include/emavfi.h, "BORDER DEFINITION"; per-element functions: border_elem.h).
+//   border_pad_f32_kernel    dst [planes][H + 2N][W + 2N] = the picture extended by replication or reflection.
+//   border_crop_f32_kernel   dst [planes][H][W] = the middle of the extended picture.
+//                          One body, two directions: every destination word is one source word, found by border_src_index().  Both in
+//                          the mould of flip_f32_kernel: grid (pieces of a DESTINATION plane, planes - at most 65535 rows of the grid, a
+//                          workgroup walks the planes beyond), 256 threads, pure streaming: no LDS, no atomics, nothing waits on anything.
+//                          A lane owns 4 units of one plane, 256 units apart, and issues the loads of all of them before the first
+//                          store.  Wide form (the destination's row length % 4 == 0 and dst 16-byte aligned, so every plane and row of it
+//                          starts on a unit): a unit is 4 destination columns, one 16-byte store.  Its four values come as ONE 16-byte
+//                          load where they are four consecutive source columns (the unit lies wholly inside the picture; always for a
+//                          crop) and `vec` holds: src 16-byte aligned, the source's row length % 4 == 0 and N % 4 == 0, which together
+//                          put every such unit on a 16-byte boundary of the source.  Otherwise - the border columns, the units that
+//                          straddle the picture's edge, a misaligned interior - four scalar loads through the index map.  Scalar form:
+//                          a unit is one element.  Plane offsets are 64-bit, indices inside a plane (at most 2^28 elements) 32-bit.
+// ------------------------------------------------------------------------------------------
+struct BorderArgs {
+    const float *src;
+    float *dst;
+    size_t planes, src_plane, dst_plane;   // elements per plane
+    int Hs, Ws, Hd, Wd, N, mode, vec;
+};
+
+template <bool CROP, bool WIDE>
+__device__ __forceinline__ void border_body(const BorderArgs &p)
+{
+    constexpr int U = 4;
+    using T = std::conditional_t<WIDE, float4, float>;
+    const unsigned Wu = (unsigned)(WIDE ? p.Wd >> 2 : p.Wd), units = (unsigned)p.Hd * Wu;
+    const unsigned u0 = blockIdx.x * (256u * U) + threadIdx.x;
+    for (size_t pl = blockIdx.y; pl < p.planes; pl += gridDim.y) {
+        const float *const s = p.src + pl * p.src_plane;
+        T v[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const unsigned u = u0 + 256u * k;
+            if (u >= units) continue;
+            const int y = (int)(u / Wu), q = (int)(u - (unsigned)y * Wu);
+            if constexpr (WIDE) {
+                const int x = 4 * q;
+                int sx0;
+                if (border_unit_inside(x, p.Ws, p.N, CROP, &sx0) && p.vec) {
+                    v[k] = *reinterpret_cast<const float4 *>(s + border_src_index(y, x, p.Hs, p.Ws, p.N, p.mode, CROP));
+                } else {
+                    v[k] = make_float4(s[border_src_index(y, x, p.Hs, p.Ws, p.N, p.mode, CROP)], s[border_src_index(y, x + 1, p.Hs, p.Ws, p.N, p.mode, CROP)],
+                                       s[border_src_index(y, x + 2, p.Hs, p.Ws, p.N, p.mode, CROP)], s[border_src_index(y, x + 3, p.Hs, p.Ws, p.N, p.mode, CROP)]);
+                }
+            } else {
+                v[k] = s[border_src_index(y, q, p.Hs, p.Ws, p.N, p.mode, CROP)];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const unsigned u = u0 + 256u * k;
+            if (u >= units) continue;
+            reinterpret_cast<T *>(p.dst + pl * p.dst_plane)[u] = v[k];
+        }
+    }
+}
+
+template <bool WIDE> __global__ __launch_bounds__(256) void border_pad_f32_kernel(BorderArgs p) { border_body<false, WIDE>(p); }
+template <bool WIDE> __global__ __launch_bounds__(256) void border_crop_f32_kernel(BorderArgs p) { border_body<true, WIDE>(p); }
+
+// the access widths of a call and its grid: the wide form needs dst alone aligned, the 16-byte loads src as well
+static dim3 border_plan(BorderArgs &p, bool *wide)
+{
+    *wide = (((uintptr_t)p.dst | (uintptr_t)(p.Wd & 3)) & 15) == 0;
+    p.vec = *wide && (((uintptr_t)p.src | (uintptr_t)(p.Ws & 3) | (uintptr_t)(p.N & 3)) & 15) == 0;
+    const size_t units = (size_t)p.Hd * (size_t)(*wide ? p.Wd >> 2 : p.Wd), per_wg = 256u * 4u;   // units <= 2^28
+    return dim3((unsigned)((units + per_wg - 1) / per_wg), (unsigned)(p.planes < 65535 ? p.planes : 65535));
+}
+
+int launch_border_pad_f32(const float *src, float *dst, size_t planes, int H, int W, int N, int mode, hipStream_t s)
+{
+    BorderArgs p{};
+    p.src = src; p.dst = dst; p.planes = planes; p.Hs = H; p.Ws = W; p.Hd = border_padded_dim(H, N); p.Wd = border_padded_dim(W, N);
+    p.src_plane = (size_t)p.Hs * p.Ws; p.dst_plane = (size_t)p.Hd * p.Wd; p.N = N; p.mode = mode;
+    bool wide;
+    const dim3 grid = border_plan(p, &wide);
+    if (wide) border_pad_f32_kernel<true><<<grid, 256, 0, s>>>(p);
+    else border_pad_f32_kernel<false><<<grid, 256, 0, s>>>(p);
+    return (int)hipGetLastError();
+}
+
+int launch_border_crop_f32(const float *src, float *dst, size_t planes, int H, int W, int N, hipStream_t s)
+{
+    BorderArgs p{};
+    p.src = src; p.dst = dst; p.planes = planes; p.Hs = border_padded_dim(H, N); p.Ws = border_padded_dim(W, N); p.Hd = H; p.Wd = W;
+    p.src_plane = (size_t)p.Hs * p.Ws; p.dst_plane = (size_t)p.Hd * p.Wd; p.N = N; p.mode = BORDER_REPLICATE;
+    bool wide;
+    const dim3 grid = border_plan(p, &wide);
+    if (wide) border_crop_f32_kernel<true><<<grid, 256, 0, s>>>(p);
+    else border_crop_f32_kernel<false><<<grid, 256, 0, s>>>(p);
     return (int)hipGetLastError();
 }
 

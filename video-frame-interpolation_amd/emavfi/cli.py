@@ -74,6 +74,12 @@ def parser() -> argparse.ArgumentParser:
                    help="test-time ensembling of every forward: the pair and the reversed pair (reverse: 2 forwards, symmetric in time), the "
                         "pair under the four mirrorings (flip: 4 forwards, equivariant under flips) or both (full: 8 forwards); no quality "
                         "claim is made, --evaluate tells what it buys on a clip")
+    p.add_argument("--border", type=int, default=None, metavar="N",
+                   help="extend every frame by N pixels (1..64) past each edge before every forward and crop the prediction back: the model "
+                        "takes the outside of the picture as mean grey, which shows as an edge band in the in-between frames wherever the "
+                        "picture continues past the frame; no quality claim is made, --evaluate tells what it buys on a clip")
+    p.add_argument("--border-mode", choices=("replicate", "reflect"), default=None,
+                   help="with --border: repeat the edge pixel (replicate, the default) or mirror the picture about it (reflect)")
     p.add_argument("--batch-pairs", type=int, default=8)
     p.add_argument("--chunk-pairs", type=int, default=64, help="frame pairs per chunk: at most chunk_pairs * frame_interval + 1 source frames are held")
     p.add_argument("--yuv-standard", default="bt601", help="bt601, bt709 or (10 / 12 / 16-bit streams) bt2020")
@@ -112,6 +118,10 @@ def _run(args) -> int:
         raise ValueError("--static-tolerance FRACTION: a fraction of full scale in 0..1")
     if args.dedup_max_run is not None and args.dedup is None:
         raise ValueError("--dedup-max-run needs --dedup FRACTION")
+    if args.border_mode is not None and args.border is None:
+        raise ValueError("--border-mode needs --border N")
+    if args.border is not None and not 1 <= args.border <= 64:
+        raise ValueError("--border N: the border must lie in 1..64")
     mode = "resample" if resample else (args.mode or "reference")
     with y4m.Y4MReader(args.input) as reader:
         head = reader.header
@@ -144,7 +154,8 @@ def _run(args) -> int:
                                   if args.dedup is not None else {}),
                                **(dict(static_guard=args.static_guard, static_tolerance=args.static_tolerance or 0.0)
                                   if args.static_guard is not None else {}),
-                               ensemble=args.ensemble)
+                               ensemble=args.ensemble,
+                               **(dict(border=args.border, border_mode=args.border_mode or "replicate") if args.border is not None else {}))
         if args.evaluate:
             print(fi.evaluate(list(reader), every=args.every))      # evaluate() indexes the clip: all of it is held
             return 0
@@ -161,7 +172,8 @@ def _run(args) -> int:
                   + (f", {len(fi.duplicates)} duplicate frames dropped" if args.dedup is not None else "")
                   + (f", static guard held {100.0 * sum(fi.static_share) / max(len(fi.static_share), 1):.2f} % of the predictions' pixels on average"
                      if args.static_guard is not None else "")
-                  + (f", ensemble {args.ensemble}" if args.ensemble is not None else ""), file=sys.stderr)
+                  + (f", ensemble {args.ensemble}" if args.ensemble is not None else "")
+                  + (f", border {args.border} {args.border_mode or 'replicate'}" if args.border is not None else ""), file=sys.stderr)
     return 0
 
 

@@ -72,6 +72,8 @@ _PROTOTYPES = {
                                    + [ctypes.c_uint, c_void_p, c_void_p]),
     "emavfi_flip_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "emavfi_ensemble_mean_f32": (c_int, [POINTER(c_void_p), POINTER(c_int), c_int, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "emavfi_border_pad_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
+    "emavfi_border_crop_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "emavfi_frame_metrics_workspace_bytes": (c_size_t, [c_int] * 4),
     "emavfi_frame_metrics_u8": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 4
                                 + [c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -1347,6 +1349,82 @@ def ensemble_mean_f32(members, flips, out=None):
     with torch.cuda.device(dev):
         check(load().emavfi_ensemble_mean_f32(ctypes.cast(ptrs, POINTER(c_void_p)), ctypes.cast(codes, POINTER(c_int)), n, out.data_ptr(),
                                               planes, H, W, _stream()), "emavfi_ensemble_mean_f32")
+    return out
+
+
+# ---------------------------------------------------------------- frame borders (include/emavfi.h, "BORDER DEFINITION")
+BORDER_REPLICATE, BORDER_REFLECT = 0, 1          # EMAVFI_BORDER_REPLICATE, EMAVFI_BORDER_REFLECT
+BORDER_MODES = ("replicate", "reflect")          # by code
+BORDER_MAX = 64                                  # EMAVFI_BORDER_MAX
+
+
+def _border_n(N, what, least=0):
+    if isinstance(N, bool) or not isinstance(N, int) or not least <= N <= BORDER_MAX:
+        raise ValueError(f"{what}: the border N must be an int in {least}..{BORDER_MAX}, got {N!r}")
+    return N
+
+
+def _border_mode(mode, what):
+    """the code of a mode given by name or by code"""
+    if isinstance(mode, str) and mode in BORDER_MODES:
+        return BORDER_MODES.index(mode)
+    if not isinstance(mode, bool) and isinstance(mode, int) and 0 <= mode < len(BORDER_MODES):
+        return mode
+    raise ValueError(f"{what}: the border mode must be one of {BORDER_MODES}, got {mode!r}")
+
+
+def border_padded_size(H, W, N):
+    """(H + 2 N, W + 2 N): the size of an H x W picture extended by N pixels on each side.  Pure; refuses an N outside 0..BORDER_MAX and
+    any dimension of either size outside 1..16384, as the entries do."""
+    H, W, N = int(H), int(W), _border_n(N, "border_padded_size")
+    Hp, Wp = H + 2 * N, W + 2 * N
+    if not (1 <= H and 1 <= W and Hp <= RESIZE_MAX_DIM and Wp <= RESIZE_MAX_DIM):
+        raise ValueError(f"border_padded_size: {H} x {W} with a border of {N} ({Hp} x {Wp} padded): every dimension must lie in 1..{RESIZE_MAX_DIM}")
+    return Hp, Wp
+
+
+def _border_out(x, out, shape, what):
+    import torch
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=x.device if x.is_cuda else "cuda")
+    _ensemble_planes(out, f"{what}(out)")
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{what}: out {tuple(out.shape)} is not of the shape {tuple(shape)} that x {tuple(x.shape)} gives")
+    return out
+
+
+def border_pad_f32(x, N, mode="replicate", out=None):
+    """out = x extended by N pixels on each side of its last two dimensions (the border definition of include/emavfi.h): mode "replicate"
+    repeats the edge sample, "reflect" mirrors about it without repeating it (several reflections where N > size - 1).  `x`: contiguous
+    float32 [..., H, W]; `out`: the same with [H + 2 N, W + 2 N]; device tensors or pinned host memory, not overlapping.  N = 0 is a copy.
+    Runs on the current stream; returns `out`."""
+    import torch
+    what = "border_pad_f32"
+    planes, H, W = _ensemble_planes(x, f"{what}(x)")
+    N, code = _border_n(N, what), _border_mode(mode, what)
+    out = _border_out(x, out, tuple(x.shape[:-2]) + border_padded_size(H, W, N), what)
+    dev = next((t.device for t in (x, out) if t.is_cuda), None) or torch.device("cuda")
+    with torch.cuda.device(dev):
+        check(load().emavfi_border_pad_f32(x.data_ptr(), out.data_ptr(), planes, H, W, N, code, _stream()), "emavfi_border_pad_f32")
+    return out
+
+
+def border_crop_f32(x, N, out=None):
+    """out = x without the N pixels on each side of its last two dimensions: the inverse of border_pad_f32 in either mode.  `x`: contiguous
+    float32 [..., H + 2 N, W + 2 N]; `out`: the same with [H, W]; device tensors or pinned host memory, not overlapping.  Runs on the
+    current stream; returns `out`."""
+    import torch
+    what = "border_crop_f32"
+    planes, Hp, Wp = _ensemble_planes(x, f"{what}(x)")
+    N = _border_n(N, what)
+    H, W = Hp - 2 * N, Wp - 2 * N
+    if H < 1 or W < 1:
+        raise ValueError(f"{what}: x {tuple(x.shape)} has nothing inside a border of {N}")
+    border_padded_size(H, W, N)
+    out = _border_out(x, out, tuple(x.shape[:-2]) + (H, W), what)
+    dev = next((t.device for t in (x, out) if t.is_cuda), None) or torch.device("cuda")
+    with torch.cuda.device(dev):
+        check(load().emavfi_border_crop_f32(x.data_ptr(), out.data_ptr(), planes, H, W, N, _stream()), "emavfi_border_crop_f32")
     return out
 
 

@@ -41,6 +41,9 @@ PACK_ADAPT_DEFAULT = (0.75, 0.65)
 # EMA_VFI.ensemble ("Ensembling"; include/emavfi.h, "ENSEMBLE DEFINITION")
 ENSEMBLES = _lib.ENSEMBLES
 _MODEL_ENSEMBLE = object()   # forward(ensemble=): "what the model's attribute says"
+# EMA_VFI.border ("Frame borders"; include/emavfi.h, "BORDER DEFINITION")
+BORDER_MODES, BORDER_MAX = _lib.BORDER_MODES, _lib.BORDER_MAX
+_MODEL_BORDER = object()     # forward(border=): "what the model's attribute says"
 
 
 class _LastCall(NamedTuple):
@@ -175,6 +178,7 @@ class EMA_VFI(nn.Module):
         self.pack_policy = os.environ.get("EMAVFI_PACK_POLICY", "window")
         self.pack_adapt = os.environ.get("EMAVFI_PACK_ADAPT")
         self.ensemble = None
+        self.border = None
         m = mid_channels
         self.feat_ext_conv1 = conv_block(in_channels * 2, m)
         self.feat_ext_blocks = nn.Sequential(OrderedDict(
@@ -409,6 +413,45 @@ class EMA_VFI(nn.Module):
             raise ValueError(f"EMA_VFI.ensemble must be one of {ENSEMBLES}, got {value!r}")
         return value
 
+    @property
+    def border(self):
+        """Frames extended past their edges for forward() ("Frame borders"; include/emavfi.h, "BORDER DEFINITION"): None
+        (default: the plain forward, every launch and byte as without the attribute), an int N in 1..64 (N pixels of replicated edge on
+        each side) or (N, "replicate" | "reflect"); read back as None or the pair (N, mode).  Both inputs are padded on the device
+        (emavfi_border_pad_f32), the plain or ensembled forward runs on the (H + 2N) x (W + 2N) batch, and the fp32 result is cropped
+        (emavfi_border_crop_f32) before it is converted; no host synchronisation is added."""
+        return self._border
+
+    @border.setter
+    def border(self, value):
+        self._border = self._check_border(value)
+
+    @staticmethod
+    def _check_border(value):
+        """None or (N, mode name) of a border given as None, N or (N, mode)"""
+        if value is None:
+            return None
+        N, mode = value if isinstance(value, tuple) and len(value) == 2 else (value, BORDER_MODES[0])
+        if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N <= BORDER_MAX or not isinstance(mode, str) or mode not in BORDER_MODES:
+            raise ValueError(f"EMA_VFI.border must be None, an int N in 1..{BORDER_MAX} or (N, mode) with mode one of {BORDER_MODES}, got {value!r}")
+        return N, mode
+
+    def _check_border_size(self, B, H, W, border, dt):
+        """(H + 2N, W + 2N), or a refusal from the shapes alone where the padded batch is beyond what the forward admits (include/emavfi.h,
+        SIZE LIMITS: B*H*W < 2^31, H*W < 2^24, the fusion plane < 4 GiB) - before anything is launched"""
+        N, mode = border
+        Hp, Wp = H + 2 * N, W + 2 * N
+        fpad = (self.mid_channels + 3 + 15) // 16 * 16
+        widest = 2 if dt in (_lib.BF16, _lib.F16) else 4
+        why = (f"a dimension is above {_lib.RESIZE_MAX_DIM}" if max(Hp, Wp) > _lib.RESIZE_MAX_DIM else
+               "H*W must be < 2^24" if Hp * Wp >= 1 << 24 else
+               "B*H*W must be < 2^31" if B * Hp * Wp >= 1 << 31 else
+               "one sample's activation plane must be < 4 GiB" if Hp * Wp * fpad * widest >= 1 << 32 else None)
+        if why is not None:
+            raise ValueError(f"EMA_VFI.forward: border ({N}, {mode!r}) extends the {H} x {W} frames to {Hp} x {Wp}, beyond the forward's "
+                             f"size limits ({why})")
+        return Hp, Wp
+
     def _start_mask(self):
         return (1 << self.num_blocks) - 1 if self._pack_policy == "gather" else 0
 
@@ -460,10 +503,13 @@ class EMA_VFI(nn.Module):
                 for i in range(self.num_blocks)]
 
     # ------------------------------------------------------------------ forward
-    def forward(self, frame1, frame2, return_taps=False, _events=None, ensemble=_MODEL_ENSEMBLE):
+    def forward(self, frame1, frame2, return_taps=False, _events=None, ensemble=_MODEL_ENSEMBLE, border=_MODEL_BORDER):
         """ema_vfi.py:110-147.  `ensemble`: one of ENSEMBLES for this call alone (FrameInterpolator passes its own); by default the
-        model's attribute decides."""
+        model's attribute decides.  `border`: None, N or (N, mode) for this call alone, likewise."""
         ensemble = self._ensemble if ensemble is _MODEL_ENSEMBLE else self._check_ensemble(ensemble)
+        border = self._border if border is _MODEL_BORDER else self._check_border(border)
+        if border is not None and return_taps:
+            raise ValueError("EMA_VFI.forward: return_taps=True with a border: the taps belong to the padded forward (set border=None)")
         if ensemble is not None and return_taps:
             raise ValueError("EMA_VFI.forward: return_taps=True with an ensemble: the taps belong to one forward (set ensemble=None)")
         if frame1.shape != frame2.shape or frame1.dim() != 4 or frame1.shape[1] != self.in_channels:
@@ -485,7 +531,19 @@ class EMA_VFI(nn.Module):
         f1, f2 = _lib._f32c(frame1), _lib._f32c(frame2)
         B, C, H, W = f1.shape
         L = _lib.load()
+        if border is not None:
+            self._check_border_size(B, H, W, border, dt)
         packed = self.packed_weights(dt, dev)
+        if border is not None:
+            # crop_N(G(pad a, pad b)) of the border definition: G sees an ordinary (H + 2N) x (W + 2N) batch
+            f1, f2 = (_lib.border_pad_f32(f, *border) for f in (f1, f2))
+            if ensemble is not None:
+                out = self._forward_ensemble(L, packed, f1, f2, dt, ensemble, _events)
+            else:
+                out = torch.empty_like(f1)
+                self._forward_f32(L, packed, f1, f2, out, dt, None, _events)
+            out = _lib.border_crop_f32(out, border[0])
+            return out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
         if ensemble is not None:
             out = self._forward_ensemble(L, packed, f1, f2, dt, ensemble, _events)
             return out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)

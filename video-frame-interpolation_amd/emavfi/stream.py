@@ -115,6 +115,13 @@ issues - all three modes, the recursion's inner midpoints, ``evaluate()``, with 
 include/emavfi.h ("ENSEMBLE DEFINITION"; ``EMA_VFI.ensemble``): 2, 4 or 8 plain forwards of the same batch, averaged on the device.  It is
 passed with each call, so the model's own attribute is neither read nor changed; ``None`` (default) leaves the decision to that attribute.
 With "reverse" or "full" every prediction is exactly symmetric in time: the reversed clip yields the reversed predictions, byte for byte.
+``border=N`` with ``border_mode="replicate" | "reflect"`` (opt-in; not in the reference) runs EVERY forward the harness issues - all three
+modes, the recursion's inner midpoints, ``evaluate()``, with any of the options above, the ensemble included - on frames extended by N
+pixels past each edge and crops the prediction back (include/emavfi.h, "BORDER DEFINITION"; ``EMA_VFI.border``): the forward takes the outside
+of the picture as zero, which is mean grey after normalisation, so the in-between frames carry an edge band where the picture continues past
+the frame.  Like ``ensemble`` it is passed with each call: the model's own attribute is neither read nor changed, ``None`` (default) leaves the
+decision to that attribute.  Everything behind the model - the post kernels, the static guard, scene holds, the resample assembly, the
+metrics - works on the cropped frames and is untouched.
 """
 from __future__ import annotations
 
@@ -219,6 +226,7 @@ class FrameInterpolator:
     static_guard = None   # the radius of the static-region guard (include/emavfi.h, "STATIC REGION DEFINITION"); None: off
     static_tol = 0        # its tolerance in sample units (lib.static_tolerance_units)
     ensemble = None       # test-time ensembling of every forward (EMA_VFI.ensemble); None: what the model's attribute says
+    border = None         # (N, mode) of the frame border of every forward (EMA_VFI.border); None: what the model's attribute says
     _depth = 0   # bits per sample of a 16-bit-word pixel format ("p010": 10, ...); 0 for the byte formats
     _planar = _yuv8 = False
     mode = "reference"
@@ -229,7 +237,8 @@ class FrameInterpolator:
                  scale: Optional[float] = None, size=None, scene_threshold: Optional[float] = None,
                  rate_in=None, rate_out=None, resample_depth: int = 3, resample_method: str = "nearest",
                  dedup_threshold: Optional[float] = None, dedup_max_run: int = 3, dedup_span: int = 64,
-                 static_guard: Optional[int] = None, static_tolerance: float = 0.0, ensemble: Optional[str] = None):
+                 static_guard: Optional[int] = None, static_tolerance: float = 0.0, ensemble: Optional[str] = None,
+                 border: Optional[int] = None, border_mode: str = "replicate"):
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
             raise ValueError("interpolation_factor >= 0, frame_interval >= 1, batch_pairs >= 1 required")
         if mode not in ("reference", "recursive", "resample"):
@@ -260,6 +269,15 @@ class FrameInterpolator:
         if ensemble is not None and (not isinstance(ensemble, str) or ensemble not in _lib.ENSEMBLES):
             raise ValueError(f"ensemble must be one of {_lib.ENSEMBLES} (None: what the model's attribute says), got {ensemble!r}")
         self.ensemble = ensemble
+        if not isinstance(border_mode, str) or border_mode not in _lib.BORDER_MODES:
+            raise ValueError(f"border_mode must be one of {_lib.BORDER_MODES}, got {border_mode!r}")
+        if border is None and border_mode != _lib.BORDER_MODES[0]:
+            raise ValueError(f"border_mode={border_mode!r} needs a border (border=N, 1..{_lib.BORDER_MAX})")
+        if border is not None and (isinstance(border, bool) or not isinstance(border, int) or not 1 <= border <= _lib.BORDER_MAX):
+            raise ValueError(f"border must be an int in 1..{_lib.BORDER_MAX} (None: what the model's attribute says), got {border!r}")
+        self.border = None if border is None else (border, border_mode)
+        # what rides on every forward: only what was given here, so that a model without these arguments still serves a plain harness
+        self._forward_kw = {**({"ensemble": ensemble} if ensemble is not None else {}), **({"border": self.border} if border is not None else {})}
         if pixel_format not in ("bgr24", "nv12", *_lib.DEPTHS, *_lib.PLANAR_DEPTHS):
             raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames), 'nv12' (uint8 [H*3/2, W] frames), 'p010' / 'p012' / 'p016' "
                              "(uint16 [H*3/2, W] frames) or planar 'yuv420p8' (uint8) / 'yuv420p10' / 'yuv420p12' / 'yuv420p16' (uint16)")
@@ -845,9 +863,9 @@ class FrameInterpolator:
         return torch.stack([x[i] for i in idx])
 
     def _forward(self, a, b):
-        """One forward of the model, every mode's and evaluate()'s: under the harness's own `ensemble` where one was given - for this call
-        alone, the model's attribute stays as it is -, else as the model's attribute says."""
-        return self.model(a, b) if self.ensemble is None else self.model(a, b, ensemble=self.ensemble)
+        """One forward of the model, every mode's and evaluate()'s: under the harness's own `ensemble` and `border` where given - for this
+        call alone, the model's attributes stay as they are -, else as the model's attributes say."""
+        return self.model(a, b, **self._forward_kw)
 
     def _predict(self, x1, x2):
         """[n, k, 3, H, W] predictions per pair: k = 1 (reference mode) or `factor` recursive midpoints."""
