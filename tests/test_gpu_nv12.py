@@ -1,6 +1,7 @@
 """NV12 frames on the GPU: emavfi_preprocess_nv12 / emavfi_postprocess_nv12 and the harness's pixel_format="nv12" against the numpy
 restatement of the colour definition (tests/nv12_oracle.py) composed with the u8 kernels they are defined by.  Every comparison is
 bit-exact."""
+import ctypes
 import itertools
 
 import numpy as np
@@ -13,7 +14,8 @@ import nv12_oracle as oracle
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(2, 2), (1, 1), (3, 5), (6, 10), (23, 37), (24, 40), (32, 30), (32, 32), (32, 34), (46, 66), (45, 67)]
-LAYOUTS = ["dense", "pad16", "odd", "bstride", "offset2"]
+LAYOUTS = ["dense", "pad16", "odd", "bstride", "offset2", "b1stride"]
+B1STRIDE = ((5, 36), 1)   # "b1stride" is this one case: two 16-column blocks, a 4-column remainder and an odd bottom row of one frame
 COLOURS = [(s, f, o) for (s, f) in oracle.STANDARDS for o in ("bgr", "rgb")]
 FILL = 0xFF
 GUARD = 64          # floats in front of and behind an fp32 result
@@ -35,11 +37,12 @@ def geometry(layout, H, W):
             off, pitch = 0, up(rowbytes, 16) + 16
         elif layout == "odd":                    # W + 3 rounded up to even: scalar path, a misaligned second row
             off, pitch = 0, up(W + 3, 2)
-        elif layout == "bstride":
+        elif layout in ("bstride", "b1stride"):
             off, pitch = 0, up(rowbytes, 16)
         else:                                    # "offset2": 2 bytes past a 16-byte boundary, aligned pitch
             off, pitch = 2, up(rowbytes, 16)
-        bstride = pitch * rows + (pitch * 3 + 32 if layout == "bstride" else 0)
+        # "b1stride": everything 16-byte aligned but the batch stride, legal and never used at B == 1 - the 16-byte accesses must be taken
+        bstride = pitch * rows + (pitch * 3 + 32 if layout == "bstride" else 2 if layout == "b1stride" else 0)
         out.append((off, pitch, bstride))
     return out
 
@@ -59,6 +62,16 @@ def planes(layout, B, H, W):
     return yraw, y, uvraw, uv
 
 
+def cases(layout, batches):
+    return [B1STRIDE] if layout == "b1stride" else itertools.product(SHAPES, batches)
+
+
+def entry_args(y, uv, colour):
+    """the C entries' plane and colour arguments with the views' own batch strides: lib's wrappers pass the dense value at B == 1"""
+    standard, full, order = colour
+    return (y.data_ptr(), y.stride(1), y.stride(0), uv.data_ptr(), uv.stride(1), uv.stride(0)), (lib.yuv_standard_code(standard, full), lib._order_code(order))
+
+
 def guarded_out(B, H, W):
     flat = torch.full((B * 3 * H * W + 2 * GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
     return flat, flat[GUARD:GUARD + B * 3 * H * W].view(B, 3, H, W)
@@ -71,7 +84,13 @@ def check_decode(ynp, uvnp, layout, colour):
     y.copy_(torch.from_numpy(ynp))
     uv.copy_(torch.from_numpy(uvnp))
     flat, out = guarded_out(B, H, W)
-    got = lib.preprocess_nv12(y, uv, standard, full, order, out=out)
+    if layout == "b1stride":
+        pl, codes = entry_args(y, uv, colour)
+        assert y.stride(0) % 16 == 2 and lib.load().emavfi_preprocess_nv12(*pl, out.data_ptr(), B, H, W, *codes, *lib._stats(lib.IMAGENET_MEAN, lib.IMAGENET_STD, 3),
+                                                                           lib._stream()) == 0, lib.last_error()
+        got = out
+    else:
+        got = lib.preprocess_nv12(y, uv, standard, full, order, out=out)
     want = lib.preprocess_u8(torch.from_numpy(oracle.decode(ynp, uvnp, standard, full, order)).cuda())
     assert got.data_ptr() == out.data_ptr()
     assert torch.equal(got.view(torch.int32), want.view(torch.int32)), (layout, colour, (B, H, W))
@@ -95,7 +114,7 @@ def test_decode_every_chroma_pair_and_the_luma_edges(standard, full, order):
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_decode_shapes_pitches_and_paths(layout):
     rng = np.random.default_rng(11)
-    for n, ((H, W), B) in enumerate(itertools.product(SHAPES, (1, 3))):
+    for n, ((H, W), B) in enumerate(cases(layout, (1, 3))):
         y = rng.integers(0, 256, (B, H, W), dtype=np.uint8)
         uv = rng.integers(0, 256, (B, (H + 1) // 2, (W + 1) // 2, 2), dtype=np.uint8)
         check_decode(y, uv, layout, COLOURS[n % len(COLOURS)])
@@ -133,7 +152,13 @@ def check_encode(x, layout, colour, denorm):
     standard, full, order = colour
     B, _, H, W = x.shape
     yraw, y, uvraw, uv = planes(layout, B, H, W)
-    lib.postprocess_nv12(x, standard, full, order, denormalize=bool(denorm), out=(y, uv))
+    if layout == "b1stride":
+        pl, codes = entry_args(y, uv, colour)
+        assert uv.stride(0) % 16 == 2 and lib.load().emavfi_postprocess_nv12(x.data_ptr(), *pl, B, H, W, *codes,
+                                                                             *lib._stats(lib.IMAGENET_MEAN, lib.IMAGENET_STD, 3, ctypes.c_double), denorm,
+                                                                             lib._stream()) == 0, lib.last_error()
+    else:
+        lib.postprocess_nv12(x, standard, full, order, denormalize=bool(denorm), out=(y, uv))
     u8 = lib.postprocess_u8(x, denormalize=bool(denorm)).cpu().numpy()
     ywant, uvwant = oracle.encode(u8, standard, full, order)
     # expected images of the two raw buffers: the planes where they belong, FILL everywhere else (pitch padding, slack, the front offset)
@@ -149,7 +174,7 @@ def check_encode(x, layout, colour, denorm):
 @pytest.mark.parametrize("denorm", [0, 1])
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_encode_shapes_pitches_and_paths(layout, denorm):
-    for n, ((H, W), B) in enumerate(itertools.product(SHAPES, (1, 3))):
+    for n, ((H, W), B) in enumerate(cases(layout, (1, 3))):
         check_encode(encode_input(B, H, W, denorm, seed=100 + n), layout, COLOURS[(n + 3 * denorm) % len(COLOURS)], denorm)
 
 

@@ -1,6 +1,7 @@
 """High-bit-depth frames on the GPU: emavfi_preprocess_p010 / emavfi_postprocess_p010 and the harness's pixel_format="p010" / "p012" / "p016"
 against the numpy restatement of the definition (tests/p010_oracle.py).  Every comparison is equality: fp32 results bit for bit, planes
 word for word, padding byte for byte."""
+import ctypes
 import itertools
 
 import numpy as np
@@ -15,7 +16,8 @@ pytestmark = pytest.mark.gpu
 
 # tests/test_gpu_nv12.py's LAYOUTS with the block width halved: 1x1, odd, one fast block, fast blocks, fast blocks + remainder, odd + remainder
 SHAPES = [(1, 1), (3, 5), (2, 8), (4, 24), (6, 26), (7, 9)]
-LAYOUTS = ["dense", "pad16", "odd", "bstride", "offset2"]
+LAYOUTS = ["dense", "pad16", "odd", "bstride", "offset2", "b1stride"]
+B1STRIDE = ((5, 36), 1)   # "b1stride" is this one case: four 8-column blocks, a 4-column remainder and an odd bottom row of one frame
 COLOURS = [(d, s, f, o) for d in oracle.DEPTHS for (s, f) in oracle.STANDARDS for o in ("bgr", "rgb")]
 FILL = 0xA5
 GUARD = 64          # floats in front of and behind an fp32 result
@@ -37,11 +39,12 @@ def geometry(layout, H, W):
             off, pitch = 0, up(rowbytes, 16) + 16
         elif layout == "odd":                    # larger than the row and no multiple of 16: scalar path, rows at every legal misalignment
             off, pitch = 0, rowbytes + 3 * align
-        elif layout == "bstride":
+        elif layout in ("bstride", "b1stride"):
             off, pitch = 0, up(rowbytes, 16)
         else:                                    # "offset2": the Y plane 2 bytes, the UV plane 4 bytes past a 16-byte boundary, aligned pitch
             off, pitch = align, up(rowbytes, 16)
-        bstride = pitch * rows + (pitch * 3 + 32 if layout == "bstride" else 0)
+        # "b1stride": everything 16-byte aligned but the batch stride, legal and never used at B == 1 - the 16-byte accesses must be taken
+        bstride = pitch * rows + (pitch * 3 + 32 if layout == "bstride" else 4 if layout == "b1stride" else 0)
         out.append((off, pitch, bstride))
     return out
 
@@ -59,6 +62,17 @@ def planes(layout, B, H, W):
     yraw, y = strided((B, H, W), yo, yp, yb)
     uvraw, uv = strided((B, (H + 1) // 2, (W + 1) // 2, 2), uo, upitch, ub)
     return yraw, y, uvraw, uv
+
+
+def cases(layout, batches):
+    return [B1STRIDE] if layout == "b1stride" else itertools.product(SHAPES, batches)
+
+
+def entry_args(y, uv, colour):
+    """the C entries' plane and colour arguments with the views' own batch strides: lib's wrappers pass the dense value at B == 1"""
+    depth, standard, full, order = colour
+    return ((y.data_ptr(), 2 * y.stride(1), 2 * y.stride(0), uv.data_ptr(), 2 * uv.stride(1), 2 * uv.stride(0)),
+            (depth, lib.yuv_standard_code_deep(standard, full), lib._order_code(order)))
 
 
 def to_t(a):
@@ -83,7 +97,13 @@ def check_decode(ynp, uvnp, layout, colour, want=None):
     y.copy_(to_t(ynp))
     uv.copy_(to_t(uvnp))
     flat, out = guarded_out(B, H, W)
-    got = lib.preprocess_p010(y, uv, depth, standard, full, order, out=out)
+    if layout == "b1stride":
+        pl, codes = entry_args(y, uv, colour)
+        assert 2 * y.stride(0) % 16 == 4 and lib.load().emavfi_preprocess_p010(*pl, out.data_ptr(), B, H, W, *codes, *lib._stats(oracle.MEAN, oracle.STD, 3),
+                                                                               lib._stream()) == 0, lib.last_error()
+        got = out
+    else:
+        got = lib.preprocess_p010(y, uv, depth, standard, full, order, out=out)
     if want is None:
         want = oracle.preprocess(ynp, uvnp, depth, standard, full, order)
     assert got.data_ptr() == out.data_ptr()
@@ -142,7 +162,7 @@ def test_low_bits_are_ignored_on_read():
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_decode_shapes_pitches_and_paths(layout):
     rng = np.random.default_rng(11)
-    for n, ((H, W), B) in enumerate(itertools.product(SHAPES, (1, 2))):
+    for n, ((H, W), B) in enumerate(cases(layout, (1, 2))):
         colour = COLOURS[(7 * n + LAYOUTS.index(layout)) % len(COLOURS)]
         y = rand_words(rng, (B, H, W), colour[0], junk=True)
         uv = rand_words(rng, (B, (H + 1) // 2, (W + 1) // 2, 2), colour[0], junk=True)
@@ -187,7 +207,14 @@ def check_encode(xnp, layout, colour, denorm):
     depth, standard, full, order = colour
     B, _, H, W = xnp.shape
     yraw, y, uvraw, uv = planes(layout, B, H, W)
-    lib.postprocess_p010(torch.from_numpy(xnp).cuda(), depth, standard, full, order, denormalize=bool(denorm), out=(y, uv))
+    if layout == "b1stride":
+        pl, codes = entry_args(y, uv, colour)
+        x = torch.from_numpy(xnp).cuda()
+        assert 2 * uv.stride(0) % 16 == 4 and lib.load().emavfi_postprocess_p010(x.data_ptr(), *pl, B, H, W, *codes,
+                                                                                 *lib._stats(oracle.MEAN, oracle.STD, 3, ctypes.c_double), denorm,
+                                                                                 lib._stream()) == 0, lib.last_error()
+    else:
+        lib.postprocess_p010(torch.from_numpy(xnp).cuda(), depth, standard, full, order, denormalize=bool(denorm), out=(y, uv))
     ywant, uvwant = oracle.postprocess(xnp, depth, standard, full, order, denormalize=bool(denorm))
     low = np.uint16((1 << (16 - depth)) - 1)
     assert not (to_np(y) & low).any() and not (to_np(uv) & low).any(), "low bits must be written as zero"
@@ -204,7 +231,7 @@ def check_encode(xnp, layout, colour, denorm):
 @pytest.mark.parametrize("denorm", [0, 1])
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_encode_shapes_pitches_and_paths(layout, denorm):
-    for n, ((H, W), B) in enumerate(itertools.product(SHAPES, (1, 2))):
+    for n, ((H, W), B) in enumerate(cases(layout, (1, 2))):
         colour = COLOURS[(5 * n + 3 * denorm + LAYOUTS.index(layout)) % len(COLOURS)]
         check_encode(encode_input(B, H, W, colour[0], denorm, seed=100 + n), layout, colour, denorm)
 

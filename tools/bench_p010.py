@@ -58,7 +58,7 @@ say(f"Box: {torch.cuda.get_device_name(0)}, {torch.cuda.get_device_properties(0)
     f"HIP {torch.version.hip}, {platform.machine()} host with {len(os.sched_getaffinity(0))} CPUs granted.")
 if args.vgprs:
     say()
-    say(f"gfx950 code object, preprocess_p010_kernel / postprocess_p010_kernel: {args.vgprs}.")
+    say(f"gfx950 code object, preprocess_yuv420_kernel<Yuv16<true>> / postprocess_yuv420_kernel<Yuv16<true>>: {args.vgprs}.")
 say()
 
 # ---------------------------------------------------------------- (1) kernels, resident frames

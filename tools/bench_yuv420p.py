@@ -4,12 +4,12 @@
       _postprocess_yuv420p at depth 8 beside emavfi_preprocess_nv12 / _postprocess_nv12 and at depth 10 beside emavfi_preprocess_p010 /
       _postprocess_p010 - the same samples, the same bytes moved (13.5 B/px at depth 8, 15 above), only the chroma planes apart instead
       of interleaved.  HIP events, warm-up, the median of N >= 20 and the spread (min .. max, and the shift of the median between the
-      first and the second half of the samples).  The NV12 / P010 kernels are the ones the library had before: unchanged.  There is no
+      first and the second half of the samples).  All eight are instantiations of one kernel pair (misc_kernels.hip, preprocess_yuv420_kernel).  There is no
       pass / fail time; the ratios are recorded, and a planar kernel slower than its counterpart by more than that counterpart's own
       spread is flagged: the explanation is written by hand under the file's "## Notes" heading, which the tool keeps when it rewrites
-      the file.  --ab-lib PATH times the same two entries of a second build of the library (the 2 rows x 32 bytes block:
-      `make -C video-frame-interpolation_amd/csrc TAG=_block32 EXTRA=-DEMAVFI_YUV420P_BLOCK32=1`) in the same process and the same
-      interleaved loop, on the same buffers.
+      the file.  --ab-lib PATH times the same eight entries of a second build of the library (`make -C video-frame-interpolation_amd/csrc
+      TAG=_other`, in a checkout of another commit or with EXTRA flags) in the same process and the same interleaved loop, on the same
+      buffers, and asserts that both builds write identical frames; both builds are then called through ctypes directly, without lib's wrappers.
   (2) run_chunked beside run on 65 frames of 1280 x 720 (64 pairs), batch_pairs 8, bf16, pixel_format="yuv420p8", alternating: what
       cutting the stream into chunks of --chunk-pairs pairs (bounded memory) costs in rate.
 Writes a markdown note (default profiles/r15_yuv420p_y4m.md); --vgprs puts the code object's register counts into it."""
@@ -25,7 +25,7 @@ ap.add_argument("--samples", type=int, default=40)
 ap.add_argument("--rounds", type=int, default=4)
 ap.add_argument("--chunk-pairs", type=int, nargs="+", default=[16, 64])
 ap.add_argument("--skip-harness", action="store_true")
-ap.add_argument("--ab-lib", default="", help="a second build of libemavfi.so whose planar entries are timed beside the loaded one's")
+ap.add_argument("--ab-lib", default="", help="a second build of libemavfi.so whose eight entries are timed beside the loaded one's")
 ap.add_argument("--vgprs", default="", help="text for the note: VGPR counts of the planar kernels read from the gfx950 code object")
 args = ap.parse_args()
 HBM_PEAK = 8.0e12   # B/s, HBM3E specification of the MI355X
@@ -101,26 +101,57 @@ kernels = {
 if args.ab_lib:
     import ctypes
     AB = ctypes.CDLL(os.path.abspath(args.ab_lib))
-    for sym in ("emavfi_preprocess_yuv420p", "emavfi_postprocess_yuv420p"):
+    for sym in ("emavfi_preprocess_nv12", "emavfi_postprocess_nv12", "emavfi_preprocess_p010", "emavfi_postprocess_p010",
+                "emavfi_preprocess_yuv420p", "emavfi_postprocess_yuv420p"):
         getattr(AB, sym).restype, getattr(AB, sym).argtypes = lib._PROTOTYPES[sym]
     m32, s32 = lib._stats(lib.IMAGENET_MEAN, lib.IMAGENET_STD, 3)
     m64, s64 = lib._stats(lib.IMAGENET_MEAN, lib.IMAGENET_STD, 3, ctypes.c_double)
 
-    def ab_pre(buf, depth):
-        _, _, _, pl = lib._yuv420p_planes(*planes3(buf, depth > 8), depth, "ab")
-        assert AB.emavfi_preprocess_yuv420p(*pl, x.data_ptr(), B, H, W, depth, 0, 0, m32, s32, lib._stream()) == 0
+    def semi_args(buf, depth):
+        """(y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride) and the depth argument, if the entry takes one"""
+        y, uv = planes2(buf)
+        _, _, _, yp, ybs, uvp, uvbs = (lib._nv12_planes if depth == 8 else lib._p010_planes)(y, uv, "ab")
+        return (y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs), (() if depth == 8 else (depth,))
 
-    def ab_post(buf, depth):
-        _, _, _, pl = lib._yuv420p_planes(*planes3(buf, depth > 8), depth, "ab")
-        assert AB.emavfi_postprocess_yuv420p(pred.data_ptr(), *pl, B, H, W, depth, 0, 0, m64, s64, 1, lib._stream()) == 0
+    def ab_pre(L, buf, depth, planar):
+        """a call of the build's preprocess entry on `buf`, arguments worked out once"""
+        if planar:
+            fn, args = L.emavfi_preprocess_yuv420p, (*lib._yuv420p_planes(*planes3(buf, depth > 8), depth, "ab")[3], x.data_ptr(), B, H, W, depth)
+        else:
+            pl, d = semi_args(buf, depth)
+            fn, args = (L.emavfi_preprocess_nv12 if depth == 8 else L.emavfi_preprocess_p010), (*pl, x.data_ptr(), B, H, W, *d)
 
-    ab8, ab10 = torch.empty_like(d_pl8), torch.empty_like(d_pl10)
-    kernels.update({
-        "preprocess_yuv420p d=8, block32 build": (lambda: ab_pre(d_pl8, 8), 13.5),
-        "preprocess_yuv420p d=10, block32 build": (lambda: ab_pre(d_pl10, 10), 15.0),
-        "postprocess_yuv420p d=8, block32 build": (lambda: ab_post(ab8, 8), 13.5),
-        "postprocess_yuv420p d=10, block32 build": (lambda: ab_post(ab10, 10), 15.0),
-    })
+        def call():
+            assert fn(*args, 0, 0, m32, s32, lib._stream()) == 0
+        return call
+
+    def ab_post(L, buf, depth, planar):
+        if planar:
+            fn, args = L.emavfi_postprocess_yuv420p, (pred.data_ptr(), *lib._yuv420p_planes(*planes3(buf, depth > 8), depth, "ab")[3], B, H, W, depth)
+        else:
+            pl, d = semi_args(buf, depth)
+            fn, args = (L.emavfi_postprocess_nv12 if depth == 8 else L.emavfi_postprocess_p010), (pred.data_ptr(), *pl, B, H, W, *d)
+
+        def call():
+            assert fn(*args, 0, 0, m64, s64, 1, lib._stream()) == 0
+        return call
+
+    ab8, ab10, ab_nv, ab_p010 = torch.empty_like(d_pl8), torch.empty_like(d_pl10), torch.empty_like(d_nv), torch.empty_like(d_p010)
+    # both builds through the same direct calls: lib's wrappers cost a few microseconds of host time in front of a launch, which HIP events
+    # around a 40 - 80 us kernel on an idle queue would count against the loaded library alone
+    def eight(L, tag, out_nv, out8, out_p010, out10):
+        return {
+            "preprocess_nv12" + tag: (ab_pre(L, d_nv, 8, False), 13.5),
+            "preprocess_yuv420p d=8" + tag: (ab_pre(L, d_pl8, 8, True), 13.5),
+            "preprocess_p010" + tag: (ab_pre(L, d_p010, 10, False), 15.0),
+            "preprocess_yuv420p d=10" + tag: (ab_pre(L, d_pl10, 10, True), 15.0),
+            "postprocess_nv12" + tag: (ab_post(L, out_nv, 8, False), 13.5),
+            "postprocess_yuv420p d=8" + tag: (ab_post(L, out8, 8, True), 13.5),
+            "postprocess_p010" + tag: (ab_post(L, out_p010, 10, False), 15.0),
+            "postprocess_yuv420p d=10" + tag: (ab_post(L, out10, 10, True), 15.0),
+        }
+
+    kernels = {**eight(lib.load(), "", o_nv, o_pl8, o_p010, o_pl10), **eight(AB, ", second build", ab_nv, ab8, ab_p010, ab10)}
 times = {k: [] for k in kernels}
 for name, (fn, _) in kernels.items():
     for _ in range(5):
@@ -129,11 +160,13 @@ torch.cuda.synchronize()
 # the planar results are the interleaved results: checked here once, on the benchmark's own frames
 assert torch.equal(planes3(o_pl8, False)[1], planes2(o_nv)[1][..., 0]) and torch.equal(planes3(o_pl8, False)[0], planes2(o_nv)[0])
 if args.ab_lib:                              # both builds write the same frames
-    assert torch.equal(ab8, o_pl8) and torch.equal(ab10, o_pl10)
-    ref = x.clone()
-    ab_pre(d_pl10, 10)
-    lib.preprocess_yuv420p(*planes3(d_pl10, True), 10, out=ref)
-    assert torch.equal(ref.view(torch.int32), x.view(torch.int32))
+    assert torch.equal(ab8, o_pl8) and torch.equal(ab10, o_pl10) and torch.equal(ab_nv, o_nv) and torch.equal(ab_p010, o_p010)
+    ref = torch.empty_like(x)
+    for buf, depth, planar in ((d_nv, 8, False), (d_pl8, 8, True), (d_p010, 10, False), (d_pl10, 10, True)):
+        ab_pre(lib.load(), buf, depth, planar)()
+        ref.copy_(x)
+        ab_pre(AB, buf, depth, planar)()
+        assert torch.equal(ref.view(torch.int32), x.view(torch.int32))
 u16 = lambda t: t.to(torch.int32).bitwise_and(0xffff)
 assert torch.equal(u16(planes3(o_pl10, True)[2]), u16(planes2(o_p010)[1][..., 1]) >> 6)
 for _ in range(max(20, args.samples)):
@@ -161,9 +194,13 @@ for a, b in (("preprocess_yuv420p d=8", "preprocess_nv12"), ("preprocess_yuv420p
     verdict = ("within the counterpart's spread" if med[a] <= med[b] + spread else
                "SLOWER than the counterpart by more than its spread: the reason belongs under \"## Notes\" at the end of this file, by hand")
     say(f"- {a} {med[a]:.1f} us vs {b} {med[b]:.1f} us: ratio {med[a] / med[b]:.3f}; {b}'s own min..max spread {spread:.1f} us: {verdict}.")
-    if args.ab_lib:
-        c = a + ", block32 build"
-        say(f"  - the 2 rows x 32 bytes block ({os.path.basename(args.ab_lib)}): {med[c]:.1f} us, {med[c] / med[b]:.3f} of {b}, {med[c] / med[a]:.3f} of the shipped block.")
+if args.ab_lib:
+    say()
+    say(f"Second build ({os.path.basename(args.ab_lib)}) beside the loaded library, same loop, same buffers; ratio of medians loaded / second:")
+    say()
+    for a in [k for k in kernels if not k.endswith(", second build")]:
+        c = a + ", second build"
+        say(f"- {a}: loaded {med[a]:.1f} us, second build {med[c]:.1f} us: {med[a] / med[c]:.3f}.")
 say()
 
 # ---------------------------------------------------------------- (2) run_chunked beside run, host frames in and out

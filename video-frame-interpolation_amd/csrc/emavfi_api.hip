@@ -1336,27 +1336,95 @@ int emavfi_postprocess_u8(const float *frames_nchw, unsigned char *out_hwc, int 
     return EMAVFI_OK;
 }
 
-// ---- NV12 frames (include/emavfi.h, "NV12"): the checks both entries share, in an order that lets a caller without a device reach each
-static int nv12_check(const char *what, const void *y, size_t y_pitch, size_t y_bstride, const void *uv, size_t uv_pitch, size_t uv_bstride,
-                      const void *f32, int B, int H, int W, int standard, int order, const float *mean32, const float *std32, const double *mean64,
-                      const double *std64)
+// ---- 4:2:0 frames (include/emavfi.h, "NV12", "HIGH BIT DEPTH", "PLANAR 4:2:0"): one check for the six entries.  An entry names its planes and
+// its format's rules in a table; yuv420_check walks it in an order that lets a caller without a device reach every refusal.
+struct Yuv420PlaneRule {
+    const char *name;
+    size_t row, rows;               // bytes of a row, rows of the plane
+    size_t ptr_align, step_align;   // what the pointer / the pitch and (B > 1) the batch stride must be a multiple of; 1: anything
+};
+struct Yuv420Table {
+    Yuv420Frame fr;                 // the planes, as the launcher takes them
+    int nplanes;
+    Yuv420PlaneRule rule[3];
+    const char *depths;             // null: fr.depth is one of the format's; else the list of those, for the message
+    int last_standard;              // EMAVFI_YUV_BT601_LIMITED .. last_standard
+    const char *last_standard_name;
+};
+static size_t half_up(int n) { return ((size_t)n + 1) / 2; }
+// NV12: bytes; both pointers 2-byte aligned, any pitch; the four 8-bit standards
+static Yuv420Table nv12_table(const void *y, size_t y_pitch, size_t y_bstride, const void *uv, size_t uv_pitch, size_t uv_bstride, int H, int W)
 {
+    return {{{(void *)y, (void *)uv, nullptr}, {{y_pitch, uv_pitch, 0}, {y_bstride, uv_bstride, 0}}, YUV420_SEMIPLANAR, 8}, 2,
+            {{"y", (size_t)W, (size_t)H, 2, 1}, {"uv", 2 * half_up(W), half_up(H), 2, 1}, {}},
+            nullptr, EMAVFI_YUV_BT709_FULL, "EMAVFI_YUV_BT709_FULL"};
+}
+// P010 / P012 / P016: words; the Y plane keeps word alignment, the UV plane pair (4-byte) alignment; all six standards
+static Yuv420Table p010_table(const void *y, size_t y_pitch, size_t y_bstride, const void *uv, size_t uv_pitch, size_t uv_bstride, int H, int W, int depth)
+{
+    return {{{(void *)y, (void *)uv, nullptr}, {{y_pitch, uv_pitch, 0}, {y_bstride, uv_bstride, 0}}, YUV420_SEMIPLANAR, depth}, 2,
+            {{"y", 2 * (size_t)W, (size_t)H, 2, 2}, {"uv", 4 * half_up(W), half_up(H), 4, 4}, {}},
+            depth == 10 || depth == 12 || depth == 16 ? nullptr : "10, 12 or 16 (P010, P012, P016)", EMAVFI_YUV_BT2020_FULL, "EMAVFI_YUV_BT2020_FULL"};
+}
+// planar: bytes with no alignment rule and the 8-bit standards, or words that keep word alignment and all six standards
+static Yuv420Table yuv420p_table(const void *y, size_t y_pitch, size_t y_bstride, const void *u, size_t u_pitch, size_t u_bstride, const void *v,
+                                 size_t v_pitch, size_t v_bstride, int H, int W, int depth)
+{
+    const size_t es = depth == 8 ? 1 : 2;   // bytes per sample
+    return {{{(void *)y, (void *)u, (void *)v}, {{y_pitch, u_pitch, v_pitch}, {y_bstride, u_bstride, v_bstride}}, YUV420_PLANAR, depth}, 3,
+            {{"y", es * (size_t)W, (size_t)H, es, es}, {"u", es * half_up(W), half_up(H), es, es}, {"v", es * half_up(W), half_up(H), es, es}},
+            depth == 8 || depth == 10 || depth == 12 || depth == 16 ? nullptr : "8, 10, 12 or 16",
+            depth == 8 ? EMAVFI_YUV_BT709_FULL : EMAVFI_YUV_BT2020_FULL, depth == 8 ? "EMAVFI_YUV_BT709_FULL" : "EMAVFI_YUV_BT2020_FULL"};
+}
+// mean / std come as float (preprocess) or as double (postprocess); sizes are compared in 128 bits
+static int yuv420_check(const char *what, const Yuv420Table &t, const void *f32, int B, int H, int W, int standard, int order, const float *mean32,
+                        const float *std32, const double *mean64, const double *std64)
+{
+    typedef unsigned __int128 u128;
+    const Yuv420Strides &st = t.fr.strides;
     if (!(mean32 && std32) && !(mean64 && std64)) return fail(EMAVFI_E_ARG, "%s: null mean / std", what);
     if (B < 1 || H < 1 || W < 1) return fail(EMAVFI_E_ARG, "%s: B, H, W must be >= 1", what);
-    if (standard < EMAVFI_YUV_BT601_LIMITED || standard > EMAVFI_YUV_BT709_FULL)
-        return fail(EMAVFI_E_ARG, "%s: unknown standard %d (EMAVFI_YUV_BT601_LIMITED .. EMAVFI_YUV_BT709_FULL)", what, standard);
+    if (t.depths) return fail(EMAVFI_E_ARG, "%s: depth %d is not %s", what, t.fr.depth, t.depths);
+    if (standard < EMAVFI_YUV_BT601_LIMITED || standard > t.last_standard)
+        return fail(EMAVFI_E_ARG, "%s: unknown standard %d at depth %d (EMAVFI_YUV_BT601_LIMITED .. %s)", what, standard, t.fr.depth, t.last_standard_name);
     if (order != EMAVFI_ORDER_BGR && order != EMAVFI_ORDER_RGB)
         return fail(EMAVFI_E_ARG, "%s: unknown order %d (EMAVFI_ORDER_BGR or EMAVFI_ORDER_RGB)", what, order);
-    const size_t uv_row = 2 * (((size_t)W + 1) / 2), uv_rows = ((size_t)H + 1) / 2;
-    if (y_pitch < (size_t)W) return fail(EMAVFI_E_ARG, "%s: y_pitch %zu is smaller than W = %d", what, y_pitch, W);
-    if (uv_pitch < uv_row) return fail(EMAVFI_E_ARG, "%s: uv_pitch %zu is smaller than 2 * ceil(W / 2) = %zu", what, uv_pitch, uv_row);
-    if (B > 1 && (y_bstride < (size_t)(H - 1) * y_pitch + (size_t)W || uv_bstride < (uv_rows - 1) * uv_pitch + uv_row))
-        return fail(EMAVFI_E_ARG, "%s: a batch stride (y %zu, uv %zu) is smaller than its plane", what, y_bstride, uv_bstride);
+    for (int p = 0; p < t.nplanes; ++p) {
+        const Yuv420PlaneRule &r = t.rule[p];
+        if (st.pitch[p] < r.row) return fail(EMAVFI_E_ARG, "%s: %s_pitch %zu is smaller than its row of %zu bytes", what, r.name, st.pitch[p], r.row);
+        if (st.pitch[p] % r.step_align) return fail(EMAVFI_E_ARG, "%s: %s_pitch %zu must be a multiple of %zu", what, r.name, st.pitch[p], r.step_align);
+    }
+    for (int p = 0; p < t.nplanes && B > 1; ++p) {
+        const Yuv420PlaneRule &r = t.rule[p];
+        if ((u128)st.bstride[p] < (u128)(r.rows - 1) * st.pitch[p] + r.row)
+            return fail(EMAVFI_E_ARG, "%s: the %s batch stride %zu is smaller than its plane", what, r.name, st.bstride[p]);
+        if (st.bstride[p] % r.step_align)
+            return fail(EMAVFI_E_ARG, "%s: the %s batch stride %zu must be a multiple of %zu (it breaks the alignment of its plane)", what, r.name,
+                        st.bstride[p], r.step_align);
+    }
     for (int c = 0; c < 3; ++c)
         if (std32 ? !(std32[c] != 0.0f) : !(std64[c] != 0.0)) return fail(EMAVFI_E_ARG, "%s: std[%d] must be non-zero", what, c);
-    if (!y || !uv || !f32) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
-    if (((uintptr_t)y | (uintptr_t)uv) & 1) return fail(EMAVFI_E_ARG, "%s: the Y and UV pointers must be 2-byte aligned", what);
+    for (int p = 0; p < t.nplanes; ++p)
+        if (!t.fr.plane[p]) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
+    if (!f32) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
+    for (int p = 0; p < t.nplanes; ++p)
+        if ((uintptr_t)t.fr.plane[p] % t.rule[p].ptr_align)
+            return fail(EMAVFI_E_ARG, "%s: the %s pointer must be %zu-byte aligned", what, t.rule[p].name, t.rule[p].ptr_align);
     if ((uintptr_t)f32 & 3) return fail(EMAVFI_E_ARG, "%s: the fp32 pointer must be 4-byte aligned", what);
+    return EMAVFI_OK;
+}
+static int preprocess_yuv420(const char *what, const Yuv420Table &t, float *out_nchw, int B, int H, int W, int standard, int order, const float *mean,
+                             const float *std, void *stream)
+{
+    if (const int rc = yuv420_check(what, t, out_nchw, B, H, W, standard, order, mean, std, nullptr, nullptr); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_preprocess_yuv420(t.fr, out_nchw, B, H, W, standard, order, mean, std, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+static int postprocess_yuv420(const char *what, const float *frames_nchw, const Yuv420Table &t, int B, int H, int W, int standard, int order,
+                              const double *mean, const double *std, int denormalize, void *stream)
+{
+    if (const int rc = yuv420_check(what, t, frames_nchw, B, H, W, standard, order, nullptr, nullptr, mean, std); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_postprocess_yuv420(frames_nchw, t.fr, B, H, W, standard, order, mean, std, denormalize ? 1 : 0, (hipStream_t)stream), what);
     return EMAVFI_OK;
 }
 
@@ -1366,58 +1434,6 @@ int emavfi_yuv_coefficients(int standard, int decode[5], int encode[9])
         return fail(EMAVFI_E_ARG, "yuv_coefficients: unknown standard %d (EMAVFI_YUV_BT601_LIMITED .. EMAVFI_YUV_BT709_FULL)", standard);
     if (!decode || !encode) return fail(EMAVFI_E_ARG, "yuv_coefficients: null pointer");
     yuv_coefficients(standard, decode, encode);
-    return EMAVFI_OK;
-}
-
-int emavfi_preprocess_nv12(const unsigned char *y, size_t y_pitch, size_t y_batch_stride, const unsigned char *uv, size_t uv_pitch,
-                           size_t uv_batch_stride, float *out_nchw, int B, int H, int W, int standard, int order, const float *mean,
-                           const float *std, void *stream)
-{
-    if (const int rc = nv12_check("preprocess_nv12", y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, out_nchw, B, H, W, standard, order,
-                                  mean, std, nullptr, nullptr); rc != EMAVFI_OK) return rc;
-    EMAVFI_TRY(launch_preprocess_nv12(y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, out_nchw, B, H, W, standard, order, mean, std,
-                                      (hipStream_t)stream), "preprocess_nv12");
-    return EMAVFI_OK;
-}
-
-int emavfi_postprocess_nv12(const float *frames_nchw, unsigned char *y, size_t y_pitch, size_t y_batch_stride, unsigned char *uv, size_t uv_pitch,
-                            size_t uv_batch_stride, int B, int H, int W, int standard, int order, const double *mean, const double *std,
-                            int denormalize, void *stream)
-{
-    if (const int rc = nv12_check("postprocess_nv12", y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, frames_nchw, B, H, W, standard,
-                                  order, nullptr, nullptr, mean, std); rc != EMAVFI_OK) return rc;
-    EMAVFI_TRY(launch_postprocess_nv12(frames_nchw, y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, B, H, W, standard, order, mean, std,
-                                       denormalize ? 1 : 0, (hipStream_t)stream), "postprocess_nv12");
-    return EMAVFI_OK;
-}
-
-// ---- 16-bit-word frames (include/emavfi.h, "HIGH BIT DEPTH"): the checks both entries share, in nv12_check's order; sizes are compared in 128 bits
-static int p010_check(const char *what, const void *y, size_t y_pitch, size_t y_bstride, const void *uv, size_t uv_pitch, size_t uv_bstride,
-                      const void *f32, int B, int H, int W, int depth, int standard, int order, const float *mean32, const float *std32,
-                      const double *mean64, const double *std64)
-{
-    typedef unsigned __int128 u128;
-    if (!(mean32 && std32) && !(mean64 && std64)) return fail(EMAVFI_E_ARG, "%s: null mean / std", what);
-    if (B < 1 || H < 1 || W < 1) return fail(EMAVFI_E_ARG, "%s: B, H, W must be >= 1", what);
-    if (depth != 10 && depth != 12 && depth != 16) return fail(EMAVFI_E_ARG, "%s: depth %d is not 10, 12 or 16 (P010, P012, P016)", what, depth);
-    if (standard < EMAVFI_YUV_BT601_LIMITED || standard > EMAVFI_YUV_BT2020_FULL)
-        return fail(EMAVFI_E_ARG, "%s: unknown standard %d (EMAVFI_YUV_BT601_LIMITED .. EMAVFI_YUV_BT2020_FULL)", what, standard);
-    if (order != EMAVFI_ORDER_BGR && order != EMAVFI_ORDER_RGB)
-        return fail(EMAVFI_E_ARG, "%s: unknown order %d (EMAVFI_ORDER_BGR or EMAVFI_ORDER_RGB)", what, order);
-    const size_t y_row = 2 * (size_t)W, uv_row = 4 * (((size_t)W + 1) / 2), uv_rows = ((size_t)H + 1) / 2;
-    if (y_pitch < y_row || (y_pitch & 1)) return fail(EMAVFI_E_ARG, "%s: y_pitch %zu must be even and at least 2 W = %zu bytes", what, y_pitch, y_row);
-    if (uv_pitch < uv_row || (uv_pitch & 3))
-        return fail(EMAVFI_E_ARG, "%s: uv_pitch %zu must be a multiple of 4 and at least 4 * ceil(W / 2) = %zu bytes", what, uv_pitch, uv_row);
-    if (B > 1 && ((u128)y_bstride < (u128)(H - 1) * y_pitch + y_row || (u128)uv_bstride < (u128)(uv_rows - 1) * uv_pitch + uv_row))
-        return fail(EMAVFI_E_ARG, "%s: a batch stride (y %zu, uv %zu) is smaller than its plane", what, y_bstride, uv_bstride);
-    if (B > 1 && ((y_bstride & 1) || (uv_bstride & 3)))
-        return fail(EMAVFI_E_ARG, "%s: a batch stride (y %zu, uv %zu) breaks the alignment of its plane (2 / 4 bytes)", what, y_bstride, uv_bstride);
-    for (int c = 0; c < 3; ++c)
-        if (std32 ? !(std32[c] != 0.0f) : !(std64[c] != 0.0)) return fail(EMAVFI_E_ARG, "%s: std[%d] must be non-zero", what, c);
-    if (!y || !uv || !f32) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
-    if ((uintptr_t)y & 1) return fail(EMAVFI_E_ARG, "%s: the Y pointer must be 2-byte aligned", what);
-    if ((uintptr_t)uv & 3) return fail(EMAVFI_E_ARG, "%s: the UV pointer must be 4-byte aligned", what);
-    if ((uintptr_t)f32 & 3) return fail(EMAVFI_E_ARG, "%s: the fp32 pointer must be 4-byte aligned", what);
     return EMAVFI_OK;
 }
 
@@ -1432,91 +1448,54 @@ int emavfi_yuv_coefficients_depth(int standard, int depth, int decode[5], int en
     return EMAVFI_OK;
 }
 
+int emavfi_preprocess_nv12(const unsigned char *y, size_t y_pitch, size_t y_batch_stride, const unsigned char *uv, size_t uv_pitch,
+                           size_t uv_batch_stride, float *out_nchw, int B, int H, int W, int standard, int order, const float *mean,
+                           const float *std, void *stream)
+{
+    return preprocess_yuv420("preprocess_nv12", nv12_table(y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, H, W), out_nchw, B, H, W,
+                             standard, order, mean, std, stream);
+}
+
+int emavfi_postprocess_nv12(const float *frames_nchw, unsigned char *y, size_t y_pitch, size_t y_batch_stride, unsigned char *uv, size_t uv_pitch,
+                            size_t uv_batch_stride, int B, int H, int W, int standard, int order, const double *mean, const double *std,
+                            int denormalize, void *stream)
+{
+    return postprocess_yuv420("postprocess_nv12", frames_nchw, nv12_table(y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, H, W), B, H, W,
+                              standard, order, mean, std, denormalize, stream);
+}
+
 int emavfi_preprocess_p010(const void *y, size_t y_pitch, size_t y_batch_stride, const void *uv, size_t uv_pitch, size_t uv_batch_stride,
                            float *out_nchw, int B, int H, int W, int depth, int standard, int order, const float *mean, const float *std,
                            void *stream)
 {
-    if (const int rc = p010_check("preprocess_p010", y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, out_nchw, B, H, W, depth, standard,
-                                  order, mean, std, nullptr, nullptr); rc != EMAVFI_OK) return rc;
-    EMAVFI_TRY(launch_preprocess_p010(y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, out_nchw, B, H, W, depth, standard, order, mean,
-                                      std, (hipStream_t)stream), "preprocess_p010");
-    return EMAVFI_OK;
+    return preprocess_yuv420("preprocess_p010", p010_table(y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, H, W, depth), out_nchw, B, H,
+                             W, standard, order, mean, std, stream);
 }
 
 int emavfi_postprocess_p010(const float *frames_nchw, void *y, size_t y_pitch, size_t y_batch_stride, void *uv, size_t uv_pitch,
                             size_t uv_batch_stride, int B, int H, int W, int depth, int standard, int order, const double *mean,
                             const double *std, int denormalize, void *stream)
 {
-    if (const int rc = p010_check("postprocess_p010", y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, frames_nchw, B, H, W, depth,
-                                  standard, order, nullptr, nullptr, mean, std); rc != EMAVFI_OK) return rc;
-    EMAVFI_TRY(launch_postprocess_p010(frames_nchw, y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, B, H, W, depth, standard, order,
-                                       mean, std, denormalize ? 1 : 0, (hipStream_t)stream), "postprocess_p010");
-    return EMAVFI_OK;
-}
-
-// ---- planar 4:2:0 frames (include/emavfi.h, "PLANAR 4:2:0"): the checks both entries share, in nv12_check's order; sizes are compared in 128 bits
-static int yuv420p_check(const char *what, const void *const ptr[3], const size_t pitch[3], const size_t bstride[3], const void *f32, int B, int H,
-                         int W, int depth, int standard, int order, const float *mean32, const float *std32, const double *mean64,
-                         const double *std64)
-{
-    typedef unsigned __int128 u128;
-    static const char *const name[3] = {"y", "u", "v"};
-    if (!(mean32 && std32) && !(mean64 && std64)) return fail(EMAVFI_E_ARG, "%s: null mean / std", what);
-    if (B < 1 || H < 1 || W < 1) return fail(EMAVFI_E_ARG, "%s: B, H, W must be >= 1", what);
-    if (depth != 8 && depth != 10 && depth != 12 && depth != 16) return fail(EMAVFI_E_ARG, "%s: depth %d is not 8, 10, 12 or 16", what, depth);
-    const int last = depth == 8 ? EMAVFI_YUV_BT709_FULL : EMAVFI_YUV_BT2020_FULL;
-    if (standard < EMAVFI_YUV_BT601_LIMITED || standard > last)
-        return fail(EMAVFI_E_ARG, "%s: unknown standard %d at depth %d (EMAVFI_YUV_BT601_LIMITED .. %s)", what, standard, depth,
-                    depth == 8 ? "EMAVFI_YUV_BT709_FULL" : "EMAVFI_YUV_BT2020_FULL");
-    if (order != EMAVFI_ORDER_BGR && order != EMAVFI_ORDER_RGB)
-        return fail(EMAVFI_E_ARG, "%s: unknown order %d (EMAVFI_ORDER_BGR or EMAVFI_ORDER_RGB)", what, order);
-    const size_t es = depth == 8 ? 1 : 2;   // bytes per sample
-    const size_t row[3] = {es * (size_t)W, es * (((size_t)W + 1) / 2), es * (((size_t)W + 1) / 2)};
-    const size_t rows[3] = {(size_t)H, ((size_t)H + 1) / 2, ((size_t)H + 1) / 2};
-    for (int p = 0; p < 3; ++p) {
-        if (pitch[p] < row[p]) return fail(EMAVFI_E_ARG, "%s: %s_pitch %zu is smaller than its row of %zu bytes", what, name[p], pitch[p], row[p]);
-        if (es == 2 && (pitch[p] & 1)) return fail(EMAVFI_E_ARG, "%s: %s_pitch %zu must be even at depth %d", what, name[p], pitch[p], depth);
-    }
-    for (int p = 0; p < 3 && B > 1; ++p) {
-        if ((u128)bstride[p] < (u128)(rows[p] - 1) * pitch[p] + row[p])
-            return fail(EMAVFI_E_ARG, "%s: the %s batch stride %zu is smaller than its plane", what, name[p], bstride[p]);
-        if (es == 2 && (bstride[p] & 1))
-            return fail(EMAVFI_E_ARG, "%s: the %s batch stride %zu must be even at depth %d (it breaks the alignment of its plane)", what, name[p],
-                        bstride[p], depth);
-    }
-    for (int c = 0; c < 3; ++c)
-        if (std32 ? !(std32[c] != 0.0f) : !(std64[c] != 0.0)) return fail(EMAVFI_E_ARG, "%s: std[%d] must be non-zero", what, c);
-    if (!ptr[0] || !ptr[1] || !ptr[2] || !f32) return fail(EMAVFI_E_ARG, "%s: null pointer", what);
-    for (int p = 0; p < 3; ++p)
-        if (es == 2 && ((uintptr_t)ptr[p] & 1)) return fail(EMAVFI_E_ARG, "%s: the %s pointer must be 2-byte aligned at depth %d", what, name[p], depth);
-    if ((uintptr_t)f32 & 3) return fail(EMAVFI_E_ARG, "%s: the fp32 pointer must be 4-byte aligned", what);
-    return EMAVFI_OK;
+    return postprocess_yuv420("postprocess_p010", frames_nchw, p010_table(y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, H, W, depth), B,
+                              H, W, standard, order, mean, std, denormalize, stream);
 }
 
 int emavfi_preprocess_yuv420p(const void *y, size_t y_pitch, size_t y_batch_stride, const void *u, size_t u_pitch, size_t u_batch_stride,
                               const void *v, size_t v_pitch, size_t v_batch_stride, float *out_nchw, int B, int H, int W, int depth,
                               int standard, int order, const float *mean, const float *std, void *stream)
 {
-    const void *const ptr[3] = {y, u, v};
-    const size_t pitch[3] = {y_pitch, u_pitch, v_pitch}, bstride[3] = {y_batch_stride, u_batch_stride, v_batch_stride};
-    if (const int rc = yuv420p_check("preprocess_yuv420p", ptr, pitch, bstride, out_nchw, B, H, W, depth, standard, order, mean, std, nullptr,
-                                     nullptr); rc != EMAVFI_OK) return rc;
-    EMAVFI_TRY(launch_preprocess_yuv420p(y, y_pitch, y_batch_stride, u, u_pitch, u_batch_stride, v, v_pitch, v_batch_stride, out_nchw, B, H, W,
-                                         depth, standard, order, mean, std, (hipStream_t)stream), "preprocess_yuv420p");
-    return EMAVFI_OK;
+    return preprocess_yuv420("preprocess_yuv420p",
+                             yuv420p_table(y, y_pitch, y_batch_stride, u, u_pitch, u_batch_stride, v, v_pitch, v_batch_stride, H, W, depth), out_nchw,
+                             B, H, W, standard, order, mean, std, stream);
 }
 
 int emavfi_postprocess_yuv420p(const float *frames_nchw, void *y, size_t y_pitch, size_t y_batch_stride, void *u, size_t u_pitch,
                                size_t u_batch_stride, void *v, size_t v_pitch, size_t v_batch_stride, int B, int H, int W, int depth,
                                int standard, int order, const double *mean, const double *std, int denormalize, void *stream)
 {
-    const void *const ptr[3] = {y, u, v};
-    const size_t pitch[3] = {y_pitch, u_pitch, v_pitch}, bstride[3] = {y_batch_stride, u_batch_stride, v_batch_stride};
-    if (const int rc = yuv420p_check("postprocess_yuv420p", ptr, pitch, bstride, frames_nchw, B, H, W, depth, standard, order, nullptr, nullptr,
-                                     mean, std); rc != EMAVFI_OK) return rc;
-    EMAVFI_TRY(launch_postprocess_yuv420p(frames_nchw, y, y_pitch, y_batch_stride, u, u_pitch, u_batch_stride, v, v_pitch, v_batch_stride, B, H,
-                                          W, depth, standard, order, mean, std, denormalize ? 1 : 0, (hipStream_t)stream), "postprocess_yuv420p");
-    return EMAVFI_OK;
+    return postprocess_yuv420("postprocess_yuv420p", frames_nchw,
+                              yuv420p_table(y, y_pitch, y_batch_stride, u, u_pitch, u_batch_stride, v, v_pitch, v_batch_stride, H, W, depth), B, H, W,
+                              standard, order, mean, std, denormalize, stream);
 }
 
 // ---- frames resized on the device (include/emavfi.h, "RESIZE DEFINITION"): checks in an order that lets a caller without a device reach each
@@ -1574,8 +1553,8 @@ int emavfi_preprocess_nv12_resized(const unsigned char *y, size_t y_pitch, size_
     if (!mean || !std) return fail(EMAVFI_E_ARG, "%s: null mean / std", what);
     if (const int rc = resize_dims_check(what, B, Hs, Ws, Hd, Wd); rc != EMAVFI_OK) return rc;
     // the source planes: emavfi_preprocess_nv12's checks (standard, order, pitches, batch strides, std, null, alignment), under this entry's name
-    if (const int rc = nv12_check(what, y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, out_nchw, B, Hs, Ws, standard, order, mean, std,
-                                  nullptr, nullptr); rc != EMAVFI_OK) return rc;
+    if (const int rc = yuv420_check(what, nv12_table(y, y_pitch, y_batch_stride, uv, uv_pitch, uv_batch_stride, Hs, Ws), out_nchw, B, Hs, Ws, standard,
+                                    order, mean, std, nullptr, nullptr); rc != EMAVFI_OK) return rc;
     const size_t uv_row = 2 * (((size_t)Wd + 1) / 2), uv_rows = ((size_t)Hd + 1) / 2;
     if (y_out)
         if (const int rc = resize_plane_check(what, "y_out", y_out_pitch, y_out_batch_stride, (size_t)Hd, (size_t)Wd, B); rc != EMAVFI_OK) return rc;

@@ -77,28 +77,24 @@ int launch_preprocess_u8(const unsigned char *src, float *dst, int B, int H, int
                          hipStream_t s);
 int launch_postprocess_u8(const float *src, unsigned char *dst, int B, int H, int W, int C, const double *mean, const double *stdv,
                           int denorm, hipStream_t s);
-// NV12 frames (include/emavfi.h): pitches and batch strides in bytes; standard / order are the header's codes, already validated
-void yuv_coefficients(int standard, int dec[5], int enc[9]);   // host only
-int launch_preprocess_nv12(const unsigned char *y, size_t y_pitch, size_t y_bstride, const unsigned char *uv, size_t uv_pitch, size_t uv_bstride,
-                           float *dst, int B, int H, int W, int standard, int order, const float *mean, const float *stdv, hipStream_t s);
-int launch_postprocess_nv12(const float *src, unsigned char *y, size_t y_pitch, size_t y_bstride, unsigned char *uv, size_t uv_pitch,
-                            size_t uv_bstride, int B, int H, int W, int standard, int order, const double *mean, const double *stdv, int denorm,
-                            hipStream_t s);
-// 16-bit-word frames, P010 / P012 / P016 (include/emavfi.h, "HIGH BIT DEPTH"): pitches and batch strides in bytes; depth / standard / order
-// already validated.  yuv_coefficients_depth also takes depth 8, where it returns yuv_coefficients' tables
+// 4:2:0 frames (include/emavfi.h, "NV12", "HIGH BIT DEPTH", "PLANAR 4:2:0").  yuv_coefficients_depth also takes depth 8, where it returns
+// yuv_coefficients' tables
+void yuv_coefficients(int standard, int dec[5], int enc[9]);                    // host only
 void yuv_coefficients_depth(int standard, int depth, int dec[5], int enc[9]);   // host only
-int launch_preprocess_p010(const void *y, size_t y_pitch, size_t y_bstride, const void *uv, size_t uv_pitch, size_t uv_bstride, float *dst, int B,
-                           int H, int W, int depth, int standard, int order, const float *mean, const float *stdv, hipStream_t s);
-int launch_postprocess_p010(const float *src, void *y, size_t y_pitch, size_t y_bstride, void *uv, size_t uv_pitch, size_t uv_bstride, int B, int H,
-                            int W, int depth, int standard, int order, const double *mean, const double *stdv, int denorm, hipStream_t s);
-// planar 4:2:0 frames (include/emavfi.h, "PLANAR 4:2:0"): three planes, pitches and batch strides in bytes; depth 8 (bytes) or 10 / 12 / 16
-// (words, the sample in the low bits); depth / standard / order already validated
-int launch_preprocess_yuv420p(const void *y, size_t y_pitch, size_t y_bstride, const void *u, size_t u_pitch, size_t u_bstride, const void *v,
-                              size_t v_pitch, size_t v_bstride, float *dst, int B, int H, int W, int depth, int standard, int order,
-                              const float *mean, const float *stdv, hipStream_t s);
-int launch_postprocess_yuv420p(const float *src, void *y, size_t y_pitch, size_t y_bstride, void *u, size_t u_pitch, size_t u_bstride, void *v,
-                               size_t v_pitch, size_t v_bstride, int B, int H, int W, int depth, int standard, int order, const double *mean,
-                               const double *stdv, int denorm, hipStream_t s);
+// One frame batch's planes: every operand of a 4:2:0 launch that says where the samples are, by name.
+enum Yuv420Layout { YUV420_SEMIPLANAR, YUV420_PLANAR };
+struct Yuv420Strides { size_t pitch[3], bstride[3]; };   // bytes between rows / between batch entries of plane [p]
+struct Yuv420Frame {
+    void *plane[3];          // [0] Y; [1] interleaved U,V pairs (semi-planar) or U (planar); [2] V (planar; null otherwise).  Read only by preprocess
+    Yuv420Strides strides;
+    int layout;              // Yuv420Layout
+    int depth;               // 8: bytes.  10 / 12 / 16: 16-bit words, the sample in the top bits (semi-planar: P010 ..) or the low bits (planar)
+};
+// layout / depth / standard / order already validated
+int launch_preprocess_yuv420(const Yuv420Frame &src, float *dst, int B, int H, int W, int standard, int order, const float *mean, const float *stdv,
+                             hipStream_t s);
+int launch_postprocess_yuv420(const float *src, const Yuv420Frame &dst, int B, int H, int W, int standard, int order, const double *mean,
+                              const double *stdv, int denorm, hipStream_t s);
 // frames resized on the device (include/emavfi.h, "RESIZE DEFINITION"): pitches and batch strides in bytes, arguments already validated.
 // launch_resize_u8: dst_u8 and / or dst_f32 (dense [B,C,Hd,Wd], normalised with mean / stdv) may be null - one launch writes what is asked for
 int launch_resize_u8(const unsigned char *src, size_t src_pitch, size_t src_bstride, unsigned char *dst_u8, size_t dst_pitch, size_t dst_bstride,

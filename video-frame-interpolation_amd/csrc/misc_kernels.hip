@@ -1283,19 +1283,29 @@ int launch_postprocess_u8(const float *src, unsigned char *dst, int B, int H, in
 }
 
 // ------------------------------------------------------------------------------------------
-// NV12 frames (include/emavfi.h, "NV12"): a pitched full-resolution Y plane and a pitched half-resolution plane of interleaved U,V
-// pairs, decoded to / encoded from the bytes the u8 kernels above read / write, in signed 32-bit fixed point with 20 fractional bits.
-//   preprocess_nv12  == preprocess_u8 of the decoded bytes (same fp32 /255, - mean, / std);
-//   postprocess_nv12 == the encode of the bytes postprocess_u8 would write (same float64 arithmetic, truncation, NaN -> 0).
-// One lane owns a block of 2 rows x 16 columns = 8 chroma pairs, in either of two forms with the same per-element arithmetic
-// (nv12_decode / nv12_byte / nv12_luma / nv12_chroma below):
-//   FAST   two 16-byte Y accesses, one 16-byte UV access, 16-byte accesses on the three fp32 planes; a wave's access to a row is
-//          consecutive addresses, every chroma pair is fetched / written once for its four pixels.  Conditions (nv12_fast_ok): both byte
-//          pointers, both pitches and both batch strides are multiples of 16, the fp32 pointer is 16-byte aligned and W % 4 == 0 (every
-//          fp32 row then starts on a 16-byte boundary) - and the block lies inside the frame (16 columns, 2 rows).
-//   SCALAR byte and dword accesses with the encode's edge clamp: every block when a FAST condition fails, otherwise the right (W % 16)
+// 4:2:0 frames (include/emavfi.h, "NV12", "HIGH BIT DEPTH", "PLANAR 4:2:0"): a pitched full-resolution Y plane and half-resolution chroma, decoded
+// to / encoded from what the u8 kernels above read / write.  One kernel pair, preprocess_yuv420_kernel<F> / postprocess_yuv420_kernel<F>, and
+// four formats F that differ in where a sample sits, never in what is computed from it:
+//   NV12                 Yuv8<true>    bytes; U and V interleaved in one plane
+//   P010 / P012 / P016   Yuv16<true>   little-endian 16-bit words, the sample in the word's top `depth` bits; U and V interleaved
+//   planar, depth 8      Yuv8<false>   bytes; a U plane and a V plane
+//   planar, depth > 8    Yuv16<false>  16-bit words, the sample in the word's low `depth` bits; a U plane and a V plane
+// Bytes go through nv12_decode / _norm / _byte / _luma / _chroma below (signed 32-bit fixed point, 20 fractional bits), words through
+// p010_elem.h's functions (signed 64-bit; the same text the host check runs), so that
+//   preprocess  == preprocess_u8 of the decoded bytes (same fp32 / 255, - mean, / std; 255 -> P = 2^depth - 1 above depth 8);
+//   postprocess == the encode of what postprocess_u8 would write (same float64 arithmetic, truncation, NaN -> 0).
+// One lane owns a block of 2 rows x 16 BYTES of Y = NX columns (16 of bytes, 8 of words) and the NX / 2 chroma pairs under it: 16 bytes of an
+// interleaved UV row, or 8 bytes of a U and 8 of a V row.  A planar chroma row is half as wide as an interleaved one, so the planar layouts take
+// the narrower chroma access and keep the block: chroma is 0.5 - 1 of the 13.5 - 15 bytes per pixel, 12 are fp32, and the fp32 pattern stays the
+// same for all four (profiles/r15_yuv420p_y4m.md measured the other choice, a block of 2 rows x 32 bytes).  A block takes either of two forms with
+// the same per-element arithmetic:
+//   FAST   two 16-byte Y accesses, one 16-byte UV access or an 8-byte U and an 8-byte V access, 16-byte accesses on the three fp32 planes; a
+//          wave's access to a row is consecutive addresses, every chroma pair is fetched / written once for its four pixels.  Conditions:
+//          yuv420_fast_ok below - and the block lies inside the frame (NX columns, 2 rows).
+//   SCALAR sample and dword accesses with the encode's edge clamp: every block when a FAST condition fails, otherwise the right (W % NX)
 //          and bottom (odd H) remainders only.
-// The byte side may be pinned host memory reached over PCIe, as for the u8 kernels.
+// No LDS, no waiting, one block per lane and a grid-stride loop: the launches are short-lived beside the persistent convolutions.  The sample
+// side may be pinned host memory reached over PCIe, as for the u8 kernels.
 // ------------------------------------------------------------------------------------------
 struct YuvCoef { int dec[5], enc[9], limited, rgb; };   // tables of include/emavfi.h; limited: Y - 16 floor / + 16 offset; rgb: channel 0 is R
 
@@ -1357,165 +1367,7 @@ __device__ __forceinline__ void nv12_chroma(const int sum[3], const YuvCoef &k, 
     V = nv12_clip(((k.enc[6] * r + k.enc[7] * g + k.enc[8] * b + (1 << 19)) >> 20) + 128);
 }
 
-struct Nv12Planes { size_t y_pitch, y_bstride, uv_pitch, uv_bstride; };
-
-__global__ __launch_bounds__(256) void preprocess_nv12_kernel(const unsigned char *__restrict__ ysrc, const unsigned char *__restrict__ uvsrc,
-                                                              float *__restrict__ dst, int B, int H, int W, Nv12Planes pl, Stats4 st,
-                                                              YuvCoef k, int fast)
-{
-    const size_t nbx = ((size_t)W + 15) / 16, nby = ((size_t)H + 1) / 2, plane = (size_t)H * W, total = (size_t)B * nby * nbx;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t b = i / (nby * nbx), rem = i - b * nby * nbx, by = rem / nbx;
-        const int y0 = (int)by * 2, x0 = (int)(rem - by * nbx) * 16;
-        const unsigned char *yp = ysrc + b * pl.y_bstride + (size_t)y0 * pl.y_pitch + x0;
-        const unsigned char *up = uvsrc + b * pl.uv_bstride + by * pl.uv_pitch + x0;   // pair x0 / 2 starts at byte x0
-        float *o = dst + b * 3 * plane + (size_t)y0 * W + x0;
-        if (fast && x0 + 16 <= W && y0 + 2 <= H) {
-            const uint4 uvq = *reinterpret_cast<const uint4 *>(up);
-            const unsigned uvw[4] = {uvq.x, uvq.y, uvq.z, uvq.w};
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const uint4 yq = *reinterpret_cast<const uint4 *>(yp + (size_t)r * pl.y_pitch);
-                const unsigned yw[4] = {yq.x, yq.y, yq.z, yq.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {   // 4 pixels = 2 chroma pairs = one dword of each plane
-                    f32x4 out[3];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const unsigned pair = uvw[q] >> (16 * (j >> 1));
-                        int ch[3];
-                        nv12_decode((int)((yw[q] >> (8 * j)) & 0xffu), (int)(pair & 0xffu), (int)((pair >> 8) & 0xffu), k, ch);
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) out[c][j] = nv12_norm(ch[c], st.mean[c], st.stdv[c]);
-                    }
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4 *>(o + c * plane + (size_t)r * W + q * 4) = out[c];
-                }
-            }
-            continue;
-        }
-        const int nx = min(16, W - x0), ny = min(2, H - y0);
-        for (int x = 0; x < nx; ++x) {
-            const int U = up[x & ~1], V = up[(x & ~1) + 1];
-            for (int r = 0; r < ny; ++r) {
-                int ch[3];
-                nv12_decode((int)yp[(size_t)r * pl.y_pitch + x], U, V, k, ch);
-                for (int c = 0; c < 3; ++c) o[c * plane + (size_t)r * W + x] = nv12_norm(ch[c], st.mean[c], st.stdv[c]);
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void postprocess_nv12_kernel(const float *__restrict__ src, unsigned char *__restrict__ ydst,
-                                                               unsigned char *__restrict__ uvdst, int B, int H, int W, Nv12Planes pl,
-                                                               Stats4d st, YuvCoef k, int denorm, int fast)
-{
-    const size_t nbx = ((size_t)W + 15) / 16, nby = ((size_t)H + 1) / 2, plane = (size_t)H * W, total = (size_t)B * nby * nbx;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t b = i / (nby * nbx), rem = i - b * nby * nbx, by = rem / nbx;
-        const int y0 = (int)by * 2, x0 = (int)(rem - by * nbx) * 16;
-        unsigned char *yp = ydst + b * pl.y_bstride + (size_t)y0 * pl.y_pitch + x0;
-        unsigned char *up = uvdst + b * pl.uv_bstride + by * pl.uv_pitch + x0;
-        const float *s = src + b * 3 * plane;
-        if (fast && x0 + 16 <= W && y0 + 2 <= H) {
-            unsigned yw[2][4], uvw[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                int by8[2][4][3];   // [row][pixel][channel]
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const f32x4 x = *reinterpret_cast<const f32x4 *>(s + c * plane + (size_t)(y0 + r) * W + x0 + q * 4);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) by8[r][j][c] = nv12_byte(x[j], st.mean[c], st.stdv[c], denorm);
-                    }
-#pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    unsigned w = 0u;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) w |= (unsigned)nv12_luma(by8[r][j], k) << (8 * j);
-                    yw[r][q] = w;
-                }
-                unsigned w = 0u;
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    int sum[3], U, V;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) sum[c] = by8[0][2 * p][c] + by8[0][2 * p + 1][c] + by8[1][2 * p][c] + by8[1][2 * p + 1][c];
-                    nv12_chroma(sum, k, U, V);
-                    w |= ((unsigned)U | ((unsigned)V << 8)) << (16 * p);
-                }
-                uvw[q] = w;
-            }
-            *reinterpret_cast<uint4 *>(yp) = make_uint4(yw[0][0], yw[0][1], yw[0][2], yw[0][3]);
-            *reinterpret_cast<uint4 *>(yp + pl.y_pitch) = make_uint4(yw[1][0], yw[1][1], yw[1][2], yw[1][3]);
-            *reinterpret_cast<uint4 *>(up) = make_uint4(uvw[0], uvw[1], uvw[2], uvw[3]);
-            continue;
-        }
-        const int nx = min(16, W - x0);
-        for (int x = 0; x < nx; x += 2) {
-            int sum[3] = {0, 0, 0}, U, V;
-            for (int r = 0; r < 2; ++r)
-                for (int dx = 0; dx < 2; ++dx) {
-                    const int yy = min(y0 + r, H - 1), xx = min(x0 + x + dx, W - 1);   // past the last row / column: clamped
-                    int ch[3];
-                    for (int c = 0; c < 3; ++c) {
-                        ch[c] = nv12_byte(s[c * plane + (size_t)yy * W + xx], st.mean[c], st.stdv[c], denorm);
-                        sum[c] += ch[c];
-                    }
-                    if (yy == y0 + r && xx == x0 + x + dx) yp[(size_t)r * pl.y_pitch + x + dx] = (unsigned char)nv12_luma(ch, k);
-                }
-            nv12_chroma(sum, k, U, V);
-            up[x] = (unsigned char)U;
-            up[x + 1] = (unsigned char)V;
-        }
-    }
-}
-
-static bool nv12_fast_ok(const void *y, const void *uv, const void *f32, int W, const Nv12Planes &pl)
-{
-    return (((uintptr_t)y | (uintptr_t)uv | (uintptr_t)f32 | pl.y_pitch | pl.y_bstride | pl.uv_pitch | pl.uv_bstride) & 15) == 0 && W % 4 == 0;
-}
-static int nv12_grid(int B, int H, int W)
-{
-    const size_t lanes = (size_t)B * (((size_t)H + 1) / 2) * (((size_t)W + 15) / 16);
-    return (int)std::min<size_t>((lanes + 255) / 256, (size_t)65535 * 4);
-}
-int launch_preprocess_nv12(const unsigned char *y, size_t y_pitch, size_t y_bstride, const unsigned char *uv, size_t uv_pitch, size_t uv_bstride,
-                           float *dst, int B, int H, int W, int standard, int order, const float *mean, const float *stdv, hipStream_t s)
-{
-    Stats4 st{};
-    for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
-    const Nv12Planes pl{y_pitch, y_bstride, uv_pitch, uv_bstride};
-    preprocess_nv12_kernel<<<nv12_grid(B, H, W), 256, 0, s>>>(y, uv, dst, B, H, W, pl, st, yuv_coef(standard, order),
-                                                              nv12_fast_ok(y, uv, dst, W, pl) ? 1 : 0);
-    return (int)hipGetLastError();
-}
-int launch_postprocess_nv12(const float *src, unsigned char *y, size_t y_pitch, size_t y_bstride, unsigned char *uv, size_t uv_pitch,
-                            size_t uv_bstride, int B, int H, int W, int standard, int order, const double *mean, const double *stdv, int denorm,
-                            hipStream_t s)
-{
-    Stats4d st{};
-    for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
-    const Nv12Planes pl{y_pitch, y_bstride, uv_pitch, uv_bstride};
-    postprocess_nv12_kernel<<<nv12_grid(B, H, W), 256, 0, s>>>(src, y, uv, B, H, W, pl, st, yuv_coef(standard, order), denorm,
-                                                               nv12_fast_ok(y, uv, src, W, pl) ? 1 : 0);
-    return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------
-// 16-bit-word frames, P010 / P012 / P016 (include/emavfi.h, "HIGH BIT DEPTH"): NV12's layout with one little-endian word per sample, the
-// sample in the word's top `depth` bits.  The colour arithmetic is p010_elem.h's (signed 64-bit fixed point, 20 fractional bits; the float
-// side is the u8 kernels' with 255 -> P), the same text the host check runs.
-// One lane owns a block of 2 rows x 8 columns = 4 chroma pairs, in either of two forms with the same per-element arithmetic:
-//   FAST   two 16-byte Y accesses, one 16-byte UV access (each pair serves its four pixels), twelve 16-byte accesses on the fp32 planes.
-//          Conditions (nv12_fast_ok): both word pointers, both pitches and both batch strides are multiples of 16, the fp32 pointer is
-//          16-byte aligned and W % 4 == 0 - and the block lies inside the frame (8 columns, 2 rows).
-//   SCALAR word and dword accesses with the encode's edge clamp: every block when a FAST condition fails, otherwise the right (W % 8)
-//          and bottom (odd H) remainders only.
-// No LDS, no waiting, one block per lane and a grid-stride loop: the launches are short-lived beside the persistent convolutions.
-// ------------------------------------------------------------------------------------------
+// yuv_coefficients with the depth as a parameter (it returns yuv_coefficients' tables at depth 8) and BT.2020
 void yuv_coefficients_depth(int standard, int depth, int dec[5], int enc[9])
 {
     const bool full = (standard & 1) != 0;
@@ -1539,286 +1391,137 @@ static P010Coef p010_coef(int standard, int depth, int order)
     return k;
 }
 
-__global__ __launch_bounds__(256) void preprocess_p010_kernel(const unsigned char *__restrict__ ysrc, const unsigned char *__restrict__ uvsrc,
-                                                              float *__restrict__ dst, int B, int H, int W, Nv12Planes pl, Stats4 st,
-                                                              P010Coef k, int fast)
-{
-    const size_t nbx = ((size_t)W + 7) / 8, nby = ((size_t)H + 1) / 2, plane = (size_t)H * W, total = (size_t)B * nby * nbx;
-    const float P = (float)k.P;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t b = i / (nby * nbx), rem = i - b * nby * nbx, by = rem / nbx;
-        const int y0 = (int)by * 2, x0 = (int)(rem - by * nbx) * 8;
-        const unsigned char *yp = ysrc + b * pl.y_bstride + (size_t)y0 * pl.y_pitch + (size_t)x0 * 2;
-        const unsigned char *up = uvsrc + b * pl.uv_bstride + by * pl.uv_pitch + (size_t)x0 * 2;   // pair x0 / 2 starts at byte 2 x0
-        float *o = dst + b * 3 * plane + (size_t)y0 * W + x0;
-        if (fast && x0 + 8 <= W && y0 + 2 <= H) {
-            const uint4 uvq = *reinterpret_cast<const uint4 *>(up);
-            const unsigned uvw[4] = {uvq.x, uvq.y, uvq.z, uvq.w};   // one pair per dword: U low, V high
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const uint4 yq = *reinterpret_cast<const uint4 *>(yp + (size_t)r * pl.y_pitch);
-                const unsigned yw[4] = {yq.x, yq.y, yq.z, yq.w};    // two pixels per dword
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {   // 4 pixels = 2 chroma pairs = one 16-byte access of each fp32 plane
-                    f32x4 out[3];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int p = q * 4 + j;
-                        const unsigned pair = uvw[p >> 1];
-                        int ch[3];
-                        p010_decode(p010_sample(yw[p >> 1] >> (16 * (p & 1)), k), p010_sample(pair, k), p010_sample(pair >> 16, k), k, ch);
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) out[c][j] = p010_norm(ch[c], P, st.mean[c], st.stdv[c]);
-                    }
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4 *>(o + c * plane + (size_t)r * W + q * 4) = out[c];
-                }
-            }
-            continue;
-        }
-        const int nx = min(8, W - x0), ny = min(2, H - y0);
-        for (int x = 0; x < nx; ++x) {
-            const unsigned short *pr = reinterpret_cast<const unsigned short *>(up) + (x & ~1);
-            const int U = p010_sample(pr[0], k), V = p010_sample(pr[1], k);
-            for (int r = 0; r < ny; ++r) {
-                int ch[3];
-                p010_decode(p010_sample(*reinterpret_cast<const unsigned short *>(yp + (size_t)r * pl.y_pitch + 2 * x), k), U, V, k, ch);
-                for (int c = 0; c < 3; ++c) o[c * plane + (size_t)r * W + x] = p010_norm(ch[c], P, st.mean[c], st.stdv[c]);
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void postprocess_p010_kernel(const float *__restrict__ src, unsigned char *__restrict__ ydst,
-                                                               unsigned char *__restrict__ uvdst, int B, int H, int W, Nv12Planes pl,
-                                                               Stats4d st, P010Coef k, int denorm, int fast)
-{
-    const size_t nbx = ((size_t)W + 7) / 8, nby = ((size_t)H + 1) / 2, plane = (size_t)H * W, total = (size_t)B * nby * nbx;
-    const double P = (double)k.P;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t b = i / (nby * nbx), rem = i - b * nby * nbx, by = rem / nbx;
-        const int y0 = (int)by * 2, x0 = (int)(rem - by * nbx) * 8;
-        unsigned char *yp = ydst + b * pl.y_bstride + (size_t)y0 * pl.y_pitch + (size_t)x0 * 2;
-        unsigned char *up = uvdst + b * pl.uv_bstride + by * pl.uv_pitch + (size_t)x0 * 2;
-        const float *s = src + b * 3 * plane;
-        if (fast && x0 + 8 <= W && y0 + 2 <= H) {
-            unsigned yw[2][4], uvw[4];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                int v[2][4][3];   // [row][pixel][channel]
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const f32x4 x = *reinterpret_cast<const f32x4 *>(s + c * plane + (size_t)(y0 + r) * W + x0 + q * 4);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[r][j][c] = p010_quant(x[j], st.mean[c], st.stdv[c], denorm, P);
-                    }
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)   // the low bits of every word: zero
-                        yw[r][q * 2 + h] = ((unsigned)p010_luma(v[r][2 * h], k) << k.shift) | ((unsigned)p010_luma(v[r][2 * h + 1], k) << (k.shift + 16));
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    int sum[3], U, V;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) sum[c] = v[0][2 * p][c] + v[0][2 * p + 1][c] + v[1][2 * p][c] + v[1][2 * p + 1][c];
-                    p010_chroma(sum, k, U, V);
-                    uvw[q * 2 + p] = ((unsigned)U << k.shift) | ((unsigned)V << (k.shift + 16));
-                }
-            }
-            *reinterpret_cast<uint4 *>(yp) = make_uint4(yw[0][0], yw[0][1], yw[0][2], yw[0][3]);
-            *reinterpret_cast<uint4 *>(yp + pl.y_pitch) = make_uint4(yw[1][0], yw[1][1], yw[1][2], yw[1][3]);
-            *reinterpret_cast<uint4 *>(up) = make_uint4(uvw[0], uvw[1], uvw[2], uvw[3]);
-            continue;
-        }
-        const int nx = min(8, W - x0);
-        for (int x = 0; x < nx; x += 2) {
-            int sum[3] = {0, 0, 0}, U, V;
-            for (int r = 0; r < 2; ++r)
-                for (int dx = 0; dx < 2; ++dx) {
-                    const int yy = min(y0 + r, H - 1), xx = min(x0 + x + dx, W - 1);   // past the last row / column: clamped
-                    int ch[3];
-                    for (int c = 0; c < 3; ++c) {
-                        ch[c] = p010_quant(s[c * plane + (size_t)yy * W + xx], st.mean[c], st.stdv[c], denorm, P);
-                        sum[c] += ch[c];
-                    }
-                    if (yy == y0 + r && xx == x0 + x + dx)
-                        *reinterpret_cast<unsigned short *>(yp + (size_t)r * pl.y_pitch + 2 * (x + dx)) = (unsigned short)(p010_luma(ch, k) << k.shift);
-                }
-            p010_chroma(sum, k, U, V);
-            unsigned short *pr = reinterpret_cast<unsigned short *>(up) + x;
-            pr[0] = (unsigned short)(U << k.shift);
-            pr[1] = (unsigned short)(V << k.shift);
-        }
-    }
-}
-
-static int p010_grid(int B, int H, int W)
-{
-    const size_t lanes = (size_t)B * (((size_t)H + 1) / 2) * (((size_t)W + 7) / 8);
-    return (int)std::min<size_t>((lanes + 255) / 256, (size_t)65535 * 4);
-}
-int launch_preprocess_p010(const void *y, size_t y_pitch, size_t y_bstride, const void *uv, size_t uv_pitch, size_t uv_bstride, float *dst, int B,
-                           int H, int W, int depth, int standard, int order, const float *mean, const float *stdv, hipStream_t s)
-{
-    Stats4 st{};
-    for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
-    const Nv12Planes pl{y_pitch, y_bstride, uv_pitch, uv_bstride};
-    preprocess_p010_kernel<<<p010_grid(B, H, W), 256, 0, s>>>((const unsigned char *)y, (const unsigned char *)uv, dst, B, H, W, pl, st,
-                                                              p010_coef(standard, depth, order), nv12_fast_ok(y, uv, dst, W, pl) ? 1 : 0);
-    return (int)hipGetLastError();
-}
-int launch_postprocess_p010(const float *src, void *y, size_t y_pitch, size_t y_bstride, void *uv, size_t uv_pitch, size_t uv_bstride, int B, int H,
-                            int W, int depth, int standard, int order, const double *mean, const double *stdv, int denorm, hipStream_t s)
-{
-    Stats4d st{};
-    for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
-    const Nv12Planes pl{y_pitch, y_bstride, uv_pitch, uv_bstride};
-    postprocess_p010_kernel<<<p010_grid(B, H, W), 256, 0, s>>>(src, (unsigned char *)y, (unsigned char *)uv, B, H, W, pl, st,
-                                                               p010_coef(standard, depth, order), denorm, nv12_fast_ok(y, uv, src, W, pl) ? 1 : 0);
-    return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------
-// Planar 4:2:0 frames (include/emavfi.h, "PLANAR 4:2:0"): a Y plane and separate half-resolution U and V planes, bytes (depth 8) or 16-bit
-// words with the sample in the LOW `depth` bits.  Nothing is computed here that NV12 / P010 do not compute: depth 8 calls nv12_decode / _norm /
-// _byte / _luma / _chroma, the deeper formats p010_elem.h's functions; only where a sample sits differs (yuv420p_elem.h).
-// One lane owns NV12's / P010's block, 2 rows x 16 BYTES of Y = NX columns (16 at depth 8, 8 above), and the NX / 2 samples = 8 bytes of a U and
-// of a V row under it.  A planar chroma row is half as wide as NV12's, so either the chroma accesses halve or the block doubles.  Chroma is
-// 0.5 - 1 of the 13.5 - 15 bytes per pixel, 12 are fp32: chroma takes the narrower access, and the fp32 side keeps NV12's / P010's pattern.
-// The other choice, 2 rows x 32 bytes of Y with 16-byte chroma accesses, is kept as a measurement variant only - `make TAG=_block32
-// EXTRA=-DEMAVFI_YUV420P_BLOCK32=1` builds libemavfi_block32.so, which tools/bench_yuv420p.py --ab-lib times beside the product library in one
-// process; profiles/r15_yuv420p_y4m.md holds both.  The product build never defines the macro.
-//   FAST   two 16-byte Y accesses, one 8-byte U and one 8-byte V access, 16-byte accesses on the three fp32 planes.  Conditions
-//          (yuv420p_fast_ok): the Y pointer, its pitch and (B > 1) its batch stride are multiples of 16, those of U and V multiples of 8, the fp32
-//          pointer is 16-byte aligned and W % 4 == 0 - and the block lies inside the frame (NX columns, 2 rows).
-//   SCALAR sample and dword accesses with the encode's edge clamp: every block when a FAST condition fails, otherwise the right (W % NX)
-//          and bottom (odd H) remainders only.
-// No LDS, no waiting, one block per lane and a grid-stride loop, as for NV12 / P010.
-// ------------------------------------------------------------------------------------------
-struct Yuv420pPlanes { size_t y_pitch, y_bstride, u_pitch, u_bstride, v_pitch, v_bstride; };
-#ifdef EMAVFI_YUV420P_BLOCK32
-constexpr int kYuv420pRowBytes = 32;   // measurement variant: 2 rows x 32 bytes of Y, 16 bytes of U and of V
-#else
-constexpr int kYuv420pRowBytes = 16;   // bytes of a Y row in a lane's block; half as many of a U and of a V row
-#endif
-// N = 2, 4 or 8 consecutive dwords at an address aligned to min(4 N, 16) bytes, moved 8 or 16 bytes at a time
+// 2 or 4 consecutive dwords at an 8- / 16-byte aligned address, moved in one access
 template <int N> __device__ __forceinline__ void load_dwords(const unsigned char *p, unsigned (&w)[N])
 {
+    static_assert(N == 2 || N == 4, "an 8- or a 16-byte access");
     if constexpr (N == 2) {
         const uint2 q = *reinterpret_cast<const uint2 *>(p);
         w[0] = q.x; w[1] = q.y;
     } else {
-#pragma unroll
-        for (int i = 0; i < N; i += 4) {
-            const uint4 q = *reinterpret_cast<const uint4 *>(p + 4 * i);
-            w[i] = q.x; w[i + 1] = q.y; w[i + 2] = q.z; w[i + 3] = q.w;
-        }
+        const uint4 q = *reinterpret_cast<const uint4 *>(p);
+        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
     }
 }
 template <int N> __device__ __forceinline__ void store_dwords(unsigned char *p, const unsigned (&w)[N])
 {
-    if constexpr (N == 2) {
-        *reinterpret_cast<uint2 *>(p) = make_uint2(w[0], w[1]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; i += 4) *reinterpret_cast<uint4 *>(p + 4 * i) = make_uint4(w[i], w[i + 1], w[i + 2], w[i + 3]);
-    }
+    static_assert(N == 2 || N == 4, "an 8- or a 16-byte access");
+    if constexpr (N == 2) *reinterpret_cast<uint2 *>(p) = make_uint2(w[0], w[1]);
+    else *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// the two sample formats: the type in memory and the per-element functions the samples go through
-struct Planar8 {
+// The four formats.  A format names the type in memory, whether U and V share a plane (SEMI), how a sample is read from its word and written
+// back, and the per-element functions the samples go through.
+// bytes, NV12 (SEMI) and planar depth 8: 32-bit fixed point
+template <bool SEMI> struct Yuv8 {
     typedef unsigned char T;
+    static constexpr bool semi = SEMI;
     YuvCoef k;
-    __device__ __forceinline__ int sample(unsigned w) const { return yuv420p_sample(w, 255); }
+    __device__ __forceinline__ int sample(unsigned w) const { return (int)w; }
+    __device__ __forceinline__ unsigned word(int v) const { return (unsigned)v; }
     __device__ __forceinline__ void decode(int Y, int U, int V, int ch[3]) const { nv12_decode(Y, U, V, k, ch); }
     __device__ __forceinline__ float norm(int v, float mean, float stdv) const { return nv12_norm(v, mean, stdv); }
     __device__ __forceinline__ int quant(float x, double mean, double stdv, int denorm) const { return nv12_byte(x, mean, stdv, denorm); }
     __device__ __forceinline__ int luma(const int ch[3]) const { return nv12_luma(ch, k); }
     __device__ __forceinline__ void chroma(const int sum[3], int &U, int &V) const { nv12_chroma(sum, k, U, V); }
 };
-struct Planar16 {
+// 16-bit words, P010 / P012 / P016 (SEMI: the sample in the word's TOP `depth` bits, the low bits written as zero) and planar depth 10 / 12 / 16
+// (the sample in the LOW `depth` bits, the high bits written as zero): p010_elem.h's 64-bit fixed point
+template <bool SEMI> struct Yuv16 {
     typedef unsigned short T;
+    static constexpr bool semi = SEMI;
     P010Coef k;
-    __device__ __forceinline__ int sample(unsigned w) const { return yuv420p_sample(w, k.P); }
+    __device__ __forceinline__ int sample(unsigned w) const { return SEMI ? p010_sample(w, k) : yuv420p_sample(w, k.P); }
+    __device__ __forceinline__ unsigned word(int v) const { return SEMI ? (unsigned)v << k.shift : (unsigned)v; }
     __device__ __forceinline__ void decode(int Y, int U, int V, int ch[3]) const { p010_decode(Y, U, V, k, ch); }
     __device__ __forceinline__ float norm(int v, float mean, float stdv) const { return p010_norm(v, (float)k.P, mean, stdv); }
     __device__ __forceinline__ int quant(float x, double mean, double stdv, int denorm) const { return p010_quant(x, mean, stdv, denorm, (double)k.P); }
     __device__ __forceinline__ int luma(const int ch[3]) const { return p010_luma(ch, k); }
     __device__ __forceinline__ void chroma(const int sum[3], int &U, int &V) const { p010_chroma(sum, k, U, V); }
 };
+// What the kernels below derive from a format.  Chroma sample c of a lane's row piece is sample CS c of the U piece and sample CS c + VO of the
+// V piece (yuv420p_get / yuv420p_put); with SEMI the V piece is the U piece, one sample further on.
+template <class F> struct Yuv420Block {
+    static constexpr int ES = (int)sizeof(typename F::T), BITS = 8 * ES;
+    static constexpr int NX = 16 / ES, NW = 4;              // columns and dwords of a lane's 16 bytes of a Y row
+    static constexpr int CS = F::semi ? 2 : 1, VO = F::semi ? 1 : 0;
+    static constexpr int NC = NW * CS / 2;                  // dwords of a lane's piece of a chroma row: 16 bytes of UV, or 8 of U and 8 of V
+};
 
 template <class F>
-__global__ __launch_bounds__(256) void preprocess_yuv420p_kernel(const unsigned char *__restrict__ ysrc, const unsigned char *__restrict__ usrc,
-                                                                 const unsigned char *__restrict__ vsrc, float *__restrict__ dst, int B, int H,
-                                                                 int W, Yuv420pPlanes pl, Stats4 st, F f, int fast)
+__global__ __launch_bounds__(256) void preprocess_yuv420_kernel(const unsigned char *__restrict__ ysrc, const unsigned char *__restrict__ usrc,
+                                                                const unsigned char *__restrict__ vsrc, float *__restrict__ dst, int B, int H,
+                                                                int W, Yuv420Strides pl, Stats4 st, F f, int fast)
 {
     typedef typename F::T T;
-    constexpr int ES = (int)sizeof(T), BITS = 8 * ES, NX = kYuv420pRowBytes / ES, NW = kYuv420pRowBytes / 4;
+    typedef Yuv420Block<F> K;
+    constexpr int ES = K::ES, BITS = K::BITS, NX = K::NX, CS = K::CS;
     const size_t nbx = ((size_t)W + NX - 1) / NX, nby = ((size_t)H + 1) / 2, plane = (size_t)H * W, total = (size_t)B * nby * nbx;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t b = i / (nby * nbx), rem = i - b * nby * nbx, by = rem / nbx;
         const int y0 = (int)by * 2, x0 = (int)(rem - by * nbx) * NX;
-        const unsigned char *yp = ysrc + b * pl.y_bstride + (size_t)y0 * pl.y_pitch + (size_t)x0 * ES;
-        const unsigned char *up = usrc + b * pl.u_bstride + by * pl.u_pitch + (size_t)(x0 / 2) * ES;   // chroma sample x0 / 2 of row y0 / 2
-        const unsigned char *vp = vsrc + b * pl.v_bstride + by * pl.v_pitch + (size_t)(x0 / 2) * ES;
+        const unsigned char *yp = ysrc + b * pl.bstride[0] + (size_t)y0 * pl.pitch[0] + (size_t)x0 * ES;
+        const unsigned char *up = usrc + b * pl.bstride[1] + by * pl.pitch[1] + (size_t)(x0 / 2) * CS * ES;   // chroma sample x0 / 2 of row y0 / 2
+        const unsigned char *vp = F::semi ? up + ES : vsrc + b * pl.bstride[2] + by * pl.pitch[2] + (size_t)(x0 / 2) * ES;
         float *o = dst + b * 3 * plane + (size_t)y0 * W + x0;
         if (fast && x0 + NX <= W && y0 + 2 <= H) {
-            unsigned uw[NW / 2], vw[NW / 2];
+            unsigned uw[K::NC], vw[K::NC];
             load_dwords(up, uw);
-            load_dwords(vp, vw);
+            if constexpr (!F::semi) load_dwords(vp, vw);
+            const unsigned *vq = F::semi ? uw : vw;
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                unsigned yw[NW];
-                load_dwords(yp + (size_t)r * pl.y_pitch, yw);
+                unsigned yw[K::NW];
+                load_dwords(yp + (size_t)r * pl.pitch[0], yw);
 #pragma unroll
-                for (int q = 0; q < NX / 4; ++q) {   // 4 pixels = 2 chroma samples of each plane = one 16-byte access of each fp32 plane
+                for (int q = 0; q < NX / 4; ++q) {   // 4 pixels = 2 chroma samples of each kind = one 16-byte access of each fp32 plane
                     f32x4 out[3];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const int p = q * 4 + j;
+                        const int p = q * 4 + j, c = CS * (p >> 1);
                         int ch[3];
-                        f.decode(f.sample(yuv420p_get<BITS>(yw, p)), f.sample(yuv420p_get<BITS>(uw, p >> 1)), f.sample(yuv420p_get<BITS>(vw, p >> 1)), ch);
+                        f.decode(f.sample(yuv420p_get<BITS>(yw, p)), f.sample(yuv420p_get<BITS>(uw, c)), f.sample(yuv420p_get<BITS>(vq, c + K::VO)), ch);
 #pragma unroll
-                        for (int c = 0; c < 3; ++c) out[c][j] = f.norm(ch[c], st.mean[c], st.stdv[c]);
+                        for (int cc = 0; cc < 3; ++cc) out[cc][j] = f.norm(ch[cc], st.mean[cc], st.stdv[cc]);
                     }
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4 *>(o + c * plane + (size_t)r * W + q * 4) = out[c];
+                    for (int cc = 0; cc < 3; ++cc) *reinterpret_cast<f32x4 *>(o + cc * plane + (size_t)r * W + q * 4) = out[cc];
                 }
             }
             continue;
         }
         const int nx = min(NX, W - x0), ny = min(2, H - y0);
         for (int x = 0; x < nx; ++x) {
-            const int U = f.sample(reinterpret_cast<const T *>(up)[x >> 1]), V = f.sample(reinterpret_cast<const T *>(vp)[x >> 1]);
+            const int c = CS * (x >> 1);
+            const int U = f.sample(reinterpret_cast<const T *>(up)[c]), V = f.sample(reinterpret_cast<const T *>(vp)[c]);
             for (int r = 0; r < ny; ++r) {
                 int ch[3];
-                f.decode(f.sample(reinterpret_cast<const T *>(yp + (size_t)r * pl.y_pitch)[x]), U, V, ch);
-                for (int c = 0; c < 3; ++c) o[c * plane + (size_t)r * W + x] = f.norm(ch[c], st.mean[c], st.stdv[c]);
+                f.decode(f.sample(reinterpret_cast<const T *>(yp + (size_t)r * pl.pitch[0])[x]), U, V, ch);
+                for (int cc = 0; cc < 3; ++cc) o[cc * plane + (size_t)r * W + x] = f.norm(ch[cc], st.mean[cc], st.stdv[cc]);
             }
         }
     }
 }
 
 template <class F>
-__global__ __launch_bounds__(256) void postprocess_yuv420p_kernel(const float *__restrict__ src, unsigned char *__restrict__ ydst,
-                                                                  unsigned char *__restrict__ udst, unsigned char *__restrict__ vdst, int B, int H,
-                                                                  int W, Yuv420pPlanes pl, Stats4d st, F f, int denorm, int fast)
+__global__ __launch_bounds__(256) void postprocess_yuv420_kernel(const float *__restrict__ src, unsigned char *__restrict__ ydst,
+                                                                 unsigned char *__restrict__ udst, unsigned char *__restrict__ vdst, int B, int H,
+                                                                 int W, Yuv420Strides pl, Stats4d st, F f, int denorm, int fast)
 {
     typedef typename F::T T;
-    constexpr int ES = (int)sizeof(T), BITS = 8 * ES, NX = kYuv420pRowBytes / ES, NW = kYuv420pRowBytes / 4;
+    typedef Yuv420Block<F> K;
+    constexpr int ES = K::ES, BITS = K::BITS, NX = K::NX, CS = K::CS;
     const size_t nbx = ((size_t)W + NX - 1) / NX, nby = ((size_t)H + 1) / 2, plane = (size_t)H * W, total = (size_t)B * nby * nbx;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t b = i / (nby * nbx), rem = i - b * nby * nbx, by = rem / nbx;
         const int y0 = (int)by * 2, x0 = (int)(rem - by * nbx) * NX;
-        unsigned char *yp = ydst + b * pl.y_bstride + (size_t)y0 * pl.y_pitch + (size_t)x0 * ES;
-        unsigned char *up = udst + b * pl.u_bstride + by * pl.u_pitch + (size_t)(x0 / 2) * ES;
-        unsigned char *vp = vdst + b * pl.v_bstride + by * pl.v_pitch + (size_t)(x0 / 2) * ES;
+        unsigned char *yp = ydst + b * pl.bstride[0] + (size_t)y0 * pl.pitch[0] + (size_t)x0 * ES;
+        unsigned char *up = udst + b * pl.bstride[1] + by * pl.pitch[1] + (size_t)(x0 / 2) * CS * ES;
+        unsigned char *vp = F::semi ? up + ES : vdst + b * pl.bstride[2] + by * pl.pitch[2] + (size_t)(x0 / 2) * ES;
         const float *s = src + b * 3 * plane;
         if (fast && x0 + NX <= W && y0 + 2 <= H) {
-            unsigned yw[2][NW] = {}, uw[NW / 2] = {}, vw[NW / 2] = {};   // at depth > 8 the high bits of every word stay zero
+            unsigned yw[2][K::NW] = {}, uw[K::NC] = {}, vw[K::NC] = {};   // the bits of a word that f.word() leaves out stay zero
+            unsigned *vq = F::semi ? uw : vw;
 #pragma unroll
             for (int q = 0; q < NX / 4; ++q) {
                 int v[2][4][3];   // [row][pixel][channel]
@@ -1833,21 +1536,21 @@ __global__ __launch_bounds__(256) void postprocess_yuv420p_kernel(const float *_
 #pragma unroll
                 for (int r = 0; r < 2; ++r)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) yuv420p_put<BITS>(yw[r], q * 4 + j, (unsigned)f.luma(v[r][j]));
+                    for (int j = 0; j < 4; ++j) yuv420p_put<BITS>(yw[r], q * 4 + j, f.word(f.luma(v[r][j])));
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
                     int sum[3], U, V;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) sum[c] = v[0][2 * p][c] + v[0][2 * p + 1][c] + v[1][2 * p][c] + v[1][2 * p + 1][c];
                     f.chroma(sum, U, V);
-                    yuv420p_put<BITS>(uw, q * 2 + p, (unsigned)U);
-                    yuv420p_put<BITS>(vw, q * 2 + p, (unsigned)V);
+                    yuv420p_put<BITS>(uw, CS * (q * 2 + p), f.word(U));
+                    yuv420p_put<BITS>(vq, CS * (q * 2 + p) + K::VO, f.word(V));
                 }
             }
 #pragma unroll
-            for (int r = 0; r < 2; ++r) store_dwords(yp + (size_t)r * pl.y_pitch, yw[r]);
+            for (int r = 0; r < 2; ++r) store_dwords(yp + (size_t)r * pl.pitch[0], yw[r]);
             store_dwords(up, uw);
-            store_dwords(vp, vw);
+            if constexpr (!F::semi) store_dwords(vp, vw);
             continue;
         }
         const int nx = min(NX, W - x0);
@@ -1861,56 +1564,68 @@ __global__ __launch_bounds__(256) void postprocess_yuv420p_kernel(const float *_
                         ch[c] = f.quant(s[c * plane + (size_t)yy * W + xx], st.mean[c], st.stdv[c], denorm);
                         sum[c] += ch[c];
                     }
-                    if (yy == y0 + r && xx == x0 + x + dx) reinterpret_cast<T *>(yp + (size_t)r * pl.y_pitch)[x + dx] = (T)f.luma(ch);
+                    if (yy == y0 + r && xx == x0 + x + dx) reinterpret_cast<T *>(yp + (size_t)r * pl.pitch[0])[x + dx] = (T)f.word(f.luma(ch));
                 }
             f.chroma(sum, U, V);
-            reinterpret_cast<T *>(up)[x >> 1] = (T)U;
-            reinterpret_cast<T *>(vp)[x >> 1] = (T)V;
+            reinterpret_cast<T *>(up)[CS * (x >> 1)] = (T)f.word(U);
+            reinterpret_cast<T *>(vp)[CS * (x >> 1)] = (T)f.word(V);
         }
     }
 }
 
-static bool yuv420p_fast_ok(const void *y, const void *u, const void *v, const void *f32, int B, int W, const Yuv420pPlanes &pl)
+// FAST needs, of every plane, the pointer, the pitch and (B > 1) the batch stride to be multiples of the plane's access width - 16 bytes of Y and
+// of interleaved UV, 8 of planar U and V -, a 16-byte aligned fp32 pointer and W % 4 == 0 (every fp32 row then starts on a 16-byte boundary).
+// A batch stride is never used at b == 0, so at B == 1 it is not looked at.  (NV12 and P010 looked at it until the formats got one predicate: a
+// B == 1 call with an unaligned batch stride took SCALAR then and takes FAST now.  Both paths write the same bytes.)
+static bool yuv420_fast_ok(const Yuv420Frame &fr, const void *f32, int B, int W)
 {
-    const size_t ybs = B > 1 ? pl.y_bstride : 0, cbs = B > 1 ? pl.u_bstride | pl.v_bstride : 0;
-    const size_t cmask = kYuv420pRowBytes / 2 - 1;   // a lane's chroma access: 8 bytes
-    return (((uintptr_t)y | (uintptr_t)f32 | pl.y_pitch | ybs) & 15) == 0 && (((uintptr_t)u | (uintptr_t)v | pl.u_pitch | pl.v_pitch | cbs) & cmask) == 0 &&
-           W % 4 == 0;
+    const bool semi = fr.layout == YUV420_SEMIPLANAR;
+    size_t bad = (uintptr_t)f32 & 15;
+    for (int p = 0; p < (semi ? 2 : 3); ++p)
+        bad |= ((uintptr_t)fr.plane[p] | fr.strides.pitch[p] | (B > 1 ? fr.strides.bstride[p] : 0)) & ((p == 0 || semi) ? 15 : 7);
+    return bad == 0 && W % 4 == 0;
 }
-static int yuv420p_grid(int B, int H, int W, int depth)
+static int yuv420_grid(int B, int H, int W, int depth)
 {
-    const size_t nx = kYuv420pRowBytes / (depth == 8 ? 1 : 2), lanes = (size_t)B * (((size_t)H + 1) / 2) * (((size_t)W + nx - 1) / nx);
+    const size_t nx = depth == 8 ? 16 : 8, lanes = (size_t)B * (((size_t)H + 1) / 2) * (((size_t)W + nx - 1) / nx);
     return (int)std::min<size_t>((lanes + 255) / 256, (size_t)65535 * 4);
 }
-int launch_preprocess_yuv420p(const void *y, size_t y_pitch, size_t y_bstride, const void *u, size_t u_pitch, size_t u_bstride, const void *v,
-                              size_t v_pitch, size_t v_bstride, float *dst, int B, int H, int W, int depth, int standard, int order,
-                              const float *mean, const float *stdv, hipStream_t s)
+int launch_preprocess_yuv420(const Yuv420Frame &src, float *dst, int B, int H, int W, int standard, int order, const float *mean, const float *stdv,
+                             hipStream_t s)
 {
     Stats4 st{};
     for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
-    const Yuv420pPlanes pl{y_pitch, y_bstride, u_pitch, u_bstride, v_pitch, v_bstride};
-    const unsigned char *yb = (const unsigned char *)y, *ub = (const unsigned char *)u, *vb = (const unsigned char *)v;
-    const int grid = yuv420p_grid(B, H, W, depth), fast = yuv420p_fast_ok(y, u, v, dst, B, W, pl) ? 1 : 0;
-    if (depth == 8)
-        preprocess_yuv420p_kernel<Planar8><<<grid, 256, 0, s>>>(yb, ub, vb, dst, B, H, W, pl, st, Planar8{yuv_coef(standard, order)}, fast);
-    else
-        preprocess_yuv420p_kernel<Planar16><<<grid, 256, 0, s>>>(yb, ub, vb, dst, B, H, W, pl, st, Planar16{p010_coef(standard, depth, order)}, fast);
+    const unsigned char *y = (const unsigned char *)src.plane[0], *u = (const unsigned char *)src.plane[1], *v = (const unsigned char *)src.plane[2];
+    const int grid = yuv420_grid(B, H, W, src.depth), fast = yuv420_fast_ok(src, dst, B, W) ? 1 : 0;
+    const bool semi = src.layout == YUV420_SEMIPLANAR;
+    if (src.depth == 8) {
+        const YuvCoef k = yuv_coef(standard, order);
+        if (semi) preprocess_yuv420_kernel<<<grid, 256, 0, s>>>(y, u, v, dst, B, H, W, src.strides, st, Yuv8<true>{k}, fast);
+        else preprocess_yuv420_kernel<<<grid, 256, 0, s>>>(y, u, v, dst, B, H, W, src.strides, st, Yuv8<false>{k}, fast);
+    } else {
+        const P010Coef k = p010_coef(standard, src.depth, order);
+        if (semi) preprocess_yuv420_kernel<<<grid, 256, 0, s>>>(y, u, v, dst, B, H, W, src.strides, st, Yuv16<true>{k}, fast);
+        else preprocess_yuv420_kernel<<<grid, 256, 0, s>>>(y, u, v, dst, B, H, W, src.strides, st, Yuv16<false>{k}, fast);
+    }
     return (int)hipGetLastError();
 }
-int launch_postprocess_yuv420p(const float *src, void *y, size_t y_pitch, size_t y_bstride, void *u, size_t u_pitch, size_t u_bstride, void *v,
-                               size_t v_pitch, size_t v_bstride, int B, int H, int W, int depth, int standard, int order, const double *mean,
-                               const double *stdv, int denorm, hipStream_t s)
+int launch_postprocess_yuv420(const float *src, const Yuv420Frame &dst, int B, int H, int W, int standard, int order, const double *mean,
+                              const double *stdv, int denorm, hipStream_t s)
 {
     Stats4d st{};
     for (int c = 0; c < 3; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
-    const Yuv420pPlanes pl{y_pitch, y_bstride, u_pitch, u_bstride, v_pitch, v_bstride};
-    unsigned char *yb = (unsigned char *)y, *ub = (unsigned char *)u, *vb = (unsigned char *)v;
-    const int grid = yuv420p_grid(B, H, W, depth), fast = yuv420p_fast_ok(y, u, v, src, B, W, pl) ? 1 : 0;
-    if (depth == 8)
-        postprocess_yuv420p_kernel<Planar8><<<grid, 256, 0, s>>>(src, yb, ub, vb, B, H, W, pl, st, Planar8{yuv_coef(standard, order)}, denorm, fast);
-    else
-        postprocess_yuv420p_kernel<Planar16><<<grid, 256, 0, s>>>(src, yb, ub, vb, B, H, W, pl, st, Planar16{p010_coef(standard, depth, order)}, denorm,
-                                                                  fast);
+    unsigned char *y = (unsigned char *)dst.plane[0], *u = (unsigned char *)dst.plane[1], *v = (unsigned char *)dst.plane[2];
+    const int grid = yuv420_grid(B, H, W, dst.depth), fast = yuv420_fast_ok(dst, src, B, W) ? 1 : 0;
+    const bool semi = dst.layout == YUV420_SEMIPLANAR;
+    if (dst.depth == 8) {
+        const YuvCoef k = yuv_coef(standard, order);
+        if (semi) postprocess_yuv420_kernel<<<grid, 256, 0, s>>>(src, y, u, v, B, H, W, dst.strides, st, Yuv8<true>{k}, denorm, fast);
+        else postprocess_yuv420_kernel<<<grid, 256, 0, s>>>(src, y, u, v, B, H, W, dst.strides, st, Yuv8<false>{k}, denorm, fast);
+    } else {
+        const P010Coef k = p010_coef(standard, dst.depth, order);
+        if (semi) postprocess_yuv420_kernel<<<grid, 256, 0, s>>>(src, y, u, v, B, H, W, dst.strides, st, Yuv16<true>{k}, denorm, fast);
+        else postprocess_yuv420_kernel<<<grid, 256, 0, s>>>(src, y, u, v, B, H, W, dst.strides, st, Yuv16<false>{k}, denorm, fast);
+    }
     return (int)hipGetLastError();
 }
 
@@ -1933,6 +1648,7 @@ int launch_postprocess_yuv420p(const float *src, void *y, size_t y_pitch, size_t
 // A tile whose span does not fit RS_SPAN_BYTES (reductions beyond about 3:1) reads its four taps from global memory instead.
 // ------------------------------------------------------------------------------------------
 constexpr int RS_SPAN_BYTES = 40 * 1024;
+struct Nv12Planes { size_t y_pitch, y_bstride, uv_pitch, uv_bstride; };
 
 // one axis: destination index d of nd <- source indices i0, min(i0 + 1, ns - 1) with weight w / 2048 on the second
 __device__ __forceinline__ void resize_axis(int d, int nd, int ns, int &i0, int &w)

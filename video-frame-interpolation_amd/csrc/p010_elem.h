@@ -1,5 +1,5 @@
 // The per-element functions of the high-bit-depth colour definition (include/emavfi.h, "HIGH BIT DEPTH"): constants, decode, normalise,
-// quantise, luma, chroma.  One text for the kernels (misc_kernels.hip) and for the host check (tests/host/host_check_p010.cpp, a plain
+// quantise, luma, chroma.  One text for the kernels (misc_kernels.hip: the Yuv16 formats of preprocess_yuv420_kernel / postprocess_yuv420_kernel) and for the host check (tests/host/host_check_p010.cpp, a plain
 // C++ program).  Integers are signed 64-bit fixed point with 20 fractional bits: a coefficient fits 32 bits, its operand 18, so every
 // product is one 32 x 32 -> 64 multiply-add; the float side is preprocess_u8's / postprocess_u8's arithmetic with 255 -> P.
 #pragma once

@@ -1,6 +1,8 @@
 // What the planar 4:2:0 formats (include/emavfi.h, "PLANAR 4:2:0") add to the per-element functions of NV12 / P010: where a sample sits.
-// One text for the kernels (misc_kernels.hip) and for the host check (tests/host/host_check_yuv420p.cpp, a plain C++ program).  The colour
-// arithmetic itself is not here: the kernels call nv12_* (depth 8) and p010_elem.h (above) on the samples these functions hand them.
+// One text for the kernels (misc_kernels.hip: preprocess_yuv420_kernel / postprocess_yuv420_kernel, whose four formats - planar and interleaved,
+// bytes and words - all read and write a row piece through yuv420p_get / yuv420p_put) and for the host check
+// (tests/host/host_check_yuv420p.cpp, a plain C++ program).  The colour arithmetic itself is not here: the kernels call nv12_* (depth 8) and
+// p010_elem.h (above) on the samples these functions hand them.
 #pragma once
 #include "p010_elem.h"
 
