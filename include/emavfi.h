@@ -282,7 +282,14 @@ int emavfi_forward_launches_adaptive(int in_channels, int mid_channels, int num_
 
 /* EMA_VFI.warp(frame2, feature, flow), ema_vfi.py:149-171 (grid build + normalise +
  * F.grid_sample bilinear/zeros/align_corners=True), fused into one HBM-bound kernel.
- * frame2 [B,C,H,W], flow [B,2,H,W] (channel 0 = dx, 1 = dy, pixels), out [B,C,H,W]; fp32. */
+ * frame2 [B,C,H,W], flow [B,2,H,W] (channel 0 = dx, 1 = dy, pixels), out [B,C,H,W]; fp32.
+ * NON-FINITE VALUES, as ATen's CPU grid_sample (the same contract holds for the warp step inside every forward):
+ *   flow:   a finite coordinate outside the image samples zeros; a NaN or infinite flow - or one so large that the reference's own
+ *           2 * (x + flow) overflows - gives NaN in every channel of that pixel.
+ *   frame2: a corner of the bilinear footprint that lies outside [0, size - 1] contributes exactly nothing, whatever frame2 holds
+ *           anywhere: a sample with all four corners outside is 0 even beside a NaN or an infinity.  A corner INSIDE multiplies in
+ *           IEEE arithmetic, a zero weight included: a NaN or infinite pixel reaches every output whose footprint covers it
+ *           (NaN * 0 = Inf * 0 = NaN).  Finite frames: four fp32 products summed in the order nw, ne, sw, se, no contraction. */
 int emavfi_warp(const float *frame2, const float *flow, float *out,
                 int B, int C, int H, int W, void *stream);
 

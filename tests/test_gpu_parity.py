@@ -37,6 +37,8 @@ def make_model(sd, mid=64, dtype="fp32"):
 
 
 # ------------------------------------------------------------------ warp (row W)
+# (a whole-tensor tolerance on random flows: the per-element gate - every element against a bound derived from the kernel's arithmetic,
+# at integer, border and window-edge positions, in the NCHW entry and inside every forward - is tests/test_gpu_warp_lattice.py)
 @pytest.mark.parametrize("B,C,H,W,sigma", [(2, 3, 17, 23, 1.0), (1, 3, 64, 48, 5.0), (2, 3, 33, 128, 40.0),
                                            (1, 3, 1, 9, 2.0), (1, 3, 9, 1, 2.0), (1, 3, 1, 1, 0.3), (1, 1, 8, 12, 3.0),
                                            (1, 3, 720, 1280, 6.0)])

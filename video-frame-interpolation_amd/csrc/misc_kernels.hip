@@ -756,7 +756,7 @@ int launch_blob_seal(void *blob, const BlobHeader &h, hipStream_t s)
 // order of the coordinate math is kept exactly, because sampling directly at x+flow differs from
 // the reference by up to 5e-4 at 720p.  Compiled without fast-math.
 // ------------------------------------------------------------------------------------------
-struct WarpTap { int o00, o01, o10, o11; float nw, ne, sw, se; int xa, xb, ya, yb; };
+struct WarpTap { int o00, o01, o10, o11; float nw, ne, sw, se; int xa, xb, ya, yb; bool v00, v01, v10, v11; };
 
 __device__ __forceinline__ WarpTap warp_tap(int x, int y, float fx, float fy, int H, int W, float wden, float hden)
 {
@@ -784,16 +784,25 @@ __device__ __forceinline__ WarpTap warp_tap(int x, int y, float fx, float fy, in
     t.ne = bad ? qnan : ((y0 && x1) ? s * w : 0.0f);
     t.sw = bad ? qnan : ((y1 && x0) ? n * e : 0.0f);
     t.se = bad ? qnan : ((y1 && x1) ? n * w : 0.0f);
+    t.v00 = y0 && x0; t.v01 = y0 && x1; t.v10 = y1 && x0; t.v11 = y1 && x1;
     return t;
+}
+// The blend of the four corner values (read at the clamped addresses o00.. / their window images).  An out-of-range corner contributes
+// exactly nothing: ATen's CPU grid_sample skips it, so what frame2 holds at its clamped address - pixel (0, 0) of the plane for a sample
+// far outside, row 0 / column 0 just past an edge - never reaches the result, not even a NaN or an infinity (selected on the corner's
+// validity; a zero weight alone would turn them into NaN).  An in-range corner multiplies in IEEE, zero weight included, as ATen does.
+// A bad coordinate has no valid corner and NaN weights: 0 * NaN = NaN in every channel.  Accumulation order nw, ne, sw, se as ATen's.
+__device__ __forceinline__ float warp_blend(float p00, float p01, float p10, float p11, const WarpTap &t)
+{
+    float a = (t.v00 ? p00 : 0.0f) * t.nw;
+    a += (t.v01 ? p01 : 0.0f) * t.ne;
+    a += (t.v10 ? p10 : 0.0f) * t.sw;
+    a += (t.v11 ? p11 : 0.0f) * t.se;
+    return a;
 }
 __device__ __forceinline__ float warp_sample(const float *__restrict__ p, const WarpTap &t)
 {
-    // accumulation order nw, ne, sw, se as ATen's CPU kernel
-    float a = p[t.o00] * t.nw;
-    a += p[t.o01] * t.ne;
-    a += p[t.o10] * t.sw;
-    a += p[t.o11] * t.se;
-    return a;
+    return warp_blend(p[t.o00], p[t.o01], p[t.o10], p[t.o11], t);
 }
 
 // NCHW -> NCHW (the C-ABI emavfi_warp; 32 algorithmic bytes per pixel at C = 3).
@@ -923,11 +932,7 @@ __global__ __launch_bounds__(256) void warp_tiled_kernel(const float *__restrict
 #pragma unroll
                     for (int c = 0; c < C; ++c) {
                         const float *p = win + c * (WR * WC);
-                        float a = p[l00] * t.nw;
-                        a += p[l01] * t.ne;
-                        a += p[l10] * t.sw;
-                        a += p[l11] * t.se;
-                        v[c] = a;
+                        v[c] = warp_blend(p[l00], p[l01], p[l10], p[l11], t);
                     }
                 } else {
 #pragma unroll
@@ -976,11 +981,7 @@ __global__ __launch_bounds__(256) void warp_tiled_kernel(const float *__restrict
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
                     const float *p = win + c * (WR * WC);
-                    float a = p[l00] * t.nw;
-                    a += p[l01] * t.ne;
-                    a += p[l10] * t.sw;
-                    a += p[l11] * t.se;
-                    v[c][q] = a;
+                    v[c][q] = warp_blend(p[l00], p[l01], p[l10], p[l11], t);
                 }
             } else {
 #pragma unroll
