@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_agreement_guard_f32 added (where the two time directions of the ensemble disagree the plain blend of the source frames is emitted, decided on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -788,6 +788,68 @@ int emavfi_ensemble_mean_f32(const float *const *members, const int *flips, int 
 #define EMAVFI_BORDER_MAX 64
 int emavfi_border_pad_f32(const float *src, float *dst, size_t planes, int H, int W, int N, int mode, void *stream);
 int emavfi_border_crop_f32(const float *src, float *dst, size_t planes, int H, int W, int N, void *stream);
+
+/* Agreement guard.  Every other guard here decides from the SOURCE frames (cuts, duplicates, static regions, borders); nothing protects
+ * against the model being wrong.  The forward estimates one flow and warps only frame2, and on large motion, occlusions and repetitive
+ * texture it tears or smears.  The "reverse" and "full" ensembles already compute F(a, b) and F(b, a), two midpoints of the same pair, and
+ * then average away where they differ; their per-pixel disagreement is a reliability map that costs no forward.  This entry keeps it:
+ * where the two time directions disagree, within a small window, the plain blend of the two source frames is emitted instead.  The
+ * reference has no such step; this is an addition, off unless asked for, and no quality claim is made.  The composition (which forwards
+ * make u and v) lives in the Python layer (EMA_VFI.agreement); the entry is the device work a C integrator needs beside
+ * emavfi_forward_routed and emavfi_ensemble_mean_f32.
+ *
+ * AGREEMENT GUARD DEFINITION (the one place).  This is the project's own definition: it claims agreement with no outside tool.
+ *   Inputs, all fp32, dense, [B][C][H][W], C in 1..4, H and W in 1..16384, B in 1..EMAVFI_AGREEMENT_MAX_BATCH:
+ *     u: the mean of the time-forward members of the ensemble; v: the mean of the time-reversed members (ENSEMBLE DEFINITION);
+ *     a, b: the two NORMALISED source batches exactly as the forward received them; mean[C], std[C]: the normalisation, HOST pointers to
+ *     fp32, as for the preprocess entries.
+ *   Disagreement.  d(b, c, y, x) = |u - v|: one IEEE fp32 subtraction, then the sign bit cleared.
+ *   Flagged.  A pixel (b, y, x) is flagged when, for some channel c, NOT (d <= tol).  tol is fp32, 0 <= tol <= 1, in units of the output's
+ *     full scale.  The negated form is the definition: a NaN in u or v (and inf - inf) flags the pixel.
+ *   Held.  A pixel (y, x) is held, for a radius r in 0..EMAVFI_STATIC_MAX_RADIUS, when some pixel (y', x') of the same sample with
+ *     y' in [max(0, y - r), min(H - 1, y + r)] and x' in [max(0, x - r), min(W - 1, x + r)] is flagged.  The window is clipped to the frame,
+ *     as the static guard's is.
+ *   Output, per channel.  Not held:  out = (u + v) * 0.5f - one fp32 addition and one exact multiplication.
+ *     Held:  h = (a + b) * 0.5f;  t = h * std[c];  t = t + mean[c]  (three roundings: no contraction);  out = t < 0 ? 0 : (t > 1 ? 1 : t).
+ *     Both comparisons fail for a NaN, so a NaN source stays NaN; a NaN in u or v at a held pixel does not reach the output.
+ *   Counts.  counts[b] = the number of held pixels of sample b.
+ *   Consequences:
+ *     - Exchanging u with v together with a with b leaves every output bit unchanged: |u - v| == |v - u|, and `+` is commutative.
+ *     - Flipping all four inputs by phi_g (ENSEMBLE DEFINITION) flips the output and the hold map: the clipped window is symmetric under
+ *       y -> H - 1 - y and x -> W - 1 - x, and everything else is per element.
+ *     - One flagged pixel in otherwise agreeing inputs holds a (2 r + 1)^2 square clipped at the frame.
+ *     - tol = 1 with finite inputs in [0, 1] holds nothing and yields (u + v) * 0.5f everywhere.
+ *     - The hold map is monotone: it grows with r and shrinks as tol grows.
+ *   Composition (EMA_VFI.agreement; G_4(x, y) = the tree mean of the four "flip" members of (x, y), emavfi_ensemble_mean_f32 with n = 4):
+ *       "reverse":  u = F(a, b), v = F(b, a).  With nothing held the result IS the "reverse" ensemble, bit for bit: the same two operations.
+ *       "full":     u = G_4(a, b), v = G_4(b, a).  With nothing held the result is (s_ab * 0.25f + s_ba * 0.25f) * 0.5f against the "full"
+ *                   ensemble's (s_ab + s_ba) * 0.125f, s being the four-member sums.  Scaling by a power of two is exact unless it
+ *                   underflows, and a frame's values are far from that, so the two are equal bit for bit wherever no intermediate is
+ *                   subnormal; that is asserted by the tests on their fixtures and is not part of the definition.
+ *     The guard needs both time directions: without an ensemble, or with "flip", it is refused, never upgraded silently.  With a border
+ *     (BORDER DEFINITION) the forwards run on the padded pair, u and v are cropped, and the guard runs on the picture with the UNPADDED
+ *     a and b: window and counts refer to the picture, and since cropping commutes with flips the symmetries carry over.  Under
+ *     EMAVFI_AMP16 everything above is fp32, ahead of the final conversion.  As for the ensemble, the symmetries hold for a deterministic
+ *     F, which the plain forward is for a fixed route (EMA_VFI.pack_adapt unset).
+ *
+ * emavfi_agreement_guard_f32 applies the definition.  counts (device memory, B u32; may be NULL): EVERY one of the B words is defined on
+ *   exit whatever the buffer held before: a launch ahead of the guard clears them on `stream` and the workgroups add their tiles' integer
+ *   sums - the order does not matter.  Every word of out is written and nothing else is; out may overlap none of u, v, a, b (those four may
+ *   alias one another).  mean and std are read before the call returns and travel as kernel arguments.
+ * EMAVFI_E_ARG (never an abort), the message naming the argument: a null u, v, a, b, out, mean or std; B outside
+ *   1..EMAVFI_AGREEMENT_MAX_BATCH; C outside 1..4; H or W outside 1..16384; a radius outside 0..16; a tol outside 0..1 or NaN; a std[c] that
+ *   is zero or not finite, a mean[c] that is not finite; a tensor pointer that is not 4-byte aligned, a counts pointer likewise; size
+ *   arithmetic that overflows size_t (a tensor that wraps the address space); out overlapping u, v, a or b.
+ * The tensors are device pointers or pinned (device-mapped) host memory.  Nothing is allocated, nothing synchronises, there is no
+ *   workspace, all work goes on `stream`.  A workgroup owns a tile of 64 x 128 pixels of one sample.  It reads u and v there plus an r-wide
+ *   halo, clipped to the frame - nothing outside a tensor is read -, stores (u + v) * 0.5f for the tile's own elements as it goes, reduces
+ *   over the channels to one flag per pixel in LDS, dilates rows then columns, and then reads a and b and stores the blend ONLY where
+ *   held.  Access width: 16-byte loads and stores, 4 columns per lane, when W % 4 == 0 and every tensor pointer of the call is 16-byte
+ *   aligned (a halo unit may then reach past the halo but never past its row); a scalar path otherwise.  Both run the same per-element
+ *   functions (csrc/agreement_elem.h).  The kernel is short-lived and waits on nothing. */
+#define EMAVFI_AGREEMENT_MAX_BATCH 65535
+int emavfi_agreement_guard_f32(const float *u, const float *v, const float *a, const float *b, float *out, int B, int C, int H, int W,
+                               int radius, float tol, const float *mean, const float *std, unsigned *counts, void *stream);
 
 /* Frame metrics on the device: how close is image a (an interpolated frame) to image b (the held-out true frame)?  The reference has no
  * evaluation script (its README names PSNR and SSIM against held-out ground-truth frames as the way to judge a model and calls an eval.py a

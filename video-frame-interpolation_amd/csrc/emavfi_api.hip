@@ -9,6 +9,7 @@
 #include "static_elem.h"
 #include "ensemble_elem.h"
 #include "border_elem.h"
+#include "agreement_elem.h"
 #include "conv_first.inl"
 
 #include <atomic>
@@ -1939,6 +1940,42 @@ int emavfi_border_crop_f32(const float *src, float *dst, size_t planes, int H, i
     if (const int rc = ensemble_pointer_check(what, "dst", -1, dst, picture); rc != EMAVFI_OK) return rc;
     if (const int rc = border_overlap_check(what, src, padded, dst, picture); rc != EMAVFI_OK) return rc;
     EMAVFI_TRY(launch_border_crop_f32(src, dst, planes, H, W, N, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+// ---- agreement guard (include/emavfi.h, "AGREEMENT GUARD DEFINITION"): every check runs on the host; mean and std are read here and not kept
+static_assert(EMAVFI_AGREEMENT_MAX_BATCH == AGREEMENT_MAX_BATCH, "header and agreement_elem.h disagree");
+
+int emavfi_agreement_guard_f32(const float *u, const float *v, const float *a, const float *b, float *out, int B, int C, int H, int W,
+                               int radius, float tol, const float *mean, const float *std, unsigned *counts, void *stream)
+{
+    const char *const what = "agreement_guard_f32";
+    if (B < 1 || B > EMAVFI_AGREEMENT_MAX_BATCH) return fail(EMAVFI_E_ARG, "%s: B = %d (B must lie in 1..%d)", what, B, EMAVFI_AGREEMENT_MAX_BATCH);
+    if (C < 1 || C > 4) return fail(EMAVFI_E_ARG, "%s: C = %d (C must be 1..4)", what, C);
+    if (const int rc = scene_dims_check(what, H, W); rc != EMAVFI_OK) return rc;
+    if (radius < 0 || radius > EMAVFI_STATIC_MAX_RADIUS)
+        return fail(EMAVFI_E_ARG, "%s: radius = %d (radius must lie in 0..%d)", what, radius, EMAVFI_STATIC_MAX_RADIUS);
+    if (!agreement_tol_ok(tol)) return fail(EMAVFI_E_ARG, "%s: tol = %g (tol must lie in 0..1)", what, (double)tol);
+    size_t bytes;                                         // at most 65535 * 4 * 16384^2 * 4 < 2^48
+    if (__builtin_mul_overflow((size_t)B * C, (size_t)H * W * sizeof(float), &bytes))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (B %d)", what, B);
+    if (!mean) return fail(EMAVFI_E_ARG, "%s: null pointer mean", what);
+    if (!std) return fail(EMAVFI_E_ARG, "%s: null pointer std", what);
+    for (int c = 0; c < C; ++c) {
+        if (!(mean[c] - mean[c] == 0.0f)) return fail(EMAVFI_E_ARG, "%s: mean[%d] must be finite", what, c);
+        if (!agreement_std_ok(std[c])) return fail(EMAVFI_E_ARG, "%s: std[%d] must be finite and non-zero", what, c);
+    }
+    const struct { const char *name; const void *p; } in[4] = {{"u", u}, {"v", v}, {"a", a}, {"b", b}};
+    for (int k = 0; k < 4; ++k)
+        if (const int rc = ensemble_pointer_check(what, in[k].name, -1, in[k].p, bytes); rc != EMAVFI_OK) return rc;
+    if (const int rc = ensemble_pointer_check(what, "out", -1, out, bytes); rc != EMAVFI_OK) return rc;
+    if ((uintptr_t)counts & 3) return fail(EMAVFI_E_ARG, "%s: the u32 pointer counts must be 4-byte aligned", what);
+    const uintptr_t o0 = (uintptr_t)out;
+    for (int k = 0; k < 4; ++k) {
+        const uintptr_t i0 = (uintptr_t)in[k].p;
+        if (o0 < i0 + bytes && i0 < o0 + bytes) return fail(EMAVFI_E_ARG, "%s: out overlaps %s", what, in[k].name);
+    }
+    EMAVFI_TRY(launch_agreement_guard_f32(u, v, a, b, out, B, C, H, W, radius, tol, mean, std, counts, (hipStream_t)stream), what);
     return EMAVFI_OK;
 }
 

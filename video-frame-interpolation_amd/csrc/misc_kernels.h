@@ -132,6 +132,10 @@ int launch_ensemble_mean_f32(const float *const *members, const int *flips, int 
 // frame borders (include/emavfi.h, "BORDER DEFINITION"): arguments already validated; H, W are the picture's size in both
 int launch_border_pad_f32(const float *src, float *dst, size_t planes, int H, int W, int N, int mode, hipStream_t s);
 int launch_border_crop_f32(const float *src, float *dst, size_t planes, int H, int W, int N, hipStream_t s);
+// agreement guard (include/emavfi.h, "AGREEMENT GUARD DEFINITION"): arguments already validated; `mean` and `std` are HOST arrays of C
+// entries, read before the call returns and passed on as kernel arguments
+int launch_agreement_guard_f32(const float *u, const float *v, const float *a, const float *b, float *out, int B, int C, int H, int W,
+                               int radius, float tol, const float *mean, const float *std, unsigned *counts, hipStream_t s);
 // frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION"): arguments already validated; `part` holds 2 u64 per (b, c, tile)
 // of frame_metrics_tiles' tx * ty tiles (32 x 32 windows each; one tile where an axis has no window)
 void frame_metrics_tiles(int H, int W, int *tx, int *ty);

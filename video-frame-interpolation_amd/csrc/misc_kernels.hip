@@ -8,6 +8,7 @@
 #include "static_elem.h"
 #include "ensemble_elem.h"
 #include "border_elem.h"
+#include "agreement_elem.h"
 #include "metrics_elem.h"
 #include "p010_elem.h"
 #include "yuv420p_elem.h"
@@ -2357,6 +2358,45 @@ __device__ __forceinline__ unsigned static_unit_sample(const uint4 &v, int k)
     else return (w[k >> 1] >> (16 * (k & 1))) & 0xffffu;
 }
 
+// The window passes the static guard and the agreement guard share.  On entry `map` [ST_RH][ST_BS] holds one byte per pixel of the tile plus
+// its r-wide halo, 1 = marked (positions outside the frame 0: the clipped window); the caller has synchronised.  Rows: lane = (row, 32
+// columns), a running count over the 2 r + 1 window; then columns: lane = (column, 32 rows).  On return `map` [ST_TH][ST_TW] holds per tile
+// pixel whether SOME marked pixel lies in its window (ANY: a dilation) or NONE does (!ANY: the erosion of the unmarked), and the result is
+// this lane's number of 1s inside the clipped tile [ty0, ty1) x [tx0, tx1); the caller synchronises before it reads the map.
+template <bool ANY>
+__device__ __forceinline__ unsigned tile_window_passes(unsigned char *map, unsigned char *rowmap, int r, int tid, int tx0, int tx1, int ty0, int ty1)
+{
+    const int RH = ST_TH + 2 * r;
+    for (int t = tid; t < 4 * RH; t += 256) {
+        const int row = t % RH, seg = t / RH;
+        const unsigned char *br = map + row * ST_BS + seg * 32;
+        unsigned char *er = rowmap + row * ST_ES + seg * 32;
+        int cnt = 0;
+        for (int k = 0; k <= 2 * r; ++k) cnt += br[k];
+        for (int x = 0; x < 32; ++x) {
+            er[x] = cnt ? 1 : 0;
+            if (x < 31) cnt += (int)br[x + 2 * r + 1] - (int)br[x];      // at most column 96 + 30 + 33 = 159 of RW = 128 + 2 r
+        }
+    }
+    __syncthreads();
+    // the result replaces `map`, which the row pass has finished reading
+    const int x = tid & (ST_TW - 1);
+    unsigned n = 0u;
+    for (int seg = tid >> 7; seg < ST_TH / 32; seg += 2) {
+        const unsigned char *cr = rowmap + seg * 32 * ST_ES + x;
+        int cnt = 0;
+        for (int k = 0; k <= 2 * r; ++k) cnt += cr[k * ST_ES];
+        for (int y = 0; y < 32; ++y) {
+            const int yy = seg * 32 + y;
+            const bool c = ANY ? cnt != 0 : cnt == 0;
+            map[yy * ST_TW + x] = c ? 1 : 0;
+            n += (c && tx0 + x < tx1 && ty0 + yy < ty1) ? 1u : 0u;
+            if (y < 31) cnt += (int)cr[(y + 2 * r + 1) * ST_ES] - (int)cr[y * ST_ES];   // at most row 32 + 30 + 33 = 95 of RH = 64 + 2 r
+        }
+    }
+    return n;
+}
+
 template <int SB>
 __global__ __launch_bounds__(256) void static_guard_kernel(StaticArgs p)
 {
@@ -2423,36 +2463,10 @@ __global__ __launch_bounds__(256) void static_guard_kernel(StaticArgs p)
     }
     __syncthreads();
 
-    // (3) rows: lane = (row, 32 columns); a running count over the 2 r + 1 window
-    for (int t = tid; t < 4 * RH; t += 256) {
-        const int row = t % RH, seg = t / RH;
-        const unsigned char *br = bad + row * ST_BS + seg * 32;
-        unsigned char *er = rowbad + row * ST_ES + seg * 32;
-        int cnt = 0;
-        for (int k = 0; k <= 2 * r; ++k) cnt += br[k];
-        for (int x = 0; x < 32; ++x) {
-            er[x] = cnt ? 1 : 0;
-            if (x < 31) cnt += (int)br[x + 2 * r + 1] - (int)br[x];      // at most column 96 + 30 + 33 = 159 of RW = 128 + 2 r
-        }
-    }
-    __syncthreads();
-    // columns: lane = (column, 32 rows); the core map replaces `bad`, which the row pass has finished reading
+    // (3) erosion, rows then columns: the core map replaces `bad`
     unsigned char *const core = bad;
     {
-        const int x = tid & (ST_TW - 1);
-        unsigned n = 0u;
-        for (int seg = tid >> 7; seg < ST_TH / 32; seg += 2) {
-            const unsigned char *cr = rowbad + seg * 32 * ST_ES + x;
-            int cnt = 0;
-            for (int k = 0; k <= 2 * r; ++k) cnt += cr[k * ST_ES];
-            for (int y = 0; y < 32; ++y) {
-                const int yy = seg * 32 + y;
-                const bool c = cnt == 0;
-                core[yy * ST_TW + x] = c ? 1 : 0;
-                n += (c && tx0 + x < tx1 && ty0 + yy < ty1) ? 1u : 0u;
-                if (y < 31) cnt += (int)cr[(y + 2 * r + 1) * ST_ES] - (int)cr[y * ST_ES];   // at most row 32 + 30 + 33 = 95 of RH = 64 + 2 r
-            }
-        }
+        unsigned n = tile_window_passes<false>(bad, rowbad, r, tid, tx0, tx1, ty0, ty1);
         if (p.counts) {
 #pragma unroll
             for (int off = 32; off >= 1; off >>= 1) n += __shfl_xor(n, off, 64);
@@ -2739,6 +2753,170 @@ int launch_border_crop_f32(const float *src, float *dst, size_t planes, int H, i
     const dim3 grid = border_plan(p, &wide);
     if (wide) border_crop_f32_kernel<true><<<grid, 256, 0, s>>>(p);
     else border_crop_f32_kernel<false><<<grid, 256, 0, s>>>(p);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Agreement guard (include/emavfi.h, "AGREEMENT GUARD DEFINITION"; per-element functions: agreement_elem.h).
+//   agreement_guard_kernel   grid (tiles along x, tiles along y, B), 256 threads, in the mould of static_guard_kernel: a workgroup owns a
+//                         tile of ST_TH x ST_TW = 64 x 128 pixels of ONE sample, and the two LDS maps, their strides and the budget
+//                         (27.8 KiB, 5 workgroups = 20 waves per CU) are that kernel's.  Here the map is `flagged` and the window passes
+//                         DILATE it (held = some flagged pixel in the window), which is the static guard's erosion of `same` read the
+//                         other way round.  Stages: (1) the map = 0; (2) every channel's u and v inside the tile plus halo, CLIPPED to
+//                         the frame, are compared and a flagged sample marks its pixel - the reduction over channels is the marking
+//                         itself; positions outside the frame stay 0, which is the clipped window.  The elements of the tile proper
+//                         get out = (u + v) * 0.5f stored right here, so u and v are read once (plus the halo: at r = 16 the tile plus
+//                         halo is 1.875 x the tile, at r = 4 1.2 x) and never again; (3) dilation along rows, then along columns, each
+//                         by a running count over the 2 r + 1 window; the column pass leaves the `held` map of the tile in the first
+//                         buffer and counts the tile's held pixels, one atomic add per wave into counts[b] (cleared by a launch of its
+//                         own ahead: an integer sum, the order does not matter); (4) a and b are read ONLY where held and the blend
+//                         overwrites what stage (2) stored there - the same workgroup, after a barrier, so the second store lands last.
+//                         With nothing held the traffic is what the definition obliges - u, v in, out out - plus the halo.  In the two
+//                         streaming stages (2) and (4) a lane issues the loads of AG_U = 4 units, 256 units apart, before the first use.
+//                         Access width: 16-byte loads and stores, 4 columns per lane, when W % 4 == 0 and u, v, a, b, out are 16-byte
+//                         aligned (every sample, plane and row then starts on a unit, and a tile's columns are whole units; a halo unit
+//                         may reach past the halo but never past its row); else one element per lane.  Both forms run the same
+//                         per-element functions.  Nothing outside a tensor is read.  Short-lived, waits on nothing.
+// ------------------------------------------------------------------------------------------
+struct AgreementArgs {
+    const float *u, *v, *a, *b;
+    float *out;
+    unsigned *counts;
+    int C, H, W, radius;
+    float tol, mean[4], std[4];
+};
+
+constexpr int AG_U = 4;                                          // units a lane has in flight in the two streaming stages
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void agreement_guard_kernel(AgreementArgs p)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char flag[ST_RH * ST_BS];      // stage (3) on: held [ST_TH][ST_TW]
+    __shared__ __attribute__((aligned(16))) unsigned char rowflag[ST_RH * ST_ES];
+    using T = std::conditional_t<WIDE, float4, float>;
+    constexpr int E = WIDE ? 4 : 1;                              // elements of a unit
+    const int tid = threadIdx.x, r = p.radius;
+    const int tx0 = blockIdx.x * ST_TW, ty0 = blockIdx.y * ST_TH;
+    const int tx1 = min(tx0 + ST_TW, p.W), ty1 = min(ty0 + ST_TH, p.H);           // the tile, clipped: [ty0, ty1) x [tx0, tx1)
+    const int X0 = static_window_lo(tx0, r), X1 = static_window_hi(tx1 - 1, r, p.W) + 1;
+    const int Y0 = static_window_lo(ty0, r), Y1 = static_window_hi(ty1 - 1, r, p.H) + 1;   // the tile plus halo, clipped to the frame
+    const int ox = tx0 - r, oy = ty0 - r, RW = ST_TW + 2 * r, RH = ST_TH + 2 * r;  // the LDS map: RH x RW pixels from (oy, ox)
+    const size_t plane = (size_t)p.H * p.W, sample = (size_t)blockIdx.z * p.C * plane;
+    const float *const u = p.u + sample, *const v = p.v + sample, *const a = p.a + sample, *const b = p.b + sample;
+    float *const out = p.out + sample;
+
+    for (int i = tid; i < ST_RH * ST_BS / 4; i += 256) reinterpret_cast<unsigned *>(flag)[i] = 0u;
+    __syncthreads();
+
+    // (2) a flagged sample marks its pixel; the tile's own elements are stored as kept.  A lane issues the loads of AG_U units, 256 units
+    // apart, before the first use: 2 AG_U loads in flight per lane.
+    {
+        const int x0 = WIDE ? X0 & ~3 : X0, x1 = WIDE ? (X1 + 3) & ~3 : X1;      // wide: W % 4 == 0, so x1 <= W
+        const int nu = (x1 - x0) / E, per = (Y1 - Y0) * nu, items = p.C * per;
+        for (int t0 = tid; t0 < items; t0 += 256 * AG_U) {
+            T uu[AG_U], vv[AG_U];
+            size_t off[AG_U];
+            int y[AG_U], x[AG_U];
+#pragma unroll
+            for (int k = 0; k < AG_U; ++k) {
+                const int t = t0 + 256 * k;
+                if (t >= items) continue;
+                const int c = t / per, rem = t - c * per, rr = rem / nu;
+                y[k] = Y0 + rr; x[k] = x0 + (rem - rr * nu) * E;
+                off[k] = (size_t)c * plane + (size_t)y[k] * p.W + x[k];
+                uu[k] = *reinterpret_cast<const T *>(u + off[k]);
+                vv[k] = *reinterpret_cast<const T *>(v + off[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < AG_U; ++k) {
+                if (t0 + 256 * k >= items) continue;
+                const float *const ue = reinterpret_cast<const float *>(&uu[k]), *const ve = reinterpret_cast<const float *>(&vv[k]);
+                const int ly = y[k] - oy;                                         // 0 <= ly < RH: Y0 >= oy and Y1 <= ty1 + r
+                T kept;
+                float *const ke = reinterpret_cast<float *>(&kept);
+#pragma unroll
+                for (int j = 0; j < E; ++j) {
+                    const int lx = x[k] + j - ox;
+                    if (agreement_flagged(ue[j], ve[j], p.tol) && lx >= 0 && lx < RW) flag[ly * ST_BS + lx] = 1;
+                    ke[j] = agreement_kept(ue[j], ve[j]);
+                }
+                // a unit lies inside the tile or outside it
+                if (y[k] >= ty0 && y[k] < ty1 && x[k] >= tx0 && x[k] < tx1) *reinterpret_cast<T *>(out + off[k]) = kept;
+            }
+        }
+    }
+    __syncthreads();
+
+    // (3) dilation, rows then columns: the held map replaces `flag`
+    unsigned char *const held = flag;
+    {
+        unsigned n = tile_window_passes<true>(flag, rowflag, r, tid, tx0, tx1, ty0, ty1);
+        if (p.counts) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) n += __shfl_xor(n, off, 64);
+            if ((tid & 63) == 0 && n) atomicAdd(p.counts + blockIdx.z, n);
+        }
+    }
+    __syncthreads();
+
+    // (4) the blend of the sources at the held positions, over what stage (2) stored there; again AG_U units' loads ahead of their use
+    {
+        const int nu = (tx1 - tx0) / E, per = (ty1 - ty0) * nu, items = p.C * per;   // wide: tx0 and tx1 are multiples of 4
+        for (int t0 = tid; t0 < items; t0 += 256 * AG_U) {
+            T aa[AG_U], bb[AG_U];
+            size_t off[AG_U];
+            unsigned hm[AG_U];
+            int ch[AG_U];
+#pragma unroll
+            for (int k = 0; k < AG_U; ++k) {
+                const int t = t0 + 256 * k;
+                hm[k] = 0u;
+                if (t >= items) continue;
+                const int c = t / per, rem = t - c * per, rr = rem / nu, x = tx0 + (rem - rr * nu) * E;
+                const unsigned char *const hp = held + rr * ST_TW + (x - tx0);
+#pragma unroll
+                for (int j = 0; j < E; ++j) hm[k] |= (hp[j] ? 1u : 0u) << j;
+                if (!hm[k]) continue;
+                ch[k] = c;
+                off[k] = (size_t)c * plane + (size_t)(ty0 + rr) * p.W + x;
+                aa[k] = *reinterpret_cast<const T *>(a + off[k]);
+                bb[k] = *reinterpret_cast<const T *>(b + off[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < AG_U; ++k) {
+                if (!hm[k]) continue;
+                const float *const ae = reinterpret_cast<const float *>(&aa[k]), *const be = reinterpret_cast<const float *>(&bb[k]);
+                T blend;
+                float *const le = reinterpret_cast<float *>(&blend);
+#pragma unroll
+                for (int j = 0; j < E; ++j) le[j] = agreement_fallback(ae[j], be[j], p.mean[ch[k]], p.std[ch[k]]);
+                if (hm[k] == (1u << E) - 1u) {
+                    *reinterpret_cast<T *>(out + off[k]) = blend;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < E; ++j)
+                        if (hm[k] >> j & 1u) out[off[k] + j] = le[j];
+                }
+            }
+        }
+    }
+}
+
+int launch_agreement_guard_f32(const float *u, const float *v, const float *a, const float *b, float *out, int B, int C, int H, int W,
+                               int radius, float tol, const float *mean, const float *std, unsigned *counts, hipStream_t s)
+{
+    AgreementArgs p{};
+    p.u = u; p.v = v; p.a = a; p.b = b; p.out = out; p.counts = counts; p.C = C; p.H = H; p.W = W; p.radius = radius; p.tol = tol;
+    for (int c = 0; c < C; ++c) { p.mean[c] = mean[c]; p.std[c] = std[c]; }
+    if (counts) {
+        static_counts_clear_kernel<<<dim3((unsigned)((B + 255) / 256)), 256, 0, s>>>(counts, B);
+        if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
+    }
+    const dim3 grid((unsigned)((W + ST_TW - 1) / ST_TW), (unsigned)((H + ST_TH - 1) / ST_TH), (unsigned)B);   // B <= 65535
+    const bool wide = W % 4 == 0 && mult_of(16, {(size_t)(uintptr_t)u, (size_t)(uintptr_t)v, (size_t)(uintptr_t)a, (size_t)(uintptr_t)b,
+                                                  (size_t)(uintptr_t)out});
+    if (wide) agreement_guard_kernel<true><<<grid, 256, 0, s>>>(p);
+    else agreement_guard_kernel<false><<<grid, 256, 0, s>>>(p);
     return (int)hipGetLastError();
 }
 

@@ -80,6 +80,12 @@ def parser() -> argparse.ArgumentParser:
                         "picture continues past the frame; no quality claim is made, --evaluate tells what it buys on a clip")
     p.add_argument("--border-mode", choices=("replicate", "reflect"), default=None,
                    help="with --border: repeat the edge pixel (replicate, the default) or mirror the picture about it (reflect)")
+    p.add_argument("--agreement", type=float, default=None, metavar="TOL",
+                   help="with --ensemble reverse or full: where the forward and the time-reversed prediction differ by more than TOL of full "
+                        "scale (0..1) the plain blend of the two source frames is written instead; no default and no quality claim is made, "
+                        "--evaluate tells what it buys on a clip; excludes --reference-quirks")
+    p.add_argument("--agreement-radius", type=int, default=None, metavar="R",
+                   help="with --agreement: a disagreeing pixel holds its neighbours within R pixels (0..16) as well (default 0)")
     p.add_argument("--batch-pairs", type=int, default=8)
     p.add_argument("--chunk-pairs", type=int, default=64, help="frame pairs per chunk: at most chunk_pairs * frame_interval + 1 source frames are held")
     p.add_argument("--yuv-standard", default="bt601", help="bt601, bt709 or (10 / 12 / 16-bit streams) bt2020")
@@ -122,6 +128,18 @@ def _run(args) -> int:
         raise ValueError("--border-mode needs --border N")
     if args.border is not None and not 1 <= args.border <= 64:
         raise ValueError("--border N: the border must lie in 1..64")
+    if args.agreement_radius is not None and args.agreement is None:
+        raise ValueError("--agreement-radius needs --agreement TOL")
+    if args.agreement is not None:
+        if not 0.0 <= args.agreement <= 1.0:     # false for a NaN
+            raise ValueError("--agreement TOL: a fraction of full scale in 0..1")
+        if args.agreement_radius is not None and not 0 <= args.agreement_radius <= 16:
+            raise ValueError("--agreement-radius R: the radius must lie in 0..16")
+        if args.ensemble not in ("reverse", "full"):
+            raise ValueError("--agreement needs --ensemble reverse or --ensemble full: the guard compares the two time directions")
+        if args.reference_quirks:
+            raise ValueError("--agreement excludes --reference-quirks: a [0, 1] blend pasted into the quirk's de-normalised prediction would "
+                             "show as patches")
     mode = "resample" if resample else (args.mode or "reference")
     with y4m.Y4MReader(args.input) as reader:
         head = reader.header
@@ -155,7 +173,8 @@ def _run(args) -> int:
                                **(dict(static_guard=args.static_guard, static_tolerance=args.static_tolerance or 0.0)
                                   if args.static_guard is not None else {}),
                                ensemble=args.ensemble,
-                               **(dict(border=args.border, border_mode=args.border_mode or "replicate") if args.border is not None else {}))
+                               **(dict(border=args.border, border_mode=args.border_mode or "replicate") if args.border is not None else {}),
+                               **(dict(agreement=args.agreement, agreement_radius=args.agreement_radius) if args.agreement is not None else {}))
         if args.evaluate:
             print(fi.evaluate(list(reader), every=args.every))      # evaluate() indexes the clip: all of it is held
             return 0
@@ -173,7 +192,9 @@ def _run(args) -> int:
                   + (f", static guard held {100.0 * sum(fi.static_share) / max(len(fi.static_share), 1):.2f} % of the predictions' pixels on average"
                      if args.static_guard is not None else "")
                   + (f", ensemble {args.ensemble}" if args.ensemble is not None else "")
-                  + (f", border {args.border} {args.border_mode or 'replicate'}" if args.border is not None else ""), file=sys.stderr)
+                  + (f", border {args.border} {args.border_mode or 'replicate'}" if args.border is not None else "")
+                  + (f", agreement guard held {100.0 * sum(fi.agreement_share) / max(len(fi.agreement_share), 1):.2f} % of the predictions' "
+                     f"pixels on average" if args.agreement is not None else ""), file=sys.stderr)
     return 0
 
 

@@ -74,6 +74,8 @@ _PROTOTYPES = {
     "emavfi_ensemble_mean_f32": (c_int, [POINTER(c_void_p), POINTER(c_int), c_int, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "emavfi_border_pad_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
     "emavfi_border_crop_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "emavfi_agreement_guard_f32": (c_int, [c_void_p] * 5 + [c_int] * 5 + [ctypes.c_float, POINTER(ctypes.c_float), POINTER(ctypes.c_float),
+                                           c_void_p, c_void_p]),
     "emavfi_frame_metrics_workspace_bytes": (c_size_t, [c_int] * 4),
     "emavfi_frame_metrics_u8": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 4
                                 + [c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -1425,6 +1427,52 @@ def border_crop_f32(x, N, out=None):
     dev = next((t.device for t in (x, out) if t.is_cuda), None) or torch.device("cuda")
     with torch.cuda.device(dev):
         check(load().emavfi_border_crop_f32(x.data_ptr(), out.data_ptr(), planes, H, W, N, _stream()), "emavfi_border_crop_f32")
+    return out
+
+
+# ---------------------------------------------------------------- agreement guard (include/emavfi.h, "AGREEMENT GUARD DEFINITION")
+AGREEMENT_MAX_BATCH = 65535                      # EMAVFI_AGREEMENT_MAX_BATCH
+AGREEMENT_ENSEMBLES = ("reverse", "full")        # the ensembles that run both time directions
+
+
+def agreement_args(tol, radius, what):
+    """(tol, radius) of an agreement guard as a float in [0, 1] and an int in 0..STATIC_MAX_RADIUS, or a ValueError naming `what`"""
+    import math
+    if isinstance(tol, bool) or not isinstance(tol, (int, float)) or math.isnan(tol) or not 0.0 <= tol <= 1.0:
+        raise ValueError(f"{what}: the agreement tolerance must be a number in [0, 1] (the output's full scale), got {tol!r}")
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= STATIC_MAX_RADIUS:
+        raise ValueError(f"{what}: the agreement radius must be an int in 0..{STATIC_MAX_RADIUS}, got {radius!r}")
+    return float(tol), radius
+
+
+def agreement_guard_f32(u, v, a, b, tol, radius=0, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, counts=None):
+    """out = the agreement guard of include/emavfi.h ("AGREEMENT GUARD DEFINITION"): (u + v) / 2 where the two time directions `u` and `v`
+    agree within `tol` (full-scale units) over the whole window of `radius` around the pixel, and the de-normalised, clamped blend of the
+    normalised sources `a`, `b` where they do not.  All five: contiguous float32 [B, C, H, W] of one shape, C = 1..4, device tensors or
+    pinned host memory; `out` overlaps none of the inputs.  `counts`: None, or a contiguous int32 [B] device tensor that receives every
+    sample's number of held pixels.  Runs on the current stream; returns `out`."""
+    import torch
+    what = "agreement_guard_f32"
+    tol, radius = agreement_args(tol, radius, what)
+    for t, name in ((u, "u"), (v, "v"), (a, "a"), (b, "b")):
+        _ensemble_planes(t, f"{what}({name})")
+        if t.dim() != 4 or t.shape != u.shape:
+            raise ValueError(f"{what}: {name} {tuple(t.shape)}: four [B, C, H, W] tensors of one shape expected (u is {tuple(u.shape)})")
+    B, C, H, W = (int(d) for d in u.shape)
+    if not (1 <= C <= 4 and B <= AGREEMENT_MAX_BATCH):
+        raise ValueError(f"{what}: [B, C, H, W] = {tuple(u.shape)}: C must be 1..4 and B at most {AGREEMENT_MAX_BATCH}")
+    m, s = _stats(mean, std, C)
+    dev = next((t.device for t in (u, v, a, b, out, counts) if t is not None and t.is_cuda), None) or torch.device("cuda")
+    if out is None:
+        out = torch.empty(u.shape, dtype=torch.float32, device=dev)
+    elif _ensemble_planes(out, f"{what}(out)") is None or out.shape != u.shape:
+        raise ValueError(f"{what}: out {tuple(out.shape)} is not of the inputs' shape {tuple(u.shape)}")
+    if counts is not None and not (counts.is_cuda and counts.dtype == torch.int32 and tuple(counts.shape) == (B,) and counts.is_contiguous()):
+        raise ValueError(f"{what}: counts must be a contiguous int32 [{B}] device tensor")
+    with torch.cuda.device(dev):
+        check(load().emavfi_agreement_guard_f32(u.data_ptr(), v.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), B, C, H, W, radius, tol,
+                                                m, s, counts.data_ptr() if counts is not None else None, _stream()),
+              "emavfi_agreement_guard_f32")
     return out
 
 

@@ -44,6 +44,8 @@ _MODEL_ENSEMBLE = object()   # forward(ensemble=): "what the model's attribute s
 # EMA_VFI.border ("Frame borders"; include/emavfi.h, "BORDER DEFINITION")
 BORDER_MODES, BORDER_MAX = _lib.BORDER_MODES, _lib.BORDER_MAX
 _MODEL_BORDER = object()     # forward(border=): "what the model's attribute says"
+# EMA_VFI.agreement ("Agreement guard"; include/emavfi.h, "AGREEMENT GUARD DEFINITION")
+_MODEL_AGREEMENT = object()  # forward(agreement=): "what the model's attribute says"
 
 
 class _LastCall(NamedTuple):
@@ -179,6 +181,8 @@ class EMA_VFI(nn.Module):
         self.pack_adapt = os.environ.get("EMAVFI_PACK_ADAPT")
         self.ensemble = None
         self.border = None
+        self.agreement = None
+        self.agreement_counts = None   # the last guarded forward's held pixels per sample: int32 [B] on the device
         m = mid_channels
         self.feat_ext_conv1 = conv_block(in_channels * 2, m)
         self.feat_ext_blocks = nn.Sequential(OrderedDict(
@@ -387,7 +391,9 @@ class EMA_VFI(nn.Module):
         made on the device from every forward's census (no host sync; a captured graph adapts on replay); pack_policy is the starting
         route.  Modes without a one-launch pack (fp32, amp16, fp32x3) run their plain forward.  A batch runs as one sequence
         (pipeline is ignored).  Initial value: EMAVFI_PACK_ADAPT (1 = PACK_ADAPT_DEFAULT, or "enter,leave").  Changing the thresholds
-        keeps the route state; load_state_dict, load_packed_weights and a new pack_policy reset it to the starting route."""
+        keeps the route state; load_state_dict, load_packed_weights and a new pack_policy reset it to the starting route.  Every forward
+        advances the state, so the members of an ensemble may run different routes: the exact symmetries of `ensemble` and of the
+        `agreement` guard (guard(a, b) == guard(b, a), flip equivariance) hold for a fixed route only, that is with pack_adapt unset."""
         return self._pack_adapt
 
     @pack_adapt.setter
@@ -435,6 +441,33 @@ class EMA_VFI(nn.Module):
         if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N <= BORDER_MAX or not isinstance(mode, str) or mode not in BORDER_MODES:
             raise ValueError(f"EMA_VFI.border must be None, an int N in 1..{BORDER_MAX} or (N, mode) with mode one of {BORDER_MODES}, got {value!r}")
         return N, mode
+
+    @property
+    def agreement(self):
+        """The agreement guard of forward() ("Agreement guard"; include/emavfi.h, "AGREEMENT GUARD DEFINITION"): None
+        (default: off), a tolerance `tol` in [0, 1] of the output's full scale, or (tol, radius) with the radius of the dilation in 0..16;
+        read back as None or the pair (tol, radius).  Needs both time directions: the call's ensemble must be "reverse" or "full", anything
+        else is refused, never upgraded.  Where the time-forward and the time-reversed half of the ensemble differ by more than `tol` in any
+        channel, within `radius` pixels, the blend of the two source frames is emitted instead of the ensemble's mean; one launch
+        (emavfi_agreement_guard_f32) in place of the ensemble's last mean.  The held pixels per sample of the last guarded forward stay on
+        the device as `agreement_counts` (int32 [B]); no host synchronisation is added."""
+        return self._agreement
+
+    @agreement.setter
+    def agreement(self, value):
+        self._agreement = self._check_agreement(value)
+
+    @staticmethod
+    def _check_agreement(value):
+        """None or (tol, radius) of a guard given as None, tol or (tol, radius)"""
+        if value is None:
+            return None
+        tol, radius = value if isinstance(value, tuple) and len(value) == 2 else (value, 0)
+        try:
+            return _lib.agreement_args(tol, radius, "EMA_VFI.agreement")
+        except ValueError:
+            raise ValueError(f"EMA_VFI.agreement must be None, a tolerance in [0, 1] or (tolerance, radius) with an int radius in "
+                             f"0..{_lib.STATIC_MAX_RADIUS}, got {value!r}") from None
 
     def _check_border_size(self, B, H, W, border, dt):
         """(H + 2N, W + 2N), or a refusal from the shapes alone where the padded batch is beyond what the forward admits (include/emavfi.h,
@@ -503,11 +536,19 @@ class EMA_VFI(nn.Module):
                 for i in range(self.num_blocks)]
 
     # ------------------------------------------------------------------ forward
-    def forward(self, frame1, frame2, return_taps=False, _events=None, ensemble=_MODEL_ENSEMBLE, border=_MODEL_BORDER):
+    def forward(self, frame1, frame2, return_taps=False, _events=None, ensemble=_MODEL_ENSEMBLE, border=_MODEL_BORDER,
+                agreement=_MODEL_AGREEMENT):
         """ema_vfi.py:110-147.  `ensemble`: one of ENSEMBLES for this call alone (FrameInterpolator passes its own); by default the
-        model's attribute decides.  `border`: None, N or (N, mode) for this call alone, likewise."""
+        model's attribute decides.  `border`: None, N or (N, mode) for this call alone, likewise.  `agreement`: None, tol or
+        (tol, radius) for this call alone, likewise."""
         ensemble = self._ensemble if ensemble is _MODEL_ENSEMBLE else self._check_ensemble(ensemble)
         border = self._border if border is _MODEL_BORDER else self._check_border(border)
+        agreement = self._agreement if agreement is _MODEL_AGREEMENT else self._check_agreement(agreement)
+        if agreement is not None and return_taps:
+            raise ValueError("EMA_VFI.forward: return_taps=True with an agreement guard: the taps belong to one forward (set agreement=None)")
+        if agreement is not None and ensemble not in _lib.AGREEMENT_ENSEMBLES:
+            raise ValueError(f"EMA_VFI.forward: agreement={agreement!r} with ensemble={ensemble!r}: the guard compares the two time directions "
+                             f"and needs an ensemble that runs both, one of {_lib.AGREEMENT_ENSEMBLES} (it is not chosen for you)")
         if border is not None and return_taps:
             raise ValueError("EMA_VFI.forward: return_taps=True with a border: the taps belong to the padded forward (set border=None)")
         if ensemble is not None and return_taps:
@@ -536,13 +577,23 @@ class EMA_VFI(nn.Module):
         packed = self.packed_weights(dt, dev)
         if border is not None:
             # crop_N(G(pad a, pad b)) of the border definition: G sees an ordinary (H + 2N) x (W + 2N) batch
+            a, b = f1, f2
             f1, f2 = (_lib.border_pad_f32(f, *border) for f in (f1, f2))
+            if agreement is not None:
+                # the two halves of the padded ensemble, cropped, then the guard on the picture with the unpadded sources
+                u, v = (_lib.border_crop_f32(h, border[0]) for h in self._forward_halves(L, packed, f1, f2, dt, ensemble, _events))
+                out = self._agreement_guard(u, v, a, b, agreement)
+                return out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
             if ensemble is not None:
                 out = self._forward_ensemble(L, packed, f1, f2, dt, ensemble, _events)
             else:
                 out = torch.empty_like(f1)
                 self._forward_f32(L, packed, f1, f2, out, dt, None, _events)
             out = _lib.border_crop_f32(out, border[0])
+            return out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
+        if agreement is not None:
+            u, v = self._forward_halves(L, packed, f1, f2, dt, ensemble, _events)
+            out = self._agreement_guard(u, v, f1, f2, agreement)
             return out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
         if ensemble is not None:
             out = self._forward_ensemble(L, packed, f1, f2, dt, ensemble, _events)
@@ -589,6 +640,10 @@ class EMA_VFI(nn.Module):
         definition's member order (under pack_adapt every one of them advances the route state, as the same calls made by hand would).
         Run one after the other and not as one larger batch: the result is the composition by construction, whatever the kernels do
         across a batch, and eight 720p batches of 8 would not share a workspace anyway.  `_events` bracket the first member's launches."""
+        return _lib.ensemble_mean_f32(*self._ensemble_members(L, packed, f1, f2, dt, ensemble, _events))
+
+    def _ensemble_members(self, L, packed, f1, f2, dt, ensemble, _events=None):
+        """(members, flip codes) of the ensemble, in the definition's order: the plain forwards, each an fp32 tensor of its own"""
         flips = (0,) if ensemble == "reverse" else _lib.ENSEMBLE_FLIPS
         mirrored = {f: (_lib.flip_f32(f1, f), _lib.flip_f32(f2, f)) if f else (f1, f2) for f in flips}
         members, codes = [], []
@@ -599,7 +654,21 @@ class EMA_VFI(nn.Module):
                 self._forward_f32(L, packed, x1, x2, m, dt, None, _events if not members else None)
                 members.append(m)
                 codes.append(f)
-        return _lib.ensemble_mean_f32(members, codes)
+        return members, codes
+
+    def _forward_halves(self, L, packed, f1, f2, dt, ensemble, _events=None):
+        """(u, v) of the agreement guard definition for ensemble "reverse" or "full": the same members as the ensemble's, in the same
+        order, the time-forward half and the time-reversed half each reduced by the definition's tree mean (one member: the member)"""
+        members, codes = self._ensemble_members(L, packed, f1, f2, dt, ensemble, _events)
+        n = len(members) // 2
+        if n == 1:
+            return members[0], members[1]
+        return _lib.ensemble_mean_f32(members[:n], codes[:n]), _lib.ensemble_mean_f32(members[n:], codes[n:])
+
+    def _agreement_guard(self, u, v, a, b, agreement):
+        """the guard's one launch on the fp32 halves and the normalised fp32 sources; the counts stay on the device"""
+        self.agreement_counts = torch.empty(u.shape[0], dtype=torch.int32, device=u.device)
+        return _lib.agreement_guard_f32(u, v, a, b, agreement[0], agreement[1], counts=self.agreement_counts)
 
     def pack_census(self):
         """What the one-launch ModulatedDeformConvPack kernels of the LAST one-sequence forward on the current stream counted while

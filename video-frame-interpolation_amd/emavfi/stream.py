@@ -115,6 +115,15 @@ issues - all three modes, the recursion's inner midpoints, ``evaluate()``, with 
 include/emavfi.h ("ENSEMBLE DEFINITION"; ``EMA_VFI.ensemble``): 2, 4 or 8 plain forwards of the same batch, averaged on the device.  It is
 passed with each call, so the model's own attribute is neither read nor changed; ``None`` (default) leaves the decision to that attribute.
 With "reverse" or "full" every prediction is exactly symmetric in time: the reversed clip yields the reversed predictions, byte for byte.
+``agreement=tol`` with ``agreement_radius=r`` (opt-in; not in the reference) runs EVERY forward the harness issues - all three modes, the
+recursion's inner midpoints, ``evaluate()`` - under the agreement guard of include/emavfi.h ("AGREEMENT GUARD DEFINITION";
+``EMA_VFI.agreement``): where the time-forward and the time-reversed half of the ensemble differ by more than ``tol`` of full scale within
+``r`` pixels, the plain blend of the two source frames is emitted.  It needs ``ensemble="reverse"`` or ``"full"`` (given here, or the
+model's attribute) and is refused otherwise, and with ``reference_quirks=True`` (a [0, 1] blend pasted into the quirk's de-normalised
+prediction would show as patches).  ``agreement_share`` lists, per emitted prediction of the last ``run()`` (mode "resample": per emitted
+frame made of node frames, the share of the first node frame it names), the share of its pixels the guard held; the counts follow the
+frames to pinned memory and are read after the ``done`` wait the drain already performs - no new synchronisation point.
+
 ``border=N`` with ``border_mode="replicate" | "reflect"`` (opt-in; not in the reference) runs EVERY forward the harness issues - all three
 modes, the recursion's inner midpoints, ``evaluate()``, with any of the options above, the ensemble included - on frames extended by N
 pixels past each edge and crops the prediction back (include/emavfi.h, "BORDER DEFINITION"; ``EMA_VFI.border``): the forward takes the outside
@@ -227,6 +236,8 @@ class FrameInterpolator:
     static_tol = 0        # its tolerance in sample units (lib.static_tolerance_units)
     ensemble = None       # test-time ensembling of every forward (EMA_VFI.ensemble); None: what the model's attribute says
     border = None         # (N, mode) of the frame border of every forward (EMA_VFI.border); None: what the model's attribute says
+    agreement = None      # (tol, radius) of the agreement guard of every forward (EMA_VFI.agreement); None: what the model's attribute says
+    _ag = None   # under `agreement`: the held pixel counts of the batch just predicted, int32 on the device, in prediction order
     _depth = 0   # bits per sample of a 16-bit-word pixel format ("p010": 10, ...); 0 for the byte formats
     _planar = _yuv8 = False
     mode = "reference"
@@ -238,7 +249,8 @@ class FrameInterpolator:
                  rate_in=None, rate_out=None, resample_depth: int = 3, resample_method: str = "nearest",
                  dedup_threshold: Optional[float] = None, dedup_max_run: int = 3, dedup_span: int = 64,
                  static_guard: Optional[int] = None, static_tolerance: float = 0.0, ensemble: Optional[str] = None,
-                 border: Optional[int] = None, border_mode: str = "replicate"):
+                 border: Optional[int] = None, border_mode: str = "replicate",
+                 agreement: Optional[float] = None, agreement_radius: Optional[int] = None):
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
             raise ValueError("interpolation_factor >= 0, frame_interval >= 1, batch_pairs >= 1 required")
         if mode not in ("reference", "recursive", "resample"):
@@ -278,6 +290,20 @@ class FrameInterpolator:
         self.border = None if border is None else (border, border_mode)
         # what rides on every forward: only what was given here, so that a model without these arguments still serves a plain harness
         self._forward_kw = {**({"ensemble": ensemble} if ensemble is not None else {}), **({"border": self.border} if border is not None else {})}
+        if agreement is None:
+            if agreement_radius is not None:
+                raise ValueError("agreement_radius without agreement: the radius belongs to the agreement guard (pass a tolerance)")
+        else:
+            self.agreement = _lib.agreement_args(agreement, 0 if agreement_radius is None else agreement_radius, "agreement / agreement_radius")
+            if reference_quirks:
+                raise ValueError("agreement with reference_quirks=True: a [0, 1] blend of the sources pasted into the quirk's de-normalised "
+                                 "prediction would show as patches (pass reference_quirks=False)")
+            runs = ensemble if ensemble is not None else getattr(model, "ensemble", None)
+            if runs not in _lib.AGREEMENT_ENSEMBLES:
+                raise ValueError(f"agreement with ensemble={runs!r}: the guard compares the two time directions and needs an ensemble that "
+                                 f"runs both, one of {_lib.AGREEMENT_ENSEMBLES} (it is not chosen for you)")
+            self._forward_kw["agreement"] = self.agreement
+        self.agreement_share = []   # per emitted prediction of the last run(): the share of its pixels the agreement guard held
         if pixel_format not in ("bgr24", "nv12", *_lib.DEPTHS, *_lib.PLANAR_DEPTHS):
             raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames), 'nv12' (uint8 [H*3/2, W] frames), 'p010' / 'p012' / 'p016' "
                              "(uint16 [H*3/2, W] frames) or planar 'yuv420p8' (uint8) / 'yuv420p10' / 'yuv420p12' / 'yuv420p16' (uint16)")
@@ -657,6 +683,9 @@ class FrameInterpolator:
                 # core pixel counts of the slot's prediction frames, on the device and pinned
                 self._slots[-1].update({"sg": torch.zeros(nb * nout, dtype=torch.int32, device=self.device),
                                         "h_sg": torch.zeros(nb * nout, dtype=torch.int32).pin_memory()})
+            if self.agreement is not None:
+                # held pixel counts of the slot's predictions, pinned (the device side is the model's own tensor per forward)
+                self._slots[-1]["h_ag"] = torch.zeros(nb * nout, dtype=torch.int32).pin_memory()
             if self.scene is not None:
                 # signatures of the slot's staged frames; flags (row 0) and scores (row 1) of its pairs, on the device and pinned
                 self._slots[-1].update({"sig": torch.empty(per * nb, _lib.SCENE_SIG_WORDS, dtype=torch.int32, device=self.device),
@@ -867,11 +896,25 @@ class FrameInterpolator:
         call alone, the model's attributes stay as they are -, else as the model's attributes say."""
         return self.model(a, b, **self._forward_kw)
 
+    def _held(self):
+        """under `agreement`: the held pixel counts of the forward just issued - int32 [n] on the device, that forward's own tensor"""
+        return self.model.agreement_counts if self.agreement is not None else None
+
+    def _held_to_host(self, slot, counts):
+        """on the post lane: the counts follow the frames into the slot's pinned buffer, ahead of `done`"""
+        n = counts.shape[0]
+        if slot["h_ag"].shape[0] < n:       # mode "resample": a batch has as many node frames as its plan needs
+            slot["h_ag"] = torch.zeros(n, dtype=torch.int32).pin_memory()
+        counts.record_stream(self._post)
+        slot["h_ag"][:n].copy_(counts, non_blocking=True)
+
     def _predict(self, x1, x2):
         """[n, k, 3, H, W] predictions per pair: k = 1 (reference mode) or `factor` recursive midpoints."""
         with torch.no_grad():
             if self.mode == "reference" or self.factor <= 1:
-                return self._forward(x1, x2).unsqueeze(1)
+                out = self._forward(x1, x2).unsqueeze(1)
+                self._ag = self._held()
+                return out
             # the model consumes normalised frames and returns [0,1] images: re-normalise midpoints to recurse.
             # The constants are created once: torch.tensor(..., device=) is a synchronous pageable copy, i.e. the host
             # would block behind the forward it has just enqueued and stop staging / draining beside it.
@@ -881,14 +924,17 @@ class FrameInterpolator:
             mean, std = self._norm
 
             def rec(a, b, depth):
-                m = self._forward(a, b)
+                m = (self._forward(a, b), self._held())
                 if depth == 1:
                     return [m]
-                mn = (m - mean) / std
+                mn = (m[0] - mean) / std
                 return rec(a, mn, depth - 1) + [m] + rec(mn, b, depth - 1)
 
             levels = (self.factor + 1).bit_length() - 1
-            return torch.stack(rec(x1, x2, levels), dim=1)
+            mids = rec(x1, x2, levels)
+            # [n, k] flattened: the counts in the order of the predictions
+            self._ag = torch.stack([c for _, c in mids], dim=1).reshape(-1) if self.agreement is not None else None
+            return torch.stack([m for m, _ in mids], dim=1)
 
     def _check_frames(self, frames, first, what):
         if self._depth:
@@ -943,7 +989,7 @@ class FrameInterpolator:
         words = (lambda v: v.view(np.uint16)) if self._depth else (lambda v: v)
         self._alloc(first.shape)
         self.scene_cuts, self.scene_scores = [], []
-        self.static_share = []
+        self.static_share, self.agreement_share = [], []
         main = torch.cuda.current_stream(self.device)
         # ramp-up: with three or more batches to come the FIRST one is half-size - the GPU starts after five staged frames instead of
         # nine, and (64 pairs at batch 8: 4 + 7 x 8 + 4) the last one's drain is half as long; every other batch is full.  Per-sample
@@ -965,16 +1011,22 @@ class FrameInterpolator:
                         self.scene_cuts.append((a, b, int(fs[1, k])))
             if self.static_guard is not None:     # written behind the frames, ahead of `done`
                 sg, area = slot["h_sg"].numpy(), float(self._dst[0] * self._dst[1])
+            if self.agreement is not None:        # likewise
+                ag, area = slot["h_ag"].numpy(), float(self._dst[0] * self._dst[1])
             for k, (a, _) in enumerate(chunk):
                 if self.mode == "recursive":
                     for j in range(npred):
                         if self.static_guard is not None:
                             self.static_share.append(int(sg[k * npred + j]) / area)
+                        if self.agreement is not None:
+                            self.agreement_share.append(int(ag[k * npred + j]) / area)
                         yield own(pred_h[k * npred + j])
                 else:
                     for _ in range(self.factor):
                         if self.static_guard is not None:
                             self.static_share.append(int(sg[k]) / area)
+                        if self.agreement is not None:
+                            self.agreement_share.append(int(ag[k]) / area)
                         yield own(pred_h[k])
                 yield own(src_h[k]) if (self.quirks or self._resize) else words(frames[a])
 
@@ -1021,11 +1073,14 @@ class FrameInterpolator:
             main.wait_event(slot["pre"])
             x1, x2 = self._rows(x, ia), self._rows(x, ib)
             pred = self._predict(x1, x2)                                      # [n, k, 3, H, W], on the caller's stream
+            held = self._ag                                                   # int32 [n k] on the device, or None
             slot["fwd"].record(main)
             with torch.cuda.stream(self._post):
                 self._post.wait_event(slot["fwd"])
                 flat = pred.reshape(-1, *pred.shape[2:])
                 flat.record_stream(self._post)                                # allocated on the caller's stream, read on this one
+                if held is not None:
+                    self._held_to_host(slot, held)
                 if self.quirks and (x1.data_ptr() < slot["x"].data_ptr() or x1.data_ptr() >= slot["x"].data_ptr() + slot["x"].numel() * 4):
                     x1.record_stream(self._post)                              # a gathered copy (non-consecutive rows), not a view of the slot
                 if self.zero_copy:
@@ -1084,7 +1139,7 @@ class FrameInterpolator:
         """levels[l] = [(pair of the batch, node)] of recursion level l + 1, in node-buffer order -> the model's output per non-empty level
         ([len(levels[l]), 3, H, W]); depths[k]: the depth of pair k's tree (a gap of m source intervals: D + ceil(log2 m)).  The recursion and
         the re-normalisation of a midpoint are ``_predict``'s."""
-        outs, norm = [], {}
+        outs, norm, held = [], {}, []
         if self._norm is None:
             self._norm = (torch.tensor(_lib.IMAGENET_MEAN, device=x.device).view(1, 3, 1, 1),
                           torch.tensor(_lib.IMAGENET_STD, device=x.device).view(1, 3, 1, 1))
@@ -1105,10 +1160,13 @@ class FrameInterpolator:
                     x2 = torch.stack([node(k, j + st) for (k, j), st in zip(items, step)])
                 m = self._forward(x1, x2)
                 outs.append(m)
+                held.append(self._held())
                 if l + 1 < len(levels) and levels[l + 1]:
                     mn = (m - mean) / std
                     for i, item in enumerate(items):
                         norm[item] = mn[i]
+        # the counts in node-buffer order, as the node frames are
+        self._ag = torch.cat(held) if self.agreement is not None and held else None
         return outs
 
     def _resample_batch(self, chunk, outs_of, ia, ib):
@@ -1188,7 +1246,7 @@ class FrameInterpolator:
         self._alloc(first.shape)
         self.scene_cuts, self.scene_scores = [], []
         self.duplicates, self.dedup_scores = [], []
-        self.static_share = []
+        self.static_share, self.agreement_share = [], []
         kept = list(range(a, b + 1)) if b > a else []
         if self.dedup is not None and b > a:
             # the set of forwards depends on the flags: the host reads them before it plans (one wait per run() call)
@@ -1216,9 +1274,12 @@ class FrameInterpolator:
                                  "d_emit": torch.empty(n_emit, *fs, dtype=torch.uint8, device=self.device),
                                  "h_emit": torch.empty(n_emit, *fs, dtype=torch.uint8).pin_memory()})
 
-        def drain(slot, chunk, n_out, first_node):
+        def drain(slot, chunk, n_out, first_node, own_node):
             slot["done"].synchronize()            # this batch's frames have been written into the pinned buffer
             emit_h = slot["h_emit"].numpy()
+            if self.agreement is not None:        # written behind the frames, ahead of `done`: an emitted frame made of node frames has the
+                ag, area = slot["h_ag"].numpy(), float(self._dst[0] * self._dst[1])     # share of the first node frame it is made of
+                self.agreement_share += [int(ag[i]) / area for i in own_node]
             if self.static_guard is not None:     # written behind the frames, ahead of `done`: an emitted frame made of node frames has its
                 sg, area = slot["h_sg"].numpy(), float(self._dst[0] * self._dst[1])     # gap's share (core depends on the two sources only)
                 self.static_share += [int(sg[i]) / area for i in first_node]
@@ -1250,9 +1311,12 @@ class FrameInterpolator:
                 slot["pre"].record(self._pre)
             main.wait_event(slot["pre"])
             preds = self._resample_forwards(x, ia, ib, levels, depths)                                     # on the caller's stream
+            held = self._ag                                                                           # int32 [n_nodes] on the device, or None
             slot["fwd"].record(main)
             with torch.cuda.stream(self._post):
                 self._post.wait_event(slot["fwd"])
+                if held is not None:
+                    self._held_to_host(slot, held)
                 off = 0
                 for m in preds:                                                                       # every node becomes bytes once
                     m.record_stream(self._post)
@@ -1281,7 +1345,9 @@ class FrameInterpolator:
                 staged = self._stage(self._slots[(ci + 1) & 1], frames, chunks[ci + 1])
             if prev is not None:
                 yield from drain(*prev)
-            prev = (slot, chunk, len(table), first_node)
+            # per emitted frame made of node frames: the first node frame its entry names
+            own_node = [(e[0] if e[0] & _lib.RESAMPLE_NODES else e[1]) & ~_lib.RESAMPLE_NODES for e in table if (e[0] | e[1]) & _lib.RESAMPLE_NODES]
+            prev = (slot, chunk, len(table), first_node, own_node)
         if prev is not None:
             yield from drain(*prev)
         if tail:
@@ -1318,10 +1384,10 @@ class FrameInterpolator:
             raise ValueError(f"run_chunked: chunk_pairs = {chunk_pairs} with dedup_threshold must be a multiple of dedup_span = {self.dedup_span}: "
                              "every chunk then starts and ends on a frame that is kept regardless, and sees what the whole clip would")
         L, it, held, lo = chunk_pairs * self.interval, iter(frames), [], 0
-        cuts, scores, dups, dscores, shares = [], [], [], [], []
+        cuts, scores, dups, dscores, shares, ashares = [], [], [], [], [], []
         self.scene_cuts, self.scene_scores = [], []
         self.duplicates, self.dedup_scores = [], []
-        self.static_share = []
+        self.static_share, self.agreement_share = [], []
         while True:
             for f in it:
                 held.append(f)
@@ -1340,6 +1406,8 @@ class FrameInterpolator:
                 self.duplicates, self.dedup_scores = list(dups), list(dscores)
                 shares += self.static_share
                 self.static_share = list(shares)
+                ashares += self.agreement_share
+                self.agreement_share = list(ashares)
             if final:
                 return
             held, lo = held[-1:], lo + L
@@ -1357,7 +1425,8 @@ class FrameInterpolator:
         ``done`` wait of the drain; no frame returns to the host.  The staged frames always reach the device by copy (``zero_copy`` is a
         property of ``run()``'s transport).  ``interpolation_factor``, ``mode``, ``reference_quirks``, ``frame_interval`` and
         ``scene_threshold`` do not affect ``evaluate``: a target has one midpoint and is never held.  ``static_guard`` does not either: the
-        model's own prediction is scored, not the guarded frame.
+        model's own prediction is scored, not the guarded frame.  ``agreement`` DOES: that guard is part of the forward, so the guarded
+        prediction is what is scored (``agreement_share`` is ``run()``'s and is left alone here).
 
         ``frames`` / ``rank`` / ``world`` as for ``run()``: a rank touches only the frames of its contiguous share of the targets, and
         the ranks' ``targets`` concatenated in rank order are the single-process result."""
