@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_agreement_guard_f32 added (where the two time directions of the ensemble disagree the plain blend of the source frames is emitted, decided on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_accumulate_frames added (motion blur from a shutter angle: every output frame the weighted integer mean of the node frames inside its exposure window, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_agreement_guard_f32 added (where the two time directions of the ensemble disagree the plain blend of the source frames is emitted, decided on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -582,6 +582,52 @@ typedef struct { unsigned a, b, w, f, h; } emavfi_resample_entry;
 int emavfi_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
                            const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_resample_entry *table,
                            const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift, void *stream);
+
+/* Motion blur.  Every frame the resampler emits is an instantaneous sample of the motion; a camera frame integrates light while the shutter
+ * is open.  With a shutter angle every output frame becomes the weighted mean of the tree nodes inside its exposure window, summed on the
+ * device: only the accumulated frames leave it.  The reference has nothing of the kind; this is an addition, off unless asked for.
+ *
+ * SHUTTER DEFINITION (the one place).  This is the project's own definition: it claims agreement with no outside tool.  It extends the
+ * TEMPORAL RESAMPLE DEFINITION; all arithmetic is integer, `/` is floor division: host, oracle and device agree bit for bit.
+ *   Scope.  P = 1 only: the output rate is an integer multiple Q >= 1 of the input rate (Q = 1, "add motion blur", included), so that every
+ *     window stays inside its pair.  P > 1 (24 -> 60) would cross pair and batch boundaries and is refused.
+ *   Exposure.  e = shutter / 360 = n / d in lowest terms, 0 < e <= 1.  Output k has s = k / Q, r = k - s Q; it opens at source time s + r / Q
+ *     and stays open for e / Q of a source interval: the angle refers to the OUTPUT frame period.
+ *   Weights, in units of 1 / (2 G Q d) of a source interval, G = 2^D: the window is [2 G d r, 2 G d r + 2 G n]; node j (0 .. G; 0 and G are
+ *     the two source frames) owns the cell [(2 j - 1) Q d, (2 j + 1) Q d]; w_j = max(0, min(cell_hi, win_hi) - max(cell_lo, win_lo)).  The
+ *     nonzero weights are contiguous and sum to 2 G n: the trapezoid rule on the node lattice.  They are divided by their gcd; the taps of the
+ *     output are the (j, w_j) with w_j > 0, S = sum w_j.  Refused: S > 65535 after the reduction, and an exposure shorter than one node
+ *     spacing (e / Q < 1 / G, that is G n < Q d: raise the depth).
+ *   Per sample out = (sum w_j s_j + S / 2) / S, s_j the sample of node j: a byte, or (word >> shift) & (2^depth - 1) of a 16-bit
+ *     little-endian word, written back as v << shift.  The largest intermediate is 65535 * 65535 + 32767 < 2^32: unsigned 32-bit holds
+ *     everything.  The mean acts on the frames AS EMITTED, the same arithmetic for every pixel format, as the blend above; it averages the
+ *     coded samples (no linear light).  A single tap copies its frame byte for byte; a single-tap output with j = 0 is the source frame.
+ *   Scene cuts.  Every output of a flagged pair is source frame s, those with r = 0 and those whose taps reach node G (the next shot) included.
+ *   The last frame.  The output that falls on the last source frame of a clip has no pair to integrate over: it is that frame itself.
+ *   Needed nodes of a pair: the taps of its outputs, closed under parents; only these are computed.
+ *   Known answers, (Q, D, shutter, r) -> (j,w) ...:  (1, 2, 180, 0) -> (0,1) (1,2) (2,1);  (1, 2, 360, 0) -> (0,1) (1,2) (2,2) (3,2) (4,1);
+ *     (1, 1, 180, 0) -> (0,1) (1,1);  (2, 2, 180, 0) -> (0,1) (1,1);  (2, 2, 180, 1) -> (2,1) (3,1);  (3, 3, 270, 1) -> (3,5) (4,6) (5,1),
+ *     needed nodes {2,3,4,5,6};  (1, 1, 90, 0) is refused.  At 180 degrees and D = 3 a pair needs nodes {1,2,3,4}: 4 forwards instead of 7.
+ *
+ * emavfi_accumulate_frames assembles n_out output frames at dst + k dst_stride from the two pools of emavfi_resample_frames, under the same
+ *   contract: `table` is a HOST pointer to n_out entries {n, f, h, tap[33], w[33]}, read and validated before the call returns, nothing of it
+ *   retained; it travels as kernel arguments, EMAVFI_ACCUMULATE_LAUNCH_CAP = 8 entries per launch.  tap[i] (i < n) = a frame index in
+ *   `srcs`, or EMAVFI_RESAMPLE_NODES + an index in `nodes`; w[i] its weight; f, h the resample entry's hold: flags != NULL, f != 0 and
+ *   flags[f - 1] != 0 copies srcs[h].  Else n = 1 copies tap[0]; else every sample is the mean above.  An entry never reads (nor forms the
+ *   address of) a frame it does not use; bytes between output frames are left as they were; dst must not overlap a pool.
+ * EMAVFI_E_ARG (never an abort), the message naming the argument: every refusal of emavfi_resample_frames that applies (all but its a, b and
+ *   w), and per entry n outside 1..33, a tap[i] (i < n) outside its pool, a w[i] of zero, weights that sum to more than 65535, f beyond
+ *   n_flags, for f != 0 an h outside srcs.
+ * Nothing is allocated, nothing synchronises, all work goes on `stream`.  Access width: an entry moves 16 bytes per lane and tap where every
+ *   frame address IT USES is 16-byte aligned - the last frame_bytes % 16 bytes: bytes / words -, else bytes / words throughout; all forms
+ *   run the same per-element functions (csrc/shutter_elem.h), the division by S as a multiply and a correction proven equal to `/` by
+ *   tests/host/host_check_shutter.cpp.  The kernel is short-lived and waits on nothing. */
+#define EMAVFI_ACCUMULATE_MAX_TAPS 33
+#define EMAVFI_ACCUMULATE_LAUNCH_CAP 8
+typedef struct { unsigned n, f, h; unsigned tap[EMAVFI_ACCUMULATE_MAX_TAPS]; unsigned w[EMAVFI_ACCUMULATE_MAX_TAPS]; } emavfi_accumulate_entry;
+int emavfi_accumulate_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
+                             const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_accumulate_entry *table,
+                             const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift, void *stream);
 
 /* Duplicate frames.  The resampler above puts every output frame at its true time and assumes that every INPUT frame sits at its true time
  * too.  24 fps film in a 30 fps stream, animation drawn on twos, screen captures and anything that went through a frame-rate filter break

@@ -1,0 +1,282 @@
+"""Motion blur from a shutter angle, the parts that need no device: the taps of an exposure window against the rational restatement
+(tests/shutter_oracle.py) and the known answers of the definition, plans and their shards, every refusal of the constructor and of the
+command line, the header, and the argument guards of emavfi_accumulate_frames."""
+import ctypes
+import os
+import re
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from emavfi import EMA_VFI, FrameInterpolator, cli, lib, y4m
+import shutter_oracle as oracle
+
+FI = FrameInterpolator
+
+KNOWN = [((1, 2, 180, 0), [(0, 1), (1, 2), (2, 1)]), ((1, 2, 360, 0), [(0, 1), (1, 2), (2, 2), (3, 2), (4, 1)]), ((1, 1, 180, 0), [(0, 1), (1, 1)]),
+         ((2, 2, 180, 0), [(0, 1), (1, 1)]), ((2, 2, 180, 1), [(2, 1), (3, 1)]), ((3, 3, 270, 1), [(3, 5), (4, 6), (5, 1)])]
+SHUTTERS = [45, 90, 144, "172.8", 180, 270, 360]
+
+
+def flat(levels):
+    return {j for lv in levels for j in lv}
+
+
+def test_the_known_answers_of_the_definition():
+    for args, want in KNOWN:
+        assert FI.shutter_taps(*args) == want == oracle.taps(*args), args
+    assert flat(FI.resample_needed({j for j, _ in FI.shutter_taps(3, 3, 270, 1)}, 3)) == {2, 3, 4, 5, 6} == oracle.needed({3, 4, 5}, 3)
+    with pytest.raises(ValueError, match="raise resample_depth"):
+        FI.shutter_taps(1, 1, 90, 0)
+    # 180 degrees at D = 3: nodes 0 .. 4 are tapped, {1, 2, 3, 4} are computed - 4 forwards instead of the full tree's 7
+    plan = FI.shutter_plan(5, 24, 24, 3, 180)
+    assert flat(plan.pairs[0]) == {1, 2, 3, 4} and plan.forwards == 4 * 4 and plan.G == 8 and plan.Q == 1
+    assert FI.resample_plan(5, 24, 8 * 24, 3).forwards == 4 * 7
+    # the same angle however it is written
+    assert FI.shutter_taps(1, 5, 172.8, 0) == FI.shutter_taps(1, 5, "172.8", 0) == FI.shutter_taps(1, 5, Fraction(864, 5), 0) == oracle.taps(1, 5, "864/5", 0)
+
+
+@pytest.mark.parametrize("shutter", SHUTTERS)
+def test_weights_are_the_rational_overlaps_and_refusals_follow_the_rule(shutter):
+    e = Fraction(shutter) / 360
+    n, d = e.numerator, e.denominator
+    for Q in range(1, 5):
+        for D in range(1, 6):
+            G = 1 << D
+            for r in range(Q):
+                short = G * n < Q * d
+                assert short == oracle.refused(Q, D, shutter)
+                if short:
+                    with pytest.raises(ValueError, match="raise resample_depth"):
+                        FI.shutter_taps(Q, D, shutter, r)
+                    continue
+                over = oracle.overlaps(Q, D, shutter, r)
+                unit = 2 * G * Q * d                                  # the definition's unit: 1 / (2 G Q d) of a source interval
+                unreduced = [int(w * unit) for _, w in over]
+                assert all((w * unit).denominator == 1 for _, w in over) and sum(unreduced) == 2 * G * n, (Q, D, r)
+                nz = [j for j, w in over if w > 0]
+                assert nz == list(range(nz[0], nz[-1] + 1)), ("contiguous", Q, D, r)
+                want = oracle.taps(Q, D, shutter, r)                  # S <= 2 G n <= 2 * 32 * 360: never refused for its sum here
+                got = FI.shutter_taps(Q, D, shutter, r)
+                assert got == want and [j for j, _ in got] == nz and 2 <= len(got) <= lib.ACCUMULATE_MAX_TAPS
+                g = unreduced[nz[0]] // got[0][1]
+                assert [w * g for _, w in got] == [unreduced[j] for j in nz] and sum(w for _, w in got) * g == 2 * G * n
+
+
+def test_a_weight_sum_above_65535_and_bad_arguments_are_refused():
+    with pytest.raises(ValueError, match="65535"):
+        FI.shutter_taps(1, 5, Fraction(359 * 1009 + 1, 1009), 0)      # a prime denominator: nothing reduces
+    with pytest.raises(ValueError):
+        oracle.taps(1, 5, Fraction(359 * 1009 + 1, 1009), 0)
+    for bad in (0, -180, 361, "360.5", "fast", None, True, float("nan")):
+        with pytest.raises(ValueError, match="shutter"):
+            FI.shutter_taps(1, 3, bad, 0)
+    for Q, D, r in ((0, 3, 0), (2, 3, 2), (2, 3, -1), (1, 0, 0), (1, 6, 0), (1.0, 3, 0)):
+        with pytest.raises(ValueError):
+            FI.shutter_taps(Q, D, 180, r)
+
+
+def test_needed_node_counts():
+    for (Q, D, shutter), want in (((1, 3, 180), 4), ((1, 3, 360), 7), ((1, 2, 180), 2), ((2, 3, 180), 5), ((1, 1, 180), 1), ((1, 5, 45), 6),
+                                  ((4, 2, 360), 3)):       # 45 degrees at D = 5 taps nodes 0 .. 4, whose ancestors 8 and 16 are computed too
+        plan = FI.shutter_plan(2, 10, 10 * Q, D, shutter)
+        tapped = {j for r in range(Q) for j, _ in oracle.taps(Q, D, shutter, r)}
+        assert flat(plan.pairs[0]) == oracle.needed(tapped, D) and plan.forwards == len(oracle.needed(tapped, D)) == want, (Q, D, shutter)
+        assert len(plan.outputs) == Q + 1 and plan.outputs[-1] == (Q, 1, ((0, 1),))
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_rank_plans_concatenate_to_the_whole(world):
+    for n, Q, shutter in ((7, 1, 180), (7, 2, 360), (2, 3, 270), (1, 1, 180), (0, 1, 180)):
+        whole = FI.shutter_plan(n, 25, 25 * Q, 3, shutter)
+        parts = [FI.shutter_plan(n, 25, 25 * Q, 3, shutter, rank, world) for rank in range(world)]
+        assert [o for p in parts for o in p.outputs] == whole.outputs and len(whole.outputs) == (0 if n == 0 else (n - 1) * Q + 1)
+        merged = {}
+        for p in parts:
+            assert not set(p.pairs) & set(merged)
+            merged.update(p.pairs)
+        assert merged == whole.pairs and sum(p.forwards for p in parts) == whole.forwards
+        assert [k for k, _, _ in whole.outputs] == list(range(len(whole.outputs)))
+        assert all(s == k // Q and taps == tuple(oracle.taps(Q, 3, shutter, k - s * Q)) for k, s, taps in whole.outputs[:-1])
+
+
+def test_the_harness_refuses_what_a_shutter_cannot_mean():
+    model = EMA_VFI(mid_channels=8)
+    ok = dict(mode="resample", reference_quirks=False, rate_in=24, rate_out=24, shutter=180)
+    for kw, word in ((dict(rate_out=60), "P > 1"), (dict(resample_method="blend"), "resample_method='blend'"),
+                     (dict(dedup_threshold=0.01), "dedup_threshold"), (dict(reference_quirks=True), "reference_quirks"),
+                     (dict(zero_copy=True), "zero_copy"), (dict(shutter=0), "shutter"), (dict(shutter=400), "shutter"),
+                     (dict(shutter="wide"), "shutter"), (dict(shutter=20), "raise resample_depth"),
+                     (dict(rate_out=96, resample_depth=1), "raise resample_depth")):
+        with pytest.raises(ValueError, match=word):
+            FI(model, **{**ok, **kw})
+    for mode in ("reference", "recursive"):
+        with pytest.raises(ValueError, match="shutter belongs to mode='resample'"):
+            FI(model, mode=mode, shutter=180, reference_quirks=False)
+    with pytest.raises(ValueError, match="P > 1"):
+        FI.shutter_plan(5, 24, 60, 3, 180)
+    for good in (ok, {**ok, "rate_out": 48, "shutter": "172.8"}, {**ok, "shutter": Fraction(1080, 7), "resample_depth": 5},
+                 {**ok, "pixel_format": "p010"}, {**ok, "scene_threshold": 0.3, "static_guard": 1, "scale": 0.5}):
+        with pytest.raises(RuntimeError, match="no CPU path"):              # valid arguments get as far as the device check
+            FI(model, **good)
+    # evaluate() on an interpolator that has a shutter: the refusal comes before anything touches a device
+    fi = FI.__new__(FI)
+    fi.shutter, fi._depth = Fraction(180), 0
+    with pytest.raises(ValueError, match="evaluate\\(\\) with a shutter"):
+        fi.evaluate([])
+
+
+def test_command_line_refusals_need_no_device(capsys, tmp_path):
+    src = tmp_path / "in.y4m"
+    with y4m.Y4MWriter(str(src), y4m.Y4MHeader(16, 16, 24, 1)) as w:
+        w.write(np.zeros((24, 16), np.uint8))
+    base = [str(src), str(tmp_path / "out.y4m"), "--synthetic-weights", "0"]
+    args = cli.parser().parse_args(base + ["--output-fps", "24", "--shutter", "1080/7"])
+    assert args.shutter == "1080/7" and cli.parser().parse_args(base).shutter is None
+    for extra, word in ((["--shutter", "180"], "--shutter needs --output-fps"),
+                        (["--output-fps", "60", "--shutter", "180"], "P > 1"),
+                        (["--output-fps", "24", "--shutter", "180", "--resample", "blend"], "--shutter excludes --resample blend"),
+                        (["--output-fps", "24", "--shutter", "180", "--dedup", "0.01"], "--shutter excludes --dedup"),
+                        (["--output-fps", "24", "--shutter", "180", "--evaluate"], "--shutter excludes --evaluate"),
+                        (["--output-fps", "24", "--shutter", "180", "--reference-quirks"], "--output-fps excludes --reference-quirks"),
+                        (["--output-fps", "24", "--shutter", "0"], "shutter"), (["--output-fps", "24", "--shutter", "wide"], "shutter"),
+                        (["--output-fps", "24", "--shutter", "20"], "raise resample_depth"),
+                        (["--output-fps", "24", "--shutter", "180", "--resample-depth", "9"], "resample_depth")):
+        assert cli.main(base + extra) != 0
+        err = capsys.readouterr().err
+        assert word in err, (extra, err)
+    assert not (tmp_path / "out.y4m").exists()
+
+
+# ---------------------------------------------------------------- the entry
+def test_header_symbols_and_exports_agree():
+    hdr = open(os.path.join(ROOT, "include", "emavfi.h")).read()
+    L = lib.load()
+    assert re.search(r"^int emavfi_accumulate_frames\(", hdr, re.M) and "emavfi_accumulate_frames" in lib.SYMBOLS and hasattr(L, "emavfi_accumulate_frames")
+    assert hdr.count("SHUTTER DEFINITION (the one place)") == 1 and hdr.count("SHUTTER DEFINITION") == 1
+    assert f"#define EMAVFI_ACCUMULATE_MAX_TAPS {lib.ACCUMULATE_MAX_TAPS}\n" in hdr and lib.ACCUMULATE_MAX_TAPS == oracle.MAX_TAPS == 33
+    assert f"#define EMAVFI_ACCUMULATE_LAUNCH_CAP {lib.ACCUMULATE_LAUNCH_CAP}\n" in hdr and lib.ACCUMULATE_LAUNCH_CAP == oracle.LAUNCH_CAP == 8
+    assert lib.ACCUMULATE_MAX_SUM == oracle.MAX_SUM == 65535
+    assert "#define EMAVFI_VERSION 403 " in hdr and L.emavfi_version() == 403
+    assert re.search(r"emavfi_accumulate_frames added \([^)]*same version: the packed layout is unchanged", hdr)
+    assert ctypes.sizeof(lib.AccumulateEntry) == 4 * (3 + 2 * 33)
+    elem = open(os.path.join(ROOT, "video-frame-interpolation_amd", "csrc", "shutter_elem.h")).read()
+    assert "SHUTTER_CAP = 8" in elem and "SHUTTER_MAX_TAPS = 33" in elem
+    for args, want in KNOWN:                                       # the known answers are stated where the definition is
+        assert f"({', '.join(map(str, args))}) -> " + " ".join(f"({j},{w})" for j, w in want) in hdr, args
+
+
+FB, N = 4096, lib.RESAMPLE_NODES
+SIZE_MAX = ctypes.c_size_t(-1).value
+
+
+def _entry(taps=(0, N | 1, 1), weights=(1, 2, 1), f=0, h=0, n=None):
+    e = lib.AccumulateEntry()
+    e.n, e.f, e.h = len(taps) if n is None else n, f, h
+    for i, (t, w) in enumerate(zip(taps, weights)):
+        e.tap[i], e.w[i] = t, w
+    return e
+
+
+def _call(L, dst=1 << 20, ds=FB, n=2, srcs=2 << 20, ss=FB, ns=2, nodes=3 << 20, nds=FB, nn=2, table=True, flags=4 << 20, nf=2, fb=FB, sb=1, depth=8,
+          shift=0, entries=None):
+    """fake (never dereferenced) frame pointers; the table is real host memory - the entry reads it"""
+    rows = [_entry() for _ in range(max(n, 1))]
+    for k, e in (entries or {}).items():
+        rows[k] = e
+    arr = (lib.AccumulateEntry * len(rows))(*rows)
+    tp = ctypes.cast(arr, ctypes.c_void_p) if table else None
+    return L.emavfi_accumulate_frames(dst, ds, n, srcs, ss, ns, nodes, nds, nn, tp, flags, nf, fb, sb, depth, shift, None), lib.last_error()
+
+
+def test_accumulate_frames_refuses_bad_arguments_with_a_message():
+    """every refusal happens on the host, before any device work, and names its argument"""
+    L = lib.load()
+    two = dict(sb=2, depth=10)
+    bad = [
+        (dict(n=0), "n_out"), (dict(n=-1), "n_out"), (dict(ns=-1), "n_srcs"), (dict(nn=-2), "n_nodes"), (dict(nf=-1), "n_flags"),
+        (dict(sb=0), "sample_bytes"), (dict(sb=4), "sample_bytes"), (dict(depth=10), "depth"), (dict(sb=2, depth=8), "depth"),
+        (dict(sb=2, depth=14), "depth"), (dict(shift=1), "shift"), (dict(**two, shift=7), "shift"), (dict(sb=2, depth=12, shift=5), "shift"),
+        (dict(sb=2, depth=16, shift=1), "shift"), (dict(**two, shift=-1), "shift"),
+        (dict(fb=0), "frame_bytes"), (dict(fb=(1 << 40) + 1, ds=1 << 41, ss=1 << 41, nds=1 << 41), "frame_bytes"), (dict(**two, fb=4095), "odd"),
+        (dict(ds=FB - 1), "dst_stride"), (dict(ss=FB - 1), "src_stride"), (dict(nds=0), "node_stride"),
+        (dict(**two, ds=FB + 1), "dst_stride"), (dict(**two, ss=FB + 3), "src_stride"), (dict(**two, nds=FB + 5), "node_stride"),
+        (dict(ds=SIZE_MAX, n=3), "overflows"), (dict(**two, ss=SIZE_MAX - 1, ns=3), "overflows"),
+        (dict(dst=None), "dst"), (dict(table=False), "table"), (dict(srcs=None), "srcs"), (dict(nodes=None), "nodes"), (dict(flags=None), "flags"),
+        (dict(**two, dst=(1 << 20) + 1), "2-byte"), (dict(**two, srcs=(2 << 20) + 1), "2-byte"), (dict(**two, nodes=(3 << 20) + 1), "2-byte"),
+        (dict(flags=(4 << 20) + 2), "4-byte"),
+        (dict(dst=(2 << 20) - 2 * FB + 1), "overlaps srcs"), (dict(dst=(2 << 20) + 2 * FB - 1), "overlaps srcs"),
+        (dict(dst=(3 << 20) + FB, n=1, nn=3), "overlaps nodes"), (dict(dst=(3 << 20) - FB, ds=3 * FB), "overlaps nodes"),
+        (dict(n=19, entries={18: _entry(n=0)}), "table[18].n"), (dict(n=19, entries={8: _entry(n=34)}), "table[8].n"),
+        (dict(entries={1: _entry(taps=(0, 1, 2))}), "table[1].tap[2]"), (dict(entries={0: _entry(taps=(0, N | 2, 1))}), "table[0].tap[1]"),
+        (dict(entries={1: _entry(weights=(1, 0, 1))}), "table[1].w[1] is zero"),
+        (dict(entries={1: _entry(weights=(65534, 1, 1))}), "table[1].w sums to more than 65535"),
+        (dict(entries={0: _entry(weights=(1, 1, 0xFFFFFFFF))}), "table[0].w sums to more than 65535"),
+        (dict(entries={0: _entry(taps=(0, 1) * 16 + (0,), weights=(1,) * 32 + (65504,))}), "table[0].w sums to more than 65535"),
+        (dict(entries={1: _entry(f=3)}), "table[1].f"), (dict(entries={1: _entry(f=1)}, flags=None, nf=0), "table[1].f"),
+        (dict(entries={0: _entry(f=1, h=2)}), "table[0].h"), (dict(nodes=None, nds=0, nn=0), "table[0].tap[1]"),
+        # with null pointers every other check is still reached and named
+        (dict(dst=None, srcs=None, nodes=None, ds=1), "dst_stride"), (dict(dst=None, table=False, depth=9), "depth"),
+    ]
+    for kw, word in bad:
+        rc, msg = _call(L, **kw)
+        assert rc == -1 and "accumulate_frames" in msg and word in msg, (kw, rc, msg)
+    # a tap beyond n is no tap and is not looked at: the next entry is what is named
+    rc, msg = _call(L, entries={0: _entry(taps=(0, 1, 0xFFFFFFFF), weights=(1, 1, 0), n=2), 1: _entry(n=0)})
+    assert rc == -1 and "table[1].n" in msg, msg
+
+
+def test_python_wrapper_validates_before_the_library():
+    import torch
+    d, s = torch.zeros(2, 8, dtype=torch.uint8), torch.zeros(2, 8, dtype=torch.uint8)
+    with pytest.raises(RuntimeError, match="PINNED"):
+        lib.accumulate_frames(d, s, None, [((0, 1), (1, 1), 0, 0)] * 2)
+
+
+def test_shutter_host_check_runs_clean_under_asan_ubsan_and_matches_the_oracle():
+    """the sanitizer build of the host side (csrc/Makefile, `make asan`) also builds tests/host/host_check_shutter, a stand-alone program:
+    every guard of the entry under ASan + UBSan - the table read from real host memory, its last entry included -, the multiply-and-correct
+    division of csrc/shutter_elem.h against `/` for every weight sum, and the per-element functions the kernel is made of in a plain loop over
+    generated frames - its checksums must be the oracle's"""
+    import shutil
+    import subprocess
+    llvm = "/opt/rocm/lib/llvm/bin/clang"
+    if not os.path.exists(llvm) or shutil.which("make") is None:
+        pytest.skip("ROCm clang not available")
+    rt = subprocess.run([llvm, "-print-file-name=libclang_rt.asan-x86_64.so"], capture_output=True, text=True).stdout.strip()
+    if not os.path.isabs(rt) or not os.path.exists(rt):
+        pytest.skip("no shared ASan runtime in this toolchain")
+    csrc = os.path.join(ROOT, "video-frame-interpolation_amd", "csrc")
+    r = subprocess.run(["make", "-C", csrc, "asan", "-j", str(min(8, os.cpu_count() or 1))], capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stderr[-3000:]
+    exe = os.path.join(ROOT, "build", "csrc_asan", "host_check_shutter")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
+               LD_LIBRARY_PATH=os.path.dirname(rt) + os.pathsep + os.environ.get("LD_LIBRARY_PATH", ""))
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "host_check_shutter: ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+    got = re.findall(r"host_check_shutter: sample_bytes (\d) depth (\d+) shift (\d+) case (\d+): mean (\d+)", r.stdout)
+    assert len(got) == 6 * len(oracle.HOST_CASES), r.stdout
+    for sb, depth, shift, case, ck in (tuple(int(v) for v in g) for g in got):
+        weights = oracle.HOST_CASES[case]
+        frames = [oracle.gen(oracle.HOST_SAMPLES, 255 if sb == 1 else 65535, t) for t in range(len(weights))]
+        if sb == 1:
+            v = oracle.mean([f.astype(np.uint8) for f in frames], weights)
+        else:
+            v = oracle.mean([f.astype("<u2").view(np.uint8) for f in frames], weights, 2, depth, shift).view("<u2")
+        assert oracle.checksum(v) == ck, (sb, depth, shift, case)
+
+
+def test_the_oracle_mean_has_the_stated_properties():
+    rng = np.random.default_rng(5)
+    a, b, c = (rng.integers(0, 256, 999, dtype=np.uint8) for _ in range(3))
+    assert np.array_equal(oracle.mean([a, b], (1, 1)), ((a.astype(int) + b + 1) >> 1).astype(np.uint8))
+    assert np.array_equal(oracle.mean([a, a, a], (5, 6, 1)), a)
+    assert np.array_equal(oracle.mean([a, b, c], (1, 2, 1)), ((a.astype(int) + 2 * b.astype(int) + c + 2) >> 2).astype(np.uint8))
+    top = np.full(8, 0xFFFF, "<u2").view(np.uint8)
+    assert np.array_equal(oracle.mean([top] * 33, (1985,) * 32 + (2015,), 2, 16, 0), top)      # 65535 * 65535 + 32767 stays below 2^32
+    words = (rng.integers(0, 1024, 64) << 6).astype("<u2")
+    got = oracle.mean([words.view(np.uint8), np.zeros(128, np.uint8)], (3, 1), 2, 10, 6).view("<u2")
+    assert np.array_equal(got, (((words >> 6).astype(int) * 3 + 2) // 4 << 6).astype("<u2"))

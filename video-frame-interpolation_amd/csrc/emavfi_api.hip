@@ -5,6 +5,7 @@
 #include "common.h"
 #include "misc_kernels.h"
 #include "resample_elem.h"
+#include "shutter_elem.h"
 #include "dedup_elem.h"
 #include "static_elem.h"
 #include "ensemble_elem.h"
@@ -1709,11 +1710,11 @@ static bool resample_span(int n, size_t stride, size_t frame_bytes, size_t *span
     return !(__builtin_mul_overflow((size_t)(n - 1), stride, span) || __builtin_add_overflow(*span, frame_bytes, span));
 }
 
-int emavfi_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
-                           const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_resample_entry *table,
-                           const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift, void *stream)
+// what emavfi_resample_frames and emavfi_accumulate_frames refuse alike: everything but the entries of the table
+static int resample_pools_check(const char *what, const unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs,
+                                size_t src_stride, int n_srcs, const unsigned char *nodes, size_t node_stride, int n_nodes, const void *table,
+                                const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift)
 {
-    const char *const what = "resample_frames";
     if (n_out < 1) return fail(EMAVFI_E_ARG, "%s: n_out must be >= 1", what);
     if (n_srcs < 0 || n_nodes < 0 || n_flags < 0) return fail(EMAVFI_E_ARG, "%s: n_srcs, n_nodes, n_flags must be >= 0", what);
     if (sample_bytes != 1 && sample_bytes != 2) return fail(EMAVFI_E_ARG, "%s: sample_bytes = %d (sample_bytes must be 1 or 2)", what, sample_bytes);
@@ -1749,6 +1750,17 @@ int emavfi_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, con
     for (int k = 1; k < 3; ++k)
         if (pools[k].n > 0 && d0 < base[k] + span[k] && base[k] < d0 + span[0])
             return fail(EMAVFI_E_ARG, "%s: dst overlaps %s", what, k == 1 ? "srcs" : "nodes");
+    return EMAVFI_OK;
+}
+
+int emavfi_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
+                           const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_resample_entry *table,
+                           const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift, void *stream)
+{
+    const char *const what = "resample_frames";
+    if (const int rc = resample_pools_check(what, dst, dst_stride, n_out, srcs, src_stride, n_srcs, nodes, node_stride, n_nodes, table, flags,
+                                            n_flags, frame_bytes, sample_bytes, depth, shift))
+        return rc;
     for (int k = 0; k < n_out; ++k) {
         const emavfi_resample_entry &e = table[k];
         if (e.w > 256u) return fail(EMAVFI_E_ARG, "%s: table[%d].w = %u is above 256", what, k, e.w);
@@ -1766,6 +1778,43 @@ int emavfi_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, con
     }
     EMAVFI_TRY(launch_resample_frames(dst, dst_stride, n_out, srcs, src_stride, nodes, node_stride, reinterpret_cast<const ResampleEntry *>(table),
                                       flags, frame_bytes, sample_bytes, depth, shift, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+// ---- shutter accumulation (include/emavfi.h, "SHUTTER DEFINITION"): every check runs on the host, the table is read here and not kept
+static_assert(sizeof(emavfi_accumulate_entry) == sizeof(AccumulateEntry) && EMAVFI_ACCUMULATE_LAUNCH_CAP == SHUTTER_CAP &&
+              EMAVFI_ACCUMULATE_MAX_TAPS == SHUTTER_MAX_TAPS, "header, misc_kernels.h and shutter_elem.h disagree");
+
+int emavfi_accumulate_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
+                             const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_accumulate_entry *table,
+                             const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift, void *stream)
+{
+    const char *const what = "accumulate_frames";
+    if (const int rc = resample_pools_check(what, dst, dst_stride, n_out, srcs, src_stride, n_srcs, nodes, node_stride, n_nodes, table, flags,
+                                            n_flags, frame_bytes, sample_bytes, depth, shift))
+        return rc;
+    for (int k = 0; k < n_out; ++k) {
+        const emavfi_accumulate_entry &e = table[k];
+        if (e.n < 1u || e.n > (unsigned)EMAVFI_ACCUMULATE_MAX_TAPS)
+            return fail(EMAVFI_E_ARG, "%s: table[%d].n = %u is outside 1..%d", what, k, e.n, EMAVFI_ACCUMULATE_MAX_TAPS);
+        unsigned sum = 0u;                                            // at most 33 weights below 2^16 each once the loop has passed
+        for (unsigned t = 0; t < e.n; ++t) {
+            const bool node = e.tap[t] & EMAVFI_RESAMPLE_NODES;
+            const unsigned i = e.tap[t] & ~EMAVFI_RESAMPLE_NODES;
+            if (i >= (unsigned)(node ? n_nodes : n_srcs))
+                return fail(EMAVFI_E_ARG, "%s: table[%d].tap[%u] = %s index %u is outside its pool of %d frames", what, k, t,
+                            node ? "nodes" : "srcs", i, node ? n_nodes : n_srcs);
+            if (e.w[t] == 0u) return fail(EMAVFI_E_ARG, "%s: table[%d].w[%u] is zero (a frame without weight is no tap)", what, k, t);
+            if (e.w[t] > SHUTTER_MAX_SUM || (sum += e.w[t]) > SHUTTER_MAX_SUM)
+                return fail(EMAVFI_E_ARG, "%s: table[%d].w sums to more than %u at w[%u] = %u", what, k, SHUTTER_MAX_SUM, t, e.w[t]);
+        }
+        if (e.f > (unsigned)n_flags) return fail(EMAVFI_E_ARG, "%s: table[%d].f = %u is beyond n_flags = %d", what, k, e.f, n_flags);
+        if (e.f != 0 && e.h >= (unsigned)n_srcs)
+            return fail(EMAVFI_E_ARG, "%s: table[%d].h = %u is outside the srcs pool of %d frames", what, k, e.h, n_srcs);
+    }
+    EMAVFI_TRY(launch_accumulate_frames(dst, dst_stride, n_out, srcs, src_stride, nodes, node_stride,
+                                        reinterpret_cast<const AccumulateEntry *>(table), flags, frame_bytes, sample_bytes, depth, shift,
+                                        (hipStream_t)stream), what);
     return EMAVFI_OK;
 }
 

@@ -119,6 +119,12 @@ struct ResampleEntry { unsigned a, b, w, f, h; };   // emavfi_resample_entry
 int launch_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride,
                            const unsigned char *nodes, size_t node_stride, const ResampleEntry *table, const unsigned *flags, size_t frame_bytes,
                            int sample_bytes, int depth, int shift, hipStream_t s);
+// shutter accumulation (include/emavfi.h, "SHUTTER DEFINITION"): arguments already validated; `table` is a HOST pointer, read before the
+// call returns and passed on as kernel arguments, SHUTTER_CAP (shutter_elem.h) entries per launch
+struct AccumulateEntry { unsigned n, f, h; unsigned tap[33]; unsigned w[33]; };   // emavfi_accumulate_entry
+int launch_accumulate_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride,
+                             const unsigned char *nodes, size_t node_stride, const AccumulateEntry *table, const unsigned *flags,
+                             size_t frame_bytes, int sample_bytes, int depth, int shift, hipStream_t s);
 // static regions held on the device (include/emavfi.h, "STATIC REGION DEFINITION"): arguments already validated; `table` is a HOST pointer, read
 // before the call returns and passed on as kernel arguments, STATIC_CAP (static_elem.h) entries per launch; `counts` may be null
 struct StaticEntry { unsigned a, b; };   // emavfi_static_entry

@@ -4,6 +4,7 @@
 #include "misc_kernels.h"
 #include "scene_elem.h"
 #include "resample_elem.h"
+#include "shutter_elem.h"
 #include "dedup_elem.h"
 #include "static_elem.h"
 #include "ensemble_elem.h"
@@ -2296,6 +2297,140 @@ int launch_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, con
         p.dst = dst + (size_t)first * dst_stride;
         for (int k = 0; k < n; ++k) p.e[k] = table[first + k];
         resample_frames_kernel<<<dim3(pieces, (unsigned)n), 256, 0, s>>>(p);
+        if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Shutter accumulation: every output frame the weighted integer mean of up to 33 source and node frames (include/emavfi.h, "SHUTTER
+// DEFINITION"; per-element functions: shutter_elem.h).
+//   accumulate_frames_kernel   grid (32 KiB pieces of a frame, entries of this launch): one workgroup row per entry.  The table travels as
+//                              kernel arguments, SHUTTER_CAP entries per launch, with each entry's weight sum S and its reciprocal word
+//                              (S is uniform per entry, so the division is shutter_div's multiply and correct); a workgroup reads its
+//                              entry through scalar loads.  A held or single-tap entry copies its piece of ONE frame and forms no other
+//                              address.  Else 16 bytes per lane and tap where dst and every tap of the entry are 16-byte aligned (the last
+//                              frame_bytes % 16 bytes: bytes / words), the 16 (or 8) sums of a lane in 32-bit registers and the loads of
+//                              SHUTTER_FLIGHT taps issued before the first is used: the kernel reads n frames and writes one, and what
+//                              limits it is how many bytes it keeps in flight.  Unaligned entries go by bytes / words throughout,
+//                              through the same per-element functions.  Nothing waits on anything: no LDS, no atomics.
+// ------------------------------------------------------------------------------------------
+constexpr int SHUTTER_FLIGHT = 4;
+struct AccumulateArgs {
+    unsigned char *dst;              // the first output frame of THIS launch
+    size_t dst_stride;
+    const unsigned char *srcs;
+    size_t src_stride;
+    const unsigned char *nodes;
+    size_t node_stride;
+    const unsigned *flags;
+    size_t frame_bytes;
+    int shift;
+    unsigned mask;
+    unsigned sum[SHUTTER_CAP], magic[SHUTTER_CAP];   // per entry: S = the sum of its weights, shutter_magic(S)
+    AccumulateEntry e[SHUTTER_CAP];
+};
+static_assert(sizeof(AccumulateArgs) <= 4096, "the table must fit the kernel argument segment");
+
+__device__ __forceinline__ const unsigned char *accumulate_frame(const AccumulateArgs &p, unsigned i)
+{
+    return (i & RESAMPLE_POOL_NODES) ? p.nodes + (size_t)(i & ~RESAMPLE_POOL_NODES) * p.node_stride : p.srcs + (size_t)i * p.src_stride;
+}
+
+// taps t0 .. t0 + K - 1 of an entry into the sums of the 16 bytes at `at`: K loads issued, then used
+template <int SB, int K>
+__device__ __forceinline__ void accumulate_taps(const AccumulateArgs &p, const AccumulateEntry &e, unsigned t0, size_t at, ShutterSums &ax,
+                                                ShutterSums &ay, ShutterSums &az, ShutterSums &aw)
+{
+    uint4 v[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) v[i] = *reinterpret_cast<const uint4 *>(accumulate_frame(p, e.tap[t0 + i]) + at);
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        const unsigned w = e.w[t0 + i];
+        shutter_add_dword(ax, v[i].x, w, SB, p.mask, p.shift);
+        shutter_add_dword(ay, v[i].y, w, SB, p.mask, p.shift);
+        shutter_add_dword(az, v[i].z, w, SB, p.mask, p.shift);
+        shutter_add_dword(aw, v[i].w, w, SB, p.mask, p.shift);
+    }
+}
+
+template <int SB>   // sample_bytes
+__global__ __launch_bounds__(256) void accumulate_frames_kernel(AccumulateArgs p)
+{
+    const AccumulateEntry &e = p.e[blockIdx.y];                       // uniform: read where it lies, among the kernel arguments
+    unsigned char *d = p.dst + (size_t)blockIdx.y * p.dst_stride;
+    const size_t lo = (size_t)blockIdx.x * HOLD_PIECE, hi = lo + HOLD_PIECE < p.frame_bytes ? lo + HOLD_PIECE : p.frame_bytes;
+    size_t x = lo;
+    const bool held = p.flags && e.f && p.flags[e.f - 1];
+    const unsigned n = e.n;
+    if (held || n == 1u) {                                            // one frame, byte for byte: source frame h, or the only tap
+        const unsigned char *a = accumulate_frame(p, held ? e.h : e.tap[0]);
+        if ((((uintptr_t)d | (uintptr_t)a) & 15) == 0) {
+            const size_t nv = (hi - lo) >> 4;
+            for (size_t q = threadIdx.x; q < nv; q += 256) reinterpret_cast<uint4 *>(d + lo)[q] = reinterpret_cast<const uint4 *>(a + lo)[q];
+            x += nv << 4;
+        }
+        for (x += threadIdx.x; x < hi; x += 256) d[x] = a[x];
+        return;
+    }
+    const unsigned S = p.sum[blockIdx.y], M = p.magic[blockIdx.y];
+    uintptr_t bits = (uintptr_t)d;
+    for (unsigned t = 0; t < n; ++t) bits |= (uintptr_t)accumulate_frame(p, e.tap[t]);
+    if ((bits & 15) == 0) {
+        const size_t nv = (hi - lo) >> 4;
+        for (size_t q = threadIdx.x; q < nv; q += 256) {
+            const size_t at = lo + (q << 4);
+            ShutterSums ax{}, ay{}, az{}, aw{};                       // one per dword of the lane's 16 bytes
+            unsigned t = 0;
+            for (; t + SHUTTER_FLIGHT <= n; t += SHUTTER_FLIGHT) accumulate_taps<SB, SHUTTER_FLIGHT>(p, e, t, at, ax, ay, az, aw);
+            if (n - t == 3u) accumulate_taps<SB, 3>(p, e, t, at, ax, ay, az, aw);
+            else if (n - t == 2u) accumulate_taps<SB, 2>(p, e, t, at, ax, ay, az, aw);
+            else if (n - t == 1u) accumulate_taps<SB, 1>(p, e, t, at, ax, ay, az, aw);
+            uint4 r;
+            r.x = shutter_mean_dword(ax, S, M, SB, p.shift);
+            r.y = shutter_mean_dword(ay, S, M, SB, p.shift);
+            r.z = shutter_mean_dword(az, S, M, SB, p.shift);
+            r.w = shutter_mean_dword(aw, S, M, SB, p.shift);
+            *reinterpret_cast<uint4 *>(d + at) = r;
+        }
+        x += nv << 4;
+    }
+    if (SB == 1) {
+        for (x += threadIdx.x; x < hi; x += 256) {
+            unsigned sum = 0u;
+            for (unsigned t = 0; t < n; ++t) sum += e.w[t] * accumulate_frame(p, e.tap[t])[x];
+            d[x] = (unsigned char)shutter_mean(sum, S, M);
+        }
+    } else {                                                          // frame_bytes, lo and every frame address are even
+        for (x += 2 * (size_t)threadIdx.x; x < hi; x += 512) {
+            unsigned sum = 0u;
+            for (unsigned t = 0; t < n; ++t)
+                sum += e.w[t] * shutter_sample(*reinterpret_cast<const unsigned short *>(accumulate_frame(p, e.tap[t]) + x), p.mask, p.shift);
+            *reinterpret_cast<unsigned short *>(d + x) = (unsigned short)(shutter_mean(sum, S, M) << p.shift);
+        }
+    }
+}
+
+int launch_accumulate_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride,
+                             const unsigned char *nodes, size_t node_stride, const AccumulateEntry *table, const unsigned *flags,
+                             size_t frame_bytes, int sample_bytes, int depth, int shift, hipStream_t s)
+{
+    AccumulateArgs p{};
+    p.dst_stride = dst_stride; p.srcs = srcs; p.src_stride = src_stride; p.nodes = nodes; p.node_stride = node_stride;
+    p.flags = flags; p.frame_bytes = frame_bytes; p.shift = shift; p.mask = (1u << depth) - 1u;
+    const unsigned pieces = (unsigned)((frame_bytes + HOLD_PIECE - 1) / HOLD_PIECE);
+    for (int first = 0; first < n_out; first += SHUTTER_CAP) {
+        const int n = n_out - first < SHUTTER_CAP ? n_out - first : SHUTTER_CAP;
+        p.dst = dst + (size_t)first * dst_stride;
+        for (int k = 0; k < n; ++k) {
+            p.e[k] = table[first + k];
+            p.sum[k] = 0u;
+            for (unsigned t = 0; t < p.e[k].n; ++t) p.sum[k] += p.e[k].w[t];
+            p.magic[k] = shutter_magic(p.sum[k]);
+        }
+        if (sample_bytes == 1) accumulate_frames_kernel<1><<<dim3(pieces, (unsigned)n), 256, 0, s>>>(p);
+        else accumulate_frames_kernel<2><<<dim3(pieces, (unsigned)n), 256, 0, s>>>(p);
         if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
     }
     return 0;

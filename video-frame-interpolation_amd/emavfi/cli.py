@@ -57,6 +57,11 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--resample", choices=("nearest", "blend"), default="nearest",
                    help="with --output-fps: the closest midpoint (default), or the two around the output time mixed")
     p.add_argument("--resample-depth", type=int, default=3, metavar="D", help="with --output-fps: midpoints down to 1 / 2^D of a frame interval (1..5, default 3)")
+    p.add_argument("--shutter", default=None, metavar="DEGREES",
+                   help="with --output-fps at an integer multiple of the stream's rate (the rate itself included: blur is added, the rate "
+                        "stays): motion blur - every output frame is the mean of the midpoints inside an exposure of DEGREES / 360 of its "
+                        "frame period (180, 172.8 or 1080/7; at most 360), summed on the device; no quality claim is made; excludes "
+                        "--resample blend, --dedup and --evaluate")
     p.add_argument("--dedup", type=float, default=None, metavar="FRACTION",
                    help="with --output-fps: drop frames that copy the frame before them and interpolate across the gap; a frame is a copy when no "
                         "cell's mean absolute luma difference exceeds FRACTION of full scale (0: bit-identical luma only; no default is claimed)")
@@ -113,6 +118,15 @@ def _run(args) -> int:
         for given, name in ((args.dedup is not None, "--dedup"), (args.dedup_max_run is not None, "--dedup-max-run")):
             if given:
                 raise ValueError(f"{name} needs --output-fps: dropped frames are replaced on the resampler's time grid")
+        if args.shutter is not None:
+            raise ValueError("--shutter needs --output-fps (the stream's own rate adds blur and keeps the rate): the exposure window is "
+                             "accumulated on the resampler's time grid")
+    if args.shutter is not None:
+        for given, name, why in ((args.resample == "blend", "--resample blend", "the window's weights already say how the midpoints are mixed"),
+                                 (args.dedup is not None, "--dedup", "a window over a gap of dropped frames is not defined"),
+                                 (args.evaluate, "--evaluate", "a held-out frame is an instantaneous sample")):
+            if given:
+                raise ValueError(f"--shutter excludes {name}: {why}")
     if args.static_tolerance is not None and args.static_guard is None:
         raise ValueError("--static-tolerance needs --static-guard R")
     if args.static_guard is not None and args.reference_quirks:
@@ -147,6 +161,8 @@ def _run(args) -> int:
             factor = 1
             if args.output_fps < head.rate:
                 raise ValueError(f"--output-fps {args.output_fps} lies below the stream's {head.rate} fps: frames are interpolated, never dropped")
+            if args.shutter is not None:      # what the shutter definition refuses is said before a device is asked for
+                FrameInterpolator.shutter_plan(0, head.rate, args.output_fps, args.resample_depth, args.shutter)
         elif args.factor is not None:
             factor = args.factor
         else:
@@ -167,7 +183,7 @@ def _run(args) -> int:
                                yuv_standard=args.yuv_standard, yuv_full_range=args.full_range, scale=args.scale, size=args.size,
                                scene_threshold=args.scene_threshold, copy_out=False,
                                **(dict(rate_in=head.rate, rate_out=args.output_fps, resample_depth=args.resample_depth,
-                                       resample_method=args.resample) if resample else {}),
+                                       resample_method=args.resample, shutter=args.shutter) if resample else {}),
                                **(dict(dedup_threshold=args.dedup, dedup_max_run=3 if args.dedup_max_run is None else args.dedup_max_run)
                                   if args.dedup is not None else {}),
                                **(dict(static_guard=args.static_guard, static_tolerance=args.static_tolerance or 0.0)
@@ -188,6 +204,7 @@ def _run(args) -> int:
             print(f"{reader.frames_read} frames in, {writer.frames_written} frames out at {out_head.fps_num}:{out_head.fps_den} fps "
                   f"({out_head.width} x {out_head.height}, {head.pixel_format}, "
                   + (f"{args.resample} at depth {args.resample_depth})" if resample else f"factor {factor})")
+                  + (f", shutter {fi.shutter} degrees" if args.shutter is not None else "")
                   + (f", {len(fi.duplicates)} duplicate frames dropped" if args.dedup is not None else "")
                   + (f", static guard held {100.0 * sum(fi.static_share) / max(len(fi.static_share), 1):.2f} % of the predictions' pixels on average"
                      if args.static_guard is not None else "")

@@ -66,6 +66,8 @@ _PROTOTYPES = {
     "emavfi_hold_frames_u8": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p, c_int, c_size_t, c_void_p]),
     "emavfi_resample_frames": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int,
                                        c_size_t, c_int, c_int, c_int, c_void_p]),
+    "emavfi_accumulate_frames": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int,
+                                         c_size_t, c_int, c_int, c_int, c_void_p]),
     "emavfi_frame_diff_cells": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 8 + [c_void_p, c_void_p]),
     "emavfi_duplicate_flags": (c_int, [c_void_p, c_size_t, c_int, ctypes.c_uint, c_void_p, c_void_p, c_void_p]),
     "emavfi_static_guard_frames": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p] + [c_int] * 8
@@ -1135,6 +1137,55 @@ def resample_frames(dst, srcs, nodes, table, flags=None, sample_bytes=1, depth=8
                                             nodes.shape[0] if nodes is not None else 0, ctypes.cast(arr, c_void_p),
                                             flags.data_ptr() if flags is not None else None, flags.numel() if flags is not None else 0,
                                             fb, int(sample_bytes), int(depth), int(shift), _stream()), "emavfi_resample_frames")
+    return dst
+
+
+# ---------------------------------------------------------------- shutter accumulation (include/emavfi.h, "SHUTTER DEFINITION")
+ACCUMULATE_MAX_TAPS = 33        # EMAVFI_ACCUMULATE_MAX_TAPS: the nodes 0 .. G of the deepest tree
+ACCUMULATE_LAUNCH_CAP = 8       # EMAVFI_ACCUMULATE_LAUNCH_CAP: table entries per launch
+ACCUMULATE_MAX_SUM = 65535      # the largest sum of an entry's weights
+
+
+class AccumulateEntry(ctypes.Structure):
+    """emavfi_accumulate_entry"""
+    _fields_ = [("n", ctypes.c_uint), ("f", ctypes.c_uint), ("h", ctypes.c_uint), ("tap", ctypes.c_uint * ACCUMULATE_MAX_TAPS),
+                ("w", ctypes.c_uint * ACCUMULATE_MAX_TAPS)]
+
+
+def accumulate_frames(dst, srcs, nodes, table, flags=None, sample_bytes=1, depth=8, shift=0):
+    """Every frame of `dst` the weighted integer mean of frames of two pools, one table entry per output (the shutter definition of
+    include/emavfi.h).  `dst`, `srcs`, `nodes`, `flags` and the sample format as for resample_frames.  `table`: n_out tuples
+    (taps, weights, f, h) - taps: 1..33 frame indices in `srcs`, or RESAMPLE_NODES + an index in `nodes`; weights: as many positive
+    integers that sum to 65535 at the most; f: 0, or 1 + an index into `flags`; h: the `srcs` frame a flagged entry holds.  The table is
+    consumed before the call returns."""
+    import torch
+    pools = [(dst, "accumulate_frames(dst)"), (srcs, "accumulate_frames(srcs)")] + ([(nodes, "accumulate_frames(nodes)")] if nodes is not None else [])
+    for t, what in pools:
+        _pinned_or_cuda(t, what)
+        if t.dtype != torch.uint8 or t.dim() < 2 or t.numel() == 0 or not t[0].is_contiguous() or tuple(t.shape[1:]) != tuple(dst.shape[1:]):
+            raise ValueError(f"{what}: a non-empty uint8 [frames, ...] tensor with dense frames of dst's frame shape expected")
+    table = list(table)
+    if len(table) != dst.shape[0]:
+        raise ValueError(f"accumulate_frames: {len(table)} table entries for {dst.shape[0]} output frames")
+    if flags is not None and not (flags.is_cuda and flags.dtype == torch.int32 and flags.dim() == 1 and flags.is_contiguous()):
+        raise ValueError("accumulate_frames: flags must be a contiguous int32 [n] device tensor")
+    arr = (AccumulateEntry * len(table))()
+    for k, (taps, weights, f, h) in enumerate(table):
+        if len(taps) != len(weights) or len(taps) > ACCUMULATE_MAX_TAPS:
+            raise ValueError(f"accumulate_frames: table[{k}] has {len(taps)} taps and {len(weights)} weights (as many of each, "
+                             f"{ACCUMULATE_MAX_TAPS} at the most)")
+        arr[k].n, arr[k].f, arr[k].h = len(taps), int(f), int(h)
+        for i, (t, w) in enumerate(zip(taps, weights)):
+            arr[k].tap[i], arr[k].w[i] = int(t), int(w)
+    fb = dst[0].numel()
+    stride = lambda t: t.stride(0) if t.shape[0] > 1 else fb     # a dimension of size 1 has no meaningful stride
+    dev = next((t.device for t, _ in pools if t.is_cuda), None) or (flags.device if flags is not None else torch.device("cuda"))
+    with torch.cuda.device(dev):
+        check(load().emavfi_accumulate_frames(dst.data_ptr(), stride(dst), len(table), srcs.data_ptr(), stride(srcs), srcs.shape[0],
+                                              nodes.data_ptr() if nodes is not None else None, stride(nodes) if nodes is not None else 0,
+                                              nodes.shape[0] if nodes is not None else 0, ctypes.cast(arr, c_void_p),
+                                              flags.data_ptr() if flags is not None else None, flags.numel() if flags is not None else 0,
+                                              fb, int(sample_bytes), int(depth), int(shift), _stream()), "emavfi_accumulate_frames")
     return dst
 
 

@@ -87,6 +87,12 @@ batch's output frames - source frames included - into the buffer that leaves for
 ``scene_threshold`` is set.  ``run_chunked`` and ``run(frames, rank, world)`` work as before on the global time grid.  Needs
 ``reference_quirks=False`` (the constructor's default is the reference's behaviour, which this is not), ``frame_interval=1``, the default
 ``interpolation_factor`` and ``zero_copy=False``; all pixel formats work, ``scale`` / ``size`` on the byte formats; ``evaluate()`` is unaffected.
+``shutter`` (opt-in, mode "resample" only; degrees in (0, 360]: 180, 172.8, "1080/7") adds motion blur: every output frame is the weighted
+integer mean of the tree nodes inside its exposure window of ``shutter / 360`` of an OUTPUT frame period (the shutter definition of
+include/emavfi.h; ``shutter_taps``, ``shutter_plan``), summed on the device by ``emavfi_accumulate_frames`` in place of the selection above,
+so that only the accumulated frames cross PCIe.  ``rate_out`` must be an integer multiple of ``rate_in`` (1 included: the frame rate stays
+and blur is added) - windows then never leave their pair, and chunks, ranks, scene holds and the static guard work as without it.  The
+output on the last frame of the clip is that frame.  Excludes ``resample_method="blend"``, ``dedup_threshold`` and ``evaluate()``.
 ``dedup_threshold`` (opt-in, mode "resample" only; a fraction in [0, 1], 0 = bit-identical luma) drops frames that copy the frame before them -
 24 fps film in a 30 fps stream, animation on twos, screen captures - and interpolates across the gap instead of yielding the copy again (the
 duplicate-frame definition of include/emavfi.h: per cell of the 32 x 32 scene grid the mean absolute luma difference, the MAXIMUM over the
@@ -136,6 +142,7 @@ from __future__ import annotations
 
 import os
 from fractions import Fraction
+from math import gcd
 from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Tuple
 
 import numpy as np
@@ -229,7 +236,23 @@ class DedupPlan(NamedTuple):
         return sum(len(lv) for _, levels in self.gaps.values() for lv in levels)
 
 
+class ShutterPlan(NamedTuple):
+    """What ``FrameInterpolator.shutter_plan`` returns.  ``outputs``: ``(k, s, taps)`` per output frame in emission order - output ``k``
+    lies in the pair ``(s, s + 1)`` and is the weighted mean of its ``taps`` ``((j, w), ...)``, nodes of that pair's tree (node 0 is source
+    ``s``, node ``G`` source ``s + 1``); the output on the last frame of the clip is that frame alone, ``((0, 1),)``.  ``pairs``:
+    ``{s: levels}`` as in ``ResamplePlan`` - one forward per listed node.  ``Q``: ``rate_out / rate_in``; ``G`` = 2^depth."""
+    outputs: List[Tuple[int, int, Tuple[Tuple[int, int], ...]]]
+    pairs: Dict[int, List[List[int]]]
+    Q: int
+    G: int
+
+    @property
+    def forwards(self) -> int:
+        return sum(len(lv) for levels in self.pairs.values() for lv in levels)
+
+
 class FrameInterpolator:
+    shutter = None   # the shutter angle in degrees as a Fraction (include/emavfi.h, "SHUTTER DEFINITION"); None: instantaneous frames
     dedup = None   # the duplicate threshold in score units (lib.dedup_threshold_units); None: duplicates are not looked for
     dedup_max_run, dedup_span = 3, 64
     static_guard = None   # the radius of the static-region guard (include/emavfi.h, "STATIC REGION DEFINITION"); None: off
@@ -250,7 +273,9 @@ class FrameInterpolator:
                  dedup_threshold: Optional[float] = None, dedup_max_run: int = 3, dedup_span: int = 64,
                  static_guard: Optional[int] = None, static_tolerance: float = 0.0, ensemble: Optional[str] = None,
                  border: Optional[int] = None, border_mode: str = "replicate",
-                 agreement: Optional[float] = None, agreement_radius: Optional[int] = None):
+                 agreement: Optional[float] = None, agreement_radius: Optional[int] = None, shutter=None):
+        if shutter is not None and mode != "resample":
+            raise ValueError("shutter belongs to mode='resample': the exposure window is accumulated over the nodes of its time grid")
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
             raise ValueError("interpolation_factor >= 0, frame_interval >= 1, batch_pairs >= 1 required")
         if mode not in ("reference", "recursive", "resample"):
@@ -270,6 +295,17 @@ class FrameInterpolator:
                 raise ValueError("mode='resample' needs rate_in and rate_out")
             self._ratio = self.resample_ratio(rate_in, rate_out)
             self.resample_depth, self.resample_method = self._resample_args(resample_depth, resample_method)
+            if shutter is not None:
+                P, Q = self._ratio
+                if P != 1:
+                    raise ValueError(f"shutter with rate_in / rate_out = {P}/{Q}: exposure windows would cross pair boundaries unless rate_out "
+                                     "is an integer multiple of rate_in (P > 1 is not supported)")
+                if resample_method == "blend":
+                    raise ValueError("shutter with resample_method='blend': the window's weights already say how the nodes are mixed")
+                if dedup_threshold is not None:
+                    raise ValueError("shutter with dedup_threshold: a window over a gap of dropped frames is not defined")
+                self._taps = [self.shutter_taps(Q, self.resample_depth, shutter, r) for r in range(Q)]     # refuses what the rule refuses
+                self.shutter = self._exposure(shutter)[2]
         elif rate_in is not None or rate_out is not None:
             raise ValueError("rate_in / rate_out belong to mode='resample'")
         if mode != "resample" and (dedup_threshold is not None or dedup_max_run != 3 or dedup_span != 64):
@@ -505,6 +541,65 @@ class FrameInterpolator:
         if rank == world - 1 and ((n_frames - 1) * Q) % P == 0:
             outs.append((((n_frames - 1) * Q) // P, n_frames - 1, 0, 0, 0))
         return ResamplePlan(outs, pairs, P, Q, 1 << depth)
+
+    # ---- motion blur (include/emavfi.h, "SHUTTER DEFINITION"): the taps of an exposure window, pure host logic over integers
+    @staticmethod
+    def _exposure(shutter):
+        """(n, d, degrees): e = shutter / 360 = n / d in lowest terms.  An int, a Fraction, a string Fraction accepts ("172.8", "1080/7") or
+        a float, taken at its shortest decimal form."""
+        try:
+            if isinstance(shutter, bool):
+                raise TypeError
+            deg = Fraction(str(shutter)) if isinstance(shutter, float) else Fraction(shutter)
+        except (TypeError, ValueError, ZeroDivisionError):
+            raise ValueError(f"shutter must be an angle in degrees (180, 172.8, '1080/7', Fraction(1080, 7)), got {shutter!r}") from None
+        if not 0 < deg <= 360:
+            raise ValueError(f"shutter {deg} lies outside (0, 360] degrees")
+        return (deg / 360).numerator, (deg / 360).denominator, deg
+
+    @staticmethod
+    def shutter_taps(Q: int, depth: int, shutter, r: int):
+        """``[(j, w)]``: the nodes of a pair's tree of depth ``depth`` inside the exposure window of its output ``r`` (0 .. Q - 1) at the
+        rate ratio ``Q`` and the angle ``shutter``, with their reduced integer weights, ascending in ``j``.  ValueError where the definition
+        refuses: an exposure shorter than one node spacing, weights that sum to more than 65535."""
+        n, d, deg = FrameInterpolator._exposure(shutter)
+        depth, _ = FrameInterpolator._resample_args(depth, "nearest")
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in (Q, r)) or Q < 1 or not 0 <= r < Q:
+            raise ValueError(f"shutter_taps: integers Q >= 1 and 0 <= r < Q expected, got Q = {Q!r}, r = {r!r}")
+        G = 1 << depth
+        if G * n < Q * d:
+            raise ValueError(f"shutter {deg} at rate ratio {Q}: the exposure of {Fraction(n, d * Q)} of a source interval is shorter than one "
+                             f"node spacing 1/{G}; raise resample_depth")
+        lo, half = 2 * G * d * r, Q * d
+        hi = lo + 2 * G * n
+        taps = [(j, min(2 * j * half + half, hi) - max(2 * j * half - half, lo)) for j in range(G + 1)]
+        taps = [(j, w) for j, w in taps if w > 0]
+        g = 0
+        for _, w in taps:
+            g = gcd(g, w)
+        taps = [(j, w // g) for j, w in taps]
+        if sum(w for _, w in taps) > _lib.ACCUMULATE_MAX_SUM:
+            raise ValueError(f"shutter {deg} at rate ratio {Q} and depth {depth}: the weights sum to {sum(w for _, w in taps)}, above "
+                             f"{_lib.ACCUMULATE_MAX_SUM}; use an angle with a smaller denominator")
+        return taps
+
+    @staticmethod
+    def shutter_plan(n_frames: int, rate_in, rate_out, depth: int = 3, shutter=180, rank: int = 0, world: int = 1) -> ShutterPlan:
+        """What ``run(frames, rank, world)`` yields in mode "resample" under a shutter, symbolically and in order, and what it computes: a
+        ``ShutterPlan``.  Ranks share the pairs as in ``resample_plan``: windows never leave their pair.  Pure host logic (no device needed)."""
+        from .dist import shard_range
+        P, Q = FrameInterpolator.resample_ratio(rate_in, rate_out)
+        if P != 1:
+            raise ValueError(f"shutter_plan: rate_in / rate_out = {P}/{Q}: rate_out must be an integer multiple of rate_in (P > 1 is not supported)")
+        taps = [tuple(FrameInterpolator.shutter_taps(Q, depth, shutter, r)) for r in range(Q)]
+        if n_frames <= 0:
+            return ShutterPlan([], {}, Q, 1 << depth)
+        a, b = shard_range(n_frames - 1, rank, world)
+        outs = [(s * Q + r, s, taps[r]) for s in range(a, b) for r in range(Q)]
+        levels = FrameInterpolator.resample_needed({j for t in taps for j, _ in t}, depth)
+        if rank == world - 1:
+            outs.append(((n_frames - 1) * Q, n_frames - 1, ((0, 1),)))
+        return ShutterPlan(outs, {s: levels for s in range(a, b)}, Q, 1 << depth)
 
     # ---- duplicate frames (include/emavfi.h, "DUPLICATE FRAME DEFINITION", Schedule): pure host logic over integers
     @staticmethod
@@ -1171,19 +1266,31 @@ class FrameInterpolator:
 
     def _resample_batch(self, chunk, outs_of, ia, ib):
         """One batch's host-side schedule: (levels, table, n_nodes, depths).  `chunk`: its pairs (s, s + m) of kept frames, local frame indices
-        (m = 1 unless duplicates were dropped between them); `outs_of[s]`: the outputs (R, j0, j1, w) of pair s in order; ia / ib: the staged
-        rows of each pair's frames.  A pair's tree has depth D + ceil(log2 m); the levels run to the deepest tree of the batch.  Node frames
+        (m = 1 unless duplicates were dropped between them); `outs_of[s]`: the outputs (R, j0, j1, w) - under a shutter (r, taps) - of pair s
+        in order; ia / ib: the staged rows of each pair's frames.  A pair's tree has depth D + ceil(log2 m); the levels run to the deepest tree of the batch.  Node frames
         are numbered level by level, pair by pair - the order the forwards produce them in."""
         depths = [self.resample_depth + (s2 - s - 1).bit_length() for s, s2 in chunk]
-        needed = [self.resample_needed({j for _, j0, j1, _ in outs_of[s] for j in (j0, j1)}, depths[k]) for k, (s, _) in enumerate(chunk)]
+        needed = [self.resample_needed({j for o in outs_of[s] for j in self._out_nodes(o)}, depths[k]) for k, (s, _) in enumerate(chunk)]
         levels = [[(k, j) for k in range(len(chunk)) if l < depths[k] for j in needed[k][l]] for l in range(max(depths))]
         index = {item: i for i, item in enumerate(item for lv in levels for item in lv)}
         table = []
         for k, (s, _) in enumerate(chunk):
             ref = lambda j: ia[k] if j == 0 else ib[k] if j == 1 << depths[k] else _lib.RESAMPLE_NODES | index[(k, j)]
+            if self.shutter is not None:      # (taps, weights, f, h) of accumulate_frames: every output of a flagged pair is held, r = 0 too
+                table += [([ref(j) for j, _ in taps], [w for _, w in taps], k + 1 if self.scene is not None else 0, ia[k])
+                          for _, taps in outs_of[s]]
+                continue
             for r, j0, j1, w in outs_of[s]:
                 table.append((ref(j0), ref(j1), w, k + 1 if (self.scene is not None and r > 0) else 0, ia[k]))
         return levels, table, len(index), depths
+
+    def _out_nodes(self, out):
+        """the nodes an output of ``outs_of`` uses: (r, j0, j1, w), or under a shutter (r, taps)"""
+        return [j for j, _ in out[1]] if self.shutter is not None else out[1:3]
+
+    def _entry_nodes(self, entry):
+        """the node frames a table entry names, in order: an entry of resample_frames, or under a shutter of accumulate_frames"""
+        return [t & ~_lib.RESAMPLE_NODES for t in (entry[0] if self.shutter is not None else entry[:2]) if t & _lib.RESAMPLE_NODES]
 
     def _dedup_image(self, buf):
         """the staged frames `buf` as the duplicate measure reads them, at source size: interleaved colour, or the Y plane as a 1-channel image
@@ -1256,8 +1363,11 @@ class FrameInterpolator:
             keep = set(kept)
             self.duplicates = [(base + t, scores[t - a - 1]) for t in range(a + 1, b + 1) if t not in keep]
         gaps = list(zip(kept, kept[1:]))          # without duplicates: the pairs (s, s + 1), and resample_gap is resample_span
-        outs_of = {t0: [(k * P - (base + t0) * Q, j0, j1, w) for k, _, _, j0, j1, w in
-                        self.resample_gap(P, Q, D, self.resample_method, base + t0, base + t1)] for t0, t1 in gaps}
+        if self.shutter is not None:              # P = 1: every pair has the outputs r = 0 .. Q - 1, each (r, the taps of its window)
+            outs_of = {t0: list(enumerate(self._taps)) for t0, _ in gaps}
+        else:
+            outs_of = {t0: [(k * P - (base + t0) * Q, j0, j1, w) for k, _, _, j0, j1, w in
+                            self.resample_gap(P, Q, D, self.resample_method, base + t0, base + t1)] for t0, t1 in gaps}
         bp = self.batch_pairs
         chunks = [gaps[i:i + bp] for i in range(0, len(gaps), bp)]
         fmt = _lib.resample_sample_format(self.pixel_format)
@@ -1265,7 +1375,7 @@ class FrameInterpolator:
         if chunks:
             # the node and emission buffers of a slot hold the largest batch of this run
             sizes = [(sum(len(outs_of[s]) for s, _ in c), sum(len(lv) for s, s2 in c for lv in self.resample_needed(
-                {j for _, j0, j1, _ in outs_of[s] for j in (j0, j1)}, D + (s2 - s - 1).bit_length()))) for c in chunks]
+                {j for o in outs_of[s] for j in self._out_nodes(o)}, D + (s2 - s - 1).bit_length()))) for c in chunks]
             n_emit, n_node = max(o for o, _ in sizes), max(1, max(n for _, n in sizes))
             for slot in self._slots:
                 fs = tuple(slot["d_src"].shape[1:])
@@ -1332,11 +1442,11 @@ class FrameInterpolator:
                     for i, k in enumerate(gap_of):
                         first.setdefault(k, i)
                     # an entry's last field is its gap's first staged row, ia[k]: distinct per gap
-                    first_node = [first[ia.index(e[4])] for e in table if (e[0] | e[1]) & _lib.RESAMPLE_NODES]
+                    first_node = [first[ia.index(e[-1])] for e in table if self._entry_nodes(e)]
                 # the source frames as emitted: the staged bytes, or the bytes the preprocess kernel resized them to
-                _lib.resample_frames(slot["d_emit"][:len(table)], rs if rs is not None else slot["d_in"][:nup],
-                                     slot["d_node"][:off] if off else None, table,
-                                     flags=slot["fs"][0] if self.scene is not None else None, sample_bytes=fmt[0], depth=fmt[1], shift=fmt[2])
+                assemble = _lib.accumulate_frames if self.shutter is not None else _lib.resample_frames
+                assemble(slot["d_emit"][:len(table)], rs if rs is not None else slot["d_in"][:nup], slot["d_node"][:off] if off else None, table,
+                         flags=slot["fs"][0] if self.scene is not None else None, sample_bytes=fmt[0], depth=fmt[1], shift=fmt[2])
                 slot["h_emit"][:len(table)].copy_(slot["d_emit"][:len(table)], non_blocking=True)     # HBM -> pinned (SDMA)
                 if self.scene is not None:
                     slot["h_fs"].copy_(slot["fs"], non_blocking=True)
@@ -1346,7 +1456,7 @@ class FrameInterpolator:
             if prev is not None:
                 yield from drain(*prev)
             # per emitted frame made of node frames: the first node frame its entry names
-            own_node = [(e[0] if e[0] & _lib.RESAMPLE_NODES else e[1]) & ~_lib.RESAMPLE_NODES for e in table if (e[0] | e[1]) & _lib.RESAMPLE_NODES]
+            own_node = [self._entry_nodes(e)[0] for e in table if self._entry_nodes(e)]
             prev = (slot, chunk, len(table), first_node, own_node)
         if prev is not None:
             yield from drain(*prev)
@@ -1432,6 +1542,8 @@ class FrameInterpolator:
         the ranks' ``targets`` concatenated in rank order are the single-process result."""
         if self._depth:
             raise ValueError(f"evaluate() with pixel_format={self.pixel_format!r}: the metric kernel reads bytes (16-bit frames are not scored)")
+        if self.shutter is not None:
+            raise ValueError("evaluate() with a shutter: a held-out frame is an instantaneous sample, an accumulated one is not comparable to it")
         if not (hasattr(frames, "__len__") and hasattr(frames, "__getitem__")):
             frames = list(frames)
         plan = self.evaluation_plan(len(frames), every, rank, world)
