@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_accumulate_frames added (motion blur from a shutter angle: every output frame the weighted integer mean of the node frames inside its exposure window, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_agreement_guard_f32 added (where the two time directions of the ensemble disagree the plain blend of the source frames is emitted, decided on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_downscale_f32, emavfi_upsample_flow_f32, emavfi_forward_flow, emavfi_forward_given_flow (and their two launch lists) added (the flow estimated on frames reduced by 2, 4 or 8 for motion beyond seven pixels, the forward split at its flow; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_accumulate_frames added (motion blur from a shutter angle: every output frame the weighted integer mean of the node frames inside its exposure window, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_agreement_guard_f32 added (where the two time directions of the ensemble disagree the plain blend of the source frames is emitted, decided on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -834,6 +834,81 @@ int emavfi_ensemble_mean_f32(const float *const *members, const int *flips, int 
 #define EMAVFI_BORDER_MAX 64
 int emavfi_border_pad_f32(const float *src, float *dst, size_t planes, int H, int W, int N, int mode, void *stream);
 int emavfi_border_crop_f32(const float *src, float *dst, size_t planes, int H, int W, int N, void *stream);
+
+/* Coarse flow.  The forward's flow comes from seven stride-1 3 x 3 convolutions between the frames and the flow field (feat_ext_conv1, three
+ * feat_ext_blocks, motion_estimation.0/.1/.2; ema_vfi.py:73-76, :89-92) plus the context vector, a global mean that carries no position: a
+ * flow value can depend on nothing farther than 7 pixels away.  At 720p and above ordinary motion is tens of pixels per frame.  The
+ * reference's answer is --scale 0.5, which halves the OUTPUT as well.  The entries here estimate the flow on frames reduced by s and run
+ * everything else at full size: the "flow scale" of flow-based interpolators.  The reference has no such step; this is an addition, off
+ * unless asked for, and no quality claim is made (the reference ships no weights).  The composition lives in the Python layer
+ * (EMA_VFI.flow_scale); the entries are the device work a C integrator needs.
+ *
+ * COARSE FLOW DEFINITION (the one place).  This is the project's own definition: it claims agreement with no outside tool.
+ *   s is 2, 4 or 8;  Hs = ceil(H / s), Ws = ceil(W / s).  All arithmetic is IEEE fp32 without contraction, in exactly the stated order.
+ *   F_s(a, b), for two normalised fp32 batches [B][3][H][W], in four steps:
+ *   1. Downscale.  a_s = down_s(a), b_s = down_s(b), each [B][3][Hs][Ws].  Block (i, j) has s x s leaves
+ *        L(r, c) = x[min(s i + r, H - 1)][min(s j + c, W - 1)]
+ *      - the clamp is applied once, at the leaves: an edge block still has s^2 of them -, reduced by the balanced quadtree
+ *        T_1 = L,   T_2m(r, c) = ((T_m(2r, 2c) + T_m(2r, 2c+1)) + (T_m(2r+1, 2c) + T_m(2r+1, 2c+1))) * 0.25f,
+ *      and the result is T_s(0, 0).  The multiplications are exact (up to underflow): host, oracle and device agree bit for bit.
+ *   2. Coarse flow.  flow_s = the flow of the plain forward of (a_s, b_s) at Hs x Ws: bit for bit what taps[2] of emavfi_forward holds for
+ *      those arguments, in the same mode and from the same packed blob (the weights do not depend on the resolution).
+ *   3. Upsample.  flow_up[b][c][y][x] = (float)s * v, v being the bilinear sample at half-pixel centres.  Per axis, with destination index
+ *      d and coarse length n:  num = 2 d + 1 - s (an integer, possibly negative);  i0 = floor(num / (2 s));
+ *      w = (float)(num - 2 s i0) / (float)(2 s) (dyadic, exact);  j0 = clamp(i0, 0, n - 1), j1 = clamp(i0 + 1, 0, n - 1).  Then
+ *        top = (1 - wx) p[y0][x0] + wx p[y0][x1],  bot the same on row y1,  v = (1 - wy) top + wy bot.
+ *      Both flow channels are scaled by s.  The block geometry is s even where H or W is not a multiple of s.
+ *   4. Fine forward.  F_s(a, b) = the plain forward of (a, b) with flow_up in place of motion_estimation's output: feature extraction,
+ *      warp, attention blocks and reconstruction run exactly as in emavfi_forward; context encoding and motion estimation, which have no
+ *      consumer but the flow, are not launched.
+ *   Consequences:
+ *     - A forward given its own plain flow is the plain forward, bit for bit.
+ *     - A zero flow makes warped == frame2.
+ *     - down_s of a constant is that constant (x + x and 2x + 2x are exact, as is * 0.25f).
+ *     - up of a constant flow c is exactly s c wherever the two products with the dyadic weights are exact (c of at most 20 significant
+ *       bits: the weights have at most 4), and in particular at every position whose weights are 0 and 1.
+ *     - The first s / 2 rows and columns of flow_up have i0 = -1: both taps clamp to coarse row / column 0.
+ *   Ensemble members, border padding and the agreement halves (the definitions above) receive F_s wherever they say F: the padded frame is
+ *   the frame that is reduced.
+ *
+ * emavfi_downscale_f32: dst [planes][ceil(H / s)][ceil(W / s)] = down_s of src [planes][H][W].
+ * emavfi_upsample_flow_f32: flow [planes][H][W] = step 3 of flow_s [planes][Hs][Ws]; Hs and Ws must be the ceilings.
+ * Both: dense fp32 tensors, device pointers or pinned (device-mapped) host memory; H, W (and Hs, Ws) in 1..16384; planes * H * W is
+ *   addressed with 64 bits (indices inside a plane are 32-bit).  Nothing is allocated, nothing synchronises, there is no workspace, there
+ *   are no atomics, all work goes on `stream`; every word of the destination is written and nothing else is.
+ * EMAVFI_E_ARG (never an abort), the message naming the argument: a null pointer; s outside {2, 4, 8}; planes of 0; a dimension outside
+ *   1..16384; Hs or Ws that is not the ceiling; a pointer that is not 4-byte aligned; size arithmetic that overflows size_t; the
+ *   destination overlapping the source.
+ * Access width.  Down: 16-byte loads of the leaves when src is 16-byte aligned and W % 4 == 0 (a unit of 4 results for s = 2 and 4, of 1
+ *   for s = 8; a unit whose leaves reach past column W - 1 takes the scalar path), one 16-byte store per 4 results when dst is 16-byte
+ *   aligned and Ws % 4 == 0.  Up: one 16-byte store of 4 destination columns when flow is 16-byte aligned and W % 4 == 0; the coarse samples
+ *   are scalar loads.  Everything else takes a scalar path built from the same per-element functions (csrc/coarse_elem.h).
+ *
+ * emavfi_forward_flow: the launches of emavfi_forward up to and including the one that writes the flow (step 2), then a device-to-device
+ *   copy of it to flow_out [B][2][H][W] fp32 (16-byte aligned).  No attention block runs and no census is produced.  The workspace is
+ *   emavfi_workspace_bytes' for the same arguments, under THE WORKSPACE CONTRACT.
+ * emavfi_forward_given_flow: step 4.  The arguments of emavfi_forward_routed plus `flow` [B][2][H][W] fp32, 16-byte aligned, read in place
+ *   (it must stay unchanged until the call's work on `stream` is done and may not overlap out or the workspace).  taps[1] (ctx) and
+ *   taps[2] (flow) must be NULL, else EMAVFI_E_ARG: this forward computes neither; the other taps work.  stage_events[0] is recorded behind
+ *   the warp.  Same workspace size and contract; the census is that of the attention blocks, as for emavfi_forward_routed.
+ * emavfi_forward_flow_launches / emavfi_forward_given_flow_launches list the launches of the two, as emavfi_forward_launches does: the
+ *   first is the prefix of the plain list through the flow's launch, the second the plain (routed) list without the context_encoding and
+ *   motion_estimation launches; names, flops and bytes of the launches that remain are unchanged.
+ * The adaptive route (emavfi_forward_adaptive) has no given-flow form. */
+int emavfi_downscale_f32(const float *src, float *dst, size_t planes, int H, int W, int s, void *stream);
+int emavfi_upsample_flow_f32(const float *flow_s, float *flow, size_t planes, int Hs, int Ws, int H, int W, int s, void *stream);
+int emavfi_forward_flow(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes,
+                        const float *frame1, const float *frame2, float *flow_out,
+                        void *workspace, size_t workspace_bytes, int B, int H, int W, int dtype, void *stream);
+int emavfi_forward_given_flow(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes,
+                              const float *frame1, const float *frame2, const float *flow, float *out,
+                              void *workspace, size_t workspace_bytes,
+                              int B, int H, int W, int dtype, float *const *taps, void *const *stage_events, void *const *events, int n_events,
+                              unsigned gather_blocks, void *stream);
+int emavfi_forward_flow_launches(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype,
+                                 char *names, size_t names_bytes, double *flops, double *bytes, int capacity);
+int emavfi_forward_given_flow_launches(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, unsigned gather_blocks,
+                                       char *names, size_t names_bytes, double *flops, double *bytes, int capacity);
 
 /* Agreement guard.  Every other guard here decides from the SOURCE frames (cuts, duplicates, static regions, borders); nothing protects
  * against the model being wrong.  The forward estimates one flow and warps only frame2, and on large motion, occlusions and repetitive

@@ -10,6 +10,7 @@
 #include "static_elem.h"
 #include "ensemble_elem.h"
 #include "border_elem.h"
+#include "coarse_elem.h"
 #include "agreement_elem.h"
 #include "conv_first.inl"
 
@@ -803,6 +804,11 @@ BlobHeader expected_header(const Plan &P, int requested_dtype)
 // include/emavfi.h; null when only enumerating) and the hysteresis thresholds (emavfi_forward_adaptive)
 struct Routes { unsigned gather_mask = 0; bool adaptive = false; unsigned *state = nullptr; float enter = 0.0f, leave = 0.0f; };
 // all (wave, tap) groups of one one-launch pack: the census denominator (emavfi_forward_census, route_select)
+// Where one forward's flow comes from and where the forward ends (include/emavfi.h, "COARSE FLOW DEFINITION"): PLAIN computes it and goes
+// on - every entry older than the coarse flow; STOP ends behind the launch that writes it and copies it to `out` (emavfi_forward_flow);
+// GIVEN launches neither context encoding nor motion estimation and warps by the caller's `given`, read in place
+// (emavfi_forward_given_flow).  When only enumerating, both pointers are null and the kind alone decides.
+struct FlowPlan { enum Kind { PLAIN, STOP, GIVEN } kind = PLAIN; float *out = nullptr; const float *given = nullptr; };
 static unsigned long long pack3_wave_taps(int B, int H, int W) { return (unsigned long long)B * ((H + 15) / 16) * ((W + 15) / 16) * 4ull * 9ull; }
 // a forward in this mode has routed packs: every block runs the one-launch pack of the deform_pack3 layout (16-bit modes at the
 // reference width; not EMAVFI_AMP16 / EMAVFI_F32X3, whose blocks run the fp32-family DCN)
@@ -816,7 +822,7 @@ static bool adaptive_applies(const Plan &P)
 
 int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes, const float *frame1,
                  const float *frame2, float *out, void *workspace, size_t workspace_bytes, int B, int H, int W, int dtype,
-                 float *const *taps, void *stream, Recorder &rec, const Routes &routes = Routes{})
+                 float *const *taps, void *stream, Recorder &rec, const Routes &routes = Routes{}, const FlowPlan &flowp = FlowPlan{})
 {
     Plan P;
     if (!build_plan(P, in_channels, mid_channels, num_blocks, dtype)) return fail(EMAVFI_E_UNSUPPORTED, "%s", P.why);
@@ -842,9 +848,14 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
     FwdBuffers f;
     carve_forward(P, ws, f, B, H, W);
     if (!rec.dry) {
-        if (!packed || !frame1 || !frame2 || !out || !workspace) return fail(EMAVFI_E_ARG, "forward: null pointer");
-        if (!aligned16(packed) || !aligned16(workspace) || !aligned16(frame1) || !aligned16(frame2) || !aligned16(out))
+        // (a forward that stops behind the flow has no frame: its output is flowp.out)
+        const void *const result = flowp.kind == FlowPlan::STOP ? (const void *)flowp.out : (const void *)out;
+        if (!packed || !frame1 || !frame2 || !result || !workspace || (flowp.kind == FlowPlan::GIVEN && !flowp.given))
+            return fail(EMAVFI_E_ARG, "forward: null pointer");
+        if (!aligned16(packed) || !aligned16(workspace) || !aligned16(frame1) || !aligned16(frame2) || !aligned16(result) || !aligned16(flowp.given))
             return fail(EMAVFI_E_ARG, "forward: pointers must be 16-byte aligned");
+        if (flowp.kind == FlowPlan::GIVEN && taps && (taps[1] || taps[2]))
+            return fail(EMAVFI_E_ARG, "forward_given_flow: taps[1] (ctx) and taps[2] (flow) must be NULL: a forward with a given flow computes neither");
         if (ws.used > workspace_bytes) return fail(EMAVFI_E_WORKSPACE, "forward: workspace needs %zu bytes, got %zu", ws.used, workspace_bytes);
         // every kernel reads the blob at offsets of THIS plan: a shorter buffer is another model's, another dtype's or a truncated one
         if (packed_bytes < P.total)
@@ -931,37 +942,46 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
     if (!rec.dry && taps && taps[0])
         EMAVFI_TRY(P.x3 ? launch_cl_to_nchw_x3(f.fu0, taps[0], B, mid, H, W, P.fps, 0, s) : launch_cl_to_nchw(f.fu0, taps[0], B, mid, H, W, P.fps, 0, feat_dtype, s), "tap feat");
 
-    // --- context encoding (ema_vfi.py:120): two stride-2 convs, one conv, global mean, linear
-    if (const int rc = context_stage(P, packed, f.fu0, f, B, H, W, s, rec); rc != EMAVFI_OK) return rc;
-    if (!rec.dry && taps && taps[1])
-        if (hipMemcpyAsync(taps[1], f.ctx, (size_t)B * mid * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return fail(EMAVFI_E_LAUNCH, "tap ctx copy failed");
+    // (a given flow replaces everything between `feat` and the warp: context encoding and motion estimation have no other consumer)
+    if (flowp.kind != FlowPlan::GIVEN) {
+        // --- context encoding (ema_vfi.py:120): two stride-2 convs, one conv, global mean, linear
+        if (const int rc = context_stage(P, packed, f.fu0, f, B, H, W, s, rec); rc != EMAVFI_OK) return rc;
+        if (!rec.dry && taps && taps[1])
+            if (hipMemcpyAsync(taps[1], f.ctx, (size_t)B * mid * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+                return fail(EMAVFI_E_LAUNCH, "tap ctx copy failed");
 
-    // --- motion estimation (ema_vfi.py:124-126); the broadcast-context concat is a per-border-class bias
-    conv_work(P, P.m0, B, H, W, e, fl, by);
-    EMAVFI_STEP(rec, conv_name(P, P.m0) + " motion_estimation.0(ctx folded)", fl, by,
-                run_conv(P, P.m0, packed, B, s, ConvCall{}.from(f.fu0, P.fps, H, W).bias_rows(f.table).to(f.fA, P.p_mid, P.p_mid).act(EPI_RELU).other16(feat16)));
-    // motion_estimation.1 + .2 in one launch (conv_ring.inl, HEAD): .1's rows never leave the LDS.  EMAVFI_CONV_HEAD=0: two launches
-    if (can_fuse_head(P.m1, P.m2, sw)) {
-        double fl2, by2;
-        conv_work(P, P.m1, B, H, W, e, fl, by);
-        conv_work(P, P.m2, B, H, W, 4.0, fl2, by2);
-        // bytes: .1's input and weights, .2's weights and output (the intermediate tensor is neither written nor read)
-        const double mid_bytes = (double)B * H * W * mid * e;
-        EMAVFI_STEP(rec, "conv3x3+head<" + std::string(dtype_name(P.dtype)) + ",64->64->" + std::to_string(P.m2.cout) + "> motion_estimation.1+.2(flow)",
-                    fl + fl2, by + by2 - 2 * mid_bytes,
-                    run_conv(P, P.m1, packed, B, s, ConvCall{}.from(f.fA, P.p_mid, H, W).act(EPI_RELU).then_head(P.m2).to_planes(f.flow, 2)));
-    } else {
-        conv_work(P, P.m1, B, H, W, e, fl, by);
-        EMAVFI_STEP(rec, conv_name(P, P.m1) + " motion_estimation.1", fl, by,
-                    run_conv(P, P.m1, packed, B, s, ConvCall{}.from(f.fA, P.p_mid, H, W).to(f.fB, P.p_mid, P.p_mid).act(EPI_RELU)));
-        conv_work(P, P.m2, B, H, W, 4.0, fl, by);
-        EMAVFI_STEP(rec, conv_name(P, P.m2) + " motion_estimation.2(flow)", fl, by,
-                    run_conv(P, P.m2, packed, B, s, ConvCall{}.from(f.fB, P.p_mid, H, W).act(EPI_PLANAR).to_planes(f.flow, 2)));
+        // --- motion estimation (ema_vfi.py:124-126); the broadcast-context concat is a per-border-class bias
+        conv_work(P, P.m0, B, H, W, e, fl, by);
+        EMAVFI_STEP(rec, conv_name(P, P.m0) + " motion_estimation.0(ctx folded)", fl, by,
+                    run_conv(P, P.m0, packed, B, s, ConvCall{}.from(f.fu0, P.fps, H, W).bias_rows(f.table).to(f.fA, P.p_mid, P.p_mid).act(EPI_RELU).other16(feat16)));
+        // motion_estimation.1 + .2 in one launch (conv_ring.inl, HEAD): .1's rows never leave the LDS.  EMAVFI_CONV_HEAD=0: two launches
+        if (can_fuse_head(P.m1, P.m2, sw)) {
+            double fl2, by2;
+            conv_work(P, P.m1, B, H, W, e, fl, by);
+            conv_work(P, P.m2, B, H, W, 4.0, fl2, by2);
+            // bytes: .1's input and weights, .2's weights and output (the intermediate tensor is neither written nor read)
+            const double mid_bytes = (double)B * H * W * mid * e;
+            EMAVFI_STEP(rec, "conv3x3+head<" + std::string(dtype_name(P.dtype)) + ",64->64->" + std::to_string(P.m2.cout) + "> motion_estimation.1+.2(flow)",
+                        fl + fl2, by + by2 - 2 * mid_bytes,
+                        run_conv(P, P.m1, packed, B, s, ConvCall{}.from(f.fA, P.p_mid, H, W).act(EPI_RELU).then_head(P.m2).to_planes(f.flow, 2)));
+        } else {
+            conv_work(P, P.m1, B, H, W, e, fl, by);
+            EMAVFI_STEP(rec, conv_name(P, P.m1) + " motion_estimation.1", fl, by,
+                        run_conv(P, P.m1, packed, B, s, ConvCall{}.from(f.fA, P.p_mid, H, W).to(f.fB, P.p_mid, P.p_mid).act(EPI_RELU)));
+            conv_work(P, P.m2, B, H, W, 4.0, fl, by);
+            EMAVFI_STEP(rec, conv_name(P, P.m2) + " motion_estimation.2(flow)", fl, by,
+                        run_conv(P, P.m2, packed, B, s, ConvCall{}.from(f.fB, P.p_mid, H, W).act(EPI_PLANAR).to_planes(f.flow, 2)));
+        }
+        if (!rec.dry && taps && taps[2])
+            if (hipMemcpyAsync(taps[2], f.flow, npx * 2 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+                return fail(EMAVFI_E_LAUNCH, "tap flow copy failed");
     }
-    if (!rec.dry && taps && taps[2])
-        if (hipMemcpyAsync(taps[2], f.flow, npx * 2 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return fail(EMAVFI_E_LAUNCH, "tap flow copy failed");
+    if (flowp.kind == FlowPlan::STOP) {
+        if (!rec.dry && hipMemcpyAsync(flowp.out, f.flow, npx * 2 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(EMAVFI_E_LAUNCH, "forward_flow: flow copy failed");
+        return EMAVFI_OK;
+    }
+    const float *const flow = flowp.kind == FlowPlan::GIVEN ? flowp.given : f.flow;
 
     void *x = f.fu0, *y = f.fu1;
     if (P.wide()) {
@@ -974,13 +994,13 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
         float *xF = f.fuF0, *yF = f.fuF1;
         // (round 5: the warp writes the fp32 values AND their fp16 rounding - was the conversion pass fusion_round_warped)
         if (P.x3) {
-            EMAVFI_STEP(rec, "warp_fused<f32>", 24.0 * px, px * (8.0 + 8.0 * C), launch_warp_fused(frame2, f.flow, xF, B, C, H, W, P.fpad, mid, EMAVFI_F32, s));
+            EMAVFI_STEP(rec, "warp_fused<f32>", 24.0 * px, px * (8.0 + 8.0 * C), launch_warp_fused(frame2, flow, xF, B, C, H, W, P.fpad, mid, EMAVFI_F32, s));
             EMAVFI_STEP(rec, "fusion_split_warped", 0, px * (P.fpad - mid) * 8.0, launch_convert_cl(xF, f.fu0, npx, P.fpad, 2 * P.fps, mid, P.fpad - mid, 0, s, P.fps));
             // (`feat`'s fp32 copy is already in xF: the last feature layer wrote it beside its f16 halves; nb == 0 has no such layer)
             if (P.nb == 0) EMAVFI_STEP(rec, "fusion_widen_feat", 0, px * mid * 8.0, launch_convert_cl(f.fu0, xF, npx, 2 * P.fps, P.fpad, 0, mid, 1, s, P.fps));
         } else {
             EMAVFI_STEP(rec, "warp_fused<f32>", 24.0 * px, px * (8.0 + 8.0 * C + 2.0 * C),
-                        launch_warp_fused(frame2, f.flow, xF, B, C, H, W, P.fpad, mid, EMAVFI_F32, s, f.fu0, P.fps));
+                        launch_warp_fused(frame2, flow, xF, B, C, H, W, P.fpad, mid, EMAVFI_F32, s, f.fu0, P.fps));
             EMAVFI_STEP(rec, "fusion_widen_feat", 0, px * mid * 6.0, launch_convert_cl(f.fu0, xF, npx, P.fps, P.fpad, 0, mid, 1, s));
         }
         if (!rec.dry && taps && taps[3])
@@ -1000,8 +1020,8 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
         // them up from there: contiguous 16-byte pixels instead of 6 useful bytes scattered into every 160-byte fusion pixel.
         const bool split_tail = P.nb > 0 && pack_fuses(P, 0) && P.fpad - mid == 16;
         EMAVFI_STEP(rec, std::string("warp_fused<") + dtype_name(dtype) + ">", 24.0 * px, px * (8.0 + 4.0 * C + C * e),
-                    split_tail ? launch_warp_fused(frame2, f.flow, f.in16, B, C, H, W, kTailPs, 0, feat_dtype, s)
-                               : launch_warp_fused(frame2, f.flow, f.fu0, B, C, H, W, P.fps, mid, feat_dtype, s));
+                    split_tail ? launch_warp_fused(frame2, flow, f.in16, B, C, H, W, kTailPs, 0, feat_dtype, s)
+                               : launch_warp_fused(frame2, flow, f.fu0, B, C, H, W, P.fps, mid, feat_dtype, s));
         if (!rec.dry && taps && taps[3])
             EMAVFI_TRY(split_tail ? launch_cl_to_nchw(f.in16, taps[3], B, C, H, W, kTailPs, 0, feat_dtype, s)
                                   : launch_cl_to_nchw(f.fu0, taps[3], B, C, H, W, P.fps, mid, feat_dtype, s), "tap warped");
@@ -1218,13 +1238,13 @@ int emavfi_forward_launches(int in_channels, int mid_channels, int num_blocks, i
 }
 
 static int list_launches(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, const Routes &routes,
-                         char *names, size_t names_bytes, double *flops, double *bytes, int capacity)
+                         char *names, size_t names_bytes, double *flops, double *bytes, int capacity, const FlowPlan &flowp = FlowPlan{})
 {
     std::vector<LaunchRec> recs;
     Recorder rec;
     rec.recs = &recs; rec.dry = true;
     const int rc = forward_impl(in_channels, mid_channels, num_blocks, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, B, H, W,
-                                dtype, nullptr, nullptr, rec, routes);
+                                dtype, nullptr, nullptr, rec, routes, flowp);
     if (rc != EMAVFI_OK) return rc;
     const int n = (int)recs.size();
     if (capacity <= 0) return n;
@@ -1258,6 +1278,51 @@ int emavfi_forward_launches_adaptive(int in_channels, int mid_channels, int num_
     Routes routes;
     routes.adaptive = true;
     return list_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, routes, names, names_bytes, flops, bytes, capacity);
+}
+
+// ---- coarse flow (include/emavfi.h, "COARSE FLOW DEFINITION"): the two halves of the forward, split at the flow
+int emavfi_forward_flow(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes, const float *frame1,
+                        const float *frame2, float *flow_out, void *workspace, size_t workspace_bytes, int B, int H, int W, int dtype, void *stream)
+{
+    Recorder rec;
+    FlowPlan flowp;
+    flowp.kind = FlowPlan::STOP; flowp.out = flow_out;
+    return forward_impl(in_channels, mid_channels, num_blocks, packed, packed_bytes, frame1, frame2, nullptr, workspace, workspace_bytes, B, H, W,
+                        dtype, nullptr, stream, rec, Routes{}, flowp);
+}
+
+int emavfi_forward_given_flow(int in_channels, int mid_channels, int num_blocks, const void *packed, size_t packed_bytes, const float *frame1,
+                              const float *frame2, const float *flow, float *out, void *workspace, size_t workspace_bytes, int B, int H, int W,
+                              int dtype, float *const *taps, void *const *stage_events, void *const *events, int n_events, unsigned gather_blocks,
+                              void *stream)
+{
+    Recorder rec;
+    rec.stage_events = stage_events;
+    if (const int rc = set_events(rec, events, n_events, "forward_given_flow"); rc != EMAVFI_OK) return rc;
+    Routes routes;
+    routes.gather_mask = gather_blocks;
+    FlowPlan flowp;
+    flowp.kind = FlowPlan::GIVEN; flowp.given = flow;
+    return forward_impl(in_channels, mid_channels, num_blocks, packed, packed_bytes, frame1, frame2, out, workspace, workspace_bytes, B, H, W,
+                        dtype, taps, stream, rec, routes, flowp);
+}
+
+int emavfi_forward_flow_launches(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype,
+                                 char *names, size_t names_bytes, double *flops, double *bytes, int capacity)
+{
+    FlowPlan flowp;
+    flowp.kind = FlowPlan::STOP;
+    return list_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, Routes{}, names, names_bytes, flops, bytes, capacity, flowp);
+}
+
+int emavfi_forward_given_flow_launches(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, unsigned gather_blocks,
+                                       char *names, size_t names_bytes, double *flops, double *bytes, int capacity)
+{
+    Routes routes;
+    routes.gather_mask = gather_blocks;
+    FlowPlan flowp;
+    flowp.kind = FlowPlan::GIVEN;
+    return list_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, routes, names, names_bytes, flops, bytes, capacity, flowp);
 }
 
 // ---- adaptive per-block route (include/emavfi.h): the states emavfi_route_state_init wrote, by address -> num_blocks.  The forward
@@ -1989,6 +2054,54 @@ int emavfi_border_crop_f32(const float *src, float *dst, size_t planes, int H, i
     if (const int rc = ensemble_pointer_check(what, "dst", -1, dst, picture); rc != EMAVFI_OK) return rc;
     if (const int rc = border_overlap_check(what, src, padded, dst, picture); rc != EMAVFI_OK) return rc;
     EMAVFI_TRY(launch_border_crop_f32(src, dst, planes, H, W, N, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+// ---- coarse flow, steps 1 and 3 (include/emavfi.h, "COARSE FLOW DEFINITION"): every check runs on the host; H, W are the FINE tensor's size
+static_assert(EMAVFI_RESIZE_MAX_DIM == COARSE_MAX_DIM, "header and coarse_elem.h disagree");
+
+// the bytes of the fine [planes][H][W] and of the coarse [planes][ceil(H / s)][ceil(W / s)] tensor, refused where s, a size or the arithmetic
+// is out of range; `given` (upsample) is the caller's {Hs, Ws}, which must be those ceilings
+static int coarse_shape_check(const char *what, size_t planes, int H, int W, int s, const int *given, size_t *fine_bytes, size_t *coarse_bytes)
+{
+    if (planes < 1) return fail(EMAVFI_E_ARG, "%s: planes must be >= 1", what);
+    if (!coarse_scale_ok(s)) return fail(EMAVFI_E_ARG, "%s: s = %d (s must be 2, 4 or 8)", what, s);
+    if (!coarse_dim_ok(H) || !coarse_dim_ok(W)) return fail(EMAVFI_E_ARG, "%s: H, W must lie in 1..16384 (got %d, %d)", what, H, W);
+    const int Hs = coarse_dim(H, s), Ws = coarse_dim(W, s);
+    if (given && (!coarse_dim_ok(given[0]) || !coarse_dim_ok(given[1])))
+        return fail(EMAVFI_E_ARG, "%s: Hs, Ws must lie in 1..16384 (got %d, %d)", what, given[0], given[1]);
+    if (given && (given[0] != Hs || given[1] != Ws))
+        return fail(EMAVFI_E_ARG, "%s: Hs x Ws = %d x %d, but ceil(H / s) x ceil(W / s) = %d x %d for %d x %d at s = %d", what, given[0], given[1], Hs, Ws,
+                    H, W, s);
+    if (__builtin_mul_overflow(planes, (size_t)H * W * sizeof(float), fine_bytes)
+        || __builtin_mul_overflow(planes, (size_t)Hs * Ws * sizeof(float), coarse_bytes))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (planes %zu)", what, planes);
+    return EMAVFI_OK;
+}
+
+int emavfi_downscale_f32(const float *src, float *dst, size_t planes, int H, int W, int s, void *stream)
+{
+    const char *const what = "downscale_f32";
+    size_t fine, coarse;
+    if (const int rc = coarse_shape_check(what, planes, H, W, s, nullptr, &fine, &coarse); rc != EMAVFI_OK) return rc;
+    if (const int rc = ensemble_pointer_check(what, "src", -1, src, fine); rc != EMAVFI_OK) return rc;
+    if (const int rc = ensemble_pointer_check(what, "dst", -1, dst, coarse); rc != EMAVFI_OK) return rc;
+    if (const int rc = border_overlap_check(what, src, fine, dst, coarse); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_coarse_down_f32(src, dst, planes, H, W, s, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+int emavfi_upsample_flow_f32(const float *flow_s, float *flow, size_t planes, int Hs, int Ws, int H, int W, int s, void *stream)
+{
+    const char *const what = "upsample_flow_f32";
+    size_t fine, coarse;
+    const int given[2] = {Hs, Ws};
+    if (const int rc = coarse_shape_check(what, planes, H, W, s, given, &fine, &coarse); rc != EMAVFI_OK) return rc;
+    if (const int rc = ensemble_pointer_check(what, "flow_s", -1, flow_s, coarse); rc != EMAVFI_OK) return rc;
+    if (const int rc = ensemble_pointer_check(what, "flow", -1, flow, fine); rc != EMAVFI_OK) return rc;
+    const uintptr_t s0 = (uintptr_t)flow_s, d0 = (uintptr_t)flow;
+    if (d0 < s0 + coarse && s0 < d0 + fine) return fail(EMAVFI_E_ARG, "%s: flow overlaps flow_s", what);
+    EMAVFI_TRY(launch_coarse_up_f32(flow_s, flow, planes, H, W, s, (hipStream_t)stream), what);
     return EMAVFI_OK;
 }
 

@@ -138,6 +138,10 @@ int launch_ensemble_mean_f32(const float *const *members, const int *flips, int 
 // frame borders (include/emavfi.h, "BORDER DEFINITION"): arguments already validated; H, W are the picture's size in both
 int launch_border_pad_f32(const float *src, float *dst, size_t planes, int H, int W, int N, int mode, hipStream_t s);
 int launch_border_crop_f32(const float *src, float *dst, size_t planes, int H, int W, int N, hipStream_t s);
+// coarse flow (include/emavfi.h, "COARSE FLOW DEFINITION"): arguments already validated; H, W are the FINE tensor's size in both, the
+// coarse one is ceil(H / s) x ceil(W / s)
+int launch_coarse_down_f32(const float *src, float *dst, size_t planes, int H, int W, int s, hipStream_t st);
+int launch_coarse_up_f32(const float *flow_s, float *flow, size_t planes, int H, int W, int s, hipStream_t st);
 // agreement guard (include/emavfi.h, "AGREEMENT GUARD DEFINITION"): arguments already validated; `mean` and `std` are HOST arrays of C
 // entries, read before the call returns and passed on as kernel arguments
 int launch_agreement_guard_f32(const float *u, const float *v, const float *a, const float *b, float *out, int B, int C, int H, int W,

@@ -9,6 +9,7 @@
 #include "static_elem.h"
 #include "ensemble_elem.h"
 #include "border_elem.h"
+#include "coarse_elem.h"
 #include "agreement_elem.h"
 #include "metrics_elem.h"
 #include "p010_elem.h"
@@ -2888,6 +2889,140 @@ int launch_border_crop_f32(const float *src, float *dst, size_t planes, int H, i
     const dim3 grid = border_plan(p, &wide);
     if (wide) border_crop_f32_kernel<true><<<grid, 256, 0, s>>>(p);
     else border_crop_f32_kernel<false><<<grid, 256, 0, s>>>(p);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Coarse flow (include/emavfi.h, "COARSE FLOW DEFINITION"; per-element functions: coarse_elem.h).
+//   coarse_down_f32_kernel   dst [planes][Hs][Ws] = down_s of src [planes][H][W]: the quadtree mean of s x s clamped leaves.
+//   coarse_up_f32_kernel     dst [planes][H][W] = s times the bilinear sample of src [planes][Hs][Ws] at half-pixel centres.
+//                          Both in the mould of border_body: grid (pieces of a DESTINATION plane, planes - at most 65535 rows of the
+//                          grid, a workgroup walks the planes beyond), 256 threads, pure streaming: no LDS, no atomics, nothing waits on
+//                          anything.  A lane owns one unit of a plane.
+//                          Down, wide form (src 16-byte aligned and W % 4 == 0, so every leaf row starts on a 16-byte boundary): a unit
+//                          is K destination columns of one row - K = 4 for s = 2 and 4, K = 1 for s = 8 -, its s K leaf columns are
+//                          s K / 4 16-byte loads per leaf row (rows clamped one by one), all issued before the first addition; a unit
+//                          whose leaves reach past column W - 1 (the clamped edge, a short last unit) runs the scalar per-element
+//                          function instead.  The K results leave as one 16-byte store where dst is 16-byte aligned and Ws % 4 == 0.
+//                          Up, wide form (dst 16-byte aligned and W % 4 == 0): a unit is 4 destination columns, one 16-byte store; the
+//                          coarse samples are scalar loads (1 / s^2 of the traffic, and neighbours share them in the cache).
+//                          Scalar forms: a unit is one element.  Plane offsets are 64-bit, indices inside a plane (at most 2^28
+//                          elements) 32-bit.  Every load's row and column index is clamped into its plane by the per-element functions.
+// ------------------------------------------------------------------------------------------
+struct CoarseArgs {
+    const float *src;
+    float *dst;
+    size_t planes, src_plane, dst_plane;   // elements per plane
+    int H, W, Hs, Ws, s, svec;             // H, W: the fine tensor; Hs, Ws: the coarse one; svec: 16-byte stores (down)
+};
+
+// the leaves of a wide unit, in registers: row r, column c of the unit's s x s K tile (every index is a constant after inlining)
+template <int S, int K> struct CoarseTileLeaf {
+    const float (&v)[S][S * K];
+    int k;
+    __device__ __forceinline__ float operator()(int r, int c) const { return v[r][S * k + c]; }
+};
+
+template <int S, bool WIDE>
+__global__ __launch_bounds__(256) void coarse_down_f32_kernel(CoarseArgs p)
+{
+    constexpr int K = WIDE ? (S == 8 ? 1 : 4) : 1, Q = WIDE ? S * K / 4 : 1;
+    const unsigned Wu = (unsigned)(p.Ws + K - 1) / K, units = (unsigned)p.Hs * Wu;
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= units) return;
+    const int i = (int)(u / Wu), j0 = (int)(u - (unsigned)i * Wu) * K;
+    const bool inside = WIDE && S * (j0 + K) <= p.W;   // every leaf column of the unit exists: no clamp along x, K valid results
+    for (size_t pl = blockIdx.y; pl < p.planes; pl += gridDim.y) {
+        const float *const s = p.src + pl * p.src_plane;
+        float *const d = p.dst + pl * p.dst_plane + (size_t)i * p.Ws + j0;
+        float o[K];
+        if constexpr (WIDE) {
+            if (inside) {
+                float v[S][S * K];
+#pragma unroll
+                for (int r = 0; r < S; ++r) {
+                    const int y = S * i + r < p.H - 1 ? S * i + r : p.H - 1;
+                    const float4 *row = reinterpret_cast<const float4 *>(s + (size_t)y * p.W + S * j0);
+#pragma unroll
+                    for (int q = 0; q < Q; ++q) {
+                        const float4 t = row[q];
+                        v[r][4 * q] = t.x; v[r][4 * q + 1] = t.y; v[r][4 * q + 2] = t.z; v[r][4 * q + 3] = t.w;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < K; ++k) o[k] = coarse_tree<S>(CoarseTileLeaf<S, K>{v, k}, 0, 0);
+                if (K == 4 && p.svec) {
+                    *reinterpret_cast<float4 *>(d) = make_float4(o[0], o[K > 1 ? 1 : 0], o[K > 2 ? 2 : 0], o[K > 3 ? 3 : 0]);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) d[k] = o[k];
+                }
+                continue;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            if (j0 + k < p.Ws) d[k] = coarse_down_elem_s<S>(s, p.H, p.W, i, j0 + k);
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void coarse_up_f32_kernel(CoarseArgs p)
+{
+    constexpr int K = WIDE ? 4 : 1;
+    const unsigned Wu = (unsigned)(WIDE ? p.W >> 2 : p.W), units = (unsigned)p.H * Wu;
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= units) return;
+    const int y = (int)(u / Wu), x0 = (int)(u - (unsigned)y * Wu) * K;
+    const CoarseTap ty = coarse_up_tap(y, p.Hs, p.s);
+    CoarseTap tx[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) tx[k] = coarse_up_tap(x0 + k, p.Ws, p.s);
+    for (size_t pl = blockIdx.y; pl < p.planes; pl += gridDim.y) {
+        const float *const s = p.src + pl * p.src_plane;
+        float *const d = p.dst + pl * p.dst_plane + (size_t)y * p.W + x0;
+        float o[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) o[k] = coarse_up_elem(s, p.Ws, ty, tx[k], p.s);
+        if constexpr (WIDE) *reinterpret_cast<float4 *>(d) = make_float4(o[0], o[K > 1 ? 1 : 0], o[K > 2 ? 2 : 0], o[K > 3 ? 3 : 0]);
+        else d[0] = o[0];
+    }
+}
+
+static CoarseArgs coarse_args(const float *src, float *dst, size_t planes, int H, int W, int s, bool down)
+{
+    CoarseArgs p{};
+    p.src = src; p.dst = dst; p.planes = planes; p.H = H; p.W = W; p.Hs = coarse_dim(H, s); p.Ws = coarse_dim(W, s); p.s = s;
+    const size_t fine = (size_t)H * W, coarse = (size_t)p.Hs * p.Ws;
+    p.src_plane = down ? fine : coarse; p.dst_plane = down ? coarse : fine;
+    return p;
+}
+static dim3 coarse_grid(size_t units, size_t planes) { return dim3((unsigned)((units + 255) / 256), (unsigned)(planes < 65535 ? planes : 65535)); }
+
+template <int S> static void launch_coarse_down_s(const CoarseArgs &p, bool wide, hipStream_t s)
+{
+    constexpr int K = S == 8 ? 1 : 4;
+    if (wide) coarse_down_f32_kernel<S, true><<<coarse_grid((size_t)p.Hs * (size_t)((p.Ws + K - 1) / K), p.planes), 256, 0, s>>>(p);
+    else coarse_down_f32_kernel<S, false><<<coarse_grid((size_t)p.Hs * (size_t)p.Ws, p.planes), 256, 0, s>>>(p);
+}
+
+int launch_coarse_down_f32(const float *src, float *dst, size_t planes, int H, int W, int s, hipStream_t st)
+{
+    CoarseArgs p = coarse_args(src, dst, planes, H, W, s, true);
+    const bool wide = (((uintptr_t)src | (uintptr_t)(W & 3)) & 15) == 0;
+    p.svec = (((uintptr_t)dst | (uintptr_t)(p.Ws & 3)) & 15) == 0;
+    if (s == 2) launch_coarse_down_s<2>(p, wide, st);
+    else if (s == 4) launch_coarse_down_s<4>(p, wide, st);
+    else launch_coarse_down_s<8>(p, wide, st);
+    return (int)hipGetLastError();
+}
+
+int launch_coarse_up_f32(const float *flow_s, float *flow, size_t planes, int H, int W, int s, hipStream_t st)
+{
+    const CoarseArgs p = coarse_args(flow_s, flow, planes, H, W, s, false);
+    const bool wide = (((uintptr_t)flow | (uintptr_t)(W & 3)) & 15) == 0;
+    if (wide) coarse_up_f32_kernel<true><<<coarse_grid((size_t)H * (size_t)(W >> 2), planes), 256, 0, st>>>(p);
+    else coarse_up_f32_kernel<false><<<coarse_grid((size_t)H * (size_t)W, planes), 256, 0, st>>>(p);
     return (int)hipGetLastError();
 }
 

@@ -91,6 +91,10 @@ def parser() -> argparse.ArgumentParser:
                         "--evaluate tells what it buys on a clip; excludes --reference-quirks")
     p.add_argument("--agreement-radius", type=int, default=None, metavar="R",
                    help="with --agreement: a disagreeing pixel holds its neighbours within R pixels (0..16) as well (default 0)")
+    p.add_argument("--flow-scale", type=int, choices=(2, 4, 8), default=None, metavar="{2,4,8}",
+                   help="estimate the flow of every forward on frames reduced by this factor and run everything else at full size: the "
+                        "model's flow sees 7 pixels, this multiplies that reach; the output keeps its size (--scale shrinks it); no quality "
+                        "claim is made, --evaluate tells what it buys on a clip")
     p.add_argument("--batch-pairs", type=int, default=8)
     p.add_argument("--chunk-pairs", type=int, default=64, help="frame pairs per chunk: at most chunk_pairs * frame_interval + 1 source frames are held")
     p.add_argument("--yuv-standard", default="bt601", help="bt601, bt709 or (10 / 12 / 16-bit streams) bt2020")
@@ -190,7 +194,8 @@ def _run(args) -> int:
                                   if args.static_guard is not None else {}),
                                ensemble=args.ensemble,
                                **(dict(border=args.border, border_mode=args.border_mode or "replicate") if args.border is not None else {}),
-                               **(dict(agreement=args.agreement, agreement_radius=args.agreement_radius) if args.agreement is not None else {}))
+                               **(dict(agreement=args.agreement, agreement_radius=args.agreement_radius) if args.agreement is not None else {}),
+                               flow_scale=args.flow_scale)
         if args.evaluate:
             print(fi.evaluate(list(reader), every=args.every))      # evaluate() indexes the clip: all of it is held
             return 0
@@ -210,6 +215,7 @@ def _run(args) -> int:
                      if args.static_guard is not None else "")
                   + (f", ensemble {args.ensemble}" if args.ensemble is not None else "")
                   + (f", border {args.border} {args.border_mode or 'replicate'}" if args.border is not None else "")
+                  + (f", flow scale {args.flow_scale}" if args.flow_scale is not None else "")
                   + (f", agreement guard held {100.0 * sum(fi.agreement_share) / max(len(fi.agreement_share), 1):.2f} % of the predictions' "
                      f"pixels on average" if args.agreement is not None else ""), file=sys.stderr)
     return 0

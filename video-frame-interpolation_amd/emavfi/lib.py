@@ -76,6 +76,14 @@ _PROTOTYPES = {
     "emavfi_ensemble_mean_f32": (c_int, [POINTER(c_void_p), POINTER(c_int), c_int, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "emavfi_border_pad_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
     "emavfi_border_crop_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "emavfi_downscale_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "emavfi_upsample_flow_f32": (c_int, [c_void_p, c_void_p, c_size_t] + [c_int] * 5 + [c_void_p]),
+    "emavfi_forward_flow": (c_int, [c_int] * 3 + [c_void_p, c_size_t] + [c_void_p] * 4 + [c_size_t] + [c_int] * 4 + [c_void_p]),
+    "emavfi_forward_given_flow": (c_int, [c_int] * 3 + [c_void_p, c_size_t] + [c_void_p] * 5 + [c_size_t] + [c_int] * 4
+                                  + [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int, ctypes.c_uint, c_void_p]),
+    "emavfi_forward_flow_launches": (c_int, [c_int] * 7 + [c_char_p, c_size_t, POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int]),
+    "emavfi_forward_given_flow_launches": (c_int, [c_int] * 7 + [ctypes.c_uint, c_char_p, c_size_t, POINTER(ctypes.c_double),
+                                                                 POINTER(ctypes.c_double), c_int]),
     "emavfi_agreement_guard_f32": (c_int, [c_void_p] * 5 + [c_int] * 5 + [ctypes.c_float, POINTER(ctypes.c_float), POINTER(ctypes.c_float),
                                            c_void_p, c_void_p]),
     "emavfi_frame_metrics_workspace_bytes": (c_size_t, [c_int] * 4),
@@ -491,17 +499,26 @@ def reconstruct(fused, params, dtype="fp32"):
                   "emavfi_reconstruct")
 
 
-def forward_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, gather_blocks=0, adaptive=False):
+def forward_launches(in_channels, mid_channels, num_blocks, B, H, W, dtype, gather_blocks=0, adaptive=False, flow=None):
     """[(name, algorithmic_flops, algorithmic_bytes)] for every kernel launch of one forward.  gather_blocks: bit i routes attention
     block i to the window-free kernel (emavfi_forward_launches_routed); 0 lists exactly what emavfi_forward launches.  adaptive: the
     launches of emavfi_forward_adaptive (a routed pack per block plus one route_select; in modes without a one-launch pack exactly
-    emavfi_forward's)."""
+    emavfi_forward's).  flow: None (the whole forward), "stop" (emavfi_forward_flow: the prefix through the launch that writes the
+    flow) or "given" (emavfi_forward_given_flow: without context encoding and motion estimation)."""
     L = load()
     dt = dtype_code(dtype)
     if adaptive and gather_blocks:
         raise ValueError("forward_launches: adaptive and gather_blocks exclude each other")
+    if flow not in (None, "stop", "given"):
+        raise ValueError(f"forward_launches: flow must be None, 'stop' or 'given', got {flow!r}")
+    if flow is not None and (adaptive or (flow == "stop" and gather_blocks)):
+        raise ValueError("forward_launches: the adaptive route has no given-flow form, and the flow's prefix has no attention block to route")
     model = (in_channels, mid_channels, num_blocks, B, H, W, dt)
-    if adaptive:
+    if flow == "stop":
+        entry, what, args = L.emavfi_forward_flow_launches, "emavfi_forward_flow_launches", model
+    elif flow == "given":
+        entry, what, args = L.emavfi_forward_given_flow_launches, "emavfi_forward_given_flow_launches", model + (gather_blocks,)
+    elif adaptive:
         entry, what, args = L.emavfi_forward_launches_adaptive, "emavfi_forward_launches_adaptive", model
     else:
         entry, what, args = L.emavfi_forward_launches_routed, "emavfi_forward_launches_routed", model + (gather_blocks,)
@@ -1479,6 +1496,129 @@ def border_crop_f32(x, N, out=None):
     with torch.cuda.device(dev):
         check(load().emavfi_border_crop_f32(x.data_ptr(), out.data_ptr(), planes, H, W, N, _stream()), "emavfi_border_crop_f32")
     return out
+
+
+# ---------------------------------------------------------------- coarse flow (include/emavfi.h, "COARSE FLOW DEFINITION")
+FLOW_SCALES = (2, 4, 8)                          # EMA_VFI.flow_scale, beside None
+
+
+def flow_scale_arg(s, what):
+    """s of the coarse flow definition: an int, one of FLOW_SCALES"""
+    if isinstance(s, bool) or not isinstance(s, int) or s not in FLOW_SCALES:
+        raise ValueError(f"{what}: the flow scale must be one of {FLOW_SCALES}, got {s!r}")
+    return s
+
+
+def coarse_size(H, W, s):
+    """(ceil(H / s), ceil(W / s)): the size at which an H x W pair's flow is estimated.  Pure."""
+    H, W, s = int(H), int(W), flow_scale_arg(s, "coarse_size")
+    if not (1 <= H <= RESIZE_MAX_DIM and 1 <= W <= RESIZE_MAX_DIM):
+        raise ValueError(f"coarse_size: {H} x {W}: every dimension must lie in 1..{RESIZE_MAX_DIM}")
+    return (H + s - 1) // s, (W + s - 1) // s
+
+
+def downscale_f32(x, s, out=None):
+    """out = down_s(x) over the last two dimensions (step 1 of the coarse flow definition): the balanced quadtree mean of s x s blocks,
+    edge blocks filled by clamping.  `x`: contiguous float32 [..., H, W]; `out`: the same with [ceil(H / s), ceil(W / s)]; device
+    tensors or pinned host memory, not overlapping.  Runs on the current stream; returns `out`."""
+    import torch
+    what = "downscale_f32"
+    planes, H, W = _ensemble_planes(x, f"{what}(x)")
+    s = flow_scale_arg(s, what)
+    out = _border_out(x, out, tuple(x.shape[:-2]) + coarse_size(H, W, s), what)
+    dev = next((t.device for t in (x, out) if t.is_cuda), None) or torch.device("cuda")
+    with torch.cuda.device(dev):
+        check(load().emavfi_downscale_f32(x.data_ptr(), out.data_ptr(), planes, H, W, s, _stream()), "emavfi_downscale_f32")
+    return out
+
+
+def upsample_flow_f32(flow_s, size, s, out=None):
+    """out = step 3 of the coarse flow definition: `flow_s` (contiguous float32 [..., Hs, Ws], estimated at 1 / s) sampled bilinearly
+    at half-pixel centres to `size` = (H, W) and multiplied by s.  Hs, Ws must be coarse_size(H, W, s).  Device tensors or pinned host
+    memory, not overlapping.  Runs on the current stream; returns `out`."""
+    import torch
+    what = "upsample_flow_f32"
+    planes, Hs, Ws = _ensemble_planes(flow_s, f"{what}(flow_s)")
+    s = flow_scale_arg(s, what)
+    H, W = (int(v) for v in size)
+    if coarse_size(H, W, s) != (Hs, Ws):
+        raise ValueError(f"{what}: flow_s is {Hs} x {Ws}, but {H} x {W} at s = {s} has a coarse size of {coarse_size(H, W, s)}")
+    out = _border_out(flow_s, out, tuple(flow_s.shape[:-2]) + (H, W), what)
+    dev = next((t.device for t in (flow_s, out) if t.is_cuda), None) or torch.device("cuda")
+    with torch.cuda.device(dev):
+        check(load().emavfi_upsample_flow_f32(flow_s.data_ptr(), out.data_ptr(), planes, Hs, Ws, H, W, s, _stream()),
+              "emavfi_upsample_flow_f32")
+    return out
+
+
+def _forward_pair(frame1, frame2, what):
+    """two checked fp32 contiguous [B, C, H, W] device batches of one shape"""
+    _require_cuda(frame1, frame2)
+    if frame1.shape != frame2.shape or frame1.dim() != 4 or frame1.device != frame2.device:
+        raise ValueError(f"{what}: two [B,C,H,W] tensors of one shape on one device expected, got {tuple(frame1.shape)} and {tuple(frame2.shape)}")
+    return _f32c(frame1), _f32c(frame2)
+
+
+def _forward_workspace(model, B, H, W, dt, dev):
+    nws = load().emavfi_workspace_bytes(*model, B, H, W, dt)
+    if nws == 0:
+        raise RuntimeError(f"emavfi_workspace_bytes: {last_error()}")
+    return workspace(nws, dev)
+
+
+def forward_flow(packed, frame1, frame2, mid_channels, num_blocks, dtype, out=None):
+    """The flow [B, 2, H, W] (float32) of the plain forward of (frame1, frame2): emavfi_forward_flow, the forward's launches up to the
+    one that writes the flow - bit for bit taps["flow"] of EMA_VFI.forward(..., return_taps=True).  `packed`: the model's blob for
+    `dtype` (EMA_VFI.packed_weights).  Runs on the current stream."""
+    import torch
+    f1, f2 = _forward_pair(frame1, frame2, "forward_flow")
+    B, C, H, W = f1.shape
+    dt, dev = dtype_code(dtype), f1.device
+    if out is None:
+        out = torch.empty(B, 2, H, W, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 2, H, W) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"forward_flow: out must be a contiguous float32 {(B, 2, H, W)} tensor on {dev}")
+    with torch.cuda.device(dev):
+        ws = _forward_workspace((C, mid_channels, num_blocks), B, H, W, dt, dev)
+        check(load().emavfi_forward_flow(C, mid_channels, num_blocks, packed.data_ptr(), packed.numel(), f1.data_ptr(), f2.data_ptr(),
+                                         out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, dt, _stream()), "emavfi_forward_flow")
+    return out
+
+
+def forward_given_flow(packed, frame1, frame2, flow, mid_channels, num_blocks, dtype, out=None, return_taps=False, gather_blocks=0,
+                       stage=None, _events=None):
+    """The plain forward of (frame1, frame2) with `flow` (contiguous float32 [B, 2, H, W], read in place) where motion estimation's
+    output would be: emavfi_forward_given_flow (step 4 of the coarse flow definition; context encoding and motion estimation are not
+    launched).  Returns the float32 frame, or (frame, taps) with the taps such a forward has: feat, warped, fused_i.  gather_blocks:
+    emavfi_forward_routed's mask; stage / _events: the C-ABI's stage-event array and bench.py's (events, count).  Runs on the current
+    stream."""
+    import torch
+    from collections import OrderedDict
+    f1, f2 = _forward_pair(frame1, frame2, "forward_given_flow")
+    B, C, H, W = f1.shape
+    dt, dev = dtype_code(dtype), f1.device
+    if not flow.is_cuda or flow.device != dev or flow.dtype != torch.float32 or tuple(flow.shape) != (B, 2, H, W) or not flow.is_contiguous():
+        raise ValueError(f"forward_given_flow: flow must be a contiguous float32 {(B, 2, H, W)} tensor on {dev}")
+    if out is None:
+        out = torch.empty_like(f1)
+    elif out.dtype != torch.float32 or out.shape != f1.shape or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"forward_given_flow: out must be a contiguous float32 {tuple(f1.shape)} tensor on {dev}")
+    taps, taps_arg = None, None
+    if return_taps:
+        m = mid_channels
+        taps = OrderedDict(feat=torch.empty(B, m, H, W, device=dev), warped=torch.empty(B, C, H, W, device=dev))
+        ptrs = [taps["feat"].data_ptr(), None, None, taps["warped"].data_ptr(), None]
+        for i in range(num_blocks):
+            taps[f"fused_{i}"] = torch.empty(B, m + 3, H, W, device=dev)
+            ptrs.append(taps[f"fused_{i}"].data_ptr())
+        taps_arg = ctypes.cast((c_void_p * len(ptrs))(*ptrs), POINTER(c_void_p))
+    evp, nev = _events_arg(_events)
+    with torch.cuda.device(dev):
+        ws = _forward_workspace((C, mid_channels, num_blocks), B, H, W, dt, dev)
+        check(load().emavfi_forward_given_flow(C, mid_channels, num_blocks, packed.data_ptr(), packed.numel(), f1.data_ptr(), f2.data_ptr(),
+                                               flow.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, dt, taps_arg, stage, evp,
+                                               nev, int(gather_blocks), _stream()), "emavfi_forward_given_flow")
+    return (out, taps) if return_taps else out
 
 
 # ---------------------------------------------------------------- agreement guard (include/emavfi.h, "AGREEMENT GUARD DEFINITION")

@@ -46,6 +46,9 @@ BORDER_MODES, BORDER_MAX = _lib.BORDER_MODES, _lib.BORDER_MAX
 _MODEL_BORDER = object()     # forward(border=): "what the model's attribute says"
 # EMA_VFI.agreement ("Agreement guard"; include/emavfi.h, "AGREEMENT GUARD DEFINITION")
 _MODEL_AGREEMENT = object()  # forward(agreement=): "what the model's attribute says"
+# EMA_VFI.flow_scale ("Flow scale"; include/emavfi.h, "COARSE FLOW DEFINITION")
+FLOW_SCALES = _lib.FLOW_SCALES
+_MODEL_FLOW_SCALE = object() # forward(flow_scale=): "what the model's attribute says"
 
 
 class _LastCall(NamedTuple):
@@ -182,6 +185,7 @@ class EMA_VFI(nn.Module):
         self.ensemble = None
         self.border = None
         self.agreement = None
+        self.flow_scale = None
         self.agreement_counts = None   # the last guarded forward's held pixels per sample: int32 [B] on the device
         m = mid_channels
         self.feat_ext_conv1 = conv_block(in_channels * 2, m)
@@ -469,6 +473,28 @@ class EMA_VFI(nn.Module):
             raise ValueError(f"EMA_VFI.agreement must be None, a tolerance in [0, 1] or (tolerance, radius) with an int radius in "
                              f"0..{_lib.STATIC_MAX_RADIUS}, got {value!r}") from None
 
+    @property
+    def flow_scale(self):
+        """The scale at which forward() estimates the flow ("Flow scale"; include/emavfi.h, "COARSE FLOW DEFINITION"):
+        None (default: the plain forward, every launch and byte as without the attribute) or s in (2, 4, 8).  Both inputs are reduced
+        by s on the device (emavfi_downscale_f32), the front of the forward runs on the reduced pair up to its flow
+        (emavfi_forward_flow), the flow is brought back to full size and multiplied by s (emavfi_upsample_flow_f32), and the full-size
+        forward runs with it (emavfi_forward_given_flow), without context encoding and motion estimation.  The output keeps its size;
+        what changes is how far the motion may reach: about 7 s pixels instead of 7.  Every F of an ensemble, of a bordered forward and
+        of the agreement guard becomes this F_s.  A batch runs as one sequence (pipeline is ignored); pack_policy applies to the
+        full-size forward; pack_adapt and return_taps are refused.  No host synchronisation is added."""
+        return self._flow_scale
+
+    @flow_scale.setter
+    def flow_scale(self, value):
+        self._flow_scale = self._check_flow_scale(value)
+
+    @staticmethod
+    def _check_flow_scale(value):
+        if value is not None and (isinstance(value, bool) or not isinstance(value, int) or value not in FLOW_SCALES):
+            raise ValueError(f"EMA_VFI.flow_scale must be None or one of {FLOW_SCALES}, got {value!r}")
+        return value
+
     def _check_border_size(self, B, H, W, border, dt):
         """(H + 2N, W + 2N), or a refusal from the shapes alone where the padded batch is beyond what the forward admits (include/emavfi.h,
         SIZE LIMITS: B*H*W < 2^31, H*W < 2^24, the fusion plane < 4 GiB) - before anything is launched"""
@@ -537,13 +563,19 @@ class EMA_VFI(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def forward(self, frame1, frame2, return_taps=False, _events=None, ensemble=_MODEL_ENSEMBLE, border=_MODEL_BORDER,
-                agreement=_MODEL_AGREEMENT):
+                agreement=_MODEL_AGREEMENT, flow_scale=_MODEL_FLOW_SCALE):
         """ema_vfi.py:110-147.  `ensemble`: one of ENSEMBLES for this call alone (FrameInterpolator passes its own); by default the
         model's attribute decides.  `border`: None, N or (N, mode) for this call alone, likewise.  `agreement`: None, tol or
-        (tol, radius) for this call alone, likewise."""
+        (tol, radius) for this call alone, likewise.  `flow_scale`: None, 2, 4 or 8 for this call alone, likewise."""
         ensemble = self._ensemble if ensemble is _MODEL_ENSEMBLE else self._check_ensemble(ensemble)
         border = self._border if border is _MODEL_BORDER else self._check_border(border)
         agreement = self._agreement if agreement is _MODEL_AGREEMENT else self._check_agreement(agreement)
+        fs = self._flow_scale if flow_scale is _MODEL_FLOW_SCALE else self._check_flow_scale(flow_scale)
+        if fs is not None and return_taps:
+            raise ValueError("EMA_VFI.forward: return_taps=True with a flow scale: ctx and flow belong to the reduced forward, the rest to "
+                             "the full-size one (set flow_scale=None, or call lib.forward_flow / lib.forward_given_flow)")
+        if fs is not None and self._pack_adapt is not None:
+            raise ValueError("EMA_VFI.forward: flow_scale with pack_adapt: the adaptive route has no given-flow form (unset one of them)")
         if agreement is not None and return_taps:
             raise ValueError("EMA_VFI.forward: return_taps=True with an agreement guard: the taps belong to one forward (set agreement=None)")
         if agreement is not None and ensemble not in _lib.AGREEMENT_ENSEMBLES:
@@ -581,22 +613,22 @@ class EMA_VFI(nn.Module):
             f1, f2 = (_lib.border_pad_f32(f, *border) for f in (f1, f2))
             if agreement is not None:
                 # the two halves of the padded ensemble, cropped, then the guard on the picture with the unpadded sources
-                u, v = (_lib.border_crop_f32(h, border[0]) for h in self._forward_halves(L, packed, f1, f2, dt, ensemble, _events))
+                u, v = (_lib.border_crop_f32(h, border[0]) for h in self._forward_halves(L, packed, f1, f2, dt, ensemble, _events, fs))
                 out = self._agreement_guard(u, v, a, b, agreement)
                 return out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
             if ensemble is not None:
-                out = self._forward_ensemble(L, packed, f1, f2, dt, ensemble, _events)
+                out = self._forward_ensemble(L, packed, f1, f2, dt, ensemble, _events, fs)
             else:
                 out = torch.empty_like(f1)
-                self._forward_f32(L, packed, f1, f2, out, dt, None, _events)
+                self._forward_f32(L, packed, f1, f2, out, dt, None, _events, fs)
             out = _lib.border_crop_f32(out, border[0])
             return out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
         if agreement is not None:
-            u, v = self._forward_halves(L, packed, f1, f2, dt, ensemble, _events)
+            u, v = self._forward_halves(L, packed, f1, f2, dt, ensemble, _events, fs)
             out = self._agreement_guard(u, v, f1, f2, agreement)
             return out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
         if ensemble is not None:
-            out = self._forward_ensemble(L, packed, f1, f2, dt, ensemble, _events)
+            out = self._forward_ensemble(L, packed, f1, f2, dt, ensemble, _events, fs)
             return out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
         out = torch.empty_like(f1)
         taps_arg, taps = None, None
@@ -609,7 +641,7 @@ class EMA_VFI(nn.Module):
                 taps[f"fused_{i}"] = torch.empty(B, m + 3, H, W, device=dev)
                 ptrs.append(taps[f"fused_{i}"].data_ptr())
             taps_arg = cast((c_void_p * len(ptrs))(*ptrs), POINTER(c_void_p))
-        self._forward_f32(L, packed, f1, f2, out, dt, taps_arg, _events)
+        self._forward_f32(L, packed, f1, f2, out, dt, taps_arg, _events, fs)
         # under autocast the reference's reconstruction tail is fp16, so its frame is an fp16 tensor (the values computed
         # here are fp16-representable: the conversion is exact)
         out = out.half() if dt == _lib.AMP16 else out.to(frame1.dtype)
@@ -618,10 +650,18 @@ class EMA_VFI(nn.Module):
             return out, taps
         return out
 
-    def _forward_f32(self, L, packed, f1, f2, out, dt, taps_arg=None, _events=None):
+    def _forward_f32(self, L, packed, f1, f2, out, dt, taps_arg=None, _events=None, fs=None):
         """F(f1, f2) of the ensemble definition: the plain forward of two checked fp32 contiguous batches into the fp32 `out`, as one
-        sequence of launches or pipelined over two streams"""
+        sequence of launches or pipelined over two streams.  With a flow scale `fs` it is F_s of the coarse flow definition: its four
+        steps on the current stream, one sequence (`_events` bracket the full-size forward's launches)."""
         B, C, H, W = f1.shape
+        if fs is not None:
+            a_s, b_s = _lib.downscale_f32(f1, fs), _lib.downscale_f32(f2, fs)
+            flow_s = _lib.forward_flow(packed, a_s, b_s, self.mid_channels, self.num_blocks, dt)
+            flow = _lib.upsample_flow_f32(flow_s, (H, W), fs)
+            gmask = (1 << self.num_blocks) - 1 if self._pack_policy == "gather" else 0
+            self._last_call = self._launch(L, packed, f1, f2, out, dt, gmask, None, None, _events, flow)
+            return
         pieces = min(int(self.pipeline), B)
         if (C * H * W) % 4 != 0:
             pieces = 1   # a slice of the batch must start 16-byte aligned (include/emavfi.h): odd sample sizes run as one sequence
@@ -635,14 +675,14 @@ class EMA_VFI(nn.Module):
         else:
             self._last_call = self._launch(L, packed, f1, f2, out, dt, gmask, taps_arg, None, _events)
 
-    def _forward_ensemble(self, L, packed, f1, f2, dt, ensemble, _events=None):
+    def _forward_ensemble(self, L, packed, f1, f2, dt, ensemble, _events=None, fs=None):
         """The fp32 ensemble of include/emavfi.h, "ENSEMBLE DEFINITION": its members are plain forwards of the same batch, issued in the
         definition's member order (under pack_adapt every one of them advances the route state, as the same calls made by hand would).
         Run one after the other and not as one larger batch: the result is the composition by construction, whatever the kernels do
         across a batch, and eight 720p batches of 8 would not share a workspace anyway.  `_events` bracket the first member's launches."""
-        return _lib.ensemble_mean_f32(*self._ensemble_members(L, packed, f1, f2, dt, ensemble, _events))
+        return _lib.ensemble_mean_f32(*self._ensemble_members(L, packed, f1, f2, dt, ensemble, _events, fs))
 
-    def _ensemble_members(self, L, packed, f1, f2, dt, ensemble, _events=None):
+    def _ensemble_members(self, L, packed, f1, f2, dt, ensemble, _events=None, fs=None):
         """(members, flip codes) of the ensemble, in the definition's order: the plain forwards, each an fp32 tensor of its own"""
         flips = (0,) if ensemble == "reverse" else _lib.ENSEMBLE_FLIPS
         mirrored = {f: (_lib.flip_f32(f1, f), _lib.flip_f32(f2, f)) if f else (f1, f2) for f in flips}
@@ -651,15 +691,15 @@ class EMA_VFI(nn.Module):
             for f in flips:
                 x1, x2 = mirrored[f][::-1] if reverse else mirrored[f]
                 m = torch.empty_like(f1)
-                self._forward_f32(L, packed, x1, x2, m, dt, None, _events if not members else None)
+                self._forward_f32(L, packed, x1, x2, m, dt, None, _events if not members else None, fs)
                 members.append(m)
                 codes.append(f)
         return members, codes
 
-    def _forward_halves(self, L, packed, f1, f2, dt, ensemble, _events=None):
+    def _forward_halves(self, L, packed, f1, f2, dt, ensemble, _events=None, fs=None):
         """(u, v) of the agreement guard definition for ensemble "reverse" or "full": the same members as the ensemble's, in the same
         order, the time-forward half and the time-reversed half each reduced by the definition's tree mean (one member: the member)"""
-        members, codes = self._ensemble_members(L, packed, f1, f2, dt, ensemble, _events)
+        members, codes = self._ensemble_members(L, packed, f1, f2, dt, ensemble, _events, fs)
         n = len(members) // 2
         if n == 1:
             return members[0], members[1]
@@ -701,9 +741,10 @@ class EMA_VFI(nn.Module):
                 row["route"] = "gather" if (gmask >> i) & 1 else "window"
         return rows
 
-    def _launch(self, L, packed, f1, f2, out, dt, gather_mask, taps=None, stage=None, _events=None):
+    def _launch(self, L, packed, f1, f2, out, dt, gather_mask, taps=None, stage=None, _events=None, flow=None):
         """One forward of f1 / f2 into `out` on the current stream of their device: emavfi_forward_routed with `gather_mask`, or
-        emavfi_forward_adaptive when it is None (pack_adapt).  taps / stage: the C-ABI's tap and stage-event pointer arrays or None;
+        emavfi_forward_adaptive when it is None (pack_adapt), or - `flow`: a contiguous fp32 [B,2,H,W] tensor -
+        emavfi_forward_given_flow with `gather_mask`.  taps / stage: the C-ABI's tap and stage-event pointer arrays or None;
         _events: (hipEvent_t array, count) or None.  Returns the call's _LastCall."""
         B, C, H, W = f1.shape
         dev = f1.device
@@ -716,7 +757,10 @@ class EMA_VFI(nn.Module):
         args = (C, self.mid_channels, self.num_blocks, packed.data_ptr(), packed.numel(), f1.data_ptr(), f2.data_ptr(), out.data_ptr(),
                 ws.data_ptr(), ws.numel(), B, H, W, dt, taps, stage, evp, nev)
         with torch.cuda.device(dev):
-            if state is not None:
+            if flow is not None:
+                _lib.check(L.emavfi_forward_given_flow(*args[:7], flow.data_ptr(), *args[7:], gather_mask, _lib._stream()),
+                           "emavfi_forward_given_flow")
+            elif state is not None:
                 enter, leave = self._pack_adapt
                 _lib.check(L.emavfi_forward_adaptive(*args, state.data_ptr(), enter, leave, _lib._stream()), "emavfi_forward_adaptive")
             else:

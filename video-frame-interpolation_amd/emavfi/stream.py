@@ -129,6 +129,11 @@ model's attribute) and is refused otherwise, and with ``reference_quirks=True`` 
 prediction would show as patches).  ``agreement_share`` lists, per emitted prediction of the last ``run()`` (mode "resample": per emitted
 frame made of node frames, the share of the first node frame it names), the share of its pixels the guard held; the counts follow the
 frames to pinned memory and are read after the ``done`` wait the drain already performs - no new synchronisation point.
+``flow_scale=2 | 4 | 8`` (opt-in; not in the reference, whose ``--scale`` shrinks the output as well) runs EVERY forward the harness issues -
+all three modes, the recursion's inner midpoints, ``evaluate()``, the members of an ensemble, with any of the options above - with the flow
+estimated on the pair reduced by that factor and everything else at full size (include/emavfi.h, "COARSE FLOW DEFINITION";
+``EMA_VFI.flow_scale``).  It is passed with each call, as ``ensemble`` is; ``None`` (default) leaves the decision to the model's attribute.
+No quality claim is made: ``evaluate()`` says what it buys on a clip.
 
 ``border=N`` with ``border_mode="replicate" | "reflect"`` (opt-in; not in the reference) runs EVERY forward the harness issues - all three
 modes, the recursion's inner midpoints, ``evaluate()``, with any of the options above, the ensemble included - on frames extended by N
@@ -260,6 +265,7 @@ class FrameInterpolator:
     ensemble = None       # test-time ensembling of every forward (EMA_VFI.ensemble); None: what the model's attribute says
     border = None         # (N, mode) of the frame border of every forward (EMA_VFI.border); None: what the model's attribute says
     agreement = None      # (tol, radius) of the agreement guard of every forward (EMA_VFI.agreement); None: what the model's attribute says
+    flow_scale = None     # the scale the flow of every forward is estimated at (EMA_VFI.flow_scale); None: what the model's attribute says
     _ag = None   # under `agreement`: the held pixel counts of the batch just predicted, int32 on the device, in prediction order
     _depth = 0   # bits per sample of a 16-bit-word pixel format ("p010": 10, ...); 0 for the byte formats
     _planar = _yuv8 = False
@@ -273,7 +279,8 @@ class FrameInterpolator:
                  dedup_threshold: Optional[float] = None, dedup_max_run: int = 3, dedup_span: int = 64,
                  static_guard: Optional[int] = None, static_tolerance: float = 0.0, ensemble: Optional[str] = None,
                  border: Optional[int] = None, border_mode: str = "replicate",
-                 agreement: Optional[float] = None, agreement_radius: Optional[int] = None, shutter=None):
+                 agreement: Optional[float] = None, agreement_radius: Optional[int] = None, shutter=None,
+                 flow_scale: Optional[int] = None):
         if shutter is not None and mode != "resample":
             raise ValueError("shutter belongs to mode='resample': the exposure window is accumulated over the nodes of its time grid")
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
@@ -340,6 +347,11 @@ class FrameInterpolator:
                                  f"runs both, one of {_lib.AGREEMENT_ENSEMBLES} (it is not chosen for you)")
             self._forward_kw["agreement"] = self.agreement
         self.agreement_share = []   # per emitted prediction of the last run(): the share of its pixels the agreement guard held
+        if flow_scale is not None:
+            self.flow_scale = _lib.flow_scale_arg(flow_scale, "flow_scale")
+            if getattr(model, "pack_adapt", None) is not None:
+                raise ValueError("flow_scale with a model under pack_adapt: the adaptive route has no given-flow form (unset one of them)")
+            self._forward_kw["flow_scale"] = self.flow_scale
         if pixel_format not in ("bgr24", "nv12", *_lib.DEPTHS, *_lib.PLANAR_DEPTHS):
             raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames), 'nv12' (uint8 [H*3/2, W] frames), 'p010' / 'p012' / 'p016' "
                              "(uint16 [H*3/2, W] frames) or planar 'yuv420p8' (uint8) / 'yuv420p10' / 'yuv420p12' / 'yuv420p16' (uint16)")
