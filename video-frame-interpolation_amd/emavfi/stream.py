@@ -148,6 +148,7 @@ from __future__ import annotations
 import os
 from fractions import Fraction
 from math import gcd
+from types import SimpleNamespace
 from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Tuple
 
 import numpy as np
@@ -1015,6 +1016,90 @@ class FrameInterpolator:
         counts.record_stream(self._post)
         slot["h_ag"][:n].copy_(counts, non_blocking=True)
 
+    def _norm_constants(self, device):
+        """(mean, std) of the model's input as [1, 3, 1, 1] device tensors, created once: torch.tensor(..., device=) is a synchronous
+        pageable copy, i.e. the host would block behind the forward it has just enqueued and stop staging / draining beside it."""
+        if self._norm is None:
+            self._norm = (torch.tensor(_lib.IMAGENET_MEAN, device=device).view(1, 3, 1, 1),
+                          torch.tensor(_lib.IMAGENET_STD, device=device).view(1, 3, 1, 1))
+        return self._norm
+
+    # ---- what a run reports beside its frames; run_chunked accumulates these over its chunks
+    _REPORTS = ("scene_cuts", "scene_scores", "duplicates", "dedup_scores", "static_share", "agreement_share")
+
+    def _reset_reports(self):
+        for name in self._REPORTS:
+            setattr(self, name, [])
+
+    def _note_scenes(self, slot, chunk):
+        """on the drain: the scores and flags of the batch's pairs, written behind the frames, ahead of `done`"""
+        fs = slot["h_fs"].numpy()
+        for k, (a, b) in enumerate(chunk):
+            self.scene_scores.append((a, b, int(fs[1, k])))
+            if fs[0, k]:
+                self.scene_cuts.append((a, b, int(fs[1, k])))
+
+    def _shares(self, counts, idx):
+        """on the drain: the held pixel counts `counts[i]` (a slot's pinned buffer, written behind the frames, ahead of `done`) for i in
+        `idx`, as shares of a frame at the size the model runs at"""
+        counts, area = counts.numpy(), float(self._dst[0] * self._dst[1])
+        return [int(counts[i]) / area for i in idx]
+
+    # ---- the three lanes: the one place that orders a slot's readers and writers across the streams and the host
+    def _lane_in(self, slot, nup, upload=True):
+        """The pre lane's prologue for a slot, under ``self._pre``.  The slot's x was last read by the forward of the batch two before
+        (`fwd`), and its x, d_in and resized bytes by that batch's post lane - the round trip of the earlier frames, the guards and holds, the
+        resample assembly, the metric kernel (`done`).  `upload`: the `nup` staged frames then travel pinned -> HBM by hipMemcpyAsync (SDMA),
+        after which the host may restage h_in (`consumed`)."""
+        self._pre.wait_event(slot["fwd"])
+        self._pre.wait_event(slot["done"])
+        if upload:
+            slot["d_in"][:nup].copy_(slot["h_in"][:nup], non_blocking=True)
+            slot["consumed"].record(self._pre)
+
+    def _batches(self, frames, chunks, pre, forward, post, drain, upload=True, early=None):
+        """The batch pipeline of run(), mode "resample" and evaluate(): owns the order across the lanes and the host, and nothing else.
+        Per batch ``b`` (``slot``, ``chunk``, ``n`` items, ``nup`` staged frames, ``rows`` = _stage's position lists; a step leaves what
+        the later steps of its batch need as further attributes of ``b``):
+          pre lane        wait `fwd`, `done` (_lane_in; `upload`: and the SDMA copy) -> ``pre(b)`` -> record `pre` -> ``early(b)``: what
+                          depends on the preprocess only and leaves from this lane, ahead of the forward
+          caller's stream wait `pre` -> ``forward(b)`` -> record `fwd`
+          post lane       wait `fwd` -> ``post(b)`` -> record `done`
+          host            stage batch ci + 1 into the other slot, then wait for `done` of batch ci - 1 and yield from its ``drain(b)``
+        in exactly that order: staging and draining overlap the compute just enqueued, and a slot is restaged only behind its `consumed`
+        (_stage) and rewritten only behind the readers above."""
+        if not chunks:
+            return
+        main = torch.cuda.current_stream(self.device)
+
+        def drained(b):
+            b.slot["done"].synchronize()           # this batch's bytes and words have been written into the pinned buffers
+            return drain(b) or ()
+
+        staged = self._stage(self._slots[0], frames, chunks[0])
+        prev = None
+        for ci, chunk in enumerate(chunks):
+            b = SimpleNamespace(slot=self._slots[ci & 1], chunk=chunk, n=len(chunk), nup=staged[0], rows=staged[1:])
+            with torch.cuda.stream(self._pre):
+                self._lane_in(b.slot, b.nup, upload)
+                pre(b)
+                b.slot["pre"].record(self._pre)
+                if early is not None:
+                    early(b)
+            main.wait_event(b.slot["pre"])
+            forward(b)
+            b.slot["fwd"].record(main)
+            with torch.cuda.stream(self._post):
+                self._post.wait_event(b.slot["fwd"])
+                post(b)
+                b.slot["done"].record(self._post)
+            if ci + 1 < len(chunks):                  # host-side staging of the next batch overlaps this batch's compute
+                staged = self._stage(self._slots[(ci + 1) & 1], frames, chunks[ci + 1])
+            if prev is not None:                      # emit the previous batch (its slot is reused only after this)
+                yield from drained(prev)
+            prev = b
+        yield from drained(prev)
+
     def _predict(self, x1, x2):
         """[n, k, 3, H, W] predictions per pair: k = 1 (reference mode) or `factor` recursive midpoints."""
         with torch.no_grad():
@@ -1022,13 +1107,8 @@ class FrameInterpolator:
                 out = self._forward(x1, x2).unsqueeze(1)
                 self._ag = self._held()
                 return out
-            # the model consumes normalised frames and returns [0,1] images: re-normalise midpoints to recurse.
-            # The constants are created once: torch.tensor(..., device=) is a synchronous pageable copy, i.e. the host
-            # would block behind the forward it has just enqueued and stop staging / draining beside it.
-            if self._norm is None:
-                self._norm = (torch.tensor(_lib.IMAGENET_MEAN, device=x1.device).view(1, 3, 1, 1),
-                              torch.tensor(_lib.IMAGENET_STD, device=x1.device).view(1, 3, 1, 1))
-            mean, std = self._norm
+            # the model consumes normalised frames and returns [0,1] images: re-normalise midpoints to recurse
+            mean, std = self._norm_constants(x1.device)
 
             def rec(a, b, depth):
                 m = (self._forward(a, b), self._held())
@@ -1095,9 +1175,7 @@ class FrameInterpolator:
             first = frames[lo]
         words = (lambda v: v.view(np.uint16)) if self._depth else (lambda v: v)
         self._alloc(first.shape)
-        self.scene_cuts, self.scene_scores = [], []
-        self.static_share, self.agreement_share = [], []
-        main = torch.cuda.current_stream(self.device)
+        self._reset_reports()
         # ramp-up: with three or more batches to come the FIRST one is half-size - the GPU starts after five staged frames instead of
         # nine, and (64 pairs at batch 8: 4 + 7 x 8 + 4) the last one's drain is half as long; every other batch is full.  Per-sample
         # results do not depend on the batch a pair travels in (tests/test_gpu_parity.py::test_forward_config2_batch16_256)
@@ -1106,133 +1184,107 @@ class FrameInterpolator:
         chunks = ([pairs[:head]] if head else []) + [pairs[i:i + bp] for i in range(head, len(pairs), bp)]
         npred = self.factor if self.mode == "recursive" else 1
 
-        def drain(slot, chunk):
-            slot["done"].synchronize()            # this batch's frames have been written into the pinned buffers
+        def pre(b):
+            slot, nup, (ia, ib) = b.slot, b.nup, b.rows
+            b.rs = rs = slot["d_rs"][:nup] if slot["d_rs"] is not None else None
+            rz = slot["p_rs"][:nup] if slot["p_rs"] is not None else rs   # where the preprocess leaves resized bytes; `rs`: they are emitted
+            if self.zero_copy:
+                b.x = self._pre_kernel(slot["h_in"][:nup], device=self.device, out=slot["x"][:nup], resized=rz)   # distinct frames, read over PCIe, normalised once
+                if self.scene is not None:
+                    self._scene_decide(slot, slot["h_in"][:nup], ia, ib)
+                    if not self.quirks and rs is None:
+                        # the bytes a held frame is made of are the staged input rows, which the host restages once `consumed` fires
+                        for k in range(b.n):
+                            slot["d_src"][k].copy_(slot["h_in"][ia[k]], non_blocking=True)
+                slot["consumed"].record(self._pre)
+            else:                                  # the staged frames are in d_in (the driver's upload)
+                b.x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=rz)             # distinct frames, normalised once
+                if self.scene is not None:
+                    self._scene_decide(slot, slot["d_in"][:nup], ia, ib)
+            b.src_here = self.quirks and not self.zero_copy and all(ia[k + 1] == ia[k] + 1 for k in range(b.n - 1))
+
+        def early(b):
+            slot, n, ia = b.slot, b.n, b.rows[0]
+            if b.rs is not None:
+                # reference_quirks=False with a resize: every pair's earlier frame leaves as the preprocess kernel resized it
+                for k in range(n):
+                    slot["h_src"][k].copy_(b.rs[ia[k]], non_blocking=True)
+                slot["src"].record(self._pre)
+            if b.src_here:
+                # the reference's round trip of every pair's earlier frame (inference.py:187-188) depends on the preprocess only:
+                # it leaves from this lane, ahead of the forward, instead of queueing behind the predictions at the end of the batch
+                self._post_kernel(b.x[ia[0]:ia[0] + n], True, out=slot["d_src"][:n])
+                slot["h_src"][:n].copy_(slot["d_src"][:n], non_blocking=True)
+                slot["src"].record(self._pre)
+
+        def forward(b):
+            b.x1, x2 = self._rows(b.x, b.rows[0]), self._rows(b.x, b.rows[1])
+            b.pred = self._predict(b.x1, x2)                                  # [n, k, 3, H, W], on the caller's stream
+            b.held = self._ag                                                 # int32 [n k] on the device, or None
+
+        def post(b):
+            slot, n, nup, (ia, ib), rs, x1 = b.slot, b.n, b.nup, b.rows, b.rs, b.x1
+            flat = b.pred.reshape(-1, *b.pred.shape[2:])
+            flat.record_stream(self._post)                                # allocated on the caller's stream, read on this one
+            if b.held is not None:
+                self._held_to_host(slot, b.held)
+            if self.quirks and (x1.data_ptr() < slot["x"].data_ptr() or x1.data_ptr() >= slot["x"].data_ptr() + slot["x"].numel() * 4):
+                x1.record_stream(self._post)                              # a gathered copy (non-consecutive rows), not a view of the slot
+            if self.zero_copy:
+                self._post_kernel(flat, self.quirks, out=slot["h_pred"][:n * npred])
+                if self.quirks:
+                    self._post_kernel(x1, True, out=slot["h_src"][:n])
+            else:
+                self._post_kernel(flat, self.quirks, out=slot["d_pred"][:n * npred])
+                if self.static_guard is not None:
+                    # every prediction of pair k against the pair's two source frames as emitted; d_in / d_rs are complete: the
+                    # forward waited for the preprocess
+                    self._static_hold(slot, slot["d_pred"], rs if rs is not None else slot["d_in"][:nup],
+                                      [(ia[k], ib[k]) for k in range(n) for _ in range(npred)])
+                if self.scene is None:
+                    slot["h_pred"][:n * npred].copy_(slot["d_pred"][:n * npred], non_blocking=True)   # HBM -> pinned (SDMA)
+                if self.quirks and not b.src_here:
+                    self._post_kernel(x1, True, out=slot["d_src"][:n])
+                    slot["h_src"][:n].copy_(slot["d_src"][:n], non_blocking=True)
+                if b.src_here:
+                    self._post.wait_event(slot["src"])                    # the drain's wait covers both lanes' writes into the pinned buffers
+            if rs is not None:
+                self._post.wait_event(slot["src"])
+            if self.scene is not None:
+                # every source of a held frame is complete here: d_src / h_src (this lane, or the `src` event above), d_rs and d_in (the
+                # preprocess the forward waited for).  The prediction frames of a flagged pair become the bytes emitted as its earlier frame
+                dst = slot["h_pred"] if self.zero_copy else slot["d_pred"]
+                if self.quirks:
+                    self._scene_hold(slot, dst, slot["h_src"] if self.zero_copy else slot["d_src"], list(range(n)), npred)
+                elif rs is not None:
+                    self._scene_hold(slot, dst, rs, ia, npred)
+                elif self.zero_copy:
+                    self._scene_hold(slot, dst, slot["d_src"], list(range(n)), npred)
+                else:
+                    self._scene_hold(slot, dst, slot["d_in"], ia, npred)
+                if not self.zero_copy:
+                    slot["h_pred"][:n * npred].copy_(slot["d_pred"][:n * npred], non_blocking=True)   # HBM -> pinned (SDMA), after the hold
+                slot["h_fs"].copy_(slot["fs"], non_blocking=True)
+
+        def drain(b):
+            slot = b.slot
             pred_h, src_h = slot["h_pred"].numpy(), slot["h_src"].numpy()
             own = (lambda v: words(v).copy()) if self.copy_out else words
-            if self.scene is not None:            # written behind the frames, ahead of `done`
-                fs = slot["h_fs"].numpy()
-                for k, (a, b) in enumerate(chunk):
-                    self.scene_scores.append((a, b, int(fs[1, k])))
-                    if fs[0, k]:
-                        self.scene_cuts.append((a, b, int(fs[1, k])))
-            if self.static_guard is not None:     # written behind the frames, ahead of `done`
-                sg, area = slot["h_sg"].numpy(), float(self._dst[0] * self._dst[1])
-            if self.agreement is not None:        # likewise
-                ag, area = slot["h_ag"].numpy(), float(self._dst[0] * self._dst[1])
-            for k, (a, _) in enumerate(chunk):
-                if self.mode == "recursive":
-                    for j in range(npred):
-                        if self.static_guard is not None:
-                            self.static_share.append(int(sg[k * npred + j]) / area)
-                        if self.agreement is not None:
-                            self.agreement_share.append(int(ag[k * npred + j]) / area)
-                        yield own(pred_h[k * npred + j])
-                else:
-                    for _ in range(self.factor):
-                        if self.static_guard is not None:
-                            self.static_share.append(int(sg[k]) / area)
-                        if self.agreement is not None:
-                            self.agreement_share.append(int(ag[k]) / area)
-                        yield own(pred_h[k])
+            if self.scene is not None:
+                self._note_scenes(slot, b.chunk)
+            sg = self._shares(slot["h_sg"], range(b.n * npred)) if self.static_guard is not None else None
+            ag = self._shares(slot["h_ag"], range(b.n * npred)) if self.agreement is not None else None
+            for k, (a, _) in enumerate(b.chunk):
+                for j in range(self.factor):
+                    i = k * npred + j % npred     # reference mode: the pair's one prediction, `factor` times; recursive: its j-th midpoint
+                    if sg is not None:
+                        self.static_share.append(sg[i])
+                    if ag is not None:
+                        self.agreement_share.append(ag[i])
+                    yield own(pred_h[i])
                 yield own(src_h[k]) if (self.quirks or self._resize) else words(frames[a])
 
-        staged = self._stage(self._slots[0], frames, chunks[0]) if chunks else None
-        prev = None
-        for ci, chunk in enumerate(chunks):
-            slot = self._slots[ci & 1]
-            nup, ia, ib = staged
-            n = len(chunk)
-            with torch.cuda.stream(self._pre):
-                # the slot's x was last read by the forward of batch ci - 2 (main) and by the round-trip postprocess of its frames (post)
-                self._pre.wait_event(slot["fwd"])
-                self._pre.wait_event(slot["done"])
-                rs = slot["d_rs"][:nup] if slot["d_rs"] is not None else None
-                rz = slot["p_rs"][:nup] if slot["p_rs"] is not None else rs   # where the preprocess leaves resized bytes; `rs`: they are emitted
-                if self.zero_copy:
-                    x = self._pre_kernel(slot["h_in"][:nup], device=self.device, out=slot["x"][:nup], resized=rz)   # distinct frames, read over PCIe, normalised once
-                    if self.scene is not None:
-                        self._scene_decide(slot, slot["h_in"][:nup], ia, ib)
-                        if not self.quirks and rs is None:
-                            # the bytes a held frame is made of are the staged input rows, which the host restages once `consumed` fires
-                            for k in range(n):
-                                slot["d_src"][k].copy_(slot["h_in"][ia[k]], non_blocking=True)
-                    slot["consumed"].record(self._pre)
-                else:
-                    slot["d_in"][:nup].copy_(slot["h_in"][:nup], non_blocking=True)                       # hipMemcpyAsync pinned -> HBM (SDMA)
-                    slot["consumed"].record(self._pre)
-                    x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=rz)             # distinct frames, normalised once
-                    if self.scene is not None:
-                        self._scene_decide(slot, slot["d_in"][:nup], ia, ib)
-                slot["pre"].record(self._pre)
-                src_here = self.quirks and not self.zero_copy and all(ia[k + 1] == ia[k] + 1 for k in range(n - 1))
-                if rs is not None:
-                    # reference_quirks=False with a resize: every pair's earlier frame leaves as the preprocess kernel resized it
-                    for k in range(n):
-                        slot["h_src"][k].copy_(rs[ia[k]], non_blocking=True)
-                    slot["src"].record(self._pre)
-                if src_here:
-                    # the reference's round trip of every pair's earlier frame (inference.py:187-188) depends on the preprocess only:
-                    # it leaves from this lane, ahead of the forward, instead of queueing behind the predictions at the end of the batch
-                    self._post_kernel(x[ia[0]:ia[0] + n], True, out=slot["d_src"][:n])
-                    slot["h_src"][:n].copy_(slot["d_src"][:n], non_blocking=True)
-                    slot["src"].record(self._pre)
-            main.wait_event(slot["pre"])
-            x1, x2 = self._rows(x, ia), self._rows(x, ib)
-            pred = self._predict(x1, x2)                                      # [n, k, 3, H, W], on the caller's stream
-            held = self._ag                                                   # int32 [n k] on the device, or None
-            slot["fwd"].record(main)
-            with torch.cuda.stream(self._post):
-                self._post.wait_event(slot["fwd"])
-                flat = pred.reshape(-1, *pred.shape[2:])
-                flat.record_stream(self._post)                                # allocated on the caller's stream, read on this one
-                if held is not None:
-                    self._held_to_host(slot, held)
-                if self.quirks and (x1.data_ptr() < slot["x"].data_ptr() or x1.data_ptr() >= slot["x"].data_ptr() + slot["x"].numel() * 4):
-                    x1.record_stream(self._post)                              # a gathered copy (non-consecutive rows), not a view of the slot
-                if self.zero_copy:
-                    self._post_kernel(flat, self.quirks, out=slot["h_pred"][:n * npred])
-                    if self.quirks:
-                        self._post_kernel(x1, True, out=slot["h_src"][:n])
-                else:
-                    self._post_kernel(flat, self.quirks, out=slot["d_pred"][:n * npred])
-                    if self.static_guard is not None:
-                        # every prediction of pair k against the pair's two source frames as emitted; d_in / d_rs are complete: the
-                        # forward waited for `pre`
-                        self._static_hold(slot, slot["d_pred"], rs if rs is not None else slot["d_in"][:nup],
-                                          [(ia[k], ib[k]) for k in range(n) for _ in range(npred)])
-                    if self.scene is None:
-                        slot["h_pred"][:n * npred].copy_(slot["d_pred"][:n * npred], non_blocking=True)   # HBM -> pinned (SDMA)
-                    if self.quirks and not src_here:
-                        self._post_kernel(x1, True, out=slot["d_src"][:n])
-                        slot["h_src"][:n].copy_(slot["d_src"][:n], non_blocking=True)
-                    if src_here:
-                        self._post.wait_event(slot["src"])                    # `done` covers both lanes' writes into the pinned buffers
-                if rs is not None:
-                    self._post.wait_event(slot["src"])
-                if self.scene is not None:
-                    # every source of a held frame is complete here: d_src / h_src (this lane, or the `src` event above), d_rs and d_in (the
-                    # `pre` event the forward waited for).  The prediction frames of a flagged pair become the bytes emitted as its earlier frame
-                    dst = slot["h_pred"] if self.zero_copy else slot["d_pred"]
-                    if self.quirks:
-                        self._scene_hold(slot, dst, slot["h_src"] if self.zero_copy else slot["d_src"], list(range(n)), npred)
-                    elif rs is not None:
-                        self._scene_hold(slot, dst, rs, ia, npred)
-                    elif self.zero_copy:
-                        self._scene_hold(slot, dst, slot["d_src"], list(range(n)), npred)
-                    else:
-                        self._scene_hold(slot, dst, slot["d_in"], ia, npred)
-                    if not self.zero_copy:
-                        slot["h_pred"][:n * npred].copy_(slot["d_pred"][:n * npred], non_blocking=True)   # HBM -> pinned (SDMA), after the hold
-                    slot["h_fs"].copy_(slot["fs"], non_blocking=True)
-                slot["done"].record(self._post)
-            if ci + 1 < len(chunks):                  # host-side staging of the next batch overlaps this batch's compute
-                staged = self._stage(self._slots[(ci + 1) & 1], frames, chunks[ci + 1])
-            if prev is not None:                      # emit the previous batch (its slot is reused only after this)
-                yield from drain(*prev)
-            prev = (slot, chunk)
-        if prev is not None:
-            yield from drain(*prev)
+        yield from self._batches(frames, chunks, pre, forward, post, drain, upload=not self.zero_copy, early=early)
         if not tail or not _emit_tail:       # the stream's final frame belongs to the highest rank (run_chunked: to the last chunk)
             return
         if last_roundtrip and self.quirks:   # skip-branch ending: the reference writes the round-tripped frame
@@ -1247,10 +1299,7 @@ class FrameInterpolator:
         ([len(levels[l]), 3, H, W]); depths[k]: the depth of pair k's tree (a gap of m source intervals: D + ceil(log2 m)).  The recursion and
         the re-normalisation of a midpoint are ``_predict``'s."""
         outs, norm, held = [], {}, []
-        if self._norm is None:
-            self._norm = (torch.tensor(_lib.IMAGENET_MEAN, device=x.device).view(1, 3, 1, 1),
-                          torch.tensor(_lib.IMAGENET_STD, device=x.device).view(1, 3, 1, 1))
-        mean, std = self._norm
+        mean, std = self._norm_constants(x.device)
 
         def node(k, j):
             return x[ia[k]] if j == 0 else x[ib[k]] if j == 1 << depths[k] else norm[(k, j)]
@@ -1330,10 +1379,7 @@ class FrameInterpolator:
             nfr, slot = f1 - f0 + 1, self._slots[bi & 1]
             self._stage(slot, frames, [tuple(range(f0, f1 + 1))])           # waits until the slot's previous upload has been read
             with torch.cuda.stream(self._pre):
-                self._pre.wait_event(slot["fwd"])
-                self._pre.wait_event(slot["done"])
-                slot["d_in"][:nfr].copy_(slot["h_in"][:nfr], non_blocking=True)
-                slot["consumed"].record(self._pre)
+                self._lane_in(slot, nfr)
                 img = self._dedup_image(slot["d_in"][:nfr])
                 cells = _lib.frame_diff_cells(img[:-1], img[1:], depth=depth, shift=shift, out=dd["cells"][:nfr - 1])
                 _lib.duplicate_flags(cells, self.dedup, flags=dd["fs"][0, f0 - lo:f1 - lo], scores=dd["fs"][1, f0 - lo:f1 - lo])
@@ -1363,9 +1409,7 @@ class FrameInterpolator:
             first = next(iter(frames.values()))
         words = (lambda v: v.view(np.uint16)) if self._depth else (lambda v: v)
         self._alloc(first.shape)
-        self.scene_cuts, self.scene_scores = [], []
-        self.duplicates, self.dedup_scores = [], []
-        self.static_share, self.agreement_share = [], []
+        self._reset_reports()
         kept = list(range(a, b + 1)) if b > a else []
         if self.dedup is not None and b > a:
             # the set of forwards depends on the flags: the host reads them before it plans (one wait per run() call)
@@ -1383,7 +1427,6 @@ class FrameInterpolator:
         bp = self.batch_pairs
         chunks = [gaps[i:i + bp] for i in range(0, len(gaps), bp)]
         fmt = _lib.resample_sample_format(self.pixel_format)
-        main = torch.cuda.current_stream(self.device)
         if chunks:
             # the node and emission buffers of a slot hold the largest batch of this run
             sizes = [(sum(len(outs_of[s]) for s, _ in c), sum(len(lv) for s, s2 in c for lv in self.resample_needed(
@@ -1396,82 +1439,62 @@ class FrameInterpolator:
                                  "d_emit": torch.empty(n_emit, *fs, dtype=torch.uint8, device=self.device),
                                  "h_emit": torch.empty(n_emit, *fs, dtype=torch.uint8).pin_memory()})
 
-        def drain(slot, chunk, n_out, first_node, own_node):
-            slot["done"].synchronize()            # this batch's frames have been written into the pinned buffer
+        def pre(b):
+            slot, nup, (ia, ib) = b.slot, b.nup, b.rows
+            b.levels, b.table, b.n_nodes, b.depths = self._resample_batch(b.chunk, outs_of, ia, ib)
+            b.rs = slot["d_rs"][:nup] if slot["d_rs"] is not None else None
+            b.x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=b.rs)
+            if self.scene is not None:
+                self._scene_decide(slot, slot["d_in"][:nup], ia, ib)
+
+        def forward(b):
+            b.preds = self._resample_forwards(b.x, *b.rows, b.levels, b.depths)                       # on the caller's stream
+            b.held = self._ag                                                                         # int32 [n_nodes] on the device, or None
+
+        def post(b):
+            slot, nup, (ia, ib), rs, table = b.slot, b.nup, b.rows, b.rs, b.table
+            if b.held is not None:
+                self._held_to_host(slot, b.held)
+            off = 0
+            for m in b.preds:                                                                         # every node becomes bytes once
+                m.record_stream(self._post)
+                self._post_kernel(m, False, out=slot["d_node"][off:off + m.shape[0]])
+                off += m.shape[0]
+            assert off == b.n_nodes
+            b.first_node = []
+            if self.static_guard is not None and off:
+                # every node frame against its gap's two kept source frames, before the outputs are selected or blended
+                gap_of = [k for lv in b.levels for k, _ in lv]
+                self._static_hold(slot, slot["d_node"], rs if rs is not None else slot["d_in"][:nup], [(ia[k], ib[k]) for k in gap_of])
+                first = {}
+                for i, k in enumerate(gap_of):
+                    first.setdefault(k, i)
+                # an entry's last field is its gap's first staged row, ia[k]: distinct per gap
+                b.first_node = [first[ia.index(e[-1])] for e in table if self._entry_nodes(e)]
+            # the source frames as emitted: the staged bytes, or the bytes the preprocess kernel resized them to
+            assemble = _lib.accumulate_frames if self.shutter is not None else _lib.resample_frames
+            assemble(slot["d_emit"][:len(table)], rs if rs is not None else slot["d_in"][:nup], slot["d_node"][:off] if off else None, table,
+                     flags=slot["fs"][0] if self.scene is not None else None, sample_bytes=fmt[0], depth=fmt[1], shift=fmt[2])
+            slot["h_emit"][:len(table)].copy_(slot["d_emit"][:len(table)], non_blocking=True)         # HBM -> pinned (SDMA)
+            if self.scene is not None:
+                slot["h_fs"].copy_(slot["fs"], non_blocking=True)
+
+        def drain(b):
+            slot = b.slot
             emit_h = slot["h_emit"].numpy()
-            if self.agreement is not None:        # written behind the frames, ahead of `done`: an emitted frame made of node frames has the
-                ag, area = slot["h_ag"].numpy(), float(self._dst[0] * self._dst[1])     # share of the first node frame it is made of
-                self.agreement_share += [int(ag[i]) / area for i in own_node]
-            if self.static_guard is not None:     # written behind the frames, ahead of `done`: an emitted frame made of node frames has its
-                sg, area = slot["h_sg"].numpy(), float(self._dst[0] * self._dst[1])     # gap's share (core depends on the two sources only)
-                self.static_share += [int(sg[i]) / area for i in first_node]
+            if self.agreement is not None:
+                # an emitted frame made of node frames has the share of the first node frame its entry names
+                self.agreement_share += self._shares(slot["h_ag"], [self._entry_nodes(e)[0] for e in b.table if self._entry_nodes(e)])
+            if self.static_guard is not None:
+                # an emitted frame made of node frames has its gap's share (core depends on the two sources only)
+                self.static_share += self._shares(slot["h_sg"], b.first_node)
             own = (lambda v: words(v).copy()) if self.copy_out else words
-            if self.scene is not None:            # written behind the frames, ahead of `done`
-                fs = slot["h_fs"].numpy()
-                for k, (s, s2) in enumerate(chunk):
-                    self.scene_scores.append((s, s2, int(fs[1, k])))
-                    if fs[0, k]:
-                        self.scene_cuts.append((s, s2, int(fs[1, k])))
-            for i in range(n_out):
+            if self.scene is not None:
+                self._note_scenes(slot, b.chunk)
+            for i in range(len(b.table)):
                 yield own(emit_h[i])
 
-        staged = self._stage(self._slots[0], frames, chunks[0]) if chunks else None
-        prev = None
-        for ci, chunk in enumerate(chunks):
-            slot = self._slots[ci & 1]
-            nup, ia, ib = staged
-            levels, table, n_nodes, depths = self._resample_batch(chunk, outs_of, ia, ib)
-            with torch.cuda.stream(self._pre):
-                self._pre.wait_event(slot["fwd"])       # the slot's x was last read by the forwards of batch ci - 2 ...
-                self._pre.wait_event(slot["done"])      # ... and its d_in / d_rs by that batch's assembly
-                rs = slot["d_rs"][:nup] if slot["d_rs"] is not None else None
-                slot["d_in"][:nup].copy_(slot["h_in"][:nup], non_blocking=True)                       # hipMemcpyAsync pinned -> HBM (SDMA)
-                slot["consumed"].record(self._pre)
-                x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=rs)
-                if self.scene is not None:
-                    self._scene_decide(slot, slot["d_in"][:nup], ia, ib)
-                slot["pre"].record(self._pre)
-            main.wait_event(slot["pre"])
-            preds = self._resample_forwards(x, ia, ib, levels, depths)                                     # on the caller's stream
-            held = self._ag                                                                           # int32 [n_nodes] on the device, or None
-            slot["fwd"].record(main)
-            with torch.cuda.stream(self._post):
-                self._post.wait_event(slot["fwd"])
-                if held is not None:
-                    self._held_to_host(slot, held)
-                off = 0
-                for m in preds:                                                                       # every node becomes bytes once
-                    m.record_stream(self._post)
-                    self._post_kernel(m, False, out=slot["d_node"][off:off + m.shape[0]])
-                    off += m.shape[0]
-                assert off == n_nodes
-                first_node = []
-                if self.static_guard is not None and off:
-                    # every node frame against its gap's two kept source frames, before the outputs are selected or blended
-                    gap_of = [k for lv in levels for k, _ in lv]
-                    self._static_hold(slot, slot["d_node"], rs if rs is not None else slot["d_in"][:nup], [(ia[k], ib[k]) for k in gap_of])
-                    first = {}
-                    for i, k in enumerate(gap_of):
-                        first.setdefault(k, i)
-                    # an entry's last field is its gap's first staged row, ia[k]: distinct per gap
-                    first_node = [first[ia.index(e[-1])] for e in table if self._entry_nodes(e)]
-                # the source frames as emitted: the staged bytes, or the bytes the preprocess kernel resized them to
-                assemble = _lib.accumulate_frames if self.shutter is not None else _lib.resample_frames
-                assemble(slot["d_emit"][:len(table)], rs if rs is not None else slot["d_in"][:nup], slot["d_node"][:off] if off else None, table,
-                         flags=slot["fs"][0] if self.scene is not None else None, sample_bytes=fmt[0], depth=fmt[1], shift=fmt[2])
-                slot["h_emit"][:len(table)].copy_(slot["d_emit"][:len(table)], non_blocking=True)     # HBM -> pinned (SDMA)
-                if self.scene is not None:
-                    slot["h_fs"].copy_(slot["fs"], non_blocking=True)
-                slot["done"].record(self._post)
-            if ci + 1 < len(chunks):                  # host-side staging of the next batch overlaps this batch's compute
-                staged = self._stage(self._slots[(ci + 1) & 1], frames, chunks[ci + 1])
-            if prev is not None:
-                yield from drain(*prev)
-            # per emitted frame made of node frames: the first node frame its entry names
-            own_node = [self._entry_nodes(e)[0] for e in table if self._entry_nodes(e)]
-            prev = (slot, chunk, len(table), first_node, own_node)
-        if prev is not None:
-            yield from drain(*prev)
+        yield from self._batches(frames, chunks, pre, forward, post, drain)
         if tail:
             yield self._resized_bytes(frames[last]) if self._resize else words(frames[last])
 
@@ -1506,10 +1529,8 @@ class FrameInterpolator:
             raise ValueError(f"run_chunked: chunk_pairs = {chunk_pairs} with dedup_threshold must be a multiple of dedup_span = {self.dedup_span}: "
                              "every chunk then starts and ends on a frame that is kept regardless, and sees what the whole clip would")
         L, it, held, lo = chunk_pairs * self.interval, iter(frames), [], 0
-        cuts, scores, dups, dscores, shares, ashares = [], [], [], [], [], []
-        self.scene_cuts, self.scene_scores = [], []
-        self.duplicates, self.dedup_scores = [], []
-        self.static_share, self.agreement_share = [], []
+        total = {name: [] for name in self._REPORTS}
+        self._reset_reports()
         while True:
             for f in it:
                 held.append(f)
@@ -1517,19 +1538,15 @@ class FrameInterpolator:
                     break
             final = len(held) < L + 1          # the stream ended inside this chunk (a full chunk is never final: its last frame starts the next)
             if held:
-                self.scene_cuts, self.scene_scores = [], []     # this chunk's own, whatever run() does with them
+                self._reset_reports()                           # this chunk's own, whatever run() does with them
                 # mode "resample": the time grid is global, so a chunk is told where it starts
                 yield from self.run(held, _emit_tail=final, **({"_base": lo} if self.mode == "resample" else {}))
-                cuts += [(a + lo, b + lo, sc) for a, b, sc in self.scene_cuts]
-                scores += [(a + lo, b + lo, sc) for a, b, sc in self.scene_scores]
-                self.scene_cuts, self.scene_scores = list(cuts), list(scores)
-                dups += self.duplicates                         # global indices already: run() was told where the chunk starts
-                dscores += self.dedup_scores
-                self.duplicates, self.dedup_scores = list(dups), list(dscores)
-                shares += self.static_share
-                self.static_share = list(shares)
-                ashares += self.agreement_share
-                self.agreement_share = list(ashares)
+                for name in self._REPORTS:
+                    mine = getattr(self, name)
+                    if name in ("scene_cuts", "scene_scores"):  # the chunk's own frame indices; duplicates / dedup_scores are global already
+                        mine = [(a + lo, b + lo, sc) for a, b, sc in mine]
+                    total[name] += mine
+                    setattr(self, name, list(total[name]))
             if final:
                 return
             held, lo = held[-1:], lo + L
@@ -1538,8 +1555,8 @@ class FrameInterpolator:
         """Scores the model on a clip by the held-out protocol and returns an ``Evaluation``: every target ``t = 1, 1 + every, ...`` with
         ``t <= n - 2`` is interpolated from frames ``t - 1`` and ``t + 1`` and compared with the true frame ``t`` (``evaluation_plan``).
 
-        Everything is decided on the device.  The forwards are batched through the same slots, lanes and events as ``run()``
-        (``batch_pairs`` targets per batch); the prediction is turned into bytes by the postprocess kernel with ``denormalize`` off - the
+        Everything is decided on the device.  The forwards are batched through ``run()``'s slots and lanes, by the same driver (``_batches``;
+        ``batch_pairs`` targets per batch); the prediction is turned into bytes by the postprocess kernel with ``denormalize`` off - the
         model's output lies in [0, 1], and de-normalising it as ``reference_quirks`` does would score the reference's quirk instead of the
         model - and scored by ``emavfi_frame_metrics_u8`` against the bytes of frame ``t`` as they sit on the device at the size the
         model runs at (with ``scale`` / ``size``: the device-resized bytes).  ``pixel_format="nv12"``: the Y planes are scored as a
@@ -1568,7 +1585,6 @@ class FrameInterpolator:
         nv12 = self._yuv8                         # the Y plane is the first H rows of NV12 and of planar frames alike
         H, W = self._dst
         result = Evaluation((H, W), 1 if nv12 else first.shape[2])
-        main = torch.cuda.current_stream(self.device)
         bp = self.batch_pairs
         chunks = [[(a, t, b) for t, a, b in plan[i:i + bp]] for i in range(0, len(plan), bp)]
 
@@ -1576,44 +1592,29 @@ class FrameInterpolator:
             """the scored image of frames at the size the model runs at: the Y plane of NV12 frames as one channel"""
             return buf[:, :H].unsqueeze(-1) if nv12 else buf
 
-        def drain(slot, chunk):
-            slot["done"].synchronize()            # this batch's metric words have been written into the pinned buffer
-            words = slot["h_met"].numpy()
-            for k, (_, t, _) in enumerate(chunk):
+        def pre(b):
+            slot, nup = b.slot, b.nup
+            b.rs = slot["e_rs"][:nup] if slot["e_rs"] is not None else None
+            b.x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=b.rs)
+
+        def forward(b):
+            with torch.no_grad():
+                b.pred = self._forward(self._rows(b.x, b.rows[0]), self._rows(b.x, b.rows[2]))   # [n, 3, H, W], on the caller's stream
+
+        def post(b):
+            slot, n, it = b.slot, b.n, b.rows[1]
+            b.pred.record_stream(self._post)
+            self._post_kernel(b.pred, False, out=slot["d_pred"][:n])
+            truth = image(b.rs if b.rs is not None else slot["d_in"][:b.nup])
+            step = it[1] - it[0] if n > 1 else 1                          # the targets' rows are an arithmetic run: frames are staged in order
+            _lib.frame_metrics_u8(image(slot["d_pred"][:n]), truth[it[0]:it[-1] + 1:step], out=slot["met"][:n])
+            slot["h_met"][:n].copy_(slot["met"][:n], non_blocking=True)
+
+        def drain(b):                             # only the metric words came back
+            words = b.slot["h_met"].numpy()
+            for k, (_, t, _) in enumerate(b.chunk):
                 result.add(t, words[k].tolist())
 
-        staged = self._stage(self._slots[0], frames, chunks[0])
-        prev = None
-        for ci, chunk in enumerate(chunks):
-            slot = self._slots[ci & 1]
-            nup, ia, it, ib = staged
-            n = len(chunk)
-            with torch.cuda.stream(self._pre):
-                self._pre.wait_event(slot["fwd"])
-                self._pre.wait_event(slot["done"])     # also: the metric kernel of batch ci - 2 has read d_in / e_rs
-                rs = slot["e_rs"][:nup] if slot["e_rs"] is not None else None
-                slot["d_in"][:nup].copy_(slot["h_in"][:nup], non_blocking=True)
-                slot["consumed"].record(self._pre)
-                x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=rs)
-                slot["pre"].record(self._pre)
-            main.wait_event(slot["pre"])
-            x1, x2 = self._rows(x, ia), self._rows(x, ib)
-            with torch.no_grad():
-                pred = self._forward(x1, x2)                                     # [n, 3, H, W], on the caller's stream
-            slot["fwd"].record(main)
-            with torch.cuda.stream(self._post):
-                self._post.wait_event(slot["fwd"])
-                pred.record_stream(self._post)
-                self._post_kernel(pred, False, out=slot["d_pred"][:n])
-                truth = image(rs if rs is not None else slot["d_in"][:nup])
-                step = it[1] - it[0] if n > 1 else 1                          # the targets' rows are an arithmetic run: frames are staged in order
-                _lib.frame_metrics_u8(image(slot["d_pred"][:n]), truth[it[0]:it[-1] + 1:step], out=slot["met"][:n])
-                slot["h_met"][:n].copy_(slot["met"][:n], non_blocking=True)
-                slot["done"].record(self._post)
-            if ci + 1 < len(chunks):
-                staged = self._stage(self._slots[(ci + 1) & 1], frames, chunks[ci + 1])
-            if prev is not None:
-                drain(*prev)
-            prev = (slot, chunk)
-        drain(*prev)
+        for _ in self._batches(frames, chunks, pre, forward, post, drain):
+            pass
         return result
