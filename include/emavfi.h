@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_downscale_f32, emavfi_upsample_flow_f32, emavfi_forward_flow, emavfi_forward_given_flow (and their two launch lists) added (the flow estimated on frames reduced by 2, 4 or 8 for motion beyond seven pixels, the forward split at its flow; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_accumulate_frames added (motion blur from a shutter angle: every output frame the weighted integer mean of the node frames inside its exposure window, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_agreement_guard_f32 added (where the two time directions of the ensemble disagree the plain blend of the source frames is emitted, decided on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_transfer_table, emavfi_transfer_table_check, emavfi_accumulate_frames_linear added (blended and motion-blurred frames mixed in linear light through a transfer table, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_downscale_f32, emavfi_upsample_flow_f32, emavfi_forward_flow, emavfi_forward_given_flow (and their two launch lists) added (the flow estimated on frames reduced by 2, 4 or 8 for motion beyond seven pixels, the forward split at its flow; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_accumulate_frames added (motion blur from a shutter angle: every output frame the weighted integer mean of the node frames inside its exposure window, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_agreement_guard_f32 added (where the two time directions of the ensemble disagree the plain blend of the source frames is emitted, decided on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -601,7 +601,7 @@ int emavfi_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, con
  *   Per sample out = (sum w_j s_j + S / 2) / S, s_j the sample of node j: a byte, or (word >> shift) & (2^depth - 1) of a 16-bit
  *     little-endian word, written back as v << shift.  The largest intermediate is 65535 * 65535 + 32767 < 2^32: unsigned 32-bit holds
  *     everything.  The mean acts on the frames AS EMITTED, the same arithmetic for every pixel format, as the blend above; it averages the
- *     coded samples (no linear light).  A single tap copies its frame byte for byte; a single-tap output with j = 0 is the source frame.
+ *     coded samples (in light: emavfi_accumulate_frames_linear below).  A single tap copies its frame byte for byte; a single-tap output with j = 0 is the source frame.
  *   Scene cuts.  Every output of a flagged pair is source frame s, those with r = 0 and those whose taps reach node G (the next shot) included.
  *   The last frame.  The output that falls on the last source frame of a clip has no pair to integrate over: it is that frame itself.
  *   Needed nodes of a pair: the taps of its outputs, closed under parents; only these are computed.
@@ -628,6 +628,70 @@ typedef struct { unsigned n, f, h; unsigned tap[EMAVFI_ACCUMULATE_MAX_TAPS]; uns
 int emavfi_accumulate_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
                              const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_accumulate_entry *table,
                              const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift, void *stream);
+
+/* Linear light.  The blend and the shutter above average CODED samples.  A camera integrates light, and a coded sample is a gamma-like
+ * function of light: a bright object blurred over a dark ground comes out too dark and too thin, and an even mix of black and white comes
+ * out as code 128 where the light says 188 (sRGB).  With a transfer table the same taps are averaged in light, on the device.  The reference
+ * has nothing of the kind; this is an addition, off unless asked for.
+ *
+ * LINEAR LIGHT DEFINITION (the one place).  This is the project's own definition: it claims agreement with no outside tool.  It extends the
+ * temporal resample and shutter definitions above; all device arithmetic is integer, `/` is floor division, floating point only builds a
+ * table on the host: oracle and device agree bit for bit.
+ *   Table.  lin[0 .. 2^depth - 1], unsigned 32-bit, depth 8, 10 or 12: lin[v] = BIAS + round(ONE g(x)), ONE = 2^28, BIAS = 2^26,
+ *     x = (v - lo) / (hi - lo), (lo, hi) = (0, 2^depth - 1) at full range and (16, 235) << (depth - 8) at limited range.  g is the inverse
+ *     transfer function on x >= 0 and -g(-x) on x < 0 (the odd extension): codes below black and above white keep distinct, ordered values.
+ *     Built in:  EMAVFI_TRANSFER_SRGB: x / 12.92 for x <= 0.04045, else ((x + 0.055) / 1.055)^2.4.  EMAVFI_TRANSFER_BT709: the inverse OETF
+ *     with BT.2020's precise constants alpha = 1.09929682680944, beta = 0.018053968510807: x / 4.5 below 4.5 beta, else
+ *     ((x + alpha - 1) / alpha)^(1 / 0.45) (the rounded 1.099 / 0.081 are discontinuous at the knee: the 12-bit full-range table would not be
+ *     monotone).  EMAVFI_TRANSFER_HLG: the inverse HLG OETF, x^2 / 3 for x <= 0.5, else (exp((x - c) / a) + b) / 12 with a = 0.17883277,
+ *     b = 0.28466892, c = 0.55991073.  A VALID table is strictly increasing with every value below 2^30.  The three built-ins are valid at
+ *     depths 8, 10 and 12 in both ranges (smallest step 5: HLG, 12-bit, full range; largest value 520 767 148); lin[lo] = BIAS exactly, lin[hi]
+ *     within 8 of BIAS + ONE (HLG's rounded constants: + 7).  Depth 16 is refused: 256 KiB of table exceed the 160 KiB of LDS, and the built-ins
+ *     lose strictness there.  PQ and a pure power law lose it at 12 bits and are not built in; the entry takes any table that passes the check.
+ *   Encode.  enc(L) = the largest v with v = 0 or lin[v - 1] + lin[v] <= 2 L: the code nearest in light, a tie going up, found by a
+ *     depth-step binary search.  enc(lin[v]) = v for every valid table.
+ *   Mean.  For an entry with taps (j, w_j), S = sum w_j <= 65535, every sample below linear_bytes is
+ *     out = enc((sum w_j lin[s_j] + S / 2) / S); the largest intermediate, 65535 * (2^30 - 1) + 32767, is below 2^46: unsigned 64-bit.  A
+ *     sample is extracted and written back as in the shutter definition: (word >> shift) & mask, then v << shift.
+ *   linear_bytes.  The first linear_bytes bytes of every frame are mixed in light, the rest by the shutter definition's coded mean, word for
+ *     word.  A multiple of sample_bytes, at most frame_bytes.  bgr24: the whole frame.  NV12, P010 / P012 and the planar formats: the Y
+ *     plane, which comes first in the emitted frame; chroma stays coded.  For Y'CbCr THIS IS A LUMA-LINEAR APPROXIMATION, exact for greys:
+ *     true RGB linear light for 4:2:0 would need chroma resampling and is out of scope.
+ *   Copies.  As above: a flagged hold copies srcs[h], a single tap copies its frame byte for byte; an entry never reads (nor forms the
+ *     address of) a frame it does not use.
+ *   Consequences.  Taps that all hold sample v give v.  linear_bytes = 0 is emavfi_accumulate_frames byte for byte.  The affine table
+ *     lin[v] = BIAS + 65536 v reproduces the coded mean bit for bit (S < 65536 keeps every tie where it was).
+ *   Known answers, table: taps (sample, weight) -> linear light (coded mean):  sRGB 8-bit full: (0,1) (255,1) -> 188 (128);
+ *     (0,3) (255,1) -> 137 (64).  bt709 8-bit limited: (16,1) (235,1) -> 170 (126);  (16,3) (235,1) -> 123 (71).
+ *
+ * emavfi_transfer_table builds a built-in table into lin_host (HOST memory, 2^depth words; pure host code).  EMAVFI_E_ARG: an unknown
+ *   transfer, a depth outside {8, 10, 12}, a null pointer.
+ * emavfi_transfer_table_check checks a host table: strictly increasing, every value below 2^30.  EMAVFI_E_ARG, the message naming the first
+ *   offending index; also a depth outside {8, 10, 12} and a null pointer.
+ * emavfi_accumulate_frames_linear is emavfi_accumulate_frames - the same entry struct, the same HOST table that travels as kernel arguments,
+ *   EMAVFI_ACCUMULATE_LAUNCH_CAP entries per launch, every one of its refusals - plus `lin`, a DEVICE pointer (4-byte aligned) to the 2^depth
+ *   words of a table, and linear_bytes.  It refuses as well: a null or misaligned lin, a depth outside {8, 10, 12}, linear_bytes above
+ *   frame_bytes or no multiple of sample_bytes.  Never an abort; nothing is allocated, nothing synchronises, all work goes on `stream`.
+ *   The device table is NOT validated on the device: the contract is that it passed emavfi_transfer_table_check.  The kernel is memory-safe
+ *   for ANY table content: the decode index is masked to 2^depth, the search is bounded to the table.  A table that is not valid gives wrong
+ *   samples and never an out-of-range access.
+ * The kernel keeps the coded kernel's shape: grid (32 KiB pieces of a frame, entries of this launch), 256 threads, 16-byte accesses where
+ *   every frame address an entry uses is 16-byte aligned, bytes / words otherwise.  A workgroup first copies lin into LDS (1, 4 or 16 KiB);
+ *   decode is one LDS gather per sample and tap, encode `depth` steps over LDS.  A 16-byte piece across linear_bytes goes sample by sample,
+ *   each by its own rule.  All forms run the same per-element functions (csrc/light_elem.h); the 46-bit quotient is three steps of schoolbook
+ *   division in base 2^16 over shutter_div, proven equal to `/` on unsigned long long by tests/host/host_check_light.cpp. */
+#define EMAVFI_TRANSFER_SRGB 0
+#define EMAVFI_TRANSFER_BT709 1
+#define EMAVFI_TRANSFER_HLG 2
+#define EMAVFI_LIGHT_ONE (1u << 28)
+#define EMAVFI_LIGHT_BIAS (1u << 26)
+#define EMAVFI_LIGHT_LIMIT (1u << 30)
+int emavfi_transfer_table(int transfer, int depth, int full_range, unsigned *lin_host);
+int emavfi_transfer_table_check(const unsigned *lin_host, int depth);
+int emavfi_accumulate_frames_linear(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
+                                    const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_accumulate_entry *table,
+                                    const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift,
+                                    const unsigned *lin, size_t linear_bytes, void *stream);
 
 /* Duplicate frames.  The resampler above puts every output frame at its true time and assumes that every INPUT frame sits at its true time
  * too.  24 fps film in a 30 fps stream, animation drawn on twos, screen captures and anything that went through a frame-rate filter break

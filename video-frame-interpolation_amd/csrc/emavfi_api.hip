@@ -6,6 +6,7 @@
 #include "misc_kernels.h"
 #include "resample_elem.h"
 #include "shutter_elem.h"
+#include "light_elem.h"
 #include "dedup_elem.h"
 #include "static_elem.h"
 #include "ensemble_elem.h"
@@ -15,6 +16,7 @@
 #include "conv_first.inl"
 
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
@@ -1850,11 +1852,12 @@ int emavfi_resample_frames(unsigned char *dst, size_t dst_stride, int n_out, con
 static_assert(sizeof(emavfi_accumulate_entry) == sizeof(AccumulateEntry) && EMAVFI_ACCUMULATE_LAUNCH_CAP == SHUTTER_CAP &&
               EMAVFI_ACCUMULATE_MAX_TAPS == SHUTTER_MAX_TAPS, "header, misc_kernels.h and shutter_elem.h disagree");
 
-int emavfi_accumulate_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
-                             const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_accumulate_entry *table,
-                             const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift, void *stream)
+// what emavfi_accumulate_frames and emavfi_accumulate_frames_linear refuse alike: everything but the light table
+static int accumulate_check(const char *what, const unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs,
+                            size_t src_stride, int n_srcs, const unsigned char *nodes, size_t node_stride, int n_nodes,
+                            const emavfi_accumulate_entry *table, const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes,
+                            int depth, int shift)
 {
-    const char *const what = "accumulate_frames";
     if (const int rc = resample_pools_check(what, dst, dst_stride, n_out, srcs, src_stride, n_srcs, nodes, node_stride, n_nodes, table, flags,
                                             n_flags, frame_bytes, sample_bytes, depth, shift))
         return rc;
@@ -1877,9 +1880,90 @@ int emavfi_accumulate_frames(unsigned char *dst, size_t dst_stride, int n_out, c
         if (e.f != 0 && e.h >= (unsigned)n_srcs)
             return fail(EMAVFI_E_ARG, "%s: table[%d].h = %u is outside the srcs pool of %d frames", what, k, e.h, n_srcs);
     }
+    return EMAVFI_OK;
+}
+
+int emavfi_accumulate_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
+                             const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_accumulate_entry *table,
+                             const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift, void *stream)
+{
+    const char *const what = "accumulate_frames";
+    if (const int rc = accumulate_check(what, dst, dst_stride, n_out, srcs, src_stride, n_srcs, nodes, node_stride, n_nodes, table, flags,
+                                        n_flags, frame_bytes, sample_bytes, depth, shift))
+        return rc;
     EMAVFI_TRY(launch_accumulate_frames(dst, dst_stride, n_out, srcs, src_stride, nodes, node_stride,
                                         reinterpret_cast<const AccumulateEntry *>(table), flags, frame_bytes, sample_bytes, depth, shift,
                                         (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+// ---- linear light (include/emavfi.h, "LINEAR LIGHT DEFINITION"): the tables are built and checked on the host, in double and in integers
+static_assert(EMAVFI_LIGHT_ONE == LIGHT_ONE && EMAVFI_LIGHT_BIAS == LIGHT_BIAS && EMAVFI_LIGHT_LIMIT == LIGHT_LIMIT,
+              "header and light_elem.h disagree");
+
+// the inverse transfer function on x >= 0
+static double light_inverse(int transfer, double x)
+{
+    if (transfer == EMAVFI_TRANSFER_SRGB) return x <= 0.04045 ? x / 12.92 : pow((x + 0.055) / 1.055, 2.4);
+    if (transfer == EMAVFI_TRANSFER_BT709) {
+        const double alpha = 1.09929682680944, beta = 0.018053968510807;
+        return x < 4.5 * beta ? x / 4.5 : pow((x + alpha - 1.0) / alpha, 1.0 / 0.45);
+    }
+    const double a = 0.17883277, b = 0.28466892, c = 0.55991073;     // EMAVFI_TRANSFER_HLG
+    return x <= 0.5 ? x * x / 3.0 : (exp((x - c) / a) + b) / 12.0;
+}
+
+static bool light_depth_ok(int depth) { return depth == 8 || depth == 10 || depth == 12; }
+
+int emavfi_transfer_table(int transfer, int depth, int full_range, unsigned *lin_host)
+{
+    const char *const what = "transfer_table";
+    if (transfer != EMAVFI_TRANSFER_SRGB && transfer != EMAVFI_TRANSFER_BT709 && transfer != EMAVFI_TRANSFER_HLG)
+        return fail(EMAVFI_E_ARG, "%s: transfer = %d (EMAVFI_TRANSFER_SRGB, _BT709 or _HLG expected)", what, transfer);
+    if (!light_depth_ok(depth)) return fail(EMAVFI_E_ARG, "%s: depth = %d (depth must be 8, 10 or 12)", what, depth);
+    if (!lin_host) return fail(EMAVFI_E_ARG, "%s: null pointer lin_host", what);
+    const int lo = full_range ? 0 : 16 << (depth - 8), hi = full_range ? (1 << depth) - 1 : 235 << (depth - 8);
+    for (int v = 0; v < 1 << depth; ++v) {
+        const double x = (double)(v - lo) / (double)(hi - lo);
+        const double g = x < 0.0 ? -light_inverse(transfer, -x) : light_inverse(transfer, x);
+        lin_host[v] = (unsigned)((long long)EMAVFI_LIGHT_BIAS + llround((double)EMAVFI_LIGHT_ONE * g));
+    }
+    return EMAVFI_OK;
+}
+
+int emavfi_transfer_table_check(const unsigned *lin_host, int depth)
+{
+    const char *const what = "transfer_table_check";
+    if (!light_depth_ok(depth)) return fail(EMAVFI_E_ARG, "%s: depth = %d (depth must be 8, 10 or 12)", what, depth);
+    if (!lin_host) return fail(EMAVFI_E_ARG, "%s: null pointer lin_host", what);
+    for (int v = 0; v < 1 << depth; ++v) {
+        if (lin_host[v] >= EMAVFI_LIGHT_LIMIT) return fail(EMAVFI_E_ARG, "%s: lin[%d] = %u is not below 2^30", what, v, lin_host[v]);
+        if (v > 0 && lin_host[v] <= lin_host[v - 1])
+            return fail(EMAVFI_E_ARG, "%s: lin[%d] = %u is not above lin[%d] = %u (the table must be strictly increasing)", what, v, lin_host[v],
+                        v - 1, lin_host[v - 1]);
+    }
+    return EMAVFI_OK;
+}
+
+int emavfi_accumulate_frames_linear(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride, int n_srcs,
+                                    const unsigned char *nodes, size_t node_stride, int n_nodes, const emavfi_accumulate_entry *table,
+                                    const unsigned *flags, int n_flags, size_t frame_bytes, int sample_bytes, int depth, int shift,
+                                    const unsigned *lin, size_t linear_bytes, void *stream)
+{
+    const char *const what = "accumulate_frames_linear";
+    if (const int rc = accumulate_check(what, dst, dst_stride, n_out, srcs, src_stride, n_srcs, nodes, node_stride, n_nodes, table, flags,
+                                        n_flags, frame_bytes, sample_bytes, depth, shift))
+        return rc;
+    if (!light_depth_ok(depth))
+        return fail(EMAVFI_E_ARG, "%s: depth = %d (linear light takes depth 8, 10 or 12: a table of 2^16 words does not fit LDS)", what, depth);
+    if (!lin) return fail(EMAVFI_E_ARG, "%s: null pointer lin", what);
+    if ((uintptr_t)lin & 3) return fail(EMAVFI_E_ARG, "%s: the u32 pointer lin must be 4-byte aligned", what);
+    if (linear_bytes > frame_bytes) return fail(EMAVFI_E_ARG, "%s: linear_bytes %zu is above frame_bytes %zu", what, linear_bytes, frame_bytes);
+    if (linear_bytes % (size_t)sample_bytes)
+        return fail(EMAVFI_E_ARG, "%s: linear_bytes %zu is not a multiple of sample_bytes %d", what, linear_bytes, sample_bytes);
+    EMAVFI_TRY(launch_accumulate_frames_linear(dst, dst_stride, n_out, srcs, src_stride, nodes, node_stride,
+                                               reinterpret_cast<const AccumulateEntry *>(table), flags, frame_bytes, sample_bytes, depth, shift,
+                                               lin, linear_bytes, (hipStream_t)stream), what);
     return EMAVFI_OK;
 }
 

@@ -125,6 +125,12 @@ struct AccumulateEntry { unsigned n, f, h; unsigned tap[33]; unsigned w[33]; }; 
 int launch_accumulate_frames(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride,
                              const unsigned char *nodes, size_t node_stride, const AccumulateEntry *table, const unsigned *flags,
                              size_t frame_bytes, int sample_bytes, int depth, int shift, hipStream_t s);
+// the same with the first linear_bytes bytes of every frame averaged in light (include/emavfi.h, "LINEAR LIGHT DEFINITION"): arguments
+// already validated (depth 8, 10 or 12); `lin` is a DEVICE pointer to 2^depth words
+int launch_accumulate_frames_linear(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride,
+                                    const unsigned char *nodes, size_t node_stride, const AccumulateEntry *table, const unsigned *flags,
+                                    size_t frame_bytes, int sample_bytes, int depth, int shift, const unsigned *lin, size_t linear_bytes,
+                                    hipStream_t s);
 // static regions held on the device (include/emavfi.h, "STATIC REGION DEFINITION"): arguments already validated; `table` is a HOST pointer, read
 // before the call returns and passed on as kernel arguments, STATIC_CAP (static_elem.h) entries per launch; `counts` may be null
 struct StaticEntry { unsigned a, b; };   // emavfi_static_entry

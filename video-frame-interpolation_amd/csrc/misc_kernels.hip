@@ -5,6 +5,7 @@
 #include "scene_elem.h"
 #include "resample_elem.h"
 #include "shutter_elem.h"
+#include "light_elem.h"
 #include "dedup_elem.h"
 #include "static_elem.h"
 #include "ensemble_elem.h"
@@ -2432,6 +2433,168 @@ int launch_accumulate_frames(unsigned char *dst, size_t dst_stride, int n_out, c
         }
         if (sample_bytes == 1) accumulate_frames_kernel<1><<<dim3(pieces, (unsigned)n), 256, 0, s>>>(p);
         else accumulate_frames_kernel<2><<<dim3(pieces, (unsigned)n), 256, 0, s>>>(p);
+        if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Shutter accumulation in linear light: the first linear_bytes bytes of every output frame are averaged in light, the rest as above
+// (include/emavfi.h, "LINEAR LIGHT DEFINITION"; per-element functions: light_elem.h, and shutter_elem.h for the coded rest).
+//   accumulate_linear_kernel   the grid, the table as kernel arguments, the copy of a held or single-tap entry and the choice of 16-byte or
+//                              byte / word accesses are accumulate_frames_kernel's.  A workgroup that mixes first copies the table `lin`
+//                              (2^depth words: 1, 4 or 16 KiB of the CU's 160 KiB) into LDS, 256 threads striding over it; one barrier.
+//                              Decode is one LDS gather per sample and tap, its index masked to the table; the 16 (or 8) sums of a lane
+//                              are 64-bit; the division by S is light_div's three multiplies; encode is a `depth`-step search, two
+//                              neighbouring LDS words per step.  A 16-byte piece lies below linear_bytes (light), at or above it (the
+//                              coded mean, through accumulate_taps) or across it: then, and in the byte / word forms, every sample
+//                              goes alone by the rule of its own offset.  No address depends on what the table holds.
+// ------------------------------------------------------------------------------------------
+struct AccumulateLinearArgs {
+    AccumulateArgs a;
+    const unsigned *lin;             // device: 2^depth words
+    size_t linear_bytes;
+    int depth;
+};
+static_assert(sizeof(AccumulateLinearArgs) <= 4096, "the table must fit the kernel argument segment");
+
+// the sample at byte offset x of the entry's output: in light below linear_bytes, else the coded mean
+template <int SB>
+__device__ __forceinline__ unsigned accumulate_linear_sample(const AccumulateLinearArgs &p, const AccumulateEntry &e, const unsigned *lin,
+                                                             size_t x, unsigned S, unsigned M)
+{
+    const AccumulateArgs &a = p.a;
+    const unsigned n = e.n;
+    if (x < p.linear_bytes) {
+        unsigned long long sum = 0ull;
+        for (unsigned t = 0; t < n; ++t) {
+            const unsigned char *f = accumulate_frame(a, e.tap[t]) + x;
+            const unsigned v = SB == 1 ? (unsigned)*f : shutter_sample(*reinterpret_cast<const unsigned short *>(f), a.mask, a.shift);
+            sum += (unsigned long long)(e.w[t] & 65535u) * lin[v & a.mask];
+        }
+        return light_enc(light_mean(sum, S, M), lin, p.depth) << a.shift;
+    }
+    unsigned sum = 0u;
+    for (unsigned t = 0; t < n; ++t) {
+        const unsigned char *f = accumulate_frame(a, e.tap[t]) + x;
+        sum += e.w[t] * (SB == 1 ? (unsigned)*f : shutter_sample(*reinterpret_cast<const unsigned short *>(f), a.mask, a.shift));
+    }
+    return shutter_mean(sum, S, M) << a.shift;
+}
+
+// taps t0 .. t0 + K - 1 of an entry into the light sums of the 16 bytes at `at`: K loads issued, then used
+template <int SB, int K>
+__device__ __forceinline__ void accumulate_linear_taps(const AccumulateArgs &p, const AccumulateEntry &e, const unsigned *lin, unsigned t0,
+                                                       size_t at, LightSums &ax, LightSums &ay, LightSums &az, LightSums &aw)
+{
+    uint4 v[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) v[i] = *reinterpret_cast<const uint4 *>(accumulate_frame(p, e.tap[t0 + i]) + at);
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        const unsigned w = e.w[t0 + i];
+        light_add_dword(ax, v[i].x, w, lin, SB, p.mask, p.shift);
+        light_add_dword(ay, v[i].y, w, lin, SB, p.mask, p.shift);
+        light_add_dword(az, v[i].z, w, lin, SB, p.mask, p.shift);
+        light_add_dword(aw, v[i].w, w, lin, SB, p.mask, p.shift);
+    }
+}
+
+template <int SB>   // sample_bytes
+__global__ __launch_bounds__(256) void accumulate_linear_kernel(AccumulateLinearArgs pl)
+{
+    __shared__ unsigned lin[SB == 1 ? 256 : 4096];                    // 2^depth words: depth 8 at bytes, 10 or 12 at words
+    const AccumulateArgs &p = pl.a;
+    const AccumulateEntry &e = p.e[blockIdx.y];                       // uniform: read where it lies, among the kernel arguments
+    unsigned char *d = p.dst + (size_t)blockIdx.y * p.dst_stride;
+    const size_t lo = (size_t)blockIdx.x * HOLD_PIECE, hi = lo + HOLD_PIECE < p.frame_bytes ? lo + HOLD_PIECE : p.frame_bytes;
+    size_t x = lo;
+    const bool held = p.flags && e.f && p.flags[e.f - 1];
+    const unsigned n = e.n;
+    if (held || n == 1u) {                                            // one frame, byte for byte: source frame h, or the only tap
+        const unsigned char *a = accumulate_frame(p, held ? e.h : e.tap[0]);
+        if ((((uintptr_t)d | (uintptr_t)a) & 15) == 0) {
+            const size_t nv = (hi - lo) >> 4;
+            for (size_t q = threadIdx.x; q < nv; q += 256) reinterpret_cast<uint4 *>(d + lo)[q] = reinterpret_cast<const uint4 *>(a + lo)[q];
+            x += nv << 4;
+        }
+        for (x += threadIdx.x; x < hi; x += 256) d[x] = a[x];
+        return;
+    }
+    if (lo < pl.linear_bytes) {                                       // uniform: a piece wholly in the coded rest needs no table
+        const unsigned words = 1u << pl.depth, cap = SB == 1 ? 256u : 4096u;
+        for (unsigned i = threadIdx.x; i < words && i < cap; i += 256) lin[i] = pl.lin[i];
+        __syncthreads();
+    }
+    const unsigned S = p.sum[blockIdx.y], M = p.magic[blockIdx.y];
+    uintptr_t bits = (uintptr_t)d;
+    for (unsigned t = 0; t < n; ++t) bits |= (uintptr_t)accumulate_frame(p, e.tap[t]);
+    if ((bits & 15) == 0) {
+        const size_t nv = (hi - lo) >> 4;
+        for (size_t q = threadIdx.x; q < nv; q += 256) {
+            const size_t at = lo + (q << 4);
+            uint4 r;
+            unsigned t = 0;
+            if (at + 16 <= pl.linear_bytes) {
+                LightSums ax{}, ay{}, az{}, aw{};                     // one per dword of the lane's 16 bytes
+                for (; t + SHUTTER_FLIGHT <= n; t += SHUTTER_FLIGHT) accumulate_linear_taps<SB, SHUTTER_FLIGHT>(p, e, lin, t, at, ax, ay, az, aw);
+                if (n - t == 3u) accumulate_linear_taps<SB, 3>(p, e, lin, t, at, ax, ay, az, aw);
+                else if (n - t == 2u) accumulate_linear_taps<SB, 2>(p, e, lin, t, at, ax, ay, az, aw);
+                else if (n - t == 1u) accumulate_linear_taps<SB, 1>(p, e, lin, t, at, ax, ay, az, aw);
+                r.x = light_mean_dword(ax, S, M, lin, SB, pl.depth, p.shift);
+                r.y = light_mean_dword(ay, S, M, lin, SB, pl.depth, p.shift);
+                r.z = light_mean_dword(az, S, M, lin, SB, pl.depth, p.shift);
+                r.w = light_mean_dword(aw, S, M, lin, SB, pl.depth, p.shift);
+            } else if (at >= pl.linear_bytes) {
+                ShutterSums ax{}, ay{}, az{}, aw{};
+                for (; t + SHUTTER_FLIGHT <= n; t += SHUTTER_FLIGHT) accumulate_taps<SB, SHUTTER_FLIGHT>(p, e, t, at, ax, ay, az, aw);
+                if (n - t == 3u) accumulate_taps<SB, 3>(p, e, t, at, ax, ay, az, aw);
+                else if (n - t == 2u) accumulate_taps<SB, 2>(p, e, t, at, ax, ay, az, aw);
+                else if (n - t == 1u) accumulate_taps<SB, 1>(p, e, t, at, ax, ay, az, aw);
+                r.x = shutter_mean_dword(ax, S, M, SB, p.shift);
+                r.y = shutter_mean_dword(ay, S, M, SB, p.shift);
+                r.z = shutter_mean_dword(az, S, M, SB, p.shift);
+                r.w = shutter_mean_dword(aw, S, M, SB, p.shift);
+            } else {                                                  // the one piece of a frame that lies across linear_bytes
+                unsigned o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int k = 0; k < 16; k += SB) o[k >> 2] |= accumulate_linear_sample<SB>(pl, e, lin, at + k, S, M) << (8 * (k & 3));
+                r.x = o[0]; r.y = o[1]; r.z = o[2]; r.w = o[3];
+            }
+            *reinterpret_cast<uint4 *>(d + at) = r;
+        }
+        x += nv << 4;
+    }
+    if (SB == 1) {
+        for (x += threadIdx.x; x < hi; x += 256) d[x] = (unsigned char)accumulate_linear_sample<1>(pl, e, lin, x, S, M);
+    } else {                                                          // frame_bytes, lo and every frame address are even
+        for (x += 2 * (size_t)threadIdx.x; x < hi; x += 512)
+            *reinterpret_cast<unsigned short *>(d + x) = (unsigned short)accumulate_linear_sample<2>(pl, e, lin, x, S, M);
+    }
+}
+
+int launch_accumulate_frames_linear(unsigned char *dst, size_t dst_stride, int n_out, const unsigned char *srcs, size_t src_stride,
+                                    const unsigned char *nodes, size_t node_stride, const AccumulateEntry *table, const unsigned *flags,
+                                    size_t frame_bytes, int sample_bytes, int depth, int shift, const unsigned *lin, size_t linear_bytes,
+                                    hipStream_t s)
+{
+    AccumulateLinearArgs pl{};
+    AccumulateArgs &p = pl.a;
+    pl.lin = lin; pl.linear_bytes = linear_bytes; pl.depth = depth;
+    p.dst_stride = dst_stride; p.srcs = srcs; p.src_stride = src_stride; p.nodes = nodes; p.node_stride = node_stride;
+    p.flags = flags; p.frame_bytes = frame_bytes; p.shift = shift; p.mask = (1u << depth) - 1u;
+    const unsigned pieces = (unsigned)((frame_bytes + HOLD_PIECE - 1) / HOLD_PIECE);
+    for (int first = 0; first < n_out; first += SHUTTER_CAP) {
+        const int n = n_out - first < SHUTTER_CAP ? n_out - first : SHUTTER_CAP;
+        p.dst = dst + (size_t)first * dst_stride;
+        for (int k = 0; k < n; ++k) {
+            p.e[k] = table[first + k];
+            p.sum[k] = 0u;
+            for (unsigned t = 0; t < p.e[k].n; ++t) p.sum[k] += p.e[k].w[t];
+            p.magic[k] = shutter_magic(p.sum[k]);
+        }
+        if (sample_bytes == 1) accumulate_linear_kernel<1><<<dim3(pieces, (unsigned)n), 256, 0, s>>>(pl);
+        else accumulate_linear_kernel<2><<<dim3(pieces, (unsigned)n), 256, 0, s>>>(pl);
         if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
     }
     return 0;

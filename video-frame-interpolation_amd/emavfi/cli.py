@@ -62,6 +62,10 @@ def parser() -> argparse.ArgumentParser:
                         "stays): motion blur - every output frame is the mean of the midpoints inside an exposure of DEGREES / 360 of its "
                         "frame period (180, 172.8 or 1080/7; at most 360), summed on the device; no quality claim is made; excludes "
                         "--resample blend, --dedup and --evaluate")
+    p.add_argument("--light", choices=("srgb", "bt709", "hlg"), default=None,
+                   help="with --shutter or --resample blend: mix the frames in linear light through this transfer function instead of "
+                        "averaging the coded samples (of a Y'CbCr stream the luma plane only: a luma-linear approximation, exact for greys; "
+                        "8-, 10- and 12-bit streams); Y4M carries no transfer tag, so there is no default")
     p.add_argument("--dedup", type=float, default=None, metavar="FRACTION",
                    help="with --output-fps: drop frames that copy the frame before them and interpolate across the gap; a frame is a copy when no "
                         "cell's mean absolute luma difference exceeds FRACTION of full scale (0: bit-identical luma only; no default is claimed)")
@@ -131,6 +135,9 @@ def _run(args) -> int:
                                  (args.evaluate, "--evaluate", "a held-out frame is an instantaneous sample")):
             if given:
                 raise ValueError(f"--shutter excludes {name}: {why}")
+    if args.light is not None:
+        if args.shutter is None and not (resample and args.resample == "blend"):
+            raise ValueError("--light needs --shutter or --output-fps with --resample blend: nothing else mixes frames")
     if args.static_tolerance is not None and args.static_guard is None:
         raise ValueError("--static-tolerance needs --static-guard R")
     if args.static_guard is not None and args.reference_quirks:
@@ -171,6 +178,8 @@ def _run(args) -> int:
             factor = args.factor
         else:
             factor, _ = y4m.choose_factor(head.fps, args.target_fps, args.max_interpolation_factor)
+        if args.light is not None and head.pixel_format in ("p016", "yuv420p16"):
+            raise ValueError(f"--light on a 16-bit stream ({head.pixel_format}): linear light takes 8-, 10- and 12-bit streams")
         if factor < 0:
             raise ValueError(f"the interpolation factor {factor} is negative (the target rate lies below the stream's {head.fps:g} fps)")
         if not torch.cuda.is_available():
@@ -195,7 +204,7 @@ def _run(args) -> int:
                                ensemble=args.ensemble,
                                **(dict(border=args.border, border_mode=args.border_mode or "replicate") if args.border is not None else {}),
                                **(dict(agreement=args.agreement, agreement_radius=args.agreement_radius) if args.agreement is not None else {}),
-                               flow_scale=args.flow_scale)
+                               flow_scale=args.flow_scale, **(dict(light=args.light) if args.light is not None else {}))
         if args.evaluate:
             print(fi.evaluate(list(reader), every=args.every))      # evaluate() indexes the clip: all of it is held
             return 0
@@ -210,6 +219,7 @@ def _run(args) -> int:
                   f"({out_head.width} x {out_head.height}, {head.pixel_format}, "
                   + (f"{args.resample} at depth {args.resample_depth})" if resample else f"factor {factor})")
                   + (f", shutter {fi.shutter} degrees" if args.shutter is not None else "")
+                  + (f", mixed in linear light ({args.light})" if args.light is not None else "")
                   + (f", {len(fi.duplicates)} duplicate frames dropped" if args.dedup is not None else "")
                   + (f", static guard held {100.0 * sum(fi.static_share) / max(len(fi.static_share), 1):.2f} % of the predictions' pixels on average"
                      if args.static_guard is not None else "")

@@ -68,6 +68,10 @@ _PROTOTYPES = {
                                        c_size_t, c_int, c_int, c_int, c_void_p]),
     "emavfi_accumulate_frames": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int,
                                          c_size_t, c_int, c_int, c_int, c_void_p]),
+    "emavfi_transfer_table": (c_int, [c_int, c_int, c_int, c_void_p]),
+    "emavfi_transfer_table_check": (c_int, [c_void_p, c_int]),
+    "emavfi_accumulate_frames_linear": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p,
+                                                c_int, c_size_t, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "emavfi_frame_diff_cells": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 8 + [c_void_p, c_void_p]),
     "emavfi_duplicate_flags": (c_int, [c_void_p, c_size_t, c_int, ctypes.c_uint, c_void_p, c_void_p, c_void_p]),
     "emavfi_static_guard_frames": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p] + [c_int] * 8
@@ -1203,6 +1207,81 @@ def accumulate_frames(dst, srcs, nodes, table, flags=None, sample_bytes=1, depth
                                               nodes.shape[0] if nodes is not None else 0, ctypes.cast(arr, c_void_p),
                                               flags.data_ptr() if flags is not None else None, flags.numel() if flags is not None else 0,
                                               fb, int(sample_bytes), int(depth), int(shift), _stream()), "emavfi_accumulate_frames")
+    return dst
+
+
+# ---------------------------------------------------------------- linear light (include/emavfi.h, "LINEAR LIGHT DEFINITION")
+TRANSFERS = ("srgb", "bt709", "hlg")     # EMAVFI_TRANSFER_SRGB, _BT709, _HLG: the index is the code
+LIGHT_DEPTHS = (8, 10, 12)
+LIGHT_ONE, LIGHT_BIAS, LIGHT_LIMIT = 1 << 28, 1 << 26, 1 << 30
+
+
+def transfer_table(name, depth=8, full_range=True):
+    """The built-in table of the transfer function `name` ("srgb", "bt709", "hlg") for `depth`-bit codes (8, 10 or 12) at full or limited
+    range: a numpy uint32 array of 2^depth values of light, LIGHT_BIAS at nominal black and LIGHT_BIAS + LIGHT_ONE at nominal white.  Pure
+    host code."""
+    import numpy as np
+    if not isinstance(name, str) or name not in TRANSFERS:
+        raise ValueError(f"transfer_table: the transfer function must be one of {TRANSFERS}, got {name!r}")
+    if isinstance(depth, bool) or not isinstance(depth, int) or depth not in LIGHT_DEPTHS:
+        raise ValueError(f"transfer_table: depth must be one of {LIGHT_DEPTHS}, got {depth!r}")
+    lin = np.empty(1 << depth, np.uint32)
+    check(load().emavfi_transfer_table(TRANSFERS.index(name), depth, 1 if full_range else 0, lin.ctypes.data), "emavfi_transfer_table")
+    return lin
+
+
+def transfer_table_check(table, depth=8):
+    """Raises (RuntimeError, the message naming the first offending index) unless `table` - 2^depth values - is strictly increasing with
+    every value below 2^30: what emavfi_accumulate_frames_linear expects of the table it is given.  Pure host code."""
+    import numpy as np
+    lin = np.ascontiguousarray(table, dtype=np.uint32)
+    if isinstance(depth, bool) or not isinstance(depth, int) or depth not in LIGHT_DEPTHS:
+        raise ValueError(f"transfer_table_check: depth must be one of {LIGHT_DEPTHS}, got {depth!r}")
+    if lin.shape != (1 << depth,):
+        raise ValueError(f"transfer_table_check: {lin.shape} values for depth {depth} ({1 << depth} expected)")
+    check(load().emavfi_transfer_table_check(lin.ctypes.data, depth), "emavfi_transfer_table_check")
+    return table
+
+
+def accumulate_frames_linear(dst, srcs, nodes, table, lin, linear_bytes, flags=None, sample_bytes=1, depth=8, shift=0):
+    """accumulate_frames with the first `linear_bytes` bytes of every frame averaged in light (the linear light definition of
+    include/emavfi.h) and the rest as accumulate_frames does.  `lin`: a contiguous int32 DEVICE tensor of 2^depth words, the bits of a table
+    that passed transfer_table_check (it is not checked again: the kernel is memory-safe for any content, and a table that is not valid
+    gives wrong samples).  Everything else as for accumulate_frames."""
+    import torch
+    pools = [(dst, "accumulate_frames_linear(dst)"), (srcs, "accumulate_frames_linear(srcs)")] + \
+        ([(nodes, "accumulate_frames_linear(nodes)")] if nodes is not None else [])
+    for t, what in pools:
+        _pinned_or_cuda(t, what)
+        if t.dtype != torch.uint8 or t.dim() < 2 or t.numel() == 0 or not t[0].is_contiguous() or tuple(t.shape[1:]) != tuple(dst.shape[1:]):
+            raise ValueError(f"{what}: a non-empty uint8 [frames, ...] tensor with dense frames of dst's frame shape expected")
+    table = list(table)
+    if len(table) != dst.shape[0]:
+        raise ValueError(f"accumulate_frames_linear: {len(table)} table entries for {dst.shape[0]} output frames")
+    if flags is not None and not (flags.is_cuda and flags.dtype == torch.int32 and flags.dim() == 1 and flags.is_contiguous()):
+        raise ValueError("accumulate_frames_linear: flags must be a contiguous int32 [n] device tensor")
+    if depth not in LIGHT_DEPTHS:
+        raise ValueError(f"accumulate_frames_linear: depth must be one of {LIGHT_DEPTHS}, got {depth!r}")
+    if not (isinstance(lin, torch.Tensor) and lin.is_cuda and lin.dtype == torch.int32 and lin.dim() == 1 and lin.is_contiguous()
+            and lin.numel() == 1 << depth):
+        raise ValueError(f"accumulate_frames_linear: lin must be a contiguous int32 [{1 << depth}] device tensor (the bits of the uint32 table)")
+    arr = (AccumulateEntry * len(table))()
+    for k, (taps, weights, f, h) in enumerate(table):
+        if len(taps) != len(weights) or len(taps) > ACCUMULATE_MAX_TAPS:
+            raise ValueError(f"accumulate_frames_linear: table[{k}] has {len(taps)} taps and {len(weights)} weights (as many of each, "
+                             f"{ACCUMULATE_MAX_TAPS} at the most)")
+        arr[k].n, arr[k].f, arr[k].h = len(taps), int(f), int(h)
+        for i, (t, w) in enumerate(zip(taps, weights)):
+            arr[k].tap[i], arr[k].w[i] = int(t), int(w)
+    fb = dst[0].numel()
+    stride = lambda t: t.stride(0) if t.shape[0] > 1 else fb     # a dimension of size 1 has no meaningful stride
+    with torch.cuda.device(lin.device):
+        check(load().emavfi_accumulate_frames_linear(dst.data_ptr(), stride(dst), len(table), srcs.data_ptr(), stride(srcs), srcs.shape[0],
+                                                     nodes.data_ptr() if nodes is not None else None, stride(nodes) if nodes is not None else 0,
+                                                     nodes.shape[0] if nodes is not None else 0, ctypes.cast(arr, c_void_p),
+                                                     flags.data_ptr() if flags is not None else None, flags.numel() if flags is not None else 0,
+                                                     fb, int(sample_bytes), int(depth), int(shift), lin.data_ptr(), int(linear_bytes), _stream()),
+              "emavfi_accumulate_frames_linear")
     return dst
 
 

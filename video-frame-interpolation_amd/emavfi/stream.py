@@ -93,6 +93,12 @@ include/emavfi.h; ``shutter_taps``, ``shutter_plan``), summed on the device by `
 so that only the accumulated frames cross PCIe.  ``rate_out`` must be an integer multiple of ``rate_in`` (1 included: the frame rate stays
 and blur is added) - windows then never leave their pair, and chunks, ranks, scene holds and the static guard work as without it.  The
 output on the last frame of the clip is that frame.  Excludes ``resample_method="blend"``, ``dedup_threshold`` and ``evaluate()``.
+``light`` (opt-in, mode "resample" with a ``shutter`` or ``resample_method="blend"``; "srgb", "bt709" or "hlg") takes those means in linear
+light instead of on the coded samples (the linear light definition of include/emavfi.h): the table of the transfer function - full range
+for ``bgr24``, ``yuv_full_range`` otherwise - is built and uploaded once here, every batch is assembled by
+``emavfi_accumulate_frames_linear`` (a blend ``(a, b, w)`` as the taps ``(a, b)`` with the weights ``(256 - w, w)``), the same forwards are
+issued and nothing else changes.  ``bgr24`` is mixed whole; of a Y'CbCr frame the Y plane is mixed in light and chroma stays coded: a
+luma-linear approximation, exact for greys.  The 16-bit formats are refused; ``evaluate()`` mixes nothing and ignores it.
 ``dedup_threshold`` (opt-in, mode "resample" only; a fraction in [0, 1], 0 = bit-identical luma) drops frames that copy the frame before them -
 24 fps film in a 30 fps stream, animation on twos, screen captures - and interpolates across the gap instead of yielding the copy again (the
 duplicate-frame definition of include/emavfi.h: per cell of the 32 x 32 scene grid the mean absolute luma difference, the MAXIMUM over the
@@ -145,6 +151,7 @@ metrics - works on the cropped frames and is untouched.
 """
 from __future__ import annotations
 
+import functools
 import os
 from fractions import Fraction
 from math import gcd
@@ -259,6 +266,7 @@ class ShutterPlan(NamedTuple):
 
 class FrameInterpolator:
     shutter = None   # the shutter angle in degrees as a Fraction (include/emavfi.h, "SHUTTER DEFINITION"); None: instantaneous frames
+    light = None     # the transfer function blends and shutter means are taken in light with (include/emavfi.h, "LINEAR LIGHT DEFINITION"); None: coded
     dedup = None   # the duplicate threshold in score units (lib.dedup_threshold_units); None: duplicates are not looked for
     dedup_max_run, dedup_span = 3, 64
     static_guard = None   # the radius of the static-region guard (include/emavfi.h, "STATIC REGION DEFINITION"); None: off
@@ -281,9 +289,14 @@ class FrameInterpolator:
                  static_guard: Optional[int] = None, static_tolerance: float = 0.0, ensemble: Optional[str] = None,
                  border: Optional[int] = None, border_mode: str = "replicate",
                  agreement: Optional[float] = None, agreement_radius: Optional[int] = None, shutter=None,
-                 flow_scale: Optional[int] = None):
+                 flow_scale: Optional[int] = None, light: Optional[str] = None):
         if shutter is not None and mode != "resample":
             raise ValueError("shutter belongs to mode='resample': the exposure window is accumulated over the nodes of its time grid")
+        if light is not None:
+            if not isinstance(light, str) or light not in _lib.TRANSFERS:
+                raise ValueError(f"light must be one of {_lib.TRANSFERS} (None: coded samples are mixed), got {light!r}")
+            if mode != "resample":
+                raise ValueError("light belongs to mode='resample': only its blends and shutter means mix frames")
         if interpolation_factor < 0 or frame_interval < 1 or batch_pairs < 1:
             raise ValueError("interpolation_factor >= 0, frame_interval >= 1, batch_pairs >= 1 required")
         if mode not in ("reference", "recursive", "resample"):
@@ -314,6 +327,8 @@ class FrameInterpolator:
                     raise ValueError("shutter with dedup_threshold: a window over a gap of dropped frames is not defined")
                 self._taps = [self.shutter_taps(Q, self.resample_depth, shutter, r) for r in range(Q)]     # refuses what the rule refuses
                 self.shutter = self._exposure(shutter)[2]
+            elif light is not None and resample_method != "blend":
+                raise ValueError("light without a shutter or resample_method='blend': nothing is mixed, every output frame is one node")
         elif rate_in is not None or rate_out is not None:
             raise ValueError("rate_in / rate_out belong to mode='resample'")
         if mode != "resample" and (dedup_threshold is not None or dedup_max_run != 3 or dedup_span != 64):
@@ -356,6 +371,9 @@ class FrameInterpolator:
         if pixel_format not in ("bgr24", "nv12", *_lib.DEPTHS, *_lib.PLANAR_DEPTHS):
             raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames), 'nv12' (uint8 [H*3/2, W] frames), 'p010' / 'p012' / 'p016' "
                              "(uint16 [H*3/2, W] frames) or planar 'yuv420p8' (uint8) / 'yuv420p10' / 'yuv420p12' / 'yuv420p16' (uint16)")
+        if light is not None and (_lib.DEPTHS.get(pixel_format) or _lib.PLANAR_DEPTHS.get(pixel_format)) == 16:
+            raise ValueError(f"light with pixel_format={pixel_format!r}: a table of 2^16 values of light does not fit LDS (8-, 10- and 12-bit "
+                             "formats only)")
         self._planar = pixel_format in _lib.PLANAR_DEPTHS      # Y, U, V planes one after the other instead of Y and interleaved UV
         self._yuv8 = pixel_format in ("nv12", "yuv420p8")      # byte frames [H*3/2, W] whose first H rows are the Y plane
         # bits per sample of a 16-bit-word format, 0 for the byte formats
@@ -421,6 +439,12 @@ class FrameInterpolator:
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
         if self.device.type != "cuda":
             raise RuntimeError("FrameInterpolator needs the model on a ROCm device (no CPU path)")
+        if light is not None:
+            # built, checked and uploaded once: full range for bgr24, the Y'CbCr range otherwise.  The bits of the uint32 table as int32.
+            table = _lib.transfer_table(light, self._depth or 8, True if pixel_format == "bgr24" else bool(yuv_full_range))
+            _lib.transfer_table_check(table, self._depth or 8)
+            self.light = light
+            self._lin = torch.from_numpy(table.view(np.int32)).to(self.device)
         self._shape = None
         self._per = 0
         self._norm = None
@@ -1342,7 +1366,13 @@ class FrameInterpolator:
                           for _, taps in outs_of[s]]
                 continue
             for r, j0, j1, w in outs_of[s]:
-                table.append((ref(j0), ref(j1), w, k + 1 if (self.scene is not None and r > 0) else 0, ia[k]))
+                f = k + 1 if (self.scene is not None and r > 0) else 0
+                if self.light is None:
+                    table.append((ref(j0), ref(j1), w, f, ia[k]))
+                elif w in (0, 256):           # in light a blend is an accumulate entry: the single tap, or ((a, b), (256 - w, w))
+                    table.append(([ref(j1 if w else j0)], [256], f, ia[k]))
+                else:
+                    table.append(([ref(j0), ref(j1)], [256 - w, w], f, ia[k]))
         return levels, table, len(index), depths
 
     def _out_nodes(self, out):
@@ -1351,7 +1381,8 @@ class FrameInterpolator:
 
     def _entry_nodes(self, entry):
         """the node frames a table entry names, in order: an entry of resample_frames, or under a shutter of accumulate_frames"""
-        return [t & ~_lib.RESAMPLE_NODES for t in (entry[0] if self.shutter is not None else entry[:2]) if t & _lib.RESAMPLE_NODES]
+        taps = entry[0] if self.shutter is not None or self.light is not None else entry[:2]
+        return [t & ~_lib.RESAMPLE_NODES for t in taps if t & _lib.RESAMPLE_NODES]
 
     def _dedup_image(self, buf):
         """the staged frames `buf` as the duplicate measure reads them, at source size: interleaved colour, or the Y plane as a 1-channel image
@@ -1473,6 +1504,10 @@ class FrameInterpolator:
                 b.first_node = [first[ia.index(e[-1])] for e in table if self._entry_nodes(e)]
             # the source frames as emitted: the staged bytes, or the bytes the preprocess kernel resized them to
             assemble = _lib.accumulate_frames if self.shutter is not None else _lib.resample_frames
+            if self.light is not None:       # in light: the whole bgr24 frame, the Y plane (the first two thirds) of a 4:2:0 frame
+                fb = slot["d_emit"][0].numel()
+                assemble = functools.partial(_lib.accumulate_frames_linear, lin=self._lin,
+                                             linear_bytes=fb if self.pixel_format == "bgr24" else fb * 2 // 3)
             assemble(slot["d_emit"][:len(table)], rs if rs is not None else slot["d_in"][:nup], slot["d_node"][:off] if off else None, table,
                      flags=slot["fs"][0] if self.scene is not None else None, sample_bytes=fmt[0], depth=fmt[1], shift=fmt[2])
             slot["h_emit"][:len(table)].copy_(slot["d_emit"][:len(table)], non_blocking=True)         # HBM -> pinned (SDMA)
