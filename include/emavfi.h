@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_transfer_table, emavfi_transfer_table_check, emavfi_accumulate_frames_linear added (blended and motion-blurred frames mixed in linear light through a transfer table, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_downscale_f32, emavfi_upsample_flow_f32, emavfi_forward_flow, emavfi_forward_given_flow (and their two launch lists) added (the flow estimated on frames reduced by 2, 4 or 8 for motion beyond seven pixels, the forward split at its flow; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_accumulate_frames added (motion blur from a shutter angle: every output frame the weighted integer mean of the node frames inside its exposure window, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_agreement_guard_f32 added (where the two time directions of the ensemble disagree the plain blend of the source frames is emitted, decided on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_active_bounds, emavfi_fill_outside_frames, emavfi_preprocess_u8_pitched, emavfi_postprocess_u8_pitched added (the forward run on the active picture only: black bars found on the device and put back around every prediction; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_transfer_table, emavfi_transfer_table_check, emavfi_accumulate_frames_linear added (blended and motion-blurred frames mixed in linear light through a transfer table, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_downscale_f32, emavfi_upsample_flow_f32, emavfi_forward_flow, emavfi_forward_given_flow (and their two launch lists) added (the flow estimated on frames reduced by 2, 4 or 8 for motion beyond seven pixels, the forward split at its flow; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_accumulate_frames added (motion blur from a shutter angle: every output frame the weighted integer mean of the node frames inside its exposure window, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_agreement_guard_f32 added (where the two time directions of the ensemble disagree the plain blend of the source frames is emitted, decided on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -798,6 +798,61 @@ typedef struct { unsigned a, b; } emavfi_static_entry;   /* indices into srcs */
 int emavfi_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst, const unsigned char *srcs, size_t src_stride, int n_srcs,
                                const emavfi_static_entry *table, int H, int W, int layout, int C, int sample_bytes, int depth, int shift,
                                int radius, unsigned tol, unsigned *counts, void *stream);
+
+/* The active picture.  A 2.39:1 film in a 16:9 container, 4:3 material pillarboxed into 16:9: a quarter of the pixels of such a frame are
+ * black bars, and the forward's cost is proportional to the pixels it is given.  The static guard above keeps the bars, but after the
+ * forward has paid for them.  The reference interpolates the whole frame (inference.py); this is an addition, off unless asked for: the bars
+ * are found on the device, the forward runs on the picture alone, and the bars are put back around every prediction.
+ *
+ * ACTIVE AREA DEFINITION (the one place).  This is the project's own definition: it claims agreement with no outside tool (ffmpeg's
+ * cropdetect and the like).  All arithmetic is integer: host, oracle and device agree bit for bit.
+ *   Sample.  A byte, or (word >> shift) & (2^depth - 1) of a 16-bit little-endian word: the (sample_bytes, depth, shift) triple
+ *     emavfi_frame_diff_cells takes.
+ *   Content.  A pixel of an image [H][W][C] has content when ANY of its C samples is GREATER than `level`; a sample equal to `level` is not
+ *     content.  C = 1: the Y plane of a Y'CbCr frame - chroma is not looked at.  C = 3: bytes only (bgr24); any channel counts, so a
+ *     saturated blue pixel is content although its luma is low.
+ *   Bounds of a frame.  Four u32 words {top, bottom, left, right}: top = the smallest y with content, bottom = the largest such y plus 1,
+ *     left and right the same in x.  A frame with no content: {H, 0, W, 0}.
+ *   Rectangle of a set of frames (host integers).  The union of the bounds, grown outward so that top and bottom are multiples of 2 and left
+ *     and right multiples of 16, clipped to the frame.  The multiples of 2 make the 4:2:0 chroma planes crop at whole samples; the multiples
+ *     of 16 keep the 16-byte paths of every pitched entry at every sample size.  An empty union, or a rectangle that covers the frame, means
+ *     "the whole frame".
+ *   A prediction with an active rectangle R for the pair (a, b).  Inside R: the samples of the forward run on the two frames cropped to R.
+ *     Outside R: the samples of frame a as emitted.  4:2:0: the chroma sample (i, j) belongs to R exactly when its 2 x 2 luma block does -
+ *     R's even edges make that unambiguous.  A replaced 16-bit sample receives a's WHOLE word, as the static guard's does.
+ *   Consequences.  R = frame is the plain path byte for byte.  Content outside an explicitly given R is not interpolated: it shows frame a.
+ *     The model sees zero padding (mean grey) at R's edge where it saw the bar before; a border (BORDER DEFINITION below) replicates the
+ *     picture there instead.  No quality claim is made.
+ *
+ * emavfi_active_bounds writes the bounds of n images (img + k batch_stride, rows `pitch` bytes apart, [H][W][C] samples: C = 1, or C = 3 at
+ *   sample_bytes 1) to bounds[4 k ..] (device memory).  EVERY one of the 4 n words is defined on exit whatever the buffer held before: a launch
+ *   ahead of the scan initialises them on `stream`, then lanes keep their extremes in registers, waves fold them, a workgroup folds its waves'
+ *   and issues atomicMin / atomicMax on the frame's words - order-free, so exact.  Access width: 16-byte loads where pointer, pitch and (n > 1) batch stride are
+ *   multiples of 16, else - and for a row's remainder - bytes through the same per-element functions (csrc/active_elem.h); pitch padding is
+ *   never read.  The image may be pinned host memory.
+ * emavfi_fill_outside_frames: destination frame k (dst + k dst_stride) receives the samples OUTSIDE the rectangle (top, left, height, width) of
+ *   frame table[k] of `srcs`; bytes inside the rectangle are neither read nor written, and a rectangle that is the frame leaves dst untouched.
+ *   Frames are dense, in the layouts of the STATIC REGION DEFINITION, sample_bytes 1 or 2.  `table` is a HOST pointer to n_dst indices, read and
+ *   validated before the call returns and passed on as kernel arguments, EMAVFI_RESAMPLE_LAUNCH_CAP entries per launch.  Only the bar bytes
+ *   move: 16-byte accesses on aligned units that lie wholly outside, samples elsewhere.
+ * emavfi_preprocess_u8_pitched / emavfi_postprocess_u8_pitched are emavfi_preprocess_u8 / emavfi_postprocess_u8 on the dense copy of the
+ *   frames, bit for bit, for frames whose rows are `pitch` and whose frames are `batch_stride` bytes apart (a sub-rectangle of a larger
+ *   frame); pitch padding is never read or written; 16-byte accesses where pointer, pitch and stride allow.
+ * EMAVFI_E_ARG (never an abort), the message naming the argument: a null pointer; n, n_dst, n_srcs or B below 1, n or B above 65535; H or W
+ *   outside 1..16384, or odd at a 4:2:0 layout; an unknown layout; C outside {1, 3} (bounds; 3 at sample_bytes 1 only) or 1..4 (the others; 1
+ *   at a 4:2:0 layout); sample_bytes, depth or shift outside the above; a level above 2^depth - 1; a pitch below the row, a stride below the
+ *   plane or frame, either odd at sample_bytes 2; a frame pointer that is not 2-byte aligned there, a u32 / fp32 pointer that is not 4-byte
+ *   aligned; size arithmetic that overflows size_t; a rectangle that leaves the frame, has no area, or is odd at a 4:2:0 layout; a table
+ *   index outside srcs; dst overlapping srcs; a zero std.  Nothing is allocated, nothing synchronises, all work goes on `stream`. */
+int emavfi_active_bounds(const unsigned char *img, size_t pitch, size_t batch_stride, int n, int H, int W, int C, int sample_bytes, int depth,
+                         int shift, unsigned level, unsigned *bounds /* n x 4 */, void *stream);
+int emavfi_fill_outside_frames(unsigned char *dst, size_t dst_stride, int n_dst, const unsigned char *srcs, size_t src_stride, int n_srcs,
+                               const unsigned *table /* n_dst indices into srcs, HOST */, int H, int W, int layout, int C, int sample_bytes,
+                               int top, int left, int height, int width, void *stream);
+int emavfi_preprocess_u8_pitched(const unsigned char *frames, size_t pitch, size_t batch_stride, float *out_nchw, int B, int H, int W, int C,
+                                 const float *mean, const float *std, void *stream);
+int emavfi_postprocess_u8_pitched(const float *frames_nchw, unsigned char *out, size_t pitch, size_t batch_stride, int B, int H, int W, int C,
+                                  const double *mean, const double *std, int denormalize, void *stream);
 
 /* Test-time ensembling.  The forward estimates one flow and warps only frame2 (ema_vfi.py:130), so F(a, b) and F(b, a) are two different
  * "midpoints" of the same pair, and its stride-2 context path and zero padding make it non-equivariant under mirroring.  The usual remedy

@@ -9,6 +9,7 @@
 #include "light_elem.h"
 #include "dedup_elem.h"
 #include "static_elem.h"
+#include "active_elem.h"
 #include "ensemble_elem.h"
 #include "border_elem.h"
 #include "coarse_elem.h"
@@ -2026,6 +2027,145 @@ int emavfi_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst,
     }
     EMAVFI_TRY(launch_static_guard_frames(dst, dst_stride, n_dst, srcs, src_stride, reinterpret_cast<const StaticEntry *>(table), H, W, layout, C,
                                           sample_bytes, depth, shift, radius, tol, counts, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+// ---- the active picture (include/emavfi.h, "ACTIVE AREA DEFINITION"): every check runs on the host, pointers are looked at last, the table is
+// read here and not kept
+static_assert(EMAVFI_RESAMPLE_LAUNCH_CAP == ACTIVE_CAP, "header and active_elem.h disagree");
+
+// what the four entries refuse alike about a sample format
+static int active_sample_check(const char *what, int sample_bytes, int depth, int shift)
+{
+    if (sample_bytes != 1 && sample_bytes != 2) return fail(EMAVFI_E_ARG, "%s: sample_bytes = %d (sample_bytes must be 1 or 2)", what, sample_bytes);
+    if (sample_bytes == 1 ? depth != 8 : (depth != 10 && depth != 12 && depth != 16))
+        return fail(EMAVFI_E_ARG, "%s: depth = %d (depth must be 8 at sample_bytes 1 and 10, 12 or 16 at sample_bytes 2)", what, depth);
+    if (shift < 0 || shift > 8 * sample_bytes - depth)
+        return fail(EMAVFI_E_ARG, "%s: shift = %d (shift must lie in 0..%d at depth %d)", what, shift, 8 * sample_bytes - depth, depth);
+    return EMAVFI_OK;
+}
+// one pitched image batch of n images of H rows of `row` bytes
+static int active_image_check(const char *what, size_t pitch, size_t bstride, int n, int H, size_t row, size_t odd)
+{
+    if (pitch < row) return fail(EMAVFI_E_ARG, "%s: pitch %zu is smaller than its row of %zu bytes", what, pitch, row);
+    if (pitch & odd) return fail(EMAVFI_E_ARG, "%s: pitch %zu is odd at sample_bytes 2", what, pitch);
+    size_t plane, span;
+    if (__builtin_mul_overflow((size_t)(H - 1), pitch, &plane) || __builtin_add_overflow(plane, row, &plane))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (pitch %zu)", what, pitch);
+    if (n > 1 && bstride < plane) return fail(EMAVFI_E_ARG, "%s: the batch stride batch_stride %zu is smaller than its plane", what, bstride);
+    if (n > 1 && (bstride & odd)) return fail(EMAVFI_E_ARG, "%s: batch_stride %zu is odd at sample_bytes 2", what, bstride);
+    if (n > 1 && (__builtin_mul_overflow((size_t)(n - 1), bstride, &span) || __builtin_add_overflow(span, plane, &span)))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (batch_stride %zu)", what, bstride);
+    return EMAVFI_OK;
+}
+
+int emavfi_active_bounds(const unsigned char *img, size_t pitch, size_t batch_stride, int n, int H, int W, int C, int sample_bytes, int depth,
+                         int shift, unsigned level, unsigned *bounds, void *stream)
+{
+    const char *const what = "active_bounds";
+    if (n < 1) return fail(EMAVFI_E_ARG, "%s: n must be >= 1", what);
+    if (n > 65535) return fail(EMAVFI_E_ARG, "%s: n = %d is above 65535", what, n);
+    if (const int rc = scene_dims_check(what, H, W); rc != EMAVFI_OK) return rc;
+    if (C != 1 && C != 3) return fail(EMAVFI_E_ARG, "%s: C = %d (C must be 1 or 3)", what, C);
+    if (const int rc = active_sample_check(what, sample_bytes, depth, shift); rc != EMAVFI_OK) return rc;
+    if (C == 3 && sample_bytes == 2) return fail(EMAVFI_E_ARG, "%s: C = 3 at sample_bytes 2 (interleaved colour is scanned as bytes only)", what);
+    if (level > (1u << depth) - 1u) return fail(EMAVFI_E_ARG, "%s: level = %u is above 2^depth - 1 = %u", what, level, (1u << depth) - 1u);
+    const size_t odd = sample_bytes == 2 ? 1 : 0;
+    if (const int rc = active_image_check(what, pitch, batch_stride, n, H, (size_t)W * C * sample_bytes, odd); rc != EMAVFI_OK) return rc;
+    if (!img) return fail(EMAVFI_E_ARG, "%s: null pointer img", what);
+    if (!bounds) return fail(EMAVFI_E_ARG, "%s: null pointer bounds", what);
+    if ((uintptr_t)img & odd) return fail(EMAVFI_E_ARG, "%s: the image pointer img must be 2-byte aligned at sample_bytes 2", what);
+    if ((uintptr_t)bounds & 3) return fail(EMAVFI_E_ARG, "%s: the u32 pointer bounds must be 4-byte aligned", what);
+    EMAVFI_TRY(launch_active_bounds(img, pitch, batch_stride, n, H, W, C, sample_bytes, depth, shift, level, bounds, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+int emavfi_fill_outside_frames(unsigned char *dst, size_t dst_stride, int n_dst, const unsigned char *srcs, size_t src_stride, int n_srcs,
+                               const unsigned *table, int H, int W, int layout, int C, int sample_bytes, int top, int left, int height, int width,
+                               void *stream)
+{
+    const char *const what = "fill_outside_frames";
+    if (n_dst < 1) return fail(EMAVFI_E_ARG, "%s: n_dst must be >= 1", what);
+    if (n_srcs < 1) return fail(EMAVFI_E_ARG, "%s: n_srcs must be >= 1", what);
+    if (const int rc = scene_dims_check(what, H, W); rc != EMAVFI_OK) return rc;
+    if (layout != EMAVFI_LAYOUT_INTERLEAVED && layout != EMAVFI_LAYOUT_NV12 && layout != EMAVFI_LAYOUT_I420)
+        return fail(EMAVFI_E_ARG, "%s: unknown layout %d (EMAVFI_LAYOUT_INTERLEAVED, EMAVFI_LAYOUT_NV12 or EMAVFI_LAYOUT_I420)", what, layout);
+    const bool sub = layout != EMAVFI_LAYOUT_INTERLEAVED;
+    if (sub && ((H | W) & 1)) return fail(EMAVFI_E_ARG, "%s: H = %d, W = %d: a 4:2:0 layout needs an even H and W", what, H, W);
+    if (C < 1 || C > 4) return fail(EMAVFI_E_ARG, "%s: C = %d (C must be 1..4)", what, C);
+    if (sub && C != 1) return fail(EMAVFI_E_ARG, "%s: C = %d at a 4:2:0 layout (C must be 1 there)", what, C);
+    if (sample_bytes != 1 && sample_bytes != 2) return fail(EMAVFI_E_ARG, "%s: sample_bytes = %d (sample_bytes must be 1 or 2)", what, sample_bytes);
+    if (height < 1 || width < 1) return fail(EMAVFI_E_ARG, "%s: the rectangle has no area (height = %d, width = %d)", what, height, width);
+    if (top < 0 || left < 0 || top > H - height || left > W - width)
+        return fail(EMAVFI_E_ARG, "%s: the rectangle (top = %d, left = %d, height = %d, width = %d) leaves the %d x %d frame", what, top, left, height,
+                    width, H, W);
+    if (sub && ((top | left | height | width) & 1))
+        return fail(EMAVFI_E_ARG, "%s: the rectangle (top = %d, left = %d, height = %d, width = %d) is odd at a 4:2:0 layout", what, top, left, height,
+                    width);
+    StaticPlane planes[3];
+    size_t frame_bytes;                                   // at most 16384^2 * 4 * 2 = 2^31
+    static_planes(layout, C, H, W, sample_bytes, planes, &frame_bytes);
+    const size_t odd = sample_bytes == 2 ? 1 : 0;
+    const struct { const char *name; size_t stride; int n; } pools[2] = {{"dst_stride", dst_stride, n_dst}, {"src_stride", src_stride, n_srcs}};
+    size_t span[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+        if (pools[k].stride < frame_bytes)
+            return fail(EMAVFI_E_ARG, "%s: %s %zu is smaller than the frame's %zu bytes", what, pools[k].name, pools[k].stride, frame_bytes);
+        if (pools[k].stride & odd) return fail(EMAVFI_E_ARG, "%s: %s %zu is odd at sample_bytes 2", what, pools[k].name, pools[k].stride);
+        if (!resample_span(pools[k].n, pools[k].stride, frame_bytes, &span[k]))
+            return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (%s %zu)", what, pools[k].name, pools[k].stride);
+    }
+    if (!dst) return fail(EMAVFI_E_ARG, "%s: null pointer dst", what);
+    if (!srcs) return fail(EMAVFI_E_ARG, "%s: null pointer srcs", what);
+    if (!table) return fail(EMAVFI_E_ARG, "%s: null pointer table", what);
+    if (((uintptr_t)dst | (uintptr_t)srcs) & odd)
+        return fail(EMAVFI_E_ARG, "%s: the frame pointers dst, srcs must be 2-byte aligned at sample_bytes 2", what);
+    const uintptr_t d0 = (uintptr_t)dst, s0 = (uintptr_t)srcs;
+    if (d0 + span[0] < d0 || s0 + span[1] < s0) return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (a pool wraps the address space)", what);
+    if (d0 < s0 + span[1] && s0 < d0 + span[0]) return fail(EMAVFI_E_ARG, "%s: dst overlaps srcs", what);
+    for (int k = 0; k < n_dst; ++k)
+        if (table[k] >= (unsigned)n_srcs) return fail(EMAVFI_E_ARG, "%s: table[%d] = %u is outside srcs (%d frames)", what, k, table[k], n_srcs);
+    EMAVFI_TRY(launch_fill_outside_frames(dst, dst_stride, n_dst, srcs, src_stride, table, H, W, layout, C, sample_bytes, top, left, height, width,
+                                          (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+// what the pitched u8 pair refuses alike: everything but the pointers
+static int u8_pitched_check(const char *what, size_t pitch, size_t batch_stride, int B, int H, int W, int C)
+{
+    if (B < 1) return fail(EMAVFI_E_ARG, "%s: B must be >= 1", what);
+    if (B > 65535) return fail(EMAVFI_E_ARG, "%s: B = %d is above 65535", what, B);
+    if (const int rc = scene_dims_check(what, H, W); rc != EMAVFI_OK) return rc;
+    if (C < 1 || C > 4) return fail(EMAVFI_E_ARG, "%s: C = %d (C must be 1..4)", what, C);
+    return active_image_check(what, pitch, batch_stride, B, H, (size_t)W * C, 0);
+}
+
+int emavfi_preprocess_u8_pitched(const unsigned char *frames, size_t pitch, size_t batch_stride, float *out_nchw, int B, int H, int W, int C,
+                                 const float *mean, const float *std, void *stream)
+{
+    const char *const what = "preprocess_u8_pitched";
+    if (const int rc = u8_pitched_check(what, pitch, batch_stride, B, H, W, C); rc != EMAVFI_OK) return rc;
+    if (!mean || !std) return fail(EMAVFI_E_ARG, "%s: null mean / std", what);
+    for (int c = 0; c < C; ++c)
+        if (!(std[c] != 0.0f)) return fail(EMAVFI_E_ARG, "%s: std[%d] must be non-zero", what, c);
+    if (!frames) return fail(EMAVFI_E_ARG, "%s: null pointer frames", what);
+    if (!out_nchw) return fail(EMAVFI_E_ARG, "%s: null pointer out_nchw", what);
+    if ((uintptr_t)out_nchw & 3) return fail(EMAVFI_E_ARG, "%s: the fp32 pointer out_nchw must be 4-byte aligned", what);
+    EMAVFI_TRY(launch_preprocess_u8_pitched(frames, pitch, batch_stride, out_nchw, B, H, W, C, mean, std, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+int emavfi_postprocess_u8_pitched(const float *frames_nchw, unsigned char *out, size_t pitch, size_t batch_stride, int B, int H, int W, int C,
+                                  const double *mean, const double *std, int denormalize, void *stream)
+{
+    const char *const what = "postprocess_u8_pitched";
+    if (const int rc = u8_pitched_check(what, pitch, batch_stride, B, H, W, C); rc != EMAVFI_OK) return rc;
+    if (!mean || !std) return fail(EMAVFI_E_ARG, "%s: null mean / std", what);
+    if (!frames_nchw) return fail(EMAVFI_E_ARG, "%s: null pointer frames_nchw", what);
+    if (!out) return fail(EMAVFI_E_ARG, "%s: null pointer out", what);
+    if ((uintptr_t)frames_nchw & 3) return fail(EMAVFI_E_ARG, "%s: the fp32 pointer frames_nchw must be 4-byte aligned", what);
+    EMAVFI_TRY(launch_postprocess_u8_pitched(frames_nchw, out, pitch, batch_stride, B, H, W, C, mean, std, denormalize ? 1 : 0, (hipStream_t)stream),
+               what);
     return EMAVFI_OK;
 }
 

@@ -137,6 +137,18 @@ struct StaticEntry { unsigned a, b; };   // emavfi_static_entry
 int launch_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst, const unsigned char *srcs, size_t src_stride,
                                const StaticEntry *table, int H, int W, int layout, int C, int sample_bytes, int depth, int shift, int radius,
                                unsigned tol, unsigned *counts, hipStream_t s);
+// the active picture (include/emavfi.h, "ACTIVE AREA DEFINITION"): arguments already validated.  launch_active_bounds: an initialising launch,
+// then the scan.  launch_fill_outside_frames: `table` is a HOST pointer to n_dst indices into srcs, read before the call returns and passed
+// on as kernel arguments, ACTIVE_CAP (active_elem.h) entries per launch; a rectangle that is the frame launches nothing.  The pitched u8
+// pair: pitches and batch strides in bytes
+int launch_active_bounds(const unsigned char *img, size_t pitch, size_t bstride, int n, int H, int W, int C, int sample_bytes, int depth, int shift,
+                         unsigned level, unsigned *bounds, hipStream_t s);
+int launch_fill_outside_frames(unsigned char *dst, size_t dst_stride, int n_dst, const unsigned char *srcs, size_t src_stride, const unsigned *table,
+                               int H, int W, int layout, int C, int sample_bytes, int top, int left, int height, int width, hipStream_t s);
+int launch_preprocess_u8_pitched(const unsigned char *src, size_t pitch, size_t bstride, float *dst, int B, int H, int W, int C, const float *mean,
+                                 const float *stdv, hipStream_t s);
+int launch_postprocess_u8_pitched(const float *src, unsigned char *dst, size_t pitch, size_t bstride, int B, int H, int W, int C, const double *mean,
+                                  const double *stdv, int denorm, hipStream_t s);
 // test-time ensembling (include/emavfi.h, "ENSEMBLE DEFINITION"): arguments already validated; `members` and `flips` are HOST arrays of n
 // entries, read before the call returns and passed on as kernel arguments
 int launch_flip_f32(const float *src, float *dst, size_t planes, int H, int W, int flip, hipStream_t s);

@@ -8,6 +8,7 @@
 #include "light_elem.h"
 #include "dedup_elem.h"
 #include "static_elem.h"
+#include "active_elem.h"
 #include "ensemble_elem.h"
 #include "border_elem.h"
 #include "coarse_elem.h"
@@ -2850,6 +2851,265 @@ int launch_static_guard_frames(unsigned char *dst, size_t dst_stride, int n_dst,
         if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The active picture found and its bars restored on the device (include/emavfi.h, "ACTIVE AREA DEFINITION"; per-element functions:
+// active_elem.h).
+//   active_bounds_init_kernel     every frame's four words = {H, 0, W, 0}: a launch of its own ahead of the scan, as the static guard's counts.
+//   active_bounds_kernel<BPP>     grid (pieces of a frame, n), 256 threads; BPP 1: bytes, C = 1; 2: 16-bit words; 3: bytes, C = 3.  A lane
+//                                 walks 16-byte units of the rows and keeps its four extremes in registers; a unit is ONE 16-byte load where
+//                                 pointer, pitch and batch stride are multiples of 16 and the unit ends inside the row (pitch padding is never
+//                                 read), byte loads otherwise and for the row's remainder (diff_load_unit: bytes beyond the row read as 0, which
+//                                 is never above a level), four units in flight.  A wave folds its lanes' extremes by shuffles, the workgroup its
+//                                 four waves' through 16 words of LDS, and one lane issues atomicMin / atomicMax on the frame's four words - those
+//                                 that beat the word as it reads then; min and max are order-free, the result is exact.  No staging in LDS.
+//   fill_outside_kernel<SB>       grid (pieces of a frame, entries of this launch), 256 threads.  Per plane the outside of the rectangle is four
+//                                 bands - above, below, left, right - walked in 16-byte units of the plane's rows: a unit that lies wholly in
+//                                 its band moves as one 16-byte load and store where the two frame addresses, the plane's offset and its row
+//                                 bytes are multiples of 16, everything else sample by sample.  Bytes inside the rectangle are not touched.
+//   preprocess_u8_pitched_kernel / postprocess_u8_pitched_kernel   the u8 kernels' per-element arithmetic (nv12_norm / nv12_byte: the same two
+//                                 functions the 4:2:0 kernels share with them) over rows of `pitch` bytes: a lane takes one 16-byte unit of a
+//                                 row, wide where pointer, pitch and batch stride allow and the unit ends inside the row.
+// All are short-lived and wait on nothing.
+// ------------------------------------------------------------------------------------------
+struct BoundsArgs { const unsigned char *img; size_t pitch, bstride; unsigned *bounds; int H, W, rowbytes, nu, wide, shift; unsigned mask, level; };
+
+__global__ __launch_bounds__(256) void active_bounds_init_kernel(unsigned *__restrict__ bounds, int n, int H, int W)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const ActiveBounds e = active_none(H, W);
+        bounds[4 * i] = e.top; bounds[4 * i + 1] = e.bottom; bounds[4 * i + 2] = e.left; bounds[4 * i + 3] = e.right;
+    }
+}
+
+template <int BPP>
+__global__ __launch_bounds__(256) void active_bounds_kernel(BoundsArgs a)
+{
+    constexpr int SB = BPP == 2 ? 2 : 1, NS = 16 / SB, PX = BPP == 3 ? 3 : 1;    // bytes per sample, samples per unit, samples per pixel
+    constexpr int UN = 4;                                                        // units a lane has in flight
+    __shared__ unsigned part[4][4];
+    const size_t b = blockIdx.y;
+    const unsigned char *img = a.img + b * a.bstride;
+    ActiveBounds mine = active_none(a.H, a.W);
+    const int items = a.H * a.nu, stride = gridDim.x * 256;                      // at most 16384 rows x 3072 units
+    for (int t0 = blockIdx.x * 256 + threadIdx.x; t0 < items; t0 += UN * stride) {
+        unsigned w[UN][4];
+        int y[UN], b0[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const int t = t0 + u * stride < items ? t0 + u * stride : t0;        // past the end: unit t0 once more, which marks nothing new
+            y[u] = t / a.nu;
+            b0[u] = (t - y[u] * a.nu) << 4;
+            const int nb = min(16, a.rowbytes - b0[u]);
+            diff_load_unit<1>(img + (size_t)y[u] * a.pitch + (size_t)b0[u], a.wide && nb == 16, nb, w[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            int first = -1, last = -1;
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                const unsigned word = SB == 2 ? (w[u][k >> 1] >> (16 * (k & 1))) & 0xffffu : (w[u][k >> 2] >> (8 * (k & 3))) & 0xffu;
+                if (active_content(active_sample(word, a.mask, a.shift), a.level)) {
+                    if (first < 0) first = k;
+                    last = k;
+                }
+            }
+            if (first >= 0) {
+                const int s0 = b0[u] / SB;
+                active_mark(mine, y[u], (s0 + first) / PX);
+                active_mark(mine, y[u], (s0 + last) / PX);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        mine.top = min(mine.top, (unsigned)__shfl_xor(mine.top, off, 64));
+        mine.bottom = max(mine.bottom, (unsigned)__shfl_xor(mine.bottom, off, 64));
+        mine.left = min(mine.left, (unsigned)__shfl_xor(mine.left, off, 64));
+        mine.right = max(mine.right, (unsigned)__shfl_xor(mine.right, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        unsigned *mp = part[threadIdx.x >> 6];
+        mp[0] = mine.top; mp[1] = mine.bottom; mp[2] = mine.left; mp[3] = mine.right;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) active_join(mine, ActiveBounds{part[k][0], part[k][1], part[k][2], part[k][3]});
+        if (!active_is_empty(mine)) {
+            // a word only ever moves one way, so what is read here is no nearer the result than the word is now: an extreme that does not
+            // beat it cannot change it and its atomic is skipped.  The words of all frames share a cache line or two: few, cheap visits.
+            unsigned *o = a.bounds + 4 * b;
+            if (mine.top < __atomic_load_n(o, __ATOMIC_RELAXED)) atomicMin(o, mine.top);
+            if (mine.bottom > __atomic_load_n(o + 1, __ATOMIC_RELAXED)) atomicMax(o + 1, mine.bottom);
+            if (mine.left < __atomic_load_n(o + 2, __ATOMIC_RELAXED)) atomicMin(o + 2, mine.left);
+            if (mine.right > __atomic_load_n(o + 3, __ATOMIC_RELAXED)) atomicMax(o + 3, mine.right);
+        }
+    }
+}
+
+int launch_active_bounds(const unsigned char *img, size_t pitch, size_t bstride, int n, int H, int W, int C, int sample_bytes, int depth, int shift,
+                         unsigned level, unsigned *bounds, hipStream_t s)
+{
+    active_bounds_init_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(bounds, n, H, W);
+    if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
+    BoundsArgs p{img, pitch, bstride, bounds, H, W, W * C * sample_bytes, 0, 0, shift, (1u << depth) - 1u, level};
+    p.nu = (p.rowbytes + 15) >> 4;
+    p.wide = mult_of(16, {(size_t)(uintptr_t)img, pitch, n > 1 ? bstride : 0});
+    // at most 64 workgroups a frame, four units in flight per lane: the frames' words share a cache line or two, and every visit to them
+    // queues there (measured: one visit per wave of a fine grid cost more than the whole scan, profiles/r27_active_area.md)
+    const size_t want = ((size_t)H * p.nu + 1023) / 1024;
+    const dim3 grid((unsigned)std::min<size_t>(std::max<size_t>(want, 1), 64), (unsigned)n);
+    if (C == 3) active_bounds_kernel<3><<<grid, 256, 0, s>>>(p);
+    else if (sample_bytes == 2) active_bounds_kernel<2><<<grid, 256, 0, s>>>(p);
+    else active_bounds_kernel<1><<<grid, 256, 0, s>>>(p);
+    return (int)hipGetLastError();
+}
+
+struct FillArgs {
+    unsigned char *dst;              // the first destination frame of THIS launch
+    size_t dst_stride;
+    const unsigned char *srcs;
+    size_t src_stride;
+    StaticPlane plane[3];
+    int n_planes, top, left, height, width, wide;
+    unsigned idx[ACTIVE_CAP];
+};
+static_assert(sizeof(FillArgs) <= 2048, "the table must fit the kernel argument segment");
+
+template <int SB>
+__global__ __launch_bounds__(256) void fill_outside_kernel(FillArgs p)
+{
+    const unsigned e = blockIdx.y;
+    const unsigned char *fa = p.srcs + (size_t)p.idx[e] * p.src_stride;
+    unsigned char *fd = p.dst + (size_t)e * p.dst_stride;
+    const bool wide = p.wide && ((((uintptr_t)fa | (uintptr_t)fd) & 15) == 0);
+    const int tid = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
+    for (int q = 0; q < p.n_planes; ++q) {
+        const StaticPlane pl = p.plane[q];
+        const int rb = pl.samples * SB;                                           // at most 16384 * 4 * 2 bytes
+        const ActiveSpan sp = active_plane_span(pl, SB, p.top, p.left, p.height, p.width);
+        // the outside of the span: rows [y0, y1) x bytes [c0, c1) above, below, left and right of it
+        const int band[4][4] = {{0, sp.r0, 0, rb}, {sp.r1, pl.rows, 0, rb}, {sp.r0, sp.r1, 0, sp.c0}, {sp.r0, sp.r1, sp.c1, rb}};
+        for (int k = 0; k < 4; ++k) {
+            const int y0 = band[k][0], y1 = band[k][1], c0 = band[k][2], c1 = band[k][3];
+            if (y1 <= y0 || c1 <= c0) continue;
+            const int u0 = c0 >> 4, nu = ((c1 + 15) >> 4) - u0, items = (y1 - y0) * nu;   // at most 16384 rows x 8192 units
+            for (int t = tid; t < items; t += step) {
+                const int rr = t / nu, ub = (u0 + (t - rr * nu)) << 4;            // the unit's first byte in its row
+                const size_t off = pl.offset + (size_t)(y0 + rr) * rb + (size_t)ub;
+                if (wide && ub >= c0 && ub + 16 <= c1) {                          // c1 <= rb: the unit ends inside the row
+                    *reinterpret_cast<uint4 *>(fd + off) = *reinterpret_cast<const uint4 *>(fa + off);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 16; j += SB) {
+                        if (ub + j < c0 || ub + j >= c1) continue;
+                        if constexpr (SB == 1) fd[off + j] = fa[off + j];
+                        else *reinterpret_cast<unsigned short *>(fd + off + j) = *reinterpret_cast<const unsigned short *>(fa + off + j);
+                    }
+                }
+            }
+        }
+    }
+}
+
+int launch_fill_outside_frames(unsigned char *dst, size_t dst_stride, int n_dst, const unsigned char *srcs, size_t src_stride, const unsigned *table,
+                               int H, int W, int layout, int C, int sample_bytes, int top, int left, int height, int width, hipStream_t s)
+{
+    if (height == H && width == W) return 0;                                       // the rectangle is the frame: nothing lies outside
+    FillArgs p{};
+    size_t frame_bytes;
+    p.n_planes = static_planes(layout, C, H, W, sample_bytes, p.plane, &frame_bytes);
+    p.dst_stride = dst_stride; p.srcs = srcs; p.src_stride = src_stride;
+    p.top = top; p.left = left; p.height = height; p.width = width;
+    p.wide = 1;
+    size_t inside = 0;
+    for (int q = 0; q < p.n_planes; ++q) {
+        p.wide = p.wide && mult_of(16, {p.plane[q].offset, (size_t)p.plane[q].samples * sample_bytes});
+        const ActiveSpan sp = active_plane_span(p.plane[q], sample_bytes, top, left, height, width);
+        inside += (size_t)(sp.r1 - sp.r0) * (size_t)(sp.c1 - sp.c0);
+    }
+    const size_t want = ((frame_bytes - inside) / 16 + 1023) / 1024;               // four units per lane
+    const unsigned gx = (unsigned)std::min<size_t>(std::max<size_t>(want, 1), 1024);
+    for (int first = 0; first < n_dst; first += ACTIVE_CAP) {
+        const int n = n_dst - first < ACTIVE_CAP ? n_dst - first : ACTIVE_CAP;
+        p.dst = dst + (size_t)first * dst_stride;
+        for (int k = 0; k < n; ++k) p.idx[k] = table[first + k];
+        if (sample_bytes == 1) fill_outside_kernel<1><<<dim3(gx, (unsigned)n), 256, 0, s>>>(p);
+        else fill_outside_kernel<2><<<dim3(gx, (unsigned)n), 256, 0, s>>>(p);
+        if (const hipError_t err = hipGetLastError(); err != hipSuccess) return (int)err;
+    }
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void preprocess_u8_pitched_kernel(const unsigned char *__restrict__ src, size_t pitch, size_t bstride,
+                                                                    float *__restrict__ dst, int B, int H, int W, int C, int wide, Stats4 st)
+{
+    const int rowbytes = W * C, nu = (rowbytes + 15) >> 4;
+    const size_t plane = (size_t)H * W, total = (size_t)B * H * nu;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t row = t / nu, b = row / H;
+        const int y = (int)(row - b * H), b0 = (int)(t - row * nu) << 4, nb = min(16, rowbytes - b0);
+        unsigned w[4];
+        diff_load_unit<1>(src + b * bstride + (size_t)y * pitch + (size_t)b0, wide && nb == 16, nb, w);
+        int x = b0 / C, c = b0 - x * C;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if (k < nb) {
+                dst[(b * C + c) * plane + (size_t)y * W + x] = nv12_norm((int)((w[k >> 2] >> (8 * (k & 3))) & 0xffu), st.mean[c], st.stdv[c]);
+                if (++c == C) { c = 0; ++x; }
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(256) void postprocess_u8_pitched_kernel(const float *__restrict__ src, unsigned char *__restrict__ dst, size_t pitch,
+                                                                     size_t bstride, int B, int H, int W, int C, int wide, Stats4d st, int denorm)
+{
+    const int rowbytes = W * C, nu = (rowbytes + 15) >> 4;
+    const size_t plane = (size_t)H * W, total = (size_t)B * H * nu;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t row = t / nu, b = row / H;
+        const int y = (int)(row - b * H), b0 = (int)(t - row * nu) << 4, nb = min(16, rowbytes - b0);
+        int x = b0 / C, c = b0 - x * C;
+        unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if (k < nb) {
+                w[k >> 2] |= (unsigned)nv12_byte(src[(b * C + c) * plane + (size_t)y * W + x], st.mean[c], st.stdv[c], denorm) << (8 * (k & 3));
+                if (++c == C) { c = 0; ++x; }
+            }
+        }
+        unsigned char *o = dst + b * bstride + (size_t)y * pitch + (size_t)b0;
+        if (wide && nb == 16) {
+            *reinterpret_cast<uint4 *>(o) = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (k < nb) o[k] = (unsigned char)((w[k >> 2] >> (8 * (k & 3))) & 0xffu);
+        }
+    }
+}
+
+int launch_preprocess_u8_pitched(const unsigned char *src, size_t pitch, size_t bstride, float *dst, int B, int H, int W, int C, const float *mean,
+                                 const float *stdv, hipStream_t s)
+{
+    Stats4 st{};
+    for (int c = 0; c < C && c < 4; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
+    const int wide = mult_of(16, {(size_t)(uintptr_t)src, pitch, B > 1 ? bstride : 0});
+    const size_t total = (size_t)B * H * (((size_t)W * C + 15) / 16);
+    preprocess_u8_pitched_kernel<<<prepost_grid(total), 256, 0, s>>>(src, pitch, bstride, dst, B, H, W, C, wide, st);
+    return (int)hipGetLastError();
+}
+int launch_postprocess_u8_pitched(const float *src, unsigned char *dst, size_t pitch, size_t bstride, int B, int H, int W, int C, const double *mean,
+                                  const double *stdv, int denorm, hipStream_t s)
+{
+    Stats4d st{};
+    for (int c = 0; c < C && c < 4; ++c) { st.mean[c] = mean[c]; st.stdv[c] = stdv[c]; }
+    const int wide = mult_of(16, {(size_t)(uintptr_t)dst, pitch, B > 1 ? bstride : 0});
+    const size_t total = (size_t)B * H * (((size_t)W * C + 15) / 16);
+    postprocess_u8_pitched_kernel<<<prepost_grid(total), 256, 0, s>>>(src, dst, pitch, bstride, B, H, W, C, wide, st, denorm);
+    return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------

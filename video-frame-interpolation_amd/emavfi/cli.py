@@ -29,6 +29,16 @@ def _size(text):
     return h, w
 
 
+def _active_area(text):
+    if text == "auto":
+        return text
+    try:
+        t, l, h, w = (int(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError("auto or T,L,H,W expected, e.g. 88,0,544,1280") from None
+    return t, l, h, w
+
+
 def _rate(text):
     try:
         return y4m.parse_rate(text)
@@ -79,6 +89,13 @@ def parser() -> argparse.ArgumentParser:
                         "source frames keeps the earlier frame's samples (no default is claimed); excludes --reference-quirks")
     p.add_argument("--static-tolerance", type=float, default=None, metavar="FRACTION",
                    help="with --static-guard: samples that differ by at most FRACTION of full scale count as the same (default 0: bit-equal only)")
+    p.add_argument("--active-area", type=_active_area, default=None, metavar="auto|T,L,H,W",
+                   help="run the model on the active picture only and put the bars of the earlier frame back around every in-between frame: "
+                        "the rectangle top,left,height,width (top and bottom even, left and right multiples of 16 unless they are the frame's "
+                        "edge), or auto: black bars are found on the device, per chunk, and the rectangle only grows; excludes --scale / "
+                        "--size, --reference-quirks and --evaluate; no quality claim is made")
+    p.add_argument("--active-tolerance", type=float, default=None, metavar="FRACTION",
+                   help="with --active-area auto: samples up to FRACTION of full scale above black still count as bar (default 0)")
     p.add_argument("--ensemble", choices=("reverse", "flip", "full"), default=None,
                    help="test-time ensembling of every forward: the pair and the reversed pair (reverse: 2 forwards, symmetric in time), the "
                         "pair under the four mirrorings (flip: 4 forwards, equivariant under flips) or both (full: 8 forwards); no quality "
@@ -147,6 +164,17 @@ def _run(args) -> int:
         raise ValueError("--static-guard R: the radius must lie in 0..16")
     if args.static_tolerance is not None and not 0.0 <= args.static_tolerance <= 1.0:
         raise ValueError("--static-tolerance FRACTION: a fraction of full scale in 0..1")
+    if args.active_tolerance is not None:
+        if args.active_area != "auto":
+            raise ValueError("--active-tolerance needs --active-area auto: the tolerance belongs to the search for the bars")
+        if not 0.0 <= args.active_tolerance <= 1.0:     # false for a NaN
+            raise ValueError("--active-tolerance FRACTION: a fraction of full scale in 0..1")
+    if args.active_area is not None:
+        for given, name, why in ((args.scale is not None or args.size is not None, "--scale / --size", "the rectangle is cut from the frames as "
+                                  "staged"), (args.reference_quirks, "--reference-quirks", "the bars are exact source samples, which the "
+                                  "quirk's de-normalised frames are not"), (args.evaluate, "--evaluate", "a held-out frame is scored whole")):
+            if given:
+                raise ValueError(f"--active-area excludes {name}: {why}")
     if args.dedup_max_run is not None and args.dedup is None:
         raise ValueError("--dedup-max-run needs --dedup FRACTION")
     if args.border_mode is not None and args.border is None:
@@ -204,7 +232,9 @@ def _run(args) -> int:
                                ensemble=args.ensemble,
                                **(dict(border=args.border, border_mode=args.border_mode or "replicate") if args.border is not None else {}),
                                **(dict(agreement=args.agreement, agreement_radius=args.agreement_radius) if args.agreement is not None else {}),
-                               flow_scale=args.flow_scale, **(dict(light=args.light) if args.light is not None else {}))
+                               flow_scale=args.flow_scale, **(dict(light=args.light) if args.light is not None else {}),
+                               **(dict(active_area=args.active_area, active_tolerance=args.active_tolerance or 0.0)
+                                  if args.active_area is not None else {}))
         if args.evaluate:
             print(fi.evaluate(list(reader), every=args.every))      # evaluate() indexes the clip: all of it is held
             return 0
@@ -223,6 +253,7 @@ def _run(args) -> int:
                   + (f", {len(fi.duplicates)} duplicate frames dropped" if args.dedup is not None else "")
                   + (f", static guard held {100.0 * sum(fi.static_share) / max(len(fi.static_share), 1):.2f} % of the predictions' pixels on average"
                      if args.static_guard is not None else "")
+                  + (f", active area {fi.active_rect} = {100.0 * fi.active_share:.1f} % of the frame" if args.active_area is not None else "")
                   + (f", ensemble {args.ensemble}" if args.ensemble is not None else "")
                   + (f", border {args.border} {args.border_mode or 'replicate'}" if args.border is not None else "")
                   + (f", flow scale {args.flow_scale}" if args.flow_scale is not None else "")

@@ -6,6 +6,7 @@ fails, a RuntimeError is raised.  Nothing here imports the oracle.
 from __future__ import annotations
 
 import ctypes
+import numbers
 import os
 import collections
 import threading
@@ -76,6 +77,12 @@ _PROTOTYPES = {
     "emavfi_duplicate_flags": (c_int, [c_void_p, c_size_t, c_int, ctypes.c_uint, c_void_p, c_void_p, c_void_p]),
     "emavfi_static_guard_frames": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p] + [c_int] * 8
                                    + [ctypes.c_uint, c_void_p, c_void_p]),
+    "emavfi_active_bounds": (c_int, [c_void_p, c_size_t, c_size_t] + [c_int] * 7 + [ctypes.c_uint, c_void_p, c_void_p]),
+    "emavfi_fill_outside_frames": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_int, c_void_p] + [c_int] * 9 + [c_void_p]),
+    "emavfi_preprocess_u8_pitched": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p] + [c_int] * 4
+                                     + [POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]),
+    "emavfi_postprocess_u8_pitched": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t] + [c_int] * 4
+                                      + [POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_int, c_void_p]),
     "emavfi_flip_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "emavfi_ensemble_mean_f32": (c_int, [POINTER(c_void_p), POINTER(c_int), c_int, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "emavfi_border_pad_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
@@ -1440,6 +1447,155 @@ def static_guard_frames(dst, srcs, table, size, layout=LAYOUT_INTERLEAVED, C=1, 
                                                 int(radius), int(tol), counts.data_ptr() if counts is not None else None, _stream()),
               "emavfi_static_guard_frames")
     return dst
+
+
+# ---------------------------------------------------------------- the active picture (include/emavfi.h, "ACTIVE AREA DEFINITION")
+ACTIVE_ALIGN = (2, 16)     # a rectangle's rows / columns: multiples of these (ACTIVE_ALIGN_Y, ACTIVE_ALIGN_X of csrc/active_elem.h)
+
+
+def active_level_units(tolerance, depth=8, yuv=False, full_range=False) -> int:
+    """The `level` of active_bounds: black plus floor(tolerance * (2^depth - 1)); a sample above it is content.  Black is 16 << (depth - 8)
+    for a limited-range Y'CbCr format (`yuv` and not `full_range`) and 0 otherwise; `tolerance` a fraction of full scale in [0, 1].  Clipped to
+    2^depth - 1 (nothing is content there)."""
+    import math
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float)) or not 0.0 <= tolerance <= 1.0:
+        raise ValueError("active_level_units: tolerance must be a number in 0..1")
+    if isinstance(depth, bool) or depth not in (8, 10, 12, 16):
+        raise ValueError("active_level_units: depth must be 8, 10, 12 or 16")
+    full = (1 << depth) - 1
+    black = (16 << (depth - 8)) if (yuv and not full_range) else 0
+    return min(full, black + int(math.floor(float(tolerance) * full)))
+
+
+def active_rect(bounds, H, W):
+    """The rectangle (top, left, height, width) of a set of frame bounds [(top, bottom, left, right), ...] as active_bounds writes them:
+    their union, grown outward to even rows and to columns that are multiples of 16, clipped to the H x W frame.  An empty union - no
+    bounds, or no frame with content - and a rectangle that covers the frame give the whole frame, (0, 0, H, W).  Pure host integers."""
+    H, W = int(H), int(W)
+    top, bottom, left, right = H, 0, W, 0
+    for b in bounds:
+        t, bo, l, r = (int(v) for v in b)
+        top, bottom, left, right = min(top, t), max(bottom, bo), min(left, l), max(right, r)
+    if bottom <= top or right <= left:
+        return 0, 0, H, W
+    ay, ax = ACTIVE_ALIGN
+    top, left = top // ay * ay, left // ax * ax
+    bottom, right = min(H, -(-bottom // ay) * ay), min(W, -(-right // ax) * ax)
+    return top, left, bottom - top, right - left
+
+
+def active_rect_check(rect, H, W, what="active_area"):
+    """(top, left, height, width) as ints, validated as the harness takes an explicit rectangle: four integers, with area, inside the H x W
+    frame, top and bottom multiples of 2 and left and right multiples of 16 - a bottom or right edge may instead be the frame's own.  With
+    H and W None the frame is not known yet: only what can be said of the rectangle alone is checked.  ValueError names the rule."""
+    if (not isinstance(rect, (tuple, list)) or len(rect) != 4
+            or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in rect)):
+        raise ValueError(f"{what}: None (the whole frame), 'auto' or a rectangle (top, left, height, width) of integers expected, got {rect!r}")
+    top, left, height, width = (int(v) for v in rect)
+    if height < 1 or width < 1:
+        raise ValueError(f"{what}: the rectangle {(top, left, height, width)} has no area")
+    if top < 0 or left < 0 or (H is not None and (top + height > H or left + width > W)):
+        raise ValueError(f"{what}: the rectangle {(top, left, height, width)} leaves the frame" + (f" of {H} x {W}" if H is not None else ""))
+    ay, ax = ACTIVE_ALIGN
+    if top % ay or (H is not None and (top + height) % ay and top + height != H):
+        raise ValueError(f"{what}: top and bottom of {(top, left, height, width)} must be multiples of {ay} (the bottom may be the frame's): "
+                         "4:2:0 chroma crops at whole samples")
+    if left % ax or (W is not None and (left + width) % ax and left + width != W):
+        raise ValueError(f"{what}: left and right of {(top, left, height, width)} must be multiples of {ax} (the right may be the frame's): "
+                         "the pitched kernels keep their 16-byte accesses")
+    return top, left, height, width
+
+
+
+def active_bounds(img, level=0, depth=None, shift=0, out=None, device=None):
+    """Per image k the bounds {top, bottom, left, right} of its content (the active area definition of include/emavfi.h) -> int32 [n,4]; an
+    image without content gives {H, 0, W, 0}.  `img`: uint8 [n,H,W,C], C = 1 (a Y plane) or 3 (interleaved colour: any channel above `level`
+    counts), or 16-bit integer [n,H,W] planes whose samples are (word >> shift) & (2^depth - 1), depth 10, 12 or 16; a device tensor or pinned
+    host memory (`device` names the GPU), rows and batches may be strided.  `level`: a sample above it is content (active_level_units).
+    `out`: a contiguous int32 [n,4] device tensor to fill - every word is written whatever it held."""
+    import torch
+    p, pitch, bs, sb, (n, H, W, C) = _sample_image(img, "active_bounds(img)")
+    depth = (8 if sb == 1 else 16) if depth is None else int(depth)
+    dev = img.device if img.is_cuda else torch.device(device if device is not None else "cuda")
+    if out is None:
+        out = torch.empty(n, 4, dtype=torch.int32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (n, 4) and out.is_contiguous()):
+        raise ValueError("active_bounds: out must be a contiguous int32 [n,4] device tensor")
+    level = int(level)
+    if not 0 <= level < 2 ** 32:
+        raise ValueError("active_bounds: level must be a u32 in sample units")
+    with torch.cuda.device(dev):
+        check(load().emavfi_active_bounds(p, pitch, bs, n, H, W, C, sb, depth, int(shift), level, out.data_ptr(), _stream()),
+              "emavfi_active_bounds")
+    return out
+
+
+def fill_outside_frames(dst, srcs, table, size, rect, layout=LAYOUT_INTERLEAVED, C=1, sample_bytes=1):
+    """Puts the bars back: frame k of `dst` receives the samples of frame table[k] of `srcs` OUTSIDE `rect` = (top, left, height, width);
+    bytes inside it are neither read nor written (the active area definition of include/emavfi.h).  `dst` uint8 [n_dst, ...], `srcs` uint8
+    [n_srcs, ...]: device tensors or pinned host memory with the same dense frame shape, the bytes of `size` = (H, W) frames of `layout` (a
+    name of LAYOUTS or its code; C channels when interleaved); their first dimension may be strided.  16-bit frames travel as their bytes
+    with sample_bytes = 2.  The table is consumed before the call returns."""
+    import torch
+    H, W = (int(v) for v in size)
+    top, left, height, width = (int(v) for v in rect)
+    layout = LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+    for t, what in ((dst, "fill_outside_frames(dst)"), (srcs, "fill_outside_frames(srcs)")):
+        _pinned_or_cuda(t, what)
+        if t.dtype != torch.uint8 or t.dim() < 2 or t.numel() == 0 or not t[0].is_contiguous() or tuple(t.shape[1:]) != tuple(dst.shape[1:]):
+            raise ValueError(f"{what}: a non-empty uint8 [frames, ...] tensor with dense frames of dst's frame shape expected")
+    table = [int(v) for v in table]
+    if len(table) != dst.shape[0]:
+        raise ValueError(f"fill_outside_frames: {len(table)} table entries for {dst.shape[0]} destination frames")
+    if any(not 0 <= v < 2 ** 32 for v in table):
+        raise ValueError("fill_outside_frames: the table holds u32 indices into srcs")
+    fb = dst[0].numel()
+    want = H * W * int(sample_bytes) * (int(C) if layout == LAYOUT_INTERLEAVED else 3) // (1 if layout == LAYOUT_INTERLEAVED else 2)
+    if fb != want:
+        raise ValueError(f"fill_outside_frames: a frame of {fb} bytes is not a {H} x {W} frame of this layout ({want} bytes)")
+    stride = lambda t: t.stride(0) if t.shape[0] > 1 else fb     # a dimension of size 1 has no meaningful stride
+    arr = (ctypes.c_uint * len(table))(*table)
+    dev = next((t.device for t in (dst, srcs) if t.is_cuda), None) or torch.device("cuda")
+    with torch.cuda.device(dev):
+        check(load().emavfi_fill_outside_frames(dst.data_ptr(), stride(dst), len(table), srcs.data_ptr(), stride(srcs), srcs.shape[0],
+                                                ctypes.cast(arr, c_void_p), H, W, layout, int(C), int(sample_bytes), top, left, height, width,
+                                                _stream()), "emavfi_fill_outside_frames")
+    return dst
+
+
+def preprocess_u8_pitched(frames_hwc, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None, out=None):
+    """preprocess_u8 of the dense copy of `frames_hwc`, bit for bit, WITHOUT making that copy: uint8 [B,H,W,C] whose rows and batches may be
+    strided (a sub-rectangle of larger frames; pitches come from .stride()) -> fp32 [B,C,H,W].  A device tensor or pinned host memory
+    (`device` names the GPU); bytes between the rows are never read.  `out`: a contiguous fp32 [B,C,H,W] device tensor to fill."""
+    import torch
+    p, pitch, bs = _byte_image(frames_hwc, "preprocess_u8_pitched")
+    B, H, W, C = frames_hwc.shape
+    dev = frames_hwc.device if frames_hwc.is_cuda else torch.device(device if device is not None else "cuda")
+    m, s = _stats(mean, std, C)
+    if out is None:
+        out = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, C, H, W) and out.is_contiguous()):
+        raise ValueError("preprocess_u8_pitched: out must be a contiguous fp32 [B,C,H,W] device tensor")
+    with torch.cuda.device(dev):
+        check(load().emavfi_preprocess_u8_pitched(p, pitch, bs, out.data_ptr(), B, H, W, C, m, s, _stream()), "emavfi_preprocess_u8_pitched")
+    return out
+
+
+def postprocess_u8_pitched(frames_nchw, out, denormalize=True, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """postprocess_u8 into `out`, uint8 [B,H,W,C] whose rows and batches may be strided (a sub-rectangle of larger frames; a device tensor or
+    pinned host memory): the bytes postprocess_u8 would write into a dense tensor, bit for bit; bytes between the rows are left as they were."""
+    import torch
+    _require_cuda(frames_nchw)
+    x = _f32c(frames_nchw)
+    if x.dim() != 4:
+        raise ValueError("postprocess_u8_pitched: [B,C,H,W] tensor expected")
+    B, C, H, W = x.shape
+    p, pitch, bs = _byte_image(out, "postprocess_u8_pitched(out=)", (B, H, W, C))
+    m, s = _stats(mean, std, C, ctypes.c_double)
+    with torch.cuda.device(x.device):
+        check(load().emavfi_postprocess_u8_pitched(x.data_ptr(), p, pitch, bs, B, H, W, C, m, s, 1 if denormalize else 0, _stream()),
+              "emavfi_postprocess_u8_pitched")
+    return out
 
 
 # ---------------------------------------------------------------- test-time ensembling (include/emavfi.h, "ENSEMBLE DEFINITION")

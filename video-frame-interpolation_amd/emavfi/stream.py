@@ -148,6 +148,22 @@ of the picture as zero, which is mean grey after normalisation, so the in-betwee
 the frame.  Like ``ensemble`` it is passed with each call: the model's own attribute is neither read nor changed, ``None`` (default) leaves the
 decision to that attribute.  Everything behind the model - the post kernels, the static guard, scene holds, the resample assembly, the
 metrics - works on the cropped frames and is untouched.
+``active_area="auto" | (top, left, height, width)`` (opt-in; not in the reference, which interpolates the whole frame) runs every forward
+of ``run()`` on the active picture alone - a 2.39:1 film in a 16:9 container is a quarter black bars - and puts the bars back (the active
+area definition of include/emavfi.h): the pre / post kernels read and write views of the rectangle inside the staged and emitted frames
+(``bgr24``: emavfi_preprocess_u8_pitched / _postprocess_u8_pitched; the Y'CbCr entries are pitched already), the slots' fp32 tensors and the
+forward have the rectangle's size, and one ``emavfi_fill_outside_frames`` call per batch on the post lane copies the bars of the pair's
+EARLIER frame around every prediction (mode "resample": around every node frame) ahead of the static guard, the scene hold and the
+assembly, which see whole frames as before.  ``ensemble``, ``border``, ``flow_scale`` and ``agreement`` act on the cropped tensors; source
+frames are emitted untouched.  An explicit rectangle needs an even top and bottom and a left and right that are multiples of 16 (a bottom
+/ right edge may be the frame's) and costs no scan and no host wait; content outside it is not interpolated.  ``"auto"`` finds it in a
+pre-pass like ``dedup_threshold``'s, with which it shares the upload and the ONE host wait per ``run()`` (``prepass_waits``): every frame's
+bounds of samples above black + ``active_tolerance`` (a fraction of full scale; black is 16 << (depth - 8) for limited-range Y'CbCr, which
+is scanned on its Y plane; ``lib.active_level_units``) are taken by ``emavfi_active_bounds`` and joined and rounded on the host
+(``lib.active_rect``).  No bars, or none found: the plain path, byte for byte.  ``active_rect`` / ``active_share`` report the rectangle in
+force and its share of the frame's pixels.  Refused with ``reference_quirks=True``, ``scale`` / ``size``, ``zero_copy=True``, in
+``evaluate()`` and, for ``"auto"``, with ``world != 1``: out of scope, not for ever.  No quality claim is made: the model sees zero padding
+at the rectangle's edge where it saw the bar before (``border`` replicates the picture there instead).
 """
 from __future__ import annotations
 
@@ -275,6 +291,11 @@ class FrameInterpolator:
     border = None         # (N, mode) of the frame border of every forward (EMA_VFI.border); None: what the model's attribute says
     agreement = None      # (tol, radius) of the agreement guard of every forward (EMA_VFI.agreement); None: what the model's attribute says
     flow_scale = None     # the scale the flow of every forward is estimated at (EMA_VFI.flow_scale); None: what the model's attribute says
+    active = None         # "auto" or an explicit (top, left, height, width) (include/emavfi.h, "ACTIVE AREA DEFINITION"); None: the whole frame
+    active_rect = None    # the rectangle in force in the last run(): (top, left, height, width); None before a run and with active_area=None
+    active_share = 1.0    # its share of the frame's pixels
+    prepass_waits = 0     # host waits of the last run()'s pre-pass (dedup_threshold and active_area="auto" share one)
+    _act = None           # the rectangle in force where it is smaller than the frame, else None: the plain path
     _ag = None   # under `agreement`: the held pixel counts of the batch just predicted, int32 on the device, in prediction order
     _depth = 0   # bits per sample of a 16-bit-word pixel format ("p010": 10, ...); 0 for the byte formats
     _planar = _yuv8 = False
@@ -289,7 +310,7 @@ class FrameInterpolator:
                  static_guard: Optional[int] = None, static_tolerance: float = 0.0, ensemble: Optional[str] = None,
                  border: Optional[int] = None, border_mode: str = "replicate",
                  agreement: Optional[float] = None, agreement_radius: Optional[int] = None, shutter=None,
-                 flow_scale: Optional[int] = None, light: Optional[str] = None):
+                 flow_scale: Optional[int] = None, light: Optional[str] = None, active_area=None, active_tolerance: float = 0.0):
         if shutter is not None and mode != "resample":
             raise ValueError("shutter belongs to mode='resample': the exposure window is accumulated over the nodes of its time grid")
         if light is not None:
@@ -414,6 +435,31 @@ class FrameInterpolator:
             self.static_guard = static_guard
             self.static_tol = _lib.static_tolerance_units(static_tolerance, self._depth or 8)
         self.static_share = []   # per emitted prediction of the last run(): the share of its pixels the guard held
+        if isinstance(active_tolerance, bool) or not isinstance(active_tolerance, (int, float)) or not 0 <= active_tolerance <= 1:
+            raise ValueError("active_tolerance must be a number in [0, 1]: how far above black, as a fraction of full scale, a sample of the "
+                             "bars may lie (0: black itself only)")
+        if active_area is None:
+            if active_tolerance != 0:
+                raise ValueError("active_tolerance without active_area: the tolerance belongs to the search for the bars (pass active_area='auto')")
+        else:
+            if isinstance(active_area, str):
+                if active_area != "auto":
+                    raise ValueError(f"active_area must be None (the whole frame), 'auto' or a rectangle (top, left, height, width), got {active_area!r}")
+                self.active = "auto"
+            else:
+                # the frame is not known yet: what can be said of the rectangle alone, the rest when the first frame arrives
+                self.active = _lib.active_rect_check(active_area, None, None, "active_area")
+                if active_tolerance != 0:
+                    raise ValueError("active_tolerance with an explicit active_area: nothing is searched for (the tolerance belongs to 'auto')")
+            if reference_quirks:
+                raise ValueError("active_area with reference_quirks=True: the bars are the exact source samples, which the quirk's de-normalised "
+                                 "frames are not (pass reference_quirks=False)")
+            if scale is not None or size is not None:
+                raise ValueError("active_area with scale / size: the rectangle is found and cut on the frames as staged, a resize in between "
+                                 "is not supported")
+            if zero_copy:
+                raise ValueError("active_area with zero_copy=True: the bars are put back in device memory around frames that leave by copy")
+            self._active_level = _lib.active_level_units(active_tolerance, self._depth or 8, pixel_format != "bgr24", bool(yuv_full_range))
         if scale is not None and size is not None:
             raise ValueError("scale and size are mutually exclusive")
         if scale is not None and not scale > 0:
@@ -857,9 +903,40 @@ class FrameInterpolator:
         for a, b in zip(self._planes3(src), self._planes3(dst)):
             _lib.resize_u8(a.unsqueeze(-1), (b.shape[1], b.shape[2]), out=b.unsqueeze(-1), device=device)
 
+    def _cropped(self, luma, *chroma):
+        """the planes of whole frames - [n,H,W(,C)], 4:2:0 chroma [n,H/2,W/2(,2)] - cut to the active rectangle in force: views, whose
+        pitches the kernels take from .stride(); no rectangle in force: the planes as they are"""
+        if self._act is None:
+            return (luma, *chroma)
+        t, l, h, w = self._act
+        return (luma[:, t:t + h, l:l + w], *(c[:, t // 2:(t + h) // 2, l // 2:(l + w) // 2] for c in chroma))
+
+    def _x(self, slot, n):
+        """the normalised frames of a slot's first n staged frames: fp32 [n,C,H,W], or with an active rectangle in force [n,C,h,w] at the
+        front of the same storage"""
+        if self._act is None:
+            return slot["x"][:n]
+        C, (_, _, h, w) = slot["x"].shape[1], self._act
+        return slot["x"].view(-1)[:n * C * h * w].view(n, C, h, w)
+
+    def _set_active(self, rect):
+        """puts `rect` = (top, left, height, width) in force for the frames the slots were made for; a rectangle that is the frame is the
+        plain path"""
+        H, W = self._dst
+        rect = tuple(int(v) for v in rect)
+        self.active_rect, self.active_share = rect, rect[2] * rect[3] / float(H * W)
+        self._act = None if rect == (0, 0, H, W) else rect
+
+    def _bars(self, dst, srcs, table):
+        """on the post lane: frame k of `dst` (whole frames whose rectangle the post kernel has just written) receives the samples outside
+        the rectangle of frame table[k] of `srcs`, the source frames as staged"""
+        if self._act is not None and len(table):
+            layout, C, sb, _, _ = _lib.static_frame_format(self.pixel_format)
+            _lib.fill_outside_frames(dst[:len(table)], srcs, table, self._dst, self._act, layout=layout, C=C, sample_bytes=sb)
+
     def _pre_kernel(self, buf, out=None, device=None, resized=None):
         """`resized`: with scale / size, a buffer of frames at the destination size that also receives the resized bytes (planar frames
-        are resized into it first: without one, a fresh buffer is made)"""
+        are resized into it first: without one, a fresh buffer is made).  With an active rectangle in force the kernels read views of it."""
         size = self._dst if self._resize else None
         if self._planar:
             if size is not None:
@@ -867,14 +944,16 @@ class FrameInterpolator:
                     resized = torch.empty(buf.shape[0], size[0] * 3 // 2, size[1], dtype=torch.uint8, device=device if device is not None else buf.device)
                 self._resize_planar(buf, resized, device)
                 buf = resized
-            return _lib.preprocess_yuv420p(*self._planes3(buf), self._depth or 8, self.yuv["standard"], self.yuv["full_range"], device=device, out=out)
+            return _lib.preprocess_yuv420p(*self._cropped(*self._planes3(buf)), self._depth or 8, self.yuv["standard"], self.yuv["full_range"], device=device, out=out)
         if self._depth:
-            y, uv = self._planes16(buf)
+            y, uv = self._cropped(*self._planes16(buf))
             return _lib.preprocess_p010(y, uv, self._depth, self.yuv["standard"], self.yuv["full_range"], device=device, out=out)
         if self.pixel_format == "nv12":
-            y, uv = self._planes(buf)
+            y, uv = self._cropped(*self._planes(buf))
             return _lib.preprocess_nv12(y, uv, self.yuv["standard"], self.yuv["full_range"], device=device, out=out, size=size,
                                         resized_out=self._planes(resized) if resized is not None else None)
+        if self._act is not None:
+            return _lib.preprocess_u8_pitched(*self._cropped(buf), device=device, out=out)
         return _lib.preprocess_u8(buf, device=device, out=out, size=size, resized_out=resized)
 
     # ---- scene cuts (include/emavfi.h, "SCENE CUT DEFINITION"): signatures and flags on the pre lane, the hold on the post lane
@@ -938,21 +1017,28 @@ class FrameInterpolator:
         return _lib.resize_u8(src, self._dst).cpu().numpy()[0]
 
     def _post_kernel(self, x, denormalize, out=None):
+        """with an active rectangle in force `x` has its size and `out`, whole frames, is written inside it only"""
+        if self._act is not None and out is None:
+            raise ValueError("_post_kernel: with an active rectangle the frames to write into must be given")
         if self._planar:
             if out is None:
                 out = torch.empty(x.shape[0], x.shape[2] * 3 // 2, x.shape[3] * (2 if self._depth else 1), dtype=torch.uint8, device=x.device)
             _lib.postprocess_yuv420p(x, self._depth or 8, self.yuv["standard"], self.yuv["full_range"], denormalize=denormalize,
-                                     out=self._planes3(out))
+                                     out=self._cropped(*self._planes3(out)))
             return out
         if self._depth:
             if out is None:
                 out = torch.empty(x.shape[0], x.shape[2] * 3 // 2, x.shape[3] * 2, dtype=torch.uint8, device=x.device)
-            _lib.postprocess_p010(x, self._depth, self.yuv["standard"], self.yuv["full_range"], denormalize=denormalize, out=self._planes16(out))
+            _lib.postprocess_p010(x, self._depth, self.yuv["standard"], self.yuv["full_range"], denormalize=denormalize,
+                                  out=self._cropped(*self._planes16(out)))
             return out
         if self.pixel_format == "nv12":
             if out is None:
                 out = torch.empty(x.shape[0], x.shape[2] * 3 // 2, x.shape[3], dtype=torch.uint8, device=x.device)
-            _lib.postprocess_nv12(x, self.yuv["standard"], self.yuv["full_range"], denormalize=denormalize, out=self._planes(out))
+            _lib.postprocess_nv12(x, self.yuv["standard"], self.yuv["full_range"], denormalize=denormalize, out=self._cropped(*self._planes(out)))
+            return out
+        if self._act is not None:
+            _lib.postprocess_u8_pitched(x, *self._cropped(out), denormalize=denormalize)
             return out
         return _lib.postprocess_u8(x, denormalize=denormalize, out=out)
 
@@ -1067,7 +1153,7 @@ class FrameInterpolator:
         """on the drain: the held pixel counts `counts[i]` (a slot's pinned buffer, written behind the frames, ahead of `done`) for i in
         `idx`, as shares of a frame at the size the model runs at"""
         counts, area = counts.numpy(), float(self._dst[0] * self._dst[1])
-        return [int(counts[i]) / area for i in idx]
+        return [int(counts[i]) / area for i in idx]     # of the whole frame, also where the forward saw the active rectangle only
 
     # ---- the three lanes: the one place that orders a slot's readers and writers across the streams and the host
     def _lane_in(self, slot, nup, upload=True):
@@ -1167,7 +1253,7 @@ class FrameInterpolator:
                 if f.dtype != np.uint8 or f.ndim != 3 or f.shape != first.shape:
                     raise ValueError(f"FrameInterpolator.{what}: same-shape uint8 HWC frames expected")
 
-    def run(self, frames, rank: int = 0, world: int = 1, *, _emit_tail: bool = True, _base: int = 0) -> Iterator[np.ndarray]:
+    def run(self, frames, rank: int = 0, world: int = 1, *, _emit_tail: bool = True, _base: int = 0, _rect=None) -> Iterator[np.ndarray]:
         """Yields uint8 HWC frames (``pixel_format="nv12"``: uint8 [H*3/2, W] frames; ``"p010"`` / ``"p012"`` / ``"p016"``: uint16 [H*3/2, W]
         frames) in the order the reference's writer receives them.
 
@@ -1179,10 +1265,13 @@ class FrameInterpolator:
         follow it, not the reference's predictions-first order (``resample_plan``)."""
         if not (hasattr(frames, "__len__") and hasattr(frames, "__getitem__")):
             frames = list(frames)
+        if self.active == "auto" and world != 1:
+            raise ValueError("run: world > 1 with active_area='auto': a shard sees only its segment, and the ranks' rectangles would differ "
+                             "(pass the rectangle explicitly)")
         if self.mode == "resample":
             if self.dedup is not None and world != 1:
                 raise ValueError("run: world > 1 with dedup_threshold: a shard boundary is no anchor of the duplicate schedule (one process)")
-            yield from self._run_resample(frames, rank, world, _emit_tail, _base)
+            yield from self._run_resample(frames, rank, world, _emit_tail, _base, _rect)
             return
         n_total = len(frames)
         mine, lo, hi, tail = self.segment(n_total, self.interval, rank, world)
@@ -1200,6 +1289,11 @@ class FrameInterpolator:
         words = (lambda v: v.view(np.uint16)) if self._depth else (lambda v: v)
         self._alloc(first.shape)
         self._reset_reports()
+        self.prepass_waits = 0
+        if self.active is not None:
+            # "auto": the size of the forwards depends on the bounds, so the host reads them before it plans (one wait per run() call)
+            scan = self.active == "auto" and hi - 1 > lo and bool(pairs)
+            self._active_setup(self._prepass(frames, lo, hi - 1, False, True)[2] if scan else None, _rect)
         # ramp-up: with three or more batches to come the FIRST one is half-size - the GPU starts after five staged frames instead of
         # nine, and (64 pairs at batch 8: 4 + 7 x 8 + 4) the last one's drain is half as long; every other batch is full.  Per-sample
         # results do not depend on the batch a pair travels in (tests/test_gpu_parity.py::test_forward_config2_batch16_256)
@@ -1222,7 +1316,7 @@ class FrameInterpolator:
                             slot["d_src"][k].copy_(slot["h_in"][ia[k]], non_blocking=True)
                 slot["consumed"].record(self._pre)
             else:                                  # the staged frames are in d_in (the driver's upload)
-                b.x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=rz)             # distinct frames, normalised once
+                b.x = self._pre_kernel(slot["d_in"][:nup], out=self._x(slot, nup), resized=rz)          # distinct frames, normalised once
                 if self.scene is not None:
                     self._scene_decide(slot, slot["d_in"][:nup], ia, ib)
             b.src_here = self.quirks and not self.zero_copy and all(ia[k + 1] == ia[k] + 1 for k in range(b.n - 1))
@@ -1260,6 +1354,8 @@ class FrameInterpolator:
                     self._post_kernel(x1, True, out=slot["h_src"][:n])
             else:
                 self._post_kernel(flat, self.quirks, out=slot["d_pred"][:n * npred])
+                # with an active rectangle: the bars of the pair's earlier frame around every prediction, ahead of the guard and the hold
+                self._bars(slot["d_pred"], slot["d_in"][:nup], [ia[k] for k in range(n) for _ in range(npred)])
                 if self.static_guard is not None:
                     # every prediction of pair k against the pair's two source frames as emitted; d_in / d_rs are complete: the
                     # forward waited for the preprocess
@@ -1391,10 +1487,12 @@ class FrameInterpolator:
             return buf[:, :buf.shape[1] * 2 // 3].view(torch.int16)
         return self._planes(buf)[0].unsqueeze(-1) if self._yuv8 else buf
 
-    def _dedup_scan(self, frames, lo, hi):
-        """The pre-pass of a run() with dedup_threshold: frames lo .. hi go to the device in slot-sized batches (consecutive batches share one
-        frame), every consecutive pair is scored, flags and scores come back with ONE host wait.  Returns (flags, scores) of the pairs
-        (lo, lo + 1) .. (hi - 1, hi).  The frames cross PCIe here and again in the batch loop that follows."""
+    def _prepass(self, frames, lo, hi, dedup, active):
+        """The pre-pass of a run() whose plan depends on the frames - dedup_threshold (`dedup`), active_area="auto" (`active`) or both:
+        frames lo .. hi (hi > lo) go to the device in slot-sized batches (consecutive batches share one frame), every consecutive pair is
+        scored and / or every frame's bounds are taken, and the words come back with ONE host wait whichever were asked for.  Returns
+        (flags, scores, bounds): flags and scores of the pairs (lo, lo + 1) .. (hi - 1, hi), the bounds {top, bottom, left, right} of the frames
+        lo .. hi; what was not asked for is None.  The frames cross PCIe here and again in the batch loop that follows."""
         n = hi - lo
         cap = self._slots[0]["d_in"].shape[0]                   # >= 2 frames
         dd = getattr(self, "_dd", None)
@@ -1402,7 +1500,9 @@ class FrameInterpolator:
             size = max(n, dd["fs"].shape[1] if dd is not None else 0)
             dd = self._dd = {"cap": cap, "cells": torch.empty(cap - 1, _lib.SCENE_SIG_WORDS, dtype=torch.int32, device=self.device),
                              "fs": torch.zeros(2, size, dtype=torch.int32, device=self.device),
-                             "h_fs": torch.zeros(2, size, dtype=torch.int32).pin_memory(), "ready": torch.cuda.Event()}
+                             "h_fs": torch.zeros(2, size, dtype=torch.int32).pin_memory(),
+                             "ab": torch.zeros(size + 1, 4, dtype=torch.int32, device=self.device),
+                             "h_ab": torch.zeros(size + 1, 4, dtype=torch.int32).pin_memory(), "ready": torch.cuda.Event()}
         _, depth, shift = _lib.resample_sample_format(self.pixel_format)
         self._pre.wait_stream(torch.cuda.current_stream(self.device))     # buffers made on the caller's stream are used on the pre lane
         for bi, f0 in enumerate(range(lo, hi, cap - 1)):
@@ -1412,16 +1512,34 @@ class FrameInterpolator:
             with torch.cuda.stream(self._pre):
                 self._lane_in(slot, nfr)
                 img = self._dedup_image(slot["d_in"][:nfr])
-                cells = _lib.frame_diff_cells(img[:-1], img[1:], depth=depth, shift=shift, out=dd["cells"][:nfr - 1])
-                _lib.duplicate_flags(cells, self.dedup, flags=dd["fs"][0, f0 - lo:f1 - lo], scores=dd["fs"][1, f0 - lo:f1 - lo])
+                if dedup:
+                    cells = _lib.frame_diff_cells(img[:-1], img[1:], depth=depth, shift=shift, out=dd["cells"][:nfr - 1])
+                    _lib.duplicate_flags(cells, self.dedup, flags=dd["fs"][0, f0 - lo:f1 - lo], scores=dd["fs"][1, f0 - lo:f1 - lo])
+                if active:                                                  # the shared frame of two batches is written twice, alike
+                    _lib.active_bounds(img, self._active_level, depth=depth, shift=shift, out=dd["ab"][f0 - lo:f1 - lo + 1])
         with torch.cuda.stream(self._pre):
-            dd["h_fs"].copy_(dd["fs"], non_blocking=True)
+            if dedup:
+                dd["h_fs"].copy_(dd["fs"], non_blocking=True)
+            if active:
+                dd["h_ab"].copy_(dd["ab"], non_blocking=True)
             dd["ready"].record(self._pre)
-        dd["ready"].synchronize()                                         # the one host wait: the plan depends on the flags
-        got = dd["h_fs"].numpy()
-        return [int(v) for v in got[0, :n]], [int(v) & 0xFFFFFFFF for v in got[1, :n]]
+        dd["ready"].synchronize()                                         # the one host wait: the plan depends on these words
+        self.prepass_waits += 1
+        got, ab = dd["h_fs"].numpy(), dd["h_ab"].numpy()
+        return ([int(v) for v in got[0, :n]] if dedup else None, [int(v) & 0xFFFFFFFF for v in got[1, :n]] if dedup else None,
+                [tuple(int(v) & 0xFFFFFFFF for v in row) for row in ab[:n + 1]] if active else None)
 
-    def _run_resample(self, frames, rank, world, emit_tail, base):
+    def _active_setup(self, bounds, carry):
+        """Puts the rectangle of this run() in force: the explicit one, now validated against the frame, or under "auto" the rectangle of
+        `bounds` (the pre-pass's; None: no pair to predict) joined with `carry`, the rectangle run_chunked carries from the chunks before."""
+        H, W = self._dst
+        if self.active != "auto":
+            self._set_active(_lib.active_rect_check(self.active, H, W, "active_area"))
+            return
+        held = [(carry[0], carry[0] + carry[2], carry[1], carry[1] + carry[3])] if carry is not None else []
+        self._set_active(_lib.active_rect(list(bounds or ()) + held, H, W))
+
+    def _run_resample(self, frames, rank, world, emit_tail, base, rect=None):
         from .dist import shard_range
         n_total = len(frames)
         if n_total <= 0:
@@ -1442,9 +1560,14 @@ class FrameInterpolator:
         self._alloc(first.shape)
         self._reset_reports()
         kept = list(range(a, b + 1)) if b > a else []
-        if self.dedup is not None and b > a:
-            # the set of forwards depends on the flags: the host reads them before it plans (one wait per run() call)
-            flags, scores = self._dedup_scan(frames, a, b)
+        self.prepass_waits = 0
+        flags = scores = bounds = None
+        if b > a and (self.dedup is not None or self.active == "auto"):
+            # the set of forwards depends on the flags, their size on the bounds: the host reads both before it plans (one wait per run() call)
+            flags, scores, bounds = self._prepass(frames, a, b, self.dedup is not None, self.active == "auto")
+        if self.active is not None:
+            self._active_setup(bounds, rect)
+        if flags is not None:
             kept = [a + t for t in self.dedup_kept(flags, b - a + 1, base + a, self.dedup_max_run, self.dedup_span)]
             self.dedup_scores = [(base + a + 1 + i, sc) for i, sc in enumerate(scores)]
             keep = set(kept)
@@ -1474,7 +1597,7 @@ class FrameInterpolator:
             slot, nup, (ia, ib) = b.slot, b.nup, b.rows
             b.levels, b.table, b.n_nodes, b.depths = self._resample_batch(b.chunk, outs_of, ia, ib)
             b.rs = slot["d_rs"][:nup] if slot["d_rs"] is not None else None
-            b.x = self._pre_kernel(slot["d_in"][:nup], out=slot["x"][:nup], resized=b.rs)
+            b.x = self._pre_kernel(slot["d_in"][:nup], out=self._x(slot, nup), resized=b.rs)
             if self.scene is not None:
                 self._scene_decide(slot, slot["d_in"][:nup], ia, ib)
 
@@ -1493,9 +1616,11 @@ class FrameInterpolator:
                 off += m.shape[0]
             assert off == b.n_nodes
             b.first_node = []
+            gap_of = [k for lv in b.levels for k, _ in lv]
+            # with an active rectangle: the bars of its gap's earlier kept frame around every node frame, ahead of the guard and the assembly
+            self._bars(slot["d_node"], slot["d_in"][:nup], [ia[k] for k in gap_of])
             if self.static_guard is not None and off:
                 # every node frame against its gap's two kept source frames, before the outputs are selected or blended
-                gap_of = [k for lv in b.levels for k, _ in lv]
                 self._static_hold(slot, slot["d_node"], rs if rs is not None else slot["d_in"][:nup], [(ia[k], ib[k]) for k in gap_of])
                 first = {}
                 for i, k in enumerate(gap_of):
@@ -1557,13 +1682,19 @@ class FrameInterpolator:
         ``chunk_pairs * frame_interval + 1`` source frames: the stream is cut as ``chunk_plan`` says, each chunk goes through ``run()``,
         and the tail frame of every chunk but the last is neither yielded nor computed.  ``scene_cuts`` / ``scene_scores`` (and ``duplicates`` /
         ``dedup_scores``) accumulate over the chunks with global frame indices.  With ``dedup_threshold`` set, ``chunk_pairs`` must be a
-        multiple of ``dedup_span``, and every chunk costs one host wait.  Single process: a stream of unknown length cannot be sharded over ranks."""
+        multiple of ``dedup_span``, and every chunk costs one host wait.  Single process: a stream of unknown length cannot be sharded over ranks.
+        With an explicit ``active_area`` the yielded bytes are always ``run()``'s.  With ``active_area="auto"`` every chunk is scanned on its
+        own (one host wait each, shared with ``dedup_threshold``'s) and its rectangle is joined with the one carried from the chunks before:
+        the rectangle never shrinks, and content that first appears outside it lies inside the rectangle of its own chunk, so none is lost.
+        The yielded bytes then equal ``run()``'s exactly when the first chunk already shows the final rectangle; ``active_rect`` /
+        ``active_share`` are the last chunk's."""
         if isinstance(chunk_pairs, bool) or not isinstance(chunk_pairs, int) or chunk_pairs < 1:
             raise ValueError("run_chunked: chunk_pairs must be an integer >= 1")
         if self.dedup is not None and chunk_pairs % self.dedup_span:
             raise ValueError(f"run_chunked: chunk_pairs = {chunk_pairs} with dedup_threshold must be a multiple of dedup_span = {self.dedup_span}: "
                              "every chunk then starts and ends on a frame that is kept regardless, and sees what the whole clip would")
         L, it, held, lo = chunk_pairs * self.interval, iter(frames), [], 0
+        carry, waits = None, 0
         total = {name: [] for name in self._REPORTS}
         self._reset_reports()
         while True:
@@ -1575,7 +1706,11 @@ class FrameInterpolator:
             if held:
                 self._reset_reports()                           # this chunk's own, whatever run() does with them
                 # mode "resample": the time grid is global, so a chunk is told where it starts
-                yield from self.run(held, _emit_tail=final, **({"_base": lo} if self.mode == "resample" else {}))
+                # active_area="auto": the rectangle in force so far is joined with this chunk's, so it never shrinks
+                yield from self.run(held, _emit_tail=final, **({"_base": lo} if self.mode == "resample" else {}),
+                                    **({"_rect": carry} if self.active == "auto" else {}))
+                carry, waits = self.active_rect, waits + self.prepass_waits
+                self.prepass_waits = waits
                 for name in self._REPORTS:
                     mine = getattr(self, name)
                     if name in ("scene_cuts", "scene_scores"):  # the chunk's own frame indices; duplicates / dedup_scores are global already
@@ -1606,6 +1741,9 @@ class FrameInterpolator:
         the ranks' ``targets`` concatenated in rank order are the single-process result."""
         if self._depth:
             raise ValueError(f"evaluate() with pixel_format={self.pixel_format!r}: the metric kernel reads bytes (16-bit frames are not scored)")
+        if self.active is not None:
+            raise ValueError("evaluate() with active_area: a held-out frame is scored whole, and the bars would score as perfect (use a "
+                             "harness without it)")
         if self.shutter is not None:
             raise ValueError("evaluate() with a shutter: a held-out frame is an instantaneous sample, an accumulated one is not comparable to it")
         if not (hasattr(frames, "__len__") and hasattr(frames, "__getitem__")):
