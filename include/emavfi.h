@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_active_bounds, emavfi_fill_outside_frames, emavfi_preprocess_u8_pitched, emavfi_postprocess_u8_pitched added (the forward run on the active picture only: black bars found on the device and put back around every prediction; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_transfer_table, emavfi_transfer_table_check, emavfi_accumulate_frames_linear added (blended and motion-blurred frames mixed in linear light through a transfer table, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_downscale_f32, emavfi_upsample_flow_f32, emavfi_forward_flow, emavfi_forward_given_flow (and their two launch lists) added (the flow estimated on frames reduced by 2, 4 or 8 for motion beyond seven pixels, the forward split at its flow; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_accumulate_frames added (motion blur from a shutter angle: every output frame the weighted integer mean of the node frames inside its exposure window, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_agreement_guard_f32 added (where the two time directions of the ensemble disagree the plain blend of the source frames is emitted, decided on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
+#define EMAVFI_VERSION 403 /* 0.4.3: emavfi_align_signature_f32, emavfi_align_workspace_bytes, emavfi_align_search, emavfi_shift_f32 added (global motion compensated before the forward: one translation per pair, found and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_active_bounds, emavfi_fill_outside_frames, emavfi_preprocess_u8_pitched, emavfi_postprocess_u8_pitched added (the forward run on the active picture only: black bars found on the device and put back around every prediction; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_transfer_table, emavfi_transfer_table_check, emavfi_accumulate_frames_linear added (blended and motion-blurred frames mixed in linear light through a transfer table, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_downscale_f32, emavfi_upsample_flow_f32, emavfi_forward_flow, emavfi_forward_given_flow (and their two launch lists) added (the flow estimated on frames reduced by 2, 4 or 8 for motion beyond seven pixels, the forward split at its flow; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_accumulate_frames added (motion blur from a shutter angle: every output frame the weighted integer mean of the node frames inside its exposure window, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_agreement_guard_f32 added (where the two time directions of the ensemble disagree the plain blend of the source frames is emitted, decided on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_border_pad_f32, emavfi_border_crop_f32 added (frames extended past their edges by replication or reflection before the forward and cropped after it, on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_flip_f32, emavfi_ensemble_mean_f32 added (test-time ensembling over time reversal and flips: the mirrored inputs and the tree mean of the members on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_static_guard_frames added (static regions of a pair held on the device: overlays, subtitles, letterbox bars; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_diff_cells, emavfi_duplicate_flags added (duplicate frames found on the device, so that the resampler interpolates across the gap; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resample_frames added (output frames at any rate assembled from source and node frames on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_preprocess_yuv420p, emavfi_postprocess_yuv420p added (planar 4:2:0 frames, 8 / 10 / 12 / 16 bits, as software decoders and Y4M hold them; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_frame_metrics_workspace_bytes, emavfi_frame_metrics_u8 added (held-out PSNR / SSIM scored on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_luma_signature_u8, emavfi_scene_flags, emavfi_hold_frames_u8 added (scene cuts decided and applied on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_resize_u8, emavfi_preprocess_u8_resized, emavfi_preprocess_nv12_resized added (frames resized on the device; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_yuv_coefficients, emavfi_preprocess_nv12, emavfi_postprocess_nv12 added (NV12 frames; same version: the packed layout is unchanged, cached blobs stay valid); emavfi_forward_census, emavfi_mdcn_census (round 6; the workspace grows by 8 KiB, the packed layout is unchanged); emavfi_forward_profiled / _staged and emavfi_mdcn_profiled later folded into emavfi_forward_routed / emavfi_mdcn_routed (same version: the packed layout is unchanged); 0.4.2: emavfi_forward_staged, emavfi_mdcn_profiled (round 5; the packed layout is 0.4.1's, but a blob says which library packed it: re-pack); 0.4.1: context_encoding.1 / .2 re-packed for conv_wreg.inl; 0.4.0: the packed blob starts with a 256-byte self-describing header, emavfi_forward takes packed_bytes (round 4): re-pack */
 
 #define EMAVFI_F32 0
 #define EMAVFI_BF16 1
@@ -1028,6 +1028,65 @@ int emavfi_forward_flow_launches(int in_channels, int mid_channels, int num_bloc
                                  char *names, size_t names_bytes, double *flops, double *bytes, int capacity);
 int emavfi_forward_given_flow_launches(int in_channels, int mid_channels, int num_blocks, int B, int H, int W, int dtype, unsigned gather_blocks,
                                        char *names, size_t names_bytes, double *flops, double *bytes, int capacity);
+
+/* Global motion.  A flow value of the forward depends on nothing farther than 7 pixels away (see "Coarse flow" above), while the largest
+ * motion of real video is usually the camera's - a pan, a tilt, a tracking shot - and that motion is global.  It can be removed exactly, by
+ * integer moves of words, before the model sees the pair; what is left (a residual of at most 2 pixels per axis, plus the objects' own
+ * motion) is what the 7-pixel reach was built for.  The reference has no such step; this is an addition, off unless asked for, and no quality
+ * claim is made.  The composition lives in the Python layer (EMA_VFI.align); the four entries here are the device work a C integrator needs
+ * beside emavfi_forward_routed.  Nothing waits on the host: the shift is decided on the device and read there by the kernel that applies it.
+ *
+ * ALIGN DEFINITION (the one place).  This is the project's own definition: it claims agreement with no outside tool.  Every decision is
+ *   taken in integers, so host, oracle and device agree bit for bit.  The inputs are two normalised fp32 batches a, b of [B][3][H][W].
+ *   EMAVFI_ALIGN_CELL = 4.  Hc = H / 4, Wc = W / 4 (floor): the remainder rows and columns at the bottom and right are not looked at.
+ *   1. Signature.  Per pixel l = (x0 + x1) + x2 of its three channels in fp32, in that order, then t = l * 64.0f.  q = 0 where !(t >= -512)
+ *      (a NaN included), q = 1023 where t >= 512, else q = (int)floorf(t) + 512.  G[i][j] is the sum of the 16 q of cell (i, j): 0..16368,
+ *      stored as uint16, dense [B][Hc][Wc].
+ *   2. Scores.  The radius R is in cells: R in 1..EMAVFI_ALIGN_MAX_RADIUS = 32 and 2 R <= min(Hc, Wc), so every candidate keeps at least
+ *      half of each axis.  Candidates are d = (dy, dx), each component in [-R, R].  SAD(d) = sum |Ga[i][j] - Gb[i + dy][j + dx]| over the
+ *      cells where both indices are inside the grid; N(d) = (Hc - |dy|)(Wc - |dx|); m(d) = floor(SAD(d) * 256 / N(d)) in unsigned 64-bit
+ *      (SAD <= 16368 * 4096 * 4096, m <= 4 190 208).  d is the displacement of the content from a to b.
+ *   3. Choice.  Of the candidates with the least m take those with the least |dy| + |dx|, of these those with the least |dy|.  If more
+ *      than one is left (they differ only in signs), d* = (0, 0).  Acceptance: a non-zero d* is kept only if m(d*) * 1024 <= m(0) * ratio,
+ *      ratio in 0..EMAVFI_ALIGN_MAX_RATIO = 1024; otherwise d* = (0, 0).  The record of a sample is four int32 words
+ *      {4 dy*, 4 dx*, m(d*), m(0)}: the first two are pixels.
+ *   4. Shift.  h = d_px / 2, exact since d_px is a multiple of 4.  a'[c][y][x] = a[c][cy(y - hy)][cx(x - hx)] and
+ *      b'[c][y][x] = b[c][cy(y + hy)][cx(x + hx)], cy and cx clamping to 0..H-1 and 0..W-1 (replication).  Pure moves of 32-bit words:
+ *      every bit pattern survives.  Both frames are moved into the midpoint's coordinates, so the output needs no shift back, and every
+ *      sample of a batch keeps H x W whatever its own shift is.
+ *   5. The aligned forward is M(a', b'), M being the forward the model would otherwise run (plain, ensembled, bordered, coarse, guarded)
+ *      with (a', b') as its pair in every role, the agreement guard's source blend included.
+ *   Consequences (each one is tested):
+ *   - SAD_(b,a)(d) = SAD_(a,b)(-d), N and the order of step 3 are symmetric under negation, so d*(b, a) = -d*(a, b) and forward(b, a) runs
+ *     on (b', a'): the exact time symmetry of the "reverse" and "full" ensembles survives bit for bit.
+ *   - If b is a translated by a multiple of 4 pixels within the radius, a' == b' bit for bit at every position whose source indices were
+ *     not clamped.
+ *   - A rejected or zero shift is the plain path, byte for byte.
+ *   - A constant frame, or a pattern whose minima tie under sign changes (stripes of period 2 cells), gives d* = 0.
+ *
+ * emavfi_align_signature_f32: sig = G of step 1 for the B samples of x.  H and W in 8..16384; x fp32 [B][3][H][W], 4-byte aligned; sig
+ *   uint16 [B][H / 4][W / 4], 2-byte aligned.  16-byte loads of the three planes where W % 4 == 0 and x is 16-byte aligned, scalar loads
+ *   through the same per-element functions (csrc/align_elem.h) otherwise.
+ * emavfi_align_workspace_bytes: the bytes emavfi_align_search needs for B samples at radius R (B (2R + 1)^2 64-bit sums); 0 for a B < 1
+ *   or an R outside 1..32.
+ * emavfi_align_search: shifts[b] = the record of steps 2 and 3 for sample b of the two signature batches.  Hc, Wc in 2..4096 cells;
+ *   workspace 8-byte aligned; shifts device int32 [B][4].  The entry clears its workspace on `stream` itself: the result does not depend
+ *   on what the workspace held before.  The sums are integer atomics: the result is the same in every run.
+ * emavfi_shift_f32: dst[b] = src[b] moved by sign * (shifts[4b] >> 1, shifts[4b + 1] >> 1) as in step 4: dst[b][c][y][x] =
+ *   src[b][c][cy(y - sign * hy)][cx(x - sign * hx)]; sign = +1 makes a' of a, sign = -1 makes b' of b.  H, W in 1..16384.  `shifts` is read
+ *   from DEVICE memory by the kernel; words 2 and 3 of a record are not looked at.  The kernel is memory-safe for any content of `shifts`:
+ *   the half-shift is clamped to +-16384 before any index arithmetic.  dst may not overlap src.
+ * All: nothing is allocated, nothing synchronises, all work goes on `stream`.  EMAVFI_E_ARG (never an abort), the message naming the
+ *   argument: a null or misaligned pointer; B or C below 1; a dimension out of range; R outside 1..32 or 2 R > min(Hc, Wc); ratio outside
+ *   0..1024; a workspace that is too small; sign other than +-1; dst overlapping src; size arithmetic that overflows size_t. */
+#define EMAVFI_ALIGN_CELL 4
+#define EMAVFI_ALIGN_MAX_RADIUS 32
+#define EMAVFI_ALIGN_MAX_RATIO 1024
+int emavfi_align_signature_f32(const float *x, unsigned short *sig, int B, int H, int W, void *stream);
+size_t emavfi_align_workspace_bytes(int B, int R);
+int emavfi_align_search(const unsigned short *sig_a, const unsigned short *sig_b, int B, int Hc, int Wc, int R, int ratio, void *workspace,
+                        size_t workspace_bytes, int *shifts, void *stream);
+int emavfi_shift_f32(const float *src, float *dst, int B, int C, int H, int W, const int *shifts, int sign, void *stream);
 
 /* Agreement guard.  Every other guard here decides from the SOURCE frames (cuts, duplicates, static regions, borders); nothing protects
  * against the model being wrong.  The forward estimates one flow and warps only frame2, and on large motion, occlusions and repetitive

@@ -12,6 +12,7 @@
 #include "active_elem.h"
 #include "ensemble_elem.h"
 #include "border_elem.h"
+#include "align_elem.h"
 #include "coarse_elem.h"
 #include "agreement_elem.h"
 #include "conv_first.inl"
@@ -2278,6 +2279,86 @@ int emavfi_border_crop_f32(const float *src, float *dst, size_t planes, int H, i
     if (const int rc = ensemble_pointer_check(what, "dst", -1, dst, picture); rc != EMAVFI_OK) return rc;
     if (const int rc = border_overlap_check(what, src, padded, dst, picture); rc != EMAVFI_OK) return rc;
     EMAVFI_TRY(launch_border_crop_f32(src, dst, planes, H, W, N, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+// ---- global motion (include/emavfi.h, "ALIGN DEFINITION"): every check runs on the host, before any work goes on the stream
+static_assert(EMAVFI_ALIGN_CELL == ALIGN_CELL && EMAVFI_ALIGN_MAX_RADIUS == ALIGN_MAX_RADIUS && EMAVFI_ALIGN_MAX_RATIO == ALIGN_MAX_RATIO
+              && EMAVFI_RESIZE_MAX_DIM == ALIGN_MAX_DIM, "header and align_elem.h disagree");
+
+// a tensor of `bytes` bytes at p whose elements are `align` bytes wide
+static int align_pointer_check(const char *what, const char *name, const void *p, size_t bytes, unsigned align)
+{
+    if (!p) return fail(EMAVFI_E_ARG, "%s: null pointer %s", what, name);
+    if ((uintptr_t)p & (align - 1)) return fail(EMAVFI_E_ARG, "%s: the pointer %s must be %u-byte aligned", what, name, align);
+    if ((uintptr_t)p + bytes < (uintptr_t)p) return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (%s wraps the address space)", what, name);
+    return EMAVFI_OK;
+}
+
+int emavfi_align_signature_f32(const float *x, unsigned short *sig, int B, int H, int W, void *stream)
+{
+    const char *const what = "align_signature_f32";
+    if (B < 1) return fail(EMAVFI_E_ARG, "%s: B = %d (B must be >= 1)", what, B);
+    if (!align_sig_dim_ok(H) || !align_sig_dim_ok(W))
+        return fail(EMAVFI_E_ARG, "%s: H, W = %d, %d (each must lie in %d..%d)", what, H, W, ALIGN_MIN_DIM, ALIGN_MAX_DIM);
+    size_t x_bytes, sig_bytes;
+    if (__builtin_mul_overflow((size_t)B, (size_t)3 * H * W * sizeof(float), &x_bytes)
+        || __builtin_mul_overflow((size_t)B, (size_t)align_cells(H) * align_cells(W) * sizeof(unsigned short), &sig_bytes))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (B %d)", what, B);
+    if (const int rc = align_pointer_check(what, "x", x, x_bytes, 4); rc != EMAVFI_OK) return rc;
+    if (const int rc = align_pointer_check(what, "sig", sig, sig_bytes, 2); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_align_signature_f32(x, sig, B, H, W, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+size_t emavfi_align_workspace_bytes(int B, int R)
+{
+    if (B < 1 || !align_radius_ok(R)) return 0;
+    size_t bytes;
+    if (__builtin_mul_overflow((size_t)B, (size_t)align_candidates(R) * sizeof(unsigned long long), &bytes)) return 0;
+    return bytes;
+}
+
+int emavfi_align_search(const unsigned short *sig_a, const unsigned short *sig_b, int B, int Hc, int Wc, int R, int ratio, void *workspace,
+                        size_t workspace_bytes, int *shifts, void *stream)
+{
+    const char *const what = "align_search";
+    if (B < 1) return fail(EMAVFI_E_ARG, "%s: B = %d (B must be >= 1)", what, B);
+    if (!align_grid_dim_ok(Hc) || !align_grid_dim_ok(Wc))
+        return fail(EMAVFI_E_ARG, "%s: Hc, Wc = %d, %d (each must lie in %d..%d cells)", what, Hc, Wc, ALIGN_MIN_DIM / ALIGN_CELL, ALIGN_MAX_DIM / ALIGN_CELL);
+    if (!align_radius_ok(R)) return fail(EMAVFI_E_ARG, "%s: R = %d (R must lie in 1..%d cells: EMAVFI_ALIGN_MAX_RADIUS)", what, R, ALIGN_MAX_RADIUS);
+    if (!align_radius_fits(R, Hc, Wc))
+        return fail(EMAVFI_E_ARG, "%s: R = %d with a grid of %d x %d cells (2 R must not exceed min(Hc, Wc))", what, R, Hc, Wc);
+    if (!align_ratio_ok(ratio)) return fail(EMAVFI_E_ARG, "%s: ratio = %d (ratio must lie in 0..%d: EMAVFI_ALIGN_MAX_RATIO)", what, ratio, ALIGN_MAX_RATIO);
+    size_t sig_bytes;
+    if (__builtin_mul_overflow((size_t)B, (size_t)Hc * Wc * sizeof(unsigned short), &sig_bytes))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (B %d)", what, B);
+    const size_t need = emavfi_align_workspace_bytes(B, R);
+    if (need == 0) return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (B %d)", what, B);
+    if (const int rc = align_pointer_check(what, "sig_a", sig_a, sig_bytes, 2); rc != EMAVFI_OK) return rc;
+    if (const int rc = align_pointer_check(what, "sig_b", sig_b, sig_bytes, 2); rc != EMAVFI_OK) return rc;
+    if (const int rc = align_pointer_check(what, "workspace", workspace, need, 8); rc != EMAVFI_OK) return rc;
+    if (workspace_bytes < need)
+        return fail(EMAVFI_E_ARG, "%s: workspace_bytes = %zu is too small (emavfi_align_workspace_bytes gives %zu)", what, workspace_bytes, need);
+    if (const int rc = align_pointer_check(what, "shifts", shifts, (size_t)B * 4 * sizeof(int), 4); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_align_search(sig_a, sig_b, B, Hc, Wc, R, ratio, (unsigned long long *)workspace, shifts, (hipStream_t)stream), what);
+    return EMAVFI_OK;
+}
+
+int emavfi_shift_f32(const float *src, float *dst, int B, int C, int H, int W, const int *shifts, int sign, void *stream)
+{
+    const char *const what = "shift_f32";
+    if (B < 1 || C < 1) return fail(EMAVFI_E_ARG, "%s: B, C = %d, %d (each must be >= 1)", what, B, C);
+    if (!align_dim_ok(H) || !align_dim_ok(W)) return fail(EMAVFI_E_ARG, "%s: H, W = %d, %d (each must lie in 1..%d)", what, H, W, ALIGN_MAX_DIM);
+    if (!align_sign_ok(sign)) return fail(EMAVFI_E_ARG, "%s: sign = %d (sign must be +1 or -1)", what, sign);
+    size_t planes, bytes;
+    if (__builtin_mul_overflow((size_t)B, (size_t)C, &planes) || __builtin_mul_overflow(planes, (size_t)H * W * sizeof(float), &bytes))
+        return fail(EMAVFI_E_ARG, "%s: the size arithmetic overflows (B %d, C %d)", what, B, C);
+    if (const int rc = align_pointer_check(what, "src", src, bytes, 4); rc != EMAVFI_OK) return rc;
+    if (const int rc = align_pointer_check(what, "dst", dst, bytes, 4); rc != EMAVFI_OK) return rc;
+    if (const int rc = align_pointer_check(what, "shifts", shifts, (size_t)B * 4 * sizeof(int), 4); rc != EMAVFI_OK) return rc;
+    if (const int rc = border_overlap_check(what, src, bytes, dst, bytes); rc != EMAVFI_OK) return rc;
+    EMAVFI_TRY(launch_shift_f32(src, dst, B, C, H, W, shifts, sign, (hipStream_t)stream), what);
     return EMAVFI_OK;
 }
 

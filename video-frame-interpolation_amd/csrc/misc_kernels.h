@@ -156,6 +156,13 @@ int launch_ensemble_mean_f32(const float *const *members, const int *flips, int 
 // frame borders (include/emavfi.h, "BORDER DEFINITION"): arguments already validated; H, W are the picture's size in both
 int launch_border_pad_f32(const float *src, float *dst, size_t planes, int H, int W, int N, int mode, hipStream_t s);
 int launch_border_crop_f32(const float *src, float *dst, size_t planes, int H, int W, int N, hipStream_t s);
+// global motion (include/emavfi.h, "ALIGN DEFINITION"): arguments already validated.  launch_align_search clears `sad`
+// ([B][2R + 1][2R + 1] u64) with a launch of its own, adds into it and finishes each sample's record; launch_shift_f32's kernel reads the records
+// from device memory
+int launch_align_signature_f32(const float *x, unsigned short *sig, int B, int H, int W, hipStream_t s);
+int launch_align_search(const unsigned short *sig_a, const unsigned short *sig_b, int B, int Hc, int Wc, int R, int ratio, unsigned long long *sad,
+                        int *shifts, hipStream_t s);
+int launch_shift_f32(const float *src, float *dst, int B, int C, int H, int W, const int *shifts, int sign, hipStream_t s);
 // coarse flow (include/emavfi.h, "COARSE FLOW DEFINITION"): arguments already validated; H, W are the FINE tensor's size in both, the
 // coarse one is ceil(H / s) x ceil(W / s)
 int launch_coarse_down_f32(const float *src, float *dst, size_t planes, int H, int W, int s, hipStream_t st);

@@ -11,6 +11,7 @@
 #include "active_elem.h"
 #include "ensemble_elem.h"
 #include "border_elem.h"
+#include "align_elem.h"
 #include "coarse_elem.h"
 #include "agreement_elem.h"
 #include "metrics_elem.h"
@@ -3872,5 +3873,280 @@ __global__ void route_state_init_kernel(unsigned *__restrict__ state, unsigned m
 int launch_route_state_init(void *state, unsigned magic, int nblocks, unsigned start_gather, hipStream_t s)
 {
     route_state_init_kernel<<<1, 32, 0, s>>>((unsigned *)state, magic, (unsigned)nblocks, start_gather);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Global motion (include/emavfi.h, "ALIGN DEFINITION"; per-element functions: align_elem.h).
+//   align_signature_f32_kernel  sig [B][Hc][Wc] u16 = the sum of the 16 quantised lumas of each 4 x 4 cell.  A lane owns one whole cell: grid
+//                          (cells / 256, samples - at most 65535 rows of the grid, a workgroup walks the samples beyond), 256 threads, pure
+//                          streaming.  Wide form (W % 4 == 0 and x 16-byte aligned, so every plane, row and cell starts on a 16-byte
+//                          boundary): a cell is 12 16-byte loads - 4 rows of 3 planes, issued together -, neighbouring lanes read
+//                          neighbouring 16 bytes.  Scalar form: 48 loads through the same align_q().  The remainder rows and columns of a
+//                          frame that is no multiple of 4 are never read.
+//   align_search_kernel    SAD[b][dy][dx] += the absolute differences of one tile: a workgroup takes (sample, dy, 32 rows x 128 columns of Ga).
+//                          It stages the tile and the dy-shifted tile of Gb, RMAX columns wider on each side, in LDS.  The u16 cells are
+//                          widened to 32 bits on the way in, which leaves room for two marks no cell can hold: 0x80000000 for a cell
+//                          outside Ga's grid, 0x40000000 for one outside Gb's.  A difference that involves a mark is above 0x3FFF0000, one
+//                          of two cells is at most 0xFFFF, so `d <= 0xFFFF` is "both inside" for any content of the grids, and the inner
+//                          loop has no index test.  A lane owns 4 neighbouring cells of a row and all 2 RMAX + 1 dx candidates: it reads
+//                          its 4 + 2 RMAX words of Gb once per row (16-byte LDS reads) and keeps one 32-bit sum per candidate in
+//                          registers - RMAX is a template argument (8, 16, 32: the least that holds R) so that they stay there;
+//                          candidates beyond R are computed and dropped.  A tile's sum is below 2^28.  The sums are reduced across the
+//                          wave by shuffles and across the workgroup by LDS adds, and the workgroup issues ONE 64-bit integer atomic per
+//                          candidate: integer sums are free of order, the result is the same bits in every run.
+//   align_clear_kernel     the sums start from zero: the entry's own launch, whatever the workspace held before.
+//   align_finish_kernel    one workgroup per sample: m(d) of every candidate, the least key (align_key) by an LDS minimum, how many
+//                          candidates hold it, the acceptance, the four words of the record.
+//   shift_f32_kernel       dst [B][C][H][W] = src moved by sign * the half-shift of its sample's record, edges replicated.  The mould of
+//                          border_body: a lane owns 4 units of one plane, 256 units apart, loads first, stores after.  The record is read
+//                          from device memory at an address that is uniform across the workgroup (a scalar load) and clamped to +-16384
+//                          before it meets an index, so any content of `shifts` is safe.  Wide form (W % 4 == 0, dst 16-byte aligned): a
+//                          unit is 4 destination columns, one 16-byte store; where its 4 sources are consecutive columns, src is 16-byte
+//                          aligned and the move is even (a recorded half-shift always is) they come as one 16-byte or two 8-byte loads,
+//                          else as 4 scalar loads through the clamp.  Scalar form: a unit is one element.
+// ------------------------------------------------------------------------------------------
+struct AlignSigArgs {
+    const float *x;
+    unsigned short *sig;
+    size_t plane;   // H * W
+    int B, H, W, Hc, Wc;
+};
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void align_signature_f32_kernel(AlignSigArgs p)
+{
+    const unsigned cells = (unsigned)p.Hc * (unsigned)p.Wc;   // <= 2^24
+    const unsigned cell = blockIdx.x * 256u + threadIdx.x;
+    if (cell >= cells) return;
+    const unsigned i = cell / (unsigned)p.Wc, j = cell - i * (unsigned)p.Wc;
+    const size_t at = (size_t)(ALIGN_CELL * i) * (size_t)p.W + ALIGN_CELL * j;   // the cell's first pixel inside a plane
+    for (size_t b = blockIdx.y; b < (size_t)p.B; b += gridDim.y) {
+        const float *const x0 = p.x + b * 3 * p.plane + at;
+        unsigned g = 0;
+        if constexpr (WIDE) {
+            float4 v[3][ALIGN_CELL];
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int r = 0; r < ALIGN_CELL; ++r) v[c][r] = *reinterpret_cast<const float4 *>(x0 + c * p.plane + (size_t)r * p.W);
+#pragma unroll
+            for (int r = 0; r < ALIGN_CELL; ++r)
+                g += (unsigned)(align_q(v[0][r].x, v[1][r].x, v[2][r].x) + align_q(v[0][r].y, v[1][r].y, v[2][r].y)
+                                + align_q(v[0][r].z, v[1][r].z, v[2][r].z) + align_q(v[0][r].w, v[1][r].w, v[2][r].w));
+        } else {
+#pragma unroll
+            for (int r = 0; r < ALIGN_CELL; ++r)
+#pragma unroll
+                for (int k = 0; k < ALIGN_CELL; ++k) {
+                    const float *const e = x0 + (size_t)r * p.W + k;
+                    g += (unsigned)align_q(e[0], e[p.plane], e[2 * p.plane]);
+                }
+        }
+        p.sig[b * cells + cell] = (unsigned short)g;
+    }
+}
+
+int launch_align_signature_f32(const float *x, unsigned short *sig, int B, int H, int W, hipStream_t s)
+{
+    AlignSigArgs p{};
+    p.x = x; p.sig = sig; p.plane = (size_t)H * W; p.B = B; p.H = H; p.W = W; p.Hc = align_cells(H); p.Wc = align_cells(W);
+    const unsigned cells = (unsigned)p.Hc * (unsigned)p.Wc;
+    const dim3 grid((cells + 255u) / 256u, (unsigned)(B < 65535 ? B : 65535));
+    if ((((uintptr_t)x | (uintptr_t)(W & 3)) & 15) == 0) align_signature_f32_kernel<true><<<grid, 256, 0, s>>>(p);
+    else align_signature_f32_kernel<false><<<grid, 256, 0, s>>>(p);
+    return (int)hipGetLastError();
+}
+
+struct AlignSearchArgs {
+    const unsigned short *ga, *gb;
+    unsigned long long *sad;   // [B][2R + 1][2R + 1]
+    int B, Hc, Wc, R, tiles_x;
+};
+constexpr int ALIGN_TR = 32, ALIGN_TC = 128, ALIGN_CPT = 4;   // a tile's rows and columns; the cells of a row a lane owns
+constexpr unsigned ALIGN_OUTSIDE_A = 0x80000000u, ALIGN_OUTSIDE_B = 0x40000000u;   // a staged cell outside its grid
+
+template <int RMAX>
+__global__ __launch_bounds__(256) void align_search_kernel(AlignSearchArgs p)
+{
+    constexpr int NDX = 2 * RMAX + 1, GBW = ALIGN_TC + 2 * RMAX, NG = ALIGN_CPT + 2 * RMAX, ROWS = 256 / (ALIGN_TC / ALIGN_CPT);
+    static_assert(NG % 4 == 0 && GBW % 4 == 0 && ALIGN_TR % ROWS == 0 && NDX <= 256, "16-byte LDS reads, whole passes, a lane per candidate");
+    __shared__ __align__(16) unsigned s_a[ALIGN_TR][ALIGN_TC];
+    __shared__ __align__(16) unsigned s_b[ALIGN_TR][GBW];
+    __shared__ unsigned s_sum[NDX];
+    const int tid = (int)threadIdx.x, n1 = 2 * p.R + 1;
+    const int i0 = (int)(blockIdx.x / (unsigned)p.tiles_x) * ALIGN_TR, j0 = (int)(blockIdx.x % (unsigned)p.tiles_x) * ALIGN_TC;
+    const int dy = (int)blockIdx.y - p.R;
+    const int rp = tid / (ALIGN_TC / ALIGN_CPT), c0 = (tid % (ALIGN_TC / ALIGN_CPT)) * ALIGN_CPT;
+    for (size_t b = blockIdx.z; b < (size_t)p.B; b += gridDim.z) {
+        const unsigned short *const ga = p.ga + b * (size_t)p.Hc * p.Wc, *const gb = p.gb + b * (size_t)p.Hc * p.Wc;
+        for (int e = tid; e < ALIGN_TR * ALIGN_TC; e += 256) {
+            const int r = e / ALIGN_TC, c = e - r * ALIGN_TC, i = i0 + r, j = j0 + c;
+            s_a[r][c] = i < p.Hc && j < p.Wc ? (unsigned)ga[(size_t)i * p.Wc + j] : ALIGN_OUTSIDE_A;
+        }
+        for (int e = tid; e < ALIGN_TR * GBW; e += 256) {
+            const int r = e / GBW, c = e - r * GBW, i = i0 + r + dy, j = j0 - RMAX + c;
+            s_b[r][c] = i >= 0 && i < p.Hc && j >= 0 && j < p.Wc ? (unsigned)gb[(size_t)i * p.Wc + j] : ALIGN_OUTSIDE_B;
+        }
+        if (tid < NDX) s_sum[tid] = 0u;
+        __syncthreads();
+        unsigned acc[NDX];
+#pragma unroll
+        for (int k = 0; k < NDX; ++k) acc[k] = 0u;
+        for (int r = rp; r < ALIGN_TR; r += ROWS) {
+            const uint4 aw = *reinterpret_cast<const uint4 *>(&s_a[r][c0]);
+            const unsigned a[ALIGN_CPT] = {aw.x, aw.y, aw.z, aw.w};
+            unsigned g[NG];
+#pragma unroll
+            for (int k = 0; k < NG / 4; ++k) {
+                const uint4 w = *reinterpret_cast<const uint4 *>(&s_b[r][c0 + 4 * k]);
+                g[4 * k] = w.x; g[4 * k + 1] = w.y; g[4 * k + 2] = w.z; g[4 * k + 3] = w.w;
+            }
+#pragma unroll
+            for (int k = 0; k < NDX; ++k)
+#pragma unroll
+                for (int c = 0; c < ALIGN_CPT; ++c) {
+                    const unsigned d = align_abs_diff(a[c], g[c + k]);
+                    acc[k] += d <= 0xFFFFu ? d : 0u;
+                }
+        }
+#pragma unroll
+        for (int k = 0; k < NDX; ++k) {
+            unsigned v = acc[k];
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+            if ((tid & 63) == 0 && v) atomicAdd(&s_sum[k], v);
+        }
+        __syncthreads();
+        const int dx = tid - RMAX;
+        if (tid < NDX && dx >= -p.R && dx <= p.R && s_sum[tid])
+            atomicAdd(p.sad + (b * n1 + (size_t)(dy + p.R)) * n1 + (size_t)(dx + p.R), (unsigned long long)s_sum[tid]);
+        __syncthreads();
+    }
+}
+
+// the sums start from zero whatever the workspace held: a kernel of the same stream, so that a captured graph replays it in order
+__global__ __launch_bounds__(256) void align_clear_kernel(unsigned long long *__restrict__ sad, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) sad[i] = 0ull;
+}
+
+__global__ __launch_bounds__(256) void align_finish_kernel(const unsigned long long *__restrict__ sad, int *__restrict__ shifts, int B, int Hc, int Wc,
+                                                           int R, int ratio)
+{
+    __shared__ unsigned long long s_key, s_m;
+    __shared__ unsigned s_win;
+    __shared__ int s_dy, s_dx;
+    const int tid = (int)threadIdx.x, n1 = 2 * R + 1, n = n1 * n1;
+    for (size_t b = blockIdx.x; b < (size_t)B; b += gridDim.x) {
+        if (tid == 0) { s_key = ~0ull; s_win = 0u; }
+        __syncthreads();
+        unsigned long long best = ~0ull, bm = 0ull;
+        int bdy = 0, bdx = 0;
+        unsigned cnt = 0u;
+        for (int c = tid; c < n; c += 256) {
+            const int dy = c / n1 - R, dx = c % n1 - R;
+            const unsigned long long m = align_m(sad[b * n + c], Hc, Wc, dy, dx), key = align_key(m, dy, dx);
+            if (key < best) { best = key; bm = m; bdy = dy; bdx = dx; cnt = 1u; }
+            else if (key == best) ++cnt;
+        }
+        atomicMin(&s_key, best);
+        __syncthreads();
+        if (cnt && best == s_key) {
+            atomicAdd(&s_win, cnt);
+            s_dy = bdy; s_dx = bdx; s_m = bm;   // one writer where it matters: several winners make the record zero
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int rec[4];
+            align_record(s_dy, s_dx, s_win, s_m, align_m(sad[b * n + (size_t)R * n1 + R], Hc, Wc, 0, 0), ratio, rec);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) shifts[4 * b + k] = rec[k];
+        }
+        __syncthreads();
+    }
+}
+
+int launch_align_search(const unsigned short *sig_a, const unsigned short *sig_b, int B, int Hc, int Wc, int R, int ratio, unsigned long long *sad,
+                        int *shifts, hipStream_t s)
+{
+    const size_t n1 = 2 * (size_t)R + 1, sums = (size_t)B * n1 * n1;
+    align_clear_kernel<<<(unsigned)((sums + 255) / 256 < 1024 ? (sums + 255) / 256 : 1024), 256, 0, s>>>(sad, sums);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
+    AlignSearchArgs p{};
+    p.ga = sig_a; p.gb = sig_b; p.sad = sad; p.B = B; p.Hc = Hc; p.Wc = Wc; p.R = R;
+    p.tiles_x = (Wc + ALIGN_TC - 1) / ALIGN_TC;
+    const dim3 grid((unsigned)(p.tiles_x * ((Hc + ALIGN_TR - 1) / ALIGN_TR)), (unsigned)n1, (unsigned)(B < 65535 ? B : 65535));
+    if (R <= 8) align_search_kernel<8><<<grid, 256, 0, s>>>(p);
+    else if (R <= 16) align_search_kernel<16><<<grid, 256, 0, s>>>(p);
+    else align_search_kernel<32><<<grid, 256, 0, s>>>(p);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
+    align_finish_kernel<<<(unsigned)(B < 65535 ? B : 65535), 256, 0, s>>>(sad, shifts, B, Hc, Wc, R, ratio);
+    return (int)hipGetLastError();
+}
+
+struct ShiftArgs {
+    const float *src;
+    float *dst;
+    const int *shifts;
+    size_t planes, plane;   // B * C; H * W
+    int C, H, W, sign, vec;
+};
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void shift_f32_kernel(ShiftArgs p)
+{
+    constexpr int U = 4;
+    using T = std::conditional_t<WIDE, float4, float>;
+    const unsigned Wu = (unsigned)(WIDE ? p.W >> 2 : p.W), units = (unsigned)p.H * Wu;
+    const unsigned u0 = blockIdx.x * (256u * U) + threadIdx.x;
+    for (size_t pl = blockIdx.y; pl < p.planes; pl += gridDim.y) {
+        const size_t b = pl / (size_t)p.C;
+        const int my = p.sign * align_half(p.shifts[4 * b]), mx = p.sign * align_half(p.shifts[4 * b + 1]);   // uniform: one read per workgroup
+        const float *const s = p.src + pl * p.plane;
+        T v[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const unsigned u = u0 + 256u * k;
+            if (u >= units) continue;
+            const int y = (int)(u / Wu), q = (int)(u - (unsigned)y * Wu);
+            const float *const row = s + (size_t)align_src_index(y, my, p.H) * p.W;
+            if constexpr (WIDE) {
+                const int x = 4 * q;
+                int sx0;
+                if (align_unit_inside(x, mx, p.W, &sx0) && p.vec && (sx0 & 1) == 0) {
+                    if ((sx0 & 3) == 0) {
+                        v[k] = *reinterpret_cast<const float4 *>(row + sx0);
+                    } else {
+                        const float2 lo = *reinterpret_cast<const float2 *>(row + sx0), hi = *reinterpret_cast<const float2 *>(row + sx0 + 2);
+                        v[k] = make_float4(lo.x, lo.y, hi.x, hi.y);
+                    }
+                } else {
+                    v[k] = make_float4(row[align_src_index(x, mx, p.W)], row[align_src_index(x + 1, mx, p.W)], row[align_src_index(x + 2, mx, p.W)],
+                                       row[align_src_index(x + 3, mx, p.W)]);
+                }
+            } else {
+                v[k] = row[align_src_index(q, mx, p.W)];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const unsigned u = u0 + 256u * k;
+            if (u >= units) continue;
+            reinterpret_cast<T *>(p.dst + pl * p.plane)[u] = v[k];
+        }
+    }
+}
+
+int launch_shift_f32(const float *src, float *dst, int B, int C, int H, int W, const int *shifts, int sign, hipStream_t s)
+{
+    ShiftArgs p{};
+    p.src = src; p.dst = dst; p.shifts = shifts; p.planes = (size_t)B * C; p.plane = (size_t)H * W; p.C = C; p.H = H; p.W = W; p.sign = sign;
+    const bool wide = (((uintptr_t)dst | (uintptr_t)(W & 3)) & 15) == 0;
+    p.vec = wide && ((uintptr_t)src & 15) == 0;
+    const size_t units = (size_t)H * (size_t)(wide ? W >> 2 : W), per_wg = 256u * 4u;   // units <= 2^28
+    const dim3 grid((unsigned)((units + per_wg - 1) / per_wg), (unsigned)(p.planes < 65535 ? p.planes : 65535));
+    if (wide) shift_f32_kernel<true><<<grid, 256, 0, s>>>(p);
+    else shift_f32_kernel<false><<<grid, 256, 0, s>>>(p);
     return (int)hipGetLastError();
 }

@@ -116,6 +116,13 @@ def parser() -> argparse.ArgumentParser:
                    help="estimate the flow of every forward on frames reduced by this factor and run everything else at full size: the "
                         "model's flow sees 7 pixels, this multiplies that reach; the output keeps its size (--scale shrinks it); no quality "
                         "claim is made, --evaluate tells what it buys on a clip")
+    p.add_argument("--align", type=int, default=None, metavar="PIXELS",
+                   help="with --align-ratio: remove the global translation of every pair before every forward - one shift per pair, a "
+                        "multiple of 4 pixels per axis within PIXELS (a multiple of 4 in 4..128), found on the device; the model's flow sees 7 "
+                        "pixels, a pan is tens; no default and no quality claim is made, --evaluate tells what it buys on a clip")
+    p.add_argument("--align-ratio", type=float, default=None, metavar="FRACTION",
+                   help="with --align: a shift is kept only where it lowers the mean absolute difference of the pair to at most FRACTION "
+                        "(0..1) of the unshifted one")
     p.add_argument("--batch-pairs", type=int, default=8)
     p.add_argument("--chunk-pairs", type=int, default=64, help="frame pairs per chunk: at most chunk_pairs * frame_interval + 1 source frames are held")
     p.add_argument("--yuv-standard", default="bt601", help="bt601, bt709 or (10 / 12 / 16-bit streams) bt2020")
@@ -193,6 +200,13 @@ def _run(args) -> int:
         if args.reference_quirks:
             raise ValueError("--agreement excludes --reference-quirks: a [0, 1] blend pasted into the quirk's de-normalised prediction would "
                              "show as patches")
+    if (args.align is None) != (args.align_ratio is None):
+        raise ValueError("--align PIXELS and --align-ratio FRACTION belong together: no default is claimed for either")
+    if args.align is not None:
+        if args.align % 4 or not 4 <= args.align <= 128:
+            raise ValueError("--align PIXELS: the radius must be a multiple of 4 in 4..128")
+        if not 0.0 <= args.align_ratio <= 1.0:     # false for a NaN
+            raise ValueError("--align-ratio FRACTION: a fraction in 0..1")
     mode = "resample" if resample else (args.mode or "reference")
     with y4m.Y4MReader(args.input) as reader:
         head = reader.header
@@ -234,7 +248,8 @@ def _run(args) -> int:
                                **(dict(agreement=args.agreement, agreement_radius=args.agreement_radius) if args.agreement is not None else {}),
                                flow_scale=args.flow_scale, **(dict(light=args.light) if args.light is not None else {}),
                                **(dict(active_area=args.active_area, active_tolerance=args.active_tolerance or 0.0)
-                                  if args.active_area is not None else {}))
+                                  if args.active_area is not None else {}),
+                               **(dict(align=args.align, align_ratio=args.align_ratio) if args.align is not None else {}))
         if args.evaluate:
             print(fi.evaluate(list(reader), every=args.every))      # evaluate() indexes the clip: all of it is held
             return 0
@@ -258,7 +273,10 @@ def _run(args) -> int:
                   + (f", border {args.border} {args.border_mode or 'replicate'}" if args.border is not None else "")
                   + (f", flow scale {args.flow_scale}" if args.flow_scale is not None else "")
                   + (f", agreement guard held {100.0 * sum(fi.agreement_share) / max(len(fi.agreement_share), 1):.2f} % of the predictions' "
-                     f"pixels on average" if args.agreement is not None else ""), file=sys.stderr)
+                     f"pixels on average" if args.agreement is not None else "")
+                  + (f", align {args.align} px at ratio {args.align_ratio:g} shifted "
+                     f"{100.0 * sum(1 for d in fi.align_shifts if d != (0, 0)) / max(len(fi.align_shifts), 1):.2f} % of the predictions"
+                     if args.align is not None else ""), file=sys.stderr)
     return 0
 
 

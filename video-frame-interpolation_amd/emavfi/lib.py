@@ -97,6 +97,10 @@ _PROTOTYPES = {
                                                                  POINTER(ctypes.c_double), c_int]),
     "emavfi_agreement_guard_f32": (c_int, [c_void_p] * 5 + [c_int] * 5 + [ctypes.c_float, POINTER(ctypes.c_float), POINTER(ctypes.c_float),
                                            c_void_p, c_void_p]),
+    "emavfi_align_signature_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "emavfi_align_workspace_bytes": (c_size_t, [c_int] * 2),
+    "emavfi_align_search": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_size_t, c_void_p, c_void_p]),
+    "emavfi_shift_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_int, c_void_p]),
     "emavfi_frame_metrics_workspace_bytes": (c_size_t, [c_int] * 4),
     "emavfi_frame_metrics_u8": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 4
                                 + [c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -1900,6 +1904,133 @@ def agreement_guard_f32(u, v, a, b, tol, radius=0, mean=IMAGENET_MEAN, std=IMAGE
                                                 m, s, counts.data_ptr() if counts is not None else None, _stream()),
               "emavfi_agreement_guard_f32")
     return out
+
+
+# ---------------------------------------------------------------- global motion (include/emavfi.h, "ALIGN DEFINITION")
+ALIGN_CELL = 4            # EMAVFI_ALIGN_CELL
+ALIGN_MAX_RADIUS = 32     # EMAVFI_ALIGN_MAX_RADIUS, in cells
+ALIGN_MAX_RATIO = 1024    # EMAVFI_ALIGN_MAX_RATIO
+
+
+def align_args(R_px, ratio, what):
+    """(R, ratio units) of an alignment given as a radius in pixels - a multiple of 4 in 4..128 - and an acceptance ratio in [0, 1]: the
+    radius in cells and round(ratio * 1024), or a ValueError naming `what`"""
+    import math
+    if isinstance(R_px, bool) or not isinstance(R_px, int) or R_px % ALIGN_CELL or not ALIGN_CELL <= R_px <= ALIGN_CELL * ALIGN_MAX_RADIUS:
+        raise ValueError(f"{what}: the align radius must be an int multiple of {ALIGN_CELL} in {ALIGN_CELL}..{ALIGN_CELL * ALIGN_MAX_RADIUS} "
+                         f"pixels, got {R_px!r}")
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or math.isnan(ratio) or not 0.0 <= ratio <= 1.0:
+        raise ValueError(f"{what}: the align ratio must be a number in [0, 1], got {ratio!r}")
+    return R_px // ALIGN_CELL, int(round(ratio * ALIGN_MAX_RATIO))
+
+
+def align_fits(R, H, W):
+    """whether a radius of R cells keeps at least half of each axis of an H x W frame's grid: 2 R <= min(H // 4, W // 4)"""
+    return 2 * R <= min(int(H) // ALIGN_CELL, int(W) // ALIGN_CELL)
+
+
+def _align_words(t, what, shape=None):
+    """a contiguous device tensor of 16-bit words (int16 or uint16: the words are unsigned either way) [B, Hc, Wc]"""
+    import torch
+    kinds = tuple(d for d in (torch.int16, getattr(torch, "uint16", None)) if d is not None)
+    if not t.is_cuda:
+        _require_cuda(t)
+    if t.dtype not in kinds or t.dim() != 3 or t.numel() == 0 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{what}: a non-empty contiguous 16-bit integer [B, Hc, Wc] device tensor expected"
+                         + (f" of shape {tuple(shape)}" if shape is not None else "") + f", got {t.dtype} {tuple(t.shape)}")
+    return tuple(int(d) for d in t.shape)
+
+
+def _align_frames(x, what):
+    import torch
+    if not x.is_cuda:
+        _require_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 4 or x.numel() == 0 or not x.is_contiguous():
+        raise ValueError(f"{what}: a non-empty contiguous float32 [B, C, H, W] device tensor expected, got {x.dtype} {tuple(x.shape)}")
+    return tuple(int(d) for d in x.shape)
+
+
+def align_signature_f32(x, out=None):
+    """out = the signature grid of the align definition: per 4 x 4 cell the sum of the 16 quantised lumas, 0..16368.  `x`: contiguous
+    float32 [B, 3, H, W] on the device, H and W in 8..16384; `out`: int16 [B, H // 4, W // 4] (the words are unsigned; no value reaches
+    the sign bit).  Runs on the current stream; returns `out`."""
+    import torch
+    what = "align_signature_f32"
+    B, C, H, W = _align_frames(x, f"{what}(x)")
+    if C != 3:
+        raise ValueError(f"{what}: x {tuple(x.shape)}: three channels expected")
+    if not (8 <= H <= RESIZE_MAX_DIM and 8 <= W <= RESIZE_MAX_DIM):
+        raise ValueError(f"{what}: x {tuple(x.shape)}: H and W must lie in 8..{RESIZE_MAX_DIM}")
+    shape = (B, H // ALIGN_CELL, W // ALIGN_CELL)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int16, device=x.device)
+    else:
+        _align_words(out, f"{what}(out)", shape)
+    with torch.cuda.device(x.device):
+        check(load().emavfi_align_signature_f32(x.data_ptr(), out.data_ptr(), B, H, W, _stream()), "emavfi_align_signature_f32")
+    return out
+
+
+def align_search(sig_a, sig_b, R, ratio, out=None, workspace_=None):
+    """out = the records {4 dy*, 4 dx*, m(d*), m(0)} of the align definition for the B samples of two signature batches: int32 [B, 4] on
+    the device.  `sig_a`, `sig_b`: 16-bit integer [B, Hc, Wc] device tensors of one shape; `R`: the radius in cells, 1..32, with
+    2 R <= min(Hc, Wc); `ratio`: the acceptance ratio in 1024ths, 0..1024.  `workspace_`: None (the stream's scratch buffer) or a uint8
+    device tensor of at least emavfi_align_workspace_bytes(B, R) bytes; it is cleared by the entry.  Runs on the current stream."""
+    import torch
+    what = "align_search"
+    B, Hc, Wc = _align_words(sig_a, f"{what}(sig_a)")
+    _align_words(sig_b, f"{what}(sig_b)", (B, Hc, Wc))
+    for v, name in ((R, "R"), (ratio, "ratio")):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{what}: {name} must be an int, got {v!r}")
+    if out is None:
+        out = torch.empty(B, 4, dtype=torch.int32, device=sig_a.device)
+    elif not (out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (B, 4) and out.is_contiguous()):
+        raise ValueError(f"{what}: out must be a contiguous int32 [{B}, 4] device tensor")
+    with torch.cuda.device(sig_a.device):
+        L = load()
+        ws = workspace_ if workspace_ is not None else workspace(max(L.emavfi_align_workspace_bytes(B, R), 8), sig_a.device)
+        check(L.emavfi_align_search(sig_a.data_ptr(), sig_b.data_ptr(), B, Hc, Wc, R, ratio, ws.data_ptr(), ws.numel() * ws.element_size(),
+                                    out.data_ptr(), _stream()), "emavfi_align_search")
+    return out
+
+
+def shift_f32(x, shifts, sign, out=None):
+    """out[b] = x[b] moved by sign * (shifts[b, 0] >> 1, shifts[b, 1] >> 1) pixels with its edges replicated (step 4 of the align
+    definition): sign = +1 makes a' of a, sign = -1 makes b' of b.  `x`, `out`: contiguous float32 [B, C, H, W] device tensors, not
+    overlapping; `shifts`: contiguous int32 [B, 4] on the device, read there by the kernel - nothing waits on the host, and any content is
+    safe.  Runs on the current stream; returns `out`."""
+    import torch
+    what = "shift_f32"
+    B, C, H, W = _align_frames(x, f"{what}(x)")
+    if not (shifts.is_cuda and shifts.dtype == torch.int32 and tuple(shifts.shape) == (B, 4) and shifts.is_contiguous()):
+        raise ValueError(f"{what}: shifts must be a contiguous int32 [{B}, 4] device tensor")
+    if isinstance(sign, bool) or not isinstance(sign, int) or sign not in (1, -1):
+        raise ValueError(f"{what}: sign must be +1 or -1, got {sign!r}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif _align_frames(out, f"{what}(out)") != (B, C, H, W):
+        raise ValueError(f"{what}: out {tuple(out.shape)} is not of x's shape {tuple(x.shape)}")
+    with torch.cuda.device(x.device):
+        check(load().emavfi_shift_f32(x.data_ptr(), out.data_ptr(), B, C, H, W, shifts.data_ptr(), int(sign), _stream()), "emavfi_shift_f32")
+    return out
+
+
+def align_pair_f32(a, b, R_px, ratio):
+    """(a', b', shifts) of the align definition for two normalised float32 [B, 3, H, W] device batches: the signatures of both, the
+    search, and both frames moved into the midpoint's coordinates - five launches and a clear on the current stream, no host wait.
+    `R_px`: the search radius in pixels, a multiple of 4 in 4..128 with 2 R_px / 4 <= min(H // 4, W // 4); `ratio`: the acceptance
+    ratio in [0, 1].  `shifts`: int32 [B, 4] = {dy, dx in pixels, m(d*), m(0)} per sample, on the device."""
+    what = "align_pair_f32"
+    R, units = align_args(R_px, ratio, what)
+    shape = _align_frames(a, f"{what}(a)")
+    if _align_frames(b, f"{what}(b)") != shape or shape[1] != 3:
+        raise ValueError(f"{what}: two [B, 3, H, W] tensors of one shape expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if min(shape[2:]) < 8 or not align_fits(R, *shape[2:]):
+        raise ValueError(f"{what}: a radius of {R_px} pixels ({R} cells) needs frames of at least {8 * R} x {8 * R} pixels "
+                         f"(2 R <= min(H // 4, W // 4)), got {shape[2]} x {shape[3]}")
+    shifts = align_search(align_signature_f32(a), align_signature_f32(b), R, units)
+    return shift_f32(a, shifts, 1), shift_f32(b, shifts, -1), shifts
 
 
 # ---------------------------------------------------------------- frame metrics on the device (include/emavfi.h, "FRAME METRIC DEFINITION")

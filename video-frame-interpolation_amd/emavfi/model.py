@@ -49,6 +49,8 @@ _MODEL_AGREEMENT = object()  # forward(agreement=): "what the model's attribute 
 # EMA_VFI.flow_scale ("Flow scale"; include/emavfi.h, "COARSE FLOW DEFINITION")
 FLOW_SCALES = _lib.FLOW_SCALES
 _MODEL_FLOW_SCALE = object() # forward(flow_scale=): "what the model's attribute says"
+# EMA_VFI.align ("Global motion"; include/emavfi.h, "ALIGN DEFINITION")
+_MODEL_ALIGN = object()      # forward(align=): "what the model's attribute says"
 
 
 class _LastCall(NamedTuple):
@@ -186,6 +188,8 @@ class EMA_VFI(nn.Module):
         self.border = None
         self.agreement = None
         self.flow_scale = None
+        self.align = None
+        self.align_shifts = None       # the last aligned forward's records {dy, dx, m(d*), m(0)} per sample: int32 [B, 4] on the device
         self.agreement_counts = None   # the last guarded forward's held pixels per sample: int32 [B] on the device
         m = mid_channels
         self.feat_ext_conv1 = conv_block(in_channels * 2, m)
@@ -495,6 +499,36 @@ class EMA_VFI(nn.Module):
             raise ValueError(f"EMA_VFI.flow_scale must be None or one of {FLOW_SCALES}, got {value!r}")
         return value
 
+    @property
+    def align(self):
+        """Global motion compensated before forward() ("Global motion"; include/emavfi.h, "ALIGN DEFINITION"): None
+        (default: the plain forward, every launch and byte as without the attribute) or (R_px, ratio): the search radius in pixels, a
+        multiple of 4 in 4..128, and the acceptance ratio in [0, 1] (taken as round(ratio * 1024)); there is no one-argument form and no
+        default.  One translation per pair, a multiple of 4 pixels per axis, is found on the device from 4 x 4 cell sums of both frames
+        (emavfi_align_signature_f32, emavfi_align_search); both frames are moved by half of it into the midpoint's coordinates
+        (emavfi_shift_f32), and whatever forward would otherwise run - plain, ensembled, bordered, coarse, guarded - runs on the moved
+        pair.  The records {dy, dx, m(d*), m(0)} of the last aligned forward stay on the device as `align_shifts` (int32 [B, 4]); no
+        host synchronisation is added."""
+        return self._align
+
+    @align.setter
+    def align(self, value):
+        self._align = self._check_align(value)
+
+    @staticmethod
+    def _check_align(value):
+        """None or (R_px, ratio) of an alignment given as None or (R_px, ratio)"""
+        if value is None:
+            return None
+        try:
+            if not isinstance(value, tuple) or len(value) != 2:
+                raise ValueError
+            _lib.align_args(value[0], value[1], "EMA_VFI.align")
+        except ValueError:
+            raise ValueError(f"EMA_VFI.align must be None or (R_px, ratio) with R_px an int multiple of {_lib.ALIGN_CELL} in "
+                             f"{_lib.ALIGN_CELL}..{_lib.ALIGN_CELL * _lib.ALIGN_MAX_RADIUS} and ratio a number in [0, 1], got {value!r}") from None
+        return value[0], float(value[1])
+
     def _check_border_size(self, B, H, W, border, dt):
         """(H + 2N, W + 2N), or a refusal from the shapes alone where the padded batch is beyond what the forward admits (include/emavfi.h,
         SIZE LIMITS: B*H*W < 2^31, H*W < 2^24, the fusion plane < 4 GiB) - before anything is launched"""
@@ -563,14 +597,18 @@ class EMA_VFI(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def forward(self, frame1, frame2, return_taps=False, _events=None, ensemble=_MODEL_ENSEMBLE, border=_MODEL_BORDER,
-                agreement=_MODEL_AGREEMENT, flow_scale=_MODEL_FLOW_SCALE):
+                agreement=_MODEL_AGREEMENT, flow_scale=_MODEL_FLOW_SCALE, align=_MODEL_ALIGN):
         """ema_vfi.py:110-147.  `ensemble`: one of ENSEMBLES for this call alone (FrameInterpolator passes its own); by default the
         model's attribute decides.  `border`: None, N or (N, mode) for this call alone, likewise.  `agreement`: None, tol or
-        (tol, radius) for this call alone, likewise.  `flow_scale`: None, 2, 4 or 8 for this call alone, likewise."""
+        (tol, radius) for this call alone, likewise.  `flow_scale`: None, 2, 4 or 8 for this call alone, likewise.  `align`: None or
+        (R_px, ratio) for this call alone, likewise."""
         ensemble = self._ensemble if ensemble is _MODEL_ENSEMBLE else self._check_ensemble(ensemble)
         border = self._border if border is _MODEL_BORDER else self._check_border(border)
         agreement = self._agreement if agreement is _MODEL_AGREEMENT else self._check_agreement(agreement)
         fs = self._flow_scale if flow_scale is _MODEL_FLOW_SCALE else self._check_flow_scale(flow_scale)
+        align = self._align if align is _MODEL_ALIGN else self._check_align(align)
+        if align is not None and return_taps:
+            raise ValueError("EMA_VFI.forward: return_taps=True with align: the taps belong to the forward of the moved pair (set align=None)")
         if fs is not None and return_taps:
             raise ValueError("EMA_VFI.forward: return_taps=True with a flow scale: ctx and flow belong to the reduced forward, the rest to "
                              "the full-size one (set flow_scale=None, or call lib.forward_flow / lib.forward_given_flow)")
@@ -590,6 +628,9 @@ class EMA_VFI(nn.Module):
                              f"{tuple(frame1.shape)} and {tuple(frame2.shape)}")
         if frame1.device != frame2.device:
             raise ValueError("EMA_VFI.forward: frame1 and frame2 are on different devices")
+        if align is not None and not (min(frame1.shape[2:]) >= 8 and _lib.align_fits(align[0] // _lib.ALIGN_CELL, *frame1.shape[2:])):
+            raise ValueError(f"EMA_VFI.forward: align={align!r}: a radius of {align[0]} pixels needs frames of at least {2 * align[0]} x "
+                             f"{2 * align[0]} pixels (2 R_px / 4 <= min(H // 4, W // 4)), got {frame1.shape[2]} x {frame1.shape[3]}")
         if self.in_channels != 3:
             # the reference's fusion width is the literal mid_channels + 3 (ema_vfi.py:97): any other in_channels
             # fails there with a channel mismatch at the first attention block
@@ -607,6 +648,9 @@ class EMA_VFI(nn.Module):
         if border is not None:
             self._check_border_size(B, H, W, border, dt)
         packed = self.packed_weights(dt, dev)
+        if align is not None:
+            # M(a', b') of the align definition: everything below sees the moved pair, in every role
+            f1, f2, self.align_shifts = _lib.align_pair_f32(f1, f2, *align)
         if border is not None:
             # crop_N(G(pad a, pad b)) of the border definition: G sees an ordinary (H + 2N) x (W + 2N) batch
             a, b = f1, f2

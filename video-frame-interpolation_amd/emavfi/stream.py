@@ -140,6 +140,14 @@ all three modes, the recursion's inner midpoints, ``evaluate()``, the members of
 estimated on the pair reduced by that factor and everything else at full size (include/emavfi.h, "COARSE FLOW DEFINITION";
 ``EMA_VFI.flow_scale``).  It is passed with each call, as ``ensemble`` is; ``None`` (default) leaves the decision to the model's attribute.
 No quality claim is made: ``evaluate()`` says what it buys on a clip.
+``align=R_px`` with ``align_ratio=q`` (opt-in; not in the reference; both or neither, no default is claimed) runs EVERY forward the harness
+issues - all three modes, the recursion's inner midpoints, ``evaluate()``, with any of the options above and below - on the pair with its
+global translation removed (include/emavfi.h, "ALIGN DEFINITION"; ``EMA_VFI.align``): one shift per pair, a multiple of 4 pixels per axis
+within ``R_px`` (a multiple of 4 in 4..128), found on the device from 4 x 4 cell sums and kept only where it lowers the mean absolute
+difference to ``q`` (in [0, 1]) of the unshifted one; both frames are moved by half of it and the model sees the moved pair.  Like
+``ensemble`` it is passed with each call.  ``align_shifts`` lists, per emitted prediction of the last ``run()`` (mode "resample": per emitted
+frame made of node frames, the first node frame it names), the (dy, dx) in pixels; the records follow the frames to pinned memory as the
+agreement counts do - no new synchronisation point.  With ``active_area`` the model, and so the search, sees the active picture.
 
 ``border=N`` with ``border_mode="replicate" | "reflect"`` (opt-in; not in the reference) runs EVERY forward the harness issues - all three
 modes, the recursion's inner midpoints, ``evaluate()``, with any of the options above, the ensemble included - on frames extended by N
@@ -296,6 +304,8 @@ class FrameInterpolator:
     active_share = 1.0    # its share of the frame's pixels
     prepass_waits = 0     # host waits of the last run()'s pre-pass (dedup_threshold and active_area="auto" share one)
     _act = None           # the rectangle in force where it is smaller than the frame, else None: the plain path
+    align = None          # (R_px, ratio) of the global motion compensated before every forward (EMA_VFI.align); None: what the model's attribute says
+    _al = None   # under `align`: the records of the batch just predicted, int32 [.., 4] on the device, in prediction order
     _ag = None   # under `agreement`: the held pixel counts of the batch just predicted, int32 on the device, in prediction order
     _depth = 0   # bits per sample of a 16-bit-word pixel format ("p010": 10, ...); 0 for the byte formats
     _planar = _yuv8 = False
@@ -310,7 +320,8 @@ class FrameInterpolator:
                  static_guard: Optional[int] = None, static_tolerance: float = 0.0, ensemble: Optional[str] = None,
                  border: Optional[int] = None, border_mode: str = "replicate",
                  agreement: Optional[float] = None, agreement_radius: Optional[int] = None, shutter=None,
-                 flow_scale: Optional[int] = None, light: Optional[str] = None, active_area=None, active_tolerance: float = 0.0):
+                 flow_scale: Optional[int] = None, light: Optional[str] = None, active_area=None, active_tolerance: float = 0.0,
+                 align: Optional[int] = None, align_ratio: Optional[float] = None):
         if shutter is not None and mode != "resample":
             raise ValueError("shutter belongs to mode='resample': the exposure window is accumulated over the nodes of its time grid")
         if light is not None:
@@ -389,6 +400,14 @@ class FrameInterpolator:
             if getattr(model, "pack_adapt", None) is not None:
                 raise ValueError("flow_scale with a model under pack_adapt: the adaptive route has no given-flow form (unset one of them)")
             self._forward_kw["flow_scale"] = self.flow_scale
+        if (align is None) != (align_ratio is None):
+            raise ValueError("align and align_ratio belong together: the search radius in pixels and the acceptance ratio (no default is "
+                             "claimed for either)")
+        if align is not None:
+            _lib.align_args(align, align_ratio, "align / align_ratio")
+            self.align = (align, float(align_ratio))
+            self._forward_kw["align"] = self.align
+        self.align_shifts = []      # per emitted prediction of the last run(): the (dy, dx) in pixels its pair was aligned by
         if pixel_format not in ("bgr24", "nv12", *_lib.DEPTHS, *_lib.PLANAR_DEPTHS):
             raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames), 'nv12' (uint8 [H*3/2, W] frames), 'p010' / 'p012' / 'p016' "
                              "(uint16 [H*3/2, W] frames) or planar 'yuv420p8' (uint8) / 'yuv420p10' / 'yuv420p12' / 'yuv420p16' (uint16)")
@@ -1118,6 +1137,18 @@ class FrameInterpolator:
         """under `agreement`: the held pixel counts of the forward just issued - int32 [n] on the device, that forward's own tensor"""
         return self.model.agreement_counts if self.agreement is not None else None
 
+    def _moved(self):
+        """under `align`: the records of the forward just issued - int32 [n, 4] on the device, that forward's own tensor"""
+        return self.model.align_shifts if self.align is not None else None
+
+    def _moved_to_host(self, slot, shifts):
+        """on the post lane: the records follow the frames into the slot's pinned buffer, ahead of `done`"""
+        n = shifts.shape[0]
+        if slot.get("h_al") is None or slot["h_al"].shape[0] < n:
+            slot["h_al"] = torch.zeros(n, 4, dtype=torch.int32).pin_memory()
+        shifts.record_stream(self._post)
+        slot["h_al"][:n].copy_(shifts, non_blocking=True)
+
     def _held_to_host(self, slot, counts):
         """on the post lane: the counts follow the frames into the slot's pinned buffer, ahead of `done`"""
         n = counts.shape[0]
@@ -1135,7 +1166,7 @@ class FrameInterpolator:
         return self._norm
 
     # ---- what a run reports beside its frames; run_chunked accumulates these over its chunks
-    _REPORTS = ("scene_cuts", "scene_scores", "duplicates", "dedup_scores", "static_share", "agreement_share")
+    _REPORTS = ("scene_cuts", "scene_scores", "duplicates", "dedup_scores", "static_share", "agreement_share", "align_shifts")
 
     def _reset_reports(self):
         for name in self._REPORTS:
@@ -1215,13 +1246,13 @@ class FrameInterpolator:
         with torch.no_grad():
             if self.mode == "reference" or self.factor <= 1:
                 out = self._forward(x1, x2).unsqueeze(1)
-                self._ag = self._held()
+                self._ag, self._al = self._held(), self._moved()
                 return out
             # the model consumes normalised frames and returns [0,1] images: re-normalise midpoints to recurse
             mean, std = self._norm_constants(x1.device)
 
             def rec(a, b, depth):
-                m = (self._forward(a, b), self._held())
+                m = (self._forward(a, b), self._held(), self._moved())
                 if depth == 1:
                     return [m]
                 mn = (m[0] - mean) / std
@@ -1230,8 +1261,9 @@ class FrameInterpolator:
             levels = (self.factor + 1).bit_length() - 1
             mids = rec(x1, x2, levels)
             # [n, k] flattened: the counts in the order of the predictions
-            self._ag = torch.stack([c for _, c in mids], dim=1).reshape(-1) if self.agreement is not None else None
-            return torch.stack([m for m, _ in mids], dim=1)
+            self._ag = torch.stack([c for _, c, _ in mids], dim=1).reshape(-1) if self.agreement is not None else None
+            self._al = torch.stack([s for _, _, s in mids], dim=1).reshape(-1, 4) if self.align is not None else None
+            return torch.stack([m for m, _, _ in mids], dim=1)
 
     def _check_frames(self, frames, first, what):
         if self._depth:
@@ -1339,6 +1371,7 @@ class FrameInterpolator:
             b.x1, x2 = self._rows(b.x, b.rows[0]), self._rows(b.x, b.rows[1])
             b.pred = self._predict(b.x1, x2)                                  # [n, k, 3, H, W], on the caller's stream
             b.held = self._ag                                                 # int32 [n k] on the device, or None
+            b.moved = self._al                                                # int32 [n k, 4] on the device, or None
 
         def post(b):
             slot, n, nup, (ia, ib), rs, x1 = b.slot, b.n, b.nup, b.rows, b.rs, b.x1
@@ -1346,6 +1379,8 @@ class FrameInterpolator:
             flat.record_stream(self._post)                                # allocated on the caller's stream, read on this one
             if b.held is not None:
                 self._held_to_host(slot, b.held)
+            if b.moved is not None:
+                self._moved_to_host(slot, b.moved)
             if self.quirks and (x1.data_ptr() < slot["x"].data_ptr() or x1.data_ptr() >= slot["x"].data_ptr() + slot["x"].numel() * 4):
                 x1.record_stream(self._post)                              # a gathered copy (non-consecutive rows), not a view of the slot
             if self.zero_copy:
@@ -1394,6 +1429,7 @@ class FrameInterpolator:
                 self._note_scenes(slot, b.chunk)
             sg = self._shares(slot["h_sg"], range(b.n * npred)) if self.static_guard is not None else None
             ag = self._shares(slot["h_ag"], range(b.n * npred)) if self.agreement is not None else None
+            al = slot["h_al"].numpy() if self.align is not None else None
             for k, (a, _) in enumerate(b.chunk):
                 for j in range(self.factor):
                     i = k * npred + j % npred     # reference mode: the pair's one prediction, `factor` times; recursive: its j-th midpoint
@@ -1401,6 +1437,8 @@ class FrameInterpolator:
                         self.static_share.append(sg[i])
                     if ag is not None:
                         self.agreement_share.append(ag[i])
+                    if al is not None:
+                        self.align_shifts.append((int(al[i, 0]), int(al[i, 1])))
                     yield own(pred_h[i])
                 yield own(src_h[k]) if (self.quirks or self._resize) else words(frames[a])
 
@@ -1418,7 +1456,7 @@ class FrameInterpolator:
         """levels[l] = [(pair of the batch, node)] of recursion level l + 1, in node-buffer order -> the model's output per non-empty level
         ([len(levels[l]), 3, H, W]); depths[k]: the depth of pair k's tree (a gap of m source intervals: D + ceil(log2 m)).  The recursion and
         the re-normalisation of a midpoint are ``_predict``'s."""
-        outs, norm, held = [], {}, []
+        outs, norm, held, moved = [], {}, [], []
         mean, std = self._norm_constants(x.device)
 
         def node(k, j):
@@ -1437,12 +1475,14 @@ class FrameInterpolator:
                 m = self._forward(x1, x2)
                 outs.append(m)
                 held.append(self._held())
+                moved.append(self._moved())
                 if l + 1 < len(levels) and levels[l + 1]:
                     mn = (m - mean) / std
                     for i, item in enumerate(items):
                         norm[item] = mn[i]
         # the counts in node-buffer order, as the node frames are
         self._ag = torch.cat(held) if self.agreement is not None and held else None
+        self._al = torch.cat(moved) if self.align is not None and moved else None
         return outs
 
     def _resample_batch(self, chunk, outs_of, ia, ib):
@@ -1604,11 +1644,14 @@ class FrameInterpolator:
         def forward(b):
             b.preds = self._resample_forwards(b.x, *b.rows, b.levels, b.depths)                       # on the caller's stream
             b.held = self._ag                                                                         # int32 [n_nodes] on the device, or None
+            b.moved = self._al                                                                        # int32 [n_nodes, 4] on the device, or None
 
         def post(b):
             slot, nup, (ia, ib), rs, table = b.slot, b.nup, b.rows, b.rs, b.table
             if b.held is not None:
                 self._held_to_host(slot, b.held)
+            if b.moved is not None:
+                self._moved_to_host(slot, b.moved)
             off = 0
             for m in b.preds:                                                                         # every node becomes bytes once
                 m.record_stream(self._post)
@@ -1645,6 +1688,11 @@ class FrameInterpolator:
             if self.agreement is not None:
                 # an emitted frame made of node frames has the share of the first node frame its entry names
                 self.agreement_share += self._shares(slot["h_ag"], [self._entry_nodes(e)[0] for e in b.table if self._entry_nodes(e)])
+            if self.align is not None:
+                # likewise: the shift of the first node frame its entry names
+                named = [self._entry_nodes(e)[0] for e in b.table if self._entry_nodes(e)]
+                al = slot["h_al"].numpy() if named else None           # a batch without a node issued no forward
+                self.align_shifts += [(int(al[i, 0]), int(al[i, 1])) for i in named]
             if self.static_guard is not None:
                 # an emitted frame made of node frames has its gap's share (core depends on the two sources only)
                 self.static_share += self._shares(slot["h_sg"], b.first_node)
