@@ -152,7 +152,7 @@ def test_forward_ragged_sizes_and_other_widths_against_the_oracle(mid, B, H, W):
 
 
 def test_forward_is_graph_capturable_and_replays_bit_identically():
-    """The split mode's launch sequence (21 launches, one memset) under torch.cuda.graph: the replay equals the eager result bit for bit,
+    """The split mode's launch sequence (21 launches and the census clear, a launch of its own) under torch.cuda.graph: the replay equals the eager result bit for bit,
     also with new frames written into the captured inputs."""
     sd = synth.synthetic_state_dict(seed=0)
     m = make_model(sd)

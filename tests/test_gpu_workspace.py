@@ -66,28 +66,46 @@ def leaves(kind, shape):
     return kind == "stress" and can_leave_window(*shape[1:])
 
 
-def forward_call(model, adaptive=False, leaves_window=False):
-    """leaves_window: the case is there for the fix-up arena and the census counters, so every block that has a census must have
+def forward_enqueue(model):
+    """the part of forward_call that only enqueues work (what tests/test_gpu_graph_replay.py captures): every tap of one forward"""
+    def call(inp):
+        with torch.no_grad():
+            _, taps = model(inp[0], inp[1], return_taps=True)
+        return dict(taps)
+    return call
+
+
+def forward_census(model, leaves_window=False):
+    """the part of forward_call that reads back: the census of the forward that ran last on the current stream.
+    leaves_window: the case is there for the fix-up arena and the census counters, so every block that has a census must have
     counted wave-taps in the fix-up loop and samples outside the window - in every run, or the case covers less than it says"""
+    def read():
+        census = model.pack_census()
+        if leaves_window:
+            assert all(r is None or (r["fixup_wave_taps"] > 0 and r["samples_outside_window"] > 0) for r in census), \
+                f"no sample left the window in some block: {census}"
+        return {"census": census}
+    return read
+
+
+def forward_call(model, adaptive=False, leaves_window=False):
+    """forward_enqueue, then forward_census"""
+    enqueue, read = forward_enqueue(model), forward_census(model, leaves_window)
+
     def call(inp):
         if adaptive:
             model._route_states.clear()   # a freshly initialised route state per run (allocated through torch.empty: guard-banded)
-        with torch.no_grad():
-            _, taps = model(inp[0], inp[1], return_taps=True)
-        res = dict(taps)
-        res["census"] = model.pack_census()
-        if leaves_window:
-            assert all(r is None or (r["fixup_wave_taps"] > 0 and r["samples_outside_window"] > 0) for r in res["census"]), \
-                f"no sample left the window in some block: {res['census']}"
+        res = enqueue(inp)
+        res.update(read())
         if adaptive:
             res["route_state"] = next(iter(model._route_states.values()))
         return res
     return call
 
 
-def frames(B, H, W, kind):
+def frames(B, H, W, kind, seed=17):
     # stress: i.i.d. bytes, run with the large-offset weights (OFFSETS) - flows and offsets that leave the pack's window
-    return list(synth.synthetic_frames(17, B, H, W, kind))
+    return list(synth.synthetic_frames(seed, B, H, W, kind))
 
 
 @pytest.mark.parametrize("kind", ["natural", "stress"])

@@ -869,7 +869,8 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
     hipStream_t s = (hipStream_t)stream;
     const unsigned sw = emavfi_switches();
     // the one-launch packs count what left their window (emavfi_forward_census reads it back): 8 KiB, zeroed per forward
-    if (!rec.dry && hipMemsetAsync(f.census, 0, kCensusBytes, s) != hipSuccess) return fail(EMAVFI_E_LAUNCH, "forward: census memset failed");
+    // (a clearing launch outside the recorded launch table, as the memset it replaced was: a captured graph replays it in order)
+    if (!rec.dry) EMAVFI_TRY(launch_clear_bytes(f.census, kCensusBytes, s), "forward: census clear");
     // the header of the blob is compared ON THE DEVICE with what this call expects (the forward's last launch, blob_guard_kernel): a
     // blob of another version / model / dtype / layout-switch setting yields an all-NaN frame instead of plausible garbage.
     // emavfi_packed_check() is the (synchronising) entry that returns a code for it.
@@ -1119,7 +1120,7 @@ int emavfi_pack_weights(int in_channels, int mid_channels, int num_blocks, const
     dtype = P.dtype;            // kernel storage type (EMAVFI_AMP16 -> EMAVFI_F16)
     const bool b16 = P.amp;     // autocast casts a convolution's bias to fp16 as well (EMAVFI_F32X3 keeps every bias in fp32)
     // (the gaps between the 256-byte aligned layers are part of the checksummed payload: zero, not whatever the buffer held)
-    if (hipMemsetAsync(packed, 0, P.total, s) != hipSuccess) return fail(EMAVFI_E_LAUNCH, "pack: blob memset failed");
+    EMAVFI_TRY(launch_clear_bytes(packed, P.total, s), "pack: blob clear");
     EMAVFI_TRY(pack_layer(P.conv1, params, packed, dtype, s, b16), "pack conv1");
     for (int i = 0; i < P.nb; ++i) EMAVFI_TRY(pack_layer(P.blk[i], params, packed, dtype, s, b16), "pack feat block");
     EMAVFI_TRY(pack_layer(P.c0, params, packed, dtype, s, b16), "pack ctx0");
@@ -2558,7 +2559,7 @@ int emavfi_conv3x3(const float *x, const float *weight, const float *bias, float
     if (ws.used > workspace_bytes) return fail(EMAVFI_E_WORKSPACE, "conv3x3: workspace needs %zu bytes, got %zu", ws.used, workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
     const void *const params[2] = {weight, bias};
-    if (hipMemsetAsync(b.zpage, 0, 256, s) != hipSuccess) return fail(EMAVFI_E_LAUNCH, "conv3x3: zero page memset failed");
+    EMAVFI_TRY(launch_clear_bytes(b.zpage, 256, s), "conv3x3: zero page clear");
     EMAVFI_TRY(pack_layer(L, params, workspace, dtype, s), "conv3x3 pack");
     EMAVFI_TRY(x3 ? launch_nchw_to_cl_x3(x, b.xcl, B, Cin, H, W, L.cin_pad, s) : launch_nchw_to_cl(x, b.xcl, B, Cin, H, W, L.cin_pad, dtype, s), "conv3x3 layout in");
     if (act == EMAVFI_ACT_TANH01) {
@@ -2606,7 +2607,7 @@ int emavfi_deform_conv2d(const float *x, const float *offset, const float *mask,
     if (ws.used > workspace_bytes) return fail(EMAVFI_E_WORKSPACE, "deform_conv2d: workspace needs %zu bytes, got %zu", ws.used, workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
     const void *const params[2] = {weight, bias};
-    if (hipMemsetAsync(b.zpage, 0, 256, s) != hipSuccess) return fail(EMAVFI_E_LAUNCH, "deform_conv2d: zero page memset failed");
+    EMAVFI_TRY(launch_clear_bytes(b.zpage, 256, s), "deform_conv2d: zero page clear");
     EMAVFI_TRY(pack_layer(L, params, workspace, dtype, s), "deform pack");
     EMAVFI_TRY(launch_nchw_to_cl(x, b.xcl, B, C, H, W, L.ck, dtype, s), "deform layout in");
     EMAVFI_TRY(launch_om_from_nchw(offset, mask, b.om, B, H, W, s), "deform offsets");
@@ -2690,8 +2691,8 @@ static int mdcn_impl(const float *x, const float *offset_weight, const float *of
     std::vector<const void *> params((size_t)emavfi_param_count(1), nullptr);
     params[P.off[0].param] = offset_weight; params[P.off[0].param + 1] = offset_bias;
     params[P.dcn[0].param] = dcn_weight; params[P.dcn[0].param + 1] = dcn_bias;
-    if (hipMemsetAsync(m.blob, 0, P.total, s) != hipSuccess || hipMemsetAsync(m.census, 0, kCensusBlock, s) != hipSuccess)
-        return fail(EMAVFI_E_LAUNCH, "mdcn: blob / census memset failed");
+    EMAVFI_TRY(launch_clear_bytes(m.blob, P.total, s), "mdcn: blob clear");
+    EMAVFI_TRY(launch_clear_bytes(m.census, kCensusBlock, s), "mdcn: census clear");
     EMAVFI_TRY(pack_layer(P.off[0], params.data(), m.blob, kd, s, P.amp), "mdcn pack offset_conv");
     if (P.has_offh) EMAVFI_TRY(pack_layer(P.offh[0], params.data(), m.blob, kd, s), "mdcn pack offset_conv (f16 fragments)");
     EMAVFI_TRY(pack_layer(P.dcn[0], params.data(), m.blob, kd, s), "mdcn pack dcn_v2");
@@ -2820,8 +2821,8 @@ int emavfi_context(const float *feat, const float *const *params, float *ctx, in
     all[P.c0.param] = params[0]; all[P.c0.param + 1] = params[1];
     all[P.c1.param] = params[2]; all[P.c1.param + 1] = params[3];
     all[P.c2.param] = params[4]; all[P.c2.param + 1] = params[5];
-    if (hipMemsetAsync(b.blob, 0, P.total, s) != hipSuccess || hipMemsetAsync(b.zeros9, 0, ((size_t)mid * 2 * mid * 9 + mid) * sizeof(float), s) != hipSuccess)
-        return fail(EMAVFI_E_LAUNCH, "context: memset failed");
+    EMAVFI_TRY(launch_clear_bytes(b.blob, P.total, s), "context: blob clear");
+    EMAVFI_TRY(launch_clear_bytes(b.zeros9, ((size_t)mid * 2 * mid * 9 + mid) * sizeof(float), s), "context: zero weights clear");
     EMAVFI_TRY(pack_layer(P.c0, all.data(), b.blob, kd, s, P.amp), "context pack 0");
     EMAVFI_TRY(pack_layer(P.c1, all.data(), b.blob, kd, s, P.amp), "context pack 1");
     EMAVFI_TRY(pack_layer(P.c2, all.data(), b.blob, kd, s, P.amp), "context pack 2");
@@ -2859,7 +2860,7 @@ int emavfi_reconstruct(const float *fused, const float *const *params, float *ou
     all[P.r0.param] = params[0]; all[P.r0.param + 1] = params[1];
     all[P.r1.param] = params[2]; all[P.r1.param + 1] = params[3];
     all[P.r2.param] = params[4]; all[P.r2.param + 1] = params[5];
-    if (hipMemsetAsync(b.blob, 0, P.total, s) != hipSuccess) return fail(EMAVFI_E_LAUNCH, "reconstruct: memset failed");
+    EMAVFI_TRY(launch_clear_bytes(b.blob, P.total, s), "reconstruct: blob clear");
     EMAVFI_TRY(pack_layer(P.r0, all.data(), b.blob, kd, s, P.amp), "reconstruct pack 0");
     EMAVFI_TRY(pack_layer(P.r1, all.data(), b.blob, kd, s, P.amp), "reconstruct pack 1");
     EMAVFI_TRY(pack_layer(P.r2, all.data(), b.blob, kd, s, P.amp), "reconstruct pack 2");

@@ -45,6 +45,8 @@ inline uint64_t blob_checksum_host(const void *payload, size_t bytes)
 // with NaN on a mismatch (misc_kernels.hip, blob_guard_kernel)
 struct BlobGuard { const BlobHeader *hdr; BlobHeader expect; };
 int launch_blob_guard(const BlobGuard &guard, float *out, size_t n, hipStream_t s);
+// `bytes` bytes at `ptr` (any alignment) set to zero by a launch on `s`: the entries' clears, which a captured graph replays in order
+int launch_clear_bytes(void *ptr, size_t bytes, hipStream_t s);
 // writes the header (pack time) and adds the payload checksum into it
 int launch_blob_seal(void *blob, const BlobHeader &h, hipStream_t s);
 

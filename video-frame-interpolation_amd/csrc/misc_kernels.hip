@@ -721,13 +721,38 @@ int launch_blob_guard(const BlobGuard &guard, float *out, size_t n, hipStream_t 
 }
 
 // ------------------------------------------------------------------------------------------
+// Bytes set to zero by a launch (misc_kernels.h, launch_clear_bytes): what the entries clear on the caller's stream - the census, the
+// zero page, a per-call blob and its padding - is cleared by a kernel of that stream and not by a memset, so that a captured graph
+// replays the clear in order like any other launch (a memset node took effect on the first replay only: profiles/r29_graph_replay.md).
+// Whole 16-byte units by vector stores; the bytes in front of the first aligned unit and behind the last whole one by block 0.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void clear_bytes_kernel(unsigned char *__restrict__ p, size_t head, size_t units, size_t tail)
+{
+    uint4 *const q = reinterpret_cast<uint4 *>(p + head);
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < units; i += (size_t)gridDim.x * 256u) q[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < head) p[threadIdx.x] = 0;
+        if (threadIdx.x < tail) p[head + units * 16u + threadIdx.x] = 0;
+    }
+}
+int launch_clear_bytes(void *ptr, size_t bytes, hipStream_t s)
+{
+    if (bytes == 0) return 0;
+    size_t head = (size_t)(-(intptr_t)ptr & 15);
+    if (head > bytes) head = bytes;
+    const size_t units = (bytes - head) / 16, tail = bytes - head - units * 16, blocks = (units + 255) / 256;
+    clear_bytes_kernel<<<(unsigned)(blocks < 1 ? 1 : blocks < 1024 ? blocks : 1024), 256, 0, s>>>((unsigned char *)ptr, head, units, tail);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
 // Blob header (misc_kernels.h, BlobHeader): written behind the pack kernels on the same stream, then the payload's checksum is
 // added into it.  Integer addition commutes, so the atomics leave a deterministic value.
 // ------------------------------------------------------------------------------------------
 __global__ void blob_header_kernel(BlobHeader *dst, const BlobHeader h)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) *dst = h;
-    // (the rest of the 256 header bytes is zeroed by the host-side memset in front of this launch)
+    // (the rest of the 256 header bytes is zeroed by the clearing launch in front of this one)
 }
 __global__ __launch_bounds__(256) void blob_checksum_kernel(const uint32_t *__restrict__ payload, size_t nwords, unsigned long long *sum)
 {
@@ -745,7 +770,7 @@ __global__ __launch_bounds__(256) void blob_checksum_kernel(const uint32_t *__re
 }
 int launch_blob_seal(void *blob, const BlobHeader &h, hipStream_t s)
 {
-    if (hipMemsetAsync(blob, 0, kBlobHeaderBytes, s) != hipSuccess) return (int)hipGetLastError();
+    if (const int e = launch_clear_bytes(blob, kBlobHeaderBytes, s); e != 0) return e;
     BlobHeader w = h;
     w.checksum = 0;
     blob_header_kernel<<<1, 64, 0, s>>>((BlobHeader *)blob, w);
