@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from emavfi import lib
+from emavfi import formats, lib
 import nv12_oracle
 import p010_oracle as oracle
 
@@ -231,7 +231,7 @@ def test_frame_interpolator_accepts_and_refuses():
         FrameInterpolator(model, pixel_format="p014")
     # evaluate() refuses before it touches a frame or the device
     fi = FrameInterpolator.__new__(FrameInterpolator)
-    fi._depth, fi.pixel_format = 10, "p010"
+    fi.fmt = formats.FORMATS["p010"]
     with pytest.raises(ValueError, match="evaluate.*p010"):
         fi.evaluate([np.zeros((36, 40), np.uint16)] * 3)
 

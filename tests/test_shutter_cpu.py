@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from emavfi import EMA_VFI, FrameInterpolator, cli, lib, y4m
+from emavfi import EMA_VFI, FrameInterpolator, cli, formats, lib, y4m
 import shutter_oracle as oracle
 
 FI = FrameInterpolator
@@ -123,7 +123,7 @@ def test_the_harness_refuses_what_a_shutter_cannot_mean():
             FI(model, **good)
     # evaluate() on an interpolator that has a shutter: the refusal comes before anything touches a device
     fi = FI.__new__(FI)
-    fi.shutter, fi._depth = Fraction(180), 0
+    fi.shutter, fi.fmt = Fraction(180), formats.FORMATS["bgr24"]
     with pytest.raises(ValueError, match="evaluate\\(\\) with a shutter"):
         fi.evaluate([])
 

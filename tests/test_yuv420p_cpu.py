@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from emavfi import lib
+from emavfi import formats, lib
 
 
 # valid defaults: W = 64, H = 8 at depth 10: 128 bytes per Y row, 64 per chroma row
@@ -159,7 +159,7 @@ def test_frame_interpolator_accepts_and_refuses():
         with pytest.raises(ValueError, match="bt2020"):
             FrameInterpolator(model, pixel_format=fmt, yuv_standard="bt2100")
         fi = FrameInterpolator.__new__(FrameInterpolator)         # evaluate() refuses before it touches a frame or the device
-        fi._depth, fi.pixel_format = lib.PLANAR_DEPTHS[fmt], fmt
+        fi.fmt = formats.FORMATS[fmt]
         with pytest.raises(ValueError, match=f"evaluate.*{fmt}"):
             fi.evaluate([np.zeros((36, 40), np.uint16)] * 3)
     with pytest.raises(ValueError, match="bt601"):
@@ -177,13 +177,11 @@ def test_frame_interpolator_accepts_and_refuses():
 def test_planar_views_of_a_frame_buffer():
     """the harness's plane views: the chroma planes are dense and need not start on a row of the [H*3/2, W] array"""
     import torch
-    from emavfi import FrameInterpolator
-    fi = FrameInterpolator.__new__(FrameInterpolator)
     H, W, n = 6, 4, 2                                     # U starts at row 6, V in the MIDDLE of row 7
-    for depth, wb in ((0, W), (10, 2 * W)):
-        fi._depth = depth
+    for fmt, wb in (("yuv420p8", W), ("yuv420p10", 2 * W)):
+        depth = 0 if fmt == "yuv420p8" else 10
         buf = torch.arange(n * (H * 3 // 2) * wb, dtype=torch.int32).to(torch.uint8).view(n, H * 3 // 2, wb)
-        y, u, v = fi._planes3(buf)
+        y, u, v = formats.FORMATS[fmt].planes(buf)
         es = 2 if depth else 1
         assert tuple(y.shape) == (n, H, W) and tuple(u.shape) == tuple(v.shape) == (n, H // 2, W // 2) and y.element_size() == es
         frame = H * 3 // 2 * wb
@@ -194,6 +192,23 @@ def test_planar_views_of_a_frame_buffer():
         assert (u.stride(1), u.stride(2), u.stride(0) * es) == (W // 2, 1, frame)
         flat = buf[1].reshape(-1).view(torch.int16 if depth else torch.uint8)
         assert torch.equal(u[1].reshape(-1), flat[H * W:H * W + H * W // 4]) and torch.equal(v[1].reshape(-1), flat[H * W * 5 // 4:])
+    # the NV12 layout, bytes and words: the UV rows follow the Y rows, one U,V pair per chroma position
+    for fmt, wb in (("nv12", W), ("p010", 2 * W)):
+        es = wb // W
+        buf = torch.arange(n * (H * 3 // 2) * wb, dtype=torch.int32).to(torch.uint8).view(n, H * 3 // 2, wb)
+        y, uv = formats.FORMATS[fmt].planes(buf)
+        assert tuple(y.shape) == (n, H, W) and tuple(uv.shape) == (n, H // 2, W // 2, 2) and y.element_size() == uv.element_size() == es
+        frame = H * 3 // 2 * wb
+        for k in range(n):
+            assert y[k].data_ptr() == buf.data_ptr() + k * frame
+            assert uv[k].data_ptr() == buf.data_ptr() + k * frame + H * W * es
+            assert uv[k, 1, 1, 1].data_ptr() == uv[k].data_ptr() + (W + 3) * es      # row 1, pair 1, V: one row of W samples and three more
+        assert (y.stride(0) * es, y.stride(1), y.stride(2)) == (frame, W, 1) and (uv.stride(0) * es, uv.stride(1), uv.stride(2), uv.stride(3)) == (frame, W, 2, 1)
+        flat = buf[1].reshape(-1).view(torch.int16 if es == 2 else torch.uint8)
+        assert torch.equal(y[1].reshape(-1), flat[:H * W]) and torch.equal(uv[1].reshape(-1), flat[H * W:])
+    # interleaved frames are their own single plane
+    buf = torch.zeros(n, H, W, 3, dtype=torch.uint8)
+    assert formats.FORMATS["bgr24"].planes(buf)[0] is buf and len(formats.FORMATS["bgr24"].planes(buf)) == 1
 
 
 def test_yuv420p_host_check_runs_clean_under_asan_ubsan():

@@ -17,7 +17,7 @@ import argparse, os, platform, statistics, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "video-frame-interpolation_amd"))
 import numpy as np, torch
-from emavfi import EMA_VFI, FrameInterpolator, lib, synth
+from emavfi import EMA_VFI, FrameInterpolator, formats, lib, synth
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r19_static_guard.md"))
@@ -79,9 +79,9 @@ for H, W in ((720, 1280), (1080, 1920)):
         if fmt == "bgr24":
             post = lambda x=x, d=d: lib.postprocess_u8(x, denormalize=False, out=d)
         elif fmt == "nv12":
-            post = lambda x=x, d=d: lib.postprocess_nv12(x, denormalize=False, out=FrameInterpolator._planes(d))
+            post = lambda x=x, d=d: lib.postprocess_nv12(x, denormalize=False, out=formats.FORMATS["nv12"].planes(d))
         else:
-            post = lambda x=x, d=d: lib.postprocess_p010(x, 10, denormalize=False, out=FrameInterpolator._planes16(d))
+            post = lambda x=x, d=d: lib.postprocess_p010(x, 10, denormalize=False, out=formats.FORMATS["p010"].planes(d))
         kernels[f"{tag}: postprocess, 8 frames"] = (post, float(N * (12 * H * W + fb)))
 if args.pmc_run:
     for name, (fn, _) in kernels.items():

@@ -17,7 +17,7 @@ import argparse, os, platform, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "video-frame-interpolation_amd"))
 import numpy as np, torch
-from emavfi import EMA_VFI, FrameInterpolator, lib, synth
+from emavfi import EMA_VFI, FrameInterpolator, formats, lib, synth
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r15_yuv420p_y4m.md"))
@@ -72,13 +72,12 @@ say()
 
 
 def planes3(buf, words):
-    n = buf.shape[0]
-    c = buf[:, H:].view(n, 2, H // 2, W // 2)
-    return buf[:, :H], c[:, 0], c[:, 1]
+    """the harness's own views (emavfi.formats) of planar frames held as bytes or as words"""
+    return formats.FORMATS["yuv420p10" if words else "yuv420p8"].planes(buf.view(torch.uint8))
 
 
 def planes2(buf):
-    return buf[:, :H], buf[:, H:].unflatten(2, (W // 2, 2))
+    return formats.FORMATS["p010" if buf.element_size() == 2 else "nv12"].planes(buf.view(torch.uint8))
 
 
 # ---------------------------------------------------------------- (1) kernels, resident frames

@@ -6,7 +6,7 @@
 (hand-written HIP for gfx950) reached through the C-ABI of ``include/emavfi.h``.
 """
 from .model import EMA_VFI, ModulatedDeformConvPack, DeformConv2d, conv, conv_block  # noqa: F401
-from . import lib, synth, dist, y4m  # noqa: F401
+from . import formats, lib, synth, dist, y4m  # noqa: F401
 from .stream import FrameInterpolator, Evaluation, FrameScore  # noqa: F401
 
-__all__ = ["EMA_VFI", "ModulatedDeformConvPack", "DeformConv2d", "conv", "conv_block", "lib", "synth", "dist", "y4m", "FrameInterpolator", "Evaluation", "FrameScore"]
+__all__ = ["EMA_VFI", "ModulatedDeformConvPack", "DeformConv2d", "conv", "conv_block", "formats", "lib", "synth", "dist", "y4m", "FrameInterpolator", "Evaluation", "FrameScore"]

@@ -15,7 +15,7 @@ from __future__ import annotations
 import argparse
 import sys
 
-from . import y4m
+from . import formats, y4m
 
 _EPILOG = """defaults that differ from the reference's inference.py: frames are NOT resized (the reference halves them: pass --scale 0.5 for
 that) and --reference-quirks is off (the reference de-normalises a model output that is already in [0, 1])."""
@@ -220,7 +220,7 @@ def _run(args) -> int:
             factor = args.factor
         else:
             factor, _ = y4m.choose_factor(head.fps, args.target_fps, args.max_interpolation_factor)
-        if args.light is not None and head.pixel_format in ("p016", "yuv420p16"):
+        if args.light is not None and not formats.lookup(head.pixel_format).light_table_fits:
             raise ValueError(f"--light on a 16-bit stream ({head.pixel_format}): linear light takes 8-, 10- and 12-bit streams")
         if factor < 0:
             raise ValueError(f"the interpolation factor {factor} is negative (the target rate lies below the stream's {head.fps:g} fps)")

@@ -12,6 +12,8 @@ import collections
 import threading
 from ctypes import c_int, c_size_t, c_void_p, c_char_p, POINTER
 
+from .formats import FORMATS, LAYOUT_INTERLEAVED, LAYOUT_NV12, LAYOUT_I420   # EMAVFI_LAYOUT_*
+
 F32, BF16, F16, AMP16, F32X3 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_TANH01 = 0, 1, 2
 MDCN_IN_F16, MDCN_OUT_F16, MDCN_SPLIT_TAIL = 1, 2, 4
@@ -704,30 +706,115 @@ def yuv_coefficients(standard="bt601", full_range=False, depth=8):
     return list(dec), list(enc)
 
 
+def _yuv420_planes(planes, es, what):
+    """The plane geometry of 4:2:0 frames, stated once: B, H, W and per plane (pitch, batch stride) in BYTES of `planes` = (y, uv) -
+    chroma interleaved, uv [B,ceil(H/2),ceil(W/2),2] - or (y, u, v) - chroma separate, u and v [B,ceil(H/2),ceil(W/2)] - around y
+    [B,H,W].  `es`, the element size: uint8 tensors at 1, 16-bit integer tensors at 2.  Device or pinned host tensors; the rows and
+    batches of each plane may be strided on their own, a row must be dense."""
+    import torch
+    names = ("y", "uv") if len(planes) == 2 else ("y", "u", "v")
+    for name, t in zip(names, planes):
+        _pinned_or_cuda(t, what)
+        if t.dim() != (4 if name == "uv" else 3):
+            raise ValueError(f"{what}: {name} must be a {4 if name == 'uv' else 3}-d tensor (y [B,H,W]; uv [B,ceil(H/2),ceil(W/2),2]; "
+                             f"u, v [B,ceil(H/2),ceil(W/2)]), got {t.dim()} dimensions")
+        if es == 1 and t.dtype != torch.uint8:
+            raise ValueError(f"{what}: {name} must be uint8, got {t.dtype}")
+        if es == 2 and (t.element_size() != 2 or t.dtype.is_floating_point):
+            raise ValueError(f"{what}: {name} must hold 16-bit integers (torch.uint16 or torch.int16), got {t.dtype}")
+    y = planes[0]
+    B, H, W = y.shape
+    if min(B, H, W) < 1:
+        raise ValueError(f"{what}: y is empty")
+    H2, W2 = (H + 1) // 2, (W + 1) // 2
+    geometry = []
+    for name, t in zip(names, planes):
+        h, w, k = (H, W, 1) if name == "y" else (H2, W2, 2) if name == "uv" else (H2, W2, 1)     # k: samples per position of a row
+        want = (B, h, w, 2) if name == "uv" else (B, h, w)
+        if tuple(t.shape) != want:
+            raise ValueError(f"{what}: {name} must be {want} for y {(B, H, W)}, got {tuple(t.shape)}")
+        if t.is_cuda != y.is_cuda or (t.is_cuda and t.device != y.device):
+            raise ValueError(f"{what}: {name} and y must live in the same memory")
+        if (w > 1 and t.stride(2) != k) or (k == 2 and t.stride(3) != 1):
+            raise ValueError(f"{what}: the rows of {name} must be dense (only rows and batches may be strided)")
+        # a dimension of size 1 has no meaningful stride: the dense value stands in
+        pitch = es * (t.stride(1) if h > 1 else k * w)
+        geometry.append((pitch, es * t.stride(0) if B > 1 else pitch * h))
+    return B, H, W, geometry
+
+
 def _nv12_planes(y, uv, what):
     """Shapes, pitches and batch strides (bytes) of a Y [B,H,W] / UV [B,ceil(H/2),ceil(W/2),2] pair of uint8 tensors; rows and
     batches may be strided, the innermost dimensions must be dense."""
+    B, H, W, (yg, uvg) = _yuv420_planes((y, uv), 1, what)
+    return (B, H, W, *yg, *uvg)
+
+
+def _preprocess_yuv420(family, planes, es, depth, standard, full_range, order, mean, std, device, out, size=None, resized_out=None):
+    """The one body of preprocess_nv12 / _p010 / _yuv420p: emavfi_preprocess_<family> on the checked planes; `depth`: () for NV12, whose
+    entry takes none, else (depth,).  `size` / `resized_out`: NV12's fused resize, emavfi_preprocess_nv12_resized."""
     import torch
-    for t in (y, uv):
-        _pinned_or_cuda(t, what)
-    if y.dtype != torch.uint8 or uv.dtype != torch.uint8 or y.dim() != 3 or uv.dim() != 4:
-        raise ValueError(f"{what}: uint8 y [B,H,W] and uv [B,ceil(H/2),ceil(W/2),2] expected")
-    B, H, W = y.shape
-    H2, W2 = (H + 1) // 2, (W + 1) // 2
-    if tuple(uv.shape) != (B, H2, W2, 2):
-        raise ValueError(f"{what}: uv must be [B,ceil(H/2),ceil(W/2),2] = {(B, H2, W2, 2)}, got {tuple(uv.shape)}")
-    if min(B, H, W) < 1:
-        raise ValueError(f"{what}: empty frames")
-    if y.is_cuda != uv.is_cuda or (y.is_cuda and y.device != uv.device):
-        raise ValueError(f"{what}: y and uv must live in the same memory")
-    if (W > 1 and y.stride(2) != 1) or uv.stride(3) != 1 or (W2 > 1 and uv.stride(2) != 2):
-        raise ValueError(f"{what}: the innermost dimensions of y and uv must be dense (only rows and batches may be strided)")
-    # a dimension of size 1 has no meaningful stride: the dense value stands in
-    y_pitch = y.stride(1) if H > 1 else W
-    uv_pitch = uv.stride(1) if H2 > 1 else 2 * W2
-    y_bs = y.stride(0) if B > 1 else y_pitch * H
-    uv_bs = uv.stride(0) if B > 1 else uv_pitch * H2
-    return B, H, W, y_pitch, y_bs, uv_pitch, uv_bs
+    what = "preprocess_" + family
+    if es == 2:
+        planes = [_words(t, device) for t in planes]
+    B, H, W, geometry = _yuv420_planes(planes, es, what)
+    st = (yuv_standard_code_deep if es == 2 else yuv_standard_code)(standard, full_range)
+    od = _order_code(order)
+    dev = planes[0].device if planes[0].is_cuda else torch.device(device if device is not None else "cuda")
+    m, s = _stats(mean, std, 3)
+    Hd, Wd = (H, W) if size is None else _resize_target(size, what)
+    if resized_out is not None and size is None:
+        raise ValueError(f"{what}: resized_out needs size=")
+    if out is None:
+        out = torch.empty(B, 3, Hd, Wd, dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, Hd, Wd) and out.is_contiguous()):
+        raise ValueError(f"{what}: out must be a contiguous fp32 [B,3,{'H,W' if size is None else 'Hd,Wd'}] device tensor")
+    args = [a for t, g in zip(planes, geometry) for a in (t.data_ptr(), *g)] + [out.data_ptr()]
+    if size is None:
+        entry, args = "emavfi_" + what, args + [B, H, W, *depth]
+    else:
+        yo, uvo = resized_out if resized_out is not None else (None, None)
+        ya = _byte_image(yo.unsqueeze(-1), f"{what}(resized_out=)", (B, Hd, Wd, 1)) if yo is not None else (None, 0, 0)
+        ua = _byte_image(uvo, f"{what}(resized_out=)", (B, (Hd + 1) // 2, (Wd + 1) // 2, 2)) if uvo is not None else (None, 0, 0)
+        entry, args = "emavfi_preprocess_nv12_resized", args + [*ya, *ua, B, H, W, Hd, Wd]
+    with torch.cuda.device(dev):
+        check(getattr(load(), entry)(*args, st, od, m, s, _stream()), entry)
+    return out
+
+
+def _postprocess_yuv420(family, frames_nchw, nplanes, es, depth, standard, full_range, order, denormalize, mean, std, out):
+    """The one body of postprocess_nv12 / _p010 / _yuv420p: emavfi_postprocess_<family> into the `nplanes` checked planes of `out`, or
+    into fresh dense ones; `depth` as for _preprocess_yuv420."""
+    import torch
+    what = "postprocess_" + family
+    _require_cuda(frames_nchw)
+    x = _f32c(frames_nchw)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"{what}: [B,3,H,W] tensor expected")
+    B, _, H, W = x.shape
+    st = (yuv_standard_code_deep if es == 2 else yuv_standard_code)(standard, full_range)
+    od = _order_code(order)
+    m, s = _stats(mean, std, 3, ctypes.c_double)
+    chroma = (B, (H + 1) // 2, (W + 1) // 2)
+    if out is None:
+        dt = torch.uint8 if es == 1 else word_dtype()
+        shapes = [(B, H, W)] + ([(*chroma, 2)] if nplanes == 2 else [chroma, chroma])
+        planes = tuple(torch.empty(shape, dtype=dt, device=x.device) for shape in shapes)
+    else:
+        try:
+            planes = tuple(out)
+        except TypeError:
+            planes = ()
+        if len(planes) != nplanes:
+            raise ValueError(f"{what}: out must be the {nplanes} planes {'(y, uv)' if nplanes == 2 else '(y, u, v)'}")
+    *shape, geometry = _yuv420_planes(planes, es, f"{what}(out=)")
+    if tuple(shape) != (B, H, W):
+        raise ValueError(f"{what}: out must be the planes of frames {(B, H, W)}, y [B,H,W] and chroma of ceil(H/2) x ceil(W/2)")
+    args = [a for t, g in zip(planes, geometry) for a in (t.data_ptr(), *g)]
+    with torch.cuda.device(x.device):
+        check(getattr(load(), "emavfi_" + what)(x.data_ptr(), *args, B, H, W, *depth, st, od, m, s, 1 if denormalize else 0, _stream()),
+              "emavfi_" + what)
+    return planes
 
 
 def preprocess_nv12(y, uv, standard="bt601", full_range=False, order="bgr", mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None, out=None,
@@ -740,35 +827,7 @@ def preprocess_nv12(y, uv, standard="bt601", full_range=False, order="bgr", mean
     ceil(Hd/2) x ceil(Wd/2); the resize definition of include/emavfi.h) - the result, fp32 [B,3,Hd,Wd], is preprocess_nv12 of the
     resize_u8-resized planes bit for bit; `resized_out=(y_out, uv_out)`: device tensors, strided like y / uv, either may be None, that then
     also receive the resized planes."""
-    import torch
-    B, H, W, yp, ybs, uvp, uvbs = _nv12_planes(y, uv, "preprocess_nv12")
-    st, od = yuv_standard_code(standard, full_range), _order_code(order)
-    dev = y.device if y.is_cuda else torch.device(device if device is not None else "cuda")
-    m, s = _stats(mean, std, 3)
-    if size is not None:
-        Hd, Wd = _resize_target(size, "preprocess_nv12")
-        Hd2, Wd2 = (Hd + 1) // 2, (Wd + 1) // 2
-        if out is None:
-            out = torch.empty(B, 3, Hd, Wd, dtype=torch.float32, device=dev)
-        elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, Hd, Wd) and out.is_contiguous()):
-            raise ValueError("preprocess_nv12: out must be a contiguous fp32 [B,3,Hd,Wd] device tensor")
-        yo, uvo = resized_out if resized_out is not None else (None, None)
-        ya = _byte_image(yo.unsqueeze(-1), "preprocess_nv12(resized_out=)", (B, Hd, Wd, 1)) if yo is not None else (None, 0, 0)
-        ua = _byte_image(uvo, "preprocess_nv12(resized_out=)", (B, Hd2, Wd2, 2)) if uvo is not None else (None, 0, 0)
-        with torch.cuda.device(dev):
-            check(load().emavfi_preprocess_nv12_resized(y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs, out.data_ptr(), *ya, *ua,
-                                                        B, H, W, Hd, Wd, st, od, m, s, _stream()), "emavfi_preprocess_nv12_resized")
-        return out
-    if resized_out is not None:
-        raise ValueError("preprocess_nv12: resized_out needs size=")
-    if out is None:
-        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
-    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, H, W) and out.is_contiguous()):
-        raise ValueError("preprocess_nv12: out must be a contiguous fp32 [B,3,H,W] device tensor")
-    with torch.cuda.device(dev):
-        check(load().emavfi_preprocess_nv12(y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs, out.data_ptr(), B, H, W, st, od, m, s, _stream()),
-              "emavfi_preprocess_nv12")
-    return out
+    return _preprocess_yuv420("nv12", (y, uv), 1, (), standard, full_range, order, mean, std, device, out, size, resized_out)
 
 
 def postprocess_nv12(frames_nchw, standard="bt601", full_range=False, order="bgr", denormalize=True, mean=IMAGENET_MEAN, std=IMAGENET_STD,
@@ -776,31 +835,14 @@ def postprocess_nv12(frames_nchw, standard="bt601", full_range=False, order="bgr
     """fp32 [B,3,H,W] -> NV12 (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]), defined as the encode of the bytes postprocess_u8 would write
     (include/emavfi.h, "NV12").  `out=(y, uv)`: device or pinned host tensors to fill, strided as for preprocess_nv12; bytes between
     the rows of a pitched destination are left as they were."""
-    import torch
-    _require_cuda(frames_nchw)
-    x = _f32c(frames_nchw)
-    if x.dim() != 4 or x.shape[1] != 3:
-        raise ValueError("postprocess_nv12: [B,3,H,W] tensor expected")
-    B, _, H, W = x.shape
-    st, od = yuv_standard_code(standard, full_range), _order_code(order)
-    m, s = _stats(mean, std, 3, ctypes.c_double)
-    if out is None:
-        y = torch.empty(B, H, W, dtype=torch.uint8, device=x.device)
-        uv = torch.empty(B, (H + 1) // 2, (W + 1) // 2, 2, dtype=torch.uint8, device=x.device)
-    else:
-        y, uv = out
-    *shape, yp, ybs, uvp, uvbs = _nv12_planes(y, uv, "postprocess_nv12(out=)")
-    if tuple(shape) != (B, H, W):
-        raise ValueError(f"postprocess_nv12: out must be (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]) for frames {(B, H, W)}")
-    with torch.cuda.device(x.device):
-        check(load().emavfi_postprocess_nv12(x.data_ptr(), y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs, B, H, W, st, od, m, s,
-                                             1 if denormalize else 0, _stream()), "emavfi_postprocess_nv12")
-    return y, uv
+    return _postprocess_yuv420("nv12", frames_nchw, 2, 1, (), standard, full_range, order, denormalize, mean, std, out)
 
 
 # ---------------------------------------------------------------- 16-bit-word frames, P010 / P012 / P016 (include/emavfi.h, "HIGH BIT DEPTH")
 YUV_STANDARDS_DEEP = {**YUV_STANDARDS, ("bt2020", False): 4, ("bt2020", True): 5}         # EMAVFI_YUV_*, BT.2020 included
-DEPTHS = {"p010": 10, "p012": 12, "p016": 16}                                             # pixel format -> bits per sample
+# pixel format -> bits per sample, of the table's word formats in the NV12 layout and of its planar formats
+DEPTHS = {f.name: f.depth for f in FORMATS.values() if f.layout == LAYOUT_NV12 and f.words}
+PLANAR_DEPTHS = {f.name: f.depth for f in FORMATS.values() if f.layout == LAYOUT_I420}
 _word = None
 
 
@@ -812,9 +854,11 @@ def yuv_standard_code_deep(standard="bt601", full_range=False) -> int:
         raise ValueError(f"yuv standard must be 'bt601', 'bt709' or 'bt2020', got {standard!r}") from None
 
 
-def _depth(depth) -> int:
-    if isinstance(depth, bool) or depth not in (10, 12, 16):
-        raise ValueError(f"depth must be 10, 12 or 16 (P010, P012, P016), got {depth!r}")
+def _depth(depth, family=DEPTHS) -> int:
+    """`depth` where a format of `family` has it"""
+    if isinstance(depth, bool) or depth not in family.values():
+        ds = sorted(family.values())
+        raise ValueError(f"depth must be {', '.join(str(d) for d in ds[:-1])} or {ds[-1]} ({', '.join(n.upper() for n in family)}), got {depth!r}")
     return int(depth)
 
 
@@ -849,25 +893,8 @@ def _words(t, device):
 def _p010_planes(y, uv, what):
     """Shapes, pitches and batch strides (BYTES) of a Y [B,H,W] / UV [B,ceil(H/2),ceil(W/2),2] pair of 16-bit tensors; rows and batches
     may be strided, the innermost dimensions must be dense."""
-    for t in (y, uv):
-        _pinned_or_cuda(t, what)
-    if y.element_size() != 2 or uv.element_size() != 2 or y.dtype.is_floating_point or uv.dtype.is_floating_point or y.dim() != 3 or uv.dim() != 4:
-        raise ValueError(f"{what}: 16-bit integer y [B,H,W] and uv [B,ceil(H/2),ceil(W/2),2] expected (torch.uint16 or torch.int16)")
-    B, H, W = y.shape
-    H2, W2 = (H + 1) // 2, (W + 1) // 2
-    if tuple(uv.shape) != (B, H2, W2, 2):
-        raise ValueError(f"{what}: uv must be [B,ceil(H/2),ceil(W/2),2] = {(B, H2, W2, 2)}, got {tuple(uv.shape)}")
-    if min(B, H, W) < 1:
-        raise ValueError(f"{what}: empty frames")
-    if y.is_cuda != uv.is_cuda or (y.is_cuda and y.device != uv.device):
-        raise ValueError(f"{what}: y and uv must live in the same memory")
-    if (W > 1 and y.stride(2) != 1) or uv.stride(3) != 1 or (W2 > 1 and uv.stride(2) != 2):
-        raise ValueError(f"{what}: the innermost dimensions of y and uv must be dense (only rows and batches may be strided)")
-    y_pitch = 2 * (y.stride(1) if H > 1 else W)
-    uv_pitch = 2 * (uv.stride(1) if H2 > 1 else 2 * W2)
-    y_bs = 2 * y.stride(0) if B > 1 else y_pitch * H
-    uv_bs = 2 * uv.stride(0) if B > 1 else uv_pitch * H2
-    return B, H, W, y_pitch, y_bs, uv_pitch, uv_bs
+    B, H, W, (yg, uvg) = _yuv420_planes((y, uv), 2, what)
+    return (B, H, W, *yg, *uvg)
 
 
 def preprocess_p010(y, uv, depth=10, standard="bt601", full_range=False, order="bgr", mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None,
@@ -877,20 +904,7 @@ def preprocess_p010(y, uv, depth=10, standard="bt601", full_range=False, order="
     the word's top bits: device tensors or pinned host tensors (read in place over PCIe; `device` names the GPU) of `word_dtype()` or
     torch.int16, strided in their row and batch dimensions as for preprocess_nv12; numpy uint16 arrays are uploaded first.  `standard`
     also takes "bt2020"."""
-    import torch
-    y, uv = _words(y, device), _words(uv, device)
-    B, H, W, yp, ybs, uvp, uvbs = _p010_planes(y, uv, "preprocess_p010")
-    d, st, od = _depth(depth), yuv_standard_code_deep(standard, full_range), _order_code(order)
-    dev = y.device if y.is_cuda else torch.device(device if device is not None else "cuda")
-    m, s = _stats(mean, std, 3)
-    if out is None:
-        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
-    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, H, W) and out.is_contiguous()):
-        raise ValueError("preprocess_p010: out must be a contiguous fp32 [B,3,H,W] device tensor")
-    with torch.cuda.device(dev):
-        check(load().emavfi_preprocess_p010(y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs, out.data_ptr(), B, H, W, d, st, od, m, s, _stream()),
-              "emavfi_preprocess_p010")
-    return out
+    return _preprocess_yuv420("p010", (y, uv), 2, (_depth(depth),), standard, full_range, order, mean, std, device, out)
 
 
 def postprocess_p010(frames_nchw, depth=10, standard="bt601", full_range=False, order="bgr", denormalize=True, mean=IMAGENET_MEAN,
@@ -899,66 +913,15 @@ def postprocess_p010(frames_nchw, depth=10, standard="bt601", full_range=False, 
     trunc(clip(x std + mean, 0, 1) P) (include/emavfi.h, "HIGH BIT DEPTH"); the low 16 - depth bits of every word are zero.
     `out=(y, uv)`: device or pinned host tensors to fill, strided as for preprocess_p010; bytes between the rows of a pitched destination
     are left as they were.  Without `out` the planes are dense device tensors of `word_dtype()`."""
-    import torch
-    _require_cuda(frames_nchw)
-    x = _f32c(frames_nchw)
-    if x.dim() != 4 or x.shape[1] != 3:
-        raise ValueError("postprocess_p010: [B,3,H,W] tensor expected")
-    B, _, H, W = x.shape
-    d, st, od = _depth(depth), yuv_standard_code_deep(standard, full_range), _order_code(order)
-    m, s = _stats(mean, std, 3, ctypes.c_double)
-    if out is None:
-        y = torch.empty(B, H, W, dtype=word_dtype(), device=x.device)
-        uv = torch.empty(B, (H + 1) // 2, (W + 1) // 2, 2, dtype=word_dtype(), device=x.device)
-    else:
-        y, uv = out
-    *shape, yp, ybs, uvp, uvbs = _p010_planes(y, uv, "postprocess_p010(out=)")
-    if tuple(shape) != (B, H, W):
-        raise ValueError(f"postprocess_p010: out must be (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]) for frames {(B, H, W)}")
-    with torch.cuda.device(x.device):
-        check(load().emavfi_postprocess_p010(x.data_ptr(), y.data_ptr(), yp, ybs, uv.data_ptr(), uvp, uvbs, B, H, W, d, st, od, m, s,
-                                             1 if denormalize else 0, _stream()), "emavfi_postprocess_p010")
-    return y, uv
+    return _postprocess_yuv420("p010", frames_nchw, 2, 2, (_depth(depth),), standard, full_range, order, denormalize, mean, std, out)
+
 
 # ---------------------------------------------------------------- planar 4:2:0 frames (include/emavfi.h, "PLANAR 4:2:0")
-PLANAR_DEPTHS = {"yuv420p8": 8, "yuv420p10": 10, "yuv420p12": 12, "yuv420p16": 16}      # pixel format -> bits per sample
-
-
-def _planar_depth(depth) -> int:
-    if isinstance(depth, bool) or depth not in (8, 10, 12, 16):
-        raise ValueError(f"depth must be 8, 10, 12 or 16, got {depth!r}")
-    return int(depth)
-
-
 def _yuv420p_planes(y, u, v, depth, what):
     """Shapes and, per plane, (pointer, pitch, batch stride) in BYTES of a Y [B,H,W] / U, V [B,ceil(H/2),ceil(W/2)] triple: uint8 tensors
     at depth 8, 16-bit integer tensors above; rows and batches may be strided, a row must be dense."""
-    import torch
-    es = 1 if depth == 8 else 2
-    for name, t in (("y", y), ("u", u), ("v", v)):
-        _pinned_or_cuda(t, what)
-        if t.dim() != 3:
-            raise ValueError(f"{what}: {name} must be a 3-d tensor (y [B,H,W]; u, v [B,ceil(H/2),ceil(W/2)]), got {t.dim()} dimensions")
-        if es == 1 and t.dtype != torch.uint8:
-            raise ValueError(f"{what}: {name} must be uint8 at depth 8, got {t.dtype}")
-        if es == 2 and (t.element_size() != 2 or t.dtype.is_floating_point):
-            raise ValueError(f"{what}: {name} must hold 16-bit integers at depth {depth} (torch.uint16 or torch.int16), got {t.dtype}")
-    B, H, W = y.shape
-    if min(B, H, W) < 1:
-        raise ValueError(f"{what}: y is empty")
-    H2, W2 = (H + 1) // 2, (W + 1) // 2
-    planes = []
-    for name, t, (h, w) in (("y", y, (H, W)), ("u", u, (H2, W2)), ("v", v, (H2, W2))):
-        if tuple(t.shape) != (B, h, w):
-            raise ValueError(f"{what}: {name} must be {(B, h, w)} for y {(B, H, W)}, got {tuple(t.shape)}")
-        if t.is_cuda != y.is_cuda or (t.is_cuda and t.device != y.device):
-            raise ValueError(f"{what}: {name} and y must live in the same memory")
-        if w > 1 and t.stride(2) != 1:
-            raise ValueError(f"{what}: the rows of {name} must be dense (only rows and batches may be strided)")
-        # a dimension of size 1 has no meaningful stride: the dense value stands in
-        pitch = es * (t.stride(1) if h > 1 else w)
-        planes += [t.data_ptr(), pitch, es * t.stride(0) if B > 1 else pitch * h]
-    return B, H, W, planes
+    B, H, W, geometry = _yuv420_planes((y, u, v), 1 if depth == 8 else 2, what)
+    return B, H, W, [a for t, g in zip((y, u, v), geometry) for a in (t.data_ptr(), *g)]
 
 
 def preprocess_yuv420p(y, u, v, depth=8, standard="bt601", full_range=False, order="bgr", mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None,
@@ -969,22 +932,8 @@ def preprocess_yuv420p(y, u, v, depth=8, standard="bt601", full_range=False, ord
     Y4M's C420p10 -, the result is preprocess_p010 of the words shifted to the top; `standard` then also takes "bt2020".  Device tensors or
     pinned host tensors (read in place over PCIe; `device` names the GPU), each plane strided in its row and batch dimensions on its own.
     YV12 is the caller swapping `u` and `v`.  `out`: a contiguous fp32 [B,3,H,W] device tensor to fill."""
-    import torch
-    d = _planar_depth(depth)
-    if d > 8:
-        y, u, v = _words(y, device), _words(u, device), _words(v, device)
-    B, H, W, planes = _yuv420p_planes(y, u, v, d, "preprocess_yuv420p")
-    st = yuv_standard_code(standard, full_range) if d == 8 else yuv_standard_code_deep(standard, full_range)
-    od = _order_code(order)
-    dev = y.device if y.is_cuda else torch.device(device if device is not None else "cuda")
-    m, s = _stats(mean, std, 3)
-    if out is None:
-        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
-    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, H, W) and out.is_contiguous()):
-        raise ValueError("preprocess_yuv420p: out must be a contiguous fp32 [B,3,H,W] device tensor")
-    with torch.cuda.device(dev):
-        check(load().emavfi_preprocess_yuv420p(*planes, out.data_ptr(), B, H, W, d, st, od, m, s, _stream()), "emavfi_preprocess_yuv420p")
-    return out
+    d = _depth(depth, PLANAR_DEPTHS)
+    return _preprocess_yuv420("yuv420p", (y, u, v), 1 if d == 8 else 2, (d,), standard, full_range, order, mean, std, device, out)
 
 
 def postprocess_yuv420p(frames_nchw, depth=8, standard="bt601", full_range=False, order="bgr", denormalize=True, mean=IMAGENET_MEAN,
@@ -993,33 +942,9 @@ def postprocess_yuv420p(frames_nchw, depth=8, standard="bt601", full_range=False
     de-interleaved; at 10 / 12 / 16 the words postprocess_p010 writes, shifted down into the LOW bits (the high bits are zero).
     `out=(y, u, v)`: device or pinned host tensors to fill, strided as for preprocess_yuv420p; bytes between the rows of a pitched
     destination are left as they were.  Without `out` the planes are dense device tensors (uint8 / `word_dtype()`)."""
-    import torch
-    _require_cuda(frames_nchw)
-    x = _f32c(frames_nchw)
-    if x.dim() != 4 or x.shape[1] != 3:
-        raise ValueError("postprocess_yuv420p: [B,3,H,W] tensor expected")
-    B, _, H, W = x.shape
-    d = _planar_depth(depth)
-    st = yuv_standard_code(standard, full_range) if d == 8 else yuv_standard_code_deep(standard, full_range)
-    od = _order_code(order)
-    m, s = _stats(mean, std, 3, ctypes.c_double)
-    if out is None:
-        dt = torch.uint8 if d == 8 else word_dtype()
-        y = torch.empty(B, H, W, dtype=dt, device=x.device)
-        u = torch.empty(B, (H + 1) // 2, (W + 1) // 2, dtype=dt, device=x.device)
-        v = torch.empty_like(u)
-    else:
-        try:
-            y, u, v = out
-        except (TypeError, ValueError):
-            raise ValueError("postprocess_yuv420p: out must be the three planes (y, u, v)") from None
-    *shape, planes = _yuv420p_planes(y, u, v, d, "postprocess_yuv420p(out=)")
-    if tuple(shape) != (B, H, W):
-        raise ValueError(f"postprocess_yuv420p: out must be (y [B,H,W], u, v [B,ceil(H/2),ceil(W/2)]) for frames {(B, H, W)}")
-    with torch.cuda.device(x.device):
-        check(load().emavfi_postprocess_yuv420p(x.data_ptr(), *planes, B, H, W, d, st, od, m, s, 1 if denormalize else 0, _stream()),
-              "emavfi_postprocess_yuv420p")
-    return y, u, v
+    d = _depth(depth, PLANAR_DEPTHS)
+    return _postprocess_yuv420("yuv420p", frames_nchw, 3, 1 if d == 8 else 2, (d,), standard, full_range, order, denormalize, mean, std, out)
+
 
 # ---------------------------------------------------------------- scene cuts on the device (include/emavfi.h, "SCENE CUT DEFINITION")
 SCENE_GRID = 32          # EMAVFI_SCENE_GRID
@@ -1135,10 +1060,7 @@ class ResampleEntry(ctypes.Structure):
 def resample_sample_format(pixel_format):
     """(sample_bytes, depth, shift) of the samples of a harness pixel format as emavfi_resample_frames takes them: bytes; P01x words with the
     sample in the top bits; planar words with it in the low bits"""
-    if pixel_format in DEPTHS:
-        return 2, DEPTHS[pixel_format], 16 - DEPTHS[pixel_format]
-    d = PLANAR_DEPTHS.get(pixel_format, 8)
-    return (1, 8, 0) if d == 8 else (2, d, 0)
+    return FORMATS[pixel_format].sample_format if pixel_format in FORMATS else (1, 8, 0)
 
 
 def resample_frames(dst, srcs, nodes, table, flags=None, sample_bytes=1, depth=8, shift=0):
@@ -1386,7 +1308,6 @@ def duplicate_flags(cells, threshold, flags=None, scores=None, with_scores=True)
 
 
 # ---------------------------------------------------------------- static regions (include/emavfi.h, "STATIC REGION DEFINITION")
-LAYOUT_INTERLEAVED, LAYOUT_NV12, LAYOUT_I420 = 0, 1, 2   # EMAVFI_LAYOUT_*
 LAYOUTS = {"interleaved": LAYOUT_INTERLEAVED, "nv12": LAYOUT_NV12, "i420": LAYOUT_I420}
 STATIC_MAX_RADIUS = 16                                   # EMAVFI_STATIC_MAX_RADIUS
 
@@ -1411,11 +1332,9 @@ def static_frame_format(pixel_format):
     """(layout, C, sample_bytes, depth, shift) of a harness pixel format as emavfi_static_guard_frames takes it: "bgr24" is interleaved
     bytes of 3 channels; "nv12" / "p01x" the NV12 layout (P01x: words with the sample in the top bits); "yuv420pN" the I420 layout (words
     with the sample in the low bits above 8 bits)"""
-    if pixel_format == "bgr24":
-        return LAYOUT_INTERLEAVED, 3, 1, 8, 0
-    if pixel_format != "nv12" and pixel_format not in DEPTHS and pixel_format not in PLANAR_DEPTHS:
+    if pixel_format not in FORMATS:
         raise ValueError(f"static_frame_format: unknown pixel_format {pixel_format!r}")
-    return (LAYOUT_I420 if pixel_format in PLANAR_DEPTHS else LAYOUT_NV12, 1, *resample_sample_format(pixel_format))
+    return FORMATS[pixel_format].frame_format
 
 
 def static_guard_frames(dst, srcs, table, size, layout=LAYOUT_INTERLEAVED, C=1, sample_bytes=1, depth=8, shift=0, radius=0, tol=0, counts=None):

@@ -185,6 +185,7 @@ from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
+from . import formats as _formats
 from . import lib as _lib
 
 
@@ -307,8 +308,7 @@ class FrameInterpolator:
     align = None          # (R_px, ratio) of the global motion compensated before every forward (EMA_VFI.align); None: what the model's attribute says
     _al = None   # under `align`: the records of the batch just predicted, int32 [.., 4] on the device, in prediction order
     _ag = None   # under `agreement`: the held pixel counts of the batch just predicted, int32 on the device, in prediction order
-    _depth = 0   # bits per sample of a 16-bit-word pixel format ("p010": 10, ...); 0 for the byte formats
-    _planar = _yuv8 = False
+    fmt = _formats.FORMATS["bgr24"]   # the record of `pixel_format` (formats.PixelFormat): what the frames are, asked here and nowhere by name
     mode = "reference"
 
     def __init__(self, model, interpolation_factor: int = 1, frame_interval: int = 1, batch_pairs: int = 8,
@@ -408,25 +408,18 @@ class FrameInterpolator:
             self.align = (align, float(align_ratio))
             self._forward_kw["align"] = self.align
         self.align_shifts = []      # per emitted prediction of the last run(): the (dy, dx) in pixels its pair was aligned by
-        if pixel_format not in ("bgr24", "nv12", *_lib.DEPTHS, *_lib.PLANAR_DEPTHS):
-            raise ValueError("pixel_format must be 'bgr24' (uint8 HWC frames), 'nv12' (uint8 [H*3/2, W] frames), 'p010' / 'p012' / 'p016' "
-                             "(uint16 [H*3/2, W] frames) or planar 'yuv420p8' (uint8) / 'yuv420p10' / 'yuv420p12' / 'yuv420p16' (uint16)")
-        if light is not None and (_lib.DEPTHS.get(pixel_format) or _lib.PLANAR_DEPTHS.get(pixel_format)) == 16:
+        fmt = self.fmt = _formats.lookup(pixel_format)   # refuses an unknown name; from here on the record answers what the format is
+        if light is not None and not fmt.light_table_fits:
             raise ValueError(f"light with pixel_format={pixel_format!r}: a table of 2^16 values of light does not fit LDS (8-, 10- and 12-bit "
                              "formats only)")
-        self._planar = pixel_format in _lib.PLANAR_DEPTHS      # Y, U, V planes one after the other instead of Y and interleaved UV
-        self._yuv8 = pixel_format in ("nv12", "yuv420p8")      # byte frames [H*3/2, W] whose first H rows are the Y plane
-        # bits per sample of a 16-bit-word format, 0 for the byte formats
-        self._depth = _lib.DEPTHS.get(pixel_format, 0) or (0 if self._yuv8 else _lib.PLANAR_DEPTHS.get(pixel_format, 0))
-        if self._depth:
-            _lib.yuv_standard_code_deep(yuv_standard, yuv_full_range)   # raises on an unknown standard; knows "bt2020"
+        # raises on an unknown standard; only the high-bit-depth definition knows "bt2020"
+        (_lib.yuv_standard_code_deep if fmt.takes_bt2020 else _lib.yuv_standard_code)(yuv_standard, yuv_full_range)
+        if not fmt.byte_kernels:
             if scale is not None or size is not None:
                 raise ValueError(f"pixel_format={pixel_format!r} with scale / size: the resize kernels read bytes (16-bit frames are not resized)")
             if scene_threshold is not None:
                 raise ValueError(f"pixel_format={pixel_format!r} with scene_threshold: the signature kernel reads bytes (16-bit frames are not "
                                  "scanned for cuts)")
-        else:
-            _lib.yuv_standard_code(yuv_standard, yuv_full_range)   # raises on an unknown standard
         if mode == "resample":
             self.dedup_max_run, self.dedup_span = self._dedup_args(dedup_max_run, dedup_span,
                                                                    self.resample_depth if dedup_threshold is not None else None)
@@ -435,7 +428,7 @@ class FrameInterpolator:
                     raise ValueError("dedup_threshold must be None (off) or a number in [0, 1]: the largest mean absolute luma difference of a "
                                      "cell, as a fraction of full scale, at which a frame still counts as a copy of the frame before it (0: "
                                      "bit-identical luma only)")
-                self.dedup = _lib.dedup_threshold_units(dedup_threshold, self._depth or 8)
+                self.dedup = _lib.dedup_threshold_units(dedup_threshold, fmt.depth)
         self.duplicates, self.dedup_scores = [], []   # (t, score) of the dropped frames / of every scored pair (t - 1, t), global indices
         if isinstance(static_tolerance, bool) or not isinstance(static_tolerance, (int, float)) or not 0 <= static_tolerance <= 1:
             raise ValueError("static_tolerance must be a number in [0, 1]: the largest difference of two samples, as a fraction of full scale, "
@@ -452,7 +445,7 @@ class FrameInterpolator:
             if zero_copy:
                 raise ValueError("static_guard with zero_copy=True: the guard compares and patches frames in device memory, which leave by copy")
             self.static_guard = static_guard
-            self.static_tol = _lib.static_tolerance_units(static_tolerance, self._depth or 8)
+            self.static_tol = _lib.static_tolerance_units(static_tolerance, fmt.depth)
         self.static_share = []   # per emitted prediction of the last run(): the share of its pixels the guard held
         if isinstance(active_tolerance, bool) or not isinstance(active_tolerance, (int, float)) or not 0 <= active_tolerance <= 1:
             raise ValueError("active_tolerance must be a number in [0, 1]: how far above black, as a fraction of full scale, a sample of the "
@@ -478,7 +471,7 @@ class FrameInterpolator:
                                  "is not supported")
             if zero_copy:
                 raise ValueError("active_area with zero_copy=True: the bars are put back in device memory around frames that leave by copy")
-            self._active_level = _lib.active_level_units(active_tolerance, self._depth or 8, pixel_format != "bgr24", bool(yuv_full_range))
+            self._active_level = _lib.active_level_units(active_tolerance, fmt.depth, fmt.yuv, bool(yuv_full_range))
         if scale is not None and size is not None:
             raise ValueError("scale and size are mutually exclusive")
         if scale is not None and not scale > 0:
@@ -506,8 +499,8 @@ class FrameInterpolator:
             raise RuntimeError("FrameInterpolator needs the model on a ROCm device (no CPU path)")
         if light is not None:
             # built, checked and uploaded once: full range for bgr24, the Y'CbCr range otherwise.  The bits of the uint32 table as int32.
-            table = _lib.transfer_table(light, self._depth or 8, True if pixel_format == "bgr24" else bool(yuv_full_range))
-            _lib.transfer_table_check(table, self._depth or 8)
+            table = _lib.transfer_table(light, fmt.depth, not fmt.yuv or bool(yuv_full_range))
+            _lib.transfer_table_check(table, fmt.depth)
             self.light = light
             self._lin = torch.from_numpy(table.view(np.int32)).to(self.device)
         self._shape = None
@@ -544,7 +537,7 @@ class FrameInterpolator:
             return int(H), int(W)
         if not (1 <= Hd <= _lib.RESIZE_MAX_DIM and 1 <= Wd <= _lib.RESIZE_MAX_DIM):
             raise ValueError(f"the resized frame {(Hd, Wd)} must lie in 1..{_lib.RESIZE_MAX_DIM} per dimension")
-        if pixel_format in ("nv12", "yuv420p8") and (Hd % 2 or Wd % 2):
+        if _formats.lookup(pixel_format).even_resize and (Hd % 2 or Wd % 2):
             raise ValueError(f"pixel_format={pixel_format!r}: the packed [H*3/2, W] layout needs an even destination H and W, got {(Hd, Wd)}")
         return Hd, Wd
 
@@ -830,17 +823,11 @@ class FrameInterpolator:
         if self._shape == shape and self._per >= per:
             return
         self._per = per
-        if self._depth:
-            Hs, Ws, C = shape[0] * 2 // 3, shape[1] // 2, 3   # the bytes of [H*3/2, W] words: rows of 2 W bytes
-        elif self._yuv8:
-            Hs, Ws, C = shape[0] * 2 // 3, shape[1], 3   # [H*3/2, W]: Y rows, then the UV rows (planar: the U plane, then the V plane)
-        else:
-            Hs, Ws, C = shape
-        fin = tuple(shape)                               # a frame as it arrives: [Hs, Ws, C] or [Hs*3/2, Ws]
-        H, W = self.output_size(Hs, Ws, self.scale, self.size, self.pixel_format)
+        Hs, Ws, C = self.fmt.geometry(shape)
+        fin = tuple(shape)                               # the bytes of a frame as it arrives: [Hs, Ws, C] or [Hs*3/2, Ws (* 2)]
+        H, W = self.output_size(Hs, Ws, self.scale, self.size, self.fmt.name)
         self._dst = (H, W)
-        # a frame as it leaves, at the size the model runs at
-        fs = fin if self._depth else (H * 3 // 2, W) if self._yuv8 else (H, W, C)
+        fs = self.fmt.byte_shape(H, W)                   # and as it leaves, at the size the model runs at
         nb, nout = self.batch_pairs, max(self.factor if self.mode == "recursive" else 1, 1)
         self._shape = shape
         self._slots = []
@@ -860,8 +847,8 @@ class FrameInterpolator:
                 "d_in": torch.empty(per * nb, *fin, dtype=torch.uint8, device=self.device),
                 # the resized bytes of the slot's frames, where frames leave as they arrived (reference_quirks=False) and arrive at another size
                 "d_rs": torch.empty(per * nb, *fs, dtype=torch.uint8, device=self.device) if self._resize and not self.quirks else None,
-                # planar frames are resized into a buffer of their own ahead of the preprocess kernel: this one where neither d_rs nor e_rs serves
-                "p_rs": torch.empty(per * nb, *fs, dtype=torch.uint8, device=self.device) if self._planar and self._resize and self.quirks else None,
+                # without a fused resize frames are resized into a buffer of their own ahead of the preprocess kernel: this one where neither d_rs nor e_rs serves
+                "p_rs": torch.empty(per * nb, *fs, dtype=torch.uint8, device=self.device) if not self.fmt.fused_resize and self._resize and self.quirks else None,
                 "d_pred": torch.empty(nb * nout, *fs, dtype=torch.uint8, device=self.device),
                 "d_src": torch.empty(nb, *fs, dtype=torch.uint8, device=self.device),
                 # consumed: the preprocess kernel has read h_in (the host may restage it); pre: x is ready; fwd: the forward has read x
@@ -872,7 +859,7 @@ class FrameInterpolator:
             if per > 2:
                 # evaluate(): the resized bytes of the staged frames whatever reference_quirks says (the ground truth at the size the model
                 # runs at), and the metric words {sse, ssimq} per target and channel, on the device and pinned
-                mc = 1 if self._yuv8 else C
+                mc = 1 if self.fmt.yuv else C
                 self._slots[-1].update({"e_rs": torch.empty(per * nb, *fs, dtype=torch.uint8, device=self.device) if self._resize else None,
                                         "met": torch.zeros(nb, mc, 2, dtype=torch.int64, device=self.device),
                                         "h_met": torch.zeros(nb, mc, 2, dtype=torch.int64).pin_memory()})
@@ -895,32 +882,17 @@ class FrameInterpolator:
         self._post = _lib.side_stream(self.device, which=3, priority=-1)
 
     # ---- the two device kernels of a frame format: uint8 frames (a slot buffer's rows, device or pinned) <-> normalised fp32 NCHW
-    @staticmethod
-    def _planes(buf):
-        """Y [n,H,W] and UV [n,H/2,W/2,2] views of n contiguous NV12 frames [n, H*3/2, W]"""
-        H = buf.shape[1] * 2 // 3
-        return buf[:, :H], buf[:, H:].unflatten(2, (buf.shape[2] // 2, 2))
+    def _resize_planes(self, src, dst, device=None):
+        """the planes of the byte frames `src` resized into those of `dst`, each as an image of its own (4:2:0 chroma to H/2 x W/2)"""
+        for a, b in zip(self.fmt.planes(src), self.fmt.planes(dst)):
+            a, b = (a, b) if a.dim() == 4 else (a.unsqueeze(-1), b.unsqueeze(-1))
+            _lib.resize_u8(a, (b.shape[1], b.shape[2]), out=b, device=device)
 
-    @staticmethod
-    def _planes16(buf):
-        """Y [n,H,W] and UV [n,H/2,W/2,2] views, as 16-bit words, of the bytes [n, H*3/2, 2 W] of n contiguous P010 / P012 / P016 frames"""
-        H = buf.shape[1] * 2 // 3
-        return buf[:, :H].view(torch.int16), buf[:, H:].view(torch.int16).unflatten(2, (buf.shape[2] // 4, 2))
-
-    def _planes3(self, buf):
-        """Y [n,H,W], U and V [n,H/2,W/2] views of n contiguous planar 4:2:0 frames: bytes [n, H*3/2, W] or, as 16-bit words, the bytes
-        [n, H*3/2, 2 W] of the deeper formats.  The chroma planes are dense: they need not start on a row of `buf`."""
-        n, H = buf.shape[0], buf.shape[1] * 2 // 3
-        y, c = buf[:, :H], buf[:, H:]
-        if self._depth:
-            y, c = y.view(torch.int16), c.view(torch.int16)
-        c = c.view(n, 2, H // 2, c.shape[2] // 2)
-        return y, c[:, 0], c[:, 1]
-
-    def _resize_planar(self, src, dst, device=None):
-        """the three planes of `src` resized into those of `dst`, each as a one-channel image (chroma to H/2 x W/2)"""
-        for a, b in zip(self._planes3(src), self._planes3(dst)):
-            _lib.resize_u8(a.unsqueeze(-1), (b.shape[1], b.shape[2]), out=b.unsqueeze(-1), device=device)
+    def _yuv_entry(self, which):
+        """the format's lib function, `which` = "preprocess" or "postprocess" of nv12, p010 or yuv420p, and the colour arguments that follow
+        its planes or its fp32 frames: the depth where the function takes one, the standard and the range"""
+        family = self.fmt.family
+        return getattr(_lib, which + "_" + family), (*(() if family == "nv12" else (self.fmt.depth,)), self.yuv["standard"], self.yuv["full_range"])
 
     def _cropped(self, luma, *chroma):
         """the planes of whole frames - [n,H,W(,C)], 4:2:0 chroma [n,H/2,W/2(,2)] - cut to the active rectangle in force: views, whose
@@ -950,30 +922,28 @@ class FrameInterpolator:
         """on the post lane: frame k of `dst` (whole frames whose rectangle the post kernel has just written) receives the samples outside
         the rectangle of frame table[k] of `srcs`, the source frames as staged"""
         if self._act is not None and len(table):
-            layout, C, sb, _, _ = _lib.static_frame_format(self.pixel_format)
+            layout, C, sb, _, _ = self.fmt.frame_format
             _lib.fill_outside_frames(dst[:len(table)], srcs, table, self._dst, self._act, layout=layout, C=C, sample_bytes=sb)
 
     def _pre_kernel(self, buf, out=None, device=None, resized=None):
         """`resized`: with scale / size, a buffer of frames at the destination size that also receives the resized bytes (planar frames
         are resized into it first: without one, a fresh buffer is made).  With an active rectangle in force the kernels read views of it."""
-        size = self._dst if self._resize else None
-        if self._planar:
-            if size is not None:
-                if resized is None:
-                    resized = torch.empty(buf.shape[0], size[0] * 3 // 2, size[1], dtype=torch.uint8, device=device if device is not None else buf.device)
-                self._resize_planar(buf, resized, device)
-                buf = resized
-            return _lib.preprocess_yuv420p(*self._cropped(*self._planes3(buf)), self._depth or 8, self.yuv["standard"], self.yuv["full_range"], device=device, out=out)
-        if self._depth:
-            y, uv = self._cropped(*self._planes16(buf))
-            return _lib.preprocess_p010(y, uv, self._depth, self.yuv["standard"], self.yuv["full_range"], device=device, out=out)
-        if self.pixel_format == "nv12":
-            y, uv = self._cropped(*self._planes(buf))
-            return _lib.preprocess_nv12(y, uv, self.yuv["standard"], self.yuv["full_range"], device=device, out=out, size=size,
-                                        resized_out=self._planes(resized) if resized is not None else None)
-        if self._act is not None:
-            return _lib.preprocess_u8_pitched(*self._cropped(buf), device=device, out=out)
-        return _lib.preprocess_u8(buf, device=device, out=out, size=size, resized_out=resized)
+        fmt, size = self.fmt, self._dst if self._resize else None
+        if size is not None and not fmt.fused_resize:
+            if resized is None:
+                resized = torch.empty(buf.shape[0], *fmt.byte_shape(*size), dtype=torch.uint8, device=device if device is not None else buf.device)
+            self._resize_planes(buf, resized, device)
+            buf, size = resized, None
+        planes = self._cropped(*fmt.planes(buf))
+        if not fmt.yuv:
+            # bgr24 has two entries: the dense one, which also resizes, and under an active rectangle the pitched one
+            if self._act is not None:
+                return _lib.preprocess_u8_pitched(*planes, device=device, out=out)
+            return _lib.preprocess_u8(buf, device=device, out=out, size=size, resized_out=resized)
+        # NV12's fused resize: the one 4:2:0 entry that takes a size
+        fused = {"size": size, "resized_out": fmt.planes(resized) if resized is not None else None} if size is not None else {}
+        entry, colour = self._yuv_entry("preprocess")
+        return entry(*planes, *colour, device=device, out=out, **fused)
 
     # ---- scene cuts (include/emavfi.h, "SCENE CUT DEFINITION"): signatures and flags on the pre lane, the hold on the post lane
     @staticmethod
@@ -987,7 +957,7 @@ class FrameInterpolator:
     def _scene_decide(self, slot, buf, ia, ib):
         """signatures of the staged frames `buf` (source size; NV12: the Y plane as a 1-channel image of pitch W), then every pair's flag and score"""
         n, sig = len(ia), slot["sig"][:buf.shape[0]]
-        img = self._planes(buf)[0].unsqueeze(-1) if self._yuv8 else buf
+        img = self.fmt.luma(buf)
         _lib.luma_signature_u8(img, out=sig, device=self.device)
         size = (img.shape[1], img.shape[2])
         a, b = self._run(sig, ia), self._run(sig, ib)
@@ -1014,7 +984,7 @@ class FrameInterpolator:
         if slot["sg"].shape[0] < n:     # mode "resample": a batch has as many node frames as its plan needs
             slot["sg"] = torch.zeros(n, dtype=torch.int32, device=self.device)
             slot["h_sg"] = torch.zeros(n, dtype=torch.int32).pin_memory()
-        layout, C, sb, depth, shift = _lib.static_frame_format(self.pixel_format)
+        layout, C, sb, depth, shift = self.fmt.frame_format
         _lib.static_guard_frames(dst[:n], srcs, table, self._dst, layout=layout, C=C, sample_bytes=sb, depth=depth, shift=shift,
                                  radius=self.static_guard, tol=self.static_tol, counts=slot["sg"][:n])
         slot["h_sg"][:n].copy_(slot["sg"][:n], non_blocking=True)
@@ -1022,44 +992,26 @@ class FrameInterpolator:
     def _resized_bytes(self, frame):
         """one source frame (numpy) at the destination size, as the device resizes it"""
         src = torch.from_numpy(frame).unsqueeze(0).to(self.device)
-        if self._planar:
-            out = torch.empty(1, self._dst[0] * 3 // 2, self._dst[1], dtype=torch.uint8, device=self.device)
-            self._resize_planar(src, out)
-            return out.cpu().numpy()[0]
-        if self.pixel_format == "nv12":
-            (H, W), (y, uv) = self._dst, self._planes(src)
-            out = torch.empty(1, H * 3 // 2, W, dtype=torch.uint8, device=self.device)
-            yo, uvo = self._planes(out)
-            _lib.resize_u8(y.unsqueeze(-1), (H, W), out=yo.unsqueeze(-1))
-            _lib.resize_u8(uv, (H // 2, W // 2), out=uvo)
-            return out.cpu().numpy()[0]
-        return _lib.resize_u8(src, self._dst).cpu().numpy()[0]
+        out = torch.empty(1, *self.fmt.byte_shape(*self._dst), dtype=torch.uint8, device=self.device)
+        self._resize_planes(src, out)
+        return out.cpu().numpy()[0]
 
     def _post_kernel(self, x, denormalize, out=None):
         """with an active rectangle in force `x` has its size and `out`, whole frames, is written inside it only"""
         if self._act is not None and out is None:
             raise ValueError("_post_kernel: with an active rectangle the frames to write into must be given")
-        if self._planar:
-            if out is None:
-                out = torch.empty(x.shape[0], x.shape[2] * 3 // 2, x.shape[3] * (2 if self._depth else 1), dtype=torch.uint8, device=x.device)
-            _lib.postprocess_yuv420p(x, self._depth or 8, self.yuv["standard"], self.yuv["full_range"], denormalize=denormalize,
-                                     out=self._cropped(*self._planes3(out)))
-            return out
-        if self._depth:
-            if out is None:
-                out = torch.empty(x.shape[0], x.shape[2] * 3 // 2, x.shape[3] * 2, dtype=torch.uint8, device=x.device)
-            _lib.postprocess_p010(x, self._depth, self.yuv["standard"], self.yuv["full_range"], denormalize=denormalize,
-                                  out=self._cropped(*self._planes16(out)))
-            return out
-        if self.pixel_format == "nv12":
-            if out is None:
-                out = torch.empty(x.shape[0], x.shape[2] * 3 // 2, x.shape[3], dtype=torch.uint8, device=x.device)
-            _lib.postprocess_nv12(x, self.yuv["standard"], self.yuv["full_range"], denormalize=denormalize, out=self._cropped(*self._planes(out)))
-            return out
-        if self._act is not None:
-            _lib.postprocess_u8_pitched(x, *self._cropped(out), denormalize=denormalize)
-            return out
-        return _lib.postprocess_u8(x, denormalize=denormalize, out=out)
+        fmt = self.fmt
+        if not fmt.yuv and self._act is None:     # bgr24 has two entries: this is the dense one, below the pitched one
+            return _lib.postprocess_u8(x, denormalize=denormalize, out=out)
+        if out is None:
+            out = torch.empty(x.shape[0], *fmt.byte_shape(x.shape[2], x.shape[3]), dtype=torch.uint8, device=x.device)
+        planes = self._cropped(*fmt.planes(out))
+        if fmt.yuv:
+            entry, colour = self._yuv_entry("postprocess")
+            entry(x, *colour, denormalize=denormalize, out=planes)
+        else:
+            _lib.postprocess_u8_pitched(x, *planes, denormalize=denormalize)
+        return out
 
     _pool = None
     _bound_pools = {}   # (node, cpus) -> a pool whose threads run on those CPUs only; the unbound pool above stays as it is
@@ -1266,24 +1218,7 @@ class FrameInterpolator:
             return torch.stack([m for m, _, _ in mids], dim=1)
 
     def _check_frames(self, frames, first, what):
-        if self._depth:
-            for f in frames.values():
-                if f.dtype != np.uint16 or f.ndim != 2 or f.shape != first.shape:
-                    raise ValueError(f"FrameInterpolator.{what}: same-shape uint16 [H*3/2, W] {self.pixel_format.upper()} frames expected")
-            if first.shape[0] % 3 or first.shape[1] % 2:
-                raise ValueError(f"FrameInterpolator.{what}: the packed {self.pixel_format.upper()} layout [H*3/2, W] needs even H and W")
-            return
-        if self._yuv8:
-            name = self.pixel_format.upper() if self._planar else "NV12"
-            for f in frames.values():
-                if f.dtype != np.uint8 or f.ndim != 2 or f.shape != first.shape:
-                    raise ValueError(f"FrameInterpolator.{what}: same-shape uint8 [H*3/2, W] {name} frames expected")
-            if first.shape[0] % 3 or first.shape[1] % 2:   # H = 2 * rows / 3 is then even
-                raise ValueError(f"FrameInterpolator.{what}: the packed {name} layout [H*3/2, W] needs even H and W")
-        else:
-            for f in frames.values():
-                if f.dtype != np.uint8 or f.ndim != 3 or f.shape != first.shape:
-                    raise ValueError(f"FrameInterpolator.{what}: same-shape uint8 HWC frames expected")
+        self.fmt.check_frames(frames.values(), first, f"FrameInterpolator.{what}")
 
     def run(self, frames, rank: int = 0, world: int = 1, *, _emit_tail: bool = True, _base: int = 0, _rect=None) -> Iterator[np.ndarray]:
         """Yields uint8 HWC frames (``pixel_format="nv12"``: uint8 [H*3/2, W] frames; ``"p010"`` / ``"p012"`` / ``"p016"``: uint16 [H*3/2, W]
@@ -1314,11 +1249,9 @@ class FrameInterpolator:
         frames = {i: np.ascontiguousarray(frames[i]) for i in range(lo, hi)}   # this rank's segment only
         first = frames[lo]
         self._check_frames(frames, first, "run")
-        if self._depth:
-            # from here on a frame is its bytes, [H*3/2, 2 W]; `words` turns what is yielded back into uint16 [H*3/2, W] (a view: no copy)
-            frames = {i: f.view(np.uint8) for i, f in frames.items()}
-            first = frames[lo]
-        words = (lambda v: v.view(np.uint16)) if self._depth else (lambda v: v)
+        # from here on a frame is its bytes (of words: [H*3/2, 2 W]); `words` turns what is yielded back into samples (views: no copy)
+        frames = {i: self.fmt.as_bytes(f) for i, f in frames.items()}
+        first, words = frames[lo], self.fmt.as_samples
         self._alloc(first.shape)
         self._reset_reports()
         self.prepass_waits = 0
@@ -1520,13 +1453,6 @@ class FrameInterpolator:
         taps = entry[0] if self.shutter is not None or self.light is not None else entry[:2]
         return [t & ~_lib.RESAMPLE_NODES for t in taps if t & _lib.RESAMPLE_NODES]
 
-    def _dedup_image(self, buf):
-        """the staged frames `buf` as the duplicate measure reads them, at source size: interleaved colour, or the Y plane as a 1-channel image
-        (bytes of pitch W, or the 16-bit words of the deeper formats)"""
-        if self._depth:
-            return buf[:, :buf.shape[1] * 2 // 3].view(torch.int16)
-        return self._planes(buf)[0].unsqueeze(-1) if self._yuv8 else buf
-
     def _prepass(self, frames, lo, hi, dedup, active):
         """The pre-pass of a run() whose plan depends on the frames - dedup_threshold (`dedup`), active_area="auto" (`active`) or both:
         frames lo .. hi (hi > lo) go to the device in slot-sized batches (consecutive batches share one frame), every consecutive pair is
@@ -1543,7 +1469,7 @@ class FrameInterpolator:
                              "h_fs": torch.zeros(2, size, dtype=torch.int32).pin_memory(),
                              "ab": torch.zeros(size + 1, 4, dtype=torch.int32, device=self.device),
                              "h_ab": torch.zeros(size + 1, 4, dtype=torch.int32).pin_memory(), "ready": torch.cuda.Event()}
-        _, depth, shift = _lib.resample_sample_format(self.pixel_format)
+        _, depth, shift = self.fmt.sample_format
         self._pre.wait_stream(torch.cuda.current_stream(self.device))     # buffers made on the caller's stream are used on the pre lane
         for bi, f0 in enumerate(range(lo, hi, cap - 1)):
             f1 = min(f0 + cap - 1, hi)
@@ -1551,7 +1477,7 @@ class FrameInterpolator:
             self._stage(slot, frames, [tuple(range(f0, f1 + 1))])           # waits until the slot's previous upload has been read
             with torch.cuda.stream(self._pre):
                 self._lane_in(slot, nfr)
-                img = self._dedup_image(slot["d_in"][:nfr])
+                img = self.fmt.luma(slot["d_in"][:nfr])    # as staged, at source size
                 if dedup:
                     cells = _lib.frame_diff_cells(img[:-1], img[1:], depth=depth, shift=shift, out=dd["cells"][:nfr - 1])
                     _lib.duplicate_flags(cells, self.dedup, flags=dd["fs"][0, f0 - lo:f1 - lo], scores=dd["fs"][1, f0 - lo:f1 - lo])
@@ -1593,10 +1519,8 @@ class FrameInterpolator:
         frames = {i: np.ascontiguousarray(frames[i]) for i in sorted(set(range(a, b + 1) if b > a else ()) | ({last} if tail else set()))}
         first = next(iter(frames.values()))
         self._check_frames(frames, first, "run")
-        if self._depth:
-            frames = {i: f.view(np.uint8) for i, f in frames.items()}
-            first = next(iter(frames.values()))
-        words = (lambda v: v.view(np.uint16)) if self._depth else (lambda v: v)
+        frames = {i: self.fmt.as_bytes(f) for i, f in frames.items()}
+        first, words = next(iter(frames.values())), self.fmt.as_samples
         self._alloc(first.shape)
         self._reset_reports()
         kept = list(range(a, b + 1)) if b > a else []
@@ -1620,7 +1544,7 @@ class FrameInterpolator:
                             self.resample_gap(P, Q, D, self.resample_method, base + t0, base + t1)] for t0, t1 in gaps}
         bp = self.batch_pairs
         chunks = [gaps[i:i + bp] for i in range(0, len(gaps), bp)]
-        fmt = _lib.resample_sample_format(self.pixel_format)
+        fmt = self.fmt.sample_format
         if chunks:
             # the node and emission buffers of a slot hold the largest batch of this run
             sizes = [(sum(len(outs_of[s]) for s, _ in c), sum(len(lv) for s, s2 in c for lv in self.resample_needed(
@@ -1675,7 +1599,7 @@ class FrameInterpolator:
             if self.light is not None:       # in light: the whole bgr24 frame, the Y plane (the first two thirds) of a 4:2:0 frame
                 fb = slot["d_emit"][0].numel()
                 assemble = functools.partial(_lib.accumulate_frames_linear, lin=self._lin,
-                                             linear_bytes=fb if self.pixel_format == "bgr24" else fb * 2 // 3)
+                                             linear_bytes=self.fmt.luma_bytes(fb))
             assemble(slot["d_emit"][:len(table)], rs if rs is not None else slot["d_in"][:nup], slot["d_node"][:off] if off else None, table,
                      flags=slot["fs"][0] if self.scene is not None else None, sample_bytes=fmt[0], depth=fmt[1], shift=fmt[2])
             slot["h_emit"][:len(table)].copy_(slot["d_emit"][:len(table)], non_blocking=True)         # HBM -> pinned (SDMA)
@@ -1787,8 +1711,8 @@ class FrameInterpolator:
 
         ``frames`` / ``rank`` / ``world`` as for ``run()``: a rank touches only the frames of its contiguous share of the targets, and
         the ranks' ``targets`` concatenated in rank order are the single-process result."""
-        if self._depth:
-            raise ValueError(f"evaluate() with pixel_format={self.pixel_format!r}: the metric kernel reads bytes (16-bit frames are not scored)")
+        if not self.fmt.byte_kernels:
+            raise ValueError(f"evaluate() with pixel_format={self.fmt.name!r}: the metric kernel reads bytes (16-bit frames are not scored)")
         if self.active is not None:
             raise ValueError("evaluate() with active_area: a held-out frame is scored whole, and the bars would score as perfect (use a "
                              "harness without it)")
@@ -1798,20 +1722,16 @@ class FrameInterpolator:
             frames = list(frames)
         plan = self.evaluation_plan(len(frames), every, rank, world)
         if not plan:                               # fewer than three frames, or a rank without a share: nothing is touched, size (0, 0)
-            return Evaluation((0, 0), 1 if self._yuv8 else 3)
+            return Evaluation((0, 0), 1 if self.fmt.yuv else 3)
         frames = {i: np.ascontiguousarray(frames[i]) for i in sorted({f for item in plan for f in item})}   # this rank's frames only
         first = frames[plan[0][1]]
         self._check_frames(frames, first, "evaluate")
         self._alloc(first.shape, per=3)
-        nv12 = self._yuv8                         # the Y plane is the first H rows of NV12 and of planar frames alike
         H, W = self._dst
-        result = Evaluation((H, W), 1 if nv12 else first.shape[2])
+        result = Evaluation((H, W), 1 if self.fmt.yuv else first.shape[2])
+        image = self.fmt.luma                     # the scored image of frames at the size the model runs at: of 4:2:0 frames the Y plane as one channel
         bp = self.batch_pairs
         chunks = [[(a, t, b) for t, a, b in plan[i:i + bp]] for i in range(0, len(plan), bp)]
-
-        def image(buf):
-            """the scored image of frames at the size the model runs at: the Y plane of NV12 frames as one channel"""
-            return buf[:, :H].unsqueeze(-1) if nv12 else buf
 
         def pre(b):
             slot, nup = b.slot, b.nup

@@ -21,6 +21,8 @@ from typing import Iterator, NamedTuple, Optional, Tuple
 
 import numpy as np
 
+from . import formats
+
 MAGIC = b"YUV4MPEG2"
 # colour-space tag -> bits per sample.  The 8-bit tags differ in chroma siting only, which is carried through to the output header: the
 # project's colour definition has one siting (include/emavfi.h)
@@ -41,13 +43,18 @@ class Y4MHeader(NamedTuple):
     extensions: Tuple[str, ...] = ()
 
     @property
+    def format(self) -> formats.PixelFormat:
+        """the record of the planar format this stream's frames have"""
+        return formats.lookup(f"yuv420p{DEPTH_OF_TAG[self.colorspace]}")
+
+    @property
     def depth(self) -> int:
-        return DEPTH_OF_TAG[self.colorspace]
+        return self.format.depth
 
     @property
     def pixel_format(self) -> str:
         """the ``FrameInterpolator`` pixel format of this stream's frames"""
-        return f"yuv420p{self.depth}"
+        return self.format.name
 
     @property
     def fps(self) -> float:
@@ -59,7 +66,7 @@ class Y4MHeader(NamedTuple):
 
     @property
     def dtype(self):
-        return np.dtype(np.uint8) if self.depth == 8 else np.dtype("<u2")
+        return np.dtype("<u2") if self.format.words else np.dtype(np.uint8)
 
     @property
     def frame_bytes(self) -> int:
