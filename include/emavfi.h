@@ -86,12 +86,26 @@ extern "C" {
  * EMAVFI_F16 stays the FAST half-precision mode (DCN contraction and blend in fp16 too). */
 #define EMAVFI_AMP16 3
 /* fp32-ACCURATE contractions on the 16-bit matrix pipe (round 6; gfx950 has no TF32 and its fp32 MFMA runs at 1/16 of the f16 rate):
- * every nn.Conv2d / nn.Linear computes x_hi w_hi + x_hi w_lo + x_lo w_hi with x = x_hi + x_lo, w = w_hi + w_lo in IEEE f16 (22
- * significant bits of each operand; the products are exact in fp32, accumulation in fp32, biases and activations in fp32), activations
- * between the layers are stored as the two f16 halves of the fp32 value; flow, warp, sampling geometry, the pooled context and the three
- * deform_conv2d are the EXACT fp32 ones of EMAVFI_F32.  Passes the fp32 mode's parity gates (<= 1e-3 on the frame, <= 5e-4 relative on
- * every stage) on every reference-run fixture; a SEPARATELY NAMED mode: EMAVFI_F32 stays the exact-fp32 parity mode.  Needs |activation|
- * < 65504; the low half underflows below 6e-5 (an absolute 6e-8 per product).  Stage entries: emavfi_conv3x3 only. */
+ * every nn.Conv2d computes x_hi w_hi + x_hi w_lo + x_lo w_hi with x = x_hi + x_lo, w = w_hi + w_lo in IEEE f16 (up to 22 significant
+ * bits of each operand, see below; the products are exact in fp32, accumulation in fp32, biases and activations in fp32), activations
+ * between the layers are stored as the two f16 halves of the fp32 value; the nn.Linear of context_encoding and the context half of
+ * motion_estimation.0 (a per-border-class bias) are fp32 FMA chains on the fp32 weights; flow, warp, the pooled context and the sampling
+ * geometry (positions, corner weights, blend) of the three deform_conv2d are the fp32 ones of EMAVFI_F32.  The deform_conv2d
+ * CONTRACTION: at mid_channels + 3 = 65..68 (mid_channels 64: the LDS-window kernel, deform_f32w.inl) it is the same three-term f16
+ * split as EMAVFI_AMP16's (above) - in the launch list "fp32 sampling, three-term f16 split contraction" -; at every other width the
+ * generic fp32 kernel runs and it is exact fp32.  Passes the fp32 mode's parity gates (<= 1e-3 on the frame, <= 5e-4 relative on every
+ * stage) on every reference-run fixture; a SEPARATELY NAMED mode: EMAVFI_F32 stays the exact-fp32 parity mode.
+ * ACCURACY AS A FUNCTION OF MAGNITUDE (derived, and checked per element: tests/rounding_model.py, conv_model_x3 / accuracy_bound_x3;
+ * tests/test_gpu_fp32x3_rounding_model.py).  An operand v is carried as hi = f16(v), lo = f16(v - hi).  While lo is a NORMAL f16
+ * number (|lo| >= 2^-14 = 6.1e-5; |lo| <= 2^-11 |v|, so every |v| < 2^-3 has a subnormal lo) hi + lo is v to 2^-22 |v|: 22 bits.  A
+ * subnormal lo is a multiple of 2^-24: hi + lo is v to 2^-25 = 3e-8 ABSOLUTELY, i.e. 2^-25 (|w| + |x|) per product - Kaiming-scale
+ * weights of 0.02 are carried to about 19 bits, an operand of 1e-3 to 15.  Per output element, against the float64 convolution of
+ * the unsplit operands: <= 3 * 2^-22 sum|w x| + 2^-25 (sum|w| + sum|x|) over the receptive field, plus the fp32 accumulation of the
+ * 27 Cin + 1 terms and the output's own split.
+ * RANGE: every |input| and |activation| must stay <= 65504 (the largest f16 number).  An accumulator v of magnitude 65520 or more
+ * (what rounds to infinity in f16) stores hi = +-inf with the sign of v and lo = v - hi = -+inf with the opposite one (v >= 65520:
+ * hi = inf, lo = -inf; v <= -65520: hi = -inf, lo = inf): that ONE element is non-finite (NaN once hi + lo is formed) and poisons
+ * what reads it; no other element is affected and no address depends on a value.  Stage entries: emavfi_conv3x3 only. */
 #define EMAVFI_F32X3 4
 
 #define EMAVFI_OK 0

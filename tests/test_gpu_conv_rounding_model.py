@@ -25,18 +25,22 @@ Kernels that exist only inside a stage or the forward - conv_first.inl, conv_rin
 tail conv_ring_tail.inl (lib.reconstruct), conv_wreg's fused tile-sum pool (lib.context), the fused flow head of conv_ring.inl (the `flow`
 tap) - are gated LAYER BY LAYER: the same layers are run one at a time through lib.conv3x3, every one against the single-layer model on
 the GPU's own previous output, and the stage's result is then held to the single-layer model of its LAST layer on the GPU's own
-intermediate (see layered_chain)."""
+intermediate (see layered_chain).
+
+The three-term f16 split mode (`fp32x3`: the tile kernel on three virtual chunks per real one, [hi | lo] activations) has its own
+model and gates: rounding_model.conv_model_x3, tests/test_gpu_fp32x3_rounding_model.py.  TILE_SHAPES, the layout switches and set_env
+are shared with that file through tests/conv_cases.py."""
 import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_cases import ALL_SWITCHES, TILE_SHAPES, set_env   # noqa: F401  (ALL_SWITCHES: tests/test_gpu_workspace.py and test_gpu_graph_replay.py take it from here)
 from emavfi import EMA_VFI, lib, synth
 from rounding_model import (MISMATCH_CAP, U32, chain_bound, conv_model, quantum, conv_weights, exact_match_share, impulse_case, scaled_input, storage_round)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ACT = {"none": lib.ACT_NONE, "relu": lib.ACT_RELU, "tanh01": lib.ACT_TANH01}
-ALL_SWITCHES = ("EMAVFI_CONV_MFMA16", "EMAVFI_CONV_RING", "EMAVFI_CONV_S2RING", "EMAVFI_CONV_WREG")
 
 
 def family_of(cin, cout, stride, dtype, env, act="none"):
@@ -67,7 +71,6 @@ def family_of(cin, cout, stride, dtype, env, act="none"):
 
 RING_SHAPES = [(1, 61), (2, 62), (3, 63), (17, 124), (17, 125)]   # widths around the 62-column strip pitch; heights 1, 2, 3, 17
 RING_SHAPES_B = [(1, 125), (2, 124), (3, 61), (17, 62), (17, 63)]   # the same widths and heights paired the other way round
-TILE_SHAPES = [(1, 1), (1, 70), (70, 1), (5, 7), (33, 47)]                                                           # tile remainders in both directions
 P16_SHAPES = [(16, 32), (17, 33), (75, 131)]
 NO_RING = {"EMAVFI_CONV_RING": "0"}
 OLD32 = {"EMAVFI_CONV_MFMA16": "0"}
@@ -96,13 +99,6 @@ FAMILIES = {
                                 ({}, 192, 250, 1, [(1, 5), (19, 67)], ("none", "relu")), ({}, 160, 256, 2, [(1, 33), (19, 67)], ("none", "relu"))]),
     "light": (("bf16", "fp16"), [({}, 32, 3, 1, [(1, 7), (21, 45), (75, 131)], ("tanh01",))]),
 }
-
-
-def set_env(monkeypatch, env):
-    for name in ALL_SWITCHES:
-        monkeypatch.delenv(name, raising=False)
-    for name, value in env.items():
-        monkeypatch.setenv(name, value)
 
 
 def expect_family(family, cin, cout, stride, dtype, env, act):

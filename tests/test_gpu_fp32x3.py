@@ -1,6 +1,7 @@
 """EMAVFI_F32X3 (round 6): fp32-ACCURATE contractions on the f16 matrix pipe - every nn.Conv2d / nn.Linear as the
 three-term split x_hi w_hi + x_hi w_lo + x_lo w_hi (IEEE f16 halves, exact products, fp32 accumulation), activations stored as their
-two f16 halves, the warp / sampling geometry / pool and the three deform_conv2d the EXACT fp32 ones - held to THE SAME GATES as the exact
+two f16 halves, the warp / pool and the sampling geometry of the three deform_conv2d the fp32 ones (their contraction: the same split at
+the reference width, exact fp32 elsewhere; gated per element in tests/test_gpu_fp32x3_rounding_model.py) - held to THE SAME GATES as the exact
 fp32 mode on every reference-run fixture: <= 1e-3 max-abs on the frame (BASELINE.json), <= 5e-4 relative on every stage.  It is a
 separately named mode: `fp32` stays the parity mode everywhere else.  Reference: ema_vfi.py:7-14 (conv / conv_block), :110-147."""
 import pytest

@@ -224,7 +224,7 @@ struct ConvParams {
     // chunks; x3_lo_off / out_lo_off = element offset of the lo half inside an input / output pixel; in_ps / out_ps are whole-pixel strides.
     int x3, x3_lo_off, out_lo_off;
     float *out32;   // x3 only: ALSO store the fp32 value, channels-last with pixel stride out32_ps (the last feature layer writes `feat` into the
-    int out32_ps;   // fp32 fusion tensor the exact DCN reads: saves the widening pass' read of 1.9 GB at B = 8 x 720p)
+    int out32_ps;   // fp32 fusion tensor the DCN samples in fp32: saves the widening pass' read of 1.9 GB at B = 8 x 720p)
 };
 static_assert(offsetof(ConvParams, w2) == 128 && sizeof(ConvParams) == 232, "a field that moves changes every convolution kernel's code object");
 

@@ -235,7 +235,7 @@ struct Plan {
                                // motion_estimation.0) run the f16 ring kernels on bf16-rounded weights and hand bf16 on
     int in_ch, mid, nb, dtype, esize;  // dtype = the KERNEL storage type (EMAVFI_AMP16 runs the f16 kernels)
     bool amp;                          // EMAVFI_AMP16: autocast op policy (fp32 DCN on an fp32 fusion tensor, fp16 roundings)
-    bool x3;                           // EMAVFI_F32X3: fp32-accurate three-term f16 split in every convolution, exact fp32 DCN; the data flow of
+    bool x3;                           // EMAVFI_F32X3: fp32-accurate three-term f16 split in every convolution, fp32 DCN (its contraction on the split too where dcn32[i].x3); the data flow of
                                        // the autocast mode (an fp32 fusion tensor beside the 16-bit one) without any of its roundings
     bool wide() const { return amp || x3; }   // the fusion tensor also exists in fp32 (what the fp32 DCN reads and writes)
     Layer dcn32[kMaxBlocks];           // amp: the deformable convolutions' fp32 master weights
@@ -718,7 +718,7 @@ int attention_block_amp(const Plan &P, int i, const void *packed, const void *x1
     EMAVFI_STEP(rec, conv_name(P, P.off[i]) + " offset_conv", fl, by, run_conv(P, P.off[i], packed, B, s, ConvCall{}.from(x16, P.fps, H, W).to(om, 32, 32).act(EPI_OM)));
     // (want16, not the pointer, decides: the enumeration-only pass has no buffers and must list the launches the real pass runs)
     const bool both = amp_dcn_writes_fp16(P, i) && want16;
-    EMAVFI_STEP(rec, both ? (P.x3 ? "deform<f32,ck=80,nf=3> dcn_v2 (exact fp32; writes fp32 + its f16 hi / lo halves)" : "deform<f32,ck=80,nf=3> dcn_v2 (fp32 under autocast; writes fp32 + its fp16 rounding)")
+    EMAVFI_STEP(rec, both ? (P.x3 ? "deform<f32,ck=80,nf=3> dcn_v2 (fp32 sampling, three-term f16 split contraction; writes fp32 + its f16 hi / lo halves)" : "deform<f32,ck=80,nf=3> dcn_v2 (fp32 under autocast; writes fp32 + its fp16 rounding)")
                           : "deform<f32,ck=80,nf=3> dcn_v2 (fp32 under autocast)",
                 2.0 * 9.0 * cf * cf * px, px * (2.0 * cf * 4.0 + 27.0 * 4.0 + (both ? cf * 2.0 * (P.x3 ? 2 : 1) : 0.0)) + 9.0 * cf * cf * 4.0,
                 run_deform(P, P.dcn32[i], packed, B, s, DeformCall{}.from(xF, P.fpad, H, W, om).to(yF, P.fpad)
@@ -937,7 +937,7 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
                                                                 .to(dst, last ? P.fps : P.p_mid, P.p_mid).other16(last && feat16)));
             i = j;
         } else {
-            // (EMAVFI_F32X3: the last block also writes `feat` in fp32 into the fusion tensor the exact DCN reads)
+            // (EMAVFI_F32X3: the last block also writes `feat` in fp32 into the fusion tensor the fp32 DCN reads)
             EMAVFI_STEP(rec, conv_name(P, P.blk[i]) + " feat_ext_blocks", fl, by + (last && P.x3 ? px * mid * 4.0 : 0.0),
                         run_conv(P, P.blk[i], packed, B, s, ConvCall{}.from(cur, P.p_mid, H, W).to(dst, last ? P.fps : P.p_mid, P.p_mid).act(EPI_RELU)
                                                                 .other16(last && feat16).to_f32(last && P.x3 ? f.fuF0 : nullptr, P.fpad)));
@@ -990,7 +990,7 @@ int forward_impl(int in_channels, int mid_channels, int num_blocks, const void *
 
     void *x = f.fu0, *y = f.fu1;
     if (P.wide()) {
-        // --- EMAVFI_F32X3 takes the same data flow without any rounding: the fp32 fusion tensor is what the exact fp32 DCN reads and
+        // --- EMAVFI_F32X3 takes the same data flow without any rounding: the fp32 fusion tensor is what the fp32 DCN reads and
         // writes, its [hi | lo] f16 halves (22 bits) are what the split convolutions read.
         // --- EMAVFI_AMP16: the autocast op policy for ema_vfi.py:130-138.  grid_sample runs in fp32 on the fp16-valued
         // flow and cat(feat, warped) promotes to fp32, so the fusion tensor exists twice: fp32 (fuF: what the fp32
@@ -2623,7 +2623,7 @@ int emavfi_deform_conv2d(const float *x, const float *offset, const float *mask,
 // mid_channels + 3 channels (ema_vfi.py:97).
 static int mdcn_plan(Plan &P, int C, int dtype, int flags, bool &split, int &in_f16, int &out_f16)
 {
-    if (dtype == EMAVFI_F32X3) return fail(EMAVFI_E_UNSUPPORTED, "mdcn: EMAVFI_F32X3 has no stage entry of its own (its DCN is the exact fp32 one: use EMAVFI_F32)");
+    if (dtype == EMAVFI_F32X3) return fail(EMAVFI_E_UNSUPPORTED, "mdcn: EMAVFI_F32X3 has no stage entry of its own (its DCN samples in fp32 and, at the reference width, contracts on the three-term f16 split, as EMAVFI_AMP16's does; EMAVFI_F32 is the exact fp32 pack)");
     if (C < 11 || !build_plan(P, 3, C - 3, 1, dtype))
         return fail(EMAVFI_E_UNSUPPORTED, "mdcn: C = %d is not mid_channels + 3 of a supported model (%s)", C, C < 11 ? "C < 11" : P.why);
     if (flags & ~(EMAVFI_MDCN_IN_F16 | EMAVFI_MDCN_OUT_F16 | EMAVFI_MDCN_SPLIT_TAIL)) return fail(EMAVFI_E_ARG, "mdcn: unknown flag bits 0x%x", flags);

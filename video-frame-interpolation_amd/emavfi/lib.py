@@ -23,7 +23,7 @@ DTYPES = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF1
           "fp16": F16, "f16": F16, "float16": F16, "half": F16,
           # the reference's forward under torch.cuda.amp.autocast(), op policy restated (include/emavfi.h, EMAVFI_AMP16)
           "amp16": AMP16, "autocast": AMP16, "autocast16": AMP16,
-          # fp32-accurate three-term f16 split on the 16-bit matrix pipe, exact fp32 DCN (include/emavfi.h, EMAVFI_F32X3)
+          # fp32-accurate three-term f16 split on the 16-bit matrix pipe; fp32 DCN sampling, its contraction on the split at the reference width (include/emavfi.h, EMAVFI_F32X3)
           "fp32x3": F32X3, "f32x3": F32X3}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
