@@ -382,9 +382,9 @@ def test_feat_of_the_forward_layer_by_layer(shape, dtype, kind, monkeypatch):
 def test_flow_from_the_forwards_own_taps(shape, dtype, switch, monkeypatch):
     """`flow` from the GPU's own `feat` and `ctx` taps: motion_estimation.0 (the ring kernel on `feat`, the context half folded into a
     per-border-class bias table in fp32) -> .1 -> .2, with the head fused into .1's launch (conv_ring.inl, HEAD) and as its own launch
-    (SW_NO_HEAD: conv_light_kernel's 64-channel form).  Neither .0's nor .1's output is visible from outside, and .0's fp32 bias table
-    cannot be handed to the single-layer entry, so NO layer-by-layer gate is possible here: the flow is held to chain_bound over the
-    three layers - .0 as a 128-channel layer whose context half is the fp32 ctx broadcast over the image (zero-padded like any input:
+    (SW_NO_HEAD: conv_light_kernel's 64-channel form).  Neither .0's nor .1's output is a tap, and .0's fp32 bias table cannot be
+    handed to the single-layer entry; the layer-by-layer gates of this stage are tests/test_gpu_motion_layers.py, which brings both
+    outputs out through exact pass-through weights.  HERE the flow of the real weights is held to chain_bound over the three layers - .0 as a 128-channel layer whose context half is the fp32 ctx broadcast over the image (zero-padded like any input:
     the border classes), counted with rounded products (2 n) because ctx is fp32; .0 and .1 rounded to the storage type after the
     ReLU, the head fp32.  Rigorous and COARSE (two rounded intermediates: the bound is some 1e-1 of |flow|); the tight statement
     about the fused head is its comparison with the two-launch path in tests/test_gpu_parity.py (2e-5).  measured: see MEASURED."""

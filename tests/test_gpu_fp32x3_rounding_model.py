@@ -243,8 +243,9 @@ def test_ctx_of_the_forward_from_its_feat_tap(case):
 @pytest.mark.parametrize("case", FORWARD_CASES[:-1], ids=case_id)
 def test_flow_of_the_forward_from_its_feat_and_ctx_taps(case):
     """motion_estimation.0 (the split convolution on `feat`; the context half folded into an fp32 per-border-class bias table:
-    ctx_finish_kernel, fp32 FMAs on the fp32 weights) -> .1 -> .2 (planar fp32).  Neither intermediate is visible and the bias table
-    cannot be handed to the stage entry, so the flow is held to chain_stats_x3 over the three layers: its rigorous chain bound, as
+    ctx_finish_kernel, fp32 FMAs on the fp32 weights) -> .1 -> .2 (planar fp32).  Neither intermediate is a tap and the bias table
+    cannot be handed to the stage entry; the layer-by-layer gates of this stage are tests/test_gpu_motion_layers.py (exact pass-through
+    weights bring both intermediates out).  Here the flow of the real weights is held to chain_stats_x3 over the three layers: its rigorous chain bound, as
     tests/test_gpu_conv_rounding_model.py does for the 16-bit modes (as coarse as there: worst cases multiplied through three layers),
     AND the z gates on the chain's standard deviation (some 1e-6 px), which is what a lost low half in .0 or .1 - 2^-12 of a layer's
     terms, 1e-4 px - cannot pass.  The context half: float64 convolution of ctx broadcast over the image (zero padded: the border
